@@ -16,6 +16,14 @@ PyTorch is used for device memory, the stream, the barrier and torch.distributed
 everything numeric is the HIP library behind include/htk_amd.h.
 
 One JSON line is printed by rank 0 (see README / DESIGN.md for the fields).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit, higher_is_better, dtype, ms_per_step,
+the configuration).  `--full` adds everything else the line used to carry, each part measured after the timed region: the split of an
+iteration's wall clock, one un-chunked pass alone (per-kernel times, roofline), the fp16 x 2 side run, the oracle check and the CPU
+baselines, the other consumers of the path (alignment, decoding, MFCC, the 10k-utterance job, the shim).
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR     # + what the last timed step computed, DIR/<name>.npy
 """
 from __future__ import annotations
 
@@ -381,6 +389,40 @@ def host_cores() -> int:
     return max(1, n)
 
 
+DUMP_SEED = 20240611                                     # --dump-outputs: the seed of the fixed samples of arrays over their cap
+
+
+def dump_outputs(d, last, params, acc):
+    """--dump-outputs DIR: what a caller of the timed path receives from its LAST step, as DIR/<name>.npy in float32 / float64 -- the
+    per-utterance log-probabilities and status (htkamd_fb_results), the model the step's update wrote (htkamd_model_get_params) and the
+    step's summed statistics (the totals whole, the accumulator vector as a sample).  An array over its cap is written as a fixed seeded
+    sample of its rows, with the rows' indices beside it as <name>_rows.npy; the caps (56 MB together) keep the whole under 64 MB."""
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(DUMP_SEED)
+    MB = 1 << 20
+    pr, st = last
+    arrays = []                                          # (name, array, cap in bytes)
+    if pr is not None:
+        arrays += [("utt_logprob", np.asarray(pr, np.float64), 2 * MB), ("utt_status", np.asarray(st, np.float32), 1 * MB)]
+    arrays += [("mean", params["mean"], 20 * MB), ("var", params["var"], 20 * MB), ("gconst", params["gconst"], 2 * MB),
+               ("comp_weight", params["compWeight"], 2 * MB), ("trans_p", params["transP"], 4 * MB),
+               ("acc_totals", np.array([acc[k] for k in ("totalPr", "totalT", "nUttDone", "nUttSkipped", "nEval")], np.float64), MB),
+               ("acc_vector", np.asarray(acc["vec"], np.float64), 4 * MB)]
+    total = 0
+    for name, x, cap in arrays:
+        x = np.ascontiguousarray(x)
+        assert x.dtype in (np.float32, np.float64), (name, x.dtype)
+        if x.nbytes > cap:
+            row_bytes = x.nbytes // max(x.shape[0], 1)
+            rows = np.sort(rng.choice(x.shape[0], size=max(1, cap // (row_bytes + 8)), replace=False))      # (the indices count against the cap)
+            x = x[rows]
+            np.save(os.path.join(d, name + "_rows.npy"), rows.astype(np.float64))
+            total += rows.size * 8
+        np.save(os.path.join(d, name + ".npy"), x)
+        total += x.nbytes
+    assert total <= 64 * MB, total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -399,14 +441,20 @@ def main():
                     help="arithmetic: exact = bit-identical to the reference; mfma = fp32 matrix-core scores; fast = mfma + fp32-transcendental LAdd in the recursions; "
                          "bf16 (default: every asserted parity figure at half the 1e-4 bar or better) = bf16 x 3 matrix-core scores + that LAdd; "
                          "fastest = fp16 x 2 matrix-core scores + that LAdd (the parity figures reach 0.6 - 1.0 of the bar depending on the sample)")
-    ap.add_argument("--also-fastest", type=int, default=1, help="1: after the measurement (N = 1, --score bf16) the same timed iterations once more with the fp16 x 2 scores, reported as `fastest_mode` beside the line, never as `value`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, everything beyond the headline figure: wall-clock split, kernels alone and roofline, "
+                         "--also-fastest, --cpu-seconds, --extras (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy (float32 / float64): per-utterance log-probabilities and "
+                         "status, the re-estimated model, a fixed seeded sample of the accumulator vector and its totals")
+    ap.add_argument("--also-fastest", type=int, default=1, help="--full, 1: after the measurement (N = 1, --score bf16) the same timed iterations once more with the fp16 x 2 scores, reported as `fastest_mode` beside the line, never as `value`")
     ap.add_argument("--two-streams", type=int, default=1, help="run the chunks of an iteration on two alternating streams (1) or on one stream (0)")
     ap.add_argument("--chunks", type=int, default=1, help="sub-batches an iteration's shard is cut into (alternating over two streams, one accumulator vector)")
     ap.add_argument("--min-var", type=float, default=0.01, help="HERest -v: variance floor of the update (the shard has ~8 frames per Gaussian)")
     ap.add_argument("--prewarm-seconds", type=float, default=2.0, help="wall time of untimed EM iterations before the warm-up steps (a freshly started box is slow for its first seconds)")
     ap.add_argument("--cpu-workers", type=int, default=0, help="processes of the reference CPU baseline (0 = one per physical host core)")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline leg (0 = skip)")
-    ap.add_argument("--extras", type=int, default=1, help="1: also time forced alignment and network decoding at the same set after the timed region (N = 1 only; reported as other_paths)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: budget of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--extras", type=int, default=1, help="--full, 1: also time forced alignment and network decoding at the same set after the timed region (N = 1 only; reported as other_paths)")
     ap.add_argument("--exchange-slices", type=int, default=4,
                     help="N > 1 only: the accumulator exchange of an iteration in this many parts by tied state -- a part travels (on a stream of its own) while the next "
                          "range of states' mixture statistics is still being summed (htkamd_fb_execute_begin / _mix); 1: one all-reduce behind the pass")
@@ -414,6 +462,8 @@ def main():
                     help="N > 1: the accumulator statistics on the wire as fp32 (every rank rounds its fp64 partial sums once; counters stay fp64) or fp64")
     ap.add_argument("--dump-model", default=None, help="rank 0 writes the model of the last iteration (npz: mean, var, compWeight, transP) -- the multi-GPU tests compare it over rank counts")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks here, as CHILDREN under torch.distributed.run, before this process has
@@ -626,7 +676,7 @@ def main():
                 print("bench: %s -- the run goes on with --score bf16" % e, file=sys.stderr)
                 cfg.scoreMode = (cfg.scoreMode & ~capi.SCORE_F16) | capi.SCORE_BF16
                 args.score = "bf16"
-    a_init = accs.download()
+    a_init = accs.download() if args.full else None                            # (the initial model's average log-probability: --full)
     units_local = sum(ch["fbs"][0].frame_states() for ch in chunks)           # (frame, chain state) evaluations of this rank's shard
 
     def any_rank(flag: bool) -> bool:
@@ -696,7 +746,7 @@ def main():
         for i in range(args.warmup):
             em_iteration(False)
         ktimes = np.zeros(5)
-        st_upd = None
+        st_upd = pr = st = None
         gc.collect(); gc.disable()                           # (no collector pause inside the few milliseconds that are timed; on again behind them)
         sync_all()
         t0 = time.perf_counter()
@@ -739,7 +789,7 @@ def main():
             tmax = torch.tensor([dt], dtype=torch.float64, device=acc_t.device)
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
             dt = float(tmax.item())
-        return dt, ktimes, st_upd
+        return dt, ktimes, st_upd, (pr, st)
 
     # a box that has just been started runs its first iterations slower (2.4 ms against 2.1 a few seconds later on the same box: clocks,
     # first touches): untimed iterations for a fixed wall time before the W warm-up steps and the K timed ones the contract asks for.
@@ -752,7 +802,7 @@ def main():
         model.set_params(mean=pk["mean"], var=pk["var"], compWeight=pk["compWeight"], transP=pk["transP"])
         for ch in chunks:
             ch["ready"] = [False, False]
-    dt, ktimes, st_upd = measure()
+    dt, ktimes, st_upd, last = measure()
     if any_rank(range_hit[0]) and (cfg.scoreMode & capi.SCORE_F16):
         # the range check tripped on a model the iterations themselves produced: initial parameters again, bf16 x 3 scores, the whole
         # measurement again (a pass whose scores overflowed has spoilt the model it fed)
@@ -761,37 +811,40 @@ def main():
         for ch in chunks:
             ch["ready"] = [False, False]
         range_hit[0] = False
-        dt, ktimes, st_upd = measure()
+        dt, ktimes, st_upd, last = measure()
         assert not any_rank(range_hit[0])
     ktimes /= max(args.steps, 1)
     a = accs.download()                                                        # the last iteration's summed statistics
-    p_dump = model.get_params() if (args.dump_model and rank == 0) else None      # the model of the MEASURED iterations (the split iterations and the side run below move it)
-    for i in range(3):                                                         # the split of an iteration's wall clock, outside the timed region
-        em_iteration(False, parts=t_parts)
-    t_parts /= 3.0
+    p_dump = model.get_params() if ((args.dump_model or args.dump_outputs) and rank == 0) else None      # the model of the MEASURED iterations (the split iterations and the side run below move it)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, p_dump, a)
+    if args.full:
+        for i in range(3):                                                     # the split of an iteration's wall clock, outside the timed region
+            em_iteration(False, parts=t_parts)
+        t_parts /= 3.0
 
-    # one un-chunked pass ALONE (outside the timed region): the kernels' own durations, the latency of a single pass
-    fb1 = capi.ForwardBackward(model)
-    frameOff = frame_off_all.astype(np.int32)
-    labOff = np.concatenate([[0], np.cumsum([len(q) for q in s.seqs])]).astype(np.int32)
-    labs = np.concatenate(s.seqs).astype(np.int32)
-    acc1 = capi.Accs(model)
-    lat = []
-    for rep in range(3):
-        torch.cuda.synchronize(); tl = time.perf_counter()
-        acc1.zero(sptr); fb1.prepare(dX.data_ptr(), frameOff, labOff, labs, sptr); fb1.execute(cfg, acc1, sptr); fb1.results(sptr)
-        lat.append(time.perf_counter() - tl)
-    ktimes_solo = np.array(fb1.kernel_times5())
-    torch.cuda.synchronize()
-    kernel_ms_source = {"score": "the dispatch's own start / stop, every timed iteration"}
-    for i_, n_ in ((1, "beta"), (2, "alpha"), (3, "stats"), (4, "mix_stats")):
-        if ktimes[i_] < 0:                                                     # not recorded in the timed iterations (set_events(1))
-            ktimes[i_] = ktimes_solo[i_]
-            kernel_ms_source[n_] = "stream events around the kernel in one un-chunked pass of the same shard behind the timed region"
+        # one un-chunked pass ALONE (outside the timed region): the kernels' own durations, the latency of a single pass
+        fb1 = capi.ForwardBackward(model)
+        frameOff = frame_off_all.astype(np.int32)
+        labOff = np.concatenate([[0], np.cumsum([len(q) for q in s.seqs])]).astype(np.int32)
+        labs = np.concatenate(s.seqs).astype(np.int32)
+        acc1 = capi.Accs(model)
+        lat = []
+        for rep in range(3):
+            torch.cuda.synchronize(); tl = time.perf_counter()
+            acc1.zero(sptr); fb1.prepare(dX.data_ptr(), frameOff, labOff, labs, sptr); fb1.execute(cfg, acc1, sptr); fb1.results(sptr)
+            lat.append(time.perf_counter() - tl)
+        ktimes_solo = np.array(fb1.kernel_times5())
+        torch.cuda.synchronize()
+        kernel_ms_source = {"score": "the dispatch's own start / stop, every timed iteration"}
+        for i_, n_ in ((1, "beta"), (2, "alpha"), (3, "stats"), (4, "mix_stats")):
+            if ktimes[i_] < 0:                                                 # not recorded in the timed iterations (set_events(1))
+                ktimes[i_] = ktimes_solo[i_]
+                kernel_ms_source[n_] = "stream events around the kernel in one un-chunked pass of the same shard behind the timed region"
 
     # the same timed iterations once more on the fp16 x 2 scores (from the initial model again): reported beside the line, never `value`
     fastest_side = None
-    if args.also_fastest and world == 1 and args.score == "bf16":
+    if args.full and args.also_fastest and world == 1 and args.score == "bf16":
         keep_mode = cfg.scoreMode
         try:
             model.set_params(mean=pk["mean"], var=pk["var"], compWeight=pk["compWeight"], transP=pk["transP"])
@@ -799,7 +852,7 @@ def main():
                 ch["ready"] = [False, False]
             cfg.scoreMode = 34
             range_hit[0] = False
-            dt_f, kt_f, _ = measure()
+            dt_f, kt_f, _, _ = measure()
             kt_f = kt_f / max(args.steps, 1)
             if not range_hit[0]:
                 fastest_side = {"score_mode": "fastest (fp16 x 2 split operands, k_score_f16w)", "ms_per_step": dt_f / args.steps * 1e3,
@@ -816,7 +869,7 @@ def main():
     utts_total = float(a["nUttDone"])
     value = units_total * args.steps / dt
 
-    if rank == 0:
+    if rank == 0 and args.full:
         flop_unit = FLOP_PER_FRAME_STATE(args.mix, D)
         kname = {"exact": "k_score_exact<39>", "bf16": "k_score_bf16w<5>" if 31 <= D <= 39 and args.mix <= 16 else "k_score_bf16w", "fastest": "k_score_f16w<3>"}.get(args.score, "k_score_mfma<20>")
         # HBM-side bytes per launch of every kernel from the committed PMC passes (FETCH_SIZE + WRITE_SIZE, separate runs: tools/prof_r03.sh),
@@ -905,6 +958,24 @@ def main():
                       "matrix_instructions_per_block": mi_blk, "mfma_issued": int(sw[0 if args.score == "bf16" else 1]) * mi_blk if mi_blk else None,
                       "mfma_needed": int(sw[2]) * mi_blk if mi_blk else None}
         dom = max(("score", "beta", "alpha", "stats"), key=lambda k_: per_kernel[k_]["ms"])
+        full_line = {
+            # split of an iteration's wall clock, from three iterations AFTER the timed region run with a stream synchronisation after every
+            # part (the timed iterations carry none but the one the model update needs: their sum is above ms_per_step)
+            "em_iteration_parts_ms": {"pass": t_parts[0] * 1e3, "allreduce": t_parts[1] * 1e3, "update_and_refresh": t_parts[2] * 1e3, "results": t_parts[3] * 1e3},
+            "pass_latency_ms": float(np.median(lat)) * 1e3,
+            "avg_logprob_per_frame": float(a_init["totalPr"] / a_init["totalT"]) if a_init["totalT"] else None,
+            "kernel_ms": {"score": k1 * 1e3, "beta": ktimes[1] * 1e3, "alpha": ktimes[2] * 1e3, "stats": ktimes[3] * 1e3, "mix_stats": ktimes[4] * 1e3},
+            "kernel_ms_source": kernel_ms_source,
+            "score_work": score_work,
+            # the kernel with the largest total time in the timed iterations
+            "roofline": dict(per_kernel[dom], units_per_launch=units_local / NCH, launches_per_step=NCH,
+                             traffic_source="profiles/%s: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes, bytes per launch as counted; "
+                                            "traffic_upper_bound: FETCH_SIZE doubled (MI355X_MICROARCH.md: gfx950 tallies 16-byte-per-lane streaming reads at half; "
+                                            "this kernel's table tiles are such reads, its feature rows and task words are not)" % PROFILE_TRAFFIC
+                             if dom == "score" and args.score in ("bf16", "fastest") else "profiles/%s: FETCH_SIZE + WRITE_SIZE per launch as counted (8- and 4-byte accesses: uncalibrated on gfx950)" % PROFILE_TRAFFIC),
+            "roofline_kernels": per_kernel,
+        }
+    if rank == 0:
         out = {
             "metric": "herest_gmm_frame_state_loglik_per_sec",
             "value": value,
@@ -933,31 +1004,18 @@ def main():
             "utterances_ok": utts_total,
             "em_iteration_ms": dt / args.steps * 1e3,
             "batch_tables_rebuilt_in_iteration": n_reprepared[0],
-            # split of an iteration's wall clock, from three iterations AFTER the timed region run with a stream synchronisation after every
-            # part (the timed iterations carry none but the one the model update needs: their sum is above ms_per_step)
-            "em_iteration_parts_ms": {"pass": t_parts[0] * 1e3, "allreduce": t_parts[1] * 1e3, "update_and_refresh": t_parts[2] * 1e3, "results": t_parts[3] * 1e3},
-            "pass_latency_ms": float(np.median(lat)) * 1e3,
-            "avg_logprob_per_frame": float(a_init["totalPr"] / a_init["totalT"]) if a_init["totalT"] else None,
             "avg_logprob_per_frame_last_iteration": float(a["totalPr"] / a["totalT"]) if a["totalT"] else None,
             "update_stats_last_iteration": st_upd,
-            "kernel_ms": {"score": k1 * 1e3, "beta": ktimes[1] * 1e3, "alpha": ktimes[2] * 1e3, "stats": ktimes[3] * 1e3, "mix_stats": ktimes[4] * 1e3},
-            "kernel_ms_source": kernel_ms_source,
-            "score_work": score_work,
             "score_mode": args.score,
             "streams": len(lanes),
-            # the kernel with the largest total time in the timed iterations
-            "roofline": dict(per_kernel[dom], units_per_launch=units_local / NCH, launches_per_step=NCH,
-                             traffic_source="profiles/%s: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes, bytes per launch as counted; "
-                                            "traffic_upper_bound: FETCH_SIZE doubled (MI355X_MICROARCH.md: gfx950 tallies 16-byte-per-lane streaming reads at half; "
-                                            "this kernel's table tiles are such reads, its feature rows and task words are not)" % PROFILE_TRAFFIC
-                             if dom == "score" and args.score in ("bf16", "fastest") else "profiles/%s: FETCH_SIZE + WRITE_SIZE per launch as counted (8- and 4-byte accesses: uncalibrated on gfx950)" % PROFILE_TRAFFIC),
-            "roofline_kernels": per_kernel,
         }
-        if fastest_side is not None:
-            out["fastest_mode"] = fastest_side
-        if ktimes_solo[0] > 0:
-            out["kernel_ms_isolated"] = {"score": ktimes_solo[0] * 1e3, "beta": ktimes_solo[1] * 1e3, "alpha": ktimes_solo[2] * 1e3, "stats": ktimes_solo[3] * 1e3, "mix_stats": ktimes_solo[4] * 1e3}
-        if args.cpu_seconds > 0 and world == 1:               # the CPU leg runs at N = 1 only
+        if args.full:
+            out.update(full_line)
+            if fastest_side is not None:
+                out["fastest_mode"] = fastest_side
+            if ktimes_solo[0] > 0:
+                out["kernel_ms_isolated"] = {"score": ktimes_solo[0] * 1e3, "beta": ktimes_solo[1] * 1e3, "alpha": ktimes_solo[2] * 1e3, "stats": ktimes_solo[3] * 1e3, "mix_stats": ktimes_solo[4] * 1e3}
+        if args.full and args.cpu_seconds > 0 and world == 1:               # the CPU leg runs at N = 1 only
             per_utt = units_local / max(len(s.feats), 1)
             n, cdt, opr, oacc, n_timed = cpu_baseline(s, pk, args.cpu_seconds)
             # the checker: the oracle's utterance log-probabilities for the same utterances under the same (initial) model
@@ -1035,7 +1093,7 @@ def main():
                 out["cpu_baseline_port"] = port
             else:
                 out["cpu_baseline"] = port
-        if args.extras and world == 1:
+        if args.full and args.extras and world == 1:
             try:
                 out["other_paths"] = other_paths(s, pk, dX, frame_off_all, cpu_utts=2 if args.cpu_seconds > 0 else 0)
                 if "k_decode" in traffic_of and "hvite_decoding" in out["other_paths"]:          # counter bytes of the token kernel, per launch (same PMC passes)
@@ -1048,7 +1106,7 @@ def main():
                     # BASELINE config[2] as ONE job on ONE GPU (10 000 utterances in one batch: the fastest way one GPU does it -- eight sub-batches
                     # on two streams take 17.5 ms for this 14.7): the denominator of the 8-GPU speed-up
                     out["other_paths"]["strong_1gpu"] = subprocess_leg(
-                        ["bench.py", "--gpus", "1", "--scaling", "strong", "--chunks", "1", "--cpu-seconds", "0", "--extras", "0", "--also-fastest", "0", "--steps", "10", "--warmup", "2"], 900,
+                        ["bench.py", "--full", "--gpus", "1", "--scaling", "strong", "--chunks", "1", "--cpu-seconds", "0", "--extras", "0", "--also-fastest", "0", "--steps", "10", "--warmup", "2"], 900,
                         lambda j: {k_: j.get(k_) for k_ in ("value", "unit", "ms_per_step", "herest_utterances_per_sec", "utterances_ok", "config", "kernel_ms")})
                     # the link-compatible boundary: the reference's unchanged HERest.o over the HFB shim, files per second (tools/shim_latency.py)
                     out["other_paths"]["boundary"] = subprocess_leg(["tools/shim_latency.py", "200"], 600, lambda j: j)
