@@ -565,6 +565,77 @@ class Mfcc:
             pass
 
 
+class FrontEndConfig(C.Structure):
+    _fields_ = [("base", MfccConfig), ("baseKind", C.c_int), ("lpcOrder", C.c_int), ("compressFact", C.c_float)]
+
+
+FRONTEND_KINDS = {"MFCC": 6, "FBANK": 7, "MELSPEC": 8, "PLP": 11}
+_LPC_KINDS = {"LPC": 1, "LPREFC": 2, "LPCEPSTRA": 3}
+
+
+def frontend_config(kind="PLP_0_D_A", sampPeriod=625.0, winDur=250000.0, frPeriod=100000.0, numChans=26, numCeps=12, cepLifter=22,
+                    preEmph=0.97, useHam=True, usePower=False, zMeanSource=False, rawEnergy=True, eNormalise=True,
+                    loFreq=-1.0, hiFreq=-1.0, cepScale=1.0, silFloor=50.0, eScale=0.1, delWin=2, accWin=2,
+                    lpcOrder=12, compressFact=0.33) -> FrontEndConfig:
+    """htkamd_frontend_config from TARGETKIND (e.g. "PLP_0_D_A", "FBANK_E_D_A_Z", "MELSPEC") and the HParm configuration variables.
+    The base kind is passed on as its HTK code; whether the device codes it is decided by the library (htkamd_frontend_num_cols)."""
+    q = kind.upper().split("_")
+    code = FRONTEND_KINDS.get(q[0], _LPC_KINDS.get(q[0]))
+    if code is None:
+        raise HtkAmdError("unknown base kind %s in %s" % (q[0], kind))
+    base = MfccConfig(sampPeriod, winDur, frPeriod, numChans, numCeps, cepLifter, preEmph, int(useHam), int(usePower), int(zMeanSource),
+                      int(rawEnergy), int(eNormalise), loFreq, hiFreq, cepScale, silFloor, eScale,
+                      int("0" in q[1:]), int("E" in q[1:]), int("D" in q[1:]), int("A" in q[1:]), int("Z" in q[1:]), delWin, accWin)
+    return FrontEndConfig(base, code, lpcOrder, compressFact)
+
+
+def frontend_num_cols(cfg: FrontEndConfig) -> int:
+    """Columns of a row of `cfg`'s output; a refused configuration raises HtkAmdError with the library's reason."""
+    n = lib().htkamd_frontend_num_cols(C.byref(cfg))
+    check(0 if n >= 0 else n, "frontend_num_cols")
+    return n
+
+
+class FrontEnd:
+    """htkamd_frontend holder: waveform -> MFCC / FBANK / MELSPEC / PLP feature matrix on the device."""
+
+    def __init__(self, cfg: FrontEndConfig):
+        self.cfg = cfg
+        self.h = C.c_void_p()
+        self.cols = frontend_num_cols(cfg)
+        check(lib().htkamd_frontend_create(C.byref(cfg), C.byref(self.h)), "frontend_create")
+
+    def compute(self, waves, stream=None):
+        """waves: list of int16 arrays.  Returns (DevArray features [sumT, cols], frameOff)."""
+        waves = [np.ascontiguousarray(w, np.int16) for w in waves]
+        sampOff = np.concatenate([[0], np.cumsum([len(w) for w in waves])]).astype(np.int32)
+        allw = np.concatenate(waves) if waves else np.zeros(0, np.int16)
+        frames = [lib().htkamd_frontend_num_frames(C.byref(self.cfg), C.c_int(len(w))) for w in waves]
+        total = int(sum(frames))
+        dW = DevArray(allw if len(allw) else np.zeros(1, np.int16))
+        dO = DevArray(nbytes=4 * max(total, 1) * self.cols)
+        frameOff = np.zeros(len(waves) + 1, np.int32)
+        check(lib().htkamd_frontend_compute(self.h, dW.ptr, _p(sampOff), C.c_int(len(waves)), _p(frameOff), dO.ptr, _stream(stream)),
+              "frontend_compute")
+        assert frameOff[-1] == total
+        return dO, frameOff
+
+    def compute_host(self, waves):
+        dO, frameOff = self.compute(waves)
+        return dO.to_host(np.float32, (int(frameOff[-1]), self.cols)), frameOff
+
+    def close(self):
+        if self.h:
+            lib().htkamd_frontend_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _desc_from_packed(pk: dict):
     """(ModelDesc, keepalive) from a packed dict -- for the pure-host entry points that take a description."""
     f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)

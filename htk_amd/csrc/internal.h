@@ -50,9 +50,16 @@ struct htkamd_mfcc_tables {
    double *tw;                 /* FFT twiddles (wr,wi), stages concatenated: fftN/2 pairs */
    double *rtw;                /* Realft (yr,yi) for i = 2..fftN/4 at [2i],[2i+1] */
    short *brev;                /* [fftN/2] bit-reversed complex index */
+   int takeLogs;               /* the bins are logged (MFCC, FBANK), or left linear (MELSPEC, PLP) */
+   float *eql;                 /* PLP: [numChans+1] 1-based equal-loudness curve (InitPLP HSigP.c:663) */
+   double *cm;                 /* PLP: [(lpcOrder+1)*(numChans+2)] IDFT cosines, row = lag, 0-based */
 };
 int  htkamd_mfcc_tables_build(const htkamd_mfcc_config *c, struct htkamd_mfcc_tables *t);
 void htkamd_mfcc_tables_free(struct htkamd_mfcc_tables *t);
+/* the tables of every FFT front end (htk_amd/host/fbank.c): validates as htkamd_frontend_num_cols does, then builds the MFCC
+   path's tables plus what the base kind needs after the bins; htkamd_frontend_check: the validation alone, 0 or HTKAMD_EINVAL */
+int  htkamd_frontend_check(const htkamd_frontend_config *c);
+int  htkamd_frontend_tables_build(const htkamd_frontend_config *c, struct htkamd_mfcc_tables *t);
 
 /* ---- packed model ---- */
 struct htkamd_model {

@@ -12,6 +12,11 @@
 // reference, so a lane owns a bin / a cepstral coefficient and walks its k range in order.  Frame energies and
 // the source mean are 400-term sequential float sums: a lane per FRAME does those in a separate tiny kernel.
 // Deltas/accelerations are one thread per output element; energy normalisation and _Z are per-utterance passes.
+//
+// The other FFT front ends (htkamd_frontend_*) share everything up to the mel bins and differ in the tail after them: FBANK writes the
+// logged bins, MELSPEC the linear ones, PLP turns the linear bins into cepstra through an all-pole model (FBank2ASpec, MatrixIDFT,
+// Durbin, LPC2Cepstrum: HSigP.c:693-750).  k_mfcc_frames takes the kind as a template parameter; its MFCC instantiation is the
+// MFCC kernel as it was.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
@@ -33,7 +38,13 @@ struct MfccArgs {
    const short *brev;
    float *frameMean;             // [F] (ZMEANSOURCE)
    float *out;
+   const float *eql;             // PLP: [numChans+1] equal-loudness curve, 1-based
+   const double *cm;             // PLP: [(lpcOrder+1) x (numChans+2)] IDFT cosines
+   int lpcOrder, plpExtra;       // PLP: LPCORDER; LDS floats per frame beyond the MFCC layout
+   float compressFact;           // PLP: COMPRESSFACT
 };
+
+enum { FE_MFCC = 6, FE_FBANK = 7, FE_MELSPEC = 8, FE_PLP = 11 };     // HTK base codes of the target kinds
 
 // first sample and utterance of every frame from the per-utterance offsets (binary search over the utterances)
 __global__ void k_mfcc_index(const int *frameOff, const int *sampOff, int nUtt, int nFrames, int frRate, long long *frameSamp, int *frameUtt)
@@ -193,12 +204,17 @@ __device__ __forceinline__ void mfcc_spectrum(const MfccArgs &a, const int f, fl
    __syncthreads();
 }
 
-// mel bin b of one frame (HSigP.c:591-594 in the reference's accumulation order, then log with floor 1.0, :598-603)
-__device__ __forceinline__ float mfcc_bin(const MfccArgs &a, const int b, const float *uk, const float *vk)
+// mel bin b of one frame, linear (HSigP.c:591-594 in the reference's accumulation order), and logged with floor 1.0 (:598-603)
+__device__ __forceinline__ float mfcc_bin_lin(const MfccArgs &a, const int b, const float *uk, const float *vk)
 {
    float acc = 0.0f;
    for (int k = a.binA0[b]; k <= a.binA1[b]; k++) acc += uk[k];
    for (int k = a.binB0[b]; k <= a.binB1[b]; k++) acc += vk[k];
+   return acc;
+}
+__device__ __forceinline__ float mfcc_bin(const MfccArgs &a, const int b, const float *uk, const float *vk)
+{
+   float acc = mfcc_bin_lin(a, b, uk, vk);
    if (acc < 1.0f) acc = 1.0f;
    return (float)log((double)acc);
 }
@@ -219,18 +235,67 @@ __device__ __forceinline__ float mfcc_c0(const MfccArgs &a, const float *fb)    
    return (sum * a.mfnorm) * a.cepScale;
 }
 
+// ---- PLP after the linear bins (ASpec2LPCep HSigP.c:735 and what it calls), in the reference's types and order.
+// Auditory-spectrum point b + 1 from linear bin b (FBank2ASpec :693): floor 1.0, equal-loudness weight, compression; the two end
+// points repeat their neighbours.  as[] is 1-based over numChans + 2 points.
+__device__ __forceinline__ void plp_aspec(const MfccArgs &a, const int b, const float bin, float *as)
+{
+   float v = (bin < 1.0f) ? 1.0f : bin;
+   v = v * a.eql[b];
+   v = (float)pow((double)v, (double)a.compressFact);
+   as[b + 1] = v;
+   if (b == 1) as[1] = v;
+   if (b == a.numChans) as[a.numChans + 2] = v;
+}
+// autocorrelation lag i (MatrixIDFT :710): a double dot product over the numChans + 2 points in order; lag 0 is the energy E
+__device__ __forceinline__ float plp_autocorr(const MfccArgs &a, const int i, const float *as)
+{
+   const int nFreq = a.numChans + 2;
+   const double *row = a.cm + (size_t)i * nFreq;
+   double acc = row[0] * (double)as[1];
+   for (int j = 1; j < nFreq; j++) acc += row[j] * (double)as[j + 1];
+   return (float)(acc / (double)(2.0 * (nFreq - 1)));
+}
+// One lane per frame: Durbin (:167) on ac[0..p] into the predictor lp[1..p], LPC2Cepstrum (:262) into cc[1..numCeps],
+// the gain as C0 into cc[numCeps+1].  Both recursions are chains of dependent float operations.  Durbin's update of the predictor is
+// done in place, a coefficient and its mirror together: every new value is the reference's expression of the old ones.
+__device__ __forceinline__ void plp_tail(const MfccArgs &a, const float *ac, float *lp, float *cc)
+{
+   const int p = a.lpcOrder;
+   float E = ac[0];
+   for (int i = 1; i <= p; i++) {
+      float ki = ac[i];
+      for (int j = 1; j < i; j++) ki = ki + lp[j] * ac[i - j];
+      ki = ki / E;
+      E *= 1.0f - ki * ki;
+      int j = 1, m = i - 1;
+      for (; j < m; j++, m--) { const float x = lp[j], y = lp[m]; lp[j] = x - ki * y; lp[m] = y - ki * x; }
+      if (j == m) lp[j] = lp[j] - ki * lp[j];
+      lp[i] = -ki;
+   }
+   for (int n = 1; n <= a.numCeps; n++) {
+      float sum = 0.0f;
+      for (int i = 1; i < n; i++) sum = sum + (float)(n - i) * lp[i] * cc[n - i];
+      cc[n] = -(lp[n] + sum / (float)n);
+   }
+   cc[a.numCeps + 1] = (float)-log(1.0 / (double)E);
+}
+
 // One wavefront per PAIR of frames (round 6).  The spectra take the whole wavefront, one frame after the other; the mel bins and the cepstra
 // are chains of dependent float additions that only numChans (26) and numCeps + 1 (13) lanes can work on -- 40 % of the kernel's vector
 // instructions ran with 26 lanes on -- so the two frames' chains run side by side, frame h in lanes 32 h .. 32 h + 31.
 // PAIR = false (numChans > 32 or numCeps > 31): one frame per wavefront, the bins and cepstra strided over the lanes.
-template <bool PAIR>
+// KIND (FE_*): what follows the bins.  FBANK / MELSPEC write the bins themselves; PLP takes a lane per auditory-spectrum point, then a
+// lane per autocorrelation lag, then one lane per frame for the two recursions (PAIR: lpcOrder <= 31 as well), its workspace behind fb:
+// as [numChans + 3] | ac [lpcOrder + 1] | lp [lpcOrder + 2] | cc [numCeps + 2] (plpExtra floats; lp and cc 1-based).
+template <bool PAIR, int KIND = FE_MFCC>
 __global__ __launch_bounds__(64) void k_mfcc_frames(MfccArgs a)
 {
    extern __shared__ float lds[];
    const int lane = threadIdx.x;
    const int fftN = a.fftN, nn = fftN / 2;
    constexpr int NF = PAIR ? 2 : 1;
-   const int per = (fftN + 2 * (nn + 2) + a.numChans + 2 + 3) & ~3;      // floats per frame (a multiple of 16 bytes): xs [fftN] interleaved (re, im) | uk [nn + 2] | vk [nn + 2], 1-based k | fb [numChans + 2]
+   const int per = (fftN + 2 * (nn + 2) + a.numChans + 2 + (KIND == FE_PLP ? a.plpExtra : 0) + 3) & ~3;      // floats per frame (a multiple of 16 bytes): xs [fftN] interleaved (re, im) | uk [nn + 2] | vk [nn + 2], 1-based k | fb [numChans + 2]
    for (int blk = blockIdx.x; NF * blk < a.nFrames; blk += gridDim.x) {
    const int f0 = NF * blk;
    for (int h = 0; h < NF; h++)
@@ -238,6 +303,7 @@ __global__ __launch_bounds__(64) void k_mfcc_frames(MfccArgs a)
    if constexpr (PAIR) {
       const int h = lane >> 5, q = lane & 31, f = f0 + h;
       float *base = lds + h * per, *fb = base + fftN + 2 * (nn + 2);
+      if constexpr (KIND == FE_MFCC) {
       if (f < a.nFrames && q < a.numChans) fb[q + 1] = mfcc_bin(a, q + 1, base + fftN, base + fftN + nn + 2);
       __syncthreads();
       if (f < a.nFrames) {
@@ -245,13 +311,48 @@ __global__ __launch_bounds__(64) void k_mfcc_frames(MfccArgs a)
          if (q < a.numCeps) row[q] = mfcc_cep(a, q + 1, fb);
          else if (a.hasC0 && q == 31) row[a.numCeps] = mfcc_c0(a, fb);
       }
+      } else if constexpr (KIND == FE_FBANK || KIND == FE_MELSPEC) {
+         if (f < a.nFrames && q < a.numChans)
+            a.out[(size_t)f * a.nCols + q] = (KIND == FE_FBANK) ? mfcc_bin(a, q + 1, base + fftN, base + fftN + nn + 2)
+                                                                : mfcc_bin_lin(a, q + 1, base + fftN, base + fftN + nn + 2);
+      } else {
+         float *as = fb + a.numChans + 2, *ac = as + a.numChans + 3, *lp = ac + a.lpcOrder + 1, *cc = lp + a.lpcOrder + 2;
+         if (f < a.nFrames && q < a.numChans) plp_aspec(a, q + 1, mfcc_bin_lin(a, q + 1, base + fftN, base + fftN + nn + 2), as);
+         __syncthreads();
+         if (f < a.nFrames && q <= a.lpcOrder) ac[q] = plp_autocorr(a, q, as);
+         __syncthreads();
+         if (f < a.nFrames && q == 0) plp_tail(a, ac, lp, cc);
+         __syncthreads();
+         if (f < a.nFrames) {
+            float *row = a.out + (size_t)f * a.nCols;
+            if (q < a.numCeps) row[q] = (cc[q + 1] * a.cepWin[q + 1]) * a.cepScale;
+            else if (a.hasC0 && q == 31) row[a.numCeps] = cc[a.numCeps + 1] * a.cepScale;
+         }
+      }
    } else {
       float *fb = lds + fftN + 2 * (nn + 2);
+      if constexpr (KIND == FE_MFCC) {
       for (int b = 1 + lane; b <= a.numChans; b += 64) fb[b] = mfcc_bin(a, b, lds + fftN, lds + fftN + nn + 2);
       __syncthreads();
       float *row = a.out + (size_t)f0 * a.nCols;
       for (int j = 1 + lane; j <= a.numCeps; j += 64) row[j - 1] = mfcc_cep(a, j, fb);
       if (a.hasC0 && lane == 63) row[a.numCeps] = mfcc_c0(a, fb);
+      } else if constexpr (KIND == FE_FBANK || KIND == FE_MELSPEC) {
+         float *row = a.out + (size_t)f0 * a.nCols;
+         for (int b = 1 + lane; b <= a.numChans; b += 64)
+            row[b - 1] = (KIND == FE_FBANK) ? mfcc_bin(a, b, lds + fftN, lds + fftN + nn + 2) : mfcc_bin_lin(a, b, lds + fftN, lds + fftN + nn + 2);
+      } else {
+         float *as = fb + a.numChans + 2, *ac = as + a.numChans + 3, *lp = ac + a.lpcOrder + 1, *cc = lp + a.lpcOrder + 2;
+         for (int b = 1 + lane; b <= a.numChans; b += 64) plp_aspec(a, b, mfcc_bin_lin(a, b, lds + fftN, lds + fftN + nn + 2), as);
+         __syncthreads();
+         for (int i = lane; i <= a.lpcOrder; i += 64) ac[i] = plp_autocorr(a, i, as);
+         __syncthreads();
+         if (lane == 0) plp_tail(a, ac, lp, cc);
+         __syncthreads();
+         float *row = a.out + (size_t)f0 * a.nCols;
+         for (int j = 1 + lane; j <= a.numCeps; j += 64) row[j - 1] = (cc[j] * a.cepWin[j]) * a.cepScale;
+         if (a.hasC0 && lane == 63) row[a.numCeps] = cc[a.numCeps + 1] * a.cepScale;
+      }
    }
    __syncthreads();                                      // (the next frames' spectra overwrite what the cepstra read)
    }
@@ -332,7 +433,12 @@ struct htkamd_mfcc {
    short *d_brev;
    long long *d_frameSamp;
    size_t capFrames, capUtt;
+   int kind, lpcOrder;                   // FE_* (FE_MFCC for htkamd_mfcc_create); PLP: LPCORDER, COMPRESSFACT and its tables
+   float compressFact;
+   float *d_eql;
+   double *d_cm;
 };
+struct htkamd_frontend { htkamd_mfcc m; };       // the same holder behind the general entry points
 
 template <typename T> static int up(T **d, const T *h, size_t n)
 {
@@ -341,43 +447,69 @@ template <typename T> static int up(T **d, const T *h, size_t n)
    return HTKAMD_OK;
 }
 
+// tables of front end `fc` (validated by htkamd_frontend_tables_build on the host) onto the device
+static int fe_create(const htkamd_frontend_config *fc, htkamd_mfcc *f)
+{
+   const htkamd_mfcc_config *cfg = &fc->base;
+   f->cfg = *cfg; f->kind = fc->baseKind; f->lpcOrder = fc->lpcOrder; f->compressFact = fc->compressFact;
+   int rc = htkamd_frontend_tables_build(fc, &f->tab);
+   if (rc) return rc;
+   const htkamd_mfcc_tables &t = f->tab;
+   const int nn = t.fftN / 2;
+   const int nCep = (f->kind == FE_MFCC || f->kind == FE_PLP) ? cfg->numCeps : 0, nDct = (f->kind == FE_MFCC) ? cfg->numCeps : 0;
+   if ((rc = up(&f->d_ham, t.ham, (size_t)t.frSize + 1)) || (rc = up(&f->d_cepWin, t.cepWin, (size_t)nCep + 1)) ||
+       (rc = up(&f->d_loWt, t.loWt, (size_t)nn + 2)) || (rc = up(&f->d_bins, t.binA0, (size_t)4 * (cfg->numChans + 2))) ||
+       (rc = up(&f->d_dct, t.dct, (size_t)(nDct + 1) * (cfg->numChans + 1))) || (rc = up(&f->d_tw, t.tw, (size_t)2 * nn)) ||
+       (rc = up(&f->d_rtw, t.rtw, (size_t)2 * (nn / 2 + 2))) || (rc = up(&f->d_brev, t.brev, (size_t)nn)))
+      return rc;
+   if (f->kind == FE_PLP &&
+       ((rc = up(&f->d_eql, t.eql, (size_t)cfg->numChans + 1)) || (rc = up(&f->d_cm, t.cm, (size_t)(fc->lpcOrder + 1) * (cfg->numChans + 2)))))
+      return rc;
+   return HTKAMD_OK;
+}
+
 extern "C" int htkamd_mfcc_create(const htkamd_mfcc_config *cfg, htkamd_mfcc **out)
 {
    if (!cfg || !out) { htkamd_set_error("mfcc_create: NULL argument"); return HTKAMD_EINVAL; }
    if (htkamd_device_count() <= 0) { htkamd_set_error("mfcc_create: no HIP device"); return HTKAMD_ENODEV; }
+   htkamd_frontend_config fc;
+   memset(&fc, 0, sizeof(fc));
+   fc.base = *cfg; fc.baseKind = FE_MFCC;
    htkamd_mfcc *f = (htkamd_mfcc *)calloc(1, sizeof(htkamd_mfcc));
-   f->cfg = *cfg;
-   int rc = htkamd_mfcc_tables_build(cfg, &f->tab);
-   if (rc) { free(f); return rc; }
-   const htkamd_mfcc_tables &t = f->tab;
-   const int nn = t.fftN / 2;
-   if ((rc = up(&f->d_ham, t.ham, (size_t)t.frSize + 1)) || (rc = up(&f->d_cepWin, t.cepWin, (size_t)cfg->numCeps + 1)) ||
-       (rc = up(&f->d_loWt, t.loWt, (size_t)nn + 2)) || (rc = up(&f->d_bins, t.binA0, (size_t)4 * (cfg->numChans + 2))) ||
-       (rc = up(&f->d_dct, t.dct, (size_t)(cfg->numCeps + 1) * (cfg->numChans + 1))) || (rc = up(&f->d_tw, t.tw, (size_t)2 * nn)) ||
-       (rc = up(&f->d_rtw, t.rtw, (size_t)2 * (nn / 2 + 2))) || (rc = up(&f->d_brev, t.brev, (size_t)nn))) {
-      htkamd_mfcc_destroy(f); return rc;
-   }
+   const int rc = fe_create(&fc, f);
+   if (rc) { htkamd_mfcc_destroy(f); return rc; }
    *out = f;
    return HTKAMD_OK;
+}
+
+static void fe_release(htkamd_mfcc *f)
+{
+   (void)hipFree(f->d_ham); (void)hipFree(f->d_cepWin); (void)hipFree(f->d_loWt); (void)hipFree(f->d_bins); (void)hipFree(f->d_dct);
+   (void)hipFree(f->d_tw); (void)hipFree(f->d_rtw); (void)hipFree(f->d_brev); (void)hipFree(f->d_frameSamp); (void)hipFree(f->d_frameMean);
+   (void)hipFree(f->d_frameOff); (void)hipFree(f->d_frameUtt); (void)hipFree(f->d_eql); (void)hipFree(f->d_cm);
+   htkamd_mfcc_tables_free(&f->tab);
 }
 
 extern "C" void htkamd_mfcc_destroy(htkamd_mfcc *f)
 {
    if (!f) return;
-   (void)hipFree(f->d_ham); (void)hipFree(f->d_cepWin); (void)hipFree(f->d_loWt); (void)hipFree(f->d_bins); (void)hipFree(f->d_dct);
-   (void)hipFree(f->d_tw); (void)hipFree(f->d_rtw); (void)hipFree(f->d_brev); (void)hipFree(f->d_frameSamp); (void)hipFree(f->d_frameMean);
-   (void)hipFree(f->d_frameOff); (void)hipFree(f->d_frameUtt);
-   htkamd_mfcc_tables_free(&f->tab);
+   fe_release(f);
    free(f);
 }
 
-extern "C" int htkamd_mfcc_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream)
+template <int KIND> static void launch_frames(bool pair, int F, int maxGrid, size_t per, hipStream_t s, const MfccArgs &a)
 {
-   if (!f || !sampOff || !frameOff || nUtt < 0 || (nUtt > 0 && (!dWav || !dOut))) { htkamd_set_error("mfcc_compute: bad argument"); return HTKAMD_EINVAL; }
+   if (pair) hipLaunchKernelGGL((k_mfcc_frames<true, KIND>), dim3(std::min((F + 1) / 2, maxGrid)), dim3(64), 2 * per, s, a);
+   else hipLaunchKernelGGL((k_mfcc_frames<false, KIND>), dim3(std::min(F, maxGrid)), dim3(64), per, s, a);
+}
+
+static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream)
+{
    hipStream_t s = (hipStream_t)stream;
    const htkamd_mfcc_config &c = f->cfg;
    const htkamd_mfcc_tables &t = f->tab;
-   const int nCols = htkamd_mfcc_num_cols(&c), nStat = c.numCeps + (c.hasC0 ? 1 : 0) + (c.hasE ? 1 : 0);
+   const int nBase = (f->kind == FE_FBANK || f->kind == FE_MELSPEC) ? c.numChans : c.numCeps;      // the statics before C0 / E
+   const int nStat = nBase + (c.hasC0 ? 1 : 0) + (c.hasE ? 1 : 0), nCols = nStat * (1 + (c.hasD ? 1 : 0) + (c.hasA ? 1 : 0));
    frameOff[0] = 0;
    for (int u = 0; u < nUtt; u++) frameOff[u + 1] = frameOff[u] + htkamd_mfcc_num_frames(&c, sampOff[u + 1] - sampOff[u]);
    const int F = frameOff[nUtt];
@@ -411,19 +543,28 @@ extern "C" int htkamd_mfcc_compute(htkamd_mfcc *f, const short *dWav, const int 
    a.ham = f->d_ham; a.cepWin = f->d_cepWin; a.loWt = f->d_loWt;
    a.binA0 = f->d_bins; a.binA1 = f->d_bins + (c.numChans + 2); a.binB0 = a.binA1 + (c.numChans + 2); a.binB1 = a.binB0 + (c.numChans + 2);
    a.dct = f->d_dct; a.tw = f->d_tw; a.rtw = f->d_rtw; a.brev = f->d_brev; a.frameMean = f->d_frameMean; a.out = dOut;
+   a.eql = f->d_eql; a.cm = f->d_cm; a.lpcOrder = f->lpcOrder; a.compressFact = f->compressFact;
+   a.plpExtra = (f->kind == FE_PLP) ? (c.numChans + 3) + (f->lpcOrder + 1) + (f->lpcOrder + 2) + (c.numCeps + 2) : 0;
 
    if (c.hasE || c.zMeanSource) {
       hipLaunchKernelGGL(k_mfcc_energy, dim3((F + 63) / 64), dim3(64), 0, s, a);
       HIPCHECK(hipGetLastError());
    }
-   const size_t per = sizeof(float) * ((((size_t)t.fftN + 2 * ((size_t)t.fftN / 2 + 2) + c.numChans + 2) + 3) & ~(size_t)3);
+   const size_t per = sizeof(float) * ((((size_t)t.fftN + 2 * ((size_t)t.fftN / 2 + 2) + c.numChans + 2 + a.plpExtra) + 3) & ~(size_t)3);
    // (a grid of persistent wavefronts -- HTKAMD_MFCC_WPC per CU -- was tried against one workgroup per pair of frames: 1.93 ms at 16 or 32 per CU
    //  against 1.78 for the plain grid, tools/r06_mfcc2.sh; the loop stays, the default grid covers every pair)
    int wpc = 1 << 20;
    { const char *e = getenv("HTKAMD_MFCC_WPC"); if (e && atoi(e) > 0) wpc = atoi(e); }
    const int maxGrid = 256 * wpc;
-   if (c.numChans <= 32 && c.numCeps <= 31 && !getenv("HTKAMD_MFCC_ONE_FRAME")) hipLaunchKernelGGL(k_mfcc_frames<true>, dim3(std::min((F + 1) / 2, maxGrid)), dim3(64), 2 * per, s, a);
-   else hipLaunchKernelGGL(k_mfcc_frames<false>, dim3(std::min(F, maxGrid)), dim3(64), per, s, a);
+   // two frames per wavefront when a frame's lanes fit in 32: the bins, the cepstra / bins written, PLP's autocorrelation lags
+   const bool pair = c.numChans <= 32 && (f->kind == FE_FBANK || f->kind == FE_MELSPEC || c.numCeps <= 31) &&
+                     (f->kind != FE_PLP || f->lpcOrder <= 31) && !getenv("HTKAMD_MFCC_ONE_FRAME");
+   switch (f->kind) {
+   case FE_MFCC: launch_frames<FE_MFCC>(pair, F, maxGrid, per, s, a); break;
+   case FE_FBANK: launch_frames<FE_FBANK>(pair, F, maxGrid, per, s, a); break;
+   case FE_MELSPEC: launch_frames<FE_MELSPEC>(pair, F, maxGrid, per, s, a); break;
+   default: launch_frames<FE_PLP>(pair, F, maxGrid, per, s, a); break;
+   }
    HIPCHECK(hipGetLastError());
    if (c.hasE && c.eNormalise) {
       hipLaunchKernelGGL(k_mfcc_enorm, dim3(nUtt), dim3(256), 0, s, dOut, f->d_frameOff, nCols, nStat - 1, c.silFloor, c.eScale);
@@ -439,12 +580,58 @@ extern "C" int htkamd_mfcc_compute(htkamd_mfcc *f, const short *dWav, const int 
       }
    }
    if (c.hasZ) {
-      const int d = c.numCeps + (c.hasC0 ? 1 : 0);
+      const int d = nBase + (c.hasC0 ? 1 : 0);                                  // HParm.c:1712-1715
       hipLaunchKernelGGL(k_mfcc_zmean, dim3((nUtt * d + 63) / 64), dim3(64), 0, s, dOut, f->d_frameOff, nUtt, nCols, d);
       HIPCHECK(hipGetLastError());
    }
    HIPCHECK(hipStreamSynchronize(s));           // (sampOff / frameOff are the caller's: the copies above must be over when the call returns)
    return HTKAMD_OK;
+}
+
+extern "C" int htkamd_mfcc_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream)
+{
+   if (!f || !sampOff || !frameOff || nUtt < 0 || (nUtt > 0 && (!dWav || !dOut))) { htkamd_set_error("mfcc_compute: bad argument"); return HTKAMD_EINVAL; }
+   return fe_compute(f, dWav, sampOff, nUtt, frameOff, dOut, stream);
+}
+
+// ------------------------------------------------------------------------------------ MFCC, FBANK, MELSPEC and PLP
+extern "C" int htkamd_frontend_num_frames(const htkamd_frontend_config *cfg, int nSamples)
+{
+   return cfg ? htkamd_mfcc_num_frames(&cfg->base, nSamples) : 0;
+}
+
+extern "C" int htkamd_frontend_num_cols(const htkamd_frontend_config *cfg)
+{
+   const int rc = htkamd_frontend_check(cfg);
+   if (rc) return rc;
+   const htkamd_mfcc_config &c = cfg->base;
+   const int nBase = (cfg->baseKind == FE_FBANK || cfg->baseKind == FE_MELSPEC) ? c.numChans : c.numCeps;
+   return (nBase + (c.hasC0 ? 1 : 0) + (c.hasE ? 1 : 0)) * (1 + (c.hasD ? 1 : 0) + (c.hasA ? 1 : 0));
+}
+
+extern "C" int htkamd_frontend_create(const htkamd_frontend_config *cfg, htkamd_frontend **out)
+{
+   if (!cfg || !out) { htkamd_set_error("frontend_create: NULL argument"); return HTKAMD_EINVAL; }
+   int rc = htkamd_frontend_check(cfg);                 // (refusals come before the device is touched)
+   if (rc) return rc;
+   if (htkamd_device_count() <= 0) { htkamd_set_error("frontend_create: no HIP device"); return HTKAMD_ENODEV; }
+   htkamd_frontend *f = (htkamd_frontend *)calloc(1, sizeof(htkamd_frontend));
+   if ((rc = fe_create(cfg, &f->m)) != HTKAMD_OK) { htkamd_frontend_destroy(f); return rc; }
+   *out = f;
+   return HTKAMD_OK;
+}
+
+extern "C" void htkamd_frontend_destroy(htkamd_frontend *f)
+{
+   if (!f) return;
+   fe_release(&f->m);
+   free(f);
+}
+
+extern "C" int htkamd_frontend_compute(htkamd_frontend *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream)
+{
+   if (!f || !sampOff || !frameOff || nUtt < 0 || (nUtt > 0 && (!dWav || !dOut))) { htkamd_set_error("frontend_compute: bad argument"); return HTKAMD_EINVAL; }
+   return fe_compute(&f->m, dWav, sampOff, nUtt, frameOff, dOut, stream);
 }
 
 // ------------------------------------------------------------------------------------ qualifiers on a parameterised table

@@ -7,6 +7,8 @@
  *   lifter                GenCepWin HSigP.c:755-770
  *   DCT cosines           FBank2MFCC HSigP.c:607-621 (cos(x*(k-0.5)) per term, double)
  *   FFT twiddles          the double-precision recurrences of FFT HSigP.c:332-349 and Realft :371-386, tabulated
+ *   PLP                   InitPLP HSigP.c:663-690: equal-loudness curve at the filters' centres, IDFT cosine matrix
+ * and the validation of the other FFT front ends (FBANK, MELSPEC, PLP: ValidCodeParms HParm.c:1317-1365).
  */
 #include <math.h>
 #include <stdlib.h>
@@ -52,22 +54,82 @@ int htkamd_mfcc_num_cols(const htkamd_mfcc_config *c)
 void htkamd_mfcc_tables_free(struct htkamd_mfcc_tables *t)
 {
    free(t->ham); free(t->cepWin); free(t->loWt); free(t->binA0); free(t->dct); free(t->tw); free(t->rtw); free(t->brev);
+   free(t->eql); free(t->cm);
    memset(t, 0, sizeof(*t));
+}
+
+/* frame and FFT geometry, channel and cepstrum counts: MFCC keeps its own limits (numChans <= 63, numCeps <= 64); the other kinds take
+   ValidCodeParms' 2..1000 channels (HParm.c:1340) and need numCeps only for PLP */
+static int check_geometry(const htkamd_mfcc_config *c, int baseKind)
+{
+   const int frSize = (int)(c->winDur / c->sampPeriod), frRate = (int)(c->frPeriod / c->sampPeriod);
+   int fftN = 2;
+   if (baseKind == 6) {
+      if (frSize < 2 || frRate < 1 || c->numChans < 1 || c->numCeps < 1 || c->numCeps > 64 || c->numChans > 63) {
+         htkamd_set_error("mfcc: unsupported geometry (frSize %d frRate %d chans %d ceps %d)", frSize, frRate, c->numChans, c->numCeps);
+         return HTKAMD_EINVAL;
+      }
+   } else if (frSize < 2 || frRate < 1 || c->numChans < 2 || c->numChans > 1000) {
+      htkamd_set_error("frontend: unsupported geometry (frSize %d frRate %d chans %d; NUMCHANS must lie in 2..1000)", frSize, frRate, c->numChans);
+      return HTKAMD_EINVAL;
+   }
+   while (frSize > fftN) fftN *= 2;
+   if (fftN < 8 || fftN > 4096) { htkamd_set_error("mfcc: FFT size %d outside 8..4096", fftN); return HTKAMD_EINVAL; }
+   return HTKAMD_OK;
+}
+
+int htkamd_frontend_check(const htkamd_frontend_config *f)
+{
+   const htkamd_mfcc_config *c;
+   if (!f) { htkamd_set_error("frontend: NULL configuration"); return HTKAMD_EINVAL; }
+   c = &f->base;
+   switch (f->baseKind) {
+   case 6: case 7: case 8: case 11: break;
+   case 1: case 2: case 3:
+      htkamd_set_error("frontend: %s is a time-domain LPC kind (Wave2LPC); only MFCC, FBANK, MELSPEC and PLP are coded on the device",
+                       f->baseKind == 1 ? "LPC" : f->baseKind == 2 ? "LPREFC" : "LPCEPSTRA");
+      return HTKAMD_EINVAL;
+   default:
+      htkamd_set_error("frontend: base kind %d is not an FFT front end (MFCC 6, FBANK 7, MELSPEC 8, PLP 11)", f->baseKind);
+      return HTKAMD_EINVAL;
+   }
+   if ((f->baseKind == 7 || f->baseKind == 8) && c->hasC0) {
+      htkamd_set_error("frontend: _0 on %s: the filterbank kinds have no C0", f->baseKind == 7 ? "FBANK" : "MELSPEC");
+      return HTKAMD_EINVAL;
+   }
+   if (f->baseKind == 11) {                           /* ValidCodeParms HParm.c:1347-1362 */
+      if (f->lpcOrder < 2 || f->lpcOrder > 1000) { htkamd_set_error("frontend: PLP: unlikely LPCORDER %d (2..1000)", f->lpcOrder); return HTKAMD_EINVAL; }
+      if (c->numCeps < 2 || c->numCeps > f->lpcOrder) {
+         htkamd_set_error("frontend: PLP: unlikely NUMCEPS %d (2..LPCORDER = %d)", c->numCeps, f->lpcOrder); return HTKAMD_EINVAL;
+      }
+      if (!(f->compressFact > 0.0f && f->compressFact < 1.0f)) {
+         htkamd_set_error("frontend: PLP: COMPRESSFACT %g must lie strictly between 0 and 1", (double)f->compressFact); return HTKAMD_EINVAL;
+      }
+   }
+   return check_geometry(c, f->baseKind);
 }
 
 int htkamd_mfcc_tables_build(const htkamd_mfcc_config *c, struct htkamd_mfcc_tables *t)
 {
-   int fftN = 2, half, nEdge, k, i, j, b;
+   htkamd_frontend_config f;
+   memset(&f, 0, sizeof(f));
+   f.base = *c; f.baseKind = 6;
+   return htkamd_frontend_tables_build(&f, t);
+}
+
+int htkamd_frontend_tables_build(const htkamd_frontend_config *fc, struct htkamd_mfcc_tables *t)
+{
+   const htkamd_mfcc_config *c = &fc->base;
+   /* cepstra (and the lifter) for MFCC and PLP, the DCT for MFCC alone; the filterbank kinds ignore NUMCEPS */
+   const int nCep = (fc->baseKind == 6 || fc->baseKind == 11) ? c->numCeps : 0, nDct = (fc->baseKind == 6) ? c->numCeps : 0;
+   int fftN = 2, half, nEdge, k, i, j, b, rc;
    float fres, melLo, melHi, *edge;
    memset(t, 0, sizeof(*t));
+   if ((rc = htkamd_frontend_check(fc)) != HTKAMD_OK) return rc;
    t->frSize = (int)(c->winDur / c->sampPeriod);
    t->frRate = (int)(c->frPeriod / c->sampPeriod);
-   if (t->frSize < 2 || t->frRate < 1 || c->numChans < 1 || c->numCeps < 1 || c->numCeps > 64 || c->numChans > 63) {
-      htkamd_set_error("mfcc: unsupported geometry (frSize %d frRate %d chans %d ceps %d)", t->frSize, t->frRate, c->numChans, c->numCeps);
-      return HTKAMD_EINVAL;
-   }
+   t->takeLogs = fc->baseKind == 6 || fc->baseKind == 7;
    while (t->frSize > fftN) fftN *= 2;
-   if (fftN < 8 || fftN > 4096) { htkamd_set_error("mfcc: FFT size %d outside 8..4096", fftN); return HTKAMD_EINVAL; }
    t->fftN = fftN; half = fftN / 2;
    /* ---- mel filterbank (InitFBank HSigP.c:471-555 supplies the numbers; the tables are this file's own form).
       Band of interest: FFT bins klo..khi, mel range melLo..melHi, optionally narrowed by LOFREQ / HIFREQ. */
@@ -109,20 +171,42 @@ int htkamd_mfcc_tables_build(const htkamd_mfcc_config *c, struct htkamd_mfcc_tab
          if (lo < c->numChans) { if (t->binA1[lo + 1] < t->binA0[lo + 1]) t->binA0[lo + 1] = k; t->binA1[lo + 1] = k; }
       }
    }
+   if (fc->baseKind == 11) {
+      /* equal-loudness curve at the centre of filter b (edge[b] is the reference's cf[b]): the centre back to Hz with exp in double,
+         then the curve in float, its two ratios formed in double as the reference's double constants make them */
+      const int nFreq = c->numChans + 2;
+      double angle;
+      t->eql = (float *)calloc((size_t)c->numChans + 1, sizeof(float));
+      for (b = 1; b <= c->numChans; b++) {
+         const float hz = (float)(700.0 * (exp((double)(edge[b] / 1127.0f)) - 1.0));
+         const float sq = hz * hz;
+         const float sub = (float)((double)sq / ((double)sq + 1.6e5));
+         t->eql[b] = (float)((double)(sub * sub) * (((double)sq + 1.44e6) / ((double)sq + 9.61e6)));
+      }
+      /* IDFT from the numChans + 2 auditory-spectrum points to lpcOrder + 1 autocorrelation lags: row i = lag i, weights 1, 2 cos, .., cos */
+      angle = HTK_PI / (double)(nFreq - 1);
+      t->cm = (double *)calloc((size_t)(fc->lpcOrder + 1) * nFreq, sizeof(double));
+      for (i = 0; i <= fc->lpcOrder; i++) {
+         double *row = t->cm + (size_t)i * nFreq;
+         row[0] = 1.0;
+         for (j = 1; j < nFreq - 1; j++) row[j] = 2.0 * cos(angle * (double)i * (double)j);
+         row[nFreq - 1] = cos(angle * (double)i * (double)(nFreq - 1));
+      }
+   }
    free(edge);
    t->ham = (float *)calloc((size_t)t->frSize + 1, sizeof(float));
    { const float a = HTK_TPI / (t->frSize - 1); for (i = 1; i <= t->frSize; i++) t->ham[i] = 0.54 - 0.46 * cos(a * (i - 1)); }
-   t->cepWin = (float *)calloc((size_t)c->numCeps + 1, sizeof(float));
-   for (i = 1; i <= c->numCeps; i++) t->cepWin[i] = 1.0f;
+   t->cepWin = (float *)calloc((size_t)nCep + 1, sizeof(float));
+   for (i = 1; i <= nCep; i++) t->cepWin[i] = 1.0f;
    if (c->cepLifter > 0) {
       const float a = HTK_PI / c->cepLifter, Lby2 = c->cepLifter / 2.0;
-      for (i = 1; i <= c->numCeps; i++) t->cepWin[i] = 1.0 + Lby2 * sin(i * a);
+      for (i = 1; i <= nCep; i++) t->cepWin[i] = 1.0 + Lby2 * sin(i * a);
    }
    t->mfnorm = sqrt(2.0 / (float)c->numChans);
-   t->dct = (double *)calloc((size_t)(c->numCeps + 1) * (c->numChans + 1), sizeof(double));
+   t->dct = (double *)calloc((size_t)(nDct + 1) * (c->numChans + 1), sizeof(double));
    {
       const float pi_factor = HTK_PI / (float)c->numChans;
-      for (j = 1; j <= c->numCeps; j++) {
+      for (j = 1; j <= nDct; j++) {
          const float x = (float)j * pi_factor;
          for (k = 1; k <= c->numChans; k++) t->dct[(size_t)j * (c->numChans + 1) + k] = cos(x * (k - 0.5));
       }

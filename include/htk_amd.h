@@ -846,6 +846,31 @@ void htkamd_parm_stream_close(htkamd_parm_stream *s);
 int  htkamd_compv(const float *dX, long long nFrames, int D, float minVar, float *mean /*[D]*/, float *var /*[D]*/, void *stream);
 int  htkamd_mfcc_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Waveform -> MFCC, FBANK, MELSPEC or PLP (+_0/_E)(+_D)(+_A)(+_Z) on the device: the FFT front ends of ConvertFrame
+ * (HParm.c:2214).  The window, FFT and mel bins are the MFCC path's; after the bins
+ *   FBANK   : log with floor 1.0 (Wave2FBank HSigP.c:598-603), the numChans bins are the statics;
+ *   MELSPEC : the linear bins (InitFBank with takeLogs = FALSE);
+ *   PLP     : FBank2ASpec :693 (equal-loudness curve, cube-root compression), MatrixIDFT :710, Durbin :167,
+ *             LPC2Cepstrum :262, C0 = the LPC gain (ASpec2LPCep :735), WeightCepstrum, CEPSCALE.
+ * Columns: c1..cN (or the N bins) [C0] [E] [deltas] [accs].  baseKind = 6 gives the bits htkamd_mfcc_compute gives.
+ * Refused (HTKAMD_EINVAL and the reason, before any device is touched): base kinds other than 6 / 7 / 8 / 11 (the LPC kinds among
+ * them), _0 on FBANK / MELSPEC, and for PLP lpcOrder outside 2..1000, numCeps outside 2..lpcOrder or compressFact outside (0, 1)
+ * (ValidCodeParms HParm.c:1317).  Argument conventions of create / num_frames / compute are those of htkamd_mfcc_*.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+   htkamd_mfcc_config base;    /* every HParm variable the MFCC path has; hasC0 / hasE / hasD / hasA / hasZ as there */
+   int   baseKind;             /* HTK base code of TARGETKIND: 6 MFCC, 7 FBANK, 8 MELSPEC, 11 PLP */
+   int   lpcOrder;             /* LPCORDER (12) */
+   float compressFact;         /* COMPRESSFACT (0.33) */
+} htkamd_frontend_config;
+typedef struct htkamd_frontend htkamd_frontend;
+int  htkamd_frontend_create(const htkamd_frontend_config *cfg, htkamd_frontend **out);
+void htkamd_frontend_destroy(htkamd_frontend *f);
+int  htkamd_frontend_num_frames(const htkamd_frontend_config *cfg, int nSamples);
+int  htkamd_frontend_num_cols(const htkamd_frontend_config *cfg);      /* < 0 and the error string set on a refused config */
+int  htkamd_frontend_compute(htkamd_frontend *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

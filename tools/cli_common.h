@@ -116,15 +116,32 @@ typedef struct {
 
 static double cfg_flt(const config *c, const char *key, double dflt) { const char *v = cfg_get(c, key); return v ? atof(v) : dflt; }
 
+static int waveform_source(const config *cfg)
+{
+   const char *sfmt = cfg_get(cfg, "SOURCEFORMAT"), *skind = cfg_get(cfg, "SOURCEKIND");
+   return (sfmt && !strcasecmp(sfmt, "WAV")) || (skind && !strcasecmp(skind, "WAVEFORM"));
+}
+
+/* the base kinds a waveform is coded as on the device; the drivers call this before they touch a device */
+static void check_waveform_kind(int targetKind)
+{
+   const int base = targetKind < 0 ? -1 : (targetKind & 077);
+   if (base >= 1 && base <= 3)
+      DIE("waveform sources: TARGETKIND %s is a time-domain LPC kind, which is not coded on the device (MFCC, FBANK, MELSPEC or PLP)", pk_base[base]);
+   if (base != 6 && base != 7 && base != 8 && base != 11)
+      DIE("waveform sources are coded as MFCC, FBANK, MELSPEC or PLP: TARGETKIND = <kind>[_0][_E][_D][_A][_T][_Z][_N] expected");
+}
+
 /* Waveform sources (SOURCEFORMAT = WAV, or SOURCEKIND = WAVEFORM with HTK waveform files): the files of the batch are coded on the
-   device as OpenBuffer does for a waveform file (htkamd_mfcc_compute: statics + _0 / _E with HParm's configuration variables and
-   their defaults, HParm.c:337-367); the differentials, _Z and _N of TARGETKIND follow in load_observations as for parameter files.
-   Returns the parameter kind of the table (MFCC + _0 / _E). */
+   device as OpenBuffer does for a waveform file (htkamd_frontend_compute: statics + _0 / _E of TARGETKIND's base kind -- MFCC, FBANK,
+   MELSPEC or PLP -- with HParm's configuration variables and their defaults, HParm.c:337-367); the differentials, _Z and _N of
+   TARGETKIND follow in load_observations as for parameter files.  Returns the parameter kind of the table (base kind + _0 / _E). */
 static int code_waveforms(const strlist *files, int first, int count, int targetKind, const config *cfg, obs_batch *ob, float **dStatOut, int *nStatOut)
 {
    const char *sfmt = cfg_get(cfg, "SOURCEFORMAT");
    const int fmt = (sfmt && !strcasecmp(sfmt, "WAV")) ? HTKAMD_WAVE_WAV : HTKAMD_WAVE_HTK;
-   if (targetKind < 0 || (targetKind & 077) != 6) DIE("waveform sources are coded as MFCC: TARGETKIND = MFCC[_0][_E][_D][_A][_T][_Z][_N] expected");
+   check_waveform_kind(targetKind);
+   const int base = targetKind & 077;
    short *all = NULL; size_t cap = 0;
    int *sampOff = (int *)calloc((size_t)count + 1, sizeof(int));
    double period = cfg_flt(cfg, "SOURCERATE", 0.0);
@@ -138,29 +155,32 @@ static int code_waveforms(const strlist *files, int first, int count, int target
       sampOff[u + 1] = sampOff[u] + (int)n;
       htkamd_free(x);
    }
-   htkamd_mfcc_config mc; memset(&mc, 0, sizeof(mc));
-   mc.sampPeriod = period; mc.winDur = cfg_flt(cfg, "WINDOWSIZE", 256000.0); mc.frPeriod = cfg_flt(cfg, "TARGETRATE", 100000.0);
-   mc.numChans = cfg_int(cfg, "NUMCHANS", 20); mc.numCeps = cfg_int(cfg, "NUMCEPS", 12); mc.cepLifter = cfg_int(cfg, "CEPLIFTER", 22);
-   mc.preEmph = (float)cfg_flt(cfg, "PREEMCOEF", 0.97); mc.useHam = cfg_bool(cfg, "USEHAMMING", 1); mc.usePower = cfg_bool(cfg, "USEPOWER", 0);
-   mc.zMeanSource = cfg_bool(cfg, "ZMEANSOURCE", 0); mc.rawEnergy = cfg_bool(cfg, "RAWENERGY", 1); mc.eNormalise = cfg_bool(cfg, "ENORMALISE", 1);
-   mc.loFreq = (float)cfg_flt(cfg, "LOFREQ", -1.0); mc.hiFreq = (float)cfg_flt(cfg, "HIFREQ", -1.0); mc.cepScale = (float)cfg_flt(cfg, "CEPSCALE", 1.0);
-   mc.silFloor = (float)cfg_flt(cfg, "SILFLOOR", 50.0); mc.eScale = (float)cfg_flt(cfg, "ESCALE", 0.1);
-   mc.hasC0 = (targetKind & PK_HASZEROC) != 0; mc.hasE = (targetKind & PK_HASENERGY) != 0;
-   mc.delWin = 2; mc.accWin = 2;
-   htkamd_mfcc *fe; CHECK(htkamd_mfcc_create(&mc, &fe));
+   htkamd_frontend_config fc; memset(&fc, 0, sizeof(fc));
+   htkamd_mfcc_config *const m = &fc.base;
+   fc.baseKind = base; fc.lpcOrder = cfg_int(cfg, "LPCORDER", 12); fc.compressFact = (float)cfg_flt(cfg, "COMPRESSFACT", 0.33);
+   m->sampPeriod = period; m->winDur = cfg_flt(cfg, "WINDOWSIZE", 256000.0); m->frPeriod = cfg_flt(cfg, "TARGETRATE", 100000.0);
+   m->numChans = cfg_int(cfg, "NUMCHANS", 20); m->numCeps = cfg_int(cfg, "NUMCEPS", 12); m->cepLifter = cfg_int(cfg, "CEPLIFTER", 22);
+   m->preEmph = (float)cfg_flt(cfg, "PREEMCOEF", 0.97); m->useHam = cfg_bool(cfg, "USEHAMMING", 1); m->usePower = cfg_bool(cfg, "USEPOWER", 0);
+   m->zMeanSource = cfg_bool(cfg, "ZMEANSOURCE", 0); m->rawEnergy = cfg_bool(cfg, "RAWENERGY", 1); m->eNormalise = cfg_bool(cfg, "ENORMALISE", 1);
+   m->loFreq = (float)cfg_flt(cfg, "LOFREQ", -1.0); m->hiFreq = (float)cfg_flt(cfg, "HIFREQ", -1.0); m->cepScale = (float)cfg_flt(cfg, "CEPSCALE", 1.0);
+   m->silFloor = (float)cfg_flt(cfg, "SILFLOOR", 50.0); m->eScale = (float)cfg_flt(cfg, "ESCALE", 0.1);
+   m->hasC0 = (targetKind & PK_HASZEROC) != 0; m->hasE = (targetKind & PK_HASENERGY) != 0;
+   m->delWin = 2; m->accWin = 2;
+   const int cols = htkamd_frontend_num_cols(&fc);
+   if (cols < 0) DIE("waveform sources: %s", htkamd_last_error());
+   htkamd_frontend *fe; CHECK(htkamd_frontend_create(&fc, &fe));
    int F = 0;
-   for (int u = 0; u < count; u++) F += htkamd_mfcc_num_frames(&mc, sampOff[u + 1] - sampOff[u]);
-   const int cols = htkamd_mfcc_num_cols(&mc);
+   for (int u = 0; u < count; u++) F += htkamd_frontend_num_frames(&fc, sampOff[u + 1] - sampOff[u]);
    short *dWav; float *dStat;
    CHECK(htkamd_dev_malloc((void **)&dWav, sizeof(short) * (size_t)(sampOff[count] ? sampOff[count] : 1)));
    CHECK(htkamd_memcpy_h2d(dWav, all, sizeof(short) * (size_t)sampOff[count], NULL));
    CHECK(htkamd_dev_malloc((void **)&dStat, sizeof(float) * (size_t)(F ? F : 1) * cols));
-   CHECK(htkamd_mfcc_compute(fe, dWav, sampOff, count, ob->frameOff, dStat, NULL));
+   CHECK(htkamd_frontend_compute(fe, dWav, sampOff, count, ob->frameOff, dStat, NULL));
    CHECK(htkamd_stream_sync(NULL));
-   CHECK(htkamd_dev_free(dWav)); htkamd_mfcc_destroy(fe); free(all); free(sampOff);
-   ob->period = (int)(mc.frPeriod + 0.5);
+   CHECK(htkamd_dev_free(dWav)); htkamd_frontend_destroy(fe); free(all); free(sampOff);
+   ob->period = (int)(m->frPeriod + 0.5);
    *dStatOut = dStat; *nStatOut = cols;
-   return 6 | (mc.hasC0 ? PK_HASZEROC : 0) | (mc.hasE ? PK_HASENERGY : 0);
+   return base | (m->hasC0 ? PK_HASZEROC : 0) | (m->hasE ? PK_HASENERGY : 0);
 }
 
 static void load_observations(const strlist *files, int first, int count, int targetKind, const config *cfg, obs_batch *ob)
@@ -169,8 +189,7 @@ static void load_observations(const strlist *files, int first, int count, int ta
    int nStat = 0, fileKind = -1;
    float *dStat = NULL;
    ob->nUtt = count; ob->frameOff = (int *)calloc((size_t)count + 1, sizeof(int)); ob->period = 100000;
-   const char *sfmtL = cfg_get(cfg, "SOURCEFORMAT"), *skindL = cfg_get(cfg, "SOURCEKIND");
-   const int waveform = (sfmtL && !strcasecmp(sfmtL, "WAV")) || (skindL && !strcasecmp(skindL, "WAVEFORM"));
+   const int waveform = waveform_source(cfg);
    if (waveform) fileKind = code_waveforms(files, first, count, targetKind, cfg, ob, &dStat, &nStat);
    else
    for (int u = 0; u < count; u++) {
