@@ -22,26 +22,6 @@ ARCH = "gfx950"
 # the tolerance-class scoring kernel never sees NaNs: lets v_max_f32 go without the IEEE canonicalisation of its operands
 EXTRA_FLAGS = {"csrc/gmm_mfma.hip": ["-fno-honor-nans"], "csrc/gmm_bf16.hip": ["-fno-honor-nans"], "csrc/gmm_f16.hip": ["-fno-honor-nans"],
                "csrc/fb_kernels.hip": ["-Wno-pass-failed"]}      # (k_mixstate asks for an occupancy it knows it cannot have: MS_EU in fb_kernels.hip)
-if os.environ.get("HTKAMD_LR_DEFS"):               # experiment switches of fb_lr.hip, e.g. HTKAMD_LR_DEFS="-DSTATS_EXP_NOOCC"
-    EXTRA_FLAGS["csrc/fb_lr.hip"] = os.environ["HTKAMD_LR_DEFS"].split()
-    EXTRA_FLAGS["csrc/fb_kernels.hip"] = EXTRA_FLAGS["csrc/fb_kernels.hip"] + os.environ["HTKAMD_LR_DEFS"].split()
-if os.environ.get("HTKAMD_DEC_DEFS"):              # ... and decode.hip (-DDEC_CLK: phase stamps)
-    EXTRA_FLAGS["csrc/decode.hip"] = os.environ["HTKAMD_DEC_DEFS"].split()
-if os.environ.get("HTKAMD_EX_DEFS"):               # ... and gmm_exact.hip
-    EXTRA_FLAGS["csrc/gmm_exact.hip"] = os.environ["HTKAMD_EX_DEFS"].split()
-if os.environ.get("HTKAMD_MFCC_DEFS"):             # ... and mfcc.hip
-    EXTRA_FLAGS["csrc/mfcc.hip"] = os.environ["HTKAMD_MFCC_DEFS"].split()
-if os.environ.get("HTKAMD_UPD_DEFS"):              # the same for update.hip / gmm_bf16.hip (tools/r05_updvar.sh)
-    EXTRA_FLAGS["csrc/update.hip"] = os.environ["HTKAMD_UPD_DEFS"].split()
-if os.environ.get("HTKAMD_B16_CT"):              # experiment switch: column tiles per wavefront of the bf16 scoring kernel (gmm_bf16.hip: B16_COL_TILES)
-    EXTRA_FLAGS["csrc/gmm_bf16.hip"] = EXTRA_FLAGS["csrc/gmm_bf16.hip"] + ["-DB16_COL_TILES=" + os.environ["HTKAMD_B16_CT"]]
-if os.environ.get("HTKAMD_B16_TF"):              # experiment switch: frames per task of the bf16 scoring kernel in forward-backward (kernels.h: B16_TASK_FRAMES)
-    EXTRA_FLAGS["csrc/gmm_bf16.hip"] = EXTRA_FLAGS["csrc/gmm_bf16.hip"] + ["-DB16_TASK_FRAMES=" + os.environ["HTKAMD_B16_TF"]]
-    EXTRA_FLAGS["csrc/fb.hip"] = ["-DB16_TASK_FRAMES=" + os.environ["HTKAMD_B16_TF"]]
-if os.environ.get("HTKAMD_B16_DEFS"):            # experiment switches of gmm_bf16.hip, e.g. HTKAMD_B16_DEFS="-DB16W_EU5=3"
-    EXTRA_FLAGS["csrc/gmm_bf16.hip"] = EXTRA_FLAGS["csrc/gmm_bf16.hip"] + os.environ["HTKAMD_B16_DEFS"].split()
-if os.environ.get("HTKAMD_B16_WPB"):             # experiment switch: wavefronts per workgroup of the bf16 scoring kernel (gmm_bf16.hip: B16_WPB)
-    EXTRA_FLAGS["csrc/gmm_bf16.hip"] = EXTRA_FLAGS["csrc/gmm_bf16.hip"] + ["-DB16_WPB=" + os.environ["HTKAMD_B16_WPB"]]
 
 
 def _newer(target, deps):

@@ -52,7 +52,7 @@ __device__ __forceinline__ void pull_fold(PullAcc &p, const DecArgs &a, const To
 }
 // The list is walked four predecessors at a time: their link words first, then their tokens, then the comparisons in list order.  One by
 // one, each token's load waited for its link's load and the next link for the comparison before it: two memory latencies per predecessor,
-// 68 % of k_decode's cycles on the 6 000-word bigram network (tools/dec_diag.py with -DDEC_CLK).
+// 68 % of k_decode's cycles on the 6 000-word bigram network (phase cycle stamps of a diagnostic build, retired: git show e507b6e:htk_amd/csrc/decode.hip).
 // EXL: predecessors with a copy in LDS (DecNet::zl) are taken from there: wl the WORD nodes' likelihoods, nullL the null nodes' tokens, tNW = frame * nWordNodes
 template <bool EXL = false>
 __device__ __forceinline__ Tok pull_range(const DecArgs &a, const Tok *ex, int k0, int k1, int kstep, float gT, float wT, int *argk, bool *tie,
@@ -110,12 +110,6 @@ __device__ __forceinline__ double block_max(double v, double *red)
 }
 
 #define DEC_LDS_TP 4096            /* floats of transition matrices cached in LDS (all of them, else global memory) */
-#ifdef DEC_NEED                    /* diagnostic build: distinct tied states whose score a live token asked for, per frame (tools/dec_diag.py) */
-__shared__ unsigned int needB[256];            // (up to 8 192 score slots)
-#define DEC_NEED_MARK(slot_) atomicOr(&needB[((slot_) >> 5) & 255], 1u << ((slot_) & 31))
-#else
-#define DEC_NEED_MARK(slot_) do { } while (0)
-#endif
 
 // StepHMM1 (HRec.c:642) on one model instance: s[1 .. NS-1] = the state tokens on entry (s[1] the entry token) and the new ones on
 // return (s[1] null: the entry is consumed); exT = the exit token, mx = the instance's maximum, wordTop raised by exit + LikeToWord.
@@ -143,7 +137,6 @@ __device__ __forceinline__ void hmm_step1(const DecArgs &a, const DecUtt &ud, co
             best.like = bl;
             if (best.like > gT) {
                best.like += __builtin_nontemporal_load(a.score + ud.score0 + (size_t)(t - 1) * a.ns + slj[j - 2]);
-               DEC_NEED_MARK(slj[j - 2]);
                nw[j] = best;
                if (best.like > mx) mx = best.like;
             }
@@ -186,7 +179,6 @@ __device__ __forceinline__ void hmm_step1(const DecArgs &a, const DecUtt &ud, co
             if constexpr (SLOTS) slot = (j == 2) ? sl2 : (j == 3) ? sl3 : sl4;      // (the register-resident models carry their score slots)
             else slot = N.stateSlot[N.hmmState[ni.w + (j - 2)]];
             best.like += __builtin_nontemporal_load(a.score + ud.score0 + (size_t)(t - 1) * a.ns + slot);      // (a frame's column is read once)
-            DEC_NEED_MARK(slot);
             nw[j] = best;
             if (best.like > mx) mx = best.like;
          }
@@ -251,9 +243,6 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
    __shared__ float thr[2];
    __shared__ float ltpS[EXL ? 1 : DEC_LDS_TP];    // (EXL: the matrices behind the dynamic block, as many floats as there are)
    __shared__ Tok nullL[EXL ? DEC_NULL_LDS : 1];
-#ifdef DEC_NEED
-   unsigned long long needSum = 0;
-#endif
    __shared__ int uhist[256];
    __shared__ unsigned int usel[4];            // -u: [0] attached instances, [1] key prefix, [2] rank still to skip, [3] scratch
    const int u = blockIdx.x, tid = threadIdx.x;
@@ -285,12 +274,6 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
    const float *tpBase = tpInLds ? ltp : N.transP;
    bool tie = false;                           // this thread met two equally likely tokens with different histories (pull_range)
    unsigned int nLive = 0, nDead = 0;          // this thread's register-resident model steps with / without a live token
-#ifdef DEC_CLK                                 // cycle stamps of thread 0 at the phase boundaries (tools/dec_diag.py): prune | models | beam tops | fused words | levels | entries
-   unsigned long long clk[6] = {0, 0, 0, 0, 0, 0}, c0 = 0;
-#define DEC_STAMP(i_) do { const unsigned long long c_ = __builtin_readcyclecounter(); clk[i_] += c_ - c0; c0 = c_; } while (0)
-#else
-#define DEC_STAMP(i_) do { } while (0)
-#endif
    const int nReg = (NPT > 0) ? N.nReg : 0;    // model nodes hmmNodes[0 .. nReg) live in registers
    // this thread's register-resident models: rs[k][0 ..] = the tokens of states 2 .. ; the entry token (the exit token between the
    // passes) of its k-th model waits in LDS, xs[k NTHR + tid] (registers for it too made the compiler spill at 12 models per thread)
@@ -313,9 +296,6 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
    if (tid == 0) { thr[0] = (float)LSMALL; thr[1] = (float)LSMALL; }
    __syncthreads();
 
-#ifdef DEC_CLK
-   c0 = __builtin_readcyclecounter();
-#endif
    for (int t = 0; t <= T; t++) {
       if (t >= 1 && a.maxActive > 0) {
          // ---- maximum-model pruning (ProcessObservation HRec.c:1966-1985): when more than maxActive instances are attached, those
@@ -386,11 +366,6 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
             __syncthreads();
          }
       }
-      DEC_STAMP(0);
-#ifdef DEC_NEED                                         /* -DDEC_NEED=1: per frame; -DDEC_NEED=16: the union over blocks of 16 frames (what ANY block-wise scheme has to score at least) */
-      if ((t - 1) % (DEC_NEED + 0 > 0 ? DEC_NEED + 0 : 1) == 0 || t < 1) { if (tid < 256) needB[tid] = 0; }
-      __syncthreads();
-#endif
       if (t >= 1) {
          const float gT = thr[0];                         // threshold of the previous frame
          double myGen = LZERO, myWord = LZERO;
@@ -465,7 +440,6 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
             }
             ex[n] = exT; imax[n] = (double)(float)mx;         // inst->max is a LogFloat (HRec.c:138)
          }
-         DEC_STAMP(1);
          double genMax = myGen, wordMax = myWord;
          block_max2<NTHR>(genMax, wordMax, red, red2);
          if (tid == 0) {
@@ -475,18 +449,6 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
          }
          __syncthreads();
       }
-#ifdef DEC_NEED
-      __syncthreads();
-      if (t >= 1 && tid < 64 && (t % (DEC_NEED + 0 > 0 ? DEC_NEED + 0 : 1) == 0 || t == ud.T)) {      /* at the end of a block: its distinct states x its frames */
-         unsigned int c = 0;
-         for (int i = tid; i < 256; i += 64) c += __popc(needB[i]);
-#pragma unroll
-         for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-         const int blk = (DEC_NEED + 0 > 0 ? DEC_NEED + 0 : 1);
-         needSum += (unsigned long long)c * (unsigned long long)(t % blk == 0 ? blk : t % blk);
-      }
-#endif
-      DEC_STAMP(2);
       // ---- zero-time nodes, level by level (at t = 0: StartRecognition's propagation of the initial token)
       const float gT = thr[0], wT = thr[1];
       if constexpr (NPT > 0) {
@@ -527,7 +489,6 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
             }
          }
       }
-      DEC_STAMP(3);
       for (int L = 0; L < N.nLevels; L++) {
          const int l0 = N.levelOff[L], lw = N.levelWide[L], l1 = N.levelOff[L + 1];
          for (int k = l0 + tid; k < lw; k += NTHR) {
@@ -590,7 +551,6 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
          }
          __syncthreads();
       }
-      DEC_STAMP(4);
       // ---- entry tokens of the emitting models for the next frame (SetEntryState from this frame's exits)
       if (t < T) {
          if constexpr (NPT > 0) {
@@ -670,15 +630,8 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
          }
          __syncthreads();
       }
-      DEC_STAMP(5);
    }
 
-#ifdef DEC_CLK
-   if (tid == 0 && a.liveCnt) for (int i = 0; i < 6; i++) atomicAdd(a.liveCnt + 2 * a.nUtt + i, clk[i]);
-#endif
-#ifdef DEC_NEED
-   if (tid == 0 && a.liveCnt) atomicAdd(a.liveCnt + 2 * a.nUtt + 6, needSum);
-#endif
    if (tie) a.tieFlag[u] = 1;                  // (zeroed by the host before the launch)
    if (NPT > 0 && a.liveCnt) {
       unsigned long long l = nLive, dd = nDead;
@@ -946,8 +899,6 @@ extern "C" int htkamd_decoder_create(htkamd_model *m, const htkamd_net_desc *nd,
       }
    }
    levelOff[nLevels] = (int)levelNodes.size();
-   if (getenv("HTKAMD_DECODE_VERBOSE"))
-      for (int L = 0; L < nLevels; L++) fprintf(stderr, "decoder_create: level %d: %d narrow + %d wide zero-time nodes (register models %d, fused nodes %d)\n", L, levelWide[L] - levelOff[L], levelOff[L + 1] - levelWide[L], nReg, (int)std::count(isFused.begin(), isFused.end(), 1));
    // ... and the same lists with every zero-time node in them, for the kernels that keep no tokens in registers (k_decode_n)
    std::vector<int> levelOffA(nLevels + 1, 0), levelWideA(nLevels, 0), levelNodesA;
    for (int L = 0; L < nLevels; L++) {
@@ -1156,7 +1107,7 @@ extern "C" int htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_con
       A(&dOutD, sizeof(double) * (size_t)nu * maxWords);
       void *dTie = nullptr;
       const size_t tieBytes = (sizeof(int) * nu + 7) & ~(size_t)7;
-      A(&dTie, tieBytes + sizeof(unsigned long long) * (2 * (size_t)nu + 8));
+      A(&dTie, tieBytes + sizeof(unsigned long long) * (2 * (size_t)nu));
       std::vector<int> hI; std::vector<float> hF; std::vector<double> hT, hD;
       if (!rc) {
          hipError_t e;
@@ -1199,7 +1150,7 @@ extern "C" int htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_con
          a.wordLike = (double *)dOutD;
          a.tieFlag = (int *)dTie;
          a.liveCnt = (unsigned long long *)((char *)dTie + tieBytes);
-         (void)hipMemsetAsync(dTie, 0, tieBytes + sizeof(unsigned long long) * (2 * (size_t)nu + 8), s);
+         (void)hipMemsetAsync(dTie, 0, tieBytes + sizeof(unsigned long long) * (2 * (size_t)nu), s);
          // tokens of the plain models in registers where the network has such models (DecNet::nReg), NPT of them per thread
          const int npt = (N.nReg + DEC_REG_THREADS - 1) / DEC_REG_THREADS;
          const bool hasG = N.nReg < N.nHmm;
@@ -1265,7 +1216,7 @@ extern "C" int htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_con
             d->lastTied += nSel;
          }
       }
-      std::vector<unsigned long long> hLive(2 * (size_t)nu + 8, 0);
+      std::vector<unsigned long long> hLive(2 * (size_t)nu, 0);
       if (!rc) (void)hipMemcpyAsync(hLive.data(), (char *)dTie + tieBytes, sizeof(unsigned long long) * hLive.size(), hipMemcpyDeviceToHost, s);
       if (!rc) {
          hI.resize((size_t)nu * maxWords * 3 + nu); hF.resize((size_t)nu * maxWords * 3 + nu); hT.resize(nu); hD.resize((size_t)nu * maxWords);
@@ -1281,13 +1232,6 @@ extern "C" int htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_con
         if (hipEventElapsedTime(&ms, d->ev[0], d->ev[1]) == hipSuccess) d->lastScoreMs += ms;
         if (hipEventElapsedTime(&ms, d->ev[2], d->ev[3]) == hipSuccess) d->lastTokenMs += ms; }
       for (int k = 0; k < nu; k++) { d->lastLive[0] += (long long)hLive[2 * k]; d->lastLive[1] += (long long)hLive[2 * k + 1]; }
-#ifdef DEC_NEED
-      fprintf(stderr, "k_decode: %llu (frame, tied state) scores asked for by live tokens, of %d x %lld in the dense block\n", hLive[2 * (size_t)nu + 6], ns, (long long)(score / (ns ? ns : 1)));
-#endif
-#ifdef DEC_CLK
-      fprintf(stderr, "k_decode phase cycles (sum over %d utterances): prune %llu | models %llu | beam tops %llu | fused words %llu | levels %llu | entries %llu\n", nu,
-              hLive[2 * (size_t)nu], hLive[2 * (size_t)nu + 1], hLive[2 * (size_t)nu + 2], hLive[2 * (size_t)nu + 3], hLive[2 * (size_t)nu + 4], hLive[2 * (size_t)nu + 5]);
-#endif
       for (int k = 0; k < nu; k++) {
          nWords[u0 + k] = hI[k]; total[u0 + k] = hT[k];
          if (finalLm) finalLm[u0 + k] = hF[(size_t)nu * maxWords * 3 + k];

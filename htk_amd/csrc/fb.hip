@@ -8,7 +8,6 @@
 #include <algorithm>
 #include <vector>
 #include <thread>
-#include <chrono>
 #include <mutex>
 #include <condition_variable>
 #include <functional>
@@ -415,10 +414,6 @@ extern "C" int htkamd_fb_prepare(htkamd_fb *fb, const htkamd_batch_desc *b, void
    }
    // from here on a failure invalidates the context: execute / results / get_trellis then see an empty batch, never a mixture of two
    struct Invalidate { htkamd_fb *f; bool ok; ~Invalidate() { if (!ok) { f->nUtt = 0; f->timed = false; } } } guard{fb, false};
-   static const bool timing = getenv("HTKAMD_PREP_TIMING") != nullptr;
-   auto tp0 = std::chrono::steady_clock::now();
-   auto lap = [&](const char *what) { if (!timing) return; auto t = std::chrono::steady_clock::now();
-      fprintf(stderr, "  prepare %-10s %.3f ms\n", what, std::chrono::duration<double, std::milli>(t - tp0).count()); tp0 = t; };
    fb->nUtt = U; fb->dX = b->dX; fb->topoVersion = fb->m->topoVersion;
    fb->mixDeferred = false;                              // (statistics left waiting by htkamd_fb_execute_begin belong to the batch before)
    fb->utt.assign(U, UttDesc());
@@ -447,7 +442,6 @@ extern "C" int htkamd_fb_prepare(htkamd_fb *fb, const htkamd_batch_desc *b, void
       for (int u = u0; u < u1; u++)
          if ((C.rc = prep_utterance(fb, b, u, C))) return;
    });
-   lap("workers");
    for (int k = 0; k < nW; k++) if (chunks[k].rc) { htkamd_set_error("%s", chunks[k].err); return chunks[k].rc; }
    // concatenate the shares, rebasing their offsets
    // (the tables are NOT cleared first: resize() of an emptied vector writes zeros over every element the workers are about to fill)
@@ -495,7 +489,6 @@ extern "C" int htkamd_fb_prepare(htkamd_fb *fb, const htkamd_batch_desc *b, void
       });
    }
    fb->gamOff[U] = gam;
-   lap("merge:copy");
    {  // the wide tasks in eight queues, utterance u in queue u % 8 (the tasks lie in utterance order: one walk finds their utterances)
       std::vector<ScoreTask> q[8];
       int u = 0;
@@ -512,7 +505,6 @@ extern "C" int htkamd_fb_prepare(htkamd_fb *fb, const htkamd_batch_desc *b, void
       }
       fb->wqStart[8] = (int)at;
    }
-   lap("merge:queues");
    fb->outpTotal = outp; fb->betaTotal = beta; fb->gamTotal = gam;
    fb->blockDim = nThrMax;
    {  // classes: chains of <= 64 / 128 / 256 models of <= 5 states go to the wave kernels with 1 / 2 / 4 wavefronts, the rest to
@@ -560,7 +552,6 @@ extern "C" int htkamd_fb_prepare(htkamd_fb *fb, const htkamd_batch_desc *b, void
       }
    }
 
-   lap("merge:classes");
    fb->nextSame.clear();
    if (compat_revisit(fb->m)) {
       // per utterance: the chain states of one tied state sorted by (model ascending, state descending); a state's successor in that
@@ -583,7 +574,6 @@ extern "C" int htkamd_fb_prepare(htkamd_fb *fb, const htkamd_batch_desc *b, void
             if (fb->slotState[d.slot0 + ord[k]] == fb->slotState[d.slot0 + ord[k + 1]]) fb->nextSame[d.slot0 + ord[k]] = ord[k + 1];
       }
    }
-   lap("merge");
    int rc;
    {
       // all tables through one pinned staging buffer and ONE host-to-device copy
@@ -631,7 +621,6 @@ extern "C" int htkamd_fb_prepare(htkamd_fb *fb, const htkamd_batch_desc *b, void
       HIPCHECK(hipEventRecord(fb->evCopy, s));
       fb->copyPending = true;
    }
-   lap("stage+copy");
    // the wave-per-utterance kernels keep beta in their own state-major block (d_betaW, reserved in execute)
    const bool wavePathPrep = fb->clsOff[5] == fb->clsOff[4];          // no utterance needs the general kernels
    const size_t nf = fb->totalFrames ? fb->totalFrames : 1;
@@ -643,7 +632,6 @@ extern "C" int htkamd_fb_prepare(htkamd_fb *fb, const htkamd_batch_desc *b, void
        (fb->m->tiedMix && ((rc = fb->d_tmE.reserve(sizeof(float) * (nf * fb->m->tmPool + 16))) || (rc = fb->d_tmMaxP.reserve(sizeof(float) * (nf * fb->m->NSt + 16))))))
       return rc;
    if (fb->debug && (rc = fb->d_alpha.reserve(sizeof(double) * (beta ? beta : 1)))) return rc;
-   lap("reserve");
    // no synchronisation here: the copy is stream-ordered before the kernels of execute, and the staging buffer is
    // guarded by evCopy against being refilled while the copy is still in flight
    guard.ok = true;
@@ -729,7 +717,7 @@ static int fb_execute_impl(htkamd_fb *fb, const htkamd_fb_config *cfg, htkamd_ac
    sa.stateCompOff = m->d_stateCompOff; sa.compGauss = m->d_compGauss; sa.compLogWt = m->d_compLogWt;
    sa.gparam = m->d_gparam; sa.PS = m->PS; sa.D = m->D; sa.minLogExp = m->minLogExp;
    sa.laddTab = m->d_laddTab; sa.taskCounter = (int *)fb->d_counter.p;
-   if (wideTasks && m->NSt == 1 && fb->wqStart.size() == 9 && !getenv("HTKAMD_NO_XCDQ")) { sa.qStart = (const int *)fb->d_wqStart.p; sa.qCounters = (int *)fb->d_counter.p + 8; }
+   if (wideTasks && m->NSt == 1 && fb->wqStart.size() == 9) { sa.qStart = (const int *)fb->d_wqStart.p; sa.qCounters = (int *)fb->d_counter.p + 8; }
    if ((cfg->scoreMode & HTKAMD_SCORE_BF16) && !(cfg->scoreMode & HTKAMD_SCORE_F16) && m->NSt == 1 && !getenv("HTKAMD_NO_TAPER_SKIP")) sa.slotRange = (const int *)fb->d_slotRange.p;      // (the switch: for A/B measurements)
    sa.mfmaTab = m->d_mfmaTab; sa.stateTileOff = m->d_stateTileOff; sa.bf16Tab = m->d_bf16Tab; sa.var = m->d_var;
    fb->f16Pass = (cfg->scoreMode & HTKAMD_SCORE_F16) != 0 && !m->tiedMix && sa.nTasks > 0;      // no tasks, no launch: nothing zeroes or raises the flag
@@ -822,11 +810,9 @@ static int fb_execute_impl(htkamd_fb *fb, const htkamd_fb_config *cfg, htkamd_ac
       if (htkamd_beta_lr_is_lean(fa, fastLadd)) fa.qBeam = (int *)fb->d_qBeamNP.p;
       fb->qBeamLast = fa.qBeam;
       fb->mixStateLast = false;
-      { const char *e = getenv("HTKAMD_LR_EXP"); fa.lrExp = e ? atoi(e) : 0; }
       fa.fastMath = fastLadd ? 1 : 0;
       // mixture statistics bucketed by tied state (k_mixstate): the default list mode, one stream, the sparse statistics kernel counting
-      static const bool noMixState = getenv("HTKAMD_NO_MIXSTATE") != nullptr;
-      if (!noMixState && fb->recCapForce == 0 && !fa.hitSlots && m->maxM <= 16 && (m->D == 39 || m->D == 26 || m->D == 13) && htkamd_stats_lr_is_sparse(fa) &&
+      if (fb->recCapForce == 0 && !fa.hitSlots && m->maxM <= 16 && (m->D == 39 || m->D == 26 || m->D == 13) &&
           (cfg->uFlags & (HTKAMD_UPMEANS | HTKAMD_UPVARS | HTKAMD_UPMIXES))) {
          // room per state: eight times an even share of 2 pairs per frame, a power of two in [64, 65536], the lot within 1 GB
          size_t cap = 64;
@@ -838,10 +824,6 @@ static int fb_execute_impl(htkamd_fb *fb, const htkamd_fb_config *cfg, htkamd_ac
          fa.stCnt = (int *)fb->d_stCnt.p; fa.nTiedStates = m->S; fa.stBucket = (HitS *)fb->d_stBucket.p; fa.stCap = (int)cap;
          HIPCHECK(hipMemsetAsync(fa.stCnt, 0, sizeof(int) * (3 * (size_t)m->S + 4), s));  /* counts; pairs turned away (+3 spare); then per state: pairs, triples */
       }
-   }
-   {  // diagnostic (tools/r06_hosttrace.sh): n more tiny fills in the pass -- what ONE more dispatch costs an iteration on the box at hand
-      static const int extra = [] { const char *e = getenv("HTKAMD_EXTRA_FILLS"); return e ? atoi(e) : 0; }();
-      for (int i = 0; i < extra; i++) HIPCHECK(hipMemsetAsync(fb->d_counter.p, 0, 4, s));
    }
    static const int clsW[4] = {1, 2, 4, 8};
    // the longest chains first: their recursions are the critical path of the pass
@@ -884,7 +866,7 @@ static int fb_execute_impl(htkamd_fb *fb, const htkamd_fb_config *cfg, htkamd_ac
             return rc;
          fa.rec = (MixRec *)fb->d_rec.p; fa.recSorted = (MixRec *)fb->d_recSorted.p; fa.recCap = (int)cap; fa.G = m->G; fa.recCtl = (int *)fb->d_recCtl.p;
       }
-      // the dense seed array serves the utterances off the left-to-right path; those on it list their pairs (k_stats_lr -> k_mixhits)
+      // the dense seed array serves the utterances off the left-to-right path; those on it list their pairs (k_stats_sp -> k_mixhits)
       if (m->tiedMix) {
          fa.stateCompOff = m->d_stateCompOff; fa.rec = nullptr;
          if (fb->nUtt > nLr && (rc = htkamd_launch_mixstats_tm(fa, s))) return rc;

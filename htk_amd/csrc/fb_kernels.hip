@@ -790,7 +790,7 @@ __device__ __forceinline__ double uniform_f64(double v)
    return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
 }
 
-// k_mixhits: the pairs come as LISTS (fb_lr.hip: every wavefront of k_stats_lr owns a region of the list -- room for all its (frame,
+// k_mixhits: the pairs come as LISTS (fb_lr_lean.inc: every wavefront of k_stats_sp owns a region of the list -- room for all its (frame,
 // state) pairs, so nothing can overflow and no cursor is shared -- and leaves the number of 16-byte records it wrote in hitCtl):
 // ~20 MB instead of the 0.5 GB seed array written and read back at the bench workload
 template <int DT, int GS>
@@ -1019,25 +1019,13 @@ __global__ __launch_bounds__(256) void k_rec_reduce(FbArgs a)
 // the list), ONE wavefront takes ALL pairs of a state: parameters in registers once, the frames' rows through LDS 64 at a time, the
 // posteriors of a chunk in LDS, and then the same wavefront with lane = dimension sums mean / variance statistics of the state's
 // Gaussians in registers -- one atomic per accumulator element and state at the end, no record list.  UpMixParms HFB.c:1573-1721.
-#ifndef LR_EXP_BUILD
-#define LR_EXP_BUILD 0
-#endif
-#define MS_EXP(bit) (LR_EXP_BUILD && (a.lrExp & (bit)))      // ablations of a diagnostic build (tools/lr_exp.py): 256 no sums, 512 fp32 exp, 1024 no rows, 2048 no distances, 8192 no atomics
-#ifndef MS_EU
-#define MS_EU 8                  /* the launch bound's second figure: 1, 2, 4, 5, 6, 8 give the same 155-register kernel at 0.28-0.29 ms, 3 a 151-register one at 0.33 (tools/r05_var.sh) */
-#endif
+#define MS_EU 8                  /* the launch bound's second figure: 1, 2, 4, 5, 6, 8 give the same 155-register kernel at 0.28-0.29 ms, 3 a 151-register one at 0.33 */
 template <int DT, int MODE>      // MODE: 3 means and variances (HFB.c:1673-1678), 1 means only (:1697), 2 variances only (:1706), 0 weights only
 __global__ __launch_bounds__(64, MS_EU) void k_mixstate(FbArgs a)
 {
-#ifndef MS_CHUNK
 #define MS_CHUNK 32
-#endif
-#ifndef MS_CAP
-#define MS_CAP 128               /* pairs per part of a state: 64 / 96 / 128 / 256 give 0.255 / 0.237 / 0.239 / 0.242 ms against 0.285 for whole states (tools/r05_var.sh) */
-#endif
-#ifndef MS_PARTS
+#define MS_CAP 128               /* pairs per part of a state: 64 / 96 / 128 / 256 give 0.255 / 0.237 / 0.239 / 0.242 ms against 0.285 for whole states */
 #define MS_PARTS 4
-#endif
    constexpr int GS = 16, HPS = 64 / GS, NQ = (DT + 1) / 2, XS = (DT + 3) & ~3;      // XS: floats per row in LDS (16-byte multiple)
    constexpr int CH = MS_CHUNK;                          // pairs per chunk: 14 KB of LDS at 32 (11 workgroups per CU), 24 KB at 64 (6)
    __shared__ float xs[CH * XS];
@@ -1097,7 +1085,7 @@ __global__ __launch_bounds__(64, MS_EU) void k_mixstate(FbArgs a)
       // (round 6: the next chunk's rows requested while this chunk is worked on -- two halves of `xs`, the entries a chunk further ahead -- measured:
       //  0.235 ms at 16 pairs per chunk against 0.239 without at 32; the second half's LDS costs the occupancy what the overlap gains.  Not kept.)
       for (int r = 0; r < n; r++) {
-         const int fr = MS_EXP(1024) ? 0 : __builtin_amdgcn_readlane(hfr, r);
+         const int fr = __builtin_amdgcn_readlane(hfr, r);
          if (lane < DT)
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.X + (size_t)fr * DT + lane),
                                              (__attribute__((address_space(3))) void *)(xs + r * XS), 4, 0, 0);
@@ -1117,7 +1105,6 @@ __global__ __launch_bounds__(64, MS_EU) void k_mixstate(FbArgs a)
                typedef float v2f __attribute__((ext_vector_type(2)));
                const v2f *xr = (const v2f *)(xs + h * XS);
                float sum = gcst;
-               if (!MS_EXP(2048))
 #pragma unroll
                for (int q = 0; q < NQ; q++) {                // the reference's sum, a dimension after the other (HModel.c:5420-5431); the products two at a time
                   const float4 pv = pl[q][sub];
@@ -1129,7 +1116,7 @@ __global__ __launch_bounds__(64, MS_EU) void k_mixstate(FbArgs a)
                   sum += tt[0];
                   if (2 * q + 1 < DT) sum += tt[1];
                }
-               const float prob = MS_EXP(2048) ? -1.0e30f : -0.5f * sum;
+               const float prob = -0.5f * sum;
                const double x = (seed + (double)wt) + (double)prob;
                if (-x < minF) { pass = true; Lr = a.fastMath ? (double)__builtin_amdgcn_exp2f((float)x * 1.44269504088896341f) : exp(x); }
             }
@@ -1140,7 +1127,7 @@ __global__ __launch_bounds__(64, MS_EU) void k_mixstate(FbArgs a)
       }
       __syncthreads();
       // ---- first- and second-order sums of the chunk: lane = dimension, a Gaussian after the other, the pairs it survived in (HFB.c:1673-1709)
-      if ((upMu || upVa) && !MS_EXP(256)) {
+      if (upMu || upVa) {
          // (the sixteen ballots first, four LDS reads in flight at a time: read Gaussian by Gaussian, every one was waited for on its own)
          unsigned long long bmAll[GS];
 #pragma unroll
@@ -1184,7 +1171,6 @@ __global__ __launch_bounds__(64, MS_EU) void k_mixstate(FbArgs a)
       }
    }
    // ---- out: one atomic per accumulator element of the state's Gaussians, component, and the state
-   if (MS_EXP(8192)) return;                             // (diagnostic: without the atomics)
 #pragma unroll
    for (int m = 0; m < GS; m++) {
       if (m < M && lane < DT) {
@@ -1259,7 +1245,7 @@ int htkamd_launch_alpha(const FbArgs &a, int blockDim, size_t lds, hipStream_t s
 }
 
 // statistics of the surviving pairs: from the dense seed array (gamTotal seeds; the utterances off the left-to-right path) and / or from
-// the hit list of k_stats_lr (a.hits: nHitsMax > 0), then the per-Gaussian reduction of the records both of them listed
+// the hit list of k_stats_sp (a.hits: nHitsMax > 0), then the per-Gaussian reduction of the records both of them listed
 int htkamd_launch_mixstats(const FbArgs &a_in, hipStream_t s, bool dense, bool listed, bool deferState)
 {
    if (!dense && !listed) return HTKAMD_OK;
@@ -1458,7 +1444,7 @@ __global__ __launch_bounds__(256) void k_mixstats_ms(FbArgs a)
 }
 
 __device__ void tm_pair(const FbArgs &a, const UttDesc *up, const int t0, const int slot, const double seed, const int lane);
-// The same from the LISTS of k_stats_lr (left-to-right chains, round 4): a wavefront per region, a pair after the other.  A record of
+// The same from the LISTS of k_stats_sp (left-to-right chains, round 4): a wavefront per region, a pair after the other.  A record of
 // these sets carries the pair's GLOBAL slot (FbArgs::hitSlots) -- the statistics want the chain state's own stream scores -- and the
 // utterance is found from it (the slots of a batch ascend with the utterances).
 template <bool TIED>

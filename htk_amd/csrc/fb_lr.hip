@@ -1,4 +1,4 @@
-// fb_lr.hip -- K2r / K3r / K3x: beta pass, alpha pass and occupation statistics for LEFT-TO-RIGHT chains, one lane per chain state.
+// fb_lr.hip -- K2r / K3r: beta pass and alpha pass for LEFT-TO-RIGHT chains, one lane per chain state (the statistics: fb_lr_lean.inc).
 //
 // The everyday HMM set -- every model left-to-right without skips: the entry state reaches state 2 only, emitting state i reaches
 // i and i+1 only, the last emitting state alone reaches the exit state, no tee model -- is a special case of what fb_state.hip
@@ -10,14 +10,15 @@
 //    lane holds anyway (fb_state.hip writes and reads a second fp64 column for it: 1.95x the algorithmic beta traffic);
 //  * NOTHING THAT DOES NOT FEED THE NEXT STEP IS IN THE CHAIN.  k_alpha_s (fb_state.hip) spends ~60 % of a step's instructions on
 //    occupation counts, transition counts and mixture seeds inside its 500-step dependent chain; here the alpha kernel stores its
-//    column (fp64, like beta) and a FRAME-PARALLEL kernel (k_stats_lr: workgroup = utterance x 64 frames, no dependence between
+//    column (fp64, like beta) and a FRAME-PARALLEL kernel (k_stats_sp: workgroup = utterance x 32 frames, no dependence between
 //    frames, ten thousand workgroups instead of 1 250) computes SetOcct / UpTranParms / the UpMixParms seeds from the stored alpha,
 //    beta and scores.  Its per-workgroup transition counts go to a table of partial rows that k_trans_reduce sums (one atomic per
 //    matrix entry and 256 rows: atomics of 10 000 workgroups on the 15 addresses of a tied matrix would serialise in L2).
 //
 // Reference semantics as fb_state.hip: SetBeta HFB.c:1149, StepAlpha :686, InitAlpha :616, MaxModelProb :655, SetOcct :399,
-// UpTranParms :1371, UpMixParms seeds :1479 (S == 1).  Arithmetic operand for operand: with FAST = false every alpha, beta and the
-// utterance probability equal fb_state.hip's and the oracle's bit for bit; FAST = true is the tolerance class of ladd.h.
+// UpTranParms :1371, UpMixParms seeds :1479 (S == 1).  Arithmetic operand for operand: every alpha, beta and utterance probability of
+// k_alpha_lr and k_beta_lr<W, false> equal fb_state.hip's and the oracle's bit for bit; FAST = true (k_beta_lr's pruned passes and the lean
+// kernels) is the tolerance class of ladd.h.
 //
 // Layout per utterance (L = 64 W lanes, T frames, Q models; QP = Q rounded up to 8):
 //   betaW [betaW0  + (t-1) L + lane]                     beta_j(t) of the lane's state (inside the beta beam of t)
@@ -274,17 +275,17 @@ __global__ __launch_bounds__(64 * W) void k_beta_lr(FbArgs a)
 // column exchange of the SAME step: every lane computes its alpha_j(t) before the beam is known, publishes it unmasked together with
 // the ballot, and after the barrier everybody derives the beam, masks its own value and masks what it reads of its neighbour (a lane
 // knows the first lane of its neighbour's model, which is what the beam is expressed in).
-template <int W, bool FAST>
+template <int W>
 __global__ __launch_bounds__(64 * W) void k_alpha_lr(FbArgs a)
 {
    constexpr int L = 64 * W, LP = L + 2 * SPAD;
-   __shared__ double ltab[FAST ? 1 : LADD_TAB_DOUBLES];
+   __shared__ double ltab[LADD_TAB_DOUBLES];
    __shared__ double xalpha[2][LP];                    // alpha_j(t) by step parity (unmasked for t >= 2)
    __shared__ double xsum[2][LP];                      // alpha_j(t) + beta_j(t) inside the beta beam (MaxModelProb)
    __shared__ unsigned long long bslot[2][8];          // the wavefronts' ballot words, by step parity
    __shared__ float stage[W][2 * 64 * 4];
    __shared__ short flOf[L + 2];
-   if constexpr (!FAST) ladd_table_to_lds(ltab, a.laddTab);
+   ladd_table_to_lds(ltab, a.laddTab);
    const int gl = threadIdx.x, lane = gl & 63, wv = gl >> 6;
    const int li = blockIdx.x;
    if (li >= a.nList) return;
@@ -322,12 +323,11 @@ __global__ __launch_bounds__(64 * W) void k_alpha_lr(FbArgs a)
    st.row = a.outp + ud.outp0 + (size_t)(valid ? gl : 0) * T;      // (lanes past the chain read the first state's row: no lane-divergent loads)
    const double mle = a.minLogExp, pr = a.pr[u];
    const double minF = (double)a.minFrwdP;
-   const float aA = s.first ? s.aEntry : s.aPrev;        // the transition into the state from the lane before it / from the entry state
    const int myFirst = gl - (j - 2);                     // first lane of the own model
    // first lane of the model of the lane before this one (what its membership of the beam is decided by)
    int prevFirst = myFirst;
    if (valid && s.first && q > 1) prevFirst = flOf[q - 1];
-#define ladd(x, y) ladd_sel<FAST>((x), (y), mle, ltab)
+#define ladd(x, y) ladd_sel<false>((x), (y), mle, ltab)
 
    double aJ = LZERO, aE = LZERO, aEnext = LZERO;        // alpha_j(t); alpha_1(q,t); alpha_1(q,t+1) = exit value of the model before, column t
    double yPrev = LZERO;                                 // alpha of the lane before this one in the column before (log-zero outside that column's beam)
@@ -353,7 +353,7 @@ __global__ __launch_bounds__(64 * W) void k_alpha_lr(FbArgs a)
    MaskW<W> mLo = MaskW<W>::range(0, L - 1), mE = MaskW<W>::range(0, -1);
    int mLoOf = 0, mEOf = 0, lo1Of = lo1, hi1Of = hi1, e0Of = -1;
    double eT = LZERO, eT1 = LZERO;                       // entry-state beta of the own model in columns t, t+1 (first lane)
-   if (valid && s.first) { eT = entry_beta<FAST>(s.aEntry, (double)oT, bT); if (T >= 2) eT1 = entry_beta<FAST>(s.aEntry, (double)oT1, bT1); }
+   if (valid && s.first) { eT = entry_beta<false>(s.aEntry, (double)oT, bT); if (T >= 2) eT1 = entry_beta<false>(s.aEntry, (double)oT1, bT1); }
 
    // (column 1 -- InitAlpha -- is a call of its own: the loop body carries no branch on t and no copies of the state it does not touch)
    // (... and so are the last two columns: in the loop between, column t + 2 exists without asking)
@@ -392,15 +392,9 @@ __global__ __launch_bounds__(64 * W) void k_alpha_lr(FbArgs a)
          // ---- alpha column t (HFB.c:729-771) as if the state were in the beam: entry term (first lane) or the state before (other
          // lanes), then the state itself
          const double a1 = (q == 1) ? LZERO : aEnext;                // alpha_1(q,t) = alpha_N(q-1,t-1)
-         double x;
-         if constexpr (FAST) {
-            const double tA = (s.first ? a1 : yPrev) + (double)aA;
-            x = ladd_fast(tA, aJ + (double)s.aSelf);
-         } else {
-            x = s.first ? (((double)s.aEntry > LSMALL) ? (double)s.aEntry + a1 : LZERO) : LZERO;
-            if (!s.first && (double)s.aPrev > LSMALL && yPrev > LSMALL) x = ladd(x, yPrev + (double)s.aPrev);
-            if ((double)s.aSelf > LSMALL && aJ > LSMALL) x = ladd(x, aJ + (double)s.aSelf);
-         }
+         double x = s.first ? (((double)s.aEntry > LSMALL) ? (double)s.aEntry + a1 : LZERO) : LZERO;
+         if (!s.first && (double)s.aPrev > LSMALL && yPrev > LSMALL) x = ladd(x, yPrev + (double)s.aPrev);
+         if ((double)s.aSelf > LSMALL && aJ > LSMALL) x = ladd(x, aJ + (double)s.aSelf);
          const double aJn = x + (double)oT;
          xalpha[par][SPAD + gl] = aJn;
          xsum[par][SPAD + gl] = inB ? aJn + bT : LZERO;
@@ -429,9 +423,7 @@ __global__ __launch_bounds__(64 * W) void k_alpha_lr(FbArgs a)
       *pS = xpre; pS += L;
       if (valid && s.first) { *pE = aE; pE += ud.QP; }
       // exit value of the model BEFORE this one in column t (HFB.c:762-769 there): alpha_1 of this model in column t+1
-      double aXp;
-      if constexpr (FAST) aXp = yPrev + (double)s.aExitPrev;
-      else aXp = ((double)s.aExitPrev > LSMALL && yPrev > LSMALL) ? from_zero(yPrev + (double)s.aExitPrev) : LZERO;
+      const double aXp = ((double)s.aExitPrev > LSMALL && yPrev > LSMALL) ? from_zero(yPrev + (double)s.aExitPrev) : LZERO;
       if (a.alphaDbg && valid) {
          double *ad = a.alphaDbg + ud.beta0 + (size_t)(t - 1) * nC + mc0;
          ad[j - 1] = aJ;
@@ -464,7 +456,7 @@ __global__ __launch_bounds__(64 * W) void k_alpha_lr(FbArgs a)
          oT1 = st.get_all(f);
       }
       eT = eT1;
-      if (has2) eT1 = entry_beta<FAST>(s.aEntry, (double)oT1, bT1);      // (meaningful at the models' first lanes)
+      if (has2) eT1 = entry_beta<false>(s.aEntry, (double)oT1, bT1);      // (meaningful at the models' first lanes)
       // The beta beam's words of columns t, t+1, t+2 decide everything below, and without pruning they stay the same for hundreds of
       // columns: while the word coming in equals the one all three had (wSame), nothing moves and the step skips the lot.
       if (!INNER || w3 != wSame) {
@@ -501,224 +493,12 @@ __global__ __launch_bounds__(64 * W) void k_alpha_lr(FbArgs a)
 #undef ladd
 }
 
-// ------------------------------------------------------------------------------------ K3x: occupation / transition counts, mixture seeds
-// Workgroup = (utterance, chunk of STATS_FC frames), lane = chain state as above.  Per frame and lane: SetOcct (HFB.c:399-418),
-// UpTranParms (HFB.c:1390-1410) and the UpMixParms seed (HFB.c:1479-1489,1573-1606) from the stored alpha column, beta column and
-// scores; frames are independent, the loads of the frames of a chunk are all in flight together.
-#ifndef STATS_FC
+// the statistics kernel (k_stats_sp, fb_lr_lean.inc): frames per chunk, doubles per row of partial transition counts
 #define STATS_FC 32
-#endif
 #define TR_ROW 16
 #define EXP_TERM(acc, x) do { if constexpr (FAST) acc += exp_fast(x); else if ((x) > EXPFLOOR) acc += exp_tab((x), etab); } while (0)
 
-template <int W, bool FAST>
-__global__ __launch_bounds__(64 * W) void k_stats_lr(FbArgs a)
-{
-   constexpr int L = 64 * W, FC = STATS_FC, OS = FC + 3;
-   __shared__ double etab[FAST ? 1 : EXP_TAB_N];
-   __shared__ float otile[(L + 1) * OS];                 // scores of frames t0 .. t1+1, one row per lane (+ one row of zeros after the last)
-   // the surviving pairs of a wavefront wait here and go out in whole lines at the end (a global store per frame made the next frame wait
-   // for it: the compiler drains vmcnt before it reuses the store's registers -- 0.33 ms of the kernel's 0.59)
-   constexpr int HB = 128;
-   __shared__ int hbSt[W][HB], hbFr[W][HB];
-   __shared__ double hbSeed[W][HB];
-   if constexpr (!FAST) exp_table_to_lds(etab);
-   const int gl = threadIdx.x, lane = gl & 63, wv = gl >> 6;
-   const int li = blockIdx.x, ch = blockIdx.y;
-   const size_t region = (size_t)((size_t)li * gridDim.y + ch) * W + wv;      // this wavefront's row of partial counts and region of the hit list
-   double *part = a.trPart + region * TR_ROW;
-   const int u = a.uttList[li];
-   const UttDesc ud = a.utt[u];
-   const int T = ud.T, Q = ud.Q, nS = ud.nSlots;
-   const int t0 = ch * FC + 1;
-   if (a.status[u] != HTKAMD_UTT_OK || t0 > T) {         // skipped, failed in the alpha pass, or shorter than this chunk's first frame
-      if (lane == 0) { part[TR_ROW - 1] = -1.0; a.hitCtl[region] = 0; }
-      return;
-   }
-   const int t1 = (t0 + FC - 1 < T) ? t0 + FC - 1 : T;
-   const bool valid = gl < nS;
-   LrRegs s;
-   load_lr(s, a, ud, gl, valid);
-   const int q = s.q;
-   const int myFirst = gl - (s.j - 2);
-   // scores: the lane's own row, frames t0 .. min(T, t1+1)
-   {
-      const int nf = ((t1 + 1 < T) ? t1 + 1 : T) - t0 + 1;
-      float *dst = otile + gl * OS;
-      if (valid) {
-         const float *row = a.outp + ud.outp0 + (size_t)gl * T + (t0 - 1);
-         int k = 0;
-         for (; k + 4 <= nf; k += 4) { const f4s v = *(const f4s *)(row + k); dst[k] = v[0]; dst[k + 1] = v[1]; dst[k + 2] = v[2]; dst[k + 3] = v[3]; }
-         for (; k < nf; k++) dst[k] = row[k];
-      } else for (int k = 0; k < nf; k++) dst[k] = 0.0f;
-      if (gl == L - 1) for (int k = 0; k < OS; k++) otile[L * OS + k] = 0.0f;
-   }
-   __syncthreads();
-   cint_lr *qBeam = (cint_lr *)(a.qBeam + ud.frame0 - 1);
-   cint_lr *aBeam = (cint_lr *)(a.aBeam + ud.frame0 - 1);
-   const double pr = a.pr[u], minF = (double)a.minFrwdP;
-   const bool wantMix = (a.uFlags & (HTKAMD_UPMEANS | HTKAMD_UPVARS | HTKAMD_UPMIXES)) != 0;
-   const bool wantTrans = (a.uFlags & HTKAMD_UPTRANS) != 0;
-   int cM = 0, sidx = 0;
-   if (valid) { sidx = a.slotState[ud.slot0 + gl]; cM = a.stateCompOff[sidx + 1] - a.stateCompOff[sidx]; }
-   MixHit *hreg = a.hits + region * (size_t)(STATS_FC * 64);
-   int hc = 0, hb = 0;                                   // records in this wavefront's region of the hit list / waiting in its LDS buffer
-   const bool single = (a.maxM == 1);
-   const bool hasNext = valid && q < Q;
-   const bool nbValid = gl + 1 < nS;                     // the lane next door holds a state
-   double taSelf = 0.0, taOut = 0.0, taEntry = 0.0, occJ = 0.0, occE = 0.0;       // taOut: to the next state (inner lanes) / to the exit state (last lane)
-   const float *orow = otile + gl * OS;
-
-   // four frames at a time: every load of the four is issued before the first of them is used (the stores of the seeds would otherwise
-   // keep the next frame's loads behind them)
-   for (int tb = t0; tb <= t1; tb += 4) {
-      double xpv[4], aEv[4], bv[5], bnv[4];
-      int wav[4], wbv[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-         const int t = tb + k;
-         xpv[k] = LZERO; aEv[k] = LZERO; bnv[k] = LZERO; wav[k] = 1; wbv[k] = 1;
-         if (t <= t1) {
-            wav[k] = aBeam[t];
-            if (t < T) wbv[k] = qBeam[t + 1];
-            if (valid) {
-               xpv[k] = ALPHA_S(t);
-               if (s.first) aEv[k] = ALPHA_E(t, q);
-               // beta_{j+1}(t+1): the lane next door's own bv[k + 1] -- taken from it below (a lane shift); only a wavefront's last lane,
-               // whose neighbour sits in the next wavefront, reads it from memory (round 3: every lane did -- the column was read twice)
-               if (lane == 63 && t < T && nbValid) bnv[k] = a.betaW[ud.betaW0 + (size_t)t * L + gl + 1];
-            }
-         }
-      }
-#pragma unroll
-      for (int k = 0; k < 5; k++) { const int t = tb + k; bv[k] = (valid && t <= T && t <= t1 + 1) ? BETA_S(t) : LZERO; }
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-         const double nb = __shfl_down(bv[k + 1], 1);      // (an invalid or out-of-range neighbour holds LZERO there, as the load gave)
-         if (lane != 63) bnv[k] = (tb + k <= t1) ? nb : LZERO;
-      }
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-      const int t = tb + k;
-      if (t > t1) break;
-      const int sl = wav[k] & 0xffff, el = wav[k] >> 16, lo2 = wbv[k] & 0xffff, hi2 = (t < T) ? (wbv[k] >> 16) : 0;
-      const bool inBeam = valid && myFirst >= sl && myFirst <= el;          // the alpha beam comes as the first lanes of its first and last model
-      const bool bqt1ok = (t < T) && q >= lo2 && q <= hi2;
-      const double xp = xpv[k], aE = aEv[k], bT = bv[k], bT1 = bv[k + 1], bN1 = bnv[k];
-      const double oT = (double)orow[t - t0], oT1 = (double)orow[t - t0 + 1], oN1 = (double)orow[OS + t - t0 + 1];
-      const double aJ = (t == 1 && !((double)s.aEntry > LSMALL)) ? LZERO : xp + oT;
-      // Every count of a state at a frame is bounded by the state's occupation there (a transition count is a part of it), and that is
-      // nothing (below e^-100) for all but the few states along the alignment: the exponentials run only where it is not, and not at all
-      // in a wavefront none of whose states is occupied in this frame.
-      const double xo = aJ + bT - pr;
-#ifdef STATS_EXP_NOOCC
-      const bool occd = false;
-#else
-      const bool occd = inBeam && xo > EXPFLOOR;
-#endif
-      if (__any(occd)) {
-      if (occd) {
-         // SetOcct + UpTranParms for state j, and for the entry state at the model's first lane
-         double x = xo;
-         occJ += (double)(float)exp_sel<FAST>(x, etab);
-         if (s.first) {
-            x = aE + entry_beta<FAST>(s.aEntry, oT, bT) - pr;
-            occE += (double)((x > EXPFLOOR) ? (float)exp_sel<FAST>(x, etab) : 0.0f);
-         }
-         if (wantTrans) {
-            if (s.first) { x = aE + (double)s.aEntry + oT + bT - pr; EXP_TERM(taEntry, x); }
-            if (bqt1ok) {
-               x = aJ + (double)s.aSelf + (oT1 + bT1) - pr;
-               EXP_TERM(taSelf, x);
-               if (!s.last) { x = aJ + (double)s.aNext + (oN1 + bN1) - pr; EXP_TERM(taOut, x); }
-            }
-            if (s.last) {
-               // beta_N(q,t): 0 for the last model at T, else beta_1(q+1,t+1) where that is in the beam of t+1
-               const double bN = (t == T) ? ((q == Q) ? 0.0 : LZERO)
-                                          : ((hasNext && q + 1 >= lo2 && q + 1 <= hi2) ? entry_beta<FAST>(s.aEntryNext, oN1, bN1) : LZERO);
-               x = aJ + (double)s.aExit + bN - pr;
-               EXP_TERM(taOut, x);
-            }
-         }
-      }
-      }
-      {
-         // UpMixParms seed (HFB.c:1479-1489,1573-1606): the pairs the MINFORPROB prune lets through go to the list of k_mixhits
-         double seed = LZERO;
-         if (inBeam && wantMix) {
-            if (cM == 1 || single) {
-               const double x = aJ + bT - pr;
-               if (-x < minF) seed = x;
-            } else {
-               const double initx = xp + (bT - pr);
-               const double ub = initx + oT;
-               if (ub > -minF - 0.01) seed = initx;
-            }
-         }
-#ifdef STATS_EXP_NOHIT
-         const bool hit = false;
-#else
-         const bool hit = seed > LSMALL;
-#endif
-         const unsigned long long hm = __ballot(hit);
-         if (hm) {
-            const int np = __popcll(hm);
-            if (hb + np > HB) {                          // the buffer is full: out with it
-               for (int i = lane; i < hb; i += 64) { MixHit h; h.st = hbSt[wv][i]; h.frame = hbFr[wv][i]; h.seed = hbSeed[wv][i]; hreg[hc + i] = h; }
-               hc += hb; hb = 0;
-            }
-            if (hit) { const int pos = hb + __popcll(hm & ((1ull << lane) - 1)); hbSt[wv][pos] = a.hitSlots ? ud.slot0 + gl : sidx; hbFr[wv][pos] = ud.frame0 + t - 1; hbSeed[wv][pos] = seed; }
-            hb += np;
-         }
-      }
-      }
-   }
-   for (int i = lane; i < hb; i += 64) { MixHit h; h.st = hbSt[wv][i]; h.frame = hbFr[wv][i]; h.seed = hbSeed[wv][i]; hreg[hc + i] = h; }
-   hc += hb;
-   if (lane == 0) a.hitCtl[region] = hc;
-
-   // ---- this workgroup's counts.  One transition matrix for the whole chain (a tied-transition system): a row of partial sums per
-   // wavefront for k_trans_reduce -- [0..2] a_ii, [3..5] a_i,i+1 (or a_iN from the last state), i = 2..4; [6] a_12; [7..9] occupation
-   // of states 2..4; [10] of the entry state; [15] the matrix.  Otherwise atomics per lane, on the lane's own matrix.
-   const int cTrans = valid ? a.mTrans[s.mi] : -1;
-   const int t0m = a.mTrans[ud.q0];
-   const bool uniform = __all(!valid || cTrans == t0m);          // per wavefront: each writes its own row
-   if (uniform) {
-      double row[11];
-#pragma unroll
-      for (int i = 2; i <= 4; i++) {
-         const bool mine = valid && s.j == i;
-         row[i - 2] = mine ? taSelf : 0.0; row[3 + i - 2] = mine ? taOut : 0.0; row[7 + i - 2] = mine ? occJ : 0.0;
-      }
-      row[6] = taEntry; row[10] = (valid && s.first) ? occE : 0.0;
-#pragma unroll
-      for (int k = 0; k < 11; k++) {
-         double v = row[k];
-#pragma unroll
-         for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-         row[k] = v;
-      }
-      if (lane == 0) {
-#pragma unroll
-         for (int k = 0; k < 11; k++) part[k] = wantTrans ? row[k] : 0.0;
-         part[TR_ROW - 1] = wantTrans ? (double)t0m : -1.0;
-      }
-   } else {
-      if (lane == 0) part[TR_ROW - 1] = -1.0;
-      if (valid && wantTrans) {
-         const int N = s.N, j = s.j;
-         double *tr = a.acc + a.lay.tr + a.transOff[cTrans];
-         double *oc = a.acc + a.lay.trOcc + a.trOccOff[cTrans];
-         if (taSelf != 0.0) atomicAdd(tr + (size_t)(j - 1) * N + (j - 1), taSelf);
-         if (taOut != 0.0) atomicAdd(tr + (size_t)(j - 1) * N + j, taOut);
-         if (taEntry != 0.0) atomicAdd(tr + 1, taEntry);
-         if (occJ != 0.0) atomicAdd(oc + (j - 1), occJ);
-         if (s.first && occE != 0.0) atomicAdd(oc, occE);
-      }
-   }
-}
-
-// rows of k_stats_lr -> accumulators: a block sums 256 rows; where they all belong to one matrix (the usual case) one atomic per
+// rows of k_stats_sp -> accumulators: a block sums 256 rows; where they all belong to one matrix (the usual case) one atomic per
 // entry and block, else one per entry and row
 __global__ __launch_bounds__(256) void k_trans_reduce(FbArgs a, int nRows)
 {
@@ -783,52 +563,43 @@ template <bool FAST> static void launch_beta_lr(const FbArgs &a, int W, hipStrea
    else if (W == 4) hipLaunchKernelGGL((k_beta_lr<4, FAST>), dim3(a.nList), dim3(256), 0, s, a);
    else hipLaunchKernelGGL((k_beta_lr<8, FAST>), dim3(a.nList), dim3(512), 0, s, a);
 }
-template <bool FAST> static void launch_alpha_lr(const FbArgs &a, int W, hipStream_t s)
+static void launch_alpha_lr(const FbArgs &a, int W, hipStream_t s)
 {
-   if (W == 1) hipLaunchKernelGGL((k_alpha_lr<1, FAST>), dim3(a.nList), dim3(64), 0, s, a);
-   else if (W == 2) hipLaunchKernelGGL((k_alpha_lr<2, FAST>), dim3(a.nList), dim3(128), 0, s, a);
-   else if (W == 4) hipLaunchKernelGGL((k_alpha_lr<4, FAST>), dim3(a.nList), dim3(256), 0, s, a);
-   else hipLaunchKernelGGL((k_alpha_lr<8, FAST>), dim3(a.nList), dim3(512), 0, s, a);
+   if (W == 1) hipLaunchKernelGGL((k_alpha_lr<1>), dim3(a.nList), dim3(64), 0, s, a);
+   else if (W == 2) hipLaunchKernelGGL((k_alpha_lr<2>), dim3(a.nList), dim3(128), 0, s, a);
+   else if (W == 4) hipLaunchKernelGGL((k_alpha_lr<4>), dim3(a.nList), dim3(256), 0, s, a);
+   else hipLaunchKernelGGL((k_alpha_lr<8>), dim3(a.nList), dim3(512), 0, s, a);
 }
-template <bool FAST> static void launch_stats_lr(const FbArgs &a, int W, int nChunks, hipStream_t s)
+// the lean kernels (fb_lr_lean.inc); W = 2 takes one wavefront with two states per lane
+template <bool DBG> static void launch_alpha_f(const FbArgs &a, int W, hipStream_t s)
 {
-   if (W == 1) hipLaunchKernelGGL((k_stats_lr<1, FAST>), dim3(a.nList, nChunks), dim3(64), 0, s, a);
-   else if (W == 2) hipLaunchKernelGGL((k_stats_lr<2, FAST>), dim3(a.nList, nChunks), dim3(128), 0, s, a);
-   else if (W == 4) hipLaunchKernelGGL((k_stats_lr<4, FAST>), dim3(a.nList, nChunks), dim3(256), 0, s, a);
-   else hipLaunchKernelGGL((k_stats_lr<8, FAST>), dim3(a.nList, nChunks), dim3(512), 0, s, a);
+   if (W == 1) hipLaunchKernelGGL((k_alpha_f<1, DBG>), dim3(a.nList), dim3(64), 0, s, a);
+   else if (W == 2) hipLaunchKernelGGL(k_alpha_f2<DBG>, dim3(a.nList), dim3(64), 0, s, a);
+   else if (W == 4) hipLaunchKernelGGL((k_alpha_f<4, DBG>), dim3(a.nList), dim3(256), 0, s, a);
+   else hipLaunchKernelGGL((k_alpha_f<8, DBG>), dim3(a.nList), dim3(512), 0, s, a);
+}
+template <bool FAST> static void launch_stats_sp(const FbArgs &a, int W, int nChunks, hipStream_t s)
+{
+   if (W == 1) hipLaunchKernelGGL((k_stats_sp<1, FAST>), dim3(a.nList, nChunks), dim3(64), 0, s, a);
+   else if (W == 2) hipLaunchKernelGGL((k_stats_sp<2, FAST>), dim3(a.nList, nChunks), dim3(128), 0, s, a);
+   else if (W == 4) hipLaunchKernelGGL((k_stats_sp<4, FAST>), dim3(a.nList, nChunks), dim3(256), 0, s, a);
+   else hipLaunchKernelGGL((k_stats_sp<8, FAST>), dim3(a.nList, nChunks), dim3(512), 0, s, a);
 }
 
 int htkamd_stats_lr_chunks(int TMax) { return (TMax + STATS_FC - 1) / STATS_FC; }
 int htkamd_stats_lr_region_cap(void) { return STATS_FC * 64; }
 size_t htkamd_stats_lr_row_doubles(void) { return TR_ROW; }
 
-// experiment / fallback switch: HTKAMD_LR_LEAN=0 keeps the round-4 kernels (bit 0: beta, bit 1: alpha, bit 2: statistics, bit 3: one
-// wavefront with two states per lane for chains of 65 .. 128 states; default 15)
-static int lr_lean_mask()
-{
-   static const int m = [] { const char *e = getenv("HTKAMD_LR_LEAN"); return e ? atoi(e) : 15; }();
-   return m;
-}
-#define LAUNCH_W(K, ...) \
-   do { \
-      if (W == 1) hipLaunchKernelGGL((K<1, ##__VA_ARGS__>), grid, dim3(64), 0, s, a); \
-      else if (W == 2) hipLaunchKernelGGL((K<2, ##__VA_ARGS__>), grid, dim3(128), 0, s, a); \
-      else if (W == 4) hipLaunchKernelGGL((K<4, ##__VA_ARGS__>), grid, dim3(256), 0, s, a); \
-      else hipLaunchKernelGGL((K<8, ##__VA_ARGS__>), grid, dim3(512), 0, s, a); \
-   } while (0)
-
-bool htkamd_stats_lr_is_sparse(const FbArgs &a) { return a.laneRec && (lr_lean_mask() & 4); }
 // no pruning beam and the fp32-transcendental class: the lean kernels (fb_lr_lean.inc)
-bool htkamd_beta_lr_is_lean(const FbArgs &a, bool fast) { return fast && a.qBeamNP && !(a.pruneInit < HTKAMD_NOPRUNE) && (lr_lean_mask() & 1); }
+bool htkamd_beta_lr_is_lean(const FbArgs &a, bool fast) { return fast && a.qBeamNP && !(a.pruneInit < HTKAMD_NOPRUNE); }
 
 int htkamd_launch_beta_lr(const FbArgs &a, int W, bool fast, hipStream_t s)
 {
    if (a.nList <= 0) return HTKAMD_OK;
    if (htkamd_beta_lr_is_lean(a, fast)) {
       const dim3 grid(a.nList);
-      if (W == 2 && (lr_lean_mask() & 8)) hipLaunchKernelGGL(k_beta_np2, grid, dim3(64), 0, s, a);      // one wavefront, two states per lane
+      if (W == 2) hipLaunchKernelGGL(k_beta_np2, grid, dim3(64), 0, s, a);      // one wavefront, two states per lane
       else if (W == 1) hipLaunchKernelGGL((k_beta_np<1>), grid, dim3(64), 0, s, a);
-      else if (W == 2) hipLaunchKernelGGL((k_beta_np<2>), grid, dim3(128), 0, s, a);
       else if (W == 4) hipLaunchKernelGGL((k_beta_np<4>), grid, dim3(256), 0, s, a);
       else hipLaunchKernelGGL((k_beta_np<8>), grid, dim3(512), 0, s, a);
       HIPCHECK(hipGetLastError());
@@ -842,16 +613,9 @@ int htkamd_launch_beta_lr(const FbArgs &a, int W, bool fast, hipStream_t s)
 int htkamd_launch_alpha_lr(const FbArgs &a, int W, bool fast, hipStream_t s)
 {
    if (a.nList <= 0) return HTKAMD_OK;
-   if (fast && (lr_lean_mask() & 2)) {
-      const dim3 grid(a.nList);
-      if (W == 2 && (lr_lean_mask() & 8)) {
-         if (a.alphaDbg) hipLaunchKernelGGL(k_alpha_f2<true>, grid, dim3(64), 0, s, a); else hipLaunchKernelGGL(k_alpha_f2<false>, grid, dim3(64), 0, s, a);
-      }
-      else if (a.alphaDbg) LAUNCH_W(k_alpha_f, true); else LAUNCH_W(k_alpha_f, false);
-      HIPCHECK(hipGetLastError());
-      return HTKAMD_OK;
-   }
-   if (fast) launch_alpha_lr<true>(a, W, s); else launch_alpha_lr<false>(a, W, s);
+   if (!fast) launch_alpha_lr(a, W, s);
+   else if (a.alphaDbg) launch_alpha_f<true>(a, W, s);
+   else launch_alpha_f<false>(a, W, s);
    HIPCHECK(hipGetLastError());
    return HTKAMD_OK;
 }
@@ -862,11 +626,7 @@ int htkamd_launch_stats_lr(const FbArgs &a, int W, bool fast, hipStream_t s)
 {
    if (a.nList <= 0) return HTKAMD_OK;
    const int nChunks = htkamd_stats_lr_chunks(a.TMax);
-   if (htkamd_stats_lr_is_sparse(a)) {
-      const dim3 grid(a.nList, nChunks);
-      if (fast) LAUNCH_W(k_stats_sp, true); else LAUNCH_W(k_stats_sp, false);
-   }
-   else if (fast) launch_stats_lr<true>(a, W, nChunks, s); else launch_stats_lr<false>(a, W, nChunks, s);
+   if (fast) launch_stats_sp<true>(a, W, nChunks, s); else launch_stats_sp<false>(a, W, nChunks, s);
    const int nRows = a.nList * nChunks * W;
    hipLaunchKernelGGL(k_trans_reduce, dim3((nRows + 255) / 256), dim3(256), 0, s, a, nRows);
    HIPCHECK(hipGetLastError());

@@ -21,14 +21,6 @@
 //
 // Reference semantics unchanged: SetBeta HFB.c:1149, StepAlpha :686, MaxModelProb :655, SetOcct :399, UpTranParms :1371, UpMixParms :1479.
 
-#ifndef LR_EXP_BUILD
-#define LR_EXP_BUILD 0
-#endif
-// ablation switches of a diagnostic build (results are wrong by design): 1 no beta stores, 2 constant scores, 4 log-add = max, 8 no alpha stores,
-// 16 alpha without the flags of MaxModelProb
-#define LR_EXP(bit) (LR_EXP_BUILD && (a.lrExp & (bit)))
-__device__ __forceinline__ double ladd_fast_x(const double x, const double y, const bool cheap) { return cheap ? fmax(x, y) : ladd_fast(x, y); }
-
 // ------------------------------------------------------------------------------------ K2n: beta, no pruning beam, fp32-transcendental class
 template <int W>
 __global__ __launch_bounds__(64 * W) void k_beta_np(FbArgs a)
@@ -379,10 +371,8 @@ __global__ __launch_bounds__(64 * W) void k_alpha_f(FbArgs a)
 }
 
 // ------------------------------------------------------------------------------------ K3y: occupation / transition counts, mixture seeds -- the pairs inside the alpha beams only
-template <int W, bool FAST>
-#ifndef STATS_EU
 #define STATS_EU 1
-#endif
+template <int W, bool FAST>
 __global__ __launch_bounds__(64 * W, STATS_EU) void k_stats_sp(FbArgs a)
 {
    constexpr int L = 64 * W, FC = STATS_FC;
@@ -609,9 +599,7 @@ __device__ __forceinline__ double dpp_from_prev(const double v, const double edg
 }
 typedef double d2s __attribute__((ext_vector_type(2), aligned(8)));
 
-#ifndef LEAN2_EU
 #define LEAN2_EU 1
-#endif
 __global__ __launch_bounds__(64, LEAN2_EU) void k_beta_np2(FbArgs a)
 {
    constexpr int L = 128;
@@ -645,17 +633,6 @@ __global__ __launch_bounds__(64, LEAN2_EU) void k_beta_np2(FbArgs a)
    const int bT = (T - 1) / BK;
    float Rc0[BK], Rc1[BK], Rn0[BK], Rn1[BK];
    auto load8 = [&](float *R, const float *row, const int b) {
-      if (LR_EXP(2)) {
-#pragma unroll
-         for (int k = 0; k < BK; k++) R[k] = -60.0f - (float)k;
-         return;
-      }
-      if (LR_EXP(128)) {                               // the access pattern of a frame-major score block (values: whatever lies there)
-         const float *tm = a.outp + ud.outp0 + (row == row0 ? 0 : 1) + 2 * lane;
-#pragma unroll
-         for (int k = 0; k < BK; k++) R[k] = tm[(size_t)(BK * b + k) * 123];
-         return;
-      }
       const f4s lo4 = *(const f4s *)(row + BK * b), hi4 = *(const f4s *)(row + BK * b + 4);
 #pragma unroll
       for (int k = 0; k < 4; k++) { R[k] = lo4[k]; R[4 + k] = hi4[k]; }
@@ -679,22 +656,15 @@ __global__ __launch_bounds__(64, LEAN2_EU) void k_beta_np2(FbArgs a)
 
    auto step = [&](const int t, const float o0_t, const float o1_t, const int w_t) {
       const double zN = dpp_from_next(z0, LZERO);            // state 2l+2 of the column before
-      const double n0 = LR_EXP_BUILD ? ladd_fast_x(cN0 + z1, dSelf0 + z0, LR_EXP(4)) : ladd_fast(cN0 + z1, dSelf0 + z0);
-      const double n1 = LR_EXP_BUILD ? ladd_fast_x(cN1 + zN, dSelf1 + z1, LR_EXP(4)) : ladd_fast(cN1 + zN, dSelf1 + z1);
+      const double n0 = ladd_fast(cN0 + z1, dSelf0 + z0);
+      const double n1 = ladd_fast(cN1 + zN, dSelf1 + z1);
       if (w_t != w) { w = w_t; lo = w & 0xffff; hi = w >> 16; in0 = q0 >= lo && q0 <= hi; in1 = q1 >= lo && q1 <= hi; }
       b0 = in0 ? n0 : LZERO; b1 = in1 ? n1 : LZERO;
-      if (LR_EXP(4096)) {                              // diagnostic: the column as floats (values rounded: results off) -- what 4-byte columns could save at most
-         typedef float f2s __attribute__((ext_vector_type(2)));
-         f2s st; st[0] = (float)b0; st[1] = (float)b1;
-         __builtin_nontemporal_store(st, (f2s *)((in0 || in1) ? (float *)(a.betaW + ud.betaW0) + (size_t)(t - 1) * L + g0 : (float *)a.sink));
-      } else
-      if (!LR_EXP(1)) {
-         d2s st; st[0] = b0; st[1] = b1;
-         // (a lane with neither state in the beam "stores" to a sink line: the column costs the beam's cache lines and one more, not 1 KB --
-         // and no branch, behind which the compiler would drain every outstanding load)
-         // (streamed: 0.47 GB that the alpha pass reads once, from the other end -- without the hint the stores cost 8 us more)
-         __builtin_nontemporal_store(st, (d2s *)((in0 || in1) ? pB + (size_t)(t - 1) * L : a.sink));
-      }
+      d2s st; st[0] = b0; st[1] = b1;
+      // (a lane with neither state in the beam "stores" to a sink line: the column costs the beam's cache lines and one more, not 1 KB --
+      // and no branch, behind which the compiler would drain every outstanding load)
+      // (streamed: 0.47 GB that the alpha pass reads once, from the other end -- without the hint the stores cost 8 us more)
+      __builtin_nontemporal_store(st, (d2s *)((in0 || in1) ? pB + (size_t)(t - 1) * L : a.sink));
       o0 = o0_t; o1 = o1_t;
       z0 = in0 ? (double)o0_t + n0 : LZERO;
       z1 = in1 ? (double)o1_t + n1 : LZERO;
@@ -878,8 +848,8 @@ __global__ __launch_bounds__(64, LEAN2_EU) void k_alpha_f2(FbArgs a)
       od0 = on0; od1 = on1; bT0 = bN0; bT1 = bN1;
       on0 = (double)oN0; on1 = (double)oN1; bN0 = bNn0; bN1 = bNn1;
       const double a10 = inc0, a11 = inc1;
-      const double x0 = LR_EXP_BUILD ? ladd_fast_x(inc0 + dIn0, aJ0 + dSelf0, LR_EXP(4)) : ladd_fast(inc0 + dIn0, aJ0 + dSelf0);
-      const double x1 = LR_EXP_BUILD ? ladd_fast_x(inc1 + dIn1, aJ1 + dSelf1, LR_EXP(4)) : ladd_fast(inc1 + dIn1, aJ1 + dSelf1);
+      const double x0 = ladd_fast(inc0 + dIn0, aJ0 + dSelf0);
+      const double x1 = ladd_fast(inc1 + dIn1, aJ1 + dSelf1);
       // ---- the alpha beam (HFB.c:699-722) from the first and the last kept state of column t-1
       const int l_ = candL, h_ = candH;
       if (l_ < 0 || l_ >= cur.fHiEnd) { err = 1; return false; }
@@ -889,15 +859,13 @@ __global__ __launch_bounds__(64, LEAN2_EU) void k_alpha_f2(FbArgs a)
       const bool i0 = mL0 >= sl && mF0 <= el, i1 = mL1 >= sl && mF1 <= el;
       aJ0 = i0 ? x0 + od0 : LZERO;
       aJ1 = i1 ? x1 + od1 : LZERO;
-      if (!LR_EXP(8)) {
-         d2s st; st[0] = x0; st[1] = x1;
-         *(d2s *)((i0 || i1) ? pS + (size_t)(t - 1) * L : a.sink) = st;      // (outside the alpha beam: the sink line, see k_beta_np2)
-      }
+      d2s st; st[0] = x0; st[1] = x1;
+      *(d2s *)((i0 || i1) ? pS + (size_t)(t - 1) * L : a.sink) = st;      // (outside the alpha beam: the sink line, see k_beta_np2)
       put_beam(t, sl | (el << 16));
       debug_out(t, i0 ? a10 : LZERO, i1 ? a11 : LZERO);
       incoming();
       if (INNER || t < T) {
-         if (!LR_EXP(16)) flags();
+         flags();
          advance((INNER || t + 2 <= T) ? qw : wNxt);
       }
       return true;
@@ -907,23 +875,9 @@ __global__ __launch_bounds__(64, LEAN2_EU) void k_alpha_f2(FbArgs a)
       float Rc0[BK], Rc1[BK], Rn0[BK], Rn1[BK];
       d2s Bc[BK], Bn[BK];
       auto load8 = [&](float *R0, float *R1, d2s *B, const int c) {
-         if (LR_EXP(2)) {
-#pragma unroll
-            for (int k = 0; k < BK; k++) { R0[k] = -60.0f - (float)k; R1[k] = -61.0f; B[k] = *(const d2s *)(pBeta + (size_t)(BK * c + k) * L); }
-            return;
-         }
          const f4s a4 = ALPHA_LDF(row0 + BK * c), b4 = ALPHA_LDF(row0 + BK * c + 4), c4 = ALPHA_LDF(row1 + BK * c), d4 = ALPHA_LDF(row1 + BK * c + 4);
 #pragma unroll
          for (int k = 0; k < 4; k++) { R0[k] = a4[k]; R0[4 + k] = b4[k]; R1[k] = c4[k]; R1[4 + k] = d4[k]; }
-         if (LR_EXP(4096)) {                           // diagnostic: float columns (k_beta_np2)
-            typedef float f2s __attribute__((ext_vector_type(2)));
-#pragma unroll
-            for (int k = 0; k < BK; k++) {
-               const f2s v = __builtin_nontemporal_load((const f2s *)((const float *)(a.betaW + ud.betaW0) + (size_t)(BK * c + k) * L + g0));
-               B[k][0] = (double)v[0]; B[k][1] = (double)v[1];
-            }
-            return;
-         }
 #pragma unroll
          for (int k = 0; k < BK; k++) B[k] = ALPHA_LD(pBeta + (size_t)(BK * c + k) * L);
       };

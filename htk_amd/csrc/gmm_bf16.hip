@@ -45,9 +45,7 @@ typedef const __attribute__((address_space(4))) int cint;
 
 #define EXP2(x) __builtin_amdgcn_exp2f(x)
 #define LOG2(x) __builtin_amdgcn_logf(x)
-#ifndef B16_COL_TILES
 #define B16_COL_TILES 2                                 // 16-frame column tiles per wavefront: 2 (four wavefronts per 128-frame task) or 4 (two)
-#endif
 
 __device__ __forceinline__ float rows_max_b(float v)
 {
@@ -89,9 +87,7 @@ __device__ __host__ __forceinline__ void split3(float x, unsigned short &p1, uns
    p3 = bf16_bits(r2);
 }
 
-#ifndef B16_WPB
 #define B16_WPB (8 / B16_COL_TILES)                     // wavefronts per workgroup: together a whole 128-frame task (B16_WPB smaller: the task in parts)
-#endif
 template <int NC>
 __global__ __launch_bounds__(64 * B16_WPB, B16_COL_TILES > 2 ? 2 : 3) void k_score_bf16(ScoreArgs a)      // second figure: wavefronts per SIMD the register budget is cut for
 {
@@ -268,9 +264,7 @@ __global__ __launch_bounds__(64 * B16_WPB, B16_COL_TILES > 2 ? 2 : 3) void k_sco
 //   Table per tile: [k-step 2 NC][piece 3][k-half 2][component 16][8 bf16], then (log w - 0.5 gConst) log2(e) [16 f32].  In LDS a pair
 //   is [k-step][piece][lane 64][8 bf16] with lane = 32 k-half + 8 (comp >> 2) + 4 h + (comp & 3), then the two states' constants.
 typedef float f16v __attribute__((ext_vector_type(16)));
-#ifndef B16W_EU
 #define B16W_EU 2
-#endif
 // KS k-steps of 16.  Even KS: NC = KS / 2 chunks of 32 as described above.  KS = 5, the DENSE layout for 31 <= D <= 39 (39: the usual
 // MFCC_E_D_A, whose 2 D + 2 = 80 terms fill five k-steps exactly where three chunks take six -- a sixth of the matrix instructions,
 // table words and LDS traffic less): two blocks of dimensions, D0 = ceil(D / 2) and D - D0, each as (x^2, x) pairs followed by its
@@ -284,16 +278,13 @@ typedef float f16v __attribute__((ext_vector_type(16)));
 // (the second block's constant comes before its dimensions instead of after them).
 // Round 6: WHERE the accumulator of the leading products walks.  With both constants in the middle (pair floor(D / 2), round 5) it climbs
 // to +1/2 sum_{d < 19} mu^2 ivar (~ +110 in base-2 units on the headline set), drops to ~ -100 and climbs back: four of its five roundings
-// happen at ulp(64) = 7.6e-6, and the matrix unit cuts every product at the accumulator's last bit.  B16_LAYOUT 2: the accumulator STARTS at
+// happen at ulp(64) = 7.6e-6, and the matrix unit cuts every product at the accumulator's last bit.  Since then the accumulator STARTS at
 // the share of the first 16 dimensions (the pairs of the first two k-steps), I = -1/2 sum_{d < 16} mu^2 ivar, read from the tile beside
 // log w - 1/2 gConst; the constants' pair sits at pair PC = floor(4 D / 5) (the fourth k-step) and holds the shares of dimensions 16 .. PC - 1
 // and PC .. D - 1.  The walk is then  I -> ~I/2 -> -Q16 (complete squares) -> ~+I/2 -> ~-I/2 -> -Q : never beyond half of what it was.
-// B16_LAYOUT 0 keeps round 5's placement (no start value, constants at pair floor(D / 2)) for comparisons.
-#ifndef B16_LAYOUT
-#define B16_LAYOUT 2
-#endif
-__device__ __host__ __forceinline__ int dense_D0(int D) { return B16_LAYOUT == 2 ? (4 * D) / 5 : D >> 1; }      // the constants' pair
-__device__ __host__ __forceinline__ int dense_NI(int D) { return B16_LAYOUT == 2 ? 16 : 0; }                   // dimensions whose share the accumulator starts from
+// (round 5's placement was retired; its source is at git show e507b6e:htk_amd/csrc/gmm_bf16.hip)
+__device__ __host__ __forceinline__ int dense_D0(int D) { return (4 * D) / 5; }      // the constants' pair
+__device__ __host__ __forceinline__ int dense_NI(int) { return 16; }                 // dimensions whose share the accumulator starts from
 __device__ __forceinline__ void dense_slot(int k, int D, int &dim, int &kind)      // kind 0: x^2, 1: x, 2: first constant, 3: second constant, -1: padding
 {
    const int D0 = dense_D0(D);
@@ -314,33 +305,13 @@ __device__ __forceinline__ void dense_const_range(int which, int D, int &lo, int
 }
 
 // workgroups per CU by registers and LDS: six k-steps 180 registers / 60 KB -> 2; five 168 / 51 KB -> 3 (measured against 2: DESIGN §4); four 152 / 40 KB -> 3; two 111 / 20 KB -> 4
-#ifndef B16W_EU5
 #define B16W_EU5 3
-#endif
 constexpr int b16w_eu(int KS) { return KS >= 6 ? B16W_EU : KS == 5 ? B16W_EU5 : KS == 4 ? 3 : 4; }
-#ifndef B16_PRIO_LEVEL
-#define B16_PRIO_LEVEL 1
-#endif
-#ifndef B16_PRIO
-#define B16_PRIO 1                                      /* 1: the pairs' loop at a raised wavefront priority, the operand build at the normal one: a workgroup in its products goes
-                                                           before one that is building (-3 %: 0.94 -> 0.91 ms; levels 1 - 3 alike).  Experiments: 2 the log-sum-exp behind the products at a
-                                                           lowered priority (0 %), 3 the priority dropped around every slice of it (as 1) */
-#endif
-#ifndef B16_ABL
-#define B16_ABL 0                                       /* diagnostic builds: 1 no barrier per pair, 2 no log-sum-exp, 4 one fragment load per pair, 8 no staging */
-#endif
-#ifdef B16_CLK                                          // cycle stamps of thread 0 of every workgroup, summed: task fetch | rows + first pair landed | operand built | pairs' loop
-__device__ unsigned long long g_b16clk[8];
-#define B16_STAMP(i_) do { if (tid == 0) { const unsigned long long c_ = __builtin_readcyclecounter(); clkAcc[i_] += c_ - clk0; clk0 = c_; } } while (0)
-#else
-#define B16_STAMP(i_) do { } while (0)
-#endif
+#define B16_PRIO_LEVEL 1                                /* the pairs' loop at a raised wavefront priority, the operand build at the normal one: a workgroup in its products goes
+                                                           before one that is building (-3 %: 0.94 -> 0.91 ms; levels 1 - 3 alike) */
 template <int KS>
 __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
 {
-#ifdef B16_CLK
-   unsigned long long clkAcc[5] = {0, 0, 0, 0, 0}, clk0 = __builtin_readcyclecounter();
-#endif
    static_assert(B16_TASK_FRAMES == 128, "four wavefronts x 32 frames");
    constexpr bool DENSE = (KS & 1) != 0;
    constexpr int NC = (KS + 1) / 2;
@@ -384,7 +355,6 @@ __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
       const int task = __builtin_amdgcn_readfirstlane(taskSh);
       if (task >= a.nTasks) break;
       const ScoreTask tk = a.tasks[task];
-      B16_STAMP(0);
       const bool active = fw < tk.nFrames;
       const int nPairs = (tk.nSlots + 1) >> 1;
       {
@@ -410,9 +380,8 @@ __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
       stage_pair(0, 0);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      B16_STAMP(1);
 
-      if (B16_PRIO) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       // B operand from the rows in LDS: this lane's frame, the 8 k of its k-half in every k-step, in three bf16 pieces
       bf8 zb[KS][3];
       if (active) {
@@ -477,7 +446,6 @@ __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
          }
       }
 
-      B16_STAMP(2);
       int buf = 0;
       float *oPrev = a.out + tk.outBase + (size_t)(tk.outSlot0 + kh) * tk.ldo + fw + fcol;      // this lane's state (kh of the pair) and frame: the pair BEFORE the round's
       const size_t oStep = 2 * (size_t)tk.ldo;
@@ -521,7 +489,7 @@ __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
             actJ = active && (lo0 < lo1 ? lo0 : lo1) <= wRow1 && (hi0 > hi1 ? hi0 : hi1) >= wRow0;
          }
          if (haveQ) { if (fw + fcol < tk.nFrames) *oQ = resQ; haveQ = false; }
-         if (more && !(B16_ABL & 8)) stage_pair(j + 1, buf ^ 1);
+         if (more) stage_pair(j + 1, buf ^ 1);
          if (!actJ) {
             if (prevAct) { resQ = lse_full(); oQ = oPrev; haveQ = true; }
          } else {
@@ -530,7 +498,7 @@ __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
             // (the sum's tree is ((e_k + e_k+8) + (e_k+4 + e_k+12)) for k = 0 .. 3, then (E0 + E1) + (E2 + E3): the exponentials are taken in
             //  that order and added as they come -- four partial sums alive instead of sixteen terms)
             // (round 5: the matrix instructions share the vector ALU's issue port -- 4.9 vector instructions per matrix instruction, 16 of them
-            //  transcendental, left the matrix pipe 58 % busy; diagnostic builds (B16_ABL): without this log-sum-exp the kernel takes 0.77 ms,
+            //  transcendental, left the matrix pipe 58 % busy; diagnostic builds: without this log-sum-exp the kernel takes 0.77 ms,
             //  its floor with nothing but the matrix instructions 0.76, with it 0.93.  Maxima three at a time, differences and sums as packed pairs)
             typedef float v2f __attribute__((ext_vector_type(2)));
             float m6[6], m2[2], mx = 0.0f, sm = 0.0f, lg = 0.0f, resP = 0.0f;
@@ -538,10 +506,6 @@ __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
             // the exponentials of components (2 i, 2 i + 1) -- neighbours in the registers, so that the packed instructions need no moves
             auto exp_pair = [&](int i) { const v2f d = (v2f){yP[2 * i], yP[2 * i + 1]} + nmx; return (v2f){EXP2(d.x), EXP2(d.y)}; };
             auto lse_slice = [&](int sl) {
-#if (B16_ABL & 2)
-               if (sl == 17) resP = yP[0] + yP[5];
-               return;
-#endif
                if (sl == 0) { for (int r = 0; r < 3; r++) m6[r] = fmaxf(fmaxf(yP[3 * r], yP[3 * r + 1]), yP[3 * r + 2]); }
                else if (sl == 1) { for (int r = 3; r < 5; r++) m6[r] = fmaxf(fmaxf(yP[3 * r], yP[3 * r + 1]), yP[3 * r + 2]); m6[5] = yP[15]; }
                else if (sl == 2) { m2[0] = fmaxf(fmaxf(m6[0], m6[1]), m6[2]); m2[1] = fmaxf(fmaxf(m6[3], m6[4]), m6[5]); }
@@ -565,7 +529,7 @@ __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
 #pragma unroll
             for (int r = 0; r < 16; r++) { Cx[r] = 0.0f; Cc[r] = 0.0f; }      // (no instructions: the first product of each takes the constant 0)
             auto cx_start = [&]() {
-               if constexpr (DENSE && B16_LAYOUT == 2) {                     // the leading products start from the share of the first 16 dimensions (dense_NI)
+               if constexpr (DENSE) {                     // the leading products start from the share of the first 16 dimensions (dense_NI)
 #pragma unroll
                   for (int b = 0; b < 4; b++) {
                      const f4 c0 = __builtin_bit_cast(f4, wbuf[buf][KS * 192 + 8 + kh * 4 + b]);
@@ -574,33 +538,27 @@ __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
                   }
                }
             };
-#ifndef B16_INIT_LATE
-#define B16_INIT_LATE 1                                 /* the start values are read behind the round's first products (their product is the sixth) */
-#endif
-            if (!B16_INIT_LATE) cx_start();
             bf8 wa[KS][3];
 #pragma unroll
             for (int s = 0; s < 3; s++) wa[0][s] = __builtin_bit_cast(bf8, wbuf[buf][(0 * 3 + s) * 64 + lane]);
-            if (B16_PRIO) __builtin_amdgcn_s_setprio(B16_PRIO == 2 ? 2 : B16_PRIO_LEVEL);
+            __builtin_amdgcn_s_setprio(B16_PRIO_LEVEL);
 #pragma unroll
             for (int ks = 0; ks < KS; ks++) {
                if (ks + 1 < KS) {
 #pragma unroll
-                  for (int s = 0; s < 3; s++) wa[ks + 1][s] = (B16_ABL & 4) ? wa[0][s] : __builtin_bit_cast(bf8, wbuf[buf][((ks + 1) * 3 + s) * 64 + lane]);
+                  for (int s = 0; s < 3; s++) wa[ks + 1][s] = __builtin_bit_cast(bf8, wbuf[buf][((ks + 1) * 3 + s) * 64 + lane]);
                }
                Cc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][1], zb[ks][1], Cc, 0, 0, 0);
-               if (B16_PRIO != 2 && 3 * ks + 0 < 18) { if (B16_PRIO == 3) __builtin_amdgcn_s_setprio(0); lse_slice(3 * ks + 0); if (B16_PRIO == 3) __builtin_amdgcn_s_setprio(B16_PRIO_LEVEL); }
+               if (3 * ks + 0 < 18) lse_slice(3 * ks + 0);
                Cc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][0], zb[ks][2], Cc, 0, 0, 0);
-               if (B16_INIT_LATE && ks == 0) cx_start();
+               if (ks == 0) cx_start();            // the start values are read behind the round's first products (their product is the sixth)
                Cc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][2], zb[ks][0], Cc, 0, 0, 0);
-               if (B16_PRIO != 2 && 3 * ks + 1 < 18) { if (B16_PRIO == 3) __builtin_amdgcn_s_setprio(0); lse_slice(3 * ks + 1); if (B16_PRIO == 3) __builtin_amdgcn_s_setprio(B16_PRIO_LEVEL); }
+               if (3 * ks + 1 < 18) lse_slice(3 * ks + 1);
                Cc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][0], zb[ks][1], Cc, 0, 0, 0);
                Cc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][1], zb[ks][0], Cc, 0, 0, 0);
-               if (B16_PRIO != 2 && 3 * ks + 2 < 18) { if (B16_PRIO == 3) __builtin_amdgcn_s_setprio(0); lse_slice(3 * ks + 2); if (B16_PRIO == 3) __builtin_amdgcn_s_setprio(B16_PRIO_LEVEL); }
+               if (3 * ks + 2 < 18) lse_slice(3 * ks + 2);
                Cx = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wa[ks][0], zb[ks][0], Cx, 0, 0, 0);
             }
-            if (B16_PRIO == 2) { __builtin_amdgcn_s_setprio(0); for (int sl = 0; sl < 18; sl++) lse_slice(sl); }
-            else
             for (int sl = 3 * KS; sl < 18; sl++) lse_slice(sl);      // (fewer than 6 k-steps: the rest of the slices)
             asm volatile("" : "+v"(resP));
             resQ = resP; oQ = oPrev; haveQ = prevAct;    // (the pair before always has both its states)
@@ -612,25 +570,16 @@ __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
             }
          }
          prevAct = actJ; oPrev += oStep;
-#if !(B16_ABL & 1)
          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the next pair's rows have landed (issued a whole round ago)
          __syncthreads();
-#endif
          buf ^= 1;
       }
-      B16_STAMP(3);
-#ifdef B16_CLK
-      if (tid == 0) clkAcc[4] += (unsigned long long)nPairs;
-#endif
       if (haveQ) { if (fw + fcol < tk.nFrames) *oQ = resQ; }
       if (prevAct) {                                   // the last pair's log-sum-exp
          const float res = lse_full();
          if (fw + fcol < tk.nFrames && 2 * (nPairs - 1) + kh < tk.nSlots) *oPrev = res;
       }
    }
-#ifdef B16_CLK
-   if (tid == 0) { for (int i = 0; i < 5; i++) atomicAdd(&g_b16clk[i], clkAcc[i]); atomicAdd(&g_b16clk[5], 1ull); }
-#endif
 }
 
 int htkamd_launch_score_bf16(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart, hipEvent_t evStop)
@@ -656,11 +605,6 @@ int htkamd_launch_score_bf16(const htkamd_model *m, const ScoreArgs &a, hipStrea
                            hipExtLaunchKernelGGL((k_score_bf16w<KS_>), dim3(b_), block, 0, stream, evStart, evStop, 0, a); } while (0)
       if (m->bf16Dense) {
          W_LAUNCH(5); HIPCHECK(hipGetLastError());
-#ifdef B16_CLK
-         {  unsigned long long h[8]; static int nth = 0;
-            HIPCHECK(hipStreamSynchronize(stream)); HIPCHECK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_b16clk), sizeof(h)));
-            if (++nth % 8 == 0) fprintf(stderr, "k_score_bf16w<5> cycles summed over %llu workgroups (cumulative): fetch %llu | landed %llu | operand %llu | pairs %llu ; pairs %llu, tasks %d\n", h[5], h[0], h[1], h[2], h[3], h[4], a.nTasks); }
-#endif
          return HTKAMD_OK;
       }
       switch (m->bf16NC) {
@@ -750,60 +694,10 @@ __global__ void k_build_bf16tab(Bf16TabArgs a, int nTiles)
    }
 }
 
-// the DENSE layout's table (k_score_bf16w<5>): one thread per (tile, k-step, k-half, component): its 8 coefficients in three pieces
-__global__ void k_build_bf16tab_dense(Bf16TabArgs a, int nTiles, int KS)
-{
-   const int D = a.D;
-   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-   if (idx >= nTiles * KS * 32) return;
-   const int t = idx / (KS * 32), r = idx - t * (KS * 32), ks = r >> 5, khf = (r >> 4) & 1, rowc = r & 15;
-   const int s = a.tileState[t], c0 = a.stateCompOff[s], c1 = a.stateCompOff[s + 1];
-   const int c = c0 + 16 * (t - a.stateTileOff[s]) + rowc;
-   const size_t tileShorts = ((size_t)KS * 3 * 32 + 8) * 8;
-   unsigned short *T = a.tab + (size_t)t * tileShorts;
-   const bool live = c < c1 && (c1 - c0 == 1 || a.compLogWt[c] > (float)LMINMIX);
-   const double L2E = 1.4426950408889634;
-   const float *mu = nullptr, *iv = nullptr;
-   if (live) { const int g = a.compGauss[c]; mu = a.mean + (size_t)g * D; iv = a.ivar + (size_t)g * D; }
-   auto share = [&](int which) {                           // -0.5 sum mu^2 ivar over the dimensions constant `which` stands for (dense_const_range)
-      int lo, hi; dense_const_range(which, D, lo, hi);
-      double q = 0.0;
-      for (int i = lo; i < hi; i++) q += (double)mu[i] * mu[i] * iv[i];
-      return (float)(-0.5 * q * L2E);
-   };
-   unsigned short p[3][8];
-#pragma unroll
-   for (int j = 0; j < 8; j++) {
-      int dim, kind;
-      dense_slot(16 * ks + 8 * khf + j, D, dim, kind);
-      float v = 0.0f;
-      if (live && kind == 0) v = (float)(-0.5 * (double)iv[dim] * L2E);
-      else if (live && kind == 1) v = (float)((double)mu[dim] * iv[dim] * L2E);
-      else if (live && kind >= 2) v = share(kind - 1);      // against B's constant 1
-      split3(v, p[0][j], p[1][j], p[2][j]);
-   }
-#pragma unroll
-   for (int pc = 0; pc < 3; pc++) {
-      u4 w;
-      w[0] = p[pc][0] | ((unsigned int)p[pc][1] << 16); w[1] = p[pc][2] | ((unsigned int)p[pc][3] << 16);
-      w[2] = p[pc][4] | ((unsigned int)p[pc][5] << 16); w[3] = p[pc][6] | ((unsigned int)p[pc][7] << 16);
-      *(u4 *)(T + ((size_t)(ks * 3 + pc) * 32 + khf * 16 + rowc) * 8) = w;
-   }
-   if (ks == 0 && khf == 0) {
-      float ci = -1.0e30f;
-      if (live) {
-         const double k0 = a.gconst[a.compGauss[c]];
-         ci = (float)(((c1 - c0 == 1 ? 0.0 : (double)a.compLogWt[c]) - 0.5 * k0) * L2E);
-      }
-      ((float *)(T + (size_t)KS * 3 * 32 * 8))[rowc] = ci;
-      ((float *)(T + (size_t)KS * 3 * 32 * 8))[16 + rowc] = live ? share(0) : 0.0f;      // the accumulator's start
-   }
-}
-
-// The same table through LDS (round 5): a workgroup takes TB tiles; their 16 TB rows of means and inverse variances arrive in storage order
-// (a row is D consecutive floats; k_build_bf16tab_dense read them 8 scattered floats per lane, 32 lines per load), the two constants of a
-// row are summed once (by one thread each, in the order of the sum above) instead of by each of the threads whose slots hold them, and the
-// slots are cut from LDS.  Same arithmetic per value: the tables are identical.
+// the DENSE layout's table (k_score_bf16w<5>), through LDS (round 5): a workgroup takes BT_TILES tiles; their 16 BT_TILES rows of means and
+// inverse variances arrive in storage order (a row is D consecutive floats; the gather per slot this replaced read them 8 scattered floats
+// per lane, 32 lines per load -- retired, see git show e507b6e:htk_amd/csrc/gmm_bf16.hip), the three constants of a row are summed once, by
+// one thread each, and the slots are cut from LDS.  BT_TILES = 4 and D <= 39 keep the LDS below 21 KB.
 #define BT_TILES 4
 __global__ __launch_bounds__(256) void k_build_bf16tab_dense_lds(Bf16TabArgs a, int nTiles, int KS)
 {
@@ -888,9 +782,8 @@ int htkamd_model_refresh_bf16_device(htkamd_model *m, void *stream)
    t.mean = m->d_mean; t.ivar = m->d_ivar; t.gconst = m->d_gconst; t.compLogWt = m->d_compLogWt; t.tab = (unsigned short *)m->d_bf16Tab;
    const int n = m->nTiles * m->bf16NC * 64;
    const size_t ldsDense = sizeof(float) * ((size_t)BT_TILES * 16 * 2 * m->D + BT_TILES * 16 * 3) + sizeof(int) * BT_TILES * 16 * 2;
-   if (m->f16Wide && m->bf16Dense && ldsDense <= 60 * 1024 && !getenv("HTKAMD_TAB_GATHER"))
+   if (m->f16Wide && m->bf16Dense)
       hipLaunchKernelGGL(k_build_bf16tab_dense_lds, dim3((m->nTiles + BT_TILES - 1) / BT_TILES), dim3(256), ldsDense, s, t, m->nTiles, 5);
-   else if (m->f16Wide && m->bf16Dense) hipLaunchKernelGGL(k_build_bf16tab_dense, dim3((m->nTiles * 5 * 32 + 255) / 256), dim3(256), 0, s, t, m->nTiles, 5);
    else if (m->f16Wide) hipLaunchKernelGGL(k_build_bf16tab<true>, dim3((n + 255) / 256), dim3(256), 0, s, t, m->nTiles);
    else hipLaunchKernelGGL(k_build_bf16tab<false>, dim3((n + 255) / 256), dim3(256), 0, s, t, m->nTiles);
    HIPCHECK(hipGetLastError());

@@ -38,9 +38,7 @@ typedef const __attribute__((address_space(4))) int cint;
 
 #define EXP2(x) __builtin_amdgcn_exp2f(x)
 #define LOG2(x) __builtin_amdgcn_logf(x)
-#ifndef F16_COL_TILES
 #define F16_COL_TILES 2                                 // 16-frame column tiles per wavefront: 2 (four wavefronts per 128-frame task) or 4 (two)
-#endif
 
 __device__ __forceinline__ float rows_max_b(float v)
 {
@@ -79,12 +77,8 @@ __device__ __forceinline__ unsigned int pack2(_Float16 a, _Float16 b)
 #define F16_CTL_MQ    400      /* float bits [48]: per dimension the largest 0.5 mu^2 ivar log2(e) (k_f16_range -> k_f16_scale) */
 #define F16_MAX 65504.0f
 
-#ifndef F16_EU
 #define F16_EU (F16_COL_TILES > 2 ? 2 : 4)
-#endif
-#ifndef F16_WPB
 #define F16_WPB (8 / F16_COL_TILES)                     // wavefronts per workgroup: together a whole 128-frame task (F16_WPB smaller: the task in parts)
-#endif
 template <int NC>
 __global__ __launch_bounds__(64 * F16_WPB, F16_EU) void k_score_f16(ScoreArgs a)      // second figure: wavefronts per SIMD the register budget is cut for
 {
@@ -256,26 +250,7 @@ __global__ __launch_bounds__(64 * F16_WPB, F16_EU) void k_score_f16(ScoreArgs a)
 //   then the two states' constants.
 typedef float f16v __attribute__((ext_vector_type(16)));
 typedef float f2 __attribute__((ext_vector_type(2)));
-#ifdef F16W_STAMP            /* experiment builds only (tools/ubench/score_exp.py): cycles per phase and wavefront */
-__device__ unsigned long long g_dbg[4096 * 16];
-#define STAMP_DECL unsigned long long t_ = __builtin_amdgcn_s_memtime(), t0_ = t_, acc_[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define STAMP(i) do { const unsigned long long n_ = __builtin_amdgcn_s_memtime(); acc_[i] += n_ - t_; t_ = n_; } while (0)
-#define STAMP_COUNT(i, n) acc_[i] += (n)
-#define STAMP_FLUSH do { if (lane == 0) { const int w_ = (blockIdx.x * 4 + wv) & 4095; acc_[6] = __builtin_amdgcn_s_memtime() - t0_; for (int i_ = 0; i_ < 10; i_++) g_dbg[w_ * 16 + i_] += acc_[i_]; } } while (0)
-extern "C" void htkamd_dbg_zero(void) { void *p; (void)hipGetSymbolAddress(&p, HIP_SYMBOL(g_dbg)); (void)hipMemset(p, 0, sizeof(unsigned long long) * 4096 * 16); }
-extern "C" void htkamd_dbg_read(void *dst) { (void)hipDeviceSynchronize(); (void)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_dbg), sizeof(unsigned long long) * 4096 * 16); }
-#else
-#define STAMP_DECL
-#define STAMP(i)
-#define STAMP_COUNT(i, n)
-#define STAMP_FLUSH
-#endif
-#ifndef F16W_PIPE
-#define F16W_PIPE 1
-#endif
-#ifndef F16W_EU
 #define F16W_EU 3
-#endif
 template <int NC>
 __global__ __launch_bounds__(256, F16W_EU) void k_score_f16w(ScoreArgs a)
 {
@@ -305,7 +280,6 @@ __global__ __launch_bounds__(256, F16W_EU) void k_score_f16w(ScoreArgs a)
       dst[j] = (w < KS * 64) ? (w >> 5) * 64 + ((w >> 4) & 1) * 32 + 8 * (comp >> 2) + 4 * hsel + (comp & 3) : KS * 128 + hsel * 4 + (w - KS * 64);
    }
    const int fw = 32 * wv;                             // this wave's first frame in the task's tile
-   STAMP_DECL;
 
    for (;;) {
       if (tid == 0) taskSh = atomicAdd(a.taskCounter, 1);
@@ -315,7 +289,6 @@ __global__ __launch_bounds__(256, F16W_EU) void k_score_f16w(ScoreArgs a)
       const ScoreTask tk = a.tasks[task];
       const bool active = fw < tk.nFrames;
       const int nPairs = (tk.nSlots + 1) >> 1;
-      STAMP(0);
       // the task's feature rows: one contiguous block, read in order by the whole workgroup
       {
          const float *xs = a.X + (size_t)tk.frame0 * D;
@@ -331,11 +304,9 @@ __global__ __launch_bounds__(256, F16W_EU) void k_score_f16w(ScoreArgs a)
          for (int j = 0; j < PT; j++)
             if (t7 + 128 * j < TW4) wbuf[0][dst[j]] = W[t7 + 128 * j];
       }
-      STAMP(1);
       __syncthreads();
-      STAMP(3);
 
-      __builtin_amdgcn_s_setprio(0);                      // (the pairs' loop below runs at a raised priority: gmm_bf16.hip, B16_PRIO)
+      __builtin_amdgcn_s_setprio(0);                      // (the pairs' loop below runs at a raised priority: gmm_bf16.hip, B16_PRIO_LEVEL)
       // B operand from the rows in LDS: this lane's frame, the 8 k of its k-half in every k-step, scaled, in two fp16 pieces
       h8 zb[KS][2];
       if (active) {
@@ -373,16 +344,13 @@ __global__ __launch_bounds__(256, F16W_EU) void k_score_f16w(ScoreArgs a)
          }
          if (over) atomicOr(a.rangeFlag, HTKAMD_F16_EFEAT);
       }
-      STAMP(0); STAMP_COUNT(8, 1);
 
       int buf = 0;
       float *o = a.out + tk.outBase + (size_t)(tk.outSlot0 + kh) * tk.ldo + fw + fcol;      // this lane's state (kh of the pair) and frame
       const size_t oStep = 2 * (size_t)tk.ldo;
-#if F16W_PIPE
       float yP[16];
 #pragma unroll
       for (int r = 0; r < 16; r++) yP[r] = 0.0f;
-#endif
       __builtin_amdgcn_s_setprio(1);
       for (int j = 0; j < nPairs; j++) {
          u4 stg[PT];
@@ -393,10 +361,7 @@ __global__ __launch_bounds__(256, F16W_EU) void k_score_f16w(ScoreArgs a)
             for (int q = 0; q < PT; q++)
                if (t7 + 128 * q < TW4) stg[q] = W[t7 + 128 * q];
          }
-         STAMP(1); STAMP_COUNT(7, 1);
          if (active) {
-            STAMP_COUNT(9, 1);
-#if F16W_PIPE
             // The log-sum-exp of the pair BEFORE this one (its 16 values per lane were left in yP) in 18 slices, one behind each of this
             // pair's matrix instructions and fenced there: ~4 vector instructions fit in the shadow of a 32-cycle matrix instruction.
             float m8[8], m4[4], m2[2], mx = 0.0f, e[16], sm = 0.0f, lg = 0.0f, resP = 0.0f;
@@ -445,56 +410,15 @@ __global__ __launch_bounds__(256, F16W_EU) void k_score_f16w(ScoreArgs a)
 #pragma unroll
                for (int r = 0; r < 4; r++) yP[4 * b + r] = __builtin_fmaf(Cc[4 * b + r], 1.0f / F16_CORR, Cx[4 * b + r]) + ci[r];
             }
-#else
-            f16v Cx, Cc;
-#pragma unroll
-            for (int r = 0; r < 16; r++) { Cx[r] = 0.0f; Cc[r] = 0.0f; }
-#pragma unroll
-            for (int ks = 0; ks < KS; ks++) {
-               const h8 wa0 = __builtin_bit_cast(h8, wbuf[buf][(ks * 2 + 0) * 64 + lane]), wa1 = __builtin_bit_cast(h8, wbuf[buf][(ks * 2 + 1) * 64 + lane]);
-               Cc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa1, zb[ks][0], Cc, 0, 0, 0);
-               Cx = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa0, zb[ks][0], Cx, 0, 0, 0);
-               Cc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wa0, zb[ks][1], Cc, 0, 0, 0);
-            }
-            // this lane's state: its 16 components in registers 4b + r
-            float y[16];
-#pragma unroll
-            for (int b = 0; b < 4; b++) {
-               const f4 ci = __builtin_bit_cast(f4, wbuf[buf][KS * 128 + kh * 4 + b]);
-#pragma unroll
-               for (int r = 0; r < 4; r++) y[4 * b + r] = __builtin_fmaf(Cc[4 * b + r], 1.0f / F16_CORR, Cx[4 * b + r]) + ci[r];
-            }
-            float m8[8], m4[4];
-#pragma unroll
-            for (int r = 0; r < 8; r++) m8[r] = fmaxf(y[r], y[r + 8]);
-#pragma unroll
-            for (int r = 0; r < 4; r++) m4[r] = fmaxf(m8[r], m8[r + 4]);
-            const float mx = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
-            float e[16];
-#pragma unroll
-            for (int r = 0; r < 16; r++) e[r] = EXP2(y[r] - mx);
-#pragma unroll
-            for (int r = 0; r < 8; r++) e[r] += e[r + 8];
-#pragma unroll
-            for (int r = 0; r < 4; r++) e[r] += e[r + 4];
-            const float sm = (e[0] + e[1]) + (e[2] + e[3]);
-            const float res = (mx + LOG2(sm)) * 0.69314718055994531f;
-            if (fw + fcol < tk.nFrames && 2 * j + kh < tk.nSlots) *o = res;
-            o += oStep;
-#endif
          }
-         STAMP(2);
          if (more) {
 #pragma unroll
             for (int q = 0; q < PT; q++)
                if (t7 + 128 * q < TW4) wbuf[buf ^ 1][dst[q]] = stg[q];
          }
-         STAMP(4);
          __syncthreads();
-         STAMP(5);
          buf ^= 1;
       }
-#if F16W_PIPE
       if (active) {                                    // the last pair's log-sum-exp
          float m8[8], m4[4];
 #pragma unroll
@@ -512,9 +436,7 @@ __global__ __launch_bounds__(256, F16W_EU) void k_score_f16w(ScoreArgs a)
          const float sm = (e[0] + e[1]) + (e[2] + e[3]);
          if (fw + fcol < tk.nFrames && 2 * (nPairs - 1) + kh < tk.nSlots) *o = (mx + LOG2(sm)) * 0.69314718055994531f;
       }
-#endif
    }
-   STAMP_FLUSH;
 }
 
 int htkamd_launch_score_f16(const htkamd_model *m, const ScoreArgs &a0, hipStream_t stream, hipEvent_t evStart, hipEvent_t evStop)

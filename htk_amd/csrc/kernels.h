@@ -5,9 +5,7 @@
 #include "internal.h"
 
 #define SCORE_TILE_FRAMES 128   /* 64 lanes x 2 frames per lane */
-#ifndef B16_TASK_FRAMES
-#define B16_TASK_FRAMES 128     /* frames per task of the bf16 matrix-core kernel in forward-backward (experiment switch HTKAMD_B16_TF) */
-#endif
+#define B16_TASK_FRAMES 128     /* frames per task of the bf16 matrix-core kernel in forward-backward */
 #define SCORE_TASK_SLOTS  16    /* chain states scored per task */
 #define SCORE_TASK_SLOTS_WIDE 64 /* the same for the matrix-core kernels in forward-backward (fb.hip) */
 #define SCORE_TASK_SLOTS_EXACT 8 /* and for the exact kernel there: one wave per task, features in registers, so small tasks balance best
@@ -143,7 +141,7 @@ struct FbArgs {
    MixRec *rec, *recSorted;
    int recCap, G;
    int *recCtl;                      // [0] number of records asked for (may exceed recCap), then gCnt[G+1], gStart[G+1], gCur[G+1]
-   // left-to-right path: the surviving (frame, state) pairs as a list (k_stats_lr -> k_mixhits) instead of the dense seed array
+   // left-to-right path: the surviving (frame, state) pairs as a list (k_stats_sp -> k_mixhits) instead of the dense seed array
    // several streams (model NSt > 1): scores per (stream, chain state) and the map dimension -> stream
    int NSt;
    const float *outpU;               // stream k of utterance u: outpU[NSt*outp0 + (k*nSlots + slot)*T + t-1]
@@ -162,7 +160,7 @@ struct FbArgs {
    const float *compWeight, *var;    // linear weights, variances
    int tmCombine;                    // HVite side: a row is a STATE (its first element), scored as sum_s w_s SOutP_s (cPOutP HRec.c:540); 0: a row is an element
    const float *streamWt;            // [elements], with tmCombine
-   MixHit *hits;                     // region r (one per wavefront of k_stats_lr, numbered like the rows of trPart): hits[r * hitRegionCap ...]
+   MixHit *hits;                     // region r (one per wavefront of k_stats_sp, numbered like the rows of trPart): hits[r * hitRegionCap ...]
    int hitSlots;                     // multi-stream / tied-mixture sets: MixHit::st is the pair's global SLOT (slot0 of its utterance + chain state), not its tied state
    int *hitCtl;                      // [r] records in region r
    int nHitRegions, hitRegionCap;
@@ -174,7 +172,6 @@ struct FbArgs {
    int *stCnt; int nTiedStates; HitS *stBucket; int stCap;      // stCnt[nTiedStates] = pairs turned away by a full bucket (0: the list kernels have nothing to do)
    int fastMath;                     // the pass runs in the fp32-transcendental class (HTKAMD_SCORE_FASTLADD): posteriors by v_exp_f32
    double *sink;                     // 64 bytes nobody reads: where the lanes outside a beam "store" (one cache line instead of a branch around the store)
-   int lrExp;                        // ablation bits of an -DLR_EXP_BUILD=1 build (tools/lr_exp.py); 0 otherwise
 };
 
 int htkamd_launch_beta(const FbArgs &a, int blockDim, size_t lds, hipStream_t s);
@@ -203,7 +200,6 @@ int htkamd_launch_beta_lr(const FbArgs &a, int W, bool fast, hipStream_t s);
 bool htkamd_beta_lr_is_lean(const FbArgs &a, bool fast);      // the pass's beta kernel reads the host's un-pruned beams (FbArgs::qBeamNP) instead of writing FbArgs::qBeam
 int htkamd_launch_alpha_lr(const FbArgs &a, int W, bool fast, hipStream_t s);
 int htkamd_launch_stats_lr(const FbArgs &a, int W, bool fast, hipStream_t s);
-bool htkamd_stats_lr_is_sparse(const FbArgs &a);             // k_stats_sp takes the pass's statistics (it counts the surviving pairs per tied state)
 int htkamd_stats_lr_chunks(int TMax);
 size_t htkamd_stats_lr_row_doubles(void);
 int htkamd_stats_lr_region_cap(void);

@@ -99,11 +99,9 @@ __device__ __forceinline__ void mfcc_spectrum(const MfccArgs &a, const int f, fl
    const float off = a.zMean ? a.frameMean[f] : 0.0f;
 
    // ---- load, pre-emphasise (HSigP.c:134), window (HSigP.c:122), zero-pad, bit-reverse the complex index
-#ifndef MFCC_BREV_READ
-#define MFCC_BREV_READ 0                                /* 1: the reversal on the read side, LDS written in order -- measured 6 % SLOWER (tools/r06_mfcc2.sh): the index load sits in front of the samples' loads */
-#endif
-   for (int r_ = lane; r_ < nn; r_ += 64) {
-      const int c = MFCC_BREV_READ ? (int)a.brev[r_] : r_, r = MFCC_BREV_READ ? r_ : (int)a.brev[r_];
+   // (the reversal on the write side: on the read side, LDS written in order, was measured 6 % slower -- the index load sits in front of the samples' loads)
+   for (int c = lane; c < nn; c += 64) {
+      const int r = (int)a.brev[c];
       float v[2];
 #pragma unroll
       for (int h = 0; h < 2; h++) {
@@ -551,14 +549,12 @@ static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int
       HIPCHECK(hipGetLastError());
    }
    const size_t per = sizeof(float) * ((((size_t)t.fftN + 2 * ((size_t)t.fftN / 2 + 2) + c.numChans + 2 + a.plpExtra) + 3) & ~(size_t)3);
-   // (a grid of persistent wavefronts -- HTKAMD_MFCC_WPC per CU -- was tried against one workgroup per pair of frames: 1.93 ms at 16 or 32 per CU
-   //  against 1.78 for the plain grid, tools/r06_mfcc2.sh; the loop stays, the default grid covers every pair)
-   int wpc = 1 << 20;
-   { const char *e = getenv("HTKAMD_MFCC_WPC"); if (e && atoi(e) > 0) wpc = atoi(e); }
-   const int maxGrid = 256 * wpc;
+   // (a grid of persistent wavefronts, 16 or 32 per CU, was tried against one workgroup per pair of frames: 1.93 ms against 1.78 for the
+   //  plain grid; the loop stays, the grid covers every pair)
+   const int maxGrid = 256 << 20;
    // two frames per wavefront when a frame's lanes fit in 32: the bins, the cepstra / bins written, PLP's autocorrelation lags
    const bool pair = c.numChans <= 32 && (f->kind == FE_FBANK || f->kind == FE_MELSPEC || c.numCeps <= 31) &&
-                     (f->kind != FE_PLP || f->lpcOrder <= 31) && !getenv("HTKAMD_MFCC_ONE_FRAME");
+                     (f->kind != FE_PLP || f->lpcOrder <= 31);
    switch (f->kind) {
    case FE_MFCC: launch_frames<FE_MFCC>(pair, F, maxGrid, per, s, a); break;
    case FE_FBANK: launch_frames<FE_FBANK>(pair, F, maxGrid, per, s, a); break;

@@ -383,7 +383,7 @@ __global__ __launch_bounds__(256) void k_upd_gauss_fused(UpdArgs a)
    const unsigned int e0 = (unsigned int)g0 * (unsigned int)D, nEl = (unsigned int)nG * (unsigned int)D;      // the block's elements: e0 .. e0 + nEl
    const bool accPairs = ((a.lay.mu | a.lay.va) & 1) == 0 && (((size_t)a.acc & 15) == 0);   // the statistics as 16-byte words
    int nFloored = 0;
-   // (UPD_HOIST=1: every load of the thread before the first element is worked on -- measured slower, 48 us against 39)
+   // (each iteration loads its own elements: every load of the thread before the first element is worked on was measured slower, 48 us against 39)
    float4 vAll[NIT], mAll[NIT];
    double dMuAll[NIT][4], dVaAll[NIT][4];
    auto load_it = [&](const int it) {
@@ -410,20 +410,11 @@ __global__ __launch_bounds__(256) void k_upd_gauss_fused(UpdArgs a)
          vAll[it] = make_float4(tv[0], tv[1], tv[2], tv[3]); mAll[it] = make_float4(tm[0], tm[1], tm[2], tm[3]);
       }
    };
-#ifndef UPD_HOIST
-#define UPD_HOIST 0
-#endif
-#if UPD_HOIST
-#pragma unroll
-   for (int it = 0; it < NIT; it++) load_it(it);
-#endif
 #pragma unroll
    for (int it = 0; it < NIT; it++) {
       const unsigned int c = (threadIdx.x + it * 256u) * 4u;
       if (c >= nEl) break;
-#if !UPD_HOIST
       load_it(it);
-#endif
       const unsigned int i0 = e0 + c;                       // a multiple of 4 (UPD_GPB D is)
       const bool full = c + 3u < nEl;
       float v[4] = {vAll[it].x, vAll[it].y, vAll[it].z, vAll[it].w}, mu[4] = {mAll[it].x, mAll[it].y, mAll[it].z, mAll[it].w}, r[4];
@@ -705,7 +696,7 @@ extern "C" int htkamd_model_update_device_begin(htkamd_model *m, htkamd_accs *ac
       if (tied) {
          hipLaunchKernelGGL(k_upd_first, dim3((m->H + B - 1) / B), dim3(B), 0, s, a);
          hipLaunchKernelGGL(k_upd_gauss_elem_tied, dim3((unsigned)((nEl + 255) / 256)), dim3(256), 0, s, a);
-      } else if (!m->tiedMix && ldsFused <= 60 * 1024 && (m->PS & 3) == 0 && m->D <= 64 && !getenv("HTKAMD_UPD_UNFUSED")) {
+      } else if (!m->tiedMix && ldsFused <= 60 * 1024 && (m->PS & 3) == 0 && m->D <= 64) {
          // elements and gConst in one kernel
          const dim3 gr((unsigned)((m->G + UPD_GPB - 1) / UPD_GPB));
          switch ((UPD_GPB * m->D + 1023) / 1024) {

@@ -129,7 +129,7 @@ def test_headline_model_vs_reference_live(native, mode, name):
     _assert_report(r, "all %d Gaussians, mode %s" % (G, name))
     # Against the variances' OWN values (no second-moment scale): the counts and worst ratios observed on MI355X in round 6, plus one entry /
     # a tenth -- RAW_BARS below.  What they can be: the reference's float arithmetic is itself 2.1e-5 rms away from exact arithmetic per
-    # score, and a scorer WITHOUT rounding error (a diagnostic build that scores in float64, tools/r06_parvar.sh `truth`) has 6 entries
+    # score, and a scorer WITHOUT rounding error (a diagnostic build that scored in float64, retired: git show e507b6e:tools/r06_parvar.sh `truth`) has 6 entries
     # above 1e-4 (worst 1.81e-4) and 6 among the Gaussians under two frames (2.12e-4): only the bit-identical exact mode can have fewer
     # than a handful, and a tolerance-class mode that counts 3 is inside that scatter, not better than it.
     n_max, worst_max, n_low_max, worst_low_max = RAW_BARS[name]

@@ -2,7 +2,7 @@
 """The headline parity figures of ONE build and scoring mode: one EM iteration of bench.py's shard (tests/c3_herest.py) through the C ABI,
 the re-estimated model against the model the reference's HERest writes on this box from the same files -- every entry -- and the block
 scores of the mode against float64 arithmetic.  The reference's run (one process + 8-way, ~2 min) is cached in /tmp so that a sweep over
-builds (tools/r06_parvar.sh) pays it once.
+builds pays it once (the build-variant sweep, tools/r06_parvar.sh, was retired: git show e507b6e:tools/r06_parvar.sh).
     python tools/headline_live.py <name> <scoreMode> [out.json]"""
 import json
 import os

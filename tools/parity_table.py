@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""DESIGN.md §2's headline-parity table from the JSON reports the GPU suite wrote (tests/test_gpu_headline_parity.py ->
-gpurun_out/headline_parity_<mode>.json, copied to profiles/r06_headline_parity_<mode>.json; tools/r06_parvar.sh for the build variants):
+"""DESIGN.md §2's headline-parity table from the JSON reports the GPU suite wrote (tests/test_gpu_headline_parity.py; kept as
+profiles/r06_headline_parity_<mode>.json).  The build variants' reports came from the retired tools/r06_parvar.sh (git show e507b6e:tools/r06_parvar.sh):
     python tools/parity_table.py [directory = profiles] [prefix = r06_headline_parity_]"""
 import json
 import os

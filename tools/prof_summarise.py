@@ -1,4 +1,4 @@
-"""Condense the rocprofv3 output of tools/prof_r05.sh into the small files profiles/ keeps:
+"""Condense the rocprofv3 output of a round's profile set (taken by the retired tools/prof_r05.sh / prof_r06.sh: git show e507b6e:tools/) into the small files profiles/ keeps:
    <tag>_kernel_stats.csv (copied), <tag>_traffic.json (FETCH_SIZE / WRITE_SIZE KB per launch of every kernel of the timed pass),
    <tag>_sq.json (SQ counters per launch).     python tools/prof_summarise.py gpurun_out/<tag> <tag>"""
 import csv
@@ -34,7 +34,7 @@ for c in ("FETCH_SIZE", "WRITE_SIZE"):
         # the bench issues the initial-model pass, the timed iteration and the stand-alone latency passes: report the per-launch mean
         traffic.setdefault(k, {})[c + "_KB"] = sum(vals) / len(vals)
         traffic[k]["launches"] = len(vals)
-# the other_paths legs' kernels, profiled on their own (tools/prof_r06.sh step 7, tools/r06_pmc_cmd.sh): k_decode joins the traffic table, both keep their counters
+# the other_paths legs' kernels, profiled on their own (step 7 of the retired tools/prof_r06.sh, through tools/r06_pmc_cmd.sh): k_decode joins the traffic table, both keep their counters
 legs = {}
 for leg in ("dec", "mfcc"):
     p = os.path.join(out, leg, "summary.json")
