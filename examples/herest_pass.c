@@ -32,6 +32,7 @@ int main(int argc, char **argv)
    const htkamd_model_desc *d = htkamd_mmf_desc(mmf);
    const char *kind = htkamd_mmf_parm_kind(mmf);
    const int hasD = strstr(kind, "_D") != NULL, hasA = strstr(kind, "_A") != NULL;
+   if (htkamd_mmf_inv_cov(mmf)) { fprintf(stderr, "re-estimation of FULLC (<INVCOVAR>) sets is not supported\n"); return 1; }
    htkamd_model *model; CHECK(htkamd_model_create(d, &model));
 
    /* parameter files + label files -> one table of statics, frame offsets, model sequences */

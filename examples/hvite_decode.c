@@ -28,7 +28,9 @@ int main(int argc, char **argv)
    const htkamd_model_desc *d = htkamd_mmf_desc(mmf);
    const char *kind = htkamd_mmf_parm_kind(mmf);
    const int hasD = strstr(kind, "_D") != NULL, hasA = strstr(kind, "_A") != NULL;
-   htkamd_model *model; CHECK(htkamd_model_create(d, &model));
+   htkamd_model *model;                                  /* a FULLC set: its packed inverse covariances in place of the variances */
+   if (htkamd_mmf_inv_cov(mmf)) CHECK(htkamd_model_create_full(d, htkamd_mmf_inv_cov(mmf), &model));
+   else CHECK(htkamd_model_create(d, &model));
    htkamd_net *net; CHECK(htkamd_net_build(slf, dict, mmf, &net));
    htkamd_decoder *dec; CHECK(htkamd_decoder_create(model, htkamd_net_get(net), lmScale, &dec));
 

@@ -150,7 +150,12 @@ class Model:
                       _p(k["transN"]), _p(k["transOff"]), _p(k["transP"]), _p(k["hmmTrans"]), _p(k["hmmStateOff"]), _p(k["hmmState"]),
                       self.NS, _p(k["dimStream"]), int(pk.get("hsKind", 0) or 0), _p(k["streamWeight"]))
         self.h = C.c_void_p()
-        check(lib().htkamd_model_create(C.byref(d), C.byref(self.h)), "model_create")
+        self.full = pk.get("invCov") is not None
+        if self.full:       # FULLC set: the packed inverse-covariance triangles, desc.var unused (htkamd_model_create_full)
+            k["invCov"] = f32(pk["invCov"]).reshape(-1)
+            check(lib().htkamd_model_create_full(C.byref(d), _p(k["invCov"]), C.byref(self.h)), "model_create_full")
+        else:
+            check(lib().htkamd_model_create(C.byref(d), C.byref(self.h)), "model_create")
         self.D, self.S, self.C, self.G = d.vecSize, d.numStates, d.numComp, d.numGauss
         self.nT, self.H = d.numTrans, d.numPhys
         self.maxN = int(np.max(k["transN"]))
@@ -233,7 +238,21 @@ class Model:
                    transP=np.empty(len(k["transP"]), np.float32))
         check(lib().htkamd_model_get_params(self.h, _p(out["mean"]), _p(out["var"]), _p(out["gconst"]),
                                             _p(out["compWeight"]), _p(out["transP"])), "model_get_params")
+        if self.full:
+            out["invCov"] = self.get_inv_cov()
         return out
+
+    def get_inv_cov(self) -> np.ndarray:
+        """FULLC model: the inverse covariances [G, D(D+1)/2], lower triangles packed row-major (htkamd_model_get_inv_cov)."""
+        out = np.empty((self.G, self.D * (self.D + 1) // 2), np.float32)
+        check(lib().htkamd_model_get_inv_cov(self.h, _p(out)), "model_get_inv_cov")
+        return out
+
+    def set_inv_cov(self, invCov, gconst=None):
+        """FULLC model: new inverse covariances; gconst None = FixFullGConst(mp, -CovDet(inv)) (htkamd_model_set_inv_cov)."""
+        ic = np.ascontiguousarray(invCov, np.float32).reshape(-1)
+        gc = None if gconst is None else np.ascontiguousarray(gconst, np.float32)
+        check(lib().htkamd_model_set_inv_cov(self.h, _p(ic), _p(gc) if gc is not None else None), "model_set_inv_cov")
 
     def outp_block(self, X: np.ndarray, states: np.ndarray, mode: int = 0) -> np.ndarray:
         """Scores [T, ns] of the listed tied states (HIP kernel K1), returned frame-major for convenience."""
@@ -827,6 +846,11 @@ class Mmf:
         self.logical = {L.htkamd_mmf_logical_name(self.h, C.c_int(i)).decode(): L.htkamd_mmf_logical_phys(self.h, C.c_int(i)) for i in range(n)}
         vf = L.htkamd_mmf_var_floor(self.h)
         self.var_floor = np.ctypeslib.as_array(vf, (self.desc.vecSize,)).copy() if vf else None
+        L.htkamd_mmf_inv_cov.restype = C.POINTER(C.c_float)
+        ic = L.htkamd_mmf_inv_cov(self.h)
+        D = self.desc.vecSize
+        self.inv_cov = np.ctypeslib.as_array(ic, (self.desc.numGauss * (D * (D + 1) // 2),)).reshape(self.desc.numGauss, -1).copy() if ic else None
+        self.cov_kind = "FULLC" if self.inv_cov is not None else "DIAGC"
 
     def packed(self) -> dict:
         """The flat description as the dict of numpy arrays Model() takes."""
@@ -838,12 +862,15 @@ class Mmf:
         pk = dict(vecSize=D, numStates=S, numComp=Cn, numGauss=G, numTrans=nT, numPhys=H,
                   stateCompOff=arr(d.stateCompOff, S * max(d.numStreams, 1) + 1, C.c_int), compWeight=arr(d.compWeight, Cn, C.c_float),
                   compGauss=arr(d.compGauss, Cn, C.c_int), mean=arr(d.mean, G * D, C.c_float).reshape(G, D),
-                  var=arr(d.var, G * D, C.c_float).reshape(G, D),
+                  var=arr(d.var, G * D, C.c_float).reshape(G, D) if d.var else None,
                   gconst=arr(d.gconst, G, C.c_float) if d.gconst else None,
                   transN=arr(d.transN, nT, C.c_int), transOff=transOff, transP=arr(d.transP, int(transOff[-1]), C.c_float),
                   hmmTrans=arr(d.hmmTrans, H, C.c_int), hmmStateOff=hmmStateOff, hmmState=arr(d.hmmState, int(hmmStateOff[-1]), C.c_int),
                   numStreams=max(d.numStreams, 1), dimStream=arr(d.dimStream, D, C.c_int) if d.numStreams > 1 else None, hsKind=int(d.hsKind),
                   streamWeight=arr(d.streamWeight, S * d.numStreams, C.c_float) if (d.numStreams > 1 and d.streamWeight) else None)
+        if self.inv_cov is not None:      # FULLC: [G, D(D+1)/2] packed lower triangles; var holds placeholders
+            pk["invCov"] = self.inv_cov.copy()
+            pk["covKind"] = "FULLC"
         return pk
 
     def sharing(self):
@@ -863,6 +890,14 @@ class Mmf:
 
     def write(self, params: dict, one_file=None, out_dir=None, binary=False):
         g = params.get("gconst")
+        if self.inv_cov is not None:      # FULLC set: params["invCov"] in place of the variances (htkamd_mmf_write_full)
+            if params.get("invCov") is None:
+                raise HtkAmdError("mmf_write: a FULLC set is written from params['invCov'] (the packed inverse covariances), which is missing")
+            check(lib().htkamd_mmf_write_full(self.h, _p(np.ascontiguousarray(params["mean"], np.float32)), _p(np.ascontiguousarray(params["invCov"], np.float32)),
+                                              _p(np.ascontiguousarray(g, np.float32)) if g is not None else None,
+                                              _p(np.ascontiguousarray(params["compWeight"], np.float32)), _p(np.ascontiguousarray(params["transP"], np.float32)),
+                                              one_file.encode() if one_file else None, out_dir.encode() if out_dir else None, C.c_int(1 if binary else 0)), "mmf_write_full")
+            return
         fn = lib().htkamd_mmf_write_binary if binary else lib().htkamd_mmf_write
         check(fn(self.h, _p(np.ascontiguousarray(params["mean"], np.float32)), _p(np.ascontiguousarray(params["var"], np.float32)),
                                      _p(np.ascontiguousarray(g, np.float32)) if g is not None else None,
@@ -873,6 +908,14 @@ class Mmf:
         """SaveHMMSet for a set loaded from several master files: master_out[k] = path for the k-th file read (htkamd_mmf_write_sources)."""
         g = params.get("gconst")
         arr = (C.c_char_p * len(master_out))(*[str(x).encode() for x in master_out])
+        if self.inv_cov is not None:
+            if params.get("invCov") is None:
+                raise HtkAmdError("mmf_write_sources: a FULLC set is written from params['invCov'] (the packed inverse covariances), which is missing")
+            check(lib().htkamd_mmf_write_sources_full(self.h, _p(np.ascontiguousarray(params["mean"], np.float32)), _p(np.ascontiguousarray(params["invCov"], np.float32)),
+                                                      _p(np.ascontiguousarray(g, np.float32)) if g is not None else None,
+                                                      _p(np.ascontiguousarray(params["compWeight"], np.float32)), _p(np.ascontiguousarray(params["transP"], np.float32)),
+                                                      arr, C.c_int(len(master_out)), out_dir.encode() if out_dir else None, C.c_int(1 if binary else 0)), "mmf_write_sources_full")
+            return
         check(lib().htkamd_mmf_write_sources(self.h, _p(np.ascontiguousarray(params["mean"], np.float32)), _p(np.ascontiguousarray(params["var"], np.float32)),
                                              _p(np.ascontiguousarray(g, np.float32)) if g is not None else None,
                                              _p(np.ascontiguousarray(params["compWeight"], np.float32)), _p(np.ascontiguousarray(params["transP"], np.float32)),

@@ -168,6 +168,7 @@ static bool compat_revisit(const htkamd_model *m) { return (m->compat & HTKAMD_C
 extern "C" int htkamd_fb_create(htkamd_model *m, htkamd_fb **out)
 {
    if (!m || !out) { htkamd_set_error("fb_create: NULL argument"); return HTKAMD_EINVAL; }
+   if (m->fullc) { htkamd_set_error("fb_create: forward-backward on FULLC models is not supported yet (its mixture statistics are diagonal)"); return HTKAMD_EMODEL; }
    if (m->maxM > 4096) { htkamd_set_error("fb_create: %d mixture components per state not supported", m->maxM); return HTKAMD_EMODEL; }
    htkamd_fb *fb = new htkamd_fb();
    fb->m = m; fb->nUtt = 0; fb->debug = 0; fb->forceGeneral = 0; fb->evValid = false; fb->timed = false; fb->copyPending = false; fb->scored = false; fb->lastWave = false; fb->betaWTotal = 0; fb->alphaWTotal = 0; fb->noStatePath = 0; fb->noLrPath = 0; fb->recCapForce = 0; for (int c = 0; c < 14; c++) fb->clsOff[c] = 0;

@@ -183,6 +183,7 @@ __global__ __launch_bounds__(256) void k_score_exact_anyD(ScoreArgs a)
 int htkamd_launch_score_exact(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart, hipEvent_t evStop, bool soutp, bool diagc)
 {
    if (a.nTasks <= 0) return HTKAMD_OK;
+   if (m->fullc) return htkamd_launch_score_full(m, a, stream, evStart, evStop, soutp, diagc);     // FOutP (gmm_full.hip)
    HIPCHECK(hipMemsetAsync(a.taskCounter, 0, sizeof(int), stream));
    int blocks = (a.nTasks + 3) / 4;
    if (blocks > 256 * 5) blocks = 256 * 5;      // persistent: up to 5 four-wave blocks per CU (VGPR-limited)

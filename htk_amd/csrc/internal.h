@@ -24,6 +24,7 @@ void htkamd_set_error(const char *fmt, ...);
 /* ---- host-side preparation (htk_amd/host/prep.c) ---- */
 void   htkamd_host_fix_diag_gconst(int D, const float *var, float *gconst);   /* HModel.c:5641 */
 void   htkamd_host_conv_diagc(size_t n, const float *var, float *ivar);        /* HUtil.c:413  */
+int    htkamd_host_fix_full_gconst(int D, const float *tri, float *gconst);    /* HModel.c:5682 + CovDet HMath.c:593; -1: not positive definite */
 float  htkamd_host_mix_log_weight(float w);                                    /* HModel.c:5288 */
 int    htkamd_host_min_dur(int N, const float *tp);                            /* HFB.c:106    */
 int    htkamd_host_stream_dims(const char *kind, int vecSize, int S, const int *width, int *dimStream, char *why, size_t whyLen);   /* HParm.c:3094,2843 */
@@ -119,6 +120,12 @@ struct htkamd_model {
    float *h_streamWt, *d_streamWt;    /* [S] stream weight of every element (1 unless <SWEIGHTS>) */
    int   *d_msCompOff;         /* [S+1] = 2e: what the recursion kernels read as "components of the chain state" (they only ask == 1) */
    int   *h_scanOrder;         /* [H] the reference's HMM scan order of the physical models (htkamd_model_set_scan_order), or NULL */
+   /* full covariances (htkamd_model_create_full): the inverse covariance of every Gaussian as its lower triangle packed row-major
+      ((i, j), j <= i, at i(i+1)/2 + j), and the exact FULLC scorer's table (gmm_full.hip): per Gaussian mean[D], triangle, gConst, zero
+      padding to FPS floats (a multiple of 4).  h_var is a placeholder of ones and d_gparam describes no density; the matrix-core tables,
+      forward-backward and the accumulators are not built for such a model */
+   int    fullc, FPS;
+   float *h_invCov, *d_fparam;
    double minLogExp;
 };
 
@@ -131,6 +138,7 @@ int htkamd_model_f16_flag(struct htkamd_model *m, void *stream, int *flag);   /*
 #define HTKAMD_F16_EMODEL 1    /* a scaled coefficient of the model exceeds fp16's range */
 #define HTKAMD_F16_EFEAT  2    /* a scaled feature value (x or x^2) exceeds fp16's range */
 int htkamd_model_device_tables(struct htkamd_model *m);      /* model.hip: uploads d_var etc. once */
+static inline size_t htkamd_tri_size(int D) { return (size_t)D * (D + 1) / 2; }
 int htkamd_model_sync_host(struct htkamd_model *m);          /* model.hip: device -> host parameter copies when stale */
 int htkamd_update_models(struct htkamd_model *m, const htkamd_accs_layout *lay, const double *acc,
                          const htkamd_update_config *cfg, htkamd_update_stats *st);   /* host/update.c */

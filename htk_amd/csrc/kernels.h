@@ -57,12 +57,18 @@ struct ScoreArgs {
 // evStart/evStop (may be NULL): updated with the dispatch's own start and stop time (hipExtLaunchKernel), i.e. without the time
 // the kernel waits for the machine when another stream is using it
 int htkamd_launch_score_exact(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart = nullptr, hipEvent_t evStop = nullptr, bool soutp = false, bool diagc = false);
+// FULLC models (gmm_full.hip, FOutP HModel.c:5361): htkamd_launch_score_exact hands them on to this
+int htkamd_launch_score_full(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart, hipEvent_t evStop, bool soutp, bool diagc);
 int htkamd_launch_score_mfma(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart = nullptr, hipEvent_t evStop = nullptr);
 int htkamd_launch_score_bf16(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart = nullptr, hipEvent_t evStop = nullptr);
 int htkamd_launch_score_f16(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart = nullptr, hipEvent_t evStop = nullptr);
 // the scoring kernel of a score mode (HTKAMD_SCORE_* bits: F16 before BF16 before MFMA before exact)
 static inline int htkamd_launch_score(int mode, const htkamd_model *m, const ScoreArgs &a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
 {
+   if (m->fullc && (mode & (HTKAMD_SCORE_F16 | HTKAMD_SCORE_BF16 | HTKAMD_SCORE_MFMA))) {
+      htkamd_set_error("score: a FULLC model is scored by the exact kernel only (score mode %d asks for a matrix-core one)", mode);
+      return HTKAMD_EMODEL;
+   }
    if (mode & HTKAMD_SCORE_F16) return htkamd_launch_score_f16(m, a, s, e0, e1);
    if (mode & HTKAMD_SCORE_BF16) return htkamd_launch_score_bf16(m, a, s, e0, e1);
    if (mode & HTKAMD_SCORE_MFMA) return htkamd_launch_score_mfma(m, a, s, e0, e1);

@@ -216,6 +216,24 @@ static int mfma_refresh(htkamd_model *m)
    return rc;
 }
 
+// The exact FULLC scorer's parameter table (gmm_full.hip): per Gaussian mean[D], the packed triangle, gConst, zeros up to FPS.
+static int fullc_refresh(htkamd_model *m)
+{
+   const int D = m->D, FPS = m->FPS;
+   const size_t TRI = htkamd_tri_size(D);
+   float *fp = (float *)calloc((size_t)m->G * FPS, sizeof(float));
+   if (!fp) { htkamd_set_error("model: out of memory (FULLC table)"); return HTKAMD_ENOMEM; }
+   for (int g = 0; g < m->G; g++) {
+      float *p = fp + (size_t)g * FPS;
+      memcpy(p, m->h_mean + (size_t)g * D, sizeof(float) * D);
+      memcpy(p + D, m->h_invCov + (size_t)g * TRI, sizeof(float) * TRI);
+      p[D + TRI] = m->h_gconst[g];
+   }
+   const int rc = toDevice(&m->d_fparam, fp, (size_t)m->G * FPS);
+   free(fp);
+   return rc;
+}
+
 // (Re)derive ivar / log weights / min durations / the interleaved scoring table and push them.
 static int model_refresh(htkamd_model *m, bool derive = true)
 {
@@ -253,6 +271,7 @@ static int model_refresh(htkamd_model *m, bool derive = true)
    if (!m->d_transP) HIPCHECK(hipMalloc((void **)&m->d_transP, sizeof(float) * ((size_t)m->h_transOff[m->nT] + 16)));      // + the device update's 16 counters: one copy brings both back (update.hip)
    if ((rc = toDevice(&m->d_transP, m->h_transP, (size_t)m->h_transOff[m->nT]))) return rc;
    if (m->d_var && ((rc = toDevice(&m->d_var, m->h_var, (size_t)m->G * D)) || (rc = toDevice(&m->d_compWeight, m->h_compWeight, (size_t)m->C)))) return rc;
+   if (m->fullc) return fullc_refresh(m);             // (no matrix-core table: only the exact kernel scores a FULLC set)
    return mfma_refresh(m);
 }
 
@@ -282,9 +301,25 @@ int htkamd_model_sync_host(htkamd_model *m)
    return HTKAMD_OK;
 }
 
-extern "C" int htkamd_model_create(const htkamd_model_desc *d, htkamd_model **out)
+static int model_create(const htkamd_model_desc *d, const float *invCov, htkamd_model **out);
+extern "C" int htkamd_model_create(const htkamd_model_desc *d, htkamd_model **out) { return model_create(d, nullptr, out); }
+
+// A full-covariance set (MixPDF with ckind FULLC and cov.inv, HModel.h; scored by FOutP HModel.c:5361): desc->var is ignored, invCov holds
+// the inverse covariances [G*D(D+1)/2] packed as htkamd_mmf_inv_cov gives them; desc->gconst NULL = FixFullGConst(mp, -CovDet(inv)) (CheckMix).
+extern "C" int htkamd_model_create_full(const htkamd_model_desc *d, const float *invCov, htkamd_model **out)
+{
+   if (!d || !invCov || !out) { htkamd_set_error("model_create_full: NULL argument"); return HTKAMD_EINVAL; }
+   if (d->numStreams > 1) { htkamd_set_error("model_create_full: FULLC together with several streams is not supported"); return HTKAMD_EMODEL; }
+   if (d->hsKind == HTKAMD_HS_TIED) { htkamd_set_error("model_create_full: FULLC together with tied mixtures (<TMIX>) is not supported"); return HTKAMD_EMODEL; }
+   return model_create(d, invCov, out);
+}
+
+static int model_create(const htkamd_model_desc *d, const float *invCov, htkamd_model **out)
 {
    if (!d || !out) { htkamd_set_error("model_create: NULL argument"); return HTKAMD_EINVAL; }
+   if (!invCov && !d->var) {                         // (the description of a FULLC set read by htkamd_mmf_* has no variances)
+      htkamd_set_error("model_create: no variances in the description (a FULLC set is made a model by htkamd_model_create_full)"); return HTKAMD_EMODEL;
+   }
    if (htkamd_device_count() <= 0) { htkamd_set_error("model_create: no HIP device"); return HTKAMD_ENODEV; }
    if (d->vecSize <= 0 || d->numStates <= 0 || d->numComp <= 0 || d->numGauss <= 0 || d->numTrans <= 0 || d->numPhys <= 0) {
       htkamd_set_error("model_create: empty model"); return HTKAMD_EINVAL;
@@ -301,7 +336,13 @@ extern "C" int htkamd_model_create(const htkamd_model_desc *d, htkamd_model **ou
    m->h_compWeight = dupHost(d->compWeight, (size_t)m->C);
    m->h_compLogWt = dupHost((const float *)nullptr, (size_t)m->C);
    m->h_mean = dupHost(d->mean, (size_t)m->G * m->D);
-   m->h_var = dupHost(d->var, (size_t)m->G * m->D);
+   m->h_var = dupHost(invCov ? nullptr : d->var, (size_t)m->G * m->D);
+   if (invCov) {
+      for (size_t i = 0; i < (size_t)m->G * m->D; i++) m->h_var[i] = 1.0f;
+      m->fullc = 1;
+      m->FPS = (int)((m->D + htkamd_tri_size(m->D) + 1 + 3) & ~(size_t)3);
+      m->h_invCov = dupHost(invCov, (size_t)m->G * htkamd_tri_size(m->D));
+   }
    m->h_ivar = dupHost((const float *)nullptr, (size_t)m->G * m->D);
    m->h_transN = dupHost(d->transN, (size_t)m->nT);
    m->h_transOff = dupHost(d->transOff, (size_t)m->nT + 1);
@@ -335,7 +376,13 @@ extern "C" int htkamd_model_create(const htkamd_model_desc *d, htkamd_model **ou
    for (int t = 0; t < m->nT; t++) m->h_transLR[t] = 2;          // unknown: model_refresh sets it
    m->h_trOccOff = dupHost((const int *)nullptr, (size_t)m->nT + 1);
    m->h_gconst = dupHost(d->gconst, (size_t)m->G);
-   if (!d->gconst)                                   // CheckMix: gConst fixed at load (HModel.c:206-208)
+   if (!d->gconst && m->fullc) {                     // CheckMix: FixFullGConst(mp, -CovDet(mp->cov.inv)) (HModel.c:210)
+      for (int g = 0; g < m->G; g++)
+         if (htkamd_host_fix_full_gconst(m->D, m->h_invCov + (size_t)g * htkamd_tri_size(m->D), m->h_gconst + g)) {
+            htkamd_set_error("model_create_full: the inverse covariance of Gaussian %d is not positive definite (CovDet)", g);
+            htkamd_model_destroy(m); return HTKAMD_EMODEL;
+         }
+   } else if (!d->gconst)                            // CheckMix: gConst fixed at load (HModel.c:206-208)
       for (int g = 0; g < m->G; g++) htkamd_host_fix_diag_gconst_ms(m->D, m->h_var + (size_t)g * m->D, m->h_dimStream, m->h_gaussStream ? m->h_gaussStream[g] : 0, m->h_gconst + g);
    m->maxN = 0; m->maxM = 1; m->h_trOccOff[0] = 0;
    for (int t = 0; t < m->nT; t++) {
@@ -419,6 +466,7 @@ extern "C" void htkamd_model_destroy(htkamd_model *m)
    free(m->h_rawLogWt); (void)hipFree(m->d_rawLogWt);
    free(m->h_tmPoolOff); (void)hipFree(m->d_tmPoolOff); free(m->h_streamWt); (void)hipFree(m->d_streamWt);
    free(m->h_dimStream); free(m->h_gaussStream); (void)hipFree(m->d_dimStream); (void)hipFree(m->d_gaussStream); (void)hipFree(m->d_msCompOff);
+   free(m->h_invCov); (void)hipFree(m->d_fparam);
    free(m);
 }
 
@@ -570,6 +618,7 @@ extern "C" int htkamd_model_set_params(htkamd_model *m, const float *mean, const
                                        const float *compWeight, const float *transP)
 {
    if (!m) { htkamd_set_error("model_set_params: NULL model"); return HTKAMD_EINVAL; }
+   if (m->fullc && var) { htkamd_set_error("model_set_params: a FULLC model has no variances (htkamd_model_set_inv_cov)"); return HTKAMD_EMODEL; }
    { int rc0 = htkamd_model_sync_host(m); if (rc0) return rc0; }
    if (mean) memcpy(m->h_mean, mean, sizeof(float) * (size_t)m->G * m->D);
    if (var) memcpy(m->h_var, var, sizeof(float) * (size_t)m->G * m->D);
@@ -586,6 +635,7 @@ extern "C" int htkamd_model_set_params(htkamd_model *m, const float *mean, const
 extern "C" int htkamd_model_set_prepared(htkamd_model *m, const float *ivar, const float *gconst, const float *compLogWt)
 {
    if (!m) { htkamd_set_error("model_set_prepared: NULL model"); return HTKAMD_EINVAL; }
+   if (m->fullc) { htkamd_set_error("model_set_prepared: the prepared DIAGC tables do not apply to a FULLC model"); return HTKAMD_EMODEL; }
    { int rc0 = htkamd_model_sync_host(m); if (rc0) return rc0; }
    if (ivar) memcpy(m->h_ivar, ivar, sizeof(float) * (size_t)m->G * m->D);
    if (gconst) memcpy(m->h_gconst, gconst, sizeof(float) * (size_t)m->G);
@@ -629,11 +679,42 @@ extern "C" int htkamd_model_get_params(htkamd_model *m, float *mean, float *var,
    return HTKAMD_OK;
 }
 
+// The inverse covariances of a FULLC model (mp->cov.inv, HModel.h), packed as htkamd_model_create_full takes them.  set: gconst NULL =
+// FixFullGConst(mp, -CovDet(inv)) for every Gaussian, as FixGConsts does after an update (HModel.c:5688, HERest.c:1309).
+extern "C" int htkamd_model_set_inv_cov(htkamd_model *m, const float *invCov, const float *gconst)
+{
+   if (!m || !invCov) { htkamd_set_error("model_set_inv_cov: NULL argument"); return HTKAMD_EINVAL; }
+   if (!m->fullc) { htkamd_set_error("model_set_inv_cov: not a FULLC model"); return HTKAMD_EMODEL; }
+   const size_t TRI = htkamd_tri_size(m->D);
+   float *gc = (float *)malloc(sizeof(float) * (size_t)(m->G ? m->G : 1));
+   for (int g = 0; g < m->G; g++) {
+      if (gconst) gc[g] = gconst[g];
+      else if (htkamd_host_fix_full_gconst(m->D, invCov + (size_t)g * TRI, gc + g)) {
+         free(gc); htkamd_set_error("model_set_inv_cov: the inverse covariance of Gaussian %d is not positive definite (CovDet)", g); return HTKAMD_EMODEL;
+      }
+   }
+   memcpy(m->h_invCov, invCov, sizeof(float) * (size_t)m->G * TRI);
+   memcpy(m->h_gconst, gc, sizeof(float) * (size_t)m->G);
+   free(gc);
+   return model_refresh(m);
+}
+
+extern "C" int htkamd_model_get_inv_cov(htkamd_model *m, float *invCov)
+{
+   if (!m || !invCov) { htkamd_set_error("model_get_inv_cov: NULL argument"); return HTKAMD_EINVAL; }
+   if (!m->fullc) { htkamd_set_error("model_get_inv_cov: not a FULLC model"); return HTKAMD_EMODEL; }
+   memcpy(invCov, m->h_invCov, sizeof(float) * (size_t)m->G * htkamd_tri_size(m->D));
+   return HTKAMD_OK;
+}
+
+extern "C" int htkamd_model_is_full(const htkamd_model *m) { return m && m->fullc ? 1 : 0; }
+
 // ------------------------------------------------------------------------------------ accumulators
 
 extern "C" int htkamd_accs_create(htkamd_model *m, htkamd_accs **out)
 {
    if (!m || !out) { htkamd_set_error("accs_create: NULL argument"); return HTKAMD_EINVAL; }
+   if (m->fullc) { htkamd_set_error("accs_create: re-estimation of FULLC models is not supported yet (scoring, alignment and decoding are)"); return HTKAMD_EMODEL; }
    htkamd_accs *a = (htkamd_accs *)calloc(1, sizeof(htkamd_accs));
    a->m = m;
    size_t o = 0, GD = (size_t)m->G * m->D;

@@ -1,6 +1,6 @@
 /* mmf.c -- HTK model definition files (text MMF / one-HMM-per-file) <-> the flat htkamd_model_desc.
  *
- * Replaces, for the model kinds the hot path supports (diagonal covariance, continuous densities, PLAINHS/SHAREDHS; one stream,
+ * Replaces, for the model kinds the hot path supports (diagonal covariance -- or full, <FULLC> with <INVCOVAR> triangles --, continuous densities, PLAINHS/SHAREDHS; one stream,
  * or several -- <STREAMINFO> S, <NUMMIXES> per stream, <SWEIGHTS>, <STREAM> s, ~v varFloorN: every vector of a stream is held at the
  * stream's dimensions of an undivided row, htkamd_host_stream_dims --): LoadHMMSet (HModel.c:3809) = MakeHMMSet (:3580, the HMM list "logical [physical]") +
  * LoadAllMacros / LoadMacroFiles (:3721) + the -d directory search; the grammar of GetOptions (:1649),
@@ -55,6 +55,9 @@ struct htkamd_mmf {
    int *gStr;                                                       /* stream of Gaussian g */
    float *swAll;                                                    /* [nSt*NS] stream weights for the desc */
    int tiedMix;                                                     /* hsKind TIEDHS: <TMIX> streams (GetStream HModel.c:1878-1892) */
+   /* full covariances (<FULLC>, <INVCOVAR> D + the lower triangle; GetCovar HModel.c:1511, ReadTriMat HMath.c:406): per Gaussian the
+      triangle packed row-major, element (i, j), j <= i, at i(i+1)/2 + j; allocated on the first <INVCOVAR> or <FULLC> only */
+   float *icov; int capIcov, fullc, sawVar, sawInv;
    char *tmName[8]; int tmM[8];                                     /* per stream: generic ~m macro name and pool size (tmRecs[s].mixId / nMix) */
    int *gPend; int capPend, lastVecN;                                         /* a ~m macro of a multi-stream set read before its stream is known: its width, values at [0..width) of the row */
    int finished, nFiles;
@@ -239,7 +242,8 @@ static int parse_options(struct htkamd_mmf *s, rd *r)
          snprintf(s->dur, sizeof(s->dur), "%.15s", t);                        /* (carried: no tool on the path evaluates a duration model) */
       }
       else if (!strcmp(t, "DIAGC")) snprintf(s->cov, sizeof(s->cov), "%.15s", t);
-      else if (!strcmp(t, "FULLC") || !strcmp(t, "XFORMC") || !strcmp(t, "LLTC") || !strcmp(t, "INVDIAGC")) return fail(r, "only DIAGC covariances are supported");
+      else if (!strcmp(t, "FULLC")) { snprintf(s->cov, sizeof(s->cov), "%.15s", t); s->fullc = 1; }
+      else if (!strcmp(t, "XFORMC") || !strcmp(t, "LLTC") || !strcmp(t, "INVDIAGC")) return fail(r, "only DIAGC and FULLC covariances are supported");
       else if (is_parm_kind(t)) {
          if (s->kind[0] && strcmp(s->kind, t)) return fail(r, "inconsistent parameter kind");
          snprintf(s->kind, sizeof(s->kind), "%.63s", t);
@@ -336,6 +340,7 @@ static int parse_shared_vector(struct htkamd_mmf *s, rd *r, int k, char type, co
    *mac = -1;
    if (k == T_MACRO && r->tok[0] == type) {
       char *nm;
+      if (s->fullc) return fail(r, "~u / ~v vector sharing inside a FULLC set is not supported");
       if (s->nStreams > 1) return fail(r, "~u / ~v macros in a multi-stream set are not supported");
       if ((rc = rd_name(r, &nm))) return rc;
       const int i = find_vmacro(s, type, nm);
@@ -405,10 +410,29 @@ static int parse_mixpdf(struct htkamd_mmf *s, rd *r, int *gOut)
      s->var = (float *)realloc(s->var, sizeof(float) * (size_t)cap * s->vecSize);
      s->hasG = (unsigned char *)realloc(s->hasG, (size_t)cap); }
    const int g = s->nG;
-   int meanMac, varMac;
+   int meanMac, varMac = -1;
    if ((rc = parse_shared_vector(s, r, k, 'u', "MEAN", s->mean + (size_t)g * s->vecSize, &meanMac))) return rc;
    k = rd_next(r);
-   if ((rc = parse_shared_vector(s, r, k, 'v', "VARIANCE", s->var + (size_t)g * s->vecSize, &varMac))) return rc;
+   if (k == T_MACRO && r->tok[0] == 'i') return fail(r, "~i (shared inverse covariance) macros are not supported");
+   if (k == T_KEY && (!strcmp(r->tok, "LLTCOVAR") || !strcmp(r->tok, "XFORM"))) return fail(r, "only DIAGC and FULLC covariances are supported");
+   if (k == T_KEY && !strcmp(r->tok, "INVCOVAR")) {      /* GetCovar: <INVCOVAR> D, then ReadTriMat's order: for j, for i >= j: m[i][j] */
+      const int D = s->vecSize, TRI = D * (D + 1) / 2;
+      int n;
+      if (s->nStreams > 1) return fail(r, "FULLC together with <STREAMINFO> S > 1 is not supported");
+      if (meanMac >= 0) return fail(r, "~u / ~v vector sharing inside a FULLC set is not supported");
+      if ((rc = rd_int(r, &n))) return rc;
+      if (n != D) return fail(r, "<INVCOVAR> size differs from <VECSIZE>");
+      if (s->capIcov < s->capG) { s->icov = (float *)realloc(s->icov, sizeof(float) * (size_t)s->capG * TRI); s->capIcov = s->capG; }
+      float *tri = s->icov + (size_t)g * TRI;
+      for (int j = 0; j < D; j++)
+         for (int i = j; i < D; i++) if ((rc = rd_float(r, tri + (size_t)i * (i + 1) / 2 + j))) return rc;
+      for (int i = 0; i < D; i++) s->var[(size_t)g * D + i] = 1.0f;      /* (no variance vector; the description of a FULLC set has var = NULL) */
+      s->sawInv = 1;
+   } else {
+      if ((rc = parse_shared_vector(s, r, k, 'v', "VARIANCE", s->var + (size_t)g * s->vecSize, &varMac))) return rc;
+      s->sawVar = 1;
+   }
+   if (s->icov && s->capIcov < s->capG) { s->icov = (float *)realloc(s->icov, sizeof(float) * (size_t)s->capG * (s->vecSize * (s->vecSize + 1) / 2)); s->capIcov = s->capG; }
    if (meanMac >= 0 || varMac >= 0) mac_set(s, g, meanMac, varMac);
    s->hasG[g] = 0; s->gconst[g] = 0.0f;
    k = rd_next(r);
@@ -793,7 +817,8 @@ int htkamd_mmf_read(struct htkamd_mmf *s, const char *path, const char *defName)
          if (rc) { free(name); break; }
          s->wm[s->nWm].name = name;
          s->nWm++;
-      } else { rc = fail(&r, "unsupported macro type"); free(name); break; }
+      } else if (type == 'i') { rc = fail(&r, "~i (shared inverse covariance) macros are not supported"); free(name); break; }
+      else { rc = fail(&r, "unsupported macro type"); free(name); break; }
    }
    fclose(r.f);
    s->nFiles++;
@@ -839,6 +864,20 @@ int htkamd_mmf_finish(struct htkamd_mmf *s, const char *hmmList, const char *dir
       s->nLog = s->nHm;
    }
    if (s->nHm == 0 || s->vecSize == 0) { htkamd_set_error("mmf_finish: no model defined"); return HTKAMD_EMODEL; }
+   if (s->fullc || s->sawInv) {
+      if (s->sawVar) { htkamd_set_error("mmf_finish: a set that mixes <VARIANCE> and <INVCOVAR> mixtures (FULLC) is not supported"); return HTKAMD_EMODEL; }
+      if (s->nStreams > 1) { htkamd_set_error("mmf_finish: FULLC together with <STREAMINFO> S > 1 is not supported"); return HTKAMD_EMODEL; }
+      if (s->tiedMix) { htkamd_set_error("mmf_finish: FULLC together with <TMIX> is not supported"); return HTKAMD_EMODEL; }
+      for (int i = 0; i < s->nVm; i++)
+         if (strncmp(s->vm[i].name, "varFloor", 8)) { htkamd_set_error("mmf_finish: ~%c macro \"%s\": ~u / ~v vector sharing inside a FULLC set is not supported", s->vm[i].type, s->vm[i].name); return HTKAMD_EMODEL; }
+      s->fullc = 1;
+      snprintf(s->cov, sizeof(s->cov), "FULLC");
+      const int TRI = s->vecSize * (s->vecSize + 1) / 2;
+      for (int g = 0; g < s->nG; g++)                  /* CheckMix: FixFullGConst(mp, -CovDet(inv)) where the file gave none (HModel.c:208-210) */
+         if (!s->hasG[g] && htkamd_host_fix_full_gconst(s->vecSize, s->icov + (size_t)g * TRI, s->gconst + g)) {
+            htkamd_set_error("mmf_finish: the inverse covariance of Gaussian %d is not positive definite (CovDet)", g); return HTKAMD_EMODEL;
+         }
+   }
    if (s->cov[0] == 0) snprintf(s->cov, sizeof(s->cov), "DIAGC");
    if (s->dur[0] == 0) snprintf(s->dur, sizeof(s->dur), "NULLD");
    if (s->streamWidth == 0) s->streamWidth = s->vecSize;
@@ -891,12 +930,12 @@ int htkamd_mmf_finish(struct htkamd_mmf *s, const char *hmmList, const char *dir
    s->hmmStateOff[s->nHm] = tot;
    int anyG = 0, allG = 1;
    for (int g = 0; g < s->nG; g++) { if (s->hasG[g]) anyG = 1; else allG = 0; }
-   if (anyG && !allG)                                 /* CheckMix: missing gConst computed at load (HModel.c:206-208) */
+   if (anyG && !allG && !s->fullc)                    /* CheckMix: missing gConst computed at load (HModel.c:206-208) */
       for (int g = 0; g < s->nG; g++) if (!s->hasG[g]) htkamd_host_fix_diag_gconst_ms(s->vecSize, s->var + (size_t)g * s->vecSize, NS > 1 ? s->dimStream : NULL, s->gStr[g], s->gconst + g);
    htkamd_model_desc *d = &s->d;
    d->vecSize = s->vecSize; d->numStates = s->nSt; d->numComp = s->nComp; d->numGauss = s->nG; d->numTrans = s->nTr; d->numPhys = s->nHm;
-   d->stateCompOff = s->stateCompOff; d->compWeight = s->wt; d->compGauss = s->cg; d->mean = s->mean; d->var = s->var;
-   d->gconst = anyG ? s->gconst : NULL;
+   d->stateCompOff = s->stateCompOff; d->compWeight = s->wt; d->compGauss = s->cg; d->mean = s->mean; d->var = s->fullc ? NULL : s->var;
+   d->gconst = (anyG || s->fullc) ? s->gconst : NULL;
    d->transN = s->transN; d->transOff = s->transOff; d->transP = s->tp;
    d->hmmTrans = s->hmmTrans; d->hmmStateOff = s->hmmStateOff; d->hmmState = s->hmmState;
    d->numStreams = NS; d->dimStream = NS > 1 ? s->dimStream : NULL;
@@ -924,6 +963,7 @@ int htkamd_mmf_logical_phys(const struct htkamd_mmf *s, int i) { return (s && i 
 const char *htkamd_mmf_phys_name(const struct htkamd_mmf *s, int h) { return (s && h >= 0 && h < s->nHm) ? s->hm[h].name : NULL; }
 const char *htkamd_mmf_parm_kind(const struct htkamd_mmf *s) { return s ? s->kind : NULL; }
 const float *htkamd_mmf_var_floor(const struct htkamd_mmf *s) { return s ? s->varFloor : NULL; }
+const float *htkamd_mmf_inv_cov(const struct htkamd_mmf *s) { return (s && s->finished && s->fullc) ? s->icov : NULL; }
 
 /* Sharing of mean / variance vectors between Gaussians (~u / ~v macros): share[g] = a number that Gaussians with the same vector
  * have in common, -1 for a private vector.  Returns the number of Gaussians that share something (0: nothing to honour). */
@@ -966,6 +1006,7 @@ void htkamd_mmf_destroy(struct htkamd_mmf *s)
    free(s->logSorted);
    for (int g = 0; g < s->capGN; g++) free(s->gName[g]);
    free(s->gName);
+   free(s->icov);
    free(s->st); free(s->wt); free(s->cg); free(s->mean); free(s->var); free(s->gconst); free(s->hasG); free(s->tr); free(s->tp); free(s->hm);
    free(s->varFloor); free(s->logName); free(s->logPhys);
    for (int i = 0; i < s->nVm; i++) { free(s->vm[i].name); free(s->vm[i].v); }
@@ -980,6 +1021,7 @@ void htkamd_mmf_destroy(struct htkamd_mmf *s)
 
 /* ------------------------------------------------------------------------------------------ writer */
 static int g_bin;                                  /* writer mode: text or binary (SaveHMMSet's `binary`), set by htkamd_mmf_write* */
+static const float *g_icov;                        /* FULLC writers (htkamd_mmf_write_full*): the packed triangles written in place of the variances */
 static void put_sym(FILE *f, const char *name, int code) { if (g_bin) { fputc(':', f); fputc(code, f); } else fprintf(f, "<%s>", name); }
 static void put_short(FILE *f, int v) { if (g_bin) { fputc((v >> 8) & 255, f); fputc(v & 255, f); } else fprintf(f, " %d", v); }
 /* printf("%e") of a float without printf: the float is m * 2^e2 exactly (m < 2^24), so the seven digits are the integer nearest to
@@ -1092,7 +1134,14 @@ static void put_gauss(const struct htkamd_mmf *s, FILE *f, int g, const float *m
    const int D = s->vecSize;
    const int mu = (g < s->capMac) ? s->gMeanMac[g] : -1, va = (g < s->capMac) ? s->gVarMac[g] : -1;
    if (mu >= 0) put_name(f, 'u', s->vm[mu].name); else put_vec_ms(s, f, "MEAN", 20, mean + (size_t)g * D, s->nStreams > 1 ? s->gStr[g] : -1);
-   if (va >= 0) put_name(f, 'v', s->vm[va].name); else put_vec_ms(s, f, "VARIANCE", 21, var + (size_t)g * D, s->nStreams > 1 ? s->gStr[g] : -1);
+   if (g_icov) {                                   /* PutCovar(.., INVCOVAR) HModel.c:2780, WriteTriMat HMath.c:431: for j, for i >= j: m[i][j], a line per j */
+      const float *tri = g_icov + (size_t)g * (D * (D + 1) / 2);
+      put_sym(f, "INVCOVAR", 22); put_short(f, D); put_nl(f);
+      for (int j = 0; j < D; j++) {
+         for (int i = j; i < D; i++) put_float(f, tri[(size_t)i * (i + 1) / 2 + j]);
+         put_nl(f);
+      }
+   } else if (va >= 0) put_name(f, 'v', s->vm[va].name); else put_vec_ms(s, f, "VARIANCE", 21, var + (size_t)g * D, s->nStreams > 1 ? s->gStr[g] : -1);
    if (gconst) { put_sym(f, "GCONST", 24); put_float(f, gconst[g]); put_nl(f); }
 }
 static void put_dur(const struct htkamd_mmf *s, FILE *f, int d, int define);
@@ -1289,6 +1338,7 @@ static int mmf_write(const struct htkamd_mmf *s, const float *mean, const float 
                      const float *transP, const char *oneFile, const char *dir)
 {
    if (!s || !s->finished || !mean || !var || !compWeight || !transP) { htkamd_set_error("mmf_write: bad argument"); return HTKAMD_EINVAL; }
+   if (s->fullc != (g_icov != NULL)) { htkamd_set_error(s->fullc ? "mmf_write: a FULLC set is written by htkamd_mmf_write_full" : "mmf_write_full: the set is not FULLC"); return HTKAMD_EINVAL; }
    if (oneFile) return write_macros(s, mean, var, gconst, compWeight, transP, oneFile, -1);
    if (!dir) { htkamd_set_error("mmf_write: neither file nor directory given"); return HTKAMD_EINVAL; }
    for (int i = 0; i < s->nSt; i++) if (s->st[i].name) { htkamd_set_error("mmf_write: a set with ~s macros must be written to one file"); return HTKAMD_EINVAL; }
@@ -1316,6 +1366,7 @@ int htkamd_mmf_write_sources(const struct htkamd_mmf *s, const float *mean, cons
                              const float *transP, const char *const *masterOut, int nMaster, const char *dir, int binary)
 {
    if (!s || !s->finished || !mean || !var || !compWeight || !transP || nMaster < 0 || (nMaster > 0 && !masterOut)) { htkamd_set_error("mmf_write_sources: bad argument"); return HTKAMD_EINVAL; }
+   if (s->fullc != (g_icov != NULL)) { htkamd_set_error(s->fullc ? "mmf_write_sources: a FULLC set is written by htkamd_mmf_write_sources_full" : "mmf_write_sources_full: the set is not FULLC"); return HTKAMD_EINVAL; }
    int rc = HTKAMD_OK;
    g_bin = binary ? 1 : 0;
    for (int k = 0; k < nMaster && !rc; k++) rc = write_macros(s, mean, var, gconst, compWeight, transP, masterOut[k], k);
@@ -1327,6 +1378,28 @@ int htkamd_mmf_write_sources(const struct htkamd_mmf *s, const float *mean, cons
       rc = write_macros(s, mean, var, gconst, compWeight, transP, path, s->hm[h].src);
    }
    g_bin = 0;
+   return rc;
+}
+
+/* FULLC sets (SaveHMMSet with PutCovar(.., INVCOVAR), HModel.c:2780): the writers above with the packed inverse-covariance triangles
+   [G*D(D+1)/2] in place of the variances; binary = SaveHMMSet's `binary`. */
+int htkamd_mmf_write_full(const struct htkamd_mmf *s, const float *mean, const float *invCov, const float *gconst, const float *compWeight,
+                          const float *transP, const char *oneFile, const char *dir, int binary)
+{
+   if (!invCov) { htkamd_set_error("mmf_write_full: NULL inverse covariances"); return HTKAMD_EINVAL; }
+   g_bin = binary ? 1 : 0; g_icov = invCov;
+   const int rc = mmf_write(s, mean, invCov, gconst, compWeight, transP, oneFile, dir);
+   g_bin = 0; g_icov = NULL;
+   return rc;
+}
+
+int htkamd_mmf_write_sources_full(const struct htkamd_mmf *s, const float *mean, const float *invCov, const float *gconst, const float *compWeight,
+                                  const float *transP, const char *const *masterOut, int nMaster, const char *dir, int binary)
+{
+   if (!invCov) { htkamd_set_error("mmf_write_sources_full: NULL inverse covariances"); return HTKAMD_EINVAL; }
+   g_icov = invCov;
+   const int rc = htkamd_mmf_write_sources(s, mean, invCov, gconst, compWeight, transP, masterOut, nMaster, dir, binary);
+   g_icov = NULL;
    return rc;
 }
 
@@ -1407,6 +1480,7 @@ int htkamd_mmf_mixup(struct htkamd_mmf *s, int target, const unsigned char *stat
 {
    if (!s || !s->finished || target == 0) { htkamd_set_error("mmf_mixup: bad argument (set not finished, or target 0)"); return HTKAMD_EINVAL; }
    if (s->nStreams > 1) { htkamd_set_error("mmf_mixup: multi-stream sets are not supported"); return HTKAMD_EMODEL; }
+   if (s->fullc) { htkamd_set_error("mmf_mixup: FULLC sets are not supported"); return HTKAMD_EMODEL; }
    const int D = s->vecSize;
    for (int g = 0; g < s->nG; g++) { htkamd_host_fix_diag_gconst(D, s->var + (size_t)g * D, s->gconst + g); s->hasG[g] = 1; }   /* FixAllGConsts */
    double sum = 0.0, sumsq = 0.0; int count = 0;

@@ -30,6 +30,35 @@ void htkamd_host_fix_diag_gconst(int D, const float *var, float *gconst)
    *gconst = sum;
 }
 
+/* FixFullGConst(mp, -CovDet(inv)) (HModel.c:5682, HMath.c:593): D*log(2 pi) - log det of the float inverse covariance, through
+   the reference's Choleski in double (HMath.c:514); ldet is a LogFloat there, so the sum of the logs is rounded to float per step.
+   tri: the lower triangle packed row-major, (i, j) at i(i+1)/2 + j.  Returns -1 (gconst untouched) if the matrix is not positive definite. */
+int htkamd_host_fix_full_gconst(int D, const float *tri, float *gconst)
+{
+   double *L = (double *)malloc(sizeof(double) * (size_t)D * D);
+   float ldet = 0.0f;
+   int i, j, k;
+   if (!L) return -1;
+   for (i = 0; i < D; i++)
+      for (j = 0; j <= i; j++) {
+         double sum = tri[(size_t)i * (i + 1) / 2 + j];
+         for (k = 0; k < j; k++) sum -= L[(size_t)i * D + k] * L[(size_t)j * D + k];
+         if (i == j && sum <= 0.0) { free(L); return -1; }
+         else if (i == j) sum = sqrt(sum);
+         else if (L[(size_t)j * D + j] == 0.0) { free(L); return -1; }
+         else sum /= L[(size_t)j * D + j];
+         L[(size_t)i * D + j] = sum;
+      }
+   for (j = 0; j < D; j++) ldet += log(L[(size_t)j * D + j]);
+   free(L);
+   {
+      const float covDet = 2.0 * ldet;          /* CovDet's LogFloat return */
+      const float negDet = -covDet;
+      *gconst = D * log(HTK_TPI) + negDet;      /* FixFullGConst: int * double + LogFloat, stored to float */
+   }
+   return 0;
+}
+
 void htkamd_host_conv_diagc(size_t n, const float *var, float *ivar)
 {
    size_t k;

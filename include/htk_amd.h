@@ -133,6 +133,19 @@ int htkamd_host_stream_dims(const char *kind, int vecSize, int S, const int *wid
 typedef struct htkamd_model htkamd_model;
 
 int  htkamd_model_create(const htkamd_model_desc *desc, htkamd_model **out);
+/* Full-covariance sets (<FULLC>, MixPDF ckind FULLC with cov.inv, HModel.h; scored by FOutP HModel.c:5361-5381).  invCov: the inverse
+   covariance of every Gaussian as its lower triangle packed row-major, element (i, j), j <= i, at g*D(D+1)/2 + i(i+1)/2 + j (what
+   htkamd_mmf_inv_cov gives).  desc->var is ignored; desc->gconst NULL = FixFullGConst(mp, -CovDet(inv)) (CheckMix HModel.c:210, the
+   reference's Choleski in double, HMath.c:514,593).  One stream, continuous densities only.  Such a model is scored by the exact kernel
+   (HTKAMD_SCORE_EXACT, with or without HTKAMD_SCORE_SOUTP) wherever the library scores -- htkamd_outp_block[_mode], the aligner, the
+   decoders --; the matrix-core score modes return HTKAMD_EMODEL, and so do htkamd_fb_create and htkamd_accs_create: re-estimation of
+   FULLC sets is not supported yet. */
+int  htkamd_model_create_full(const htkamd_model_desc *desc, const float *invCov, htkamd_model **out);
+/* mp->cov.inv of every Gaussian, packed as above.  set: gconst NULL = FixFullGConst(mp, -CovDet(inv)) as FixGConsts (HModel.c:5688);
+   HTKAMD_EMODEL on a DIAGC model or an inverse that is not positive definite (the reference's HError 5220). */
+int  htkamd_model_set_inv_cov(htkamd_model *m, const float *invCov, const float *gconst);
+int  htkamd_model_get_inv_cov(htkamd_model *m, float *invCov /*[G*D(D+1)/2]*/);
+int  htkamd_model_is_full(const htkamd_model *m);              /* 1 for a model made by htkamd_model_create_full */
 /* Tied mean / variance vectors (~u / ~v macros: SVector with nUse > 1, HModel.c:1737-1790).  meanShare[g] / varShare[g] >= 0 name the
  * vector Gaussian g's mean / variance is a copy of (-1 = private; either array may be NULL); htkamd_mmf_sharing gives them for a set
  * read from files.  Scoring and the statistics are per Gaussian as always; htkamd_model_update pools the statistics of the sharers
@@ -177,7 +190,7 @@ int  htkamd_model_get_prepared(htkamd_model *m, float *ivar /*[G*D]*/, float *gc
 
 /* ------------------------------------------------------------------------------------------
  * Model definition files: replaces LoadHMMSet (HModel.c:3809) = MakeHMMSet (:3580) + LoadMacroFiles (:3721) with the
- * -d directory search, and SaveHMMSet (:4979) / SaveInOneFile (:4858), for text definitions of one-stream DIAGC
+ * -d directory search, and SaveHMMSet (:4979) / SaveInOneFile (:4858), for text definitions of one-stream DIAGC or FULLC
  * continuous-density sets, text or binary (macros ~o ~s ~t ~m ~h ~v"varFloor"; ~u/~v sharing inside a pdf, streams, durations and
  * transforms are rejected with HTKAMD_EMODEL).  Pure host code.
  *   mmf_read    : one master macro file, or one HMM file (a definition without ~h takes `defName` / the file's base name)
@@ -206,6 +219,12 @@ int  htkamd_mmf_find_logical(const htkamd_mmf *s, const char *name);     /* phys
 const char *htkamd_mmf_phys_name(const htkamd_mmf *s, int h);
 const char *htkamd_mmf_parm_kind(const htkamd_mmf *s);                   /* e.g. "MFCC_E_D" */
 const float *htkamd_mmf_var_floor(const htkamd_mmf *s);                  /* ~v "varFloor1" [vecSize] or NULL */
+/* A <FULLC> set (GetCovar HModel.c:1511: <INVCOVAR> D + the lower triangle in ReadTriMat's order, HMath.c:406): the inverse covariances,
+   [numGauss * D(D+1)/2] packed as htkamd_model_create_full takes them; NULL for a DIAGC set.  The description of such a set has var = NULL,
+   so that htkamd_model_create refuses it (only htkamd_model_create_full makes a model of a FULLC set), and its gconst is always given (the file's <GCONST>, else FixFullGConst(mp, -CovDet(inv))).  Refused with
+   HTKAMD_EMODEL: ~i macros, ~u / ~v sharing inside a FULLC set (the ~v varFloor macros excepted), <VARIANCE> and <INVCOVAR> mixtures in
+   one set, FULLC with <STREAMINFO> S > 1 or with <TMIX>; LLTC, XFORMC and INVDIAGC as before. */
+const float *htkamd_mmf_inv_cov(const htkamd_mmf *s);
 int  htkamd_mmf_sharing(const htkamd_mmf *s, int *meanShare /*[numGauss]*/, int *varShare /*[numGauss]*/);   /* ~u / ~v macros; returns the number of Gaussians sharing a vector */
 int  htkamd_mmf_write(const htkamd_mmf *s, const float *mean, const float *var, const float *gconst, const float *compWeight,
                       const float *transP, const char *oneFile, const char *dir);
@@ -217,6 +236,13 @@ int  htkamd_mmf_write_binary(const htkamd_mmf *s, const float *mean, const float
    their own beyond those go to dir/<name>. */
 int  htkamd_mmf_write_sources(const htkamd_mmf *s, const float *mean, const float *var, const float *gconst, const float *compWeight,
                               const float *transP, const char *const *masterOut, int nMaster, const char *dir, int binary);
+/* FULLC sets: htkamd_mmf_write / _write_binary (binary != 0) and htkamd_mmf_write_sources with the packed inverse covariances in place of
+   the variances, written by PutCovar(.., INVCOVAR) (HModel.c:2780, WriteTriMat HMath.c:431).  The DIAGC writers refuse a FULLC set and
+   these refuse a DIAGC one. */
+int  htkamd_mmf_write_full(const htkamd_mmf *s, const float *mean, const float *invCov, const float *gconst, const float *compWeight,
+                           const float *transP, const char *oneFile, const char *dir, int binary);
+int  htkamd_mmf_write_sources_full(const htkamd_mmf *s, const float *mean, const float *invCov, const float *gconst, const float *compWeight,
+                                   const float *transP, const char *const *masterOut, int nMaster, const char *dir, int binary);
 
 /* Script files (-S scp): white-space separated or quoted words (ScriptWord HShell.c:661), each a data file name or an extended
  * file name logical=physical[start,end] (RegisterExtFileName HShell.c:86: frames start..end of `physical`, known as `logical`). */

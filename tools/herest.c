@@ -161,6 +161,7 @@ int main(int argc, char **argv)
    CHECK(htkamd_mmf_finish(mmf, hmmList, hmmDir, hmmExt));
    const htkamd_model_desc *d = htkamd_mmf_desc(mmf);
    const int D = d->vecSize, H = d->numPhys;
+   if (htkamd_mmf_inv_cov(mmf)) DIE("herest: re-estimation of FULLC (<INVCOVAR>) sets is not supported");
    TOC(0);
    htkamd_model *model; CHECK(htkamd_model_create(d, &model));
    if (compat) CHECK(htkamd_model_set_compat(model, compat));

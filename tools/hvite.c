@@ -217,7 +217,11 @@ int main(int argc, char **argv)
    CHECK(htkamd_mmf_finish(mmf, hmmList, hmmDir, hmmExt));
    const htkamd_model_desc *d = htkamd_mmf_desc(mmf);
    const int D = d->vecSize;
-   htkamd_model *model; CHECK(htkamd_model_create(d, &model));
+   htkamd_model *model;
+   if (htkamd_mmf_inv_cov(mmf)) {                      /* a FULLC set: FOutP through the exact kernel (MOutP HModel.c:5484) */
+      if (scoreMode != HTKAMD_SCORE_EXACT) DIE("hvite: a FULLC set is scored in the exact mode only (--score exact)");
+      CHECK(htkamd_model_create_full(d, htkamd_mmf_inv_cov(mmf), &model));
+   } else CHECK(htkamd_model_create(d, &model));
    if (d->hsKind == HTKAMD_HS_TIED) CHECK(htkamd_model_set_tm_beam(model, tmBeam));
    htkamd_viterbi *vit; CHECK(htkamd_viterbi_create(model, &vit));
    const char *tk = cfg_get(&cfg, "TARGETKIND");
