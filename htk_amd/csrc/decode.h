@@ -1,8 +1,10 @@
 // decode.h -- what the network decoder's kernels (decode.hip: 1-best; decode_n.hip: N-best token sets + lattice) and their host code share.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <functional>
 #include <vector>
 #include "internal.h"
+#include "kernels.h"
 
 #define DEC_THREADS 1024
 #define DEC_MAXN 8              /* states per model incl. entry/exit */
@@ -99,6 +101,46 @@ int htkamd_launch_decode_ord(const OrdArgs &a, int nSel, hipStream_t s);
 int htkamd_launch_score_transpose(const float *in, float *out, const DecUtt *dUtt, int nUtt, int maxT, int ns, hipStream_t s);
 
 
+// The decoders' device workspace: a fixed table of buffers kept between calls and grown (never shrunk) when a batch needs more -- the score
+// block and the path tables are gigabytes at 256 utterances: allocating and freeing them per call cost 5 - 500 ms of a 130 ms call.
+// A call takes its buffers in a fixed order from slot 0 (begin, get, get, ...); a group of buffers that only some calls need starts at a
+// slot of its own (seek), so that the buffers after it keep their slots whether the group is there or not.
+struct DecArena {
+   enum { SLOTS = 64 };
+   void *ptr[SLOTS] = {};
+   size_t cap[SLOTS] = {};
+   hipStream_t stream = nullptr;       // of the current call: synchronised before a buffer in use is replaced
+   const char *who = "";               // ... and the name its errors start with
+   int next = 0;                       // slot the next get() takes
+   int rc = HTKAMD_OK;                 // first failure of the call: every later get() returns NULL
+   void begin(hipStream_t s, const char *prefix) { stream = s; who = prefix; next = 0; rc = HTKAMD_OK; }
+   void seek(int slot)                 // the next get() takes `slot` (HTKAMD_EINVAL where the buffers before it have reached it)
+   {
+      if (next > slot && !rc) { htkamd_set_error("%s: workspace buffers run into slot %d", who, slot); rc = HTKAMD_EINVAL; }
+      next = slot;
+   }
+   void *get(size_t bytes);            // at least `bytes` (0 counts as 1); NULL and rc on failure: HTKAMD_ENOMEM, HTKAMD_EINVAL out of slots
+   void release() { for (int i = 0; i < SLOTS; i++) { if (ptr[i]) (void)hipFree(ptr[i]); ptr[i] = nullptr; cap[i] = 0; } }
+};
+
+// What the two decoders do alike before their token kernels run (decode.hip).
+int htkamd_decoder_order(const htkamd_decoder *d);      // the decoder's order mode, HTKAMD_DECODE_ORDER (fast | exact | anything else: auto) overriding it
+// Utterances u0 .. u1 of a batch: as many as stay under ~24 GB of per-utterance work space by the caller's estimate (at least one), their
+// descriptors, the score block's tasks and the sizes of the per-utterance arrays in elements.
+struct DecBatch {
+   int u1, maxT;
+   std::vector<DecUtt> utt;
+   std::vector<ScoreTask> tasks;
+   size_t score, tok, node, path;
+};
+// uttBytes(T): the estimate for an utterance of T frames; DecUtt::out0 = k * outStride; path records per utterance: pathMul * (T + 1) * nWordNodes + pathExtra
+void htkamd_decoder_plan(const DecNet &N, const int *frameOff, int u0, int nUtt, int ns, int FR, int SL, const std::function<size_t(size_t)> &uttBytes,
+                         size_t outStride, size_t pathMul, size_t pathExtra, DecBatch &b);
+// Uploads the batch's descriptors and tasks (dTasks: room for the tasks and the queue's counter behind them), scores the network's states
+// for the batch's frames into dScore (state-major) and transposes that into dScoreT.  evScore (may be NULL): recorded before the scoring launch.
+int htkamd_decoder_score(const htkamd_decoder *d, int scoreMode, const float *dX, int nRows, const DecBatch &b, int ns, void *dUtt, void *dTasks,
+                         float *dScore, float *dScoreT, hipEvent_t evScore, const char *who, hipStream_t s);
+
 struct htkamd_decoder {
    htkamd_model *m;
    DecNet net;                         // device pointers
@@ -107,15 +149,10 @@ struct htkamd_decoder {
    std::vector<int> hostModel;         // [nNodes] htkamd_net_desc.model (WORD nodes: the pronunciation)
    int *d_usedStates;
    int maxWidthNodes;
-   // workspace of htkamd_decoder_run, kept between calls and grown when a batch needs more (the score block and the path tables are
-   // gigabytes at 256 utterances: allocating and freeing them per call cost 5 - 500 ms of a 130 ms call)
-   void *ws[32];
-   size_t wsCap[32];
+   DecArena ws, wsN;                   // workspaces of htkamd_decoder_run and of htkamd_decoder_run_lattice (one each: alternating calls do not evict each other)
    int orderMode;                      // HTKAMD_ORDER_AUTO / _FAST / _EXACT (htkamd_decoder_set_order)
    int lastTied;                       // utterances of the last run that went through the exact-order kernel
    hipEvent_t ev[4];                   // around the scoring kernels and around the token kernel of the last chunk of a run
    float lastScoreMs, lastTokenMs;
    long long lastLive[2];              // model-instance steps of the last run's register kernel: with a live token, without
-   void *wsN[48];                      // ... and of htkamd_decoder_run_lattice
-   size_t wsNCap[48];
 };

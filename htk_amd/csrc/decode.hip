@@ -27,6 +27,7 @@
 #include <cstring>
 #include <vector>
 #include <algorithm>
+#include <functional>
 #include "internal.h"
 #include "hipcheck.h"
 #include "kernels.h"
@@ -724,6 +725,73 @@ template <typename T> static int upv(htkamd_decoder *d, const std::vector<T> &v,
    return HTKAMD_OK;
 }
 
+void *DecArena::get(size_t n)
+{
+   const int i = next++;
+   if (rc) return nullptr;
+   if (i >= SLOTS) { htkamd_set_error("%s: more than %d workspace buffers", who, (int)SLOTS); rc = HTKAMD_EINVAL; return nullptr; }
+   if (n < 1) n = 1;
+   if (cap[i] < n) {
+      if (ptr[i]) { (void)hipStreamSynchronize(stream); (void)hipFree(ptr[i]); ptr[i] = nullptr; cap[i] = 0; }
+      const size_t want = n + n / 8;
+      hipError_t e = hipMalloc(&ptr[i], want);
+      if (e != hipSuccess) { htkamd_set_error("%s: hipMalloc(%zu): %s", who, want, hipGetErrorString(e)); rc = HTKAMD_ENOMEM; ptr[i] = nullptr; return nullptr; }
+      cap[i] = want;
+   }
+   return ptr[i];
+}
+
+int htkamd_decoder_order(const htkamd_decoder *d)
+{
+   if (const char *ev = getenv("HTKAMD_DECODE_ORDER")) return !strcmp(ev, "fast") ? HTKAMD_ORDER_FAST : !strcmp(ev, "exact") ? HTKAMD_ORDER_EXACT : HTKAMD_ORDER_AUTO;
+   return d->orderMode;
+}
+
+void htkamd_decoder_plan(const DecNet &N, const int *frameOff, int u0, int nUtt, int ns, int FR, int SL, const std::function<size_t(size_t)> &uttBytes,
+                         size_t outStride, size_t pathMul, size_t pathExtra, DecBatch &b)
+{
+   size_t bytes = 0; int u1 = u0;
+   while (u1 < nUtt) {
+      const size_t ub = uttBytes((size_t)(frameOff[u1 + 1] - frameOff[u1]));
+      if (u1 > u0 && bytes + ub > ((size_t)24 << 30)) break;
+      bytes += ub; u1++;
+   }
+   const int nu = u1 - u0;
+   b.u1 = u1; b.maxT = 0; b.score = b.tok = b.node = b.path = 0;
+   b.utt.assign(nu, DecUtt()); b.tasks.clear();
+   for (int k = 0; k < nu; k++) {
+      DecUtt &ud = b.utt[k];
+      ud.T = frameOff[u0 + k + 1] - frameOff[u0 + k]; ud.frame0 = frameOff[u0 + k]; ud.status = HTKAMD_UTT_OK; ud.idx = k;
+      ud.score0 = b.score; ud.tok0 = b.tok; ud.node0 = b.node; ud.path0 = b.path; ud.out0 = (size_t)k * outStride;
+      htkamd_tile_tasks(b.tasks, ud.frame0, ud.T, 0, ns, ud.score0, ud.T, FR, SL);
+      b.maxT = std::max(b.maxT, ud.T);
+      b.score += (size_t)ns * ud.T; b.tok += (size_t)N.nTok; b.node += (size_t)N.nNodes; b.path += pathMul * ((size_t)(ud.T + 1) * N.nWordNodes) + pathExtra;
+   }
+}
+
+int htkamd_decoder_score(const htkamd_decoder *d, int scoreMode, const float *dX, int nRows, const DecBatch &b, int ns, void *dUtt, void *dTasks,
+                         float *dScore, float *dScoreT, hipEvent_t evScore, const char *who, hipStream_t s)
+{
+   const htkamd_model *m = d->m;
+   const int nu = (int)b.utt.size();
+   hipError_t e;
+   if ((e = hipMemcpyAsync(dUtt, b.utt.data(), sizeof(DecUtt) * nu, hipMemcpyHostToDevice, s)) != hipSuccess ||
+       (e = hipMemcpyAsync(dTasks, b.tasks.data(), sizeof(ScoreTask) * b.tasks.size(), hipMemcpyHostToDevice, s)) != hipSuccess) {
+      htkamd_set_error("%s: %s", who, hipGetErrorString(e)); return HTKAMD_EHIP;
+   }
+   if (evScore) (void)hipEventRecord(evScore, s);
+   ScoreArgs sa = htkamd_score_args(m);
+   sa.tasks = (const ScoreTask *)dTasks; sa.nTasks = (int)b.tasks.size(); sa.X = dX; sa.slotState = d->d_usedStates; sa.out = dScore;
+   sa.taskCounter = (int *)((char *)dTasks + sizeof(ScoreTask) * b.tasks.size());
+   int rc;
+   if (m->NSt > 1 && scoreMode != HTKAMD_SCORE_EXACT) { htkamd_set_error("%s: multi-stream sets are scored in the exact mode only", who); return HTKAMD_EINVAL; }
+   else if (m->tiedMix) rc = htkamd_tm_score_block(m, sa, nRows, m->tmBeam, s);
+   else if (scoreMode != HTKAMD_SCORE_EXACT && scoreMode != HTKAMD_SCORE_MFMA && scoreMode != HTKAMD_SCORE_BF16) { htkamd_set_error("%s: unknown score mode %d", who, scoreMode); return HTKAMD_EINVAL; }
+   else rc = htkamd_launch_score(scoreMode, m, sa, s);   // exact: the decoded path is the reference's; matrix-core modes: tolerance class
+   if (rc) return rc;
+   return htkamd_launch_score_transpose(dScore, dScoreT, (const DecUtt *)dUtt, nu, b.maxT, ns, s);
+}
+
 extern "C" int htkamd_decoder_set_order(htkamd_decoder *d, int mode)
 {
    if (!d || mode < HTKAMD_ORDER_AUTO || mode > HTKAMD_ORDER_EXACT) { htkamd_set_error("decoder_set_order: bad argument"); return HTKAMD_EINVAL; }
@@ -751,8 +819,8 @@ extern "C" void htkamd_decoder_destroy(htkamd_decoder *d)
    if (!d) return;
    for (void *p : d->owned) (void)hipFree(p);
    for (hipEvent_t e : d->ev) if (e) (void)hipEventDestroy(e);
-   for (void *p : d->ws) if (p) (void)hipFree(p);
-   for (void *p : d->wsN) if (p) (void)hipFree(p);
+   d->ws.release();
+   d->wsN.release();
    delete d;
 }
 
@@ -1043,7 +1111,6 @@ extern "C" int htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_con
    }
    if (nUtt == 0) return HTKAMD_OK;
    hipStream_t s = (hipStream_t)stream;
-   htkamd_model *m = d->m;
    const DecNet &N = d->net;
    const int ns = (int)d->usedStates.size();
    // (the matrix-core kernels build their frames' operand once per task: four times as many states per task for them, as in forward-backward)
@@ -1051,90 +1118,30 @@ extern "C" int htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_con
    if (!d->ev[0]) for (int i = 0; i < 4; i++) HIPCHECK(hipEventCreate(&d->ev[i]));
    d->lastScoreMs = d->lastTokenMs = 0.0f;
    d->lastLive[0] = d->lastLive[1] = 0;
-   int orderMode = d->orderMode;
-   if (const char *ev = getenv("HTKAMD_DECODE_ORDER")) orderMode = !strcmp(ev, "fast") ? HTKAMD_ORDER_FAST : !strcmp(ev, "exact") ? HTKAMD_ORDER_EXACT : HTKAMD_ORDER_AUTO;
+   const int orderMode = htkamd_decoder_order(d);
    d->lastTied = 0;
+   DecArena &ws = d->ws;
+   enum { WS_ORDER = 16 };      // first slot of the exact-order pass's buffers
+   DecBatch bt;
    // chunk the batch so that the per-utterance work space (scores, tokens, path table) stays under ~24 GB
    int u0 = 0;
    while (u0 < nUtt) {
-      size_t bytes = 0; int u1 = u0;
-      while (u1 < nUtt) {
-         const size_t T = (size_t)(frameOff[u1 + 1] - frameOff[u1]);
-         const size_t b = (size_t)ns * T * 8 + (size_t)N.nTok * 16 + (size_t)N.nNodes * 24 + (T + 1) * (size_t)N.nWordNodes * 16;
-         if (u1 > u0 && bytes + b > ((size_t)24 << 30)) break;
-         bytes += b; u1++;
-      }
-      const int nu = u1 - u0;
-      std::vector<DecUtt> utt(nu);
-      std::vector<ScoreTask> tasks;
-      size_t score = 0, tok = 0, node = 0, path = 0;
-      for (int k = 0; k < nu; k++) {
-         DecUtt &ud = utt[k];
-         ud.T = frameOff[u0 + k + 1] - frameOff[u0 + k]; ud.frame0 = frameOff[u0 + k]; ud.status = HTKAMD_UTT_OK; ud.idx = k;
-         ud.score0 = score; ud.tok0 = tok; ud.node0 = node; ud.path0 = path; ud.out0 = (size_t)k * maxWords;
-         for (int ti = 0; ti * FR < ud.T; ti++)
-            for (int ch = 0; ch * SL < ns; ch++) {
-               ScoreTask tk;
-               tk.frame0 = ud.frame0 + ti * FR; tk.nFrames = std::min(FR, ud.T - ti * FR);
-               tk.slot0 = ch * SL; tk.nSlots = std::min(SL, ns - ch * SL); tk.outSlot0 = ch * SL; tk.ldo = ud.T;
-               tk.outBase = ud.score0 + (size_t)ti * FR;
-               tasks.push_back(tk);
-            }
-         score += (size_t)ns * ud.T; tok += (size_t)N.nTok; node += (size_t)N.nNodes; path += (size_t)(ud.T + 1) * N.nWordNodes;
-      }
-      void *dScore = nullptr, *dTok = nullptr, *dEx = nullptr, *dImax = nullptr;
-      void *dPPrev = nullptr, *dPLike = nullptr, *dPLm = nullptr, *dUtt = nullptr, *dTasks = nullptr, *dOutI = nullptr, *dOutF = nullptr, *dTot = nullptr, *dOutD = nullptr;
-      int rc = HTKAMD_OK;
-      int wsi = 0;
-      auto A = [&](void **p, size_t n) {                 // the decoder's own buffers, grown (not shrunk) as batches ask
-         const int i = wsi++;
-         if (rc) return;
-         if (n < 1) n = 1;
-         if (d->wsCap[i] < n) {
-            if (d->ws[i]) { (void)hipStreamSynchronize(s); (void)hipFree(d->ws[i]); d->ws[i] = nullptr; d->wsCap[i] = 0; }
-            const size_t want = n + n / 8;
-            hipError_t e = hipMalloc(&d->ws[i], want);
-            if (e != hipSuccess) { htkamd_set_error("decoder_run: hipMalloc(%zu): %s", want, hipGetErrorString(e)); rc = HTKAMD_ENOMEM; d->ws[i] = nullptr; return; }
-            d->wsCap[i] = want;
-         }
-         *p = d->ws[i];
-      };
-      void *dScoreT = nullptr;
-      A(&dScore, score * 4); A(&dScoreT, score * 4); A(&dTok, tok * sizeof(Tok)); A(&dEx, node * sizeof(Tok)); A(&dImax, node * 8);
-      A(&dPPrev, path * 4); A(&dPLike, path * 8); A(&dPLm, path * 4);
-      A(&dUtt, sizeof(DecUtt) * nu); A(&dTasks, sizeof(ScoreTask) * tasks.size() + sizeof(int));
-      A(&dOutI, sizeof(int) * ((size_t)nu * maxWords * 3 + nu)); A(&dOutF, sizeof(float) * ((size_t)nu * maxWords * 3 + nu)); A(&dTot, sizeof(double) * nu);
-      A(&dOutD, sizeof(double) * (size_t)nu * maxWords);
-      void *dTie = nullptr;
+      htkamd_decoder_plan(N, frameOff, u0, nUtt, ns, FR, SL,
+                          [&](size_t T) { return (size_t)ns * T * 8 + (size_t)N.nTok * 16 + (size_t)N.nNodes * 24 + (T + 1) * (size_t)N.nWordNodes * 16; },
+                          (size_t)maxWords, 1, 0, bt);
+      const int u1 = bt.u1, nu = u1 - u0;
+      const size_t score = bt.score, tok = bt.tok, node = bt.node, path = bt.path;
+      ws.begin(s, "decoder_run");
+      void *dScore = ws.get(score * 4), *dScoreT = ws.get(score * 4), *dTok = ws.get(tok * sizeof(Tok)), *dEx = ws.get(node * sizeof(Tok)), *dImax = ws.get(node * 8);
+      void *dPPrev = ws.get(path * 4), *dPLike = ws.get(path * 8), *dPLm = ws.get(path * 4);
+      void *dUtt = ws.get(sizeof(DecUtt) * nu), *dTasks = ws.get(sizeof(ScoreTask) * bt.tasks.size() + sizeof(int));
+      void *dOutI = ws.get(sizeof(int) * ((size_t)nu * maxWords * 3 + nu)), *dOutF = ws.get(sizeof(float) * ((size_t)nu * maxWords * 3 + nu)), *dTot = ws.get(sizeof(double) * nu);
+      void *dOutD = ws.get(sizeof(double) * (size_t)nu * maxWords);
       const size_t tieBytes = (sizeof(int) * nu + 7) & ~(size_t)7;
-      A(&dTie, tieBytes + sizeof(unsigned long long) * (2 * (size_t)nu));
+      void *dTie = ws.get(tieBytes + sizeof(unsigned long long) * (2 * (size_t)nu));
+      int rc = ws.rc;
       std::vector<int> hI; std::vector<float> hF; std::vector<double> hT, hD;
-      if (!rc) {
-         hipError_t e;
-         if ((e = hipMemcpyAsync(dUtt, utt.data(), sizeof(DecUtt) * nu, hipMemcpyHostToDevice, s)) != hipSuccess ||
-             (e = hipMemcpyAsync(dTasks, tasks.data(), sizeof(ScoreTask) * tasks.size(), hipMemcpyHostToDevice, s)) != hipSuccess) {
-            htkamd_set_error("decoder_run: %s", hipGetErrorString(e)); rc = HTKAMD_EHIP;
-         }
-      }
-      if (!rc) (void)hipEventRecord(d->ev[0], s);
-      if (!rc) {
-         ScoreArgs sa;
-         sa.tasks = (const ScoreTask *)dTasks; sa.nTasks = (int)tasks.size(); sa.X = dX; sa.slotState = d->d_usedStates; sa.out = (float *)dScore;
-         sa.stateCompOff = m->d_stateCompOff; sa.compGauss = m->d_compGauss; sa.compLogWt = m->d_compLogWt;
-         sa.gparam = m->d_gparam; sa.PS = m->PS; sa.D = m->D; sa.minLogExp = m->minLogExp;
-         sa.laddTab = m->d_laddTab; sa.taskCounter = (int *)((char *)dTasks + sizeof(ScoreTask) * tasks.size());
-         sa.mfmaTab = m->d_mfmaTab; sa.stateTileOff = m->d_stateTileOff; sa.bf16Tab = m->d_bf16Tab; sa.var = m->d_var;
-         sa.NSt = m->NSt; sa.streamWt = m->d_streamWt;
-         if (m->NSt > 1 && cfg->scoreMode != HTKAMD_SCORE_EXACT) { htkamd_set_error("decoder_run: multi-stream sets are scored in the exact mode only"); rc = HTKAMD_EINVAL; }
-         else if (m->tiedMix) rc = htkamd_tm_score_block(m, sa, frameOff[u1], m->tmBeam, s);
-         else if (cfg->scoreMode != HTKAMD_SCORE_EXACT && cfg->scoreMode != HTKAMD_SCORE_MFMA && cfg->scoreMode != HTKAMD_SCORE_BF16) { htkamd_set_error("decoder_run: unknown score mode %d", cfg->scoreMode); rc = HTKAMD_EINVAL; }
-         else rc = htkamd_launch_score(cfg->scoreMode, m, sa, s);   // exact: the decoded path is the reference's; matrix-core modes: tolerance class
-      }
-      if (!rc) {
-         int maxT = 0;
-         for (int k = 0; k < nu; k++) maxT = std::max(maxT, utt[k].T);
-         rc = htkamd_launch_score_transpose((const float *)dScore, (float *)dScoreT, (const DecUtt *)dUtt, nu, maxT, ns, s);
-      }
+      if (!rc) rc = htkamd_decoder_score(d, cfg->scoreMode, dX, frameOff[u1], bt, ns, dUtt, dTasks, (float *)dScore, (float *)dScoreT, d->ev[0], "decoder_run", s);
       if (!rc) { (void)hipEventRecord(d->ev[1], s); (void)hipEventRecord(d->ev[2], s); }
       DecArgs a;
       memset(&a, 0, sizeof(a));
@@ -1188,7 +1195,7 @@ extern "C" int htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_con
          const int pathExtra = 64;
          for (int k = 0; k < nu && !rc; k++)
             if (flags[k]) {
-               DecUtt ud = utt[k];
+               DecUtt ud = bt.utt[k];
                ud.path0 = opath;
                opath += 3 * ((size_t)(ud.T + 1) * N.nWordNodes) + pathExtra;      // StepWord2 "may be repeated" (HRec.c:1046): room for every word node thrice per frame
                sel.push_back(ud);
@@ -1196,9 +1203,10 @@ extern "C" int htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_con
          if (!rc && !sel.empty()) {
             const int nSel = (int)sel.size();
             const int seqCap = 8 * N.nNodes + 1024;          // appends of one frame's pass 2 (attaches + moves) on top of the live instances
-            void *dSel = nullptr, *dSeq = nullptr, *dPos = nullptr, *dOoo = nullptr, *oPrev = nullptr, *oLike = nullptr, *oLm = nullptr, *oNode = nullptr, *oFrame = nullptr;
-            A(&dSel, sizeof(DecUtt) * nSel); A(&dSeq, sizeof(int) * (size_t)nSel * 2 * seqCap); A(&dPos, sizeof(int) * node); A(&dOoo, node);
-            A(&oPrev, opath * 4); A(&oLike, opath * 8); A(&oLm, opath * 4); A(&oNode, opath * 4); A(&oFrame, opath * 4);
+            ws.seek(WS_ORDER);
+            void *dSel = ws.get(sizeof(DecUtt) * nSel), *dSeq = ws.get(sizeof(int) * (size_t)nSel * 2 * seqCap), *dPos = ws.get(sizeof(int) * node), *dOoo = ws.get(node);
+            void *oPrev = ws.get(opath * 4), *oLike = ws.get(opath * 8), *oLm = ws.get(opath * 4), *oNode = ws.get(opath * 4), *oFrame = ws.get(opath * 4);
+            rc = ws.rc;
             if (!rc) {
                hipError_t e = hipMemcpyAsync(dSel, sel.data(), sizeof(DecUtt) * nSel, hipMemcpyHostToDevice, s);
                if (e != hipSuccess) { htkamd_set_error("decoder_run: %s", hipGetErrorString(e)); rc = HTKAMD_EHIP; }

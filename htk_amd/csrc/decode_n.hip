@@ -899,112 +899,61 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
    if (nToks < 2 || nToks > NT) { htkamd_set_error("decoder_run_lattice: nToks = %d (2..%d tokens per state)", nToks, NT); return HTKAMD_EINVAL; }
    if (nUtt == 0) return HTKAMD_OK;
    hipStream_t s = (hipStream_t)stream;
-   htkamd_model *m = d->m;
    const DecNet &N = d->net;
    const int ns = (int)d->usedStates.size();
    const int FR = SCORE_TILE_FRAMES, SL = SCORE_TASK_SLOTS;
    // the list kernel (k_decode_ord_n) unless the static order was asked for: in N-best mode the order of the merges is in every
    // alternative's likelihood, so "exact" is the default here, not a fallback
-   int orderMode = d->orderMode;
-   if (const char *ev = getenv("HTKAMD_DECODE_ORDER")) orderMode = !strcmp(ev, "fast") ? HTKAMD_ORDER_FAST : !strcmp(ev, "exact") ? HTKAMD_ORDER_EXACT : HTKAMD_ORDER_AUTO;
+   const int orderMode = htkamd_decoder_order(d);
    if (alignMode && orderMode == HTKAMD_ORDER_FAST) { htkamd_set_error("decoder_run_lattice_align: alignment records need the list kernel (not HTKAMD_ORDER_FAST)"); return HTKAMD_EINVAL; }
    const bool listOrder = orderMode != HTKAMD_ORDER_FAST;
    const size_t pathMul = listOrder ? 3 : 1, pathExtra = listOrder ? 64 : 0;       // StepWord2 "may be repeated" (HRec.c:1046)
    const int seqCap = 8 * N.nNodes + 1024;
    d->lastTied = 0;
+   DecArena &ws = d->wsN;
+   enum { WS_LIST = 32, WS_ALIGN = 40 };      // first slots of the list kernel's buffers and of the alignment records
+   DecBatch bt;
    int u0 = 0;
    while (u0 < nUtt) {
-      size_t bytes = 0; int u1 = u0;
-      while (u1 < nUtt) {
-         const size_t T = (size_t)(frameOff[u1 + 1] - frameOff[u1]);
-         const size_t b = (size_t)ns * T * 8 + (size_t)N.nTok * 2 * sizeof(TSet) + (size_t)N.nNodes * (sizeof(TSet) + 8) + (pathMul * (T + 1) * (size_t)N.nWordNodes + pathExtra) * (24 + 16 * (NT - 1) + 8) +
-                          (listOrder ? (size_t)seqCap * 8 : 0);
-         if (u1 > u0 && bytes + b > ((size_t)24 << 30)) break;
-         bytes += b; u1++;
-      }
-      const int nu = u1 - u0;
-      std::vector<DecUtt> utt(nu);
-      std::vector<ScoreTask> tasks;
-      size_t score = 0, tok = 0, node = 0, path = 0;
-      for (int k = 0; k < nu; k++) {
-         DecUtt &ud = utt[k];
-         ud.T = frameOff[u0 + k + 1] - frameOff[u0 + k]; ud.frame0 = frameOff[u0 + k]; ud.status = HTKAMD_UTT_OK; ud.idx = k;
-         ud.score0 = score; ud.tok0 = tok; ud.node0 = node; ud.path0 = path; ud.out0 = 0;
-         for (int ti = 0; ti * FR < ud.T; ti++)
-            for (int ch = 0; ch * SL < ns; ch++) {
-               ScoreTask tk;
-               tk.frame0 = ud.frame0 + ti * FR; tk.nFrames = std::min(FR, ud.T - ti * FR);
-               tk.slot0 = ch * SL; tk.nSlots = std::min(SL, ns - ch * SL); tk.outSlot0 = ch * SL; tk.ldo = ud.T;
-               tk.outBase = ud.score0 + (size_t)ti * FR;
-               tasks.push_back(tk);
-            }
-         score += (size_t)ns * ud.T; tok += (size_t)N.nTok; node += (size_t)N.nNodes; path += pathMul * ((size_t)(ud.T + 1) * N.nWordNodes) + pathExtra;
-      }
-      int rc = HTKAMD_OK, wsi = 0;
-      auto A = [&](size_t n) -> void * {                 // the decoder's own buffers, kept between calls and grown as batches ask (decode.hip)
-         const int i = wsi++;
-         if (rc) return nullptr;
-         if (n < 1) n = 1;
-         if (d->wsNCap[i] < n) {
-            if (d->wsN[i]) { (void)hipStreamSynchronize(s); (void)hipFree(d->wsN[i]); d->wsN[i] = nullptr; d->wsNCap[i] = 0; }
-            const size_t want = n + n / 8;
-            hipError_t e = hipMalloc(&d->wsN[i], want);
-            if (e != hipSuccess) { htkamd_set_error("decoder_run_lattice: hipMalloc(%zu): %s", want, hipGetErrorString(e)); rc = HTKAMD_ENOMEM; d->wsN[i] = nullptr; return nullptr; }
-            d->wsNCap[i] = want;
-         }
-         return d->wsN[i];
-      };
+      htkamd_decoder_plan(N, frameOff, u0, nUtt, ns, FR, SL,
+                          [&](size_t T) { return (size_t)ns * T * 8 + (size_t)N.nTok * 2 * sizeof(TSet) + (size_t)N.nNodes * (sizeof(TSet) + 8) +
+                                                 (pathMul * (T + 1) * (size_t)N.nWordNodes + pathExtra) * (24 + 16 * (NT - 1) + 8) + (listOrder ? (size_t)seqCap * 8 : 0); },
+                          0, pathMul, pathExtra, bt);
+      const int u1 = bt.u1, nu = u1 - u0, maxT = bt.maxT;
+      const size_t score = bt.score, tok = bt.tok, node = bt.node, path = bt.path;
+      ws.begin(s, "decoder_run_lattice");
       NArgs a; memset(&a, 0, sizeof(a));
-      void *dScore = A(score * 4), *dScoreT = A(score * 4);
-      a.tokA = (TSet *)A(tok * sizeof(TSet)); a.tokB = (TSet *)A(tok * sizeof(TSet)); a.ex = (TSet *)A(node * sizeof(TSet)); a.imax = (double *)A(node * 8);
-      a.pathPrev = (int *)A(path * 4); a.pathLike = (double *)A(path * 8); a.pathLm = (float *)A(path * 4);
-      a.altN = (int *)A(path * 4); a.altPrev = (int *)A(path * 4 * (NT - 1)); a.altLike = (double *)A(path * 8 * (NT - 1)); a.altLm = (float *)A(path * 4 * (NT - 1));
-      a.mark = (int *)A(path * 4); a.stack = (int *)A(sizeof(int) * (size_t)nu * 2 * maxLatNodes); a.nodePath = (int *)A(sizeof(int) * (size_t)nu * maxLatNodes);
-      void *dUtt = A(sizeof(DecUtt) * nu), *dTasks = A(sizeof(ScoreTask) * tasks.size() + sizeof(int));
-      a.latN = (int *)A(sizeof(int) * 2 * nu);
-      a.nodeFrame = (int *)A(sizeof(int) * (size_t)nu * maxLatNodes); a.nodeNet = (int *)A(sizeof(int) * (size_t)nu * maxLatNodes); a.nodeLike = (double *)A(8 * (size_t)nu * maxLatNodes);
-      a.arcStart = (int *)A(sizeof(int) * (size_t)nu * maxLatArcs); a.arcEnd = (int *)A(sizeof(int) * (size_t)nu * maxLatArcs);
-      a.arcAc = (float *)A(4 * (size_t)nu * maxLatArcs); a.arcLm = (float *)A(4 * (size_t)nu * maxLatArcs); a.arcPr = (float *)A(4 * (size_t)nu * maxLatArcs);
-      a.arcScore = (double *)A(8 * (size_t)nu * maxLatArcs); a.total = (double *)A(8 * (size_t)nu);
+      void *dScore = ws.get(score * 4), *dScoreT = ws.get(score * 4);
+      a.tokA = (TSet *)ws.get(tok * sizeof(TSet)); a.tokB = (TSet *)ws.get(tok * sizeof(TSet)); a.ex = (TSet *)ws.get(node * sizeof(TSet)); a.imax = (double *)ws.get(node * 8);
+      a.pathPrev = (int *)ws.get(path * 4); a.pathLike = (double *)ws.get(path * 8); a.pathLm = (float *)ws.get(path * 4);
+      a.altN = (int *)ws.get(path * 4); a.altPrev = (int *)ws.get(path * 4 * (NT - 1)); a.altLike = (double *)ws.get(path * 8 * (NT - 1)); a.altLm = (float *)ws.get(path * 4 * (NT - 1));
+      a.mark = (int *)ws.get(path * 4); a.stack = (int *)ws.get(sizeof(int) * (size_t)nu * 2 * maxLatNodes); a.nodePath = (int *)ws.get(sizeof(int) * (size_t)nu * maxLatNodes);
+      void *dUtt = ws.get(sizeof(DecUtt) * nu), *dTasks = ws.get(sizeof(ScoreTask) * bt.tasks.size() + sizeof(int));
+      a.latN = (int *)ws.get(sizeof(int) * 2 * nu);
+      a.nodeFrame = (int *)ws.get(sizeof(int) * (size_t)nu * maxLatNodes); a.nodeNet = (int *)ws.get(sizeof(int) * (size_t)nu * maxLatNodes); a.nodeLike = (double *)ws.get(8 * (size_t)nu * maxLatNodes);
+      a.arcStart = (int *)ws.get(sizeof(int) * (size_t)nu * maxLatArcs); a.arcEnd = (int *)ws.get(sizeof(int) * (size_t)nu * maxLatArcs);
+      a.arcAc = (float *)ws.get(4 * (size_t)nu * maxLatArcs); a.arcLm = (float *)ws.get(4 * (size_t)nu * maxLatArcs); a.arcPr = (float *)ws.get(4 * (size_t)nu * maxLatArcs);
+      a.arcScore = (double *)ws.get(8 * (size_t)nu * maxLatArcs); a.total = (double *)ws.get(8 * (size_t)nu);
       if (listOrder) {
-         a.seq = (int *)A(sizeof(int) * (size_t)nu * 2 * seqCap); a.seqCap = seqCap; a.pos = (int *)A(sizeof(int) * node); a.ooo = (unsigned char *)A(node);
-         a.pathNode = (int *)A(path * 4); a.pathFrame = (int *)A(path * 4); a.pathExtra = (int)pathExtra;
+         ws.seek(WS_LIST);
+         a.seq = (int *)ws.get(sizeof(int) * (size_t)nu * 2 * seqCap); a.seqCap = seqCap; a.pos = (int *)ws.get(sizeof(int) * node); a.ooo = (unsigned char *)ws.get(node);
+         a.pathNode = (int *)ws.get(path * 4); a.pathFrame = (int *)ws.get(path * 4); a.pathExtra = (int)pathExtra;
       }
-      int maxT = 0;
-      for (int k = 0; k < nu; k++) maxT = std::max(maxT, utt[k].T);
       if (alignMode) {
+         ws.seek(WS_ALIGN);
          // Align records: one per token of a set where it enters a state (-f) and where it leaves a model (-m), never freed within an
          // utterance (the reference collects garbage; here the utterance must fit): frames x model nodes x tokens x (states + 1), capped
          size_t cap = (size_t)(maxT + 1) * (size_t)N.nHmm * (size_t)nToks * (size_t)((alignMode & 2 ? 3 : 0) + (alignMode & 1 ? 1 : 0));
          if (cap > ((size_t)1 << 27)) cap = (size_t)1 << 27;
          if (cap * (size_t)nu * sizeof(AlignRec) > ((size_t)16 << 30)) cap = ((size_t)16 << 30) / ((size_t)nu * sizeof(AlignRec));
-         a.alignMode = alignMode; a.alCap = (int)cap; a.al = (AlignRec *)A(sizeof(AlignRec) * cap * nu); a.alCount = (int *)A(sizeof(int) * nu);
-         a.pathAlign = (int *)A(path * 4); a.altAlign = (int *)A(path * 4 * (NT - 1));
-         a.maxAlign = maxAlign; a.arcAlignOff = (int *)A(sizeof(int) * (size_t)nu * (maxLatArcs + 1));
-         a.alState = (int *)A(sizeof(int) * (size_t)nu * maxAlign); a.alNode = (int *)A(sizeof(int) * (size_t)nu * maxAlign); a.alDur = (int *)A(sizeof(int) * (size_t)nu * maxAlign);
-         a.alLike = (float *)A(sizeof(float) * (size_t)nu * maxAlign);
+         a.alignMode = alignMode; a.alCap = (int)cap; a.al = (AlignRec *)ws.get(sizeof(AlignRec) * cap * nu); a.alCount = (int *)ws.get(sizeof(int) * nu);
+         a.pathAlign = (int *)ws.get(path * 4); a.altAlign = (int *)ws.get(path * 4 * (NT - 1));
+         a.maxAlign = maxAlign; a.arcAlignOff = (int *)ws.get(sizeof(int) * (size_t)nu * (maxLatArcs + 1));
+         a.alState = (int *)ws.get(sizeof(int) * (size_t)nu * maxAlign); a.alNode = (int *)ws.get(sizeof(int) * (size_t)nu * maxAlign); a.alDur = (int *)ws.get(sizeof(int) * (size_t)nu * maxAlign);
+         a.alLike = (float *)ws.get(sizeof(float) * (size_t)nu * maxAlign);
       }
-      if (!rc) {
-         hipError_t e;
-         if ((e = hipMemcpyAsync(dUtt, utt.data(), sizeof(DecUtt) * nu, hipMemcpyHostToDevice, s)) != hipSuccess ||
-             (e = hipMemcpyAsync(dTasks, tasks.data(), sizeof(ScoreTask) * tasks.size(), hipMemcpyHostToDevice, s)) != hipSuccess) {
-            htkamd_set_error("decoder_run_lattice: %s", hipGetErrorString(e)); rc = HTKAMD_EHIP;
-         }
-      }
-      if (!rc) {
-         ScoreArgs sa;
-         sa.tasks = (const ScoreTask *)dTasks; sa.nTasks = (int)tasks.size(); sa.X = dX; sa.slotState = d->d_usedStates; sa.out = (float *)dScore;
-         sa.stateCompOff = m->d_stateCompOff; sa.compGauss = m->d_compGauss; sa.compLogWt = m->d_compLogWt;
-         sa.gparam = m->d_gparam; sa.PS = m->PS; sa.D = m->D; sa.minLogExp = m->minLogExp;
-         sa.laddTab = m->d_laddTab; sa.taskCounter = (int *)((char *)dTasks + sizeof(ScoreTask) * tasks.size());
-         sa.mfmaTab = m->d_mfmaTab; sa.stateTileOff = m->d_stateTileOff; sa.bf16Tab = m->d_bf16Tab; sa.var = m->d_var;
-         sa.NSt = m->NSt; sa.streamWt = m->d_streamWt;
-         if (m->NSt > 1 && cfg->scoreMode != HTKAMD_SCORE_EXACT) { htkamd_set_error("decoder_run_lattice: multi-stream sets are scored in the exact mode only"); rc = HTKAMD_EINVAL; }
-         else if (m->tiedMix) rc = htkamd_tm_score_block(m, sa, frameOff[u1], m->tmBeam, s);
-         else if (cfg->scoreMode != HTKAMD_SCORE_EXACT && cfg->scoreMode != HTKAMD_SCORE_MFMA && cfg->scoreMode != HTKAMD_SCORE_BF16) { htkamd_set_error("decoder_run_lattice: unknown score mode %d", cfg->scoreMode); rc = HTKAMD_EINVAL; }
-         else rc = htkamd_launch_score(cfg->scoreMode, m, sa, s);
-      }
-      if (!rc) rc = htkamd_launch_score_transpose((const float *)dScore, (float *)dScoreT, (const DecUtt *)dUtt, nu, maxT, ns, s);
+      int rc = ws.rc;
+      if (!rc) rc = htkamd_decoder_score(d, cfg->scoreMode, dX, frameOff[u1], bt, ns, dUtt, dTasks, (float *)dScore, (float *)dScoreT, nullptr, "decoder_run_lattice", s);
       if (!rc) {
          a.net = N; a.utt = (const DecUtt *)dUtt; a.nUtt = nu; a.score = (const float *)dScoreT; a.ns = ns;
          a.genBeam = cfg->genBeam; a.wordBeam = cfg->wordBeam; a.nBeam = nBeam; a.lmScale = cfg->lmScale; a.wordPen = cfg->wordPen; a.prScale = cfg->prScale;

@@ -14,26 +14,10 @@
 #include "internal.h"
 #include "hipcheck.h"
 #include "kernels.h"
+#include "devbuf.h"
 
-struct DevBuf {
-   void *p = nullptr;
-   size_t cap = 0;
-   bool view = false;            // p points into another allocation (the batch-table arena)
-   void set_view(void *q) { if (p && !view) (void)hipFree(p); p = q; cap = 0; view = true; }
-   int reserve(size_t bytes)
-   {
-      if (view) { p = nullptr; view = false; cap = 0; }
-      if (bytes <= cap) return HTKAMD_OK;
-      if (p) (void)hipFree(p);
-      p = nullptr; cap = 0;
-      size_t want = bytes + bytes / 8;
-      hipError_t e = hipMalloc(&p, want);
-      if (e != hipSuccess) { htkamd_set_error("fb: hipMalloc(%zu bytes): %s", want, hipGetErrorString(e)); return HTKAMD_ENOMEM; }
-      cap = want;
-      return HTKAMD_OK;
-   }
-   void release() { if (p && !view) (void)hipFree(p); p = nullptr; cap = 0; view = false; }
-};
+static constexpr char fbOwner[] = "fb";
+typedef DevBufT<fbOwner> DevBuf;
 
 // Small persistent worker pool for the host-side batch preparation (thread creation costs more than a share's work).
 struct PrepPool {
@@ -710,17 +694,15 @@ static int fb_execute_impl(htkamd_fb *fb, const htkamd_fb_config *cfg, htkamd_ac
       return HTKAMD_EINVAL;
    }
 
-   ScoreArgs sa;
+   ScoreArgs sa = htkamd_score_args(m);
+   sa.NSt = 1; sa.streamWt = nullptr;      // the rows are (stream, chain state) elements: htkamd_launch_combine_streams sums them
    const bool wideTasks = (cfg->scoreMode & (HTKAMD_SCORE_F16 | HTKAMD_SCORE_BF16 | HTKAMD_SCORE_MFMA)) != 0;
    sa.tasks = (const ScoreTask *)(wideTasks ? fb->d_tasksW.p : fb->d_tasks.p); sa.nTasks = (int)(wideTasks ? fb->tasksW.size() : fb->tasks.size()); sa.X = fb->dX;
    sa.slotState = (const int *)fb->d_slotState.p; sa.out = (float *)fb->d_outp.p;
    if (m->NSt > 1) { sa.slotState = (const int *)fb->d_slotStateU.p; sa.out = (float *)fb->d_outpU.p; }      // per (stream, chain state)
-   sa.stateCompOff = m->d_stateCompOff; sa.compGauss = m->d_compGauss; sa.compLogWt = m->d_compLogWt;
-   sa.gparam = m->d_gparam; sa.PS = m->PS; sa.D = m->D; sa.minLogExp = m->minLogExp;
-   sa.laddTab = m->d_laddTab; sa.taskCounter = (int *)fb->d_counter.p;
+   sa.taskCounter = (int *)fb->d_counter.p;
    if (wideTasks && m->NSt == 1 && fb->wqStart.size() == 9) { sa.qStart = (const int *)fb->d_wqStart.p; sa.qCounters = (int *)fb->d_counter.p + 8; }
    if ((cfg->scoreMode & HTKAMD_SCORE_BF16) && !(cfg->scoreMode & HTKAMD_SCORE_F16) && m->NSt == 1 && !getenv("HTKAMD_NO_TAPER_SKIP")) sa.slotRange = (const int *)fb->d_slotRange.p;      // (the switch: for A/B measurements)
-   sa.mfmaTab = m->d_mfmaTab; sa.stateTileOff = m->d_stateTileOff; sa.bf16Tab = m->d_bf16Tab; sa.var = m->d_var;
    fb->f16Pass = (cfg->scoreMode & HTKAMD_SCORE_F16) != 0 && !m->tiedMix && sa.nTasks > 0;      // no tasks, no launch: nothing zeroes or raises the flag
    if (fb->f16Pass) {      // the pass's own range flag, behind the status words (zeroed with the task counter before it, by the launcher)
       sa.taskCounter = (int *)((char *)fb->d_pr.p + (sizeof(double) + sizeof(int)) * (size_t)fb->nUtt);

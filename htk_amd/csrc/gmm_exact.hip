@@ -258,8 +258,7 @@ static int outp_block(htkamd_model *m, const float *dX, int T, const int *dState
    if (T == 0 || ns == 0) return HTKAMD_OK;
    hipStream_t s = (hipStream_t)stream;
    const int FR = SCORE_TILE_FRAMES, SL = SCORE_TASK_SLOTS;
-   const int nTiles = (T + FR - 1) / FR, nChunks = (ns + SL - 1) / SL;
-   const int nTasks = nTiles * nChunks;
+   const int nTasks = htkamd_tile_count(T, ns, FR, SL);
    if (!m->obRing) { m->obRing = calloc(1, sizeof(ObRing)); if (!m->obRing) { htkamd_set_error("outp_block: out of memory"); return HTKAMD_ENOMEM; } }
    ObRing *ring = (ObRing *)m->obRing;
    ObSlot &sl = ring->s[ring->next];
@@ -276,28 +275,13 @@ static int outp_block(htkamd_model *m, const float *dX, int T, const int *dState
       HIPCHECK(hipHostMalloc((void **)&sl.h, want, hipHostMallocDefault));
       sl.cap = want;
    }
-   ScoreTask *h = (ScoreTask *)sl.h;
-   int n = 0;
-   for (int ti = 0; ti < nTiles; ti++)
-      for (int ch = 0; ch < nChunks; ch++) {
-         ScoreTask &tk = h[n++];
-         tk.frame0 = ti * FR;
-         tk.nFrames = (T - ti * FR < FR) ? T - ti * FR : FR;
-         tk.slot0 = ch * SL;
-         tk.nSlots = (ns - ch * SL < SL) ? ns - ch * SL : SL;
-         tk.outSlot0 = ch * SL;
-         tk.ldo = ldo;
-         tk.outBase = (size_t)ti * FR;
-      }
+   htkamd_tile_tasks((ScoreTask *)sl.h, 0, T, 0, ns, 0, ldo, FR, SL);
    HIPCHECK(hipMemcpyAsync(sl.d, sl.h, sizeof(ScoreTask) * (size_t)nTasks, hipMemcpyHostToDevice, s));
-   ScoreArgs a;
-   a.tasks = (const ScoreTask *)sl.d; a.nTasks = nTasks; a.X = dX; a.slotState = dStates; a.out = dOut;
-   a.stateCompOff = m->d_stateCompOff; a.compGauss = m->d_compGauss; a.compLogWt = m->d_compLogWt;
-   a.gparam = m->d_gparam; a.PS = m->PS; a.D = m->D; a.minLogExp = m->minLogExp;
-   a.laddTab = m->d_laddTab; a.taskCounter = (int *)(sl.d + sizeof(ScoreTask) * (size_t)nTasks);
-   a.mfmaTab = m->d_mfmaTab; a.stateTileOff = m->d_stateTileOff; a.bf16Tab = m->d_bf16Tab;
    if (mode & HTKAMD_SCORE_DIAGC) { int rcv = htkamd_model_device_tables(m); if (rcv) return rcv; }
-   a.var = m->d_var;
+   ScoreArgs a = htkamd_score_args(m);
+   a.NSt = 1; a.streamWt = nullptr;        // dStates names (state, stream) elements: each is scored as it stands
+   a.tasks = (const ScoreTask *)sl.d; a.nTasks = nTasks; a.X = dX; a.slotState = dStates; a.out = dOut;
+   a.taskCounter = (int *)(sl.d + sizeof(ScoreTask) * (size_t)nTasks);
    const int rc = htkamd_launch_score(mode, m, a, s);
    HIPCHECK(hipEventRecord(sl.ev, s));
    sl.busy = true;

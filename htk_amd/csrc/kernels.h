@@ -2,6 +2,7 @@
 #ifndef HTKAMD_KERNELS_H
 #define HTKAMD_KERNELS_H
 #include <hip/hip_runtime.h>
+#include <vector>
 #include "internal.h"
 
 #define SCORE_TILE_FRAMES 128   /* 64 lanes x 2 frames per lane */
@@ -22,27 +23,27 @@ struct ScoreTask {
 };
 
 struct ScoreArgs {
-   const ScoreTask *tasks;
-   int nTasks;
-   const float *X;
-   const int *slotState;
-   float *out;
-   const int *stateCompOff, *compGauss;
-   const float *compLogWt, *gparam;
-   int PS, D;
-   double minLogExp;
-   const double *laddTab;
-   int *taskCounter;          // dynamic task queue head (zeroed before the launch)
-   const float *mfmaTab;      // MFMA path only
-   const int *stateTileOff;
-   const void *bf16Tab;       // bf16 x 3 path only
+   const ScoreTask *tasks = nullptr;
+   int nTasks = 0;
+   const float *X = nullptr;
+   const int *slotState = nullptr;
+   float *out = nullptr;
+   const int *stateCompOff = nullptr, *compGauss = nullptr;
+   const float *compLogWt = nullptr, *gparam = nullptr;
+   int PS = 0, D = 0;
+   double minLogExp = 0.0;
+   const double *laddTab = nullptr;
+   int *taskCounter = nullptr;          // dynamic task queue head (zeroed before the launch)
+   const float *mfmaTab = nullptr;      // MFMA path only
+   const int *stateTileOff = nullptr;
+   const void *bf16Tab = nullptr;       // bf16 x 3 path only
    const void *f16Tab = nullptr;       // fp16 x 2 path only (set by its launcher): the table, the model's control block
    const int *f16Ctl = nullptr;
    int *rangeFlag = nullptr;           // fp16 x 2 path: where HTKAMD_F16_* bits are raised (NULL: the model's sticky flag)
-   const float *var;          // DIAGC form only: variances [G*D]
+   const float *var = nullptr;          // DIAGC form only: variances [G*D]
    // several streams, HRec's state output probability (cPOutP HRec.c:510-548: outp += w[s] * cSOutP(s), float): a slot names the state's
    // first (state, stream) element, the kernel scores its NSt elements and writes their weighted sum.  NSt <= 1 (what forward-backward
-   // passes, whose rows ARE elements): a slot is scored as it stands.
+   // and htkamd_outp_block pass, whose rows ARE elements): a slot is scored as it stands.
    int NSt = 1;
    const float *streamWt = nullptr;   // [elements]
    // k_score_bf16w: the task list cut into eight queues, one per XCD (tasks of utterance u in queue u % 8, so that the frame tiles of a
@@ -53,6 +54,40 @@ struct ScoreArgs {
    // pass evaluates the chain state (HFB.c:1014, 1177, 1215) -- [2] ints per slot; NULL (block scoring, decoders): every frame of a task
    const int *slotRange = nullptr;
 };
+
+// The model's half of a ScoreArgs, for every scoring mode; the caller adds its own (tasks, nTasks, X, slotState, out, taskCounter, and
+// forward-backward its queues and ranges).  var is the model's d_var as it is now: the DIAGC form calls htkamd_model_device_tables first.
+// Rows are states (NSt streams summed); a caller whose rows are (state, stream) elements sets NSt back to 1.
+static inline ScoreArgs htkamd_score_args(const htkamd_model *m)
+{
+   ScoreArgs a;
+   a.stateCompOff = m->d_stateCompOff; a.compGauss = m->d_compGauss; a.compLogWt = m->d_compLogWt;
+   a.gparam = m->d_gparam; a.PS = m->PS; a.D = m->D; a.minLogExp = m->minLogExp; a.laddTab = m->d_laddTab;
+   a.mfmaTab = m->d_mfmaTab; a.stateTileOff = m->d_stateTileOff; a.bf16Tab = m->d_bf16Tab; a.var = m->d_var;
+   a.NSt = m->NSt; a.streamWt = m->d_streamWt;
+   return a;
+}
+
+// The tasks of a rectangle of T frames (rows frame0.. of X) x nSlots states (entries slot0.. of slotState) whose scores go to the block at
+// out + outBase with leading dimension ldo: tiles of FR frames outermost, chunks of SL states within -- the order the task queue hands
+// them out in.  Writes htkamd_tile_count(..) tasks at tk; the vector form appends.
+static inline int htkamd_tile_count(int T, int nSlots, int FR, int SL) { return ((T + FR - 1) / FR) * ((nSlots + SL - 1) / SL); }
+static inline void htkamd_tile_tasks(ScoreTask *tk, int frame0, int T, int slot0, int nSlots, size_t outBase, int ldo, int FR, int SL)
+{
+   for (int t0 = 0; t0 < T; t0 += FR)
+      for (int k0 = 0; k0 < nSlots; k0 += SL, tk++) {
+         tk->frame0 = frame0 + t0; tk->nFrames = (T - t0 < FR) ? T - t0 : FR;
+         tk->slot0 = slot0 + k0; tk->nSlots = (nSlots - k0 < SL) ? nSlots - k0 : SL;
+         tk->outSlot0 = k0; tk->ldo = ldo; tk->outBase = outBase + (size_t)t0;
+      }
+}
+static inline void htkamd_tile_tasks(std::vector<ScoreTask> &v, int frame0, int T, int slot0, int nSlots, size_t outBase, int ldo, int FR, int SL)
+{
+   if (T <= 0 || nSlots <= 0) return;
+   const size_t n = v.size();
+   v.resize(n + (size_t)htkamd_tile_count(T, nSlots, FR, SL));
+   htkamd_tile_tasks(v.data() + n, frame0, T, slot0, nSlots, outBase, ldo, FR, SL);
+}
 
 // evStart/evStop (may be NULL): updated with the dispatch's own start and stop time (hipExtLaunchKernel), i.e. without the time
 // the kernel waits for the machine when another stream is using it

@@ -21,6 +21,7 @@
 #include "internal.h"
 #include "hipcheck.h"
 #include "kernels.h"
+#include "devbuf.h"
 #include "wavegrp.h"
 
 #define UPB(W) ((W) == 1 ? 4 : 1)   // utterances per workgroup: four single-wave utterances, or one multi-wave utterance
@@ -455,21 +456,8 @@ __global__ void k_viterbi_trace(VitArgs a)
 }
 
 // ------------------------------------------------------------------------------------ host side
-struct VBuf {
-   void *p = nullptr; size_t cap = 0;
-   int reserve(size_t bytes)
-   {
-      if (bytes <= cap) return HTKAMD_OK;
-      if (p) (void)hipFree(p);
-      p = nullptr; cap = 0;
-      const size_t want = bytes + bytes / 8 + 64;
-      hipError_t e = hipMalloc(&p, want);
-      if (e != hipSuccess) { htkamd_set_error("viterbi: hipMalloc(%zu): %s", want, hipGetErrorString(e)); return HTKAMD_ENOMEM; }
-      cap = want;
-      return HTKAMD_OK;
-   }
-   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
+static constexpr char vitOwner[] = "viterbi";
+typedef DevBufT<vitOwner> DevBuf;
 
 struct htkamd_viterbi {
    htkamd_model *m;
@@ -478,9 +466,9 @@ struct htkamd_viterbi {
    std::vector<int> mN, mTp, mSlot0, slotState;
    std::vector<ScoreTask> tasks;
    size_t segTotal, modTotal;
-   VBuf d_uttList;
-   VBuf d_utt, d_mN, d_mTp, d_mSlot0, d_slotState, d_tasks, d_counter, d_outp, d_bp, d_pre, d_exl, d_ent, d_exbp;
-   VBuf d_segStart, d_segEnd, d_segScore, d_modStart, d_modEnd, d_modScore, d_total, d_status;
+   DevBuf d_uttList;
+   DevBuf d_utt, d_mN, d_mTp, d_mSlot0, d_slotState, d_tasks, d_counter, d_outp, d_bp, d_pre, d_exl, d_ent, d_exbp;
+   DevBuf d_segStart, d_segEnd, d_segScore, d_modStart, d_modEnd, d_modScore, d_total, d_status;
 };
 
 extern "C" int htkamd_viterbi_create(htkamd_model *m, htkamd_viterbi **out)
@@ -496,14 +484,14 @@ extern "C" int htkamd_viterbi_create(htkamd_model *m, htkamd_viterbi **out)
 extern "C" void htkamd_viterbi_destroy(htkamd_viterbi *v)
 {
    if (!v) return;
-   VBuf *all[] = {&v->d_uttList, &v->d_utt, &v->d_mN, &v->d_mTp, &v->d_mSlot0, &v->d_slotState, &v->d_tasks, &v->d_counter, &v->d_outp, &v->d_bp,
+   DevBuf *all[] = {&v->d_uttList, &v->d_utt, &v->d_mN, &v->d_mTp, &v->d_mSlot0, &v->d_slotState, &v->d_tasks, &v->d_counter, &v->d_outp, &v->d_bp,
                   &v->d_pre, &v->d_exl, &v->d_ent, &v->d_exbp, &v->d_segStart, &v->d_segEnd, &v->d_segScore, &v->d_modStart,
                   &v->d_modEnd, &v->d_modScore, &v->d_total, &v->d_status};
-   for (VBuf *b : all) b->release();
+   for (DevBuf *b : all) b->release();
    delete v;
 }
 
-template <typename T> static int vupload(VBuf &b, const std::vector<T> &v, hipStream_t s)
+template <typename T> static int vupload(DevBuf &b, const std::vector<T> &v, hipStream_t s)
 {
    int rc = b.reserve(sizeof(T) * (v.size() ? v.size() : 1));
    if (rc) return rc;
@@ -556,14 +544,7 @@ extern "C" int htkamd_viterbi_align_mode(htkamd_viterbi *v, const htkamd_batch_d
          nSlots += N - 2;
       }
       d.nSlots = nSlots;
-      for (int t0 = 0; t0 < T; t0 += SCORE_TILE_FRAMES)
-         for (int k0 = 0; k0 < nSlots; k0 += SCORE_TASK_SLOTS) {
-            ScoreTask tk;
-            tk.frame0 = d.frame0 + t0; tk.nFrames = (T - t0 < SCORE_TILE_FRAMES) ? T - t0 : SCORE_TILE_FRAMES;
-            tk.slot0 = d.slot0 + k0; tk.nSlots = (nSlots - k0 < SCORE_TASK_SLOTS) ? nSlots - k0 : SCORE_TASK_SLOTS;
-            tk.outSlot0 = k0; tk.ldo = T; tk.outBase = d.outp0 + (size_t)t0;
-            v->tasks.push_back(tk);
-         }
+      htkamd_tile_tasks(v->tasks, d.frame0, T, d.slot0, nSlots, d.outp0, T, SCORE_TILE_FRAMES, SCORE_TASK_SLOTS);
       outp += (size_t)T * nSlots; tr += (size_t)T * nSlots; mt += (size_t)(T + 1) * Q; seg += nSlots; mod += Q;
    }
    v->segTotal = seg; v->modTotal = mod;
@@ -585,15 +566,10 @@ extern "C" int htkamd_viterbi_align_mode(htkamd_viterbi *v, const htkamd_batch_d
       return rc;
    if (U == 0) return HTKAMD_OK;
 
-   ScoreArgs sa;
-   sa.tasks = (const ScoreTask *)v->d_tasks.p; sa.nTasks = (int)v->tasks.size(); sa.X = b->dX;
-   sa.slotState = (const int *)v->d_slotState.p; sa.out = (float *)v->d_outp.p;
-   sa.stateCompOff = m->d_stateCompOff; sa.compGauss = m->d_compGauss; sa.compLogWt = m->d_compLogWt;
-   sa.gparam = m->d_gparam; sa.PS = m->PS; sa.D = m->D; sa.minLogExp = m->minLogExp;
-   sa.laddTab = m->d_laddTab; sa.taskCounter = (int *)v->d_counter.p;
    if (scoreMode & HTKAMD_SCORE_DIAGC) { if ((rc = htkamd_model_device_tables((htkamd_model *)m))) return rc; }
-   sa.var = m->d_var;
-   sa.NSt = m->NSt; sa.streamWt = m->d_streamWt;
+   ScoreArgs sa = htkamd_score_args(m);
+   sa.tasks = (const ScoreTask *)v->d_tasks.p; sa.nTasks = (int)v->tasks.size(); sa.X = b->dX;
+   sa.slotState = (const int *)v->d_slotState.p; sa.out = (float *)v->d_outp.p; sa.taskCounter = (int *)v->d_counter.p;
    if (m->tiedMix) {                                      // hsKind TIEDHS: PrecomputeTMix(tmBeam) per frame + SOutP's pool sum (HRec.c:1987, 493-503)
       if ((rc = htkamd_tm_score_block(m, sa, b->frameOff[U], m->tmBeam, s))) return rc;
    } else
