@@ -7,7 +7,7 @@
 // the reference's order, so the output equals HCopy's up to the device's double log()/sqrt() rounding.
 //
 // MI355X mapping: frames are independent, so one wavefront owns one frame (thousands of frames in flight).  The
-// 512-point real FFT is a 256-point complex radix-2 DIT in LDS (2 butterflies per lane and stage, double
+// real FFT of fftN points (8..4096; 512 at 16 kHz / 25 ms) is a complex radix-2 DIT of fftN/2 points in LDS (2 butterflies per lane and stage at 512, double
 // arithmetic, float storage -- as the reference); mel bins and cepstra are sequential float sums in the
 // reference, so a lane owns a bin / a cepstral coefficient and walks its k range in order.  Frame energies and
 // the source mean are 400-term sequential float sums: a lane per FRAME does those in a separate tiny kernel.
@@ -282,7 +282,8 @@ __device__ __forceinline__ void plp_tail(const MfccArgs &a, const float *ac, flo
 // One wavefront per PAIR of frames (round 6).  The spectra take the whole wavefront, one frame after the other; the mel bins and the cepstra
 // are chains of dependent float additions that only numChans (26) and numCeps + 1 (13) lanes can work on -- 40 % of the kernel's vector
 // instructions ran with 26 lanes on -- so the two frames' chains run side by side, frame h in lanes 32 h .. 32 h + 31.
-// PAIR = false (numChans > 32 or numCeps > 31): one frame per wavefront, the bins and cepstra strided over the lanes.
+// PAIR = false (numChans > 32, numCeps > 31, PLP's lpcOrder > 31, or two frames beyond 64 KB of LDS): one frame per wavefront, the bins and
+// cepstra strided over the lanes.
 // KIND (FE_*): what follows the bins.  FBANK / MELSPEC write the bins themselves; PLP takes a lane per auditory-spectrum point, then a
 // lane per autocorrelation lag, then one lane per frame for the two recursions (PAIR: lpcOrder <= 31 as well), its workspace behind fb:
 // as [numChans + 3] | ac [lpcOrder + 1] | lp [lpcOrder + 2] | cc [numCeps + 2] (plpExtra floats; lp and cc 1-based).
@@ -552,9 +553,11 @@ static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int
    // (a grid of persistent wavefronts, 16 or 32 per CU, was tried against one workgroup per pair of frames: 1.93 ms against 1.78 for the
    //  plain grid; the loop stays, the grid covers every pair)
    const int maxGrid = 256 << 20;
-   // two frames per wavefront when a frame's lanes fit in 32: the bins, the cepstra / bins written, PLP's autocorrelation lags
+   // two frames per wavefront when a frame's lanes fit in 32 (the bins, the cepstra / bins written, PLP's autocorrelation lags) and the
+   // two frames' LDS fits in the 64 KB a workgroup gets without asking for more: a 4096-point FFT (frSize 2049..4096) takes 32.9 KB a
+   // frame and goes one frame per wavefront, which computes the same numbers
    const bool pair = c.numChans <= 32 && (f->kind == FE_FBANK || f->kind == FE_MELSPEC || c.numCeps <= 31) &&
-                     (f->kind != FE_PLP || f->lpcOrder <= 31);
+                     (f->kind != FE_PLP || f->lpcOrder <= 31) && 2 * per <= (size_t)64 * 1024;
    switch (f->kind) {
    case FE_MFCC: launch_frames<FE_MFCC>(pair, F, maxGrid, per, s, a); break;
    case FE_FBANK: launch_frames<FE_FBANK>(pair, F, maxGrid, per, s, a); break;

@@ -163,7 +163,7 @@ int htkamd_wave_read(const char *path, int format, short **samples, long *nSampl
             if (type != 1 || chans != 1 || bits != 16 || rate == 0) {
                fclose(f); htkamd_set_error("wave_read: %s: only 16-bit mono PCM is supported (format %u, %u channels, %u bits)", path, type, chans, bits); return HTKAMD_EINVAL;
             }
-            per = (double)(1.0E7f / (float)rate);                   /* w->sampPeriod = 1.0E7 / (float)lng (HWave.c:1107) */
+            per = 1.0E7 / (float)rate;                              /* w->sampPeriod = 1.0E7 / (float)lng (HWave.c:1107): a double division */
             gotFmt = 1; len -= 16;
          }
          len += len & 1u;                                         /* RIFF chunks are padded to an even length */

@@ -150,21 +150,22 @@ int orc_mfcc(const short *wav, int nSamples, const orc_mfcc_cfg *c, float *out)
    int nStat = c->numCeps + (c->hasC0 ? 1 : 0) + (c->hasE ? 1 : 0), nCols = orc_mfcc_cols(c);
    float fres, mlo, mhi, ms, melk, *cf, *loWt, *s, *x, *fbank, *ham, *cepWin, *cc;
    short *loChan;
+   long sampPeriod = (long)c->sampPeriod;   /* InitFBank takes the period as a long (HParm.c:2167): 453.51.. at 22.05 kHz is 453 to it */
    if (T <= 0) return 0;
    /* InitFBank HSigP.c:471-555 */
    while (frSize > fftN) fftN *= 2;
    Nby2 = fftN / 2;
-   fres = 1.0E7 / (c->sampPeriod * fftN * 700.0);
+   fres = 1.0E7 / (sampPeriod * fftN * 700.0);
    klo = 2; khi = Nby2;
    mlo = 0; mhi = mel(Nby2 + 1, fres);
    if (c->loFreq >= 0.0) {
       mlo = 1127 * log(1 + c->loFreq / 700.0);
-      klo = (int)((c->loFreq * c->sampPeriod * 1.0e-7 * fftN) + 2.5);
+      klo = (int)((c->loFreq * sampPeriod * 1.0e-7 * fftN) + 2.5);
       if (klo < 2) klo = 2;
    }
    if (c->hiFreq >= 0.0) {
       mhi = 1127 * log(1 + c->hiFreq / 700.0);
-      khi = (int)((c->hiFreq * c->sampPeriod * 1.0e-7 * fftN) + 0.5);
+      khi = (int)((c->hiFreq * sampPeriod * 1.0e-7 * fftN) + 0.5);
       if (khi > Nby2) khi = Nby2;
    }
    cf = (float *)malloc(sizeof(float) * (maxChan + 2));

@@ -434,8 +434,8 @@ def mfcc_case(rng):
     base = str(rng.choice(["0", "E"]))
     quals = [base] + (["D"] + (["A"] if rng.random() < 0.6 else []) if rng.random() < 0.7 else []) + (["Z"] if rng.random() < 0.3 else [])
     kind = "MFCC_" + "_".join(quals)
-    rate = int(rng.choice([8000, 16000]))
-    kw = dict(sampPeriod=1.0e7 / rate, winDur=float(rng.choice([200000.0, 250000.0, 320000.0])), frPeriod=float(rng.choice([100000.0, 80000.0, 125000.0])),
+    rate = int(rng.choice([8000, 16000, 22050, 48000]))
+    kw = dict(sampPeriod=1.0e7 / rate, winDur=float(rng.choice([200000.0, 250000.0, 320000.0, 400000.0])), frPeriod=float(rng.choice([100000.0, 80000.0, 125000.0])),
               numChans=int(rng.choice([20, 24, 26, 40])), numCeps=int(rng.choice([8, 12, 13])), cepLifter=int(rng.choice([0, 22, 30])),
               preEmph=float(rng.choice([0.0, 0.95, 0.97])), useHam=bool(rng.random() < 0.8), usePower=bool(rng.random() < 0.3),
               zMeanSource=bool(rng.random() < 0.3), rawEnergy=bool(rng.random() < 0.6), eNormalise=bool(rng.random() < 0.6),
