@@ -615,33 +615,69 @@ def frontend_num_cols(cfg: FrontEndConfig) -> int:
     return n
 
 
-class FrontEnd:
-    """htkamd_frontend holder: waveform -> MFCC / FBANK / MELSPEC / PLP feature matrix on the device."""
+class Warp(C.Structure):
+    """htkamd_warp: WARPFREQ, WARPLCUTOFF, WARPUCUTOFF."""
+    _fields_ = [("warpFreq", C.c_float), ("warpLCutoff", C.c_float), ("warpUCutoff", C.c_float)]
 
-    def __init__(self, cfg: FrontEndConfig):
+
+class FrontEnd:
+    """htkamd_frontend holder: waveform -> MFCC / FBANK / MELSPEC / PLP feature matrix on the device.
+    warps: [(WARPFREQ, WARPLCUTOFF, WARPUCUTOFF), ...] (1..64) makes a front end with one filterbank per warp (VTLN): compute codes
+    every utterance with the warp `warp_index` names for it, compute_grid every utterance under every warp."""
+
+    def __init__(self, cfg: FrontEndConfig, warps=None):
         self.cfg = cfg
         self.h = C.c_void_p()
         self.cols = frontend_num_cols(cfg)
-        check(lib().htkamd_frontend_create(C.byref(cfg), C.byref(self.h)), "frontend_create")
+        if warps is None:
+            check(lib().htkamd_frontend_create(C.byref(cfg), C.byref(self.h)), "frontend_create")
+        else:
+            arr = (Warp * max(len(warps), 1))(*[Warp(*w) for w in warps])
+            check(lib().htkamd_frontend_create_warped(C.byref(cfg), arr, C.c_int(len(warps)), C.byref(self.h)), "frontend_create_warped")
+        self.num_warps = lib().htkamd_frontend_num_warps(self.h)
 
-    def compute(self, waves, stream=None):
-        """waves: list of int16 arrays.  Returns (DevArray features [sumT, cols], frameOff)."""
+    def _upload(self, waves, tables=1):
         waves = [np.ascontiguousarray(w, np.int16) for w in waves]
         sampOff = np.concatenate([[0], np.cumsum([len(w) for w in waves])]).astype(np.int32)
         allw = np.concatenate(waves) if waves else np.zeros(0, np.int16)
         frames = [lib().htkamd_frontend_num_frames(C.byref(self.cfg), C.c_int(len(w))) for w in waves]
         total = int(sum(frames))
         dW = DevArray(allw if len(allw) else np.zeros(1, np.int16))
-        dO = DevArray(nbytes=4 * max(total, 1) * self.cols)
-        frameOff = np.zeros(len(waves) + 1, np.int32)
-        check(lib().htkamd_frontend_compute(self.h, dW.ptr, _p(sampOff), C.c_int(len(waves)), _p(frameOff), dO.ptr, _stream(stream)),
-              "frontend_compute")
+        dO = DevArray(nbytes=4 * max(total, 1) * self.cols * tables)
+        return dW, dO, sampOff, np.zeros(len(waves) + 1, np.int32), total
+
+    def compute(self, waves, warp_index=None, stream=None):
+        """waves: list of int16 arrays; warp_index: the warp of every utterance (None: the first, or only, one for all).
+        Returns (DevArray features [sumT, cols], frameOff)."""
+        dW, dO, sampOff, frameOff, total = self._upload(waves)
+        if warp_index is None:
+            check(lib().htkamd_frontend_compute(self.h, dW.ptr, _p(sampOff), C.c_int(len(waves)), _p(frameOff), dO.ptr, _stream(stream)),
+                  "frontend_compute")
+        else:
+            idx = np.ascontiguousarray(warp_index, np.int32)
+            if idx.shape != (len(waves),):
+                raise HtkAmdError("warp_index: one entry per utterance expected")
+            check(lib().htkamd_frontend_compute_warped(self.h, dW.ptr, _p(sampOff), C.c_int(len(waves)), _p(idx), _p(frameOff), dO.ptr,
+                                                       _stream(stream)), "frontend_compute_warped")
         assert frameOff[-1] == total
         return dO, frameOff
 
-    def compute_host(self, waves):
-        dO, frameOff = self.compute(waves)
+    def compute_host(self, waves, warp_index=None):
+        dO, frameOff = self.compute(waves, warp_index)
         return dO.to_host(np.float32, (int(frameOff[-1]), self.cols)), frameOff
+
+    def compute_grid(self, waves, stream=None):
+        """Every utterance under every warp.  Returns (DevArray [num_warps, sumT, cols], frameOff): table w is what compute gives with
+        every utterance on warp w."""
+        dW, dO, sampOff, frameOff, total = self._upload(waves, self.num_warps)
+        check(lib().htkamd_frontend_compute_grid(self.h, dW.ptr, _p(sampOff), C.c_int(len(waves)), _p(frameOff), dO.ptr, _stream(stream)),
+              "frontend_compute_grid")
+        assert frameOff[-1] == total
+        return dO, frameOff
+
+    def compute_grid_host(self, waves):
+        dO, frameOff = self.compute_grid(waves)
+        return dO.to_host(np.float32, (self.num_warps, int(frameOff[-1]), self.cols)), frameOff
 
     def close(self):
         if self.h:

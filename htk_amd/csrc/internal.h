@@ -52,8 +52,9 @@ struct htkamd_mfcc_tables {
    double *rtw;                /* Realft (yr,yi) for i = 2..fftN/4 at [2i],[2i+1] */
    short *brev;                /* [fftN/2] bit-reversed complex index */
    int takeLogs;               /* the bins are logged (MFCC, FBANK), or left linear (MELSPEC, PLP) */
-   float *eql;                 /* PLP: [numChans+1] 1-based equal-loudness curve (InitPLP HSigP.c:663) */
+   float *eql;                 /* PLP: [numChans+1] 1-based equal-loudness curve (InitPLP HSigP.c:663), at the warped centres under a warp */
    double *cm;                 /* PLP: [(lpcOrder+1)*(numChans+2)] IDFT cosines, row = lag, 0-based */
+   float *edge;                /* [numChans+3] mel edges of the filters: melLo, the reference's cf[1..numChans+1] (warped under a warp), the guard */
 };
 int  htkamd_mfcc_tables_build(const htkamd_mfcc_config *c, struct htkamd_mfcc_tables *t);
 void htkamd_mfcc_tables_free(struct htkamd_mfcc_tables *t);
@@ -61,6 +62,11 @@ void htkamd_mfcc_tables_free(struct htkamd_mfcc_tables *t);
    path's tables plus what the base kind needs after the bins; htkamd_frontend_check: the validation alone, 0 or HTKAMD_EINVAL */
 int  htkamd_frontend_check(const htkamd_frontend_config *c);
 int  htkamd_frontend_tables_build(const htkamd_frontend_config *c, struct htkamd_mfcc_tables *t);
+/* VTLN: htkamd_frontend_check plus ValidCodeParms' checks of the warp (HParm.c:1366-1372) and the triples on which WarpFreq
+   (HSigP.c:449) divides by zero or stops increasing; the tables with the filters' edges warped (InitFBank HSigP.c:513-526): loWt, the
+   bins' k ranges and PLP's eql follow from them, every other table is the un-warped one.  warp NULL, or warpFreq 1.0: no warping */
+int  htkamd_frontend_warp_check(const htkamd_frontend_config *c, const htkamd_warp *w);
+int  htkamd_frontend_tables_build_warped(const htkamd_frontend_config *c, const htkamd_warp *w, struct htkamd_mfcc_tables *t);
 
 /* ---- packed model ---- */
 struct htkamd_model {

@@ -17,6 +17,12 @@
 // logged bins, MELSPEC the linear ones, PLP turns the linear bins into cepstra through an all-pole model (FBank2ASpec, MatrixIDFT,
 // Durbin, LPC2Cepstrum: HSigP.c:693-750).  k_mfcc_frames takes the kind as a template parameter; its MFCC instantiation is the
 // MFCC kernel as it was.
+//
+// Frequency warping (VTLN: WARPFREQ / WARPLCUTOFF / WARPUCUTOFF, htkamd_frontend_create_warped): a warp moves the filters' edges and with
+// them loWt, the bins' k ranges and PLP's equal-loudness curve -- nothing before the bins -- so a handle holds one such table set per warp.
+// A call whose utterances all take one warp runs the kernels above on that set.  k_mfcc_frames_warp is the sibling for the other two
+// cases: utterances of different warps in one call (each frame reads the set of its utterance), and the warp GRID, every frame under every
+// warp: window, FFT and magnitudes once, the magnitudes kept in LDS, then per warp the two terms of every k, the bins and the kind's tail.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include <cstring>
@@ -92,6 +98,8 @@ __global__ void k_mfcc_energy(MfccArgs a)
 // One frame's spectrum by a whole wavefront: window, FFT, Realft, magnitudes -- and (round 6) what every k hands its two mel bins:
 //   uk[k] = ek - loWt[k] ek  (to the bin above, HSigP.c:594)   vk[k] = loWt[k] ek  (to its own bin, :593)
 // computed by all lanes in parallel, so that the bins' sums below are nothing but the reference's chain of float additions.
+// MAGS (the warp grid): the magnitudes alone, into vk[k]; the two terms follow per warp (mfcc_warp_terms).
+template <bool MAGS = false>
 __device__ __forceinline__ void mfcc_spectrum(const MfccArgs &a, const int f, float *xs, float *uk, float *vk, const int lane)
 {
    const int fftN = a.fftN, nn = fftN / 2;
@@ -196,10 +204,22 @@ __device__ __forceinline__ void mfcc_spectrum(const MfccArgs &a, const int f, fl
       const float t1 = xs[2 * k - 2], t2 = xs[2 * k - 1];
       const float p = t1 * t1 + t2 * t2;
       const float e = a.usePower ? p : (float)sqrt((double)p);
+      if constexpr (MAGS) vk[k] = e;
+      else {
+      const float tw = a.loWt[k] * e;
+      uk[k] = e - tw; vk[k] = tw;
+      }
+   }
+   __syncthreads();
+}
+// the two terms of every k (HSigP.c:593-594) of one warp from the magnitudes mfcc_spectrum<true> left: the same two float operations
+__device__ __forceinline__ void mfcc_warp_terms(const MfccArgs &a, const float *mag, float *uk, float *vk, const int lane)
+{
+   for (int k = a.klo + lane; k <= a.khi; k += 64) {
+      const float e = mag[k];
       const float tw = a.loWt[k] * e;
       uk[k] = e - tw; vk[k] = tw;
    }
-   __syncthreads();
 }
 
 // mel bin b of one frame, linear (HSigP.c:591-594 in the reference's accumulation order), and logged with floor 1.0 (:598-603)
@@ -357,6 +377,139 @@ __global__ __launch_bounds__(64) void k_mfcc_frames(MfccArgs a)
    }
 }
 
+// ---- frequency warping: one table set (loWt, the bins' four k ranges, PLP's eql) per warp, the sets back to back
+struct WarpArgs {
+   const float *loWt, *eql;      // [nWarp x loStride], [nWarp x eqlStride]
+   const int *bins;              // [nWarp x 4 (numChans + 2)]
+   int loStride, eqlStride;
+   const int *frameUtt, *uttWarp;        // per-utterance warps: utterance of a frame, set of an utterance
+   int nWarp;                    // the grid: sets 0 .. nWarp - 1, table s at out + s * tableStride
+   size_t tableStride;
+};
+__device__ __forceinline__ MfccArgs mfcc_warp_set(const MfccArgs &a, const WarpArgs &w, const int s)
+{
+   MfccArgs r = a;
+   const int nb = a.numChans + 2;
+   r.loWt = w.loWt + (size_t)s * w.loStride;
+   r.eql = w.eql ? w.eql + (size_t)s * w.eqlStride : nullptr;
+   r.binA0 = w.bins + (size_t)s * 4 * nb; r.binA1 = r.binA0 + nb; r.binB0 = r.binA1 + nb; r.binB1 = r.binB0 + nb;
+   return r;
+}
+
+// What follows the spectra of the frames f0 .. f0 + NF - 1 of a workgroup in k_mfcc_frames_warp: the bins, the kind's tail, the rows written,
+// statement for statement what k_mfcc_frames does there (PAIR, KIND and the layout of a frame's LDS are described with it; that kernel keeps its
+// own text, so that warping leaves its code as it was).  In the PAIR layout `a` may differ between the two halves of the wavefront: each half's
+// table set and output table.  VKX (the warp grid): the terms vk sit at the head of the frame's LDS, where xs was, behind them the magnitudes.
+template <bool PAIR, int KIND, bool VKX = false>
+__device__ __forceinline__ void mfcc_frames_tail(const MfccArgs &a, const int f0, float *lds, const int per, const int lane)
+{
+   const int fftN = a.fftN, nn = fftN / 2;
+   if constexpr (PAIR) {
+      const int h = lane >> 5, q = lane & 31, f = f0 + h;
+      float *base = lds + h * per, *fb = base + fftN + 2 * (nn + 2);
+      const float *uk = base + fftN, *vk = VKX ? base : base + fftN + nn + 2;
+      if constexpr (KIND == FE_MFCC) {
+      if (f < a.nFrames && q < a.numChans) fb[q + 1] = mfcc_bin(a, q + 1, uk, vk);
+      __syncthreads();
+      if (f < a.nFrames) {
+         float *row = a.out + (size_t)f * a.nCols;
+         if (q < a.numCeps) row[q] = mfcc_cep(a, q + 1, fb);
+         else if (a.hasC0 && q == 31) row[a.numCeps] = mfcc_c0(a, fb);
+      }
+      } else if constexpr (KIND == FE_FBANK || KIND == FE_MELSPEC) {
+         if (f < a.nFrames && q < a.numChans)
+            a.out[(size_t)f * a.nCols + q] = (KIND == FE_FBANK) ? mfcc_bin(a, q + 1, uk, vk)
+                                                                : mfcc_bin_lin(a, q + 1, uk, vk);
+      } else {
+         float *as = fb + a.numChans + 2, *ac = as + a.numChans + 3, *lp = ac + a.lpcOrder + 1, *cc = lp + a.lpcOrder + 2;
+         if (f < a.nFrames && q < a.numChans) plp_aspec(a, q + 1, mfcc_bin_lin(a, q + 1, uk, vk), as);
+         __syncthreads();
+         if (f < a.nFrames && q <= a.lpcOrder) ac[q] = plp_autocorr(a, q, as);
+         __syncthreads();
+         if (f < a.nFrames && q == 0) plp_tail(a, ac, lp, cc);
+         __syncthreads();
+         if (f < a.nFrames) {
+            float *row = a.out + (size_t)f * a.nCols;
+            if (q < a.numCeps) row[q] = (cc[q + 1] * a.cepWin[q + 1]) * a.cepScale;
+            else if (a.hasC0 && q == 31) row[a.numCeps] = cc[a.numCeps + 1] * a.cepScale;
+         }
+      }
+   } else {
+      float *fb = lds + fftN + 2 * (nn + 2);
+      const float *uk = lds + fftN, *vk = VKX ? lds : lds + fftN + nn + 2;
+      if constexpr (KIND == FE_MFCC) {
+      for (int b = 1 + lane; b <= a.numChans; b += 64) fb[b] = mfcc_bin(a, b, uk, vk);
+      __syncthreads();
+      float *row = a.out + (size_t)f0 * a.nCols;
+      for (int j = 1 + lane; j <= a.numCeps; j += 64) row[j - 1] = mfcc_cep(a, j, fb);
+      if (a.hasC0 && lane == 63) row[a.numCeps] = mfcc_c0(a, fb);
+      } else if constexpr (KIND == FE_FBANK || KIND == FE_MELSPEC) {
+         float *row = a.out + (size_t)f0 * a.nCols;
+         for (int b = 1 + lane; b <= a.numChans; b += 64)
+            row[b - 1] = (KIND == FE_FBANK) ? mfcc_bin(a, b, uk, vk) : mfcc_bin_lin(a, b, uk, vk);
+      } else {
+         float *as = fb + a.numChans + 2, *ac = as + a.numChans + 3, *lp = ac + a.lpcOrder + 1, *cc = lp + a.lpcOrder + 2;
+         for (int b = 1 + lane; b <= a.numChans; b += 64) plp_aspec(a, b, mfcc_bin_lin(a, b, uk, vk), as);
+         __syncthreads();
+         for (int i = lane; i <= a.lpcOrder; i += 64) ac[i] = plp_autocorr(a, i, as);
+         __syncthreads();
+         if (lane == 0) plp_tail(a, ac, lp, cc);
+         __syncthreads();
+         float *row = a.out + (size_t)f0 * a.nCols;
+         for (int j = 1 + lane; j <= a.numCeps; j += 64) row[j - 1] = (cc[j] * a.cepWin[j]) * a.cepScale;
+         if (a.hasC0 && lane == 63) row[a.numCeps] = cc[a.numCeps + 1] * a.cepScale;
+      }
+   }
+}
+
+// The sibling of k_mfcc_frames for a call with more than one warp (k_mfcc_frames itself is untouched by warping: a call on one warp runs
+// it on that warp's set).  Layouts, LDS per frame and every float operation are k_mfcc_frames'.
+// GRID = false: every frame under the warp of its utterance.  A spectrum takes the whole wavefront, so its set is uniform; in the PAIR
+//   layout the two halves then walk the bins' ranges (and eql) of their own frame's set, which may be two different ones.
+// GRID = true: every frame under every warp.  The spectrum once, its magnitudes into the vk region; xs is dead from there on, so per warp
+//   the terms go to uk and to xs' place (the magnitudes stay), then the bins, the tail and the row of table s.  The energy column, written
+//   by k_mfcc_energy into table 0 before this kernel, is copied to the other tables.
+template <bool PAIR, int KIND, bool GRID>
+__global__ __launch_bounds__(64) void k_mfcc_frames_warp(MfccArgs a, WarpArgs w)
+{
+   extern __shared__ float lds[];
+   const int lane = threadIdx.x;
+   const int fftN = a.fftN, nn = fftN / 2;
+   constexpr int NF = PAIR ? 2 : 1;
+   const int per = (fftN + 2 * (nn + 2) + a.numChans + 2 + (KIND == FE_PLP ? a.plpExtra : 0) + 3) & ~3;
+   for (int blk = blockIdx.x; NF * blk < a.nFrames; blk += gridDim.x) {
+   const int f0 = NF * blk;
+   if constexpr (!GRID) {
+      for (int h = 0; h < NF; h++)
+         if (f0 + h < a.nFrames)
+            mfcc_spectrum(mfcc_warp_set(a, w, w.uttWarp[w.frameUtt[f0 + h]]), f0 + h, lds + h * per, lds + h * per + fftN, lds + h * per + fftN + nn + 2, lane);
+      const int fl = PAIR ? min(f0 + (lane >> 5), a.nFrames - 1) : f0;       // (a last half without a frame writes nothing: any set)
+      mfcc_frames_tail<PAIR, KIND>(mfcc_warp_set(a, w, w.uttWarp[w.frameUtt[fl]]), f0, lds, per, lane);
+   } else {
+      for (int h = 0; h < NF; h++)
+         if (f0 + h < a.nFrames) mfcc_spectrum<true>(a, f0 + h, lds + h * per, lds + h * per + fftN, lds + h * per + fftN + nn + 2, lane);
+      for (int s = 0; s < w.nWarp; s++) {
+         MfccArgs as = mfcc_warp_set(a, w, s);
+         as.out = a.out + (size_t)s * w.tableStride;
+         for (int h = 0; h < NF; h++)
+            if (f0 + h < a.nFrames) mfcc_warp_terms(as, lds + h * per + fftN + nn + 2, lds + h * per + fftN, lds + h * per, lane);
+         __syncthreads();
+         mfcc_frames_tail<PAIR, KIND, true>(as, f0, lds, per, lane);
+         __syncthreads();                                // (the next warp's terms and bins overwrite what this one's tail read)
+      }
+      if (a.hasE) {
+         const int f = PAIR ? f0 + (lane >> 5) : f0, q = PAIR ? (lane & 31) : lane;
+         if (f < a.nFrames) {
+            const size_t at = (size_t)f * a.nCols + a.nStat - 1;
+            const float e = a.out[at];
+            for (int s = 1 + q; s < w.nWarp; s += (PAIR ? 32 : 64)) a.out[(size_t)s * w.tableStride + at] = e;
+         }
+      }
+   }
+   __syncthreads();                                      // (the next frames' spectra overwrite what the cepstra read)
+   }
+}
+
 // NormaliseLogEnergy (HSigP.c:911-932): one block per utterance
 __global__ void k_mfcc_enorm(float *out, const int *frameOff, int nCols, int col, float silFloor, float eScale)
 {
@@ -436,6 +589,9 @@ struct htkamd_mfcc {
    float compressFact;
    float *d_eql;
    double *d_cm;
+   int nWarp;                            // table sets: d_loWt [nWarp x (fftN/2 + 2)], d_bins [nWarp x 4 (numChans + 2)], d_eql [nWarp x (numChans + 1)]
+   int *d_uttWarp, *d_gridOff, *d_gridUtt;       // per-utterance warps; the grid's nWarp tables as nWarp * nUtt utterances: frame offsets, utterance of a frame
+   size_t capUttWarp, capGridUtt, capGridFrames;
 };
 struct htkamd_frontend { htkamd_mfcc m; };       // the same holder behind the general entry points
 
@@ -447,22 +603,35 @@ template <typename T> static int up(T **d, const T *h, size_t n)
 }
 
 // tables of front end `fc` (validated by htkamd_frontend_tables_build on the host) onto the device
-static int fe_create(const htkamd_frontend_config *fc, htkamd_mfcc *f)
+// warps NULL: the un-warped front end (one table set)
+static int fe_create(const htkamd_frontend_config *fc, htkamd_mfcc *f, const htkamd_warp *warps = nullptr, int nWarp = 1)
 {
    const htkamd_mfcc_config *cfg = &fc->base;
-   f->cfg = *cfg; f->kind = fc->baseKind; f->lpcOrder = fc->lpcOrder; f->compressFact = fc->compressFact;
-   int rc = htkamd_frontend_tables_build(fc, &f->tab);
+   f->cfg = *cfg; f->kind = fc->baseKind; f->lpcOrder = fc->lpcOrder; f->compressFact = fc->compressFact; f->nWarp = nWarp;
+   int rc = htkamd_frontend_tables_build_warped(fc, warps, &f->tab);
    if (rc) return rc;
    const htkamd_mfcc_tables &t = f->tab;
    const int nn = t.fftN / 2;
    const int nCep = (f->kind == FE_MFCC || f->kind == FE_PLP) ? cfg->numCeps : 0, nDct = (f->kind == FE_MFCC) ? cfg->numCeps : 0;
+   // what a warp changes, set after set (set 0 is f->tab's)
+   const size_t nLo = (size_t)nn + 2, nBins = (size_t)4 * (cfg->numChans + 2), nEql = (f->kind == FE_PLP) ? (size_t)cfg->numChans + 1 : 0;
+   std::vector<float> loWt(t.loWt, t.loWt + nLo), eql;
+   std::vector<int> bins(t.binA0, t.binA0 + nBins);
+   if (nEql) eql.assign(t.eql, t.eql + nEql);
+   for (int w = 1; w < nWarp; w++) {
+      htkamd_mfcc_tables tw;
+      if ((rc = htkamd_frontend_tables_build_warped(fc, warps + w, &tw)) != HTKAMD_OK) return rc;
+      loWt.insert(loWt.end(), tw.loWt, tw.loWt + nLo); bins.insert(bins.end(), tw.binA0, tw.binA0 + nBins);
+      if (nEql) eql.insert(eql.end(), tw.eql, tw.eql + nEql);
+      htkamd_mfcc_tables_free(&tw);
+   }
    if ((rc = up(&f->d_ham, t.ham, (size_t)t.frSize + 1)) || (rc = up(&f->d_cepWin, t.cepWin, (size_t)nCep + 1)) ||
-       (rc = up(&f->d_loWt, t.loWt, (size_t)nn + 2)) || (rc = up(&f->d_bins, t.binA0, (size_t)4 * (cfg->numChans + 2))) ||
+       (rc = up(&f->d_loWt, loWt.data(), loWt.size())) || (rc = up(&f->d_bins, bins.data(), bins.size())) ||
        (rc = up(&f->d_dct, t.dct, (size_t)(nDct + 1) * (cfg->numChans + 1))) || (rc = up(&f->d_tw, t.tw, (size_t)2 * nn)) ||
        (rc = up(&f->d_rtw, t.rtw, (size_t)2 * (nn / 2 + 2))) || (rc = up(&f->d_brev, t.brev, (size_t)nn)))
       return rc;
    if (f->kind == FE_PLP &&
-       ((rc = up(&f->d_eql, t.eql, (size_t)cfg->numChans + 1)) || (rc = up(&f->d_cm, t.cm, (size_t)(fc->lpcOrder + 1) * (cfg->numChans + 2)))))
+       ((rc = up(&f->d_eql, eql.data(), eql.size())) || (rc = up(&f->d_cm, t.cm, (size_t)(fc->lpcOrder + 1) * (cfg->numChans + 2)))))
       return rc;
    return HTKAMD_OK;
 }
@@ -486,6 +655,7 @@ static void fe_release(htkamd_mfcc *f)
    (void)hipFree(f->d_ham); (void)hipFree(f->d_cepWin); (void)hipFree(f->d_loWt); (void)hipFree(f->d_bins); (void)hipFree(f->d_dct);
    (void)hipFree(f->d_tw); (void)hipFree(f->d_rtw); (void)hipFree(f->d_brev); (void)hipFree(f->d_frameSamp); (void)hipFree(f->d_frameMean);
    (void)hipFree(f->d_frameOff); (void)hipFree(f->d_frameUtt); (void)hipFree(f->d_eql); (void)hipFree(f->d_cm);
+   (void)hipFree(f->d_uttWarp); (void)hipFree(f->d_gridOff); (void)hipFree(f->d_gridUtt);
    htkamd_mfcc_tables_free(&f->tab);
 }
 
@@ -502,7 +672,30 @@ template <int KIND> static void launch_frames(bool pair, int F, int maxGrid, siz
    else hipLaunchKernelGGL((k_mfcc_frames<false, KIND>), dim3(std::min(F, maxGrid)), dim3(64), per, s, a);
 }
 
-static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream)
+template <int KIND> static void launch_frames_warp(bool grid, bool pair, int F, int maxGrid, size_t per, hipStream_t s, const MfccArgs &a, const WarpArgs &w)
+{
+   const dim3 blocks(std::min(pair ? (F + 1) / 2 : F, maxGrid));
+   const size_t lds = pair ? 2 * per : per;
+   if (grid) {
+      if (pair) hipLaunchKernelGGL((k_mfcc_frames_warp<true, KIND, true>), blocks, dim3(64), lds, s, a, w);
+      else hipLaunchKernelGGL((k_mfcc_frames_warp<false, KIND, true>), blocks, dim3(64), lds, s, a, w);
+   } else {
+      if (pair) hipLaunchKernelGGL((k_mfcc_frames_warp<true, KIND, false>), blocks, dim3(64), lds, s, a, w);
+      else hipLaunchKernelGGL((k_mfcc_frames_warp<false, KIND, false>), blocks, dim3(64), lds, s, a, w);
+   }
+}
+
+// the grid's tables, one behind the other, as nWarp * nUtt utterances: utterance of every frame of the tables 1 .. nWarp - 1 and of table 0
+__global__ void k_mfcc_grid_index(const int *frameUtt, int nFrames, int nUtt, int nWarp, int *gridUtt)
+{
+   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+   if (g >= (size_t)nFrames * nWarp) return;
+   gridUtt[g] = (int)(g / nFrames) * nUtt + frameUtt[g % nFrames];
+}
+
+// uttWarp: the table set of every utterance (NULL: set 0 for all); grid: every utterance under every set, nWarp tables behind one another
+static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream,
+                      const int *uttWarp = nullptr, bool grid = false)
 {
    hipStream_t s = (hipStream_t)stream;
    const htkamd_mfcc_config &c = f->cfg;
@@ -513,6 +706,16 @@ static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int
    for (int u = 0; u < nUtt; u++) frameOff[u + 1] = frameOff[u] + htkamd_mfcc_num_frames(&c, sampOff[u + 1] - sampOff[u]);
    const int F = frameOff[nUtt];
    if (F == 0) return HTKAMD_OK;
+   // one set for the whole call (no warps, NULL, or the same entry throughout): the plain kernels on that set
+   int set = 0;
+   bool mixed = false;
+   if (uttWarp && !grid) {
+      set = uttWarp[0];
+      for (int u = 1; u < nUtt; u++) if (uttWarp[u] != set) mixed = true;
+      if (mixed) set = 0;                                // (the kernel picks every frame's set from the first one on)
+   }
+   if (grid && f->nWarp == 1) grid = false;
+   if (grid && (size_t)F * f->nWarp > (size_t)0x7fffffff) { htkamd_set_error("frontend_compute_grid: %d frames x %d warps exceed 2^31 - 1 rows", F, f->nWarp); return HTKAMD_EINVAL; }
    if ((size_t)F > f->capFrames) {
       (void)hipFree(f->d_frameSamp); (void)hipFree(f->d_frameMean); (void)hipFree(f->d_frameUtt);
       f->d_frameSamp = nullptr; f->d_frameMean = nullptr; f->d_frameUtt = nullptr;
@@ -542,7 +745,12 @@ static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int
    a.ham = f->d_ham; a.cepWin = f->d_cepWin; a.loWt = f->d_loWt;
    a.binA0 = f->d_bins; a.binA1 = f->d_bins + (c.numChans + 2); a.binB0 = a.binA1 + (c.numChans + 2); a.binB1 = a.binB0 + (c.numChans + 2);
    a.dct = f->d_dct; a.tw = f->d_tw; a.rtw = f->d_rtw; a.brev = f->d_brev; a.frameMean = f->d_frameMean; a.out = dOut;
-   a.eql = f->d_eql; a.cm = f->d_cm; a.lpcOrder = f->lpcOrder; a.compressFact = f->compressFact;
+   if (set > 0) {
+      a.loWt += (size_t)set * (t.fftN / 2 + 2);
+      a.binA0 += (size_t)set * 4 * (c.numChans + 2); a.binA1 += (size_t)set * 4 * (c.numChans + 2);
+      a.binB0 += (size_t)set * 4 * (c.numChans + 2); a.binB1 += (size_t)set * 4 * (c.numChans + 2);
+   }
+   a.eql = (f->d_eql && set > 0) ? f->d_eql + (size_t)set * (c.numChans + 1) : f->d_eql; a.cm = f->d_cm; a.lpcOrder = f->lpcOrder; a.compressFact = f->compressFact;
    a.plpExtra = (f->kind == FE_PLP) ? (c.numChans + 3) + (f->lpcOrder + 1) + (f->lpcOrder + 2) + (c.numCeps + 2) : 0;
 
    if (c.hasE || c.zMeanSource) {
@@ -558,6 +766,49 @@ static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int
    // frame and goes one frame per wavefront, which computes the same numbers
    const bool pair = c.numChans <= 32 && (f->kind == FE_FBANK || f->kind == FE_MELSPEC || c.numCeps <= 31) &&
                      (f->kind != FE_PLP || f->lpcOrder <= 31) && 2 * per <= (size_t)64 * 1024;
+   // what follows the frame kernel works per utterance: the grid's nWarp tables are nWarp * nUtt utterances of nWarp * F frames
+   const int *dOff = f->d_frameOff, *dUtt = f->d_frameUtt;
+   int nU = nUtt, nF = F;
+   if (mixed || grid) {
+      WarpArgs w;
+      w.loWt = f->d_loWt; w.eql = f->d_eql; w.bins = f->d_bins; w.loStride = t.fftN / 2 + 2; w.eqlStride = c.numChans + 1;
+      w.frameUtt = f->d_frameUtt; w.uttWarp = nullptr; w.nWarp = f->nWarp; w.tableStride = (size_t)F * nCols;
+      if (mixed) {
+         if ((size_t)nUtt > f->capUttWarp) {
+            (void)hipFree(f->d_uttWarp); f->d_uttWarp = nullptr; f->capUttWarp = 0;
+            HIPCHECK(hipMalloc((void **)&f->d_uttWarp, sizeof(int) * (size_t)nUtt));
+            f->capUttWarp = (size_t)nUtt;
+         }
+         HIPCHECK(hipMemcpy(f->d_uttWarp, uttWarp, sizeof(int) * (size_t)nUtt, hipMemcpyHostToDevice));      // (small, and the caller's: over when it returns)
+         w.uttWarp = f->d_uttWarp;
+      } else {
+         nU = nUtt * f->nWarp; nF = F * f->nWarp;
+         if ((size_t)nU + 1 > f->capGridUtt) {
+            (void)hipFree(f->d_gridOff); f->d_gridOff = nullptr; f->capGridUtt = 0;
+            HIPCHECK(hipMalloc((void **)&f->d_gridOff, sizeof(int) * ((size_t)nU + 1)));
+            f->capGridUtt = (size_t)nU + 1;
+         }
+         if ((size_t)nF > f->capGridFrames) {
+            (void)hipFree(f->d_gridUtt); f->d_gridUtt = nullptr; f->capGridFrames = 0;
+            HIPCHECK(hipMalloc((void **)&f->d_gridUtt, sizeof(int) * (size_t)nF));
+            f->capGridFrames = (size_t)nF;
+         }
+         std::vector<int> gridOff((size_t)nU + 1);
+         for (int k = 0; k < f->nWarp; k++)
+            for (int u = 0; u < nUtt; u++) gridOff[(size_t)k * nUtt + u] = k * F + frameOff[u];
+         gridOff[nU] = nF;
+         HIPCHECK(hipMemcpy(f->d_gridOff, gridOff.data(), sizeof(int) * gridOff.size(), hipMemcpyHostToDevice));
+         hipLaunchKernelGGL(k_mfcc_grid_index, dim3((unsigned)(((size_t)nF + 255) / 256)), dim3(256), 0, s, f->d_frameUtt, F, nUtt, f->nWarp, f->d_gridUtt);
+         HIPCHECK(hipGetLastError());
+         dOff = f->d_gridOff; dUtt = f->d_gridUtt;
+      }
+      switch (f->kind) {
+      case FE_MFCC: launch_frames_warp<FE_MFCC>(grid, pair, F, maxGrid, per, s, a, w); break;
+      case FE_FBANK: launch_frames_warp<FE_FBANK>(grid, pair, F, maxGrid, per, s, a, w); break;
+      case FE_MELSPEC: launch_frames_warp<FE_MELSPEC>(grid, pair, F, maxGrid, per, s, a, w); break;
+      default: launch_frames_warp<FE_PLP>(grid, pair, F, maxGrid, per, s, a, w); break;
+      }
+   } else
    switch (f->kind) {
    case FE_MFCC: launch_frames<FE_MFCC>(pair, F, maxGrid, per, s, a); break;
    case FE_FBANK: launch_frames<FE_FBANK>(pair, F, maxGrid, per, s, a); break;
@@ -566,21 +817,21 @@ static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int
    }
    HIPCHECK(hipGetLastError());
    if (c.hasE && c.eNormalise) {
-      hipLaunchKernelGGL(k_mfcc_enorm, dim3(nUtt), dim3(256), 0, s, dOut, f->d_frameOff, nCols, nStat - 1, c.silFloor, c.eScale);
+      hipLaunchKernelGGL(k_mfcc_enorm, dim3(nU), dim3(256), 0, s, dOut, dOff, nCols, nStat - 1, c.silFloor, c.eScale);
       HIPCHECK(hipGetLastError());
    }
    if (c.hasD) {
-      const size_t n = (size_t)F * nStat;
-      hipLaunchKernelGGL(k_mfcc_delta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dOut, f->d_frameUtt, f->d_frameOff, F, nCols, 0, nStat, nStat, c.delWin);
+      const size_t n = (size_t)nF * nStat;
+      hipLaunchKernelGGL(k_mfcc_delta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dOut, dUtt, dOff, nF, nCols, 0, nStat, nStat, c.delWin);
       HIPCHECK(hipGetLastError());
       if (c.hasA) {
-         hipLaunchKernelGGL(k_mfcc_delta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dOut, f->d_frameUtt, f->d_frameOff, F, nCols, nStat, 2 * nStat, nStat, c.accWin);
+         hipLaunchKernelGGL(k_mfcc_delta, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dOut, dUtt, dOff, nF, nCols, nStat, 2 * nStat, nStat, c.accWin);
          HIPCHECK(hipGetLastError());
       }
    }
    if (c.hasZ) {
       const int d = nBase + (c.hasC0 ? 1 : 0);                                  // HParm.c:1712-1715
-      hipLaunchKernelGGL(k_mfcc_zmean, dim3((nUtt * d + 63) / 64), dim3(64), 0, s, dOut, f->d_frameOff, nUtt, nCols, d);
+      hipLaunchKernelGGL(k_mfcc_zmean, dim3((nU * d + 63) / 64), dim3(64), 0, s, dOut, dOff, nU, nCols, d);
       HIPCHECK(hipGetLastError());
    }
    HIPCHECK(hipStreamSynchronize(s));           // (sampOff / frameOff are the caller's: the copies above must be over when the call returns)
@@ -631,6 +882,40 @@ extern "C" int htkamd_frontend_compute(htkamd_frontend *f, const short *dWav, co
 {
    if (!f || !sampOff || !frameOff || nUtt < 0 || (nUtt > 0 && (!dWav || !dOut))) { htkamd_set_error("frontend_compute: bad argument"); return HTKAMD_EINVAL; }
    return fe_compute(&f->m, dWav, sampOff, nUtt, frameOff, dOut, stream);
+}
+
+// ------------------------------------------------------------------------------------ frequency warping (VTLN)
+extern "C" int htkamd_frontend_create_warped(const htkamd_frontend_config *cfg, const htkamd_warp *warps, int nWarp, htkamd_frontend **out)
+{
+   if (!cfg || !warps || !out) { htkamd_set_error("frontend_create_warped: NULL argument"); return HTKAMD_EINVAL; }
+   if (nWarp < 1 || nWarp > 64) { htkamd_set_error("frontend_create_warped: %d warps (1..64)", nWarp); return HTKAMD_EINVAL; }
+   int rc;
+   for (int w = 0; w < nWarp; w++)                       // (refusals come before the device is touched)
+      if ((rc = htkamd_frontend_warp_check(cfg, warps + w)) != HTKAMD_OK) return rc;
+   if (htkamd_device_count() <= 0) { htkamd_set_error("frontend_create_warped: no HIP device"); return HTKAMD_ENODEV; }
+   htkamd_frontend *f = (htkamd_frontend *)calloc(1, sizeof(htkamd_frontend));
+   if ((rc = fe_create(cfg, &f->m, warps, nWarp)) != HTKAMD_OK) { htkamd_frontend_destroy(f); return rc; }
+   *out = f;
+   return HTKAMD_OK;
+}
+
+extern "C" int htkamd_frontend_num_warps(const htkamd_frontend *f) { return f ? f->m.nWarp : 0; }
+
+extern "C" int htkamd_frontend_compute_warped(htkamd_frontend *f, const short *dWav, const int *sampOff, int nUtt, const int *uttWarp,
+                                              int *frameOff, float *dOut, void *stream)
+{
+   if (!f || !sampOff || !frameOff || nUtt < 0 || (nUtt > 0 && (!dWav || !dOut))) { htkamd_set_error("frontend_compute_warped: bad argument"); return HTKAMD_EINVAL; }
+   for (int u = 0; uttWarp && u < nUtt; u++)
+      if (uttWarp[u] < 0 || uttWarp[u] >= f->m.nWarp) {
+         htkamd_set_error("frontend_compute_warped: utterance %d asks for warp %d of %d", u, uttWarp[u], f->m.nWarp); return HTKAMD_EINVAL;
+      }
+   return fe_compute(&f->m, dWav, sampOff, nUtt, frameOff, dOut, stream, nUtt > 0 ? uttWarp : nullptr, false);
+}
+
+extern "C" int htkamd_frontend_compute_grid(htkamd_frontend *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream)
+{
+   if (!f || !sampOff || !frameOff || nUtt < 0 || (nUtt > 0 && (!dWav || !dOut))) { htkamd_set_error("frontend_compute_grid: bad argument"); return HTKAMD_EINVAL; }
+   return fe_compute(&f->m, dWav, sampOff, nUtt, frameOff, dOut, stream, nullptr, true);
 }
 
 // ------------------------------------------------------------------------------------ qualifiers on a parameterised table

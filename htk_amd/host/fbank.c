@@ -8,6 +8,7 @@
  *   DCT cosines           FBank2MFCC HSigP.c:607-621 (cos(x*(k-0.5)) per term, double)
  *   FFT twiddles          the double-precision recurrences of FFT HSigP.c:332-349 and Realft :371-386, tabulated
  *   PLP                   InitPLP HSigP.c:663-690: equal-loudness curve at the filters' centres, IDFT cosine matrix
+ *   VTLN                  WarpFreq HSigP.c:449-468 on the filters' centres (InitFBank :513-526), ValidCodeParms HParm.c:1366-1383
  * and the validation of the other FFT front ends (FBANK, MELSPEC, PLP: ValidCodeParms HParm.c:1317-1365).
  */
 #include <math.h>
@@ -54,7 +55,7 @@ int htkamd_mfcc_num_cols(const htkamd_mfcc_config *c)
 void htkamd_mfcc_tables_free(struct htkamd_mfcc_tables *t)
 {
    free(t->ham); free(t->cepWin); free(t->loWt); free(t->binA0); free(t->dct); free(t->tw); free(t->rtw); free(t->brev);
-   free(t->eql); free(t->cm);
+   free(t->eql); free(t->cm); free(t->edge);
    memset(t, 0, sizeof(*t));
 }
 
@@ -109,6 +110,102 @@ int htkamd_frontend_check(const htkamd_frontend_config *f)
    return check_geometry(c, f->baseKind);
 }
 
+/* FFT size, band of interest (FFT bins klo..khi, mel range melLo..melHi, optionally narrowed by LOFREQ / HIFREQ): InitFBank HSigP.c:485-504 */
+static void fbank_band(const htkamd_mfcc_config *c, int *fftNOut, float *fresOut, int *kloOut, int *khiOut, float *melLoOut, float *melHiOut)
+{
+   const int frSize = (int)(c->winDur / c->sampPeriod);
+   int fftN = 2, half, klo, khi;
+   float fres, melLo, melHi;
+   while (frSize > fftN) fftN *= 2;
+   half = fftN / 2;
+   fres = 1.0E7 / ((long)c->sampPeriod * fftN * 700.0);
+   klo = 2; khi = half;
+   melLo = 0; melHi = bin_mel(half + 1, fres);
+   if (c->loFreq >= 0.0) {
+      melLo = hz_mel(c->loFreq);
+      klo = (int)((c->loFreq * (long)c->sampPeriod * 1.0e-7 * fftN) + 2.5);
+      if (klo < 2) klo = 2;
+   }
+   if (c->hiFreq >= 0.0) {
+      melHi = hz_mel(c->hiFreq);
+      khi = (int)((c->hiFreq * (long)c->sampPeriod * 1.0e-7 * fftN) + 0.5);
+      if (khi > half) khi = half;
+   }
+   *fftNOut = fftN; *fresOut = fres; *kloOut = klo; *khiOut = khi; *melLoOut = melLo; *melHiOut = melHi;
+}
+
+/* the band's ends in Hz as InitFBank forms them for WarpFreq (HSigP.c:518-519): exp in double, stored as float */
+static float mel_hz(float mel) { return 700.0 * (exp(mel / 1127.0) - 1.0); }
+
+/* WarpFreq HSigP.c:449-468, every step in float as there: piecewise linear, slope 1/alpha between the two corner frequencies cl and cu,
+   the pieces below and above them bent so that minFreq and maxFreq stay where they are */
+static float warp_freq(float fcl, float fcu, float freq, float minFreq, float maxFreq, float alpha)
+{
+   if (alpha == 1.0)
+      return freq;
+   else {
+      float scale = 1.0 / alpha;
+      float cu = fcu * 2 / (1 + scale);
+      float cl = fcl * 2 / (1 + scale);
+      float au = (maxFreq - cu * scale) / (maxFreq - cu);
+      float al = (cl * scale - minFreq) / (cl - minFreq);
+      if (freq > cu) return au * (freq - cu) + scale * cu;
+      else if (freq < cl) return al * (freq - minFreq) + minFreq;
+      else return scale * freq;
+   }
+}
+
+/* ValidCodeParms' own checks of a warp (HParm.c:1366-1372): they need no front-end configuration */
+int htkamd_warp_check(const htkamd_warp *w)
+{
+   if (!w) { htkamd_set_error("frontend: NULL warp"); return HTKAMD_EINVAL; }
+   if (!(w->warpFreq >= 0.5f && w->warpFreq <= 2.0f)) {
+      htkamd_set_error("frontend: unlikely warping factor WARPFREQ %g (0.5..2.0)", (double)w->warpFreq); return HTKAMD_EINVAL;
+   }
+   if (w->warpFreq != 1.0 && (w->warpLCutoff == 0.0 || w->warpUCutoff == 0.0 || !(w->warpLCutoff <= w->warpUCutoff))) {
+      htkamd_set_error("frontend: invalid warping cut-off frequencies WARPLCUTOFF %g WARPUCUTOFF %g (both set, lower <= upper)",
+                       (double)w->warpLCutoff, (double)w->warpUCutoff);
+      return HTKAMD_EINVAL;
+   }
+   return HTKAMD_OK;
+}
+
+int htkamd_frontend_warp_check(const htkamd_frontend_config *f, const htkamd_warp *w)
+{
+   int rc, fftN, klo, khi;
+   float fres, melLo, melHi;
+   if ((rc = htkamd_warp_check(w)) != HTKAMD_OK || (rc = htkamd_frontend_check(f)) != HTKAMD_OK) return rc;
+   if (w->warpFreq == 1.0) return HTKAMD_OK;
+   /* what the reference leaves unchecked: WarpFreq's two outer pieces divide by cl - minFreq and maxFreq - cu, and the map only
+      increases while both pieces keep a positive slope */
+   fbank_band(&f->base, &fftN, &fres, &klo, &khi, &melLo, &melHi);
+   {
+      const float minFreq = mel_hz(melLo), maxFreq = mel_hz(melHi);
+      const float scale = 1.0 / w->warpFreq, cu = w->warpUCutoff * 2 / (1 + scale), cl = w->warpLCutoff * 2 / (1 + scale);
+      if (!(cl > minFreq)) {
+         htkamd_set_error("frontend: WARPLCUTOFF %g: the lower corner %g Hz does not lie above the band's lower end %g Hz",
+                          (double)w->warpLCutoff, (double)cl, (double)minFreq);
+         return HTKAMD_EINVAL;
+      }
+      if (!(cu < maxFreq)) {
+         htkamd_set_error("frontend: WARPUCUTOFF %g: the upper corner %g Hz does not lie below the band's upper end %g Hz",
+                          (double)w->warpUCutoff, (double)cu, (double)maxFreq);
+         return HTKAMD_EINVAL;
+      }
+      if (!(scale * cu < maxFreq)) {
+         htkamd_set_error("frontend: WARPFREQ %g maps the upper corner %g Hz to %g Hz, at or beyond the band's upper end %g Hz",
+                          (double)w->warpFreq, (double)cu, (double)(scale * cu), (double)maxFreq);
+         return HTKAMD_EINVAL;
+      }
+      if (!(scale * cl > minFreq)) {
+         htkamd_set_error("frontend: WARPFREQ %g maps the lower corner %g Hz to %g Hz, at or below the band's lower end %g Hz",
+                          (double)w->warpFreq, (double)cl, (double)(scale * cl), (double)minFreq);
+         return HTKAMD_EINVAL;
+      }
+   }
+   return HTKAMD_OK;
+}
+
 int htkamd_mfcc_tables_build(const htkamd_mfcc_config *c, struct htkamd_mfcc_tables *t)
 {
    htkamd_frontend_config f;
@@ -119,38 +216,41 @@ int htkamd_mfcc_tables_build(const htkamd_mfcc_config *c, struct htkamd_mfcc_tab
 
 int htkamd_frontend_tables_build(const htkamd_frontend_config *fc, struct htkamd_mfcc_tables *t)
 {
+   return htkamd_frontend_tables_build_warped(fc, NULL, t);
+}
+
+/* warp NULL: no warping (the reference's alpha == 1.0 branch) */
+int htkamd_frontend_tables_build_warped(const htkamd_frontend_config *fc, const htkamd_warp *warp, struct htkamd_mfcc_tables *t)
+{
    const htkamd_mfcc_config *c = &fc->base;
    /* cepstra (and the lifter) for MFCC and PLP, the DCT for MFCC alone; the filterbank kinds ignore NUMCEPS */
    const int nCep = (fc->baseKind == 6 || fc->baseKind == 11) ? c->numCeps : 0, nDct = (fc->baseKind == 6) ? c->numCeps : 0;
-   int fftN = 2, half, nEdge, k, i, j, b, rc;
+   int fftN, half, nEdge, k, i, j, b, rc;
    float fres, melLo, melHi, *edge;
    memset(t, 0, sizeof(*t));
-   if ((rc = htkamd_frontend_check(fc)) != HTKAMD_OK) return rc;
+   if ((rc = warp ? htkamd_frontend_warp_check(fc, warp) : htkamd_frontend_check(fc)) != HTKAMD_OK) return rc;
    t->frSize = (int)(c->winDur / c->sampPeriod);
    t->frRate = (int)(c->frPeriod / c->sampPeriod);
    t->takeLogs = fc->baseKind == 6 || fc->baseKind == 7;
-   while (t->frSize > fftN) fftN *= 2;
+   /* ---- mel filterbank (InitFBank HSigP.c:471-555 supplies the numbers; the tables are this file's own form). */
+   fbank_band(c, &fftN, &fres, &t->klo, &t->khi, &melLo, &melHi);
    t->fftN = fftN; half = fftN / 2;
-   /* ---- mel filterbank (InitFBank HSigP.c:471-555 supplies the numbers; the tables are this file's own form).
-      Band of interest: FFT bins klo..khi, mel range melLo..melHi, optionally narrowed by LOFREQ / HIFREQ. */
-   fres = 1.0E7 / ((long)c->sampPeriod * fftN * 700.0);
-   t->klo = 2; t->khi = half;
-   melLo = 0; melHi = bin_mel(half + 1, fres);
-   if (c->loFreq >= 0.0) {
-      melLo = hz_mel(c->loFreq);
-      t->klo = (int)((c->loFreq * (long)c->sampPeriod * 1.0e-7 * fftN) + 2.5);
-      if (t->klo < 2) t->klo = 2;
-   }
-   if (c->hiFreq >= 0.0) {
-      melHi = hz_mel(c->hiFreq);
-      t->khi = (int)((c->hiFreq * (long)c->sampPeriod * 1.0e-7 * fftN) + 0.5);
-      if (t->khi > half) t->khi = half;
-   }
-   /* numChans triangular filters share numChans+2 equally spaced mel edges: edge[0] = melLo, edge[e] = e/(numChans+1) of the span */
+   /* numChans triangular filters share numChans+2 equally spaced mel edges: edge[0] = melLo, edge[e] = e/(numChans+1) of the span.
+      Under a warp (VTLN) every edge goes back to Hz, through WarpFreq and back to mel, in the reference's types at every step
+      (HSigP.c:516-525); the band's ends stay, the last edge up to rounding */
    nEdge = c->numChans + 1;
-   edge = (float *)malloc(sizeof(float) * (size_t)(nEdge + 2));
+   edge = t->edge = (float *)malloc(sizeof(float) * (size_t)(nEdge + 2));
    edge[0] = melLo;
-   for (b = 1; b <= nEdge; b++) edge[b] = ((float)b / (float)nEdge) * (melHi - melLo) + melLo;
+   if (!warp || warp->warpFreq == 1.0)
+      for (b = 1; b <= nEdge; b++) edge[b] = ((float)b / (float)nEdge) * (melHi - melLo) + melLo;
+   else {
+      const float ms = melHi - melLo, minFreq = mel_hz(melLo), maxFreq = mel_hz(melHi);
+      for (b = 1; b <= nEdge; b++) {
+         float cf = ((float)b / (float)nEdge) * ms + melLo;
+         cf = 700 * (exp(cf / 1127.0) - 1.0);
+         edge[b] = 1127.0 * log(1.0 + warp_freq(warp->warpLCutoff, warp->warpUCutoff, cf, minFreq, maxFreq, warp->warpFreq) / 700.0);
+      }
+   }
    edge[nEdge + 1] = edge[nEdge] + 1.0f;                /* guard: a top bin whose centre rounds above HIFREQ feeds no filter */
    /* An FFT bin k between edge[lo] and edge[lo+1] feeds filter lo with weight loWt[k] = (edge[lo+1] - mel)/(edge[lo+1] - edge[lo]) and
       filter lo+1 with the rest (Wave2FBank HSigP.c:558-604 adds loWt*ek to bin lo and ek - loWt*ek to bin lo+1, for k ascending).
@@ -193,7 +293,6 @@ int htkamd_frontend_tables_build(const htkamd_frontend_config *fc, struct htkamd
          row[nFreq - 1] = cos(angle * (double)i * (double)(nFreq - 1));
       }
    }
-   free(edge);
    t->ham = (float *)calloc((size_t)t->frSize + 1, sizeof(float));
    { const float a = HTK_TPI / (t->frSize - 1); for (i = 1; i <= t->frSize; i++) t->ham[i] = 0.54 - 0.46 * cos(a * (i - 1)); }
    t->cepWin = (float *)calloc((size_t)nCep + 1, sizeof(float));

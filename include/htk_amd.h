@@ -897,6 +897,32 @@ int  htkamd_frontend_num_frames(const htkamd_frontend_config *cfg, int nSamples)
 int  htkamd_frontend_num_cols(const htkamd_frontend_config *cfg);      /* < 0 and the error string set on a refused config */
 int  htkamd_frontend_compute(htkamd_frontend *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Vocal-tract-length normalisation (VTLN): the mel filterbank's frequency axis warped per speaker, HParm's WARPFREQ, WARPLCUTOFF and
+ * WARPUCUTOFF (HParm.c:249-251; InitFBank HSigP.c:513-526 warps the filters' centres through WarpFreq :449-468).  A front end is
+ * created with 1..64 warps; the window, FFT and magnitudes are the un-warped ones, the filter weights (and PLP's equal-loudness
+ * curve, taken at the warped centres) are one table set per warp.
+ *   htkamd_frontend_compute_warped : utterance u is coded with warps[uttWarp[u]] (uttWarp NULL: all with warps[0]); an entry outside
+ *                                    0..nWarp-1 is HTKAMD_EINVAL.  htkamd_frontend_compute on such a handle codes with warps[0].
+ *   htkamd_frontend_compute_grid   : every utterance under every warp, each frame transformed once and binned nWarp times: dOut holds
+ *                                    nWarp tables of [F x nCols], table w at dOut + w*F*nCols, each bit-equal to what
+ *                                    htkamd_frontend_compute_warped gives with every utterance on warp w (the grid search of VTLN
+ *                                    warp estimation; frameOff [nUtt+1] describes every table).
+ * warpFreq 1.0 is the un-warped front end whatever the cut-offs.  Refused (HTKAMD_EINVAL and the reason, before any device is
+ * touched): nWarp outside 1..64; warpFreq outside 0.5..2.0; for warpFreq != 1 a cut-off equal to 0 or warpLCutoff > warpUCutoff
+ * (ValidCodeParms HParm.c:1366-1372); and what the reference leaves unchecked but what makes WarpFreq divide by zero or stop
+ * increasing: with scale = 1/warpFreq and the corners cl, cu = cut-off * 2 / (1 + scale), cl <= minFreq, cu >= maxFreq,
+ * scale*cu >= maxFreq or scale*cl <= minFreq (minFreq, maxFreq: the band's ends, LOFREQ / HIFREQ or 0 / half the sample rate).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct { float warpFreq, warpLCutoff, warpUCutoff; } htkamd_warp;      /* WARPFREQ WARPLCUTOFF WARPUCUTOFF */
+int  htkamd_frontend_create_warped(const htkamd_frontend_config *cfg, const htkamd_warp *warps, int nWarp /*1..64*/, htkamd_frontend **out);
+int  htkamd_frontend_num_warps(const htkamd_frontend *f);      /* 1 for a handle made by htkamd_frontend_create */
+int  htkamd_warp_check(const htkamd_warp *w);                  /* ValidCodeParms' checks alone (no configuration, no device): 0, or HTKAMD_EINVAL and the reason */
+int  htkamd_frontend_compute_warped(htkamd_frontend *f, const short *dWav, const int *sampOff, int nUtt, const int *uttWarp,
+                                    int *frameOff, float *dOut, void *stream);
+int  htkamd_frontend_compute_grid(htkamd_frontend *f, const short *dWav, const int *sampOff, int nUtt,
+                                  int *frameOff, float *dOut, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,15 +132,33 @@ static void check_waveform_kind(int targetKind)
       DIE("waveform sources are coded as MFCC, FBANK, MELSPEC or PLP: TARGETKIND = <kind>[_0][_E][_D][_A][_T][_Z][_N] expected");
 }
 
+/* WARPFREQ / WARPLCUTOFF / WARPUCUTOFF of a waveform source */
+static htkamd_warp waveform_warp(const config *cfg)
+{
+   htkamd_warp w;
+   w.warpFreq = (float)cfg_flt(cfg, "WARPFREQ", 1.0); w.warpLCutoff = (float)cfg_flt(cfg, "WARPLCUTOFF", 0.0); w.warpUCutoff = (float)cfg_flt(cfg, "WARPUCUTOFF", 0.0);
+   return w;
+}
+/* what the library refuses of them whatever the files' rate (htkamd_warp_check: ValidCodeParms HParm.c:1366-1372); the drivers call this
+   before they touch a device.  What depends on the band the library refuses when the front end is made (code_waveforms) */
+static void check_waveform_warp(const config *cfg)
+{
+   const htkamd_warp w = waveform_warp(cfg);
+   if (htkamd_warp_check(&w)) DIE("waveform sources: %s", htkamd_last_error());
+}
+
 /* Waveform sources (SOURCEFORMAT = WAV, or SOURCEKIND = WAVEFORM with HTK waveform files): the files of the batch are coded on the
    device as OpenBuffer does for a waveform file (htkamd_frontend_compute: statics + _0 / _E of TARGETKIND's base kind -- MFCC, FBANK,
-   MELSPEC or PLP -- with HParm's configuration variables and their defaults, HParm.c:337-367); the differentials, _Z and _N of
-   TARGETKIND follow in load_observations as for parameter files.  Returns the parameter kind of the table (base kind + _0 / _E). */
+   MELSPEC or PLP -- with HParm's configuration variables and their defaults, HParm.c:337-367; WARPFREQ, WARPLCUTOFF and WARPUCUTOFF
+   among them: a one-warp front end, refused with the library's reason on a triple that ValidCodeParms or WarpFreq cannot take); the
+   differentials, _Z and _N of TARGETKIND follow in load_observations as for parameter files.  Returns the parameter kind of the table
+   (base kind + _0 / _E). */
 static int code_waveforms(const strlist *files, int first, int count, int targetKind, const config *cfg, obs_batch *ob, float **dStatOut, int *nStatOut)
 {
    const char *sfmt = cfg_get(cfg, "SOURCEFORMAT");
    const int fmt = (sfmt && !strcasecmp(sfmt, "WAV")) ? HTKAMD_WAVE_WAV : HTKAMD_WAVE_HTK;
    check_waveform_kind(targetKind);
+   check_waveform_warp(cfg);
    const int base = targetKind & 077;
    short *all = NULL; size_t cap = 0;
    int *sampOff = (int *)calloc((size_t)count + 1, sizeof(int));
@@ -168,7 +186,9 @@ static int code_waveforms(const strlist *files, int first, int count, int target
    m->delWin = 2; m->accWin = 2;
    const int cols = htkamd_frontend_num_cols(&fc);
    if (cols < 0) DIE("waveform sources: %s", htkamd_last_error());
-   htkamd_frontend *fe; CHECK(htkamd_frontend_create(&fc, &fe));
+   const htkamd_warp warp = waveform_warp(cfg);
+   htkamd_frontend *fe;
+   { const int rc = htkamd_frontend_create_warped(&fc, &warp, 1, &fe); if (rc == HTKAMD_EINVAL) DIE("waveform sources: %s", htkamd_last_error()); CHECK(rc); }
    int F = 0;
    for (int u = 0; u < count; u++) F += htkamd_frontend_num_frames(&fc, sampOff[u + 1] - sampOff[u]);
    short *dWav; float *dStat;

@@ -5,7 +5,8 @@
  * Options (the subset of HTKBook ref.tex "HERest" that SURVEY.md 8(b) lists; same letters, same meaning, same defaults, HERest.c:292-500):
  *   -C cf          configuration file (TARGETKIND, DELTAWINDOW, ACCWINDOW, THIRDWINDOW, V1COMPAT, SIMPLEDIFFS)
  *                  with SOURCEFORMAT = WAV (or SOURCEKIND = WAVEFORM) the files are waveforms, coded on the device as TARGETKIND's
- *                  MFCC, FBANK, MELSPEC or PLP (NUMCHANS, NUMCEPS, LPCORDER, COMPRESSFACT, ...); the LPC kinds are refused
+ *                  MFCC, FBANK, MELSPEC or PLP (NUMCHANS, NUMCEPS, LPCORDER, COMPRESSFACT, ...); the LPC kinds are refused;
+ *                  WARPFREQ, WARPLCUTOFF and WARPUCUTOFF warp the filterbank's frequency axis (VTLN), as HCopy does
  *   -S scp         script file: further data files (extended file names logical=physical[s,e] are accepted, the segment is ignored)
  *   -H mmf         load a master macro file (repeatable)          -d dir / -x ext   directory / extension of single-model files
  *   -M dir         directory for the re-estimated models          -B                save them in binary
@@ -151,6 +152,7 @@ int main(int argc, char **argv)
    if (nIter > 1 && parMode >= 0) DIE("herest: --iterations goes with the single-process form (or --ranks), not with -p");
 
    if (waveform_source(&cfg) && cfg_get(&cfg, "TARGETKIND")) check_waveform_kind(kind_parse(cfg_get(&cfg, "TARGETKIND")));
+   if (waveform_source(&cfg)) check_waveform_warp(&cfg);
    if (htkamd_device_count() <= 0) DIE("herest: no HIP device (the MI355X path has no CPU fallback)");
    CHECK(htkamd_set_device(nRanks > 1 ? rank % htkamd_device_count() : 0));
 

@@ -6,7 +6,8 @@
  * Options (the subset of HTKBook ref.tex "HVite" that SURVEY.md 8(b) lists; same letters, meaning and defaults, HVite.c:227-420):
  *   -C cf        configuration file (TARGETKIND, DELTAWINDOW, ACCWINDOW, THIRDWINDOW, V1COMPAT, SIMPLEDIFFS)
  *                with SOURCEFORMAT = WAV (or SOURCEKIND = WAVEFORM) the files are waveforms, coded on the device as TARGETKIND's
- *                MFCC, FBANK, MELSPEC or PLP (NUMCHANS, NUMCEPS, LPCORDER, COMPRESSFACT, ...); the LPC kinds are refused
+ *                MFCC, FBANK, MELSPEC or PLP (NUMCHANS, NUMCEPS, LPCORDER, COMPRESSFACT, ...); the LPC kinds are refused;
+ *                WARPFREQ, WARPLCUTOFF and WARPUCUTOFF warp the filterbank's frequency axis (VTLN), as HCopy does
  *   -S scp       script file with further data files            -H mmf / -d dir / -x ext   model sources
  *   -w net       recognition network (SLF word lattice)         -a            align against the label files instead
  *   -b word      alignment: boundary word at both ends          -L dir / -X ext / -I mlf   transcriptions to align (default .lab)
@@ -210,6 +211,7 @@ int main(int argc, char **argv)
    if (nToks > 1 && align) DIE("hvite: alignment using multiple tokens is not supported");       /* HVite.c:448 (-m / -f with -n: as the reference built with -DPHNALG, alignment records inside the lattice arcs) */
    if (latExt && nToks < 2) DIE("hvite -z: lattices need -n i with i > 1");
    if (waveform_source(&cfg) && cfg_get(&cfg, "TARGETKIND")) check_waveform_kind(kind_parse(cfg_get(&cfg, "TARGETKIND")));
+   if (waveform_source(&cfg)) check_waveform_warp(&cfg);
    if (htkamd_device_count() <= 0) DIE("hvite: no HIP device (the MI355X path has no CPU fallback)");
 
    htkamd_mmf *mmf; CHECK(htkamd_mmf_create(&mmf));
