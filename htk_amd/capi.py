@@ -828,6 +828,89 @@ def parm_qualify(stat_list, quals: ParmQuals):
     return dOut, frameOff, cols
 
 
+def mask_match(mask: str, name: str):
+    """htkamd_mask_match (MaskMatch): the characters the mask's % capture from `name`, or None when it does not match."""
+    out = C.create_string_buffer(1024)
+    rc = lib().htkamd_mask_match(mask.encode(), name.encode(), out, C.c_int(len(out)))
+    if rc < 0:
+        check(rc, "mask_match")
+    return out.value.decode() if rc == 1 else None
+
+
+def parm_kind_parse(kind: str) -> int:
+    return lib().htkamd_parm_kind_parse(kind.encode())
+
+
+def parm_kind_str(kind: int) -> str:
+    buf = C.create_string_buffer(64)
+    check(lib().htkamd_parm_kind_str(C.c_int(kind), buf, C.c_int(len(buf))), "parm_kind_str")
+    return buf.value.decode()
+
+
+def cepsnorm_read(path: str, max_dim: int = 4096) -> dict:
+    """A <CEPSNORM> side file -> {"kind": code, "nFrames": n or None, "mean": float32 [dim] or None, "var": float32 [dim] or None}."""
+    kind = C.c_int(); nf = C.c_int(); dm = C.c_int(); dv = C.c_int()
+    mean = np.zeros(max_dim, np.float32); var = np.zeros(max_dim, np.float32)
+    check(lib().htkamd_cepsnorm_read(path.encode(), C.byref(kind), C.byref(nf), _p(mean), C.byref(dm), _p(var), C.byref(dv), C.c_int(max_dim)), "cepsnorm_read")
+    return {"kind": kind.value, "nFrames": nf.value if nf.value >= 0 else None,
+            "mean": mean[:dm.value].copy() if dm.value else None, "var": var[:dv.value].copy() if dv.value else None}
+
+
+def cepsnorm_write(path: str, kind: int, flags: str, nFrames: int = 0, mean=None, var=None):
+    """htkamd_cepsnorm_write (ExportNMV): flags = HCompV's -q subsets m, v, mv, nv, nmv."""
+    mean = None if mean is None else np.ascontiguousarray(mean, np.float32)
+    var = None if var is None else np.ascontiguousarray(var, np.float32)
+    dim = len(mean) if mean is not None else (len(var) if var is not None else 0)
+    check(lib().htkamd_cepsnorm_write(path.encode(), C.c_int(kind), flags.encode(), C.c_int(nFrames), _p(mean), _p(var), C.c_int(dim)), "cepsnorm_write")
+
+
+def varscale_read(path: str, max_dim: int = 4096) -> np.ndarray:
+    v = np.zeros(max_dim, np.float32); dim = C.c_int()
+    check(lib().htkamd_varscale_read(path.encode(), _p(v), C.byref(dim), C.c_int(max_dim)), "varscale_read")
+    return v[:dim.value].copy()
+
+
+def cepsnorm_check_kinds(targetKind: int, meanKind: int = -1, varKind: int = -1):
+    check(lib().htkamd_cepsnorm_check_kinds(C.c_int(targetKind), C.c_int(meanKind), C.c_int(varKind)), "cepsnorm_check_kinds")
+
+
+def cepsnorm_scale(varScale, sideVar, sideNames=None) -> np.ndarray:
+    """htkamd_cepsnorm_scale: float32 [nSide, dim] = (float)sqrt(varScale / sideVar), the quotient a float as in the reference."""
+    vs = np.ascontiguousarray(varScale, np.float32)
+    sv = np.ascontiguousarray(np.atleast_2d(sideVar), np.float32)
+    out = np.zeros(sv.shape, np.float32)
+    names = None if sideNames is None else (C.c_char_p * len(sideNames))(*[n.encode() for n in sideNames])
+    check(lib().htkamd_cepsnorm_scale(_p(vs), C.c_int(len(vs)), _p(sv), C.c_int(sv.shape[1]), C.c_int(sv.shape[0]), names, _p(out)), "cepsnorm_scale")
+    return out
+
+
+def side_stats(dX_ptr, frameOff, uttSide, nSide: int, nCols: int, D: int, stream=None):
+    """htkamd_side_stats: per side the fp64 sums and sums of squares [nSide, D] of the first D columns, and the frame counts [nSide]."""
+    frameOff = np.ascontiguousarray(frameOff, np.int32); uttSide = np.ascontiguousarray(uttSide, np.int32)
+    s = np.zeros((nSide, D), np.float64); q = np.zeros((nSide, D), np.float64); n = np.zeros(nSide, np.int64)
+    check(lib().htkamd_side_stats(dX_ptr, _p(frameOff), _p(uttSide), C.c_int(len(uttSide)), C.c_int(nSide), C.c_int(nCols), C.c_int(D),
+                                  _p(s), _p(q), _p(n), _stream(stream)), "side_stats")
+    return s, q, n
+
+
+def side_stats_finish(s, q, n):
+    """htkamd_side_stats_finish: (mean, var) float32 [nSide, D] from the sums."""
+    s = np.ascontiguousarray(s, np.float64); q = np.ascontiguousarray(q, np.float64); n = np.ascontiguousarray(n, np.int64)
+    mean = np.zeros(s.shape, np.float32); var = np.zeros(s.shape, np.float32)
+    check(lib().htkamd_side_stats_finish(_p(s), _p(q), _p(n), C.c_int(s.shape[0]), C.c_int(s.shape[1]), _p(mean), _p(var)), "side_stats_finish")
+    return mean, var
+
+
+def parm_normalise(dX_ptr, frameOff, uttSide, nSide: int, nCols: int, mean=None, scale=None, stream=None):
+    """htkamd_parm_normalise, in place on the device table: row - mean[side] (float32 [nSide, dMean]), then row * scale[side]."""
+    frameOff = np.ascontiguousarray(frameOff, np.int32); uttSide = np.ascontiguousarray(uttSide, np.int32)
+    mean = None if mean is None else np.ascontiguousarray(np.atleast_2d(mean), np.float32)
+    scale = None if scale is None else np.ascontiguousarray(np.atleast_2d(scale), np.float32)
+    check(lib().htkamd_parm_normalise(dX_ptr, _p(frameOff), _p(uttSide), C.c_int(len(uttSide)), C.c_int(nSide), C.c_int(nCols),
+                                      _p(mean), C.c_int(0 if mean is None else mean.shape[1]), _p(scale), C.c_int(0 if scale is None else scale.shape[1]),
+                                      _stream(stream)), "parm_normalise")
+
+
 class ParmStream:
     """htkamd_parm_stream holder: the qualifier step in HParm's buffer mode (rows in pushes, observations out with qwin rows of delay)."""
 

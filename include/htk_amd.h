@@ -923,6 +923,65 @@ int  htkamd_frontend_compute_warped(htkamd_frontend *f, const short *dWav, const
 int  htkamd_frontend_compute_grid(htkamd_frontend *f, const short *dWav, const int *sampOff, int nUtt,
                                   int *frameOff, float *dOut, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Side-based cepstral mean and variance normalisation: HParm's CMEANDIR / CMEANMASK / CMEANPATHMASK and VARSCALEDIR / VARSCALEMASK /
+ * VARSCALEPATHMASK / VARSCALEFN (HParm.c:859-866), and what `HCompV -c dir -k mask [-p mask] -q nmv` estimates (HCompV.c:520-740).
+ * A "side" is a speaker or conversation side: the characters a mask's % capture from a file's name.  The host functions look for no
+ * device; every refusal is HTKAMD_EINVAL (HTKAMD_EIO: a file that cannot be opened or written) with the reason in htkamd_last_error.
+ *
+ *   htkamd_mask_match          the behaviour of MaskMatch (HShell.c:1851): % captures one character, ? matches one, * any run.  Returns 1 and the
+ *                              captured characters in out, 0 (out empty) when the name does not match, HTKAMD_EINVAL when the mask
+ *                              captures outLen characters or more.
+ *   htkamd_parm_kind_parse     Str2ParmKind (HParm.c:1109): "MFCC_E_D_A" -> base code + qualifier bits; -1 for an unknown name.
+ *   htkamd_parm_kind_str       ParmKind2Str (HParm.c:1092), qualifiers in the reference's order.
+ *   htkamd_cepsnorm_read       a `<CEPSNORM> <KIND>` side file as LoadCMeanVector / LoadVarScaleVector read it (HParm.c:3172-3349): skips to
+ *                              `<MEAN> n` / `<VARIANCE> n` and reads n floats into mean / var (each may be NULL: not wanted; at most
+ *                              maxDim values each).  *dimMean / *dimVar = 0 for a vector the file does not hold, *nFrames = -1 without
+ *                              <NFRAMES>.
+ *   htkamd_cepsnorm_write      ExportNMV (HCompV.c:686-740): " %e" per value; flags = HCompV's -q subsets "m" "v" "mv" "nv" "nmv".
+ *   htkamd_varscale_read       the global `<VARSCALE> n ...` file of VARSCALEFN (LoadVarScale HParm.c:560-615).
+ *   htkamd_cepsnorm_check_kinds  a mean file's kind equals the target kind once the target's _D _A _T _Z _V bits are masked out of both
+ *                              (HParm.c:3221-3224); a variance file's kind equals the target kind, or lacks only its _V (:3298).
+ *                              meanKind / varKind -1: no such file.
+ *   htkamd_cepsnorm_scale      scale[side][i] = (float)sqrt(varScale[i] / sideVar[side][i]): a float quotient, the double sqrt, stored as
+ *                              a float (HParm.c:1624, :1806).  dScale != dVar is refused (:1797-1800), and so is a side variance that is
+ *                              not positive, with the side's name (sideNames may be NULL: its index).
+ *   htkamd_side_stats_finish   UpdateMeanVar (HCompV.c:640-656) from the fp64 sums: mean = sum/N, var = sqsum/N - mean^2, formed in fp64
+ *                              and rounded once; a side without frames keeps zeros.
+ *
+ * On the device (csrc/cepsnorm.hip; HTKAMD_ENODEV without one, after the arguments were checked):
+ *   htkamd_side_stats          AccGenUtt / UpdateSpkrAccList (HCompV.c:520-636): per side and column the sum, the sum of squares and the
+ *                              frame count over the first D columns of the table dX [frameOff[nUtt] x nCols]; utterance u belongs to
+ *                              side uttSide[u].  frameOff, uttSide and the results are host arrays (sum, sqsum: [nSide x D]).  The
+ *                              reference sums floats in file order; this sums in fp64 in a fixed order (per-utterance partial sums,
+ *                              then the utterances of a side in utterance order, no atomics): the same bits on every call.
+ *   htkamd_parm_normalise      the tail of AddQualifiers, in place: row - mean[side] over the first dMean columns (HParm.c:1728-1741), then
+ *                              row * scale[side] over the first dScale columns (:1804-1812): two separately rounded float operations.
+ *                              mean [nSide x dMean] and scale [nSide x dScale] are host tables; either may be NULL.
+ *   An uttSide entry outside 0..nSide-1 is HTKAMD_EINVAL before anything is launched.
+ * Order of calls for TARGETKIND = <kind>_Z with side means: htkamd_parm_qualify with nZeroMean = 0 (the reference skips FZeroMean when
+ * it has a side mean, HParm.c:1709-1741), then htkamd_parm_normalise.  Without _Z in the target the mean is not applied at all
+ * (HParm.c:4375); variance scaling needs no _Z.  With _N in the target the reference applies the side vectors while the energy column
+ * is still in the row (it leaves when an observation is extracted, HParm.c:2882): a caller with _N normalises a table qualified without
+ * nullECol and drops the column itself; the command-line drivers refuse _N together with side normalisation.
+ * Not served: MATTRANFN and the side `~j` input transforms (ApplyStaticMat, sideXForm), USEOLDXFORMCVN, HIGHDIFF, and buffer mode
+ * (htkamd_parm_stream_* keeps refusing _Z).
+ * ------------------------------------------------------------------------------------------ */
+int  htkamd_mask_match(const char *mask, const char *name, char *out, int outLen);
+int  htkamd_parm_kind_parse(const char *str);
+int  htkamd_parm_kind_str(int kind, char *buf, int bufLen);
+int  htkamd_cepsnorm_read(const char *path, int *kind, int *nFrames, float *mean, int *dimMean, float *var, int *dimVar, int maxDim);
+int  htkamd_cepsnorm_write(const char *path, int kind, const char *flags, int nFrames, const float *mean, const float *var, int dim);
+int  htkamd_varscale_read(const char *path, float *v, int *dim, int maxDim);
+int  htkamd_cepsnorm_check_kinds(int targetKind, int meanKind, int varKind);
+int  htkamd_cepsnorm_scale(const float *varScale, int dScale, const float *sideVar /*[nSide x dVar]*/, int dVar, int nSide,
+                           const char *const *sideNames, float *scale /*[nSide x dVar]*/);
+int  htkamd_side_stats_finish(const double *sum, const double *sqsum, const long long *nFrames, int nSide, int D, float *mean, float *var);
+int  htkamd_side_stats(const float *dX, const int *frameOff /*[nUtt+1]*/, const int *uttSide /*[nUtt]*/, int nUtt, int nSide, int nCols, int D,
+                       double *sum /*[nSide x D]*/, double *sqsum, long long *nFrames /*[nSide]*/, void *stream);
+int  htkamd_parm_normalise(float *dX, const int *frameOff, const int *uttSide, int nUtt, int nSide, int nCols,
+                           const float *mean, int dMean, const float *scale, int dScale, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -75,23 +75,16 @@ static int cfg_bool(const config *c, const char *key, int dflt) { const char *v 
 #define PK_HASZEROC  020000
 #define PK_HASTHIRD  0100000
 static const char *const pk_base[] = {"WAVEFORM", "LPC", "LPREFC", "LPCEPSTRA", "LPDELCEP", "IREFC", "MFCC", "FBANK", "MELSPEC", "USER", "DISCRETE", "PLP", NULL};
+/* the library's parser (htkamd_parm_kind_parse = Str2ParmKind), in any letter case; the storage qualifiers _C _K have no effect on the observation */
 static int kind_parse(const char *s)
 {
-   char buf[128]; int k = -1;
+   char buf[128];
    snprintf(buf, sizeof(buf), "%s", s);
    for (char *q = buf; *q; q++) *q = (char)toupper((unsigned char)*q);
-   char *tok = strtok(buf, "_");
-   for (int i = 0; pk_base[i]; i++) if (tok && !strcmp(tok, pk_base[i])) k = i;
+   const int k = htkamd_parm_kind_parse(buf);
    if (k < 0) DIE("unknown parameter kind %s", s);
-   while ((tok = strtok(NULL, "_")) != NULL) {
-      switch (tok[0]) {
-      case 'E': k |= PK_HASENERGY; break; case 'N': k |= PK_HASNULLE; break; case 'D': k |= PK_HASDELTA; break; case 'A': k |= PK_HASACCS; break;
-      case 'Z': k |= PK_HASZEROM; break; case '0': k |= PK_HASZEROC; break; case 'T': k |= PK_HASTHIRD; break;
-      case 'C': case 'K': break;                               /* storage qualifiers: no effect on the observation */
-      default: DIE("unknown qualifier _%s in parameter kind %s", tok, s);
-      }
-   }
-   return k;
+   if (k & 040000) DIE("parameter kind %s: _V (vector quantisation) is not supported", s);
+   return k & ~(02000 | 010000);
 }
 
 /* ---- file names: MakeFN (HShell.c:1258): directory and extension of `fn` replaced ---- */
@@ -108,7 +101,8 @@ static void make_fn(const char *fn, const char *dir, const char *ext, char *out,
 
 /* ---- a batch of parameter files -> one device table of observations of the TARGET kind ----
  * The files hold `fileKind` (all the same); the qualifiers the target kind has beyond it (_D _A _T _Z _N) are computed on the device
- * (htkamd_parm_qualify = AddQualifiers HParm.c:1618), as OpenBuffer does when TARGETKIND asks for more than the file has. */
+ * (htkamd_parm_qualify = AddQualifiers HParm.c:1618), as OpenBuffer does when TARGETKIND asks for more than the file has; side means
+ * and variances (CMEANDIR ..., VARSCALEDIR ...) are applied behind them (normalise_sides). */
 typedef struct {
    int nUtt, cols, period, *frameOff;
    float *dX;                  /* device [frameOff[nUtt] * cols] */
@@ -203,6 +197,113 @@ static int code_waveforms(const strlist *files, int first, int count, int target
    return base | (m->hasC0 ? PK_HASZEROC : 0) | (m->hasE ? PK_HASENERGY : 0);
 }
 
+/* ---- side-based cepstral mean and variance normalisation (HParm.c:3172-3349, :1728-1741, :1793-1812) ----
+ * CMEANDIR / CMEANMASK [/ CMEANPATHMASK]: with _Z in TARGETKIND (and not in the files) the mean vector of the file's side --
+ * <CMEANDIR>/[<path mask's capture>/]<mask's capture> -- is subtracted in place of the utterance's own mean.  VARSCALEDIR / VARSCALEMASK
+ * [/ VARSCALEPATHMASK] + VARSCALEFN: every column is scaled by sqrt(global variance / side variance).  For parameter files and waveforms alike. */
+static const char *const side_norm_vars[] = {"CMEANDIR", "CMEANMASK", "CMEANPATHMASK", "VARSCALEDIR", "VARSCALEMASK", "VARSCALEPATHMASK", "VARSCALEFN", NULL};
+static int side_mean_set(const config *c) { return cfg_get(c, "CMEANDIR") || cfg_get(c, "CMEANMASK"); }       /* HParm.c:4376 */
+static int side_var_set(const config *c) { return cfg_get(c, "VARSCALEDIR") || cfg_get(c, "VARSCALEMASK"); }  /* HParm.c:4380 */
+
+/* what can be refused from the configuration alone; the drivers call this before they touch a device */
+static void check_side_norm(const config *c)
+{
+   if (side_mean_set(c) && !(cfg_get(c, "CMEANDIR") && cfg_get(c, "CMEANMASK"))) DIE("side mean (CMEANDIR / CMEANMASK): mask or dir missing");
+   if (side_var_set(c) && !(cfg_get(c, "VARSCALEDIR") && cfg_get(c, "VARSCALEMASK"))) DIE("side variance (VARSCALEDIR / VARSCALEMASK): mask or dir missing");
+   if (side_var_set(c) && !cfg_get(c, "VARSCALEFN")) DIE("VARSCALEDIR is set without VARSCALEFN: the side variances have no global variance to be scaled to");
+   if (cfg_get(c, "VARSCALEFN") && !side_var_set(c)) DIE("VARSCALEFN without VARSCALEDIR / VARSCALEMASK: no variance scaling vector found");
+   if ((side_mean_set(c) || side_var_set(c)) &&            /* what the reference mixes into this step and this path does not serve */
+       (cfg_get(c, "MATTRANFN") || cfg_get(c, "SIDEXFORMMASK") || cfg_bool(c, "USEOLDXFORMCVN", 0) || cfg_bool(c, "HIGHDIFF", 0)))
+      DIE("side normalisation together with MATTRANFN, SIDEXFORMMASK, USEOLDXFORMCVN or HIGHDIFF is not supported");
+}
+
+/* the side files read so far: each is read once per process */
+typedef struct { strlist path; float **vec; int *dim, *kind; } side_cache;
+static side_cache g_sideMeans, g_sideVars;
+static const float *side_vector(side_cache *sc, int wantVar, const char *what, const char *dir, const char *mask, const char *pathMask, const char *fname,
+                                int targetKind, int *dim, const char **pathOut)
+{
+   char side[1024], sub[1024], path[4096];
+   int rc = htkamd_mask_match(mask, fname, side, sizeof(side));
+   if (rc < 0) DIE("%s", htkamd_last_error());
+   if (rc == 0) DIE("%s: non-matching mask %s (file %s)", what, mask, fname);
+   if (pathMask) {
+      rc = htkamd_mask_match(pathMask, fname, sub, sizeof(sub));
+      if (rc < 0) DIE("%s", htkamd_last_error());
+      if (rc == 0) DIE("%s: non-matching path mask %s (file %s)", what, pathMask, fname);
+      snprintf(path, sizeof(path), "%s/%s/%s", dir, sub, side);
+   } else snprintf(path, sizeof(path), "%s/%s", dir, side);
+   int i;
+   for (i = 0; i < sc->path.n; i++) if (!strcmp(sc->path.v[i], path)) break;
+   if (i == sc->path.n) {
+      float buf[4096];
+      int kind, d = 0;
+      if (wantVar) CHECK(htkamd_cepsnorm_read(path, &kind, NULL, NULL, NULL, buf, &d, 4096));
+      else CHECK(htkamd_cepsnorm_read(path, &kind, NULL, buf, &d, NULL, NULL, 4096));
+      if (d == 0) DIE("%s: %s missing in %s", what, wantVar ? "<VARIANCE>" : "<MEAN>", path);
+      sl_add(&sc->path, path);
+      sc->vec = (float **)realloc(sc->vec, sizeof(float *) * (size_t)sc->path.n);
+      sc->dim = (int *)realloc(sc->dim, sizeof(int) * (size_t)sc->path.n);
+      sc->kind = (int *)realloc(sc->kind, sizeof(int) * (size_t)sc->path.n);
+      sc->vec[i] = (float *)malloc(sizeof(float) * (size_t)d); memcpy(sc->vec[i], buf, sizeof(float) * (size_t)d);
+      sc->dim[i] = d; sc->kind[i] = kind;
+   }
+   if (htkamd_cepsnorm_check_kinds(targetKind, wantVar ? -1 : sc->kind[i], wantVar ? sc->kind[i] : -1)) DIE("%s: %s", sc->path.v[i], htkamd_last_error());
+   *dim = sc->dim[i]; *pathOut = sc->path.v[i];
+   return sc->vec[i];
+}
+
+/* the tail of AddQualifiers on the table of a batch: every file goes to its side through the masks; the sides of the batch get one row
+   each in the mean and scale tables, and the device normalises in place (htkamd_parm_normalise) */
+static void normalise_sides(const strlist *files, int first, int count, int targetKind, int useMean, const config *cfg, int cols, const int *frameOff, float *dX)
+{
+   const int useVar = side_var_set(cfg);
+   if (!useMean && !useVar) return;
+   /* _N: the reference applies the side vectors while the energy column is still in the row (AddQualifiers) and drops it when an
+      observation is extracted (HParm.c:2882); here the column is gone by now, so vectors beyond the statics would meet the wrong columns */
+   if (targetKind & PK_HASNULLE) DIE("side normalisation (CMEAN* / VARSCALE*) with _N in TARGETKIND is not supported");
+   static float *varScale = NULL; static int dVS = 0;
+   if (useVar && !varScale) {                              /* LoadVarScale: once per process */
+      varScale = (float *)malloc(sizeof(float) * 4096);
+      CHECK(htkamd_varscale_read(cfg_get(cfg, "VARSCALEFN"), varScale, &dVS, 4096));
+   }
+   strlist keys = {0};
+   int *uttSide = (int *)calloc((size_t)count + 1, sizeof(int));
+   float *mean = NULL, *var = NULL, *scale = NULL;
+   const char **names = NULL;
+   int dMean = 0, dVar = 0, nSide = 0;
+   for (int u = 0; u < count; u++) {
+      const char *fn = files->v[first + u], *mp = "", *vp = "";
+      const float *mv = NULL, *vv = NULL;
+      int dm = 0, dv = 0;
+      if (useMean) mv = side_vector(&g_sideMeans, 0, "side mean (CMEANMASK)", cfg_get(cfg, "CMEANDIR"), cfg_get(cfg, "CMEANMASK"), cfg_get(cfg, "CMEANPATHMASK"), fn, targetKind, &dm, &mp);
+      if (useVar) vv = side_vector(&g_sideVars, 1, "side variance (VARSCALEMASK)", cfg_get(cfg, "VARSCALEDIR"), cfg_get(cfg, "VARSCALEMASK"), cfg_get(cfg, "VARSCALEPATHMASK"), fn, targetKind, &dv, &vp);
+      if (u == 0) { dMean = dm; dVar = dv; }
+      if (dm != dMean || dv != dVar) DIE("%s: the side's vectors have %d / %d values, those of the batch's first file %d / %d", fn, dm, dv, dMean, dVar);
+      if (dMean > cols || dVar > cols) DIE("%s: side vectors of %d / %d values for observations of %d", fn, dMean, dVar, cols);
+      char key[8192]; snprintf(key, sizeof(key), "%s|%s", mp, vp);
+      int s;
+      for (s = 0; s < nSide; s++) if (!strcmp(keys.v[s], key)) break;
+      if (s == nSide) {
+         sl_add(&keys, key); nSide++;
+         mean = (float *)realloc(mean, sizeof(float) * (size_t)nSide * (size_t)(dMean ? dMean : 1));
+         var = (float *)realloc(var, sizeof(float) * (size_t)nSide * (size_t)(dVar ? dVar : 1));
+         names = (const char **)realloc((void *)names, sizeof(char *) * (size_t)nSide);
+         if (mv) memcpy(mean + (size_t)s * dMean, mv, sizeof(float) * (size_t)dMean);
+         if (vv) memcpy(var + (size_t)s * dVar, vv, sizeof(float) * (size_t)dVar);
+         names[s] = vp;
+      }
+      uttSide[u] = s;
+   }
+   if (useVar && nSide) {
+      scale = (float *)malloc(sizeof(float) * (size_t)nSide * (size_t)dVar);
+      if (htkamd_cepsnorm_scale(varScale, dVS, var, dVar, nSide, names, scale)) DIE("variance scaling (VARSCALEFN %s): %s", cfg_get(cfg, "VARSCALEFN"), htkamd_last_error());
+   }
+   CHECK(htkamd_parm_normalise(dX, frameOff, uttSide, count, nSide, cols, useMean ? mean : NULL, dMean, scale, dVar, NULL));
+   for (int s = 0; s < nSide; s++) free(keys.v[s]);
+   free(keys.v); free(uttSide); free(mean); free(var); free(scale); free((void *)names);
+}
+
 static void load_observations(const strlist *files, int first, int count, int targetKind, const config *cfg, obs_batch *ob)
 {
    float *stat = NULL; size_t cap = 0;
@@ -234,14 +335,16 @@ static void load_observations(const strlist *files, int first, int count, int ta
       CHECK(htkamd_memcpy_h2d(dStat, stat, sizeof(float) * (size_t)F * nStat, NULL));
       free(stat);
    }
-   if (add == 0) { ob->dX = dStat; ob->cols = nStat; return; }
+   /* a side mean takes the place of the utterance's own (HParm.c:1709-1741, :4375): _Z asked for, not in the files, CMEANDIR / CMEANMASK set */
+   const int sideMean = side_mean_set(cfg) && (add & PK_HASZEROM);
+   if (add == 0) { ob->dX = dStat; ob->cols = nStat; normalise_sides(files, first, count, targetKind, 0, cfg, ob->cols, ob->frameOff, ob->dX); return; }
    if (fileKind & (PK_HASDELTA | PK_HASACCS | PK_HASTHIRD)) DIE("files already carry differentials: further qualifiers cannot be appended");
    htkamd_parm_quals q; memset(&q, 0, sizeof(q));
    const int nE = ((fileKind & PK_HASENERGY) ? 1 : 0) + ((fileKind & PK_HASZEROC) ? 1 : 0), base = nStat - nE;
    q.nStat = nStat;
    q.hasD = (targetKind & PK_HASDELTA) != 0; q.hasA = (targetKind & PK_HASACCS) != 0; q.hasT = (targetKind & PK_HASTHIRD) != 0;
    q.delWin = cfg_int(cfg, "DELTAWINDOW", 2); q.accWin = cfg_int(cfg, "ACCWINDOW", 2); q.thirdWin = cfg_int(cfg, "THIRDWINDOW", 2);
-   q.nZeroMean = (add & PK_HASZEROM) ? base + (((targetKind & PK_HASZEROC) && !(targetKind & PK_HASNULLE)) ? 1 : 0) : 0;   /* HParm.c:1712-1715 */
+   q.nZeroMean = ((add & PK_HASZEROM) && !sideMean) ? base + (((targetKind & PK_HASZEROC) && !(targetKind & PK_HASNULLE)) ? 1 : 0) : 0;   /* HParm.c:1712-1715 */
    q.nullECol = ((targetKind & PK_HASNULLE) && nE) ? base : -1;
    q.v1Compat = cfg_bool(cfg, "V1COMPAT", 0); q.simpleDiffs = cfg_bool(cfg, "SIMPLEDIFFS", 0);
    ob->cols = htkamd_parm_quals_cols(&q);
@@ -249,9 +352,23 @@ static void load_observations(const strlist *files, int first, int count, int ta
    CHECK(htkamd_parm_qualify(dStat, ob->frameOff, count, &q, ob->dX, NULL));
    CHECK(htkamd_stream_sync(NULL));
    CHECK(htkamd_dev_free(dStat));
+   normalise_sides(files, first, count, targetKind, sideMean, cfg, ob->cols, ob->frameOff, ob->dX);
 }
 
 static void free_observations(obs_batch *ob) { if (ob->dX) htkamd_dev_free(ob->dX); free(ob->frameOff); memset(ob, 0, sizeof(*ob)); }
+
+/* --help: the configuration variables the drivers honour */
+static void print_config_help(FILE *f)
+{
+   fprintf(f, "Configuration variables (-C file):\n"
+              "  TARGETKIND DELTAWINDOW ACCWINDOW THIRDWINDOW V1COMPAT SIMPLEDIFFS\n"
+              "  waveform sources (SOURCEFORMAT = WAV or SOURCEKIND = WAVEFORM): SOURCERATE TARGETRATE WINDOWSIZE NUMCHANS NUMCEPS CEPLIFTER\n"
+              "    PREEMCOEF USEHAMMING USEPOWER ZMEANSOURCE RAWENERGY ENORMALISE LOFREQ HIFREQ CEPSCALE SILFLOOR ESCALE LPCORDER COMPRESSFACT\n"
+              "    WARPFREQ WARPLCUTOFF WARPUCUTOFF\n"
+              "  side-based mean and variance normalisation:");
+   for (int i = 0; side_norm_vars[i]; i++) fprintf(f, " %s", side_norm_vars[i]);
+   fprintf(f, "\n");
+}
 
 /* ---- option scanning in HTK's style: switches first ("-x", optionally followed by values), then positional arguments ---- */
 typedef struct { int argc, at; char **argv; } args;

@@ -7,6 +7,8 @@
  *                  with SOURCEFORMAT = WAV (or SOURCEKIND = WAVEFORM) the files are waveforms, coded on the device as TARGETKIND's
  *                  MFCC, FBANK, MELSPEC or PLP (NUMCHANS, NUMCEPS, LPCORDER, COMPRESSFACT, ...); the LPC kinds are refused;
  *                  WARPFREQ, WARPLCUTOFF and WARPUCUTOFF warp the filterbank's frequency axis (VTLN), as HCopy does
+ *                  CMEANDIR / CMEANMASK [/ CMEANPATHMASK] and VARSCALEDIR / VARSCALEMASK [/ VARSCALEPATHMASK] / VARSCALEFN: side-based mean and
+ *                  variance normalisation behind the qualifiers, as HParm does (files and waveforms alike); --help lists the variables
  *   -S scp         script file: further data files (extended file names logical=physical[s,e] are accepted, the segment is ignored)
  *   -H mmf         load a master macro file (repeatable)          -d dir / -x ext   directory / extension of single-model files
  *   -M dir         directory for the re-estimated models          -B                save them in binary
@@ -107,6 +109,7 @@ int main(int argc, char **argv)
             if (wire < 0) DIE("--wire: f32 | f64");
          }
          else if (!strcmp(lo, "compat")) compat = HTKAMD_COMPAT_STREAM_REVISIT | HTKAMD_COMPAT_SHARED_LOGWT;      /* HERest's own numbers on sets of 2 or 4+ streams (HFB.c:1059) and on sets with shared pdfs (HUtil.c:474) */
+         else if (!strcmp(lo, "help")) { printf("USAGE: herest [options] hmmList dataFiles...   (the options: the comment at the head of tools/herest.c)\n"); print_config_help(stdout); return 0; }
          else DIE("unknown option --%s", lo);
          continue;
       }
@@ -153,6 +156,7 @@ int main(int argc, char **argv)
 
    if (waveform_source(&cfg) && cfg_get(&cfg, "TARGETKIND")) check_waveform_kind(kind_parse(cfg_get(&cfg, "TARGETKIND")));
    if (waveform_source(&cfg)) check_waveform_warp(&cfg);
+   check_side_norm(&cfg);
    if (htkamd_device_count() <= 0) DIE("herest: no HIP device (the MI355X path has no CPU fallback)");
    CHECK(htkamd_set_device(nRanks > 1 ? rank % htkamd_device_count() : 0));
 

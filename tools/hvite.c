@@ -8,6 +8,8 @@
  *                with SOURCEFORMAT = WAV (or SOURCEKIND = WAVEFORM) the files are waveforms, coded on the device as TARGETKIND's
  *                MFCC, FBANK, MELSPEC or PLP (NUMCHANS, NUMCEPS, LPCORDER, COMPRESSFACT, ...); the LPC kinds are refused;
  *                WARPFREQ, WARPLCUTOFF and WARPUCUTOFF warp the filterbank's frequency axis (VTLN), as HCopy does
+ *                CMEANDIR / CMEANMASK [/ CMEANPATHMASK] and VARSCALEDIR / VARSCALEMASK [/ VARSCALEPATHMASK] / VARSCALEFN: side-based mean and
+ *                variance normalisation behind the qualifiers, as HParm does (files and waveforms alike); --help lists the variables
  *   -S scp       script file with further data files            -H mmf / -d dir / -x ext   model sources
  *   -w net       recognition network (SLF word lattice)         -a            align against the label files instead
  *   -b word      alignment: boundary word at both ends          -L dir / -X ext / -I mlf   transcriptions to align (default .lab)
@@ -141,6 +143,7 @@ int main(int argc, char **argv)
             scoreMode = !strcmp(m, "exact") ? HTKAMD_SCORE_EXACT : !strcmp(m, "fast") ? HTKAMD_SCORE_MFMA : !strcmp(m, "fastest") ? HTKAMD_SCORE_BF16 : -1;
             if (scoreMode < 0) DIE("--score: exact | fast | fastest");
          } else if (!strcmp(lo, "batch")) batchN = atoi(str_arg(&a, "-batch"));
+         else if (!strcmp(lo, "help")) { printf("USAGE: hvite [options] -w net.slf | -a [-b sil] dict hmmList dataFiles...   (the options: the comment at the head of tools/hvite.c)\n"); print_config_help(stdout); return 0; }
          else DIE("unknown option --%s", lo);
          continue;
       }
@@ -212,6 +215,7 @@ int main(int argc, char **argv)
    if (latExt && nToks < 2) DIE("hvite -z: lattices need -n i with i > 1");
    if (waveform_source(&cfg) && cfg_get(&cfg, "TARGETKIND")) check_waveform_kind(kind_parse(cfg_get(&cfg, "TARGETKIND")));
    if (waveform_source(&cfg)) check_waveform_warp(&cfg);
+   check_side_norm(&cfg);
    if (htkamd_device_count() <= 0) DIE("hvite: no HIP device (the MI355X path has no CPU fallback)");
 
    htkamd_mmf *mmf; CHECK(htkamd_mmf_create(&mmf));
