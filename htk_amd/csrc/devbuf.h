@@ -8,11 +8,10 @@
 template <const char *Owner> struct DevBufT {
    void *p = nullptr;
    size_t cap = 0;
-   bool view = false;            // p points into another allocation (forward-backward's batch-table arena)
-   void set_view(void *q) { if (p && !view) (void)hipFree(p); p = q; cap = 0; view = true; }
+   DevBufT() = default; DevBufT(const DevBufT &) = delete; DevBufT &operator=(const DevBufT &) = delete;      // (owns p)
+   ~DevBufT() { release(); }
    int reserve(size_t bytes)
    {
-      if (view) { p = nullptr; view = false; cap = 0; }
       if (bytes <= cap) return HTKAMD_OK;
       if (p) (void)hipFree(p);
       p = nullptr; cap = 0;
@@ -22,5 +21,5 @@ template <const char *Owner> struct DevBufT {
       cap = want;
       return HTKAMD_OK;
    }
-   void release() { if (p && !view) (void)hipFree(p); p = nullptr; cap = 0; view = false; }
+   void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };

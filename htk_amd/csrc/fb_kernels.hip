@@ -772,7 +772,7 @@ __global__ __launch_bounds__(256, 4) void k_mixstats(FbArgs a)
        const size_t udGam0 = up->gam0;
        const int udSlots = up->nSlots, udSlot0 = up->slot0, udFrame0 = up->frame0;
        // utterances of the left-to-right path have no seeds here (their statistics kernel lists the pairs itself: k_mixhits)
-       const bool ok = have && a.status[u] == HTKAMD_UTT_OK && up->pad != 2;
+       const bool ok = have && a.status[u] == HTKAMD_UTT_OK && up->family != FB_LEFT_TO_RIGHT;
        const size_t rel = hidx - udGam0;
        const int nSl = udSlots > 0 ? udSlots : 1;
        const int t0 = (int)(rel / nSl), slot = (int)(rel % nSl);
@@ -1435,7 +1435,7 @@ __global__ __launch_bounds__(256) void k_mixstats_ms(FbArgs a)
          const double seed = hSeed[i];
          while (u + 1 < a.nUtt && a.gamOffByUtt[u + 1] <= hidx) u++;
          const UttDesc *up = a.utt + u;
-         if (a.status[u] != HTKAMD_UTT_OK || up->pad == 2) continue;      // (an utterance of the left-to-right path has no seeds here: its pairs are listed)
+         if (a.status[u] != HTKAMD_UTT_OK || up->family == FB_LEFT_TO_RIGHT) continue;      // (an utterance of the left-to-right path has no seeds here: its pairs are listed)
          const int nSl_ = up->nSlots;
          const size_t rel = hidx - up->gam0;
          ms_pair(a, up, (int)(rel / nSl_), (int)(rel % nSl_), seed, lane);
@@ -1685,7 +1685,7 @@ __global__ __launch_bounds__(256) void k_mixstats_tm(FbArgs a)
          const double seed = hSeed[i];
          while (u + 1 < a.nUtt && a.gamOffByUtt[u + 1] <= hidx) u++;
          const UttDesc *up = a.utt + u;
-         if (a.status[u] != HTKAMD_UTT_OK || up->pad == 2) continue;      // (an utterance of the left-to-right path has no seeds here: its pairs are listed)
+         if (a.status[u] != HTKAMD_UTT_OK || up->family == FB_LEFT_TO_RIGHT) continue;      // (an utterance of the left-to-right path has no seeds here: its pairs are listed)
          const int nSl_ = up->nSlots;
          const size_t rel = hidx - up->gam0;
          tm_pair(a, up, (int)(rel / nSl_), (int)(rel % nSl_), seed, lane);

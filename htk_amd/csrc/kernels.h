@@ -111,6 +111,11 @@ static inline int htkamd_launch_score(int mode, const htkamd_model *m, const Sco
 }
 
 // ---- forward-backward ----
+enum FbFamily {             // the kernels an utterance with W > 0 runs on (UttDesc::family)
+   FB_LANE_PER_MODEL = 0,   // fb_wave.hip: a lane per MODEL, chain of <= 64*W models; beta block = [T][5 states][64*W]
+   FB_LANE_PER_STATE = 1,   // fb_state.hip: a lane per chain STATE, <= 64*W emitting states, no tee models; beta block = betaS[T][64*W] then betaE[T][64*W]
+   FB_LEFT_TO_RIGHT = 2     // fb_lr.hip: the same for left-to-right chains; beta block = betaS[T][64*W], alpha block (alphaW0) = alphaS[T][64*W] then alphaE[T][QP]
+};
 struct UttDesc {
    int T, Q, nCells, nSlots;
    int frame0;        // first row in X and in the per-frame beam arrays
@@ -124,12 +129,9 @@ struct UttDesc {
    size_t beta0;      // doubles: beta[beta0 + (t-1)*nCells + cell]
    size_t gam0;       // doubles: gam [gam0  + (t-1)*nSlots + slot]
    size_t betaW0;     // doubles: wave path's beta block of this utterance, betaW[betaW0 + ((t-1)*5 + i-1)*64*W + model-1]
-   int W, pad;        // wavefronts working on the utterance (1, 2, 4 or 8); 0 = general kernels.  pad = 0: a lane per MODEL (fb_wave.hip,
-                      // chain of <= 64*W models); pad = 1: a lane per chain STATE (fb_state.hip, <= 64*W emitting states, no tee models),
-                      // beta block = betaS[T][64*W] then betaE[T][64*W]; pad = 2: the same for left-to-right chains (fb_lr.hip), beta block =
-                      // betaS[T][64*W], alpha block (alphaW0) = alphaS[T][64*W] then alphaE[T][QP]
-   size_t alphaW0;    // doubles: the utterance's block in alphaW (pad = 2)
-   int QP, pad2;      // Q rounded up to a multiple of 8
+   int W, family;     // wavefronts working on the utterance (1, 2, 4 or 8), and on which kernels (FbFamily); W = 0: the general kernels
+   size_t alphaW0;    // doubles: the utterance's block in alphaW (FB_LEFT_TO_RIGHT)
+   int QP, reserved;  // Q rounded up to a multiple of 8
 };
 
 // what the statistics of a (frame, chain state) pair need of the state (left-to-right path: written by the beta kernels, a record per slot)

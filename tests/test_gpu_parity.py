@@ -1039,3 +1039,93 @@ def test_run_to_run_reproducibility(native, mode):
         for k in ("nEgs", "totalT", "nUttDone", "nUttSkipped", "nEval"):
             o = getattr(lay, k)
             assert vec[o] == ref[o]
+
+
+# ----------------------------------------------------------------------------------------- one context, batch after batch
+def _chain_from_models(rng, pk, seq):
+    """An utterance for the chain `seq`: two or three frames per state, drawn around one of the state's components."""
+    fr = []
+    for h in seq:
+        for s in pk["hmmState"][pk["hmmStateOff"][h]:pk["hmmStateOff"][h + 1]]:
+            for _ in range(int(rng.integers(2, 4))):
+                c = int(rng.integers(pk["stateCompOff"][s], pk["stateCompOff"][s + 1]))
+                fr.append(pk["mean"][c] + rng.normal(0, 1, pk["vecSize"]) * np.sqrt(pk["var"][c]))
+    return dict(seq=np.asarray(seq, np.int32), feat=np.array(fr, np.float32))
+
+
+def _pass_snapshot(native, fb, model, utts):
+    """prepare + execute + results of `utts` on `fb`: what the pass leaves per utterance and in fresh accumulators."""
+    X, frameOff, labOff, labs = batch_arrays(utts)
+    dX = native.DevArray(X)
+    acc = native.Accs(model)
+    fb.prepare(dX.ptr.value, frameOff, labOff, labs)
+    fb.execute(native.fb_config(uFlags=15), acc)
+    pr, st = fb.results()
+    beams = {u: {k: v.copy() for k, v in fb.trellis(u).items() if k in ("qLo", "qHi", "aLo", "aHi")} for u in range(len(utts)) if st[u] == 1}
+    return dict(pr=np.array(pr), st=np.array(st), beams=beams, vec=acc.download()["vec"].copy())
+
+
+@pytest.mark.parametrize("general", [False, True], ids=["classes", "general"])
+def test_context_reused_batch_after_batch(native, general):
+    """What a context carries from one prepare to the next (host tables that keep their size, the arena, the class lists, the per-frame
+    words that are refilled only when the frame count changes, workspaces that never shrink) must not reach the next batch's results:
+    A, B, A, a prepare that fails, A on ONE context give what each batch gives on a fresh context -- `pr`, status and the four beams
+    bit for bit, the accumulators to the summation-order noise of fp64 atomics (test_run_to_run_reproducibility's bound), the counters
+    exactly.  Batch A holds every class the set can put into one batch: a left-to-right chain (fb_lr.hip), one with a skip model and
+    no tee (fb_state.hip), one with the tee model inside (fb_wave.hip), and pool utterances strung together to more than 64 models
+    (two wavefronts).  A chain of more than 512 models is refused by prepare (more than 1024 model states), so the general kernels
+    cannot share a batch with the others here: they get the same sequence on a context that forces them (`general`)."""
+    from htk_amd import synth
+    pk, names, seqs, feats = synth.make_topo_set(seed=77, D=13, NU=8)
+    a, b, sp, c, d, e = (names.index(n) for n in ("a", "b", "sp", "c", "d", "e"))
+    rng = np.random.default_rng(31)
+    lr = _chain_from_models(rng, pk, [a, d, b, e, d, a])
+    skip = _chain_from_models(rng, pk, [b, c, d, c, a])
+    tee = _chain_from_models(rng, pk, [a, sp, c, b, sp, d, e])
+    for ut, has, lacks in ((lr, (), (sp, c)), (skip, (c,), (sp,)), (tee, (sp,), ())):
+        q = list(ut["seq"])
+        assert all(h in q for h in has) and not any(h in q for h in lacks)
+    assert tee["seq"][0] != sp and tee["seq"][-1] != sp and not any(x == sp and y == sp for x, y in zip(tee["seq"], tee["seq"][1:]))
+    longer = _concat_chains(rng, seqs, feats, [70, 520])
+    assert 64 < len(longer[0]["seq"]) <= 128 and len(longer[1]["seq"]) > 512
+    A = [lr, skip, tee, longer[0], _chain_from_models(rng, pk, [d, d, a])]
+    B = [_chain_from_models(rng, pk, [e, sp, b]), _chain_from_models(rng, pk, [c, a, d])]
+    assert len(B) < len(A) and sum(len(u["feat"]) for u in B) < sum(len(u["feat"]) for u in A) and all(len(u["seq"]) for u in B)
+    model = native.Model(pk)
+    new = lambda: native.ForwardBackward(model, debug=True, force_general=general)
+    fresh = {"A": _pass_snapshot(native, new(), model, A), "B": _pass_snapshot(native, new(), model, B)}
+    assert (fresh["A"]["st"] == 1).all() and (fresh["B"]["st"] == 1).all()
+    lay = native.accs_layout(pk)
+
+    def same(got, ref, what):
+        assert np.array_equal(got["pr"], ref["pr"]) and np.array_equal(got["st"], ref["st"]), what
+        assert got["beams"].keys() == ref["beams"].keys(), what
+        for u, bm in ref["beams"].items():
+            for k, v in bm.items():
+                assert np.array_equal(got["beams"][u][k], v), (what, u, k)
+        err = np.abs(got["vec"] - ref["vec"]) - (1e-12 * np.abs(ref["vec"]) + 1e-14)
+        assert (err <= 0).all(), (what, int(np.argmax(err)), float(np.max(err)))
+        for k in ("nEgs", "totalT", "nUttDone", "nUttSkipped", "nEval"):
+            o = getattr(lay, k)
+            assert got["vec"][o] == ref["vec"][o], (what, k)
+
+    fb = new()
+    for step, name in enumerate("ABA"):
+        same(_pass_snapshot(native, fb, model, A if name == "A" else B), fresh[name], "%s (step %d)" % (name, step))
+    # a label index one past the last model: the prepare fails behind the batch description's check, and the context holds no batch
+    bad = [dict(seq=u["seq"].copy(), feat=u["feat"]) for u in B]
+    bad[-1]["seq"][-1] = len(names)
+    X, frameOff, labOff, labs = batch_arrays(bad)
+    dX = native.DevArray(X)
+    with pytest.raises(native.HtkAmdError):
+        fb.prepare(dX.ptr.value, frameOff, labOff, labs)
+    acc = native.Accs(model)
+    fb.execute(native.fb_config(uFlags=15), acc)
+    assert acc.download()["nUttDone"] == 0
+    same(_pass_snapshot(native, fb, model, A), fresh["A"], "A after the failed prepare")
+    if not general:      # the chain beyond 512 models: refused, and the context is as usable afterwards
+        X, frameOff, labOff, labs = batch_arrays([longer[1]])
+        dX = native.DevArray(X)
+        with pytest.raises(native.HtkAmdError):
+            fb.prepare(dX.ptr.value, frameOff, labOff, labs)
+        same(_pass_snapshot(native, fb, model, B), fresh["B"], "B after the refused chain")
