@@ -29,6 +29,7 @@ int main(int argc, char **argv)
    /* LoadHMMSet */
    htkamd_mmf *mmf; CHECK(htkamd_mmf_create(&mmf));
    CHECK(htkamd_mmf_finish(mmf, hmmList, hmmDir, NULL));
+   if (htkamd_mmf_inputxform(mmf)) { fprintf(stderr, "herest_pass: the model set carries an input transform (<INPUTXFORM>), which this program does not apply\n"); return 1; }
    const htkamd_model_desc *d = htkamd_mmf_desc(mmf);
    const char *kind = htkamd_mmf_parm_kind(mmf);
    const int hasD = strstr(kind, "_D") != NULL, hasA = strstr(kind, "_A") != NULL;

@@ -36,6 +36,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
 
     mmf = capi.Mmf(files=args.mmf, hmm_list=args.hmmlist, hmm_dir=args.hmmdir)
+    mmf.refuse_input_xform("herest_pass")
     pk = mmf.packed()
     model = capi.Model(pk)
     files = list(args.data)

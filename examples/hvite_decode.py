@@ -31,6 +31,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
 
     mmf = capi.Mmf(files=args.mmf, hmm_list=args.hmmlist)
+    mmf.refuse_input_xform("hvite_decode")
     net = capi.Net(args.net, args.dict, mmf)
     model = capi.Model(mmf.packed())
     feats, period = [], 100000

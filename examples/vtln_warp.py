@@ -112,6 +112,7 @@ def main(argv=None):
 
     capi.check(capi.lib().htkamd_set_device(0), "set_device")
     mmf = capi.Mmf(a.mmf, hmm_list=a.hmmlist)
+    mmf.refuse_input_xform("vtln_warp")
     model = capi.Model(mmf.packed())
     seqs = [[mmf.logical[l.split()[-1]] for l in open(os.path.splitext(f)[0] + ".lab") if l.strip()] for f in files]
     labOff = np.concatenate([[0], np.cumsum([len(q) for q in seqs])]).astype(np.int32)

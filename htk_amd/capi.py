@@ -942,6 +942,74 @@ class ParmStream:
             pass
 
 
+class InputXForm:
+    """htkamd_inputxform holder: a global linear input transform -- a model set's (Mmf.input_xform, owned by the set) or a file's
+    (InputXForm.read: HParm's MATTRANFN names such a file)."""
+
+    def __init__(self, handle, owned: bool, keep=None):
+        L = lib()
+        for f in ("htkamd_inputxform_name", "htkamd_inputxform_mask", "htkamd_inputxform_parm_kind"):
+            getattr(L, f).restype = C.c_char_p
+        L.htkamd_inputxform_matrix.restype = C.POINTER(C.c_float)
+        L.htkamd_inputxform_bias.restype = C.POINTER(C.c_float)
+        L.htkamd_inputxform_logdet.restype = C.c_float
+        self.h, self.owned, self._keep = handle, owned, keep
+        self.name = L.htkamd_inputxform_name(handle).decode()
+        self.mask = L.htkamd_inputxform_mask(handle).decode()
+        self.kind = L.htkamd_inputxform_parm_kind(handle).decode()
+        self.prequal = bool(L.htkamd_inputxform_prequal(handle))
+        self.rows, self.cols = L.htkamd_inputxform_rows(handle), L.htkamd_inputxform_cols(handle)
+        self.vec_size = L.htkamd_inputxform_vec_size(handle)
+        self.matrix = np.ctypeslib.as_array(L.htkamd_inputxform_matrix(handle), (self.rows * self.cols,)).reshape(self.rows, self.cols).copy()
+        n = C.c_int(0)
+        b = L.htkamd_inputxform_bias(handle, C.byref(n))
+        self.bias = np.ctypeslib.as_array(b, (n.value,)).copy() if b else None
+        self.logdet = float(L.htkamd_inputxform_logdet(handle))
+
+    @classmethod
+    def read(cls, path: str) -> "InputXForm":
+        h = C.c_void_p()
+        check(lib().htkamd_inputxform_read(str(path).encode(), C.byref(h)), "inputxform_read")
+        return cls(h, True)
+
+    def write(self, path: str, binary: bool = False):
+        check(lib().htkamd_inputxform_write(self.h, str(path).encode(), C.c_int(int(binary))), "inputxform_write")
+
+    def check_against(self, srcKind: str, targetKind: str, nStat: int, setId: str = "", vecSize: int = 0):
+        """htkamd_inputxform_check: the reference's checks of a transform against the data and the set it meets."""
+        check(lib().htkamd_inputxform_check(self.h, C.c_int(parm_kind_parse(srcKind)), C.c_int(parm_kind_parse(targetKind)), C.c_int(nStat),
+                                            setId.encode(), C.c_int(vecSize)), "inputxform_check")
+
+    def apply(self, stat_list, quals: ParmQuals):
+        """htkamd_inputxform_apply: the qualifier step of a transformed set on the statics of several utterances, in the reference's
+        order.  Returns (DevArray [sum T, cols], frameOff, cols)."""
+        stat = np.ascontiguousarray(np.concatenate(stat_list), np.float32)
+        frameOff = np.concatenate([[0], np.cumsum([x.shape[0] for x in stat_list])]).astype(np.int32)
+        assert stat.shape[1] == quals.nStat
+        cols = lib().htkamd_inputxform_apply_cols(self.h, C.byref(quals))
+        dIn = DevArray(stat)
+        dOut = DevArray(nbytes=4 * max(stat.shape[0] * cols, 1))
+        check(lib().htkamd_inputxform_apply(self.h, dIn.ptr, _p(frameOff), C.c_int(len(stat_list)), C.byref(quals), dOut.ptr, None), "inputxform_apply")
+        return dOut, frameOff, cols
+
+    def close(self):
+        if self.owned and self.h:
+            lib().htkamd_inputxform_free(self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parm_xform(dIn_ptr, inCols: int, dOut_ptr, outCols: int, nRows: int, dMat_ptr, mrows: int, mcols: int, stream=None):
+    """htkamd_parm_xform: out[r][0..mrows) = M . in[r][0..mcols) in the reference's float arithmetic; asynchronous on `stream`."""
+    check(lib().htkamd_parm_xform(dIn_ptr, C.c_int(inCols), dOut_ptr, C.c_int(outCols), C.c_longlong(nRows), dMat_ptr, C.c_int(mrows), C.c_int(mcols),
+                                  _stream(stream)), "parm_xform")
+
+
 class Mmf:
     """htkamd_mmf holder: LoadHMMSet / SaveHMMSet for text model definitions (htk_amd/host/mmf.c)."""
 
@@ -970,6 +1038,18 @@ class Mmf:
         D = self.desc.vecSize
         self.inv_cov = np.ctypeslib.as_array(ic, (self.desc.numGauss * (D * (D + 1) // 2),)).reshape(self.desc.numGauss, -1).copy() if ic else None
         self.cov_kind = "FULLC" if self.inv_cov is not None else "DIAGC"
+        L.htkamd_mmf_inputxform.restype = C.c_void_p
+        L.htkamd_mmf_set_id.restype = C.c_char_p
+        self.set_id = L.htkamd_mmf_set_id(self.h).decode()
+        xf = L.htkamd_mmf_inputxform(self.h)
+        self.input_xform = InputXForm(C.c_void_p(xf), False, keep=self) if xf else None      # <INPUTXFORM>: owned by the set
+
+    def refuse_input_xform(self, who: str):
+        """For a caller that prepares its observations without looking at the set's transform: a set with <INPUTXFORM> would be trained
+        or recognised on untransformed rows.  Such a caller says so and stops (InputXForm.apply is the step it lacks)."""
+        if self.input_xform is not None:
+            raise HtkAmdError("%s: the model set carries an input transform (<INPUTXFORM> %s), which this program does not apply"
+                              % (who, self.input_xform.name))
 
     def packed(self) -> dict:
         """The flat description as the dict of numpy arrays Model() takes."""

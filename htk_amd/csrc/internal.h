@@ -68,6 +68,17 @@ int  htkamd_frontend_tables_build(const htkamd_frontend_config *c, struct htkamd
 int  htkamd_frontend_warp_check(const htkamd_frontend_config *c, const htkamd_warp *w);
 int  htkamd_frontend_tables_build_warped(const htkamd_frontend_config *c, const htkamd_warp *w, struct htkamd_mfcc_tables *t);
 
+/* ---- input transforms (htk_amd/host/mmf.c reads and writes them, csrc/inputxform.hip applies them) ---- */
+struct htkamd_inputxform {
+   char *name, *mask;          /* macro name (an inline transform: the file it stood in); <MMFIDMASK> */
+   char kind[64];              /* parameter kind of the rows it takes */
+   int preQual;                /* <PREQUAL>: applied to the statics, before the qualifiers */
+   int vecSize, blockSize;     /* <VECSIZE> and the one block's size of <BLOCKINFO>: carried */
+   int nBias; float *bias;     /* <OFFSET> <BIAS>: carried, not applied (ApplyStaticMat uses the matrix alone) */
+   float det;                  /* <LOGDET>: carried (0 = none) */
+   int mrows, mcols; float *mat;   /* <XFORM> r c, row-major */
+};
+
 /* ---- packed model ---- */
 struct htkamd_model {
    int D, S, C, G, nT, H, maxN, maxM;

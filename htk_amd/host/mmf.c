@@ -12,8 +12,9 @@
  * written as well, shared mixture pdfs (~m) are kept shared (one Gaussian, several components).  Shared mean / variance vectors
  * (~u / ~v macros referenced inside a mixture, GetMean :1737 / GetVariance :1770) are read, kept (every Gaussian holds its copy of the
  * values plus the number of the macro it shares: htkamd_mmf_sharing) and written back as macros; duration vectors (<DURATION>, ~d macros; the set's <POISSOND> / <GAMMAD> / <GEND> kind) are carried and written
- * back (round 6); ~u / ~v macros inside multi-stream sets and
- * transforms are rejected with HTKAMD_EMODEL: they do not occur on the path's configurations.
+ * back (round 6); global input transforms (<INPUTXFORM> inline or ~j "name", ~j macros, transform files of their own: GetInputXForm :2373,
+ * GetLinXForm :2195, LoadInputXForm :4640, PutInputXForm :3177, SaveInputXForm :4839) are read, kept and written back; ~u / ~v macros inside
+ * multi-stream sets, <PARENTXFORM> and the other transform macros (~a ~b ~g ~f ~x ~y) are rejected with HTKAMD_EMODEL.
  */
 #include <ctype.h>
 #include <math.h>
@@ -60,6 +61,10 @@ struct htkamd_mmf {
    float *icov; int capIcov, fullc, sawVar, sawInv;
    char *tmName[8]; int tmM[8];                                     /* per stream: generic ~m macro name and pool size (tmRecs[s].mixId / nMix) */
    int *gPend; int capPend, lastVecN;                                         /* a ~m macro of a multi-stream set read before its stream is known: its width, values at [0..width) of the row */
+   /* input transforms (GetInputXForm HModel.c:2373): the ~j macros met so far, and the set's own (<INPUTXFORM> of the global options:
+      one of jm[], or an inline body that the set owns) */
+   struct htkamd_inputxform **jm; int nJm, capJm;
+   struct htkamd_inputxform *xf; int xfInline;
    int finished, nFiles;
 };
 
@@ -102,6 +107,11 @@ static int rd_next(rd *r)
          "DURATION", "INVDIAGC", "TRANSP", "DPROB", "LLTC", "LLTCOVAR", "PROJSIZE"};
       c = rd_getc(r);
       if (c >= 0 && c < 32) snprintf(r->tok, sizeof(r->tok), "%s", code[c]);
+      else if (c >= 90 && c <= 109) {                /* the transform symbols (enum Symbol HModel.c:403-406) */
+         static const char *const xcode[20] = {"XFORMKIND", "PARENTXFORM", "NUMXFORMS", "XFORMSET", "LINXFORM", "OFFSET", "BIAS", "LOGDET", "BLOCKINFO", "BLOCK",
+            "BASECLASS", "CLASS", "XFORMWGTSET", "CLASSXFORM", "MMFIDMASK", "PARAMETERS", "NUMCLASSES", "ADAPTKIND", "PREQUAL", "INPUTXFORM"};
+         snprintf(r->tok, sizeof(r->tok), "%s", xcode[c - 90]);
+      }
       else if (c == 110) snprintf(r->tok, sizeof(r->tok), "RCLASS");
       else if (c == 119) snprintf(r->tok, sizeof(r->tok), "HMMSETID");
       else snprintf(r->tok, sizeof(r->tok), "?BINARY%d", c);
@@ -136,6 +146,16 @@ static int rd_int(rd *r, int *v)
    if (rd_next(r) != T_WORD) return fail(r, "integer expected");
    *v = (int)strtol(r->tok, &e, 10);
    return *e ? fail(r, "integer expected") : HTKAMD_OK;
+}
+static int rd_int32(rd *r, int *v)
+{
+   if (r->bin && !r->pushed) {                       /* ReadInt, big-endian (HShell.c:1465) */
+      unsigned int u = 0;
+      for (int i = 0; i < 4; i++) { const int c = getc_unlocked(r->f); if (c == EOF) return fail(r, "unexpected end of binary data"); u = (u << 8) | (unsigned int)c; }
+      *v = (int)u;
+      return HTKAMD_OK;
+   }
+   return rd_int(r, v);
 }
 /* Decimal text -> the correctly rounded float without strtof for the numbers model files are made of ([-]d.dddddde[+-]dd, up to 15
    digits): digits as an integer m < 2^53, then m * 10^k or m / 10^k with k <= 22 -- both operands exact doubles, so the double is
@@ -209,6 +229,120 @@ static int is_parm_kind(const char *t)
    return 0;
 }
 
+
+/* ------------------------------------------------------------------------------------------ input transforms */
+void htkamd_inputxform_free(struct htkamd_inputxform *x)
+{
+   if (!x) return;
+   free(x->name); free(x->mask); free(x->bias); free(x->mat);
+   free(x);
+}
+/* GetInputXForm (HModel.c:2373) + GetLinXForm (:2195) + GetBias (:2156) + GetTransform (:1540); the <MMFIDMASK> keyword has been read.
+   <MMFIDMASK> mask <kind> [<PREQUAL>] <LINXFORM> <VECSIZE> n [<OFFSET> <BIAS> n v..] [<LOGDET> x] <BLOCKINFO> nb b1.. <BLOCK> i <XFORM> r c v..
+   Sizes in <VECSIZE>, <BLOCKINFO> and <BLOCK> are ints (four bytes in binary), those of <BIAS> and <XFORM> shorts. */
+static int parse_inputxform_body(rd *r, char *name, struct htkamd_inputxform **out)
+{
+   int rc, k, nb, b;
+   struct htkamd_inputxform *x = (struct htkamd_inputxform *)calloc(1, sizeof(*x));
+   x->name = name;
+#define XBAD(what) do { rc = fail(r, what); goto bad; } while (0)
+   if (rd_next(r) != T_WORD) XBAD("<MMFIDMASK>: mask expected");
+   x->mask = strdup(r->tok);
+   if (rd_next(r) != T_KEY || !is_parm_kind(r->tok)) XBAD("input transform: parameter kind symbol expected");
+   snprintf(x->kind, sizeof(x->kind), "%.63s", r->tok);
+   k = rd_next(r);
+   if (k == T_KEY && !strcmp(r->tok, "PREQUAL")) { x->preQual = 1; k = rd_next(r); }
+   if (k != T_KEY || strcmp(r->tok, "LINXFORM")) XBAD("input transform: <LINXFORM> symbol expected");
+   k = rd_next(r);
+   if (k == T_MACRO && r->tok[0] == 'f') XBAD("~f macros (shared linear transforms) are not supported");
+   if (k != T_KEY || strcmp(r->tok, "VECSIZE")) XBAD("input transform: <VECSIZE> symbol expected");
+   if ((rc = rd_int32(r, &x->vecSize))) goto bad;
+   k = rd_next(r);
+   if (k == T_KEY && !strcmp(r->tok, "OFFSET")) {
+      k = rd_next(r);
+      if (k == T_MACRO && r->tok[0] == 'y') XBAD("~y macros (shared bias vectors) are not supported");
+      if (k != T_KEY || strcmp(r->tok, "BIAS")) XBAD("input transform: <BIAS> symbol expected");
+      if ((rc = rd_int(r, &x->nBias))) goto bad;
+      if (x->nBias < 1 || x->nBias > 4096) XBAD("input transform: bad size of the bias vector");
+      x->bias = (float *)malloc(sizeof(float) * (size_t)x->nBias);
+      for (int i = 0; i < x->nBias; i++) if ((rc = rd_float(r, x->bias + i))) goto bad;
+      k = rd_next(r);
+   }
+   if (k == T_KEY && !strcmp(r->tok, "LOGDET")) { if ((rc = rd_float(r, &x->det))) goto bad; k = rd_next(r); }
+   if (k != T_KEY || strcmp(r->tok, "BLOCKINFO")) XBAD("input transform: <BLOCKINFO> symbol expected");
+   if ((rc = rd_int32(r, &nb))) goto bad;
+   if (nb != 1) XBAD("input transform: only full linear transforms are supported (<BLOCKINFO> must name one block)");      /* SetInputXFormConfig HParm.c:631 */
+   if ((rc = rd_int32(r, &x->blockSize))) goto bad;
+   if (rd_next(r) != T_KEY || strcmp(r->tok, "BLOCK")) XBAD("input transform: <BLOCK> symbol expected");
+   if ((rc = rd_int32(r, &b))) goto bad;
+   if (b != 1) XBAD("input transform: inconsistency in transform definition (<BLOCK> index)");
+   k = rd_next(r);
+   if (k == T_MACRO && r->tok[0] == 'x') XBAD("~x macros (shared transform matrices) are not supported");
+   if (k != T_KEY || strcmp(r->tok, "XFORM")) XBAD("input transform: <XFORM> symbol expected");
+   if ((rc = rd_int(r, &x->mrows)) || (rc = rd_int(r, &x->mcols))) goto bad;
+   if (x->mrows < 1 || x->mcols < 1 || x->mrows > 4096 || x->mcols > 4096) XBAD("input transform: bad size of the <XFORM> matrix");
+   x->mat = (float *)malloc(sizeof(float) * (size_t)x->mrows * (size_t)x->mcols);
+   for (size_t i = 0; i < (size_t)x->mrows * (size_t)x->mcols; i++) if ((rc = rd_float(r, x->mat + i))) goto bad;
+   k = rd_next(r);
+   if (k == T_KEY && !strcmp(r->tok, "VARIANCE")) XBAD("input transform: a variance floor inside a transform (semi-tied) is not supported");
+   rd_push(r);
+#undef XBAD
+   *out = x;
+   return HTKAMD_OK;
+bad:
+   htkamd_inputxform_free(x);
+   return rc;
+}
+
+static struct htkamd_inputxform *find_jmacro(const struct htkamd_mmf *s, const char *name)
+{
+   for (int i = 0; i < s->nJm; i++) if (!strcmp(s->jm[i]->name, name)) return s->jm[i];
+   return NULL;
+}
+static void add_jmacro(struct htkamd_mmf *s, struct htkamd_inputxform *x)
+{
+   GROW(s->jm, s->nJm, s->capJm, 1, struct htkamd_inputxform *);
+   s->jm[s->nJm++] = x;
+}
+static int inputxform_read_file(const char *path, const char *wantName, struct htkamd_inputxform **out);
+
+/* <INPUTXFORM> of the global options (GetOption HModel.c:639-653): ~j "name" -- a macro read before, else a file of that name
+   (LoadInputXForm :4640; looked for as given and beside the file being read) -- or the body inline */
+static int parse_inputxform_option(struct htkamd_mmf *s, rd *r)
+{
+   int rc, k = rd_next(r);
+   struct htkamd_inputxform *x = NULL;
+   if (k == T_MACRO && r->tok[0] == 'j') {
+      char *nm;
+      if ((rc = rd_name(r, &nm))) return rc;
+      x = find_jmacro(s, nm);
+      if (!x) {
+         char path[1400];
+         const char *slash = strrchr(r->path, '/');
+         FILE *probe = fopen(nm, "rb");
+         if (probe) snprintf(path, sizeof(path), "%s", nm);
+         else if (slash) { snprintf(path, sizeof(path), "%.*s/%s", (int)(slash - r->path), r->path, nm); probe = fopen(path, "rb"); }
+         if (!probe) {
+            htkamd_set_error("%s:%d: <INPUTXFORM>: undefined ~j macro \"%s\", and no file of that name", r->path, r->line, nm);
+            free(nm); return HTKAMD_EMODEL;
+         }
+         fclose(probe);
+         if ((rc = inputxform_read_file(path, nm, &x))) { free(nm); return rc; }
+         add_jmacro(s, x);
+      }
+      free(nm);
+      if (s->xfInline) htkamd_inputxform_free(s->xf);
+      s->xf = x; s->xfInline = 0;
+      return HTKAMD_OK;
+   }
+   if (k == T_MACRO) return fail(r, "<INPUTXFORM>: ~j macro or <MMFIDMASK> expected");
+   if (k != T_KEY || strcmp(r->tok, "MMFIDMASK")) return fail(r, "<MMFIDMASK> symbol expected in the input transform");
+   if ((rc = parse_inputxform_body(r, strdup(r->path), &x))) return rc;      /* an inline transform is known by the name of its file (:650) */
+   if (s->xfInline) htkamd_inputxform_free(s->xf);
+   s->xf = x; s->xfInline = 1;
+   return HTKAMD_OK;
+}
+
 /* ------------------------------------------------------------------------------------------ grammar */
 static int parse_options(struct htkamd_mmf *s, rd *r)
 {
@@ -247,7 +381,9 @@ static int parse_options(struct htkamd_mmf *s, rd *r)
       else if (is_parm_kind(t)) {
          if (s->kind[0] && strcmp(s->kind, t)) return fail(r, "inconsistent parameter kind");
          snprintf(s->kind, sizeof(s->kind), "%.63s", t);
-      } else if (!strcmp(t, "PROJSIZE") || !strcmp(t, "INPUTXFORM") || !strcmp(t, "PARENTXFORM") || !strcmp(t, "MSDINFO") ||
+      } else if (!strcmp(t, "INPUTXFORM")) {
+         if ((rc = parse_inputxform_option(s, r))) return rc;
+      } else if (!strcmp(t, "PROJSIZE") || !strcmp(t, "PARENTXFORM") || !strcmp(t, "MSDINFO") ||
                  !strcmp(t, "DISCRETE") || !strcmp(t, "DPROB")) {
          return fail(r, "unsupported global option");
       } else { rd_push(r); return HTKAMD_OK; }      /* structural keyword: the caller's business */
@@ -817,6 +953,12 @@ int htkamd_mmf_read(struct htkamd_mmf *s, const char *path, const char *defName)
          if (rc) { free(name); break; }
          s->wm[s->nWm].name = name;
          s->nWm++;
+      } else if (type == 'j') {                              /* ~j "name" <MMFIDMASK> ...: an input transform as a macro */
+         struct htkamd_inputxform *x;
+         if (find_jmacro(s, name)) { rc = fail(&r, "~j macro defined twice"); free(name); break; }
+         if (rd_next(&r) != T_KEY || strcmp(r.tok, "MMFIDMASK")) { rc = fail(&r, "<MMFIDMASK> symbol expected in the input transform"); free(name); break; }
+         if ((rc = parse_inputxform_body(&r, name, &x))) break;
+         add_jmacro(s, x);
       } else if (type == 'i') { rc = fail(&r, "~i (shared inverse covariance) macros are not supported"); free(name); break; }
       else { rc = fail(&r, "unsupported macro type"); free(name); break; }
    }
@@ -1015,6 +1157,9 @@ void htkamd_mmf_destroy(struct htkamd_mmf *s)
    for (int i = 0; i < s->nDm; i++) { free(s->dm[i].name); free(s->dm[i].v); }
    free(s->dm);
    free(s->vm); free(s->gMeanMac); free(s->gVarMac);
+   if (s->xfInline) htkamd_inputxform_free(s->xf);
+   for (int i = 0; i < s->nJm; i++) htkamd_inputxform_free(s->jm[i]);
+   free(s->jm);
    free(s->stateCompOff); free(s->transN); free(s->transOff); free(s->hmmTrans); free(s->hmmStateOff); free(s->hmmState);
    free(s);
 }
@@ -1101,6 +1246,31 @@ static void put_name(FILE *f, char type, const char *name)
    fprintf(f, "\"");
    put_nl(f);
 }
+static void put_int32(FILE *f, int v) { if (g_bin) { fputc((v >> 24) & 255, f); fputc((v >> 16) & 255, f); fputc((v >> 8) & 255, f); fputc(v & 255, f); } else fprintf(f, " %d", v); }
+/* PutInputXForm (HModel.c:3177) + PutLinXForm (:3116) + PutBias (:2820) + PutTransform (:2800), the body without a macro header */
+static void put_inputxform(FILE *f, const struct htkamd_inputxform *x)
+{
+   put_sym(f, "MMFIDMASK", 104);
+   fprintf(f, " %s <%s>", x->mask, x->kind);                         /* mask and kind are text even in binary files */
+   if (x->preQual) put_sym(f, "PREQUAL", 108);
+   put_nl(f);
+   put_sym(f, "LINXFORM", 94);
+   put_sym(f, "VECSIZE", 6); put_int32(f, x->vecSize); put_nl(f);
+   if (x->bias) {
+      put_sym(f, "OFFSET", 95); put_nl(f);
+      put_sym(f, "BIAS", 96); put_short(f, x->nBias); put_nl(f);
+      for (int i = 0; i < x->nBias; i++) put_float(f, x->bias[i]);
+      put_nl(f);
+   }
+   if (x->det != 0) { put_sym(f, "LOGDET", 97); put_float(f, x->det); put_nl(f); }
+   put_sym(f, "BLOCKINFO", 98); put_int32(f, 1); put_int32(f, x->blockSize); put_nl(f);
+   put_sym(f, "BLOCK", 99); put_int32(f, 1); put_nl(f);
+   put_sym(f, "XFORM", 23); put_short(f, x->mrows); put_short(f, x->mcols); put_nl(f);
+   for (int i = 0; i < x->mrows; i++) {
+      for (int j = 0; j < x->mcols; j++) put_float(f, x->mat[(size_t)i * x->mcols + j]);
+      put_nl(f);
+   }
+}
 static void put_options(const struct htkamd_mmf *s, FILE *f)
 {
    fprintf(f, "~o\n");
@@ -1113,6 +1283,8 @@ static void put_options(const struct htkamd_mmf *s, FILE *f)
    put_sym(f, s->dur, !strcmp(s->dur, "POISSOND") ? 8 : !strcmp(s->dur, "GAMMAD") ? 9 : !strcmp(s->dur, "RELD") ? 10 : !strcmp(s->dur, "GEND") ? 11 : 7);      /* NULLD unless the set says otherwise */
    fprintf(f, "<%s><%s>", s->kind[0] ? s->kind : "USER", s->cov);      /* parameter and covariance kinds are text even in binary files */
    put_nl(f);
+   if (s->xf) { put_sym(f, "INPUTXFORM", 109); put_inputxform(f, s->xf); }      /* PutOptions HModel.c:3257: a transform nobody took through a ~j reference
+      (nUse 0: GetOption :647 does not count its own) is written in full, whichever form it was read in */
 }
 static void put_vec(FILE *f, const char *key, int code, const float *v, int n)
 {
@@ -1401,6 +1573,98 @@ int htkamd_mmf_write_sources_full(const struct htkamd_mmf *s, const float *mean,
    const int rc = htkamd_mmf_write_sources(s, mean, invCov, gconst, compWeight, transP, masterOut, nMaster, dir, binary);
    g_icov = NULL;
    return rc;
+}
+
+
+/* ------------------------------------------------------------------------------------------ input transforms: files of their own, accessors, checks */
+/* LoadInputXForm without a model set (HModel.c:4652-4682): the macro header ~j "name" may be missing; wantName != NULL: it must agree */
+static int inputxform_read_file(const char *path, const char *wantName, struct htkamd_inputxform **out)
+{
+   rd r; memset(&r, 0, sizeof(r));
+   r.f = fopen(path, "rb"); r.path = path; r.line = 1;
+   if (!r.f) { htkamd_set_error("inputxform_read: cannot open %s", path); return HTKAMD_EIO; }
+   int rc = HTKAMD_OK, k = rd_next(&r);
+   char *name = NULL;
+   if (k == T_MACRO) {
+      if (r.tok[0] != 'j') rc = fail(&r, "only an input transform (~j) can be read without a model set");
+      else if (!(rc = rd_name(&r, &name))) {
+         if (wantName && strcmp(name, wantName)) { rc = fail(&r, "inconsistent macro names"); free(name); name = NULL; }
+         else k = rd_next(&r);
+      }
+   } else name = strdup(wantName ? wantName : path);
+   if (!rc && (k != T_KEY || strcmp(r.tok, "MMFIDMASK"))) { rc = fail(&r, "<MMFIDMASK> symbol expected in the input transform"); free(name); }
+   if (!rc) rc = parse_inputxform_body(&r, name, out);
+   fclose(r.f);
+   return rc;
+}
+int htkamd_inputxform_read(const char *path, struct htkamd_inputxform **out)
+{
+   if (!path || !out) { htkamd_set_error("inputxform_read: NULL argument"); return HTKAMD_EINVAL; }
+   *out = NULL;
+   return inputxform_read_file(path, NULL, out);
+}
+/* SaveInputXForm (HModel.c:4839) */
+int htkamd_inputxform_write(const struct htkamd_inputxform *x, const char *path, int binary)
+{
+   if (!x || !path) { htkamd_set_error("inputxform_write: NULL argument"); return HTKAMD_EINVAL; }
+   FILE *f = fopen(path, "wb");
+   if (!f) { htkamd_set_error("inputxform_write: cannot create %s", path); return HTKAMD_EIO; }
+   g_bin = binary ? 1 : 0;
+   put_name(f, 'j', x->name);
+   put_inputxform(f, x);
+   g_bin = 0;
+   if (fclose(f)) { htkamd_set_error("inputxform_write: write error on %s", path); return HTKAMD_EIO; }
+   return HTKAMD_OK;
+}
+const struct htkamd_inputxform *htkamd_mmf_inputxform(const struct htkamd_mmf *s) { return s ? s->xf : NULL; }
+const char *htkamd_mmf_set_id(const struct htkamd_mmf *s) { return s ? s->setId : NULL; }
+int htkamd_mmf_vec_size(const struct htkamd_mmf *s) { return s ? s->vecSize : 0; }
+const char *htkamd_inputxform_name(const struct htkamd_inputxform *x) { return x ? x->name : NULL; }
+const char *htkamd_inputxform_mask(const struct htkamd_inputxform *x) { return x ? x->mask : NULL; }
+const char *htkamd_inputxform_parm_kind(const struct htkamd_inputxform *x) { return x ? x->kind : NULL; }
+int htkamd_inputxform_prequal(const struct htkamd_inputxform *x) { return x ? x->preQual : 0; }
+int htkamd_inputxform_rows(const struct htkamd_inputxform *x) { return x ? x->mrows : 0; }
+int htkamd_inputxform_cols(const struct htkamd_inputxform *x) { return x ? x->mcols : 0; }
+const float *htkamd_inputxform_matrix(const struct htkamd_inputxform *x) { return x ? x->mat : NULL; }
+int htkamd_inputxform_vec_size(const struct htkamd_inputxform *x) { return x ? x->vecSize : 0; }
+const float *htkamd_inputxform_bias(const struct htkamd_inputxform *x, int *n) { if (n) *n = x ? x->nBias : 0; return x ? x->bias : NULL; }
+float htkamd_inputxform_logdet(const struct htkamd_inputxform *x) { return x ? x->det : 0.0f; }
+
+/* The checks the reference makes where it applies a transform.  srcKind: the kind of the rows the qualifiers start from (a parameter file's,
+   or what a waveform was coded as); targetKind: the kind asked for; nStat: the width of those rows. */
+int htkamd_inputxform_check(const struct htkamd_inputxform *x, int srcKind, int targetKind, int nStat, const char *setId, int vecSize)
+{
+   const int BASE = 077, E = 0100, N = 0200, D = 0400, A = 01000, Z = 04000, C0 = 020000, T = 0100000;
+   char a[64], b[64], cap[256];
+   if (!x) { htkamd_set_error("inputxform_check: NULL transform"); return HTKAMD_EINVAL; }
+   const int mat = htkamd_parm_kind_parse(x->kind);
+   if (mat < 0 || srcKind < 0 || targetKind < 0 || nStat < 1) { htkamd_set_error("inputxform_check: bad argument"); return HTKAMD_EINVAL; }
+   if ((srcKind | targetKind) & N) { htkamd_set_error("input transform: _N in the source or target kind is not supported"); return HTKAMD_EINVAL; }
+   if (srcKind & (D | A | T)) { htkamd_set_error("input transform: the source rows already carry differentials"); return HTKAMD_EINVAL; }
+   const int nDiff = 1 + ((targetKind & D) ? 1 : 0) + ((targetKind & A) ? 1 : 0) + ((targetKind & T) ? 1 : 0);
+   const int cur = srcKind | (targetKind & (D | A | T | Z));          /* the kind of the rows once the qualifiers are in place */
+   htkamd_parm_kind_str(mat, b, sizeof(b));
+   if (((mat & BASE) & (srcKind & BASE)) != (mat & BASE) || ((mat & E) != 0) != ((srcKind & E) != 0) || ((mat & C0) != 0) != ((srcKind & C0) != 0)) {      /* HParm.c:1636-1642 */
+      htkamd_parm_kind_str(srcKind, a, sizeof(a));
+      htkamd_set_error("input transform: its parameter kind %s does not fit the data's %s (base kind, _E and _0 must agree)", b, a); return HTKAMD_EINVAL;
+   }
+   if (x->preQual && ((mat & Z) != 0) != ((srcKind & Z) != 0)) {     /* HParm.c:1646 */
+      htkamd_parm_kind_str(srcKind, a, sizeof(a));
+      htkamd_set_error("input transform: <PREQUAL> kind %s and the data's %s disagree in _Z", b, a); return HTKAMD_EINVAL;
+   }
+   if (!x->preQual && mat != cur) {                                   /* HParm.c:1835 */
+      htkamd_parm_kind_str(cur, a, sizeof(a));
+      htkamd_set_error("input transform: its parameter kind %s is not the qualified data's %s", b, a); return HTKAMD_EINVAL;
+   }
+   const int width = x->preQual ? nStat : nStat * nDiff;
+   if (x->mcols != width) { htkamd_set_error("input transform: %d matrix columns for rows of %d values", x->mcols, width); return HTKAMD_EINVAL; }     /* HParm.c:1256 */
+   const int produced = x->preQual ? x->mrows * nDiff : x->mrows;     /* HParm.c:2199-2208 */
+   if (vecSize > 0 && vecSize != produced) { htkamd_set_error("input transform: the set's <VECSIZE> %d differs from the %d values the transform produces", vecSize, produced); return HTKAMD_EINVAL; }
+   if (setId && setId[0]) {                                           /* HParm.c:691 */
+      const int m = htkamd_mask_match(x->mask, setId, cap, sizeof(cap));
+      if (m <= 0) { htkamd_set_error("input transform: HMM set %s is not compatible with <MMFIDMASK> %s", setId, x->mask); return HTKAMD_EINVAL; }
+   }
+   return HTKAMD_OK;
 }
 
 /* HCompV's variance floor macro file (PutVFloor, HCompV.c:359-389): one stream. */

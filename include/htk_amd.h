@@ -191,8 +191,9 @@ int  htkamd_model_get_prepared(htkamd_model *m, float *ivar /*[G*D]*/, float *gc
 /* ------------------------------------------------------------------------------------------
  * Model definition files: replaces LoadHMMSet (HModel.c:3809) = MakeHMMSet (:3580) + LoadMacroFiles (:3721) with the
  * -d directory search, and SaveHMMSet (:4979) / SaveInOneFile (:4858), for text definitions of one-stream DIAGC or FULLC
- * continuous-density sets, text or binary (macros ~o ~s ~t ~m ~h ~v"varFloor"; ~u/~v sharing inside a pdf, streams, durations and
- * transforms are rejected with HTKAMD_EMODEL).  Pure host code.
+ * continuous-density sets, text or binary (macros ~o ~s ~t ~m ~h ~v"varFloor"; ~u/~v sharing inside a pdf, streams and durations as
+ * described with their accessors; <INPUTXFORM> and ~j input transforms: see "Global linear input transforms" below; <PARENTXFORM> and
+ * the other transform macros are rejected with HTKAMD_EMODEL).  Pure host code.
  *   mmf_read    : one master macro file, or one HMM file (a definition without ~h takes `defName` / the file's base name)
  *   mmf_finish  : HMM list "logical [physical]" (NULL: every defined model is its own logical name); physical models still
  *                 undefined are read from dir/name[.ext]; builds the flat description for htkamd_model_create.
@@ -964,8 +965,8 @@ int  htkamd_frontend_compute_grid(htkamd_frontend *f, const short *dWav, const i
  * (HParm.c:4375); variance scaling needs no _Z.  With _N in the target the reference applies the side vectors while the energy column
  * is still in the row (it leaves when an observation is extracted, HParm.c:2882): a caller with _N normalises a table qualified without
  * nullECol and drops the column itself; the command-line drivers refuse _N together with side normalisation.
- * Not served: MATTRANFN and the side `~j` input transforms (ApplyStaticMat, sideXForm), USEOLDXFORMCVN, HIGHDIFF, and buffer mode
- * (htkamd_parm_stream_* keeps refusing _Z).
+ * Not served: side transforms (SIDEXFORMMASK, sideXForm), USEOLDXFORMCVN, HIGHDIFF, side normalisation together with an input
+ * transform (below), and buffer mode (htkamd_parm_stream_* keeps refusing _Z).
  * ------------------------------------------------------------------------------------------ */
 int  htkamd_mask_match(const char *mask, const char *name, char *out, int outLen);
 int  htkamd_parm_kind_parse(const char *str);
@@ -981,6 +982,79 @@ int  htkamd_side_stats(const float *dX, const int *frameOff /*[nUtt+1]*/, const 
                        double *sum /*[nSide x D]*/, double *sqsum, long long *nFrames /*[nSide]*/, void *stream);
 int  htkamd_parm_normalise(float *dX, const int *frameOff, const int *uttSide, int nUtt, int nSide, int nCols,
                            const float *mean, int dMean, const float *scale, int dScale, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Global linear input transforms (HLDA and other projections): <INPUTXFORM> of a model set's global options -- the body inline, or
+ * ~j "name", a ~j macro of the loaded files or else a file of that name (looked for as given, then beside the file that names it) --,
+ * ~j macro definitions in a model file, and transform files of their own (what HParm's MATTRANFN names).  Reader and writer restate
+ * GetInputXForm / GetLinXForm / LoadInputXForm and PutInputXForm / PutLinXForm / SaveInputXForm (HModel.c:2373, :2195, :4640, :3177,
+ * :3116, :4839), text and binary.  The body:
+ *   <MMFIDMASK> mask <kind> [<PREQUAL>] <LINXFORM> <VECSIZE> n [<OFFSET> <BIAS> n ..] [<LOGDET> x] <BLOCKINFO> 1 b <BLOCK> 1 <XFORM> r c ..
+ * An <OFFSET> bias and a <LOGDET> are carried and written back; applying the transform uses the matrix alone (ApplyStaticMat
+ * HParm.c:1235).  More than one block is HTKAMD_EMODEL (SetInputXFormConfig HParm.c:631), and so are ~f ~x ~y references inside a
+ * transform; <PARENTXFORM>, ~a ~b ~g ~f macros and side transforms stay refused.  htkamd_mmf_write* put the set's transform back
+ * behind the global options, in full, as SaveHMMSet does for a transform read either way (PutOptions HModel.c:3257).
+ *
+ *   htkamd_mmf_inputxform        the set's transform, owned by the set, or NULL;   htkamd_mmf_set_id: <HMMSETID> ("" without);
+ *                                htkamd_mmf_vec_size: <VECSIZE>.
+ *   htkamd_inputxform_read       a transform file, with or without its ~j "name" header (without: known by the file's name); the handle
+ *                                is released with htkamd_inputxform_free.   htkamd_inputxform_write: SaveInputXForm.
+ *   htkamd_inputxform_name .. _logdet   macro name (an inline transform: the file it stood in), <MMFIDMASK>, parameter kind, <PREQUAL>,
+ *                                matrix rows, columns and the row-major matrix [rows x cols]; <VECSIZE>, bias (NULL without), <LOGDET>.
+ *   htkamd_inputxform_check      what the reference checks where it applies a transform, each with its own message (HTKAMD_EINVAL):
+ *                                the transform's kind against the data's (base kind, _E and _0; with <PREQUAL> also _Z of the source
+ *                                rows, HParm.c:1636-1647; without, the whole kind of the qualified rows, :1835); the matrix columns
+ *                                against the width of the rows it meets (:1256); the set's <VECSIZE> (0: not checked) against what the
+ *                                transform produces -- its rows, with <PREQUAL> rows x (1 + differentials present), :2199-2208 --; and
+ *                                <MMFIDMASK> against <HMMSETID> (NULL or "": not checked, :691).  srcKind: kind of the rows the
+ *                                qualifiers start from, nStat their width; kinds as htkamd_parm_kind_parse gives them.  _N is refused.
+ * On the device (csrc/inputxform.hip; HTKAMD_ENODEV without one, after the arguments were checked):
+ *   htkamd_parm_xform            row r of dOut holds, in its first mrows columns, M . dIn[r][0..mcols): each output starts at 0.0f, then
+ *                                acc = acc + (M[j][m] * x[m]) for m = 0 .. mcols-1, product and sum each rounded to float (no fused
+ *                                multiply-add, subnormals kept): the reference's bits.  Columns of dIn beyond mcols are ignored, columns
+ *                                of dOut beyond mrows are left untouched.  dOut == dIn is allowed when inCols == outCols; otherwise the
+ *                                tables must not overlap.  dMat [mrows x mcols] row-major on the device.  mrows or mcols above 128 is
+ *                                refused with HTKAMD_EINVAL (there is no slower path).  Asynchronous on `stream`.
+ *   htkamd_inputxform_apply      the whole qualifier step of a transformed set in the reference's order (AddQualifiers HParm.c:1636-1844,
+ *                                USEOLDXFORMCVN unset), so that no caller re-derives it: dStatic [F x q->nStat] -> dOut
+ *                                [F x htkamd_inputxform_apply_cols(x, q)].  q describes the qualifiers as for a set without a transform
+ *                                (nZeroMean by the usual rule, HParm.c:1712-1715).  Without <PREQUAL>: htkamd_parm_qualify, then the
+ *                                transform over the whole qualified row; the row becomes mrows wide.  With <PREQUAL>: the transform over
+ *                                the statics, then htkamd_parm_qualify on mrows statics, and _Z (q->nZeroMean > 0) takes the mean off
+ *                                every one of them (the reference's "do everything" rule, HParm.c:1716-1720).  q->nullECol >= 0 (_N) is
+ *                                refused.  Synchronises `stream`.
+ * Not served: side transforms (SIDEXFORMMASK), <PARENTXFORM>, USEOLDXFORMCVN, HIGHDIFF, an input transform together with side
+ * normalisation (CMEAN* / VARSCALE*: the command-line drivers refuse that combination before they touch a device), and source rows that
+ * already carry _D _A _T (the reference applies a transform without <PREQUAL> to files qualified beforehand, HParm.c:1633;
+ * htkamd_inputxform_check refuses them: qualifiers are appended here, on the device, never found in the files).
+ * ~j macros nobody names: a ~j macro of the loaded files that is not the set's <INPUTXFORM> is read and dropped by htkamd_mmf_write*, and
+ * the set's own is written inline, not as a macro -- both as the reference does (SaveMacros HModel.c:4350 writes a ~j macro only when a
+ * ~j reference inside a structure has counted it, and <INPUTXFORM> ~j "name" is no such reference, :647): HHEd's re-save of a set with a
+ * used and an unused ~j macro holds neither definition (tests/golden/make_inputxform_golden.py).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct htkamd_inputxform htkamd_inputxform;
+const htkamd_inputxform *htkamd_mmf_inputxform(const htkamd_mmf *s);
+const char *htkamd_mmf_set_id(const htkamd_mmf *s);
+int  htkamd_mmf_vec_size(const htkamd_mmf *s);
+int  htkamd_inputxform_read(const char *path, htkamd_inputxform **out);
+int  htkamd_inputxform_write(const htkamd_inputxform *x, const char *path, int binary);
+void htkamd_inputxform_free(htkamd_inputxform *x);
+const char *htkamd_inputxform_name(const htkamd_inputxform *x);
+const char *htkamd_inputxform_mask(const htkamd_inputxform *x);
+const char *htkamd_inputxform_parm_kind(const htkamd_inputxform *x);
+int  htkamd_inputxform_prequal(const htkamd_inputxform *x);
+int  htkamd_inputxform_rows(const htkamd_inputxform *x);
+int  htkamd_inputxform_cols(const htkamd_inputxform *x);
+const float *htkamd_inputxform_matrix(const htkamd_inputxform *x);
+int  htkamd_inputxform_vec_size(const htkamd_inputxform *x);
+const float *htkamd_inputxform_bias(const htkamd_inputxform *x, int *n);
+float htkamd_inputxform_logdet(const htkamd_inputxform *x);
+int  htkamd_inputxform_check(const htkamd_inputxform *x, int srcKind, int targetKind, int nStat, const char *setId, int vecSize);
+int  htkamd_parm_xform(const float *dIn, int inCols, float *dOut, int outCols, long long nRows,
+                       const float *dMat /* [mrows x mcols], row-major, device */, int mrows, int mcols, void *stream);
+int  htkamd_inputxform_apply_cols(const htkamd_inputxform *x, const htkamd_parm_quals *q);
+int  htkamd_inputxform_apply(const htkamd_inputxform *x, const float *dStatic, const int *frameOff, int nUtt,
+                             const htkamd_parm_quals *q, float *dOut, void *stream);
 
 #ifdef __cplusplus
 }

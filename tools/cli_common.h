@@ -304,6 +304,36 @@ static void normalise_sides(const strlist *files, int first, int count, int targ
    free(keys.v); free(uttSide); free(mean); free(var); free(scale); free((void *)names);
 }
 
+/* ---- the input transform of the model set (<INPUTXFORM>, inline or ~j): ApplyStaticMat, HParm.c:1235 ----
+ * The drivers honour the transform of the set they load (the configuration variable MATTRANFN stays ignored): load_observations hands the
+ * qualifier step to htkamd_inputxform_apply, which runs transform and qualifiers in the reference's order.  Together with side
+ * normalisation (CMEAN* / VARSCALE*) a transformed set is refused: that combination is not served. */
+static const htkamd_inputxform *g_inputXf;
+static const char *g_inputXfSetId;
+static int g_inputXfVecSize;
+static void use_input_xform(const htkamd_mmf *mmf)
+{
+   g_inputXf = htkamd_mmf_inputxform(mmf); g_inputXfSetId = htkamd_mmf_set_id(mmf); g_inputXfVecSize = htkamd_mmf_vec_size(mmf);
+}
+static void refuse_xform_with_side_norm(const config *cfg, const htkamd_mmf *mmf)
+{
+   if (htkamd_mmf_inputxform(mmf) && (side_mean_set(cfg) || side_var_set(cfg)))
+      DIE("a model set with an input transform (INPUTXFORM) together with side normalisation (CMEAN* / VARSCALE*) is not supported");
+}
+/* The same before a device is touched: with side normalisation configured the model files are read once more on the host alone, only to
+   see whether the set carries a transform.  A set that cannot be read is the business of the load proper, with its own message. */
+static void check_input_xform(const config *cfg, const strlist *mmfs, const char *hmmList, const char *hmmDir, const char *hmmExt)
+{
+   if (!side_mean_set(cfg) && !side_var_set(cfg)) return;
+   htkamd_mmf *m;
+   if (htkamd_mmf_create(&m)) return;
+   int rc = 0;
+   for (int i = 0; i < mmfs->n && !rc; i++) rc = htkamd_mmf_read(m, mmfs->v[i], NULL);
+   if (!rc) rc = htkamd_mmf_finish(m, hmmList, hmmDir, hmmExt);
+   if (!rc) refuse_xform_with_side_norm(cfg, m);
+   htkamd_mmf_destroy(m);
+}
+
 static void load_observations(const strlist *files, int first, int count, int targetKind, const config *cfg, obs_batch *ob)
 {
    float *stat = NULL; size_t cap = 0;
@@ -334,6 +364,21 @@ static void load_observations(const strlist *files, int first, int count, int ta
       CHECK(htkamd_dev_malloc((void **)&dStat, sizeof(float) * (size_t)(F ? F : 1) * nStat));
       CHECK(htkamd_memcpy_h2d(dStat, stat, sizeof(float) * (size_t)F * nStat, NULL));
       free(stat);
+   }
+   if (g_inputXf) {                                        /* a transformed set: the checks of HParm.c:1636-1647, :1835, :1256, :2199-2208, :691, then the whole step */
+      if (htkamd_inputxform_check(g_inputXf, fileKind, targetKind, nStat, g_inputXfSetId, g_inputXfVecSize)) DIE("%s", htkamd_last_error());
+      htkamd_parm_quals q; memset(&q, 0, sizeof(q));
+      const int nE = ((fileKind & PK_HASENERGY) ? 1 : 0) + ((fileKind & PK_HASZEROC) ? 1 : 0);
+      q.nStat = nStat; q.nullECol = -1;
+      q.hasD = (targetKind & PK_HASDELTA) != 0; q.hasA = (targetKind & PK_HASACCS) != 0; q.hasT = (targetKind & PK_HASTHIRD) != 0;
+      q.delWin = cfg_int(cfg, "DELTAWINDOW", 2); q.accWin = cfg_int(cfg, "ACCWINDOW", 2); q.thirdWin = cfg_int(cfg, "THIRDWINDOW", 2);
+      q.nZeroMean = (add & PK_HASZEROM) ? nStat - nE + ((targetKind & PK_HASZEROC) ? 1 : 0) : 0;                 /* HParm.c:1712-1715 */
+      q.v1Compat = cfg_bool(cfg, "V1COMPAT", 0); q.simpleDiffs = cfg_bool(cfg, "SIMPLEDIFFS", 0);
+      ob->cols = htkamd_inputxform_apply_cols(g_inputXf, &q);
+      CHECK(htkamd_dev_malloc((void **)&ob->dX, sizeof(float) * (size_t)(F ? F : 1) * ob->cols));
+      CHECK(htkamd_inputxform_apply(g_inputXf, dStat, ob->frameOff, count, &q, ob->dX, NULL));
+      CHECK(htkamd_dev_free(dStat));
+      return;
    }
    /* a side mean takes the place of the utterance's own (HParm.c:1709-1741, :4375): _Z asked for, not in the files, CMEANDIR / CMEANMASK set */
    const int sideMean = side_mean_set(cfg) && (add & PK_HASZEROM);

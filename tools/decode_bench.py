@@ -39,6 +39,7 @@ def main():
             f.write("J=%d S=%d E=%d l=0.00\n" % (j, 2 + i, V + 2)); j += 1
         f.write("J=%d S=%d E=%d l=0.00\n" % (j, V + 2, V + 3))
     mmf = capi.Mmf(files=[os.path.join(d, "MMF")], hmm_list=os.path.join(d, "hmmlist"))
+    mmf.refuse_input_xform("decode_bench")
     net = capi.Net(os.path.join(d, "net.slf"), os.path.join(d, "dict"), mmf)
     print("setup %.1f s; nodes %d links %d" % (time.time() - t0, net.desc.nNodes, net.desc.nLinks))
     dec = capi.Decoder(model, net)

@@ -157,6 +157,7 @@ int main(int argc, char **argv)
    if (waveform_source(&cfg) && cfg_get(&cfg, "TARGETKIND")) check_waveform_kind(kind_parse(cfg_get(&cfg, "TARGETKIND")));
    if (waveform_source(&cfg)) check_waveform_warp(&cfg);
    check_side_norm(&cfg);
+   check_input_xform(&cfg, &mmfs, hmmList, hmmDir, hmmExt);
    if (htkamd_device_count() <= 0) DIE("herest: no HIP device (the MI355X path has no CPU fallback)");
    CHECK(htkamd_set_device(nRanks > 1 ? rank % htkamd_device_count() : 0));
 
@@ -165,6 +166,8 @@ int main(int argc, char **argv)
    htkamd_mmf *mmf; CHECK(htkamd_mmf_create(&mmf));
    for (int i = 0; i < mmfs.n; i++) CHECK(htkamd_mmf_read(mmf, mmfs.v[i], NULL));
    CHECK(htkamd_mmf_finish(mmf, hmmList, hmmDir, hmmExt));
+   refuse_xform_with_side_norm(&cfg, mmf);
+   use_input_xform(mmf);
    const htkamd_model_desc *d = htkamd_mmf_desc(mmf);
    const int D = d->vecSize, H = d->numPhys;
    if (htkamd_mmf_inv_cov(mmf)) DIE("herest: re-estimation of FULLC (<INVCOVAR>) sets is not supported");

@@ -216,11 +216,14 @@ int main(int argc, char **argv)
    if (waveform_source(&cfg) && cfg_get(&cfg, "TARGETKIND")) check_waveform_kind(kind_parse(cfg_get(&cfg, "TARGETKIND")));
    if (waveform_source(&cfg)) check_waveform_warp(&cfg);
    check_side_norm(&cfg);
+   check_input_xform(&cfg, &mmfs, hmmList, hmmDir, hmmExt);
    if (htkamd_device_count() <= 0) DIE("hvite: no HIP device (the MI355X path has no CPU fallback)");
 
    htkamd_mmf *mmf; CHECK(htkamd_mmf_create(&mmf));
    for (int i = 0; i < mmfs.n; i++) CHECK(htkamd_mmf_read(mmf, mmfs.v[i], NULL));
    CHECK(htkamd_mmf_finish(mmf, hmmList, hmmDir, hmmExt));
+   refuse_xform_with_side_norm(&cfg, mmf);
+   use_input_xform(mmf);
    const htkamd_model_desc *d = htkamd_mmf_desc(mmf);
    const int D = d->vecSize;
    htkamd_model *model;
