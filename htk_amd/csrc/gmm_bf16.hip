@@ -585,12 +585,7 @@ __global__ __launch_bounds__(256, b16w_eu(KS)) void k_score_bf16w(ScoreArgs a)
 int htkamd_launch_score_bf16(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart, hipEvent_t evStop)
 {
    if (a.nTasks <= 0) return HTKAMD_OK;
-   if (!m->d_bf16Tab) { htkamd_set_error("score_bf16: vector size %d not supported by the bf16 matrix-core path (up to 45)", m->D); return HTKAMD_EMODEL; }
-   if (m->bf16Stale) {                               // parameters were re-estimated on the device since the table was built (and this path was not in use then)
-      int rc = htkamd_model_refresh_bf16_device((htkamd_model *)m, (void *)stream);
-      if (rc) return rc;
-   }
-   ((htkamd_model *)m)->fastUse |= HTKAMD_SCORE_BF16;
+   { const int rc = htkamd_model_table_current(m, HTKAMD_SCORE_BF16, stream); if (rc) return rc; }
    if (a.qCounters == a.taskCounter + 8) HIPCHECK(hipMemsetAsync(a.taskCounter, 0, 16 * sizeof(int), stream));      // the counter and the eight queues' behind it: one fill
    else {
       HIPCHECK(hipMemsetAsync(a.taskCounter, 0, sizeof(int), stream));
@@ -787,6 +782,5 @@ int htkamd_model_refresh_bf16_device(htkamd_model *m, void *stream)
    else if (m->f16Wide) hipLaunchKernelGGL(k_build_bf16tab<true>, dim3((n + 255) / 256), dim3(256), 0, s, t, m->nTiles);
    else hipLaunchKernelGGL(k_build_bf16tab<false>, dim3((n + 255) / 256), dim3(256), 0, s, t, m->nTiles);
    HIPCHECK(hipGetLastError());
-   m->bf16Stale = 0;
    return HTKAMD_OK;
 }

@@ -442,12 +442,7 @@ __global__ __launch_bounds__(256, F16W_EU) void k_score_f16w(ScoreArgs a)
 int htkamd_launch_score_f16(const htkamd_model *m, const ScoreArgs &a0, hipStream_t stream, hipEvent_t evStart, hipEvent_t evStop)
 {
    if (a0.nTasks <= 0) return HTKAMD_OK;
-   if (!m->d_f16Tab) { htkamd_set_error("score_f16: vector size %d not supported by the fp16 matrix-core path (up to 45)", m->D); return HTKAMD_EMODEL; }
-   if (m->f16Stale) {                                // parameters were re-estimated on the device since the table was built (and this path was not in use then)
-      int rc = htkamd_model_refresh_f16_device((htkamd_model *)m, (void *)stream);
-      if (rc) return rc;
-   }
-   ((htkamd_model *)m)->fastUse |= HTKAMD_SCORE_F16;
+   { const int rc = htkamd_model_table_current(m, HTKAMD_SCORE_F16, stream); if (rc) return rc; }
    ScoreArgs a = a0;
    a.f16Tab = m->d_f16Tab; a.f16Ctl = (const int *)m->d_f16Ctl;
    if (!a.rangeFlag) a.rangeFlag = (int *)m->d_f16Ctl + F16_CTL_STICKY;      // the model's sticky flag
@@ -633,7 +628,6 @@ int htkamd_model_refresh_f16_device(htkamd_model *m, void *stream)
       else hipLaunchKernelGGL(k_build_f16tab<false>, dim3(m->nTiles), dim3(64 * m->bf16NC), 0, s, t, m->nTiles);
    }
    HIPCHECK(hipGetLastError());
-   m->f16Stale = 0;
    return HTKAMD_OK;
 }
 

@@ -15,7 +15,7 @@
 // (128 frames x up to 16 chain states); each wave owns 32 of the frames (two column tiles of 16) and all four walk
 // the task's states together.  The GAUSSIANS are the rows of the product and the FRAMES its columns:
 //   A[row = lane&15][k = lane>>4] : the state's 16 components -- host-built fragment table [tile][step][lane]
-//       (model.hip mfma_refresh).  One copy per workgroup, staged global -> registers -> LDS a tile ahead of use
+//       (update.hip k_upd_mfma).  One copy per workgroup, staged global -> registers -> LDS a tile ahead of use
 //       (double buffer, one barrier per tile), read by all four waves: parameter traffic per 128 frames, not per wave.
 //   B[k = lane>>4][col = lane&15] : the wave's frames.  K index 4*s+kq carries dimension 2*s+(kq>>1), as x^2 for
 //       even kq and x for odd kq: ceil(D/2) registers per column tile, loaded once per task (2*20 VGPRs at D=39).
@@ -188,11 +188,7 @@ __global__ __launch_bounds__(256, 4) void k_score_mfma(ScoreArgs a)
 int htkamd_launch_score_mfma(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart, hipEvent_t evStop)
 {
    if (a.nTasks <= 0) return HTKAMD_OK;
-   if (!m->d_mfmaTab) { htkamd_set_error("score_mfma: vector size %d not supported by the MFMA path (up to 40)", m->D); return HTKAMD_EMODEL; }
-   if (m->mfmaStale) {                             // parameters were re-estimated on the device since the table was built
-      int rcr = htkamd_model_refresh_mfma_device(const_cast<htkamd_model *>(m), stream);
-      if (rcr) return rcr;
-   }
+   { const int rc = htkamd_model_table_current(m, HTKAMD_SCORE_MFMA, stream); if (rc) return rc; }
    HIPCHECK(hipMemsetAsync(a.taskCounter, 0, sizeof(int), stream));
    int blocks = a.nTasks;
    if (blocks > 256 * 4) blocks = 256 * 4;      // persistent blocks (4 per CU at <= 128 VGPRs), one task (128 frames x 16 states) at a time

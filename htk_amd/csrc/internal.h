@@ -109,14 +109,16 @@ struct htkamd_model {
    int   *d_stateTileOff;      /* [S+1] */
    int   *d_tileState;         /* [nTiles] tied state of every fragment tile */
    int    mfmaNS, nTiles;
-   int    mfmaStale;           /* the fp32 fragment table is older than the parameters (device update): rebuilt on its next use */
    void  *d_bf16Tab;           /* bf16 x 3 scoring path (gmm_bf16.hip): A-operand pieces per tile; NULL when D > 45 */
    int    bf16NC;              /* K chunks of 32 per piece: ceil(D/15) */
    int    bf16Dense;           /* the 32 x 32 bf16 kernel's five-k-step layout (31 <= D <= 39, every state in one tile): gmm_bf16.hip, k_score_bf16w<5> */
    void  *d_f16Tab;            /* fp16 x 2 scoring path (gmm_f16.hip): A-operand pieces per tile, K chunks as the bf16 path; NULL when D > 45 */
    int    f16Wide;             /* every state fits one tile (<= 16 components): the 32 x 32 form of the kernel and its table layout */
    float *d_f16Ctl;            /* its control block: scale[96], 1/scale[96], range[192], flag of the last table build, sticky range flag */
-   int    bf16Stale, f16Stale; /* the table is older than the parameters (a device update while the path was not in use): rebuilt on its next use */
+   /* freshness of the three derived tables above (model.hip: htkamd_model_params_changed, htkamd_model_table_current).  The rule: after
+      a change of the parameters on the device, the tables of the paths that have scored are rebuilt on the update's stream; every
+      other table is rebuilt on its next use, on the scoring call's stream */
+   int    tabStale;            /* HTKAMD_SCORE_MFMA / _BF16 / _F16 bits: the path's table is older than the parameters */
    int    compat;              /* HTKAMD_COMPAT_* bits (htkamd_model_set_compat) */
    unsigned char *h_rawLogWt, *d_rawLogWt;   /* [C] HTKAMD_COMPAT_SHARED_LOGWT: the component's weight is read as a LOG weight as it stands (ConvLogWt skipped it), or NULL */
    int    fastUse;             /* HTKAMD_SCORE_BF16 / _F16 bits: the paths that have scored with this model (their tables follow every device update) */
@@ -147,9 +149,16 @@ struct htkamd_model {
 };
 
 void htkamd_outp_ring_free(void *ring);                      /* gmm_exact.hip */
+/* the builders of the derived tables, each the only one of its table (stream: hipStream_t); called through the two functions below */
 int htkamd_model_refresh_mfma_device(struct htkamd_model *m, void *stream);   /* update.hip */
-int htkamd_model_refresh_bf16_device(struct htkamd_model *m, void *stream);   /* gmm_bf16.hip (stream: hipStream_t) */
+int htkamd_model_refresh_bf16_device(struct htkamd_model *m, void *stream);   /* gmm_bf16.hip */
 int htkamd_model_refresh_f16_device(struct htkamd_model *m, void *stream);    /* gmm_f16.hip */
+/* model.hip.  The parameters on the device changed: every derived table is stale; fromDevice (a device update): those of the paths in
+   fastUse are rebuilt on `stream` and the host copies are stale; otherwise (the host pushed them) all are rebuilt and waited for */
+__attribute__((visibility("hidden"))) int htkamd_model_params_changed(struct htkamd_model *m, void *stream, int fromDevice);
+/* the head of a matrix-core launcher: refuses a vector size the path (one HTKAMD_SCORE_* bit) has no table for, rebuilds its table on
+   `stream` if it is stale and notes the path in fastUse */
+__attribute__((visibility("hidden"))) int htkamd_model_table_current(const struct htkamd_model *m, int path, void *stream);
 int htkamd_model_f16_flag(struct htkamd_model *m, void *stream, int *flag);   /* gmm_f16.hip: the sticky range flag, read and cleared */
 /* range flag of the fp16 path (ScoreArgs::rangeFlag) */
 #define HTKAMD_F16_EMODEL 1    /* a scaled coefficient of the model exceeds fp16's range */

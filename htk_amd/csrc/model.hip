@@ -128,92 +128,142 @@ template <typename T> static T *dupHost(const T *src, size_t n)
    return p;
 }
 
-template <typename T> static int toDevice(T **dst, const T *src, size_t n)
+// Every array of the model, once: its host field, its device field (NOF: none), the element size and the count as a function of the
+// model's sizes.  The loops over this list free, upload and read back; a new array needs its line here, its fill and its use.
+// AR_PARAM: a re-estimated parameter -- pushed by model_refresh, read back by htkamd_model_sync_host after a device update.
+// AR_UPD: the device copy serves the device update and the DIAGC form alone (htkamd_model_device_tables uploads it on first use).
+enum { AR_PARAM = 1, AR_UPD = 2 };
+struct ModelArray { size_t h, d, elem; size_t (*count)(const htkamd_model *); int flags; };
+#define NOF ((size_t)-1)
+#define OF(f) offsetof(htkamd_model, f)
+#define CNT(expr) [](const htkamd_model *m) -> size_t { return (size_t)(expr); }
+#define TABLE_BYTES(pieces) ((size_t)m->nTiles * ((size_t)(pieces) * m->bf16NC * 64 * 16 + 64 * 16))      /* bf16 x 3, fp16 x 2 (gmm_bf16.hip) */
+static const ModelArray MODEL_ARRAYS[] = {
+   {OF(h_stateCompOff), OF(d_stateCompOff), sizeof(int), CNT(m->S + 1), 0},
+   {OF(h_compGauss), OF(d_compGauss), sizeof(int), CNT(m->C), 0},
+   {OF(h_transN), OF(d_transN), sizeof(int), CNT(m->nT), 0},
+   {OF(h_transOff), OF(d_transOff), sizeof(int), CNT(m->nT + 1), 0},
+   {OF(h_trOccOff), OF(d_trOccOff), sizeof(int), CNT(m->nT + 1), AR_UPD},
+   {OF(h_hmmTrans), OF(d_hmmTrans), sizeof(int), CNT(m->H), AR_UPD},
+   {OF(h_hmmStateOff), OF(d_hmmStateOff), sizeof(int), CNT(m->H + 1), AR_UPD},
+   {OF(h_hmmState), OF(d_hmmState), sizeof(int), CNT(m->h_hmmStateOff[m->H]), AR_UPD},
+   {OF(h_minDur), NOF, sizeof(int), CNT(m->nT), 0},
+   {OF(h_transLR), NOF, 1, CNT(m->nT), 0},
+   {OF(h_mean), OF(d_mean), sizeof(float), CNT((size_t)m->G * m->D), AR_PARAM},
+   {OF(h_var), OF(d_var), sizeof(float), CNT((size_t)m->G * m->D), AR_PARAM | AR_UPD},
+   {OF(h_ivar), OF(d_ivar), sizeof(float), CNT((size_t)m->G * m->D), AR_PARAM},
+   {OF(h_gconst), OF(d_gconst), sizeof(float), CNT(m->G), AR_PARAM},
+   {OF(h_compWeight), OF(d_compWeight), sizeof(float), CNT(m->C), AR_PARAM | AR_UPD},
+   {OF(h_compLogWt), OF(d_compLogWt), sizeof(float), CNT(m->C), AR_PARAM},
+   {OF(h_transP), OF(d_transP), sizeof(float), CNT(m->h_transOff[m->nT]), 0},      // (the device side has 16 counters behind it: model_refresh)
+   {OF(h_rawLogWt), OF(d_rawLogWt), 1, CNT(m->C), 0},
+   {OF(h_meanLeader), NOF, sizeof(int), CNT(m->G), 0},
+   {OF(h_varLeader), NOF, sizeof(int), CNT(m->G), 0},
+   {OF(h_varGroupSize), NOF, sizeof(int), CNT(m->G), 0},
+   {OF(h_dimStream), OF(d_dimStream), sizeof(int), CNT(m->D), 0},
+   {OF(h_gaussStream), OF(d_gaussStream), sizeof(int), CNT(m->G), 0},
+   {OF(h_tmPoolOff), OF(d_tmPoolOff), sizeof(int), CNT(m->NSt + 1), 0},
+   {OF(h_streamWt), OF(d_streamWt), sizeof(float), CNT(m->S), 0},
+   {OF(h_scanOrder), NOF, sizeof(int), CNT(m->H), 0},
+   {OF(h_invCov), NOF, sizeof(float), CNT((size_t)m->G * htkamd_tri_size(m->D)), 0},
+   {NOF, OF(d_gparam), sizeof(float), CNT((size_t)m->G * m->PS), 0},
+   {NOF, OF(d_fparam), sizeof(float), CNT((size_t)m->G * m->FPS), 0},
+   {NOF, OF(d_laddTab), sizeof(double), CNT(htkamd_host_ladd_table_size()), 0},
+   {NOF, OF(d_msCompOff), sizeof(int), CNT(m->S + 1), 0},
+   {NOF, OF(d_shareTab), sizeof(int), CNT(5 * (size_t)m->G + 2 + m->shareMuMem + m->shareVaMem), 0},
+   {NOF, OF(d_stateTileOff), sizeof(int), CNT(m->S + 1), 0},
+   {NOF, OF(d_tileState), sizeof(int), CNT(m->nTiles), 0},
+   {NOF, OF(d_mfmaTab), sizeof(float), CNT((size_t)m->nTiles * (m->mfmaNS + 8) * 64), 0},
+   {NOF, OF(d_bf16Tab), 1, CNT(TABLE_BYTES(3)), 0},
+   {NOF, OF(d_f16Tab), 1, CNT(TABLE_BYTES(2)), 0},
+   {NOF, OF(d_f16Ctl), sizeof(float), CNT(512), 0},
+};
+static void *&field(htkamd_model *m, size_t off) { return *(void **)((char *)m + off); }
+static const ModelArray &array_of(size_t off)           // by its host or device field
 {
-   if (*dst == nullptr) HIPCHECK(hipMalloc((void **)dst, sizeof(T) * (n ? n : 1)));
-   if (n) HIPCHECK(hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice));
+   for (const ModelArray &a : MODEL_ARRAYS) if (a.h == off || a.d == off) return a;
+   abort();
+}
+static size_t array_bytes(const htkamd_model *m, size_t off) { const ModelArray &a = array_of(off); return a.count(m) * a.elem; }
+#define BYTES(m, f) array_bytes(m, OF(f))
+
+// the device side of an array allocated (on first use), and filled from `src` or, src NULL, from its host side
+static int upload(htkamd_model *m, const ModelArray &a, const void *src = nullptr)
+{
+   const size_t n = a.count(m) * a.elem;
+   if (!field(m, a.d)) HIPCHECK(hipMalloc(&field(m, a.d), n ? n : 1));
+   if (!src && a.h != NOF) src = field(m, a.h);
+   if (n && src) HIPCHECK(hipMemcpy(field(m, a.d), src, n, hipMemcpyHostToDevice));
+   return HTKAMD_OK;
+}
+#define UPLOAD(m, f, ...) upload(m, array_of(OF(f)), ##__VA_ARGS__)
+
+// ---- the derived tables of the matrix-core paths: fp32 fragments (gmm_mfma.hip), bf16 x 3 (gmm_bf16.hip), fp16 x 2 (gmm_f16.hip), named
+// by their HTKAMD_SCORE_* bit.  Each has one builder, on the device; a FULLC model has none of them.
+static const struct DerivedTable { int path; size_t tab; int (*build)(htkamd_model *, void *); const char *refusal; } DERIVED[] = {
+   {HTKAMD_SCORE_MFMA, OF(d_mfmaTab), htkamd_model_refresh_mfma_device, "score_mfma: vector size %d not supported by the MFMA path (up to 40)"},
+   {HTKAMD_SCORE_BF16, OF(d_bf16Tab), htkamd_model_refresh_bf16_device, "score_bf16: vector size %d not supported by the bf16 matrix-core path (up to 45)"},
+   {HTKAMD_SCORE_F16, OF(d_f16Tab), htkamd_model_refresh_f16_device, "score_f16: vector size %d not supported by the fp16 matrix-core path (up to 45)"},
+};
+// the paths whose tables follow every device update once they have scored; the fp32 table is always rebuilt on its next use
+static const int FOLLOWING_PATHS = HTKAMD_SCORE_BF16 | HTKAMD_SCORE_F16, ALL_PATHS = HTKAMD_SCORE_MFMA | FOLLOWING_PATHS;
+
+static int rebuild(htkamd_model *m, int paths, void *stream)
+{
+   for (const DerivedTable &t : DERIVED)
+      if (paths & m->tabStale & t.path) {
+         const int rc = t.build(m, stream);
+         if (rc) return rc;
+         m->tabStale &= ~t.path;
+      }
    return HTKAMD_OK;
 }
 
-// A-operand fragment table of the MFMA scoring kernel (layout: gmm_mfma.hip).  Column j of tile t of state s is
-// component stateCompOff[s] + 16*(t - stateTileOff[s]) + j; K index 4*step + kq carries dimension 2*step + (kq>>1),
-// as the x^2 coefficient -0.5*ivar for even kq and the x coefficient mean*ivar for odd kq; rows mfmaNS..mfmaNS+3 are
-// the accumulator start -0.25*sum mean^2*ivar and rows mfmaNS+4..mfmaNS+7 the closing constant log weight - 0.5*gConst -
-// 0.25*sum mean^2*ivar, both in the C-operand layout.  Unused components close at -1e30 (drop out of the sum).
-static int mfma_refresh(htkamd_model *m)
+int htkamd_model_params_changed(htkamd_model *m, void *stream, int fromDevice)
+{
+   m->tabStale = ALL_PATHS;
+   const int rc = rebuild(m, fromDevice ? m->fastUse : ALL_PATHS, stream);
+   if (rc) return rc;
+   if (fromDevice) m->hostStale = 1;
+   else HIPCHECK(hipStreamSynchronize((hipStream_t)stream));
+   return HTKAMD_OK;
+}
+
+int htkamd_model_table_current(const htkamd_model *cm, int path, void *stream)
+{
+   htkamd_model *m = const_cast<htkamd_model *>(cm);      // (a launcher reads the model; bringing a table up to date is the one thing it may change)
+   for (const DerivedTable &t : DERIVED)
+      if (t.path == path && !field(m, t.tab)) { htkamd_set_error(t.refusal, m->D); return HTKAMD_EMODEL; }
+   const int rc = rebuild(m, path, stream);
+   if (rc) return rc;
+   m->fastUse |= path & FOLLOWING_PATHS;
+   return HTKAMD_OK;
+}
+
+// The tile bookkeeping of the derived tables and their memory, once per model: 16 components per tile, a state's tiles one behind the other.
+static int derived_tables_alloc(htkamd_model *m)
 {
    const int D = m->D;
-   if (D > 48) return HTKAMD_OK;                      // no matrix-core kernel: the exact path serves such sets
+   if (D > 48 || m->d_stateTileOff) return HTKAMD_OK;    // D > 48: no matrix-core kernel, the exact path serves such sets
    // fp32 path: K steps of 4 = 2 dimensions each; kernels exist for 7, 13 and 20 steps, smaller sizes are zero-padded up to the next
    const int need = (D + 1) / 2;
-   const int NS = need <= 7 ? 7 : (need <= 13 ? 13 : 20);
-   if (!m->d_stateTileOff) {
-      int *off = (int *)malloc(sizeof(int) * ((size_t)m->S + 1));
-      off[0] = 0;
-      for (int s = 0; s < m->S; s++) off[s + 1] = off[s] + (m->h_stateCompOff[s + 1] - m->h_stateCompOff[s] + 15) / 16;
-      m->nTiles = off[m->S]; m->mfmaNS = NS;
-      int rc = toDevice(&m->d_stateTileOff, off, (size_t)m->S + 1);
-      if (!rc) {
-         int *ts = (int *)malloc(sizeof(int) * (size_t)(m->nTiles ? m->nTiles : 1));
-         for (int s = 0; s < m->S; s++) for (int t = off[s]; t < off[s + 1]; t++) ts[t] = s;
-         rc = toDevice(&m->d_tileState, ts, (size_t)m->nTiles);
-         free(ts);
-      }
-      free(off);
-      if (rc) return rc;
-      m->bf16NC = (D + 14) / 15;                      // 15 dimensions as (x^2, x) pairs + the chunk's constant per K chunk of 32 (gmm_bf16.hip)
-      if (m->bf16NC <= 3) {
-         HIPCHECK(hipMalloc(&m->d_bf16Tab, (size_t)m->nTiles * ((size_t)3 * m->bf16NC * 64 * 16 + 64 * 16)));
-         m->f16Wide = m->nTiles == m->S;
-         m->bf16Dense = m->f16Wide && D >= 31 && D <= 39;
-         HIPCHECK(hipMalloc(&m->d_f16Tab, (size_t)m->nTiles * ((size_t)2 * m->bf16NC * 64 * 16 + 64 * 16)));
-         HIPCHECK(hipMalloc(&m->d_f16Ctl, sizeof(float) * 512));
-         HIPCHECK(hipMemset(m->d_f16Ctl, 0, sizeof(float) * 512));
-      }
-   }
-   {  // bf16 x 3 and fp16 x 2 paths: their tables are built on the device from the tables just uploaded
-      int rcb = htkamd_model_refresh_bf16_device(m, nullptr);
-      if (!rcb) rcb = htkamd_model_refresh_f16_device(m, nullptr);
-      if (rcb) return rcb;
-      HIPCHECK(hipStreamSynchronize(nullptr));
-   }
-   if (D > 40) return HTKAMD_OK;
-   const size_t stride = (size_t)(NS + 8) * 64;
-   float *tab = (float *)calloc((size_t)m->nTiles * stride, sizeof(float));
-   size_t t = 0;
+   m->mfmaNS = need <= 7 ? 7 : (need <= 13 ? 13 : 20);
+   std::vector<int> off((size_t)m->S + 1), ts;
    for (int s = 0; s < m->S; s++) {
-      const int c0 = m->h_stateCompOff[s], c1 = m->h_stateCompOff[s + 1];
-      for (int cb = c0; cb < c1; cb += 16, t++) {
-         float *T = tab + t * stride;
-         for (int col = 0; col < 16; col++) {
-            const int c = cb + col;
-            const bool live = c < c1 && (c1 - c0 == 1 || m->h_compLogWt[c] > (float)LMINMIX);
-            // accumulator start of row `col`: lane (kq = col/4, any column) register col%4, i.e. table row NS + col%4
-            float *ciRow = T + (size_t)(NS + (col & 3)) * 64 + (col >> 2) * 16, *endRow = ciRow + 4 * 64;
-            if (!live) { for (int j = 0; j < 16; j++) { ciRow[j] = 0.0f; endRow[j] = -1.0e30f; } continue; }
-            const int g = m->h_compGauss[c];
-            const float *mu = m->h_mean + (size_t)g * D, *iv = m->h_ivar + (size_t)g * D;
-            double q = 0.0;
-            for (int i = 0; i < D; i++) q += (double)mu[i] * mu[i] * iv[i];
-            const double L2E = 1.4426950408889634;           // table in base-2 logarithms (gmm_mfma.hip)
-            // the accumulators start at half of -0.5 sum mu^2 ivar; the rest is added after the contraction (gmm_mfma.hip)
-            const float ci = (float)(-0.25 * q * L2E);
-            const float ce = (float)(((c1 - c0 == 1 ? 0.0 : (double)m->h_compLogWt[c]) - 0.5 * (double)m->h_gconst[g] - 0.25 * q) * L2E);
-            for (int j = 0; j < 16; j++) { ciRow[j] = ci; endRow[j] = ce; }
-            for (int st = 0; st < NS; st++)
-               for (int kq = 0; kq < 4; kq++) {
-                  const int dim = 2 * st + (kq >> 1);
-                  float v = 0.0f;
-                  if (dim < D) v = (kq & 1) ? (float)((double)mu[dim] * iv[dim] * L2E) : (float)(-0.5 * (double)iv[dim] * L2E);
-                  T[(size_t)st * 64 + kq * 16 + col] = v;
-               }
-         }
-      }
+      off[s + 1] = off[s] + (m->h_stateCompOff[s + 1] - m->h_stateCompOff[s] + 15) / 16;
+      for (int t = off[s]; t < off[s + 1]; t++) ts.push_back(s);
    }
-   int rc = toDevice(&m->d_mfmaTab, tab, (size_t)m->nTiles * stride);
-   free(tab);
-   m->mfmaStale = 0;
-   return rc;
+   m->nTiles = off[m->S];
+   int rc;
+   if ((rc = UPLOAD(m, d_stateTileOff, off.data())) || (rc = UPLOAD(m, d_tileState, ts.data()))) return rc;
+   m->bf16NC = (D + 14) / 15;                         // 15 dimensions as (x^2, x) pairs + the chunk's constant per K chunk of 32 (gmm_bf16.hip)
+   if (m->bf16NC <= 3) {                              // D <= 45
+      m->f16Wide = m->nTiles == m->S;
+      m->bf16Dense = m->f16Wide && D >= 31 && D <= 39;
+      if ((rc = UPLOAD(m, d_bf16Tab)) || (rc = UPLOAD(m, d_f16Tab)) || (rc = UPLOAD(m, d_f16Ctl))) return rc;
+      HIPCHECK(hipMemset(m->d_f16Ctl, 0, BYTES(m, d_f16Ctl)));
+   }
+   return D > 40 ? HTKAMD_OK : UPLOAD(m, d_mfmaTab);     // (the fp32 kernels go up to 20 K steps)
 }
 
 // The exact FULLC scorer's parameter table (gmm_full.hip): per Gaussian mean[D], the packed triangle, gConst, zeros up to FPS.
@@ -229,7 +279,7 @@ static int fullc_refresh(htkamd_model *m)
       memcpy(p + D, m->h_invCov + (size_t)g * TRI, sizeof(float) * TRI);
       p[D + TRI] = m->h_gconst[g];
    }
-   const int rc = toDevice(&m->d_fparam, fp, (size_t)m->G * FPS);
+   const int rc = UPLOAD(m, d_fparam, fp);
    free(fp);
    return rc;
 }
@@ -261,29 +311,26 @@ static int model_refresh(htkamd_model *m, bool derive = true)
       }
       p[2 * D] = m->h_gconst[g];
    }
-   int rc = toDevice(&m->d_gparam, gp, (size_t)m->G * PS);
+   int rc = UPLOAD(m, d_gparam, gp);
    free(gp);
    if (rc) return rc;
-   if ((rc = toDevice(&m->d_mean, m->h_mean, (size_t)m->G * D))) return rc;
-   if ((rc = toDevice(&m->d_ivar, m->h_ivar, (size_t)m->G * D))) return rc;
-   if ((rc = toDevice(&m->d_gconst, m->h_gconst, (size_t)m->G))) return rc;
-   if ((rc = toDevice(&m->d_compLogWt, m->h_compLogWt, (size_t)m->C))) return rc;
-   if (!m->d_transP) HIPCHECK(hipMalloc((void **)&m->d_transP, sizeof(float) * ((size_t)m->h_transOff[m->nT] + 16)));      // + the device update's 16 counters: one copy brings both back (update.hip)
-   if ((rc = toDevice(&m->d_transP, m->h_transP, (size_t)m->h_transOff[m->nT]))) return rc;
-   if (m->d_var && ((rc = toDevice(&m->d_var, m->h_var, (size_t)m->G * D)) || (rc = toDevice(&m->d_compWeight, m->h_compWeight, (size_t)m->C)))) return rc;
+   if (!m->d_transP) HIPCHECK(hipMalloc((void **)&m->d_transP, BYTES(m, h_transP) + sizeof(float) * 16));      // + the device update's 16 counters: one copy brings both back (update.hip)
+   if ((rc = UPLOAD(m, h_transP))) return rc;
+   for (const ModelArray &a : MODEL_ARRAYS)
+      if ((a.flags & AR_PARAM) && (!(a.flags & AR_UPD) || m->d_var) && (rc = upload(m, a))) return rc;
    if (m->fullc) return fullc_refresh(m);             // (no matrix-core table: only the exact kernel scores a FULLC set)
-   return mfma_refresh(m);
+   if ((rc = derived_tables_alloc(m))) return rc;
+   return htkamd_model_params_changed(m, nullptr, 0);
 }
 
 // Linear parameters and the model topology on the device, for the device-side update (uploaded on its first call).
 int htkamd_model_device_tables(htkamd_model *m)
 {
    if (m->d_var) return HTKAMD_OK;
-   int rc;
-   if ((rc = toDevice(&m->d_var, m->h_var, (size_t)m->G * m->D)) || (rc = toDevice(&m->d_compWeight, m->h_compWeight, (size_t)m->C)) ||
-       (rc = toDevice(&m->d_trOccOff, m->h_trOccOff, (size_t)m->nT + 1)) || (rc = toDevice(&m->d_hmmTrans, m->h_hmmTrans, (size_t)m->H)) ||
-       (rc = toDevice(&m->d_hmmStateOff, m->h_hmmStateOff, (size_t)m->H + 1)) ||
-       (rc = toDevice(&m->d_hmmState, m->h_hmmState, (size_t)m->h_hmmStateOff[m->H]))) return rc;
+   for (const ModelArray &a : MODEL_ARRAYS) {
+      const int rc = (a.flags & AR_UPD) ? upload(m, a) : HTKAMD_OK;
+      if (rc) return rc;
+   }
    return HTKAMD_OK;
 }
 
@@ -291,12 +338,8 @@ int htkamd_model_device_tables(htkamd_model *m)
 int htkamd_model_sync_host(htkamd_model *m)
 {
    if (!m->hostStale) return HTKAMD_OK;
-   HIPCHECK(hipMemcpy(m->h_mean, m->d_mean, sizeof(float) * (size_t)m->G * m->D, hipMemcpyDeviceToHost));
-   HIPCHECK(hipMemcpy(m->h_var, m->d_var, sizeof(float) * (size_t)m->G * m->D, hipMemcpyDeviceToHost));
-   HIPCHECK(hipMemcpy(m->h_ivar, m->d_ivar, sizeof(float) * (size_t)m->G * m->D, hipMemcpyDeviceToHost));
-   HIPCHECK(hipMemcpy(m->h_gconst, m->d_gconst, sizeof(float) * (size_t)m->G, hipMemcpyDeviceToHost));
-   HIPCHECK(hipMemcpy(m->h_compWeight, m->d_compWeight, sizeof(float) * (size_t)m->C, hipMemcpyDeviceToHost));
-   HIPCHECK(hipMemcpy(m->h_compLogWt, m->d_compLogWt, sizeof(float) * (size_t)m->C, hipMemcpyDeviceToHost));
+   for (const ModelArray &a : MODEL_ARRAYS)
+      if (a.flags & AR_PARAM) HIPCHECK(hipMemcpy(field(m, a.h), field(m, a.d), a.count(m) * a.elem, hipMemcpyDeviceToHost));
    m->hostStale = 0;
    return HTKAMD_OK;
 }
@@ -407,10 +450,7 @@ static int model_create(const htkamd_model_desc *d, const float *invCov, htkamd_
       }
    }
    int rc;
-   if ((rc = toDevice(&m->d_stateCompOff, m->h_stateCompOff, (size_t)m->S + 1)) ||
-       (rc = toDevice(&m->d_compGauss, m->h_compGauss, (size_t)m->C)) ||
-       (rc = toDevice(&m->d_transN, m->h_transN, (size_t)m->nT)) ||
-       (rc = toDevice(&m->d_transOff, m->h_transOff, (size_t)m->nT + 1)) ||
+   if ((rc = UPLOAD(m, d_stateCompOff)) || (rc = UPLOAD(m, d_compGauss)) || (rc = UPLOAD(m, d_transN)) || (rc = UPLOAD(m, d_transOff)) ||
        (rc = model_refresh(m))) {
       htkamd_model_destroy(m); return rc;
    }
@@ -426,20 +466,19 @@ static int model_create(const htkamd_model_desc *d, const float *invCov, htkamd_
          if (!same) { htkamd_set_error("model_create: tied-mixture set: stream %d of state %d does not list its stream's pool", k + 1, e / NSt); htkamd_model_destroy(m); return HTKAMD_EINVAL; }
          if (M < 2) { htkamd_set_error("model_create: tied-mixture set: a pool of one Gaussian"); htkamd_model_destroy(m); return HTKAMD_EINVAL; }
       }
-      if ((rc = toDevice(&m->d_tmPoolOff, m->h_tmPoolOff, (size_t)NSt + 1)) || (rc = htkamd_model_device_tables(m))) { htkamd_model_destroy(m); return rc; }
+      if ((rc = UPLOAD(m, d_tmPoolOff)) || (rc = htkamd_model_device_tables(m))) { htkamd_model_destroy(m); return rc; }
    }
    if (NSt > 1 || m->tiedMix) {
       std::vector<int> two((size_t)m->S + 1);
       for (int e = 0; e <= m->S; e++) two[e] = 2 * e;
-      if ((NSt > 1 && ((rc = toDevice(&m->d_dimStream, m->h_dimStream, (size_t)m->D)) || (rc = toDevice(&m->d_gaussStream, m->h_gaussStream, (size_t)m->G)) ||
-                       (rc = toDevice(&m->d_streamWt, m->h_streamWt, (size_t)m->S)))) ||
-          (rc = toDevice(&m->d_msCompOff, two.data(), (size_t)m->S + 1))) { htkamd_model_destroy(m); return rc; }
+      if ((NSt > 1 && ((rc = UPLOAD(m, d_dimStream)) || (rc = UPLOAD(m, d_gaussStream)) || (rc = UPLOAD(m, d_streamWt)))) ||
+          (rc = UPLOAD(m, d_msCompOff, two.data()))) { htkamd_model_destroy(m); return rc; }
    }
    {
       const int n = htkamd_host_ladd_table_size();
       double *tab = (double *)malloc(sizeof(double) * (size_t)n);
       htkamd_host_build_ladd_table(tab);
-      rc = toDevice(&m->d_laddTab, tab, (size_t)n);
+      rc = UPLOAD(m, d_laddTab, tab);
       free(tab);
       if (rc) { htkamd_model_destroy(m); return rc; }
    }
@@ -450,23 +489,14 @@ static int model_create(const htkamd_model_desc *d, const float *invCov, htkamd_
 extern "C" void htkamd_model_destroy(htkamd_model *m)
 {
    if (!m) return;
-   free(m->h_stateCompOff); free(m->h_compGauss); free(m->h_transN); free(m->h_transOff); free(m->h_hmmTrans);
-   free(m->h_hmmStateOff); free(m->h_hmmState); free(m->h_minDur); free(m->h_transLR); free(m->h_trOccOff); free(m->h_scanOrder);
-   free(m->h_mean); free(m->h_var); free(m->h_ivar); free(m->h_gconst); free(m->h_compWeight); free(m->h_compLogWt); free(m->h_transP);
-   (void)hipFree(m->d_gparam); (void)hipFree(m->d_laddTab); (void)hipFree(m->d_mean); (void)hipFree(m->d_ivar); (void)hipFree(m->d_gconst);
-   (void)hipFree(m->d_compLogWt); (void)hipFree(m->d_transP); (void)hipFree(m->d_stateCompOff); (void)hipFree(m->d_compGauss);
-   (void)hipFree(m->d_transN); (void)hipFree(m->d_transOff); (void)hipFree(m->d_mfmaTab); (void)hipFree(m->d_stateTileOff);
-   (void)hipFree(m->d_bf16Tab); (void)hipFree(m->d_f16Tab); (void)hipFree(m->d_f16Ctl); (void)hipFree(m->d_tileState);
-   (void)hipFree(m->d_var); (void)hipFree(m->d_compWeight); (void)hipFree(m->d_trOccOff); (void)hipFree(m->d_hmmTrans);
-   (void)hipFree(m->d_hmmStateOff); (void)hipFree(m->d_hmmState); (void)hipFree(m->d_updScratch);
+   for (const ModelArray &a : MODEL_ARRAYS) {
+      if (a.h != NOF) free(field(m, a.h));
+      if (a.d != NOF) (void)hipFree(field(m, a.d));
+   }
+   (void)hipFree(m->d_updScratch);
    htkamd_outp_ring_free(m->obRing);
-   free(m->h_meanLeader); free(m->h_varLeader); free(m->h_varGroupSize); (void)hipFree(m->d_shareTab);
    if (m->h_updPin) (void)hipHostFree(m->h_updPin);
    if (m->evUpd) (void)hipEventDestroy((hipEvent_t)m->evUpd);
-   free(m->h_rawLogWt); (void)hipFree(m->d_rawLogWt);
-   free(m->h_tmPoolOff); (void)hipFree(m->d_tmPoolOff); free(m->h_streamWt); (void)hipFree(m->d_streamWt);
-   free(m->h_dimStream); free(m->h_gaussStream); (void)hipFree(m->d_dimStream); (void)hipFree(m->d_gaussStream); (void)hipFree(m->d_msCompOff);
-   free(m->h_invCov); (void)hipFree(m->d_fparam);
    free(m);
 }
 
@@ -489,7 +519,6 @@ extern "C" int htkamd_model_set_scan_order(htkamd_model *m, const int *order)
       int rc = compat_raw_logwt(m);
       if (rc) return rc;
       if ((rc = model_refresh(m))) return rc;
-      m->bf16Stale = 1; m->f16Stale = 1;
    }
    return HTKAMD_OK;
 }
@@ -607,7 +636,6 @@ extern "C" int htkamd_model_set_compat(htkamd_model *m, int flags)
       int rc = compat_raw_logwt(m);
       if (rc) return rc;
       if ((rc = model_refresh(m))) return rc;
-      m->bf16Stale = 1; m->f16Stale = 1;
    }
    return HTKAMD_OK;
 }
@@ -620,13 +648,13 @@ extern "C" int htkamd_model_set_params(htkamd_model *m, const float *mean, const
    if (!m) { htkamd_set_error("model_set_params: NULL model"); return HTKAMD_EINVAL; }
    if (m->fullc && var) { htkamd_set_error("model_set_params: a FULLC model has no variances (htkamd_model_set_inv_cov)"); return HTKAMD_EMODEL; }
    { int rc0 = htkamd_model_sync_host(m); if (rc0) return rc0; }
-   if (mean) memcpy(m->h_mean, mean, sizeof(float) * (size_t)m->G * m->D);
-   if (var) memcpy(m->h_var, var, sizeof(float) * (size_t)m->G * m->D);
-   if (gconst) memcpy(m->h_gconst, gconst, sizeof(float) * (size_t)m->G);
+   if (mean) memcpy(m->h_mean, mean, BYTES(m, h_mean));
+   if (var) memcpy(m->h_var, var, BYTES(m, h_var));
+   if (gconst) memcpy(m->h_gconst, gconst, BYTES(m, h_gconst));
    else if (var)
       for (int g = 0; g < m->G; g++) htkamd_host_fix_diag_gconst_ms(m->D, m->h_var + (size_t)g * m->D, m->h_dimStream, m->h_gaussStream ? m->h_gaussStream[g] : 0, m->h_gconst + g);
-   if (compWeight) memcpy(m->h_compWeight, compWeight, sizeof(float) * (size_t)m->C);
-   if (transP) memcpy(m->h_transP, transP, sizeof(float) * (size_t)m->h_transOff[m->nT]);
+   if (compWeight) memcpy(m->h_compWeight, compWeight, BYTES(m, h_compWeight));
+   if (transP) memcpy(m->h_transP, transP, BYTES(m, h_transP));
    return model_refresh(m);
 }
 
@@ -637,9 +665,9 @@ extern "C" int htkamd_model_set_prepared(htkamd_model *m, const float *ivar, con
    if (!m) { htkamd_set_error("model_set_prepared: NULL model"); return HTKAMD_EINVAL; }
    if (m->fullc) { htkamd_set_error("model_set_prepared: the prepared DIAGC tables do not apply to a FULLC model"); return HTKAMD_EMODEL; }
    { int rc0 = htkamd_model_sync_host(m); if (rc0) return rc0; }
-   if (ivar) memcpy(m->h_ivar, ivar, sizeof(float) * (size_t)m->G * m->D);
-   if (gconst) memcpy(m->h_gconst, gconst, sizeof(float) * (size_t)m->G);
-   if (compLogWt) memcpy(m->h_compLogWt, compLogWt, sizeof(float) * (size_t)m->C);
+   if (ivar) memcpy(m->h_ivar, ivar, BYTES(m, h_ivar));
+   if (gconst) memcpy(m->h_gconst, gconst, BYTES(m, h_gconst));
+   if (compLogWt) memcpy(m->h_compLogWt, compLogWt, BYTES(m, h_compLogWt));
    return model_refresh(m, false);
 }
 
@@ -647,10 +675,10 @@ extern "C" int htkamd_model_get_prepared(htkamd_model *m, float *ivar, float *gc
 {
    if (!m) { htkamd_set_error("model_get_prepared: NULL model"); return HTKAMD_EINVAL; }
    // read back from the DEVICE copies so that tests see what the kernels see
-   if (ivar) HIPCHECK(hipMemcpy(ivar, m->d_ivar, sizeof(float) * (size_t)m->G * m->D, hipMemcpyDeviceToHost));
-   if (gconst) HIPCHECK(hipMemcpy(gconst, m->d_gconst, sizeof(float) * (size_t)m->G, hipMemcpyDeviceToHost));
-   if (compLogWt) HIPCHECK(hipMemcpy(compLogWt, m->d_compLogWt, sizeof(float) * (size_t)m->C, hipMemcpyDeviceToHost));
-   if (minDur) memcpy(minDur, m->h_minDur, sizeof(int) * (size_t)m->nT);
+   if (ivar) HIPCHECK(hipMemcpy(ivar, m->d_ivar, BYTES(m, d_ivar), hipMemcpyDeviceToHost));
+   if (gconst) HIPCHECK(hipMemcpy(gconst, m->d_gconst, BYTES(m, d_gconst), hipMemcpyDeviceToHost));
+   if (compLogWt) HIPCHECK(hipMemcpy(compLogWt, m->d_compLogWt, BYTES(m, d_compLogWt), hipMemcpyDeviceToHost));
+   if (minDur) memcpy(minDur, m->h_minDur, BYTES(m, h_minDur));
    return HTKAMD_OK;
 }
 
@@ -671,11 +699,11 @@ extern "C" int htkamd_model_get_params(htkamd_model *m, float *mean, float *var,
 {
    if (!m) { htkamd_set_error("model_get_params: NULL model"); return HTKAMD_EINVAL; }
    { int rc0 = htkamd_model_sync_host(m); if (rc0) return rc0; }
-   if (mean) memcpy(mean, m->h_mean, sizeof(float) * (size_t)m->G * m->D);
-   if (var) memcpy(var, m->h_var, sizeof(float) * (size_t)m->G * m->D);
-   if (gconst) memcpy(gconst, m->h_gconst, sizeof(float) * (size_t)m->G);
-   if (compWeight) memcpy(compWeight, m->h_compWeight, sizeof(float) * (size_t)m->C);
-   if (transP) memcpy(transP, m->h_transP, sizeof(float) * (size_t)m->h_transOff[m->nT]);
+   if (mean) memcpy(mean, m->h_mean, BYTES(m, h_mean));
+   if (var) memcpy(var, m->h_var, BYTES(m, h_var));
+   if (gconst) memcpy(gconst, m->h_gconst, BYTES(m, h_gconst));
+   if (compWeight) memcpy(compWeight, m->h_compWeight, BYTES(m, h_compWeight));
+   if (transP) memcpy(transP, m->h_transP, BYTES(m, h_transP));
    return HTKAMD_OK;
 }
 
@@ -693,8 +721,8 @@ extern "C" int htkamd_model_set_inv_cov(htkamd_model *m, const float *invCov, co
          free(gc); htkamd_set_error("model_set_inv_cov: the inverse covariance of Gaussian %d is not positive definite (CovDet)", g); return HTKAMD_EMODEL;
       }
    }
-   memcpy(m->h_invCov, invCov, sizeof(float) * (size_t)m->G * TRI);
-   memcpy(m->h_gconst, gc, sizeof(float) * (size_t)m->G);
+   memcpy(m->h_invCov, invCov, BYTES(m, h_invCov));
+   memcpy(m->h_gconst, gc, BYTES(m, h_gconst));
    free(gc);
    return model_refresh(m);
 }
@@ -703,7 +731,7 @@ extern "C" int htkamd_model_get_inv_cov(htkamd_model *m, float *invCov)
 {
    if (!m || !invCov) { htkamd_set_error("model_get_inv_cov: NULL argument"); return HTKAMD_EINVAL; }
    if (!m->fullc) { htkamd_set_error("model_get_inv_cov: not a FULLC model"); return HTKAMD_EMODEL; }
-   memcpy(invCov, m->h_invCov, sizeof(float) * (size_t)m->G * htkamd_tri_size(m->D));
+   memcpy(invCov, m->h_invCov, BYTES(m, h_invCov));
    return HTKAMD_OK;
 }
 

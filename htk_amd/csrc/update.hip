@@ -546,7 +546,12 @@ __global__ __launch_bounds__(128) void k_upd_gconst(UpdArgs a)
    a.gparam[(size_t)g * a.PS + 2 * D] = a.gconst[g];
 }
 
-// A-operand fragment table of gmm_mfma.hip; layout and arithmetic as mfma_refresh() in model.hip
+// A-operand fragment table of the MFMA scoring kernel (layout: gmm_mfma.hip), built here alone.  Column j of tile t of state s is
+// component stateCompOff[s] + 16*(t - stateTileOff[s]) + j; K index 4*step + kq carries dimension 2*step + (kq>>1),
+// as the x^2 coefficient -0.5*ivar for even kq and the x coefficient mean*ivar for odd kq; rows mfmaNS..mfmaNS+3 are
+// the accumulator start -0.25*sum mean^2*ivar and rows mfmaNS+4..mfmaNS+7 the closing constant log weight - 0.5*gConst -
+// 0.25*sum mean^2*ivar, both in the C-operand layout.  Unused components close at -1e30 (drop out of the sum).  The table is in
+// base-2 logarithms; the accumulators start at half of -0.5 sum mu^2 ivar, the rest is added after the contraction (gmm_mfma.hip).
 struct MfmaTabArgs {
    int D, NS, S;
    const int *stateCompOff, *stateTileOff, *compGauss;
@@ -578,7 +583,7 @@ __global__ void k_upd_mfma(MfmaTabArgs a, int nTiles)
    double q = 0.0;
    for (int i = 0; i < D; i++) q += (double)mu[i] * mu[i] * iv[i];
    const double L2E = 1.4426950408889634;
-   const float ci = (float)(-0.25 * q * L2E);          // start and closing constant as in model.hip
+   const float ci = (float)(-0.25 * q * L2E);          // start and closing constant
    const float ce = (float)(((c1 - c0 == 1 ? 0.0 : (double)a.compLogWt[c]) - 0.5 * (double)a.gconst[g] - 0.25 * q) * L2E);
    for (int j = 0; j < 16; j++) { ciRow[j] = ci; endRow[j] = ce; }
    for (int st = 0; st < NS; st++)
@@ -603,7 +608,6 @@ __global__ void k_upd_export(const int *stats, int *dst, const int *blkStats, in
 int htkamd_model_refresh_mfma_device(htkamd_model *m, void *stream)
 {
    hipStream_t s = (hipStream_t)stream;
-   m->mfmaStale = 0;
    if (!m->d_mfmaTab) return HTKAMD_OK;
    MfmaTabArgs t;
    t.D = m->D; t.NS = m->mfmaNS; t.S = m->S; t.stateCompOff = m->d_stateCompOff; t.stateTileOff = m->d_stateTileOff; t.compGauss = m->d_compGauss;
@@ -715,12 +719,7 @@ extern "C" int htkamd_model_update_device_begin(htkamd_model *m, htkamd_accs *ac
       hipLaunchKernelGGL(k_upd_gconst, dim3((m->G + B - 1) / B), dim3(B), ag.logVar ? sizeof(float) * (size_t)B * m->D : 0, s, ag);
    }
    HIPCHECK(hipGetLastError());
-   // the fragment tables of the matrix-core paths that have been scoring with this model now (bf16 x 3, fp16 x 2), the others when
-   // they are next asked for (htkamd_launch_score_mfma / _bf16 / _f16)
-   m->mfmaStale = 1; m->bf16Stale = 1; m->f16Stale = 1;
-   if ((m->fastUse & HTKAMD_SCORE_BF16) && (rc = htkamd_model_refresh_bf16_device(m, s))) return rc;
-   if ((m->fastUse & HTKAMD_SCORE_F16) && (rc = htkamd_model_refresh_f16_device(m, s))) return rc;
-   m->hostStale = 1;
+   if ((rc = htkamd_model_params_changed(m, s, 1))) return rc;
    // the transition matrices are small and the host needs them (minimum durations for CreateInsts, tee flags for the decoder)
    const size_t nTp = (size_t)m->h_transOff[m->nT];
    if (!m->h_updPin) HIPCHECK(hipHostMalloc(&m->h_updPin, sizeof(float) * (nTp + 16), hipHostMallocDefault));
