@@ -1,0 +1,37 @@
+"""Tree-based state tying (HHEd's RO / QS / TB / ST) on the device: the step between cloned single-Gaussian triphones plus an HERest -s
+statistics file and a tied-state set ready for mix-up.
+
+    python examples/tree_cluster.py tree.hed hmmdefs triphones stats -o tied.mmf [--trees trees] [--no-merge] [--no-leaf-stats]
+
+The edit script may hold RO, TR, QS, TB and ST only; any other command is refused by name.  --no-merge / --no-leaf-stats are HHEd's
+configuration variables TREEMERGE = F / USELEAFSTATS = F.  The trees file is what the reference's LT + AU read to synthesise unseen
+triphones (not built here)."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from htk_amd import capi, treeclust
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("script"); ap.add_argument("mmf"); ap.add_argument("hmmlist"); ap.add_argument("stats")
+    ap.add_argument("-o", "--out", required=True, help="the tied model set (one master file)")
+    ap.add_argument("--trees", help="trees file (overrides the script's ST)")
+    ap.add_argument("--no-merge", action="store_true"); ap.add_argument("--no-leaf-stats", action="store_true")
+    a = ap.parse_args(argv)
+    sc = treeclust.parse_script(open(a.script).read())
+    if a.trees:
+        sc.trees_path = os.path.abspath(a.trees)
+    mmf = capi.Mmf([a.mmf], hmm_list=a.hmmlist)
+    before = mmf.desc.numStates
+    warn = treeclust.run_script(mmf, sc, stats_path=a.stats, merge=not a.no_merge, leaf_stats=not a.no_leaf_stats, base_dir=os.path.dirname(os.path.abspath(a.script)))
+    if warn:
+        print(warn, file=sys.stderr)
+    mmf.write(mmf.packed(), one_file=a.out)
+    print("tree_cluster: %d trees, %d states -> %d" % (len(sc.specs), before, mmf.desc.numStates))
+
+
+if __name__ == "__main__":
+    main()

@@ -1010,6 +1010,66 @@ def parm_xform(dIn_ptr, inCols: int, dOut_ptr, outCols: int, nRows: int, dMat_pt
                                   _stream(stream)), "parm_xform")
 
 
+TREE_MERGE, TREE_LEAFSTATS = 1, 2
+
+
+class TreeQuestion(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("patterns", C.POINTER(C.c_char_p)), ("nPatterns", C.c_int)]
+
+
+class TreeSpec(C.Structure):
+    _fields_ = [("threshold", C.c_float), ("macRoot", C.c_char_p), ("itemList", C.c_char_p)]
+
+
+class TreeDesc(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("state", C.c_int), ("nNodes", C.c_int), ("quest", C.POINTER(C.c_int)), ("no", C.POINTER(C.c_int)),
+                ("yes", C.POINTER(C.c_int)), ("leafMacro", C.POINTER(C.c_char_p)), ("nLeaves", C.c_int)]
+
+
+def _tree_questions(questions):
+    keep = []
+    arr = (TreeQuestion * max(len(questions), 1))()
+    for k, (name, pats) in enumerate(questions):
+        pa = (C.c_char_p * max(len(pats), 1))(*[str(x).encode() for x in pats])
+        keep.append(pa)
+        arr[k] = TreeQuestion(str(name).encode(), pa, len(pats))
+    return arr, keep
+
+
+def read_stats(mmf: "Mmf", path: str):
+    """An HERest -s statistics file (htkamd_stats_read_file): (occ float32[numStates], count int32[numPhys])."""
+    occ = np.zeros(max(mmf.desc.numStates, 1), np.float32); cnt = np.zeros(max(mmf.desc.numPhys, 1), np.int32)
+    check(lib().htkamd_stats_read_file(mmf.h, str(path).encode(), _p(occ), _p(cnt)), "stats_read_file")
+    return occ[:mmf.desc.numStates], cnt[:mmf.desc.numPhys]
+
+
+def trees_write(path: str, questions, trees):
+    """An ST trees file (htkamd_trees_write): `trees` = [dict(name, state, quest=[..], no=[..], yes=[..], leaves=[macro, ...])]."""
+    qs, keepq = _tree_questions(questions)
+    keep = []
+    td = (TreeDesc * max(len(trees), 1))()
+    for k, t in enumerate(trees):
+        n = len(t["quest"])
+        a = [(C.c_int * max(n, 1))(*t[key]) for key in ("quest", "no", "yes")]
+        lm = (C.c_char_p * max(len(t["leaves"]), 1))(*[str(x).encode() for x in t["leaves"]])
+        keep.append((a, lm))
+        td[k] = TreeDesc(str(t["name"]).encode(), int(t["state"]), n, a[0], a[1], a[2], lm, len(t["leaves"]))
+    check(lib().htkamd_trees_write(str(path).encode(), qs, C.c_int(len(questions)), td, C.c_int(len(trees))), "trees_write")
+
+
+def tree_split_sums(item_stats, node_items, answers, stream=None) -> np.ndarray:
+    """Test aid (htkamd_tree_split_sums): the yes / no sums of one node on the device, float32[nQ, 2, 2D+1] (no side first)."""
+    st = np.ascontiguousarray(item_stats, np.float32); it = np.ascontiguousarray(node_items, np.int32); an = np.ascontiguousarray(answers, np.uint8)
+    nItems, Cc = st.shape
+    nQ = an.shape[0]
+    if an.shape != (nQ, nItems) or Cc % 2 != 1:
+        raise HtkAmdError("tree_split_sums: bad shapes %s %s" % (st.shape, an.shape))
+    out = np.zeros((nQ, 2, Cc), np.float32)
+    check(lib().htkamd_tree_split_sums(_p(st), C.c_int(nItems), C.c_int((Cc - 1) // 2), _p(it), C.c_int(it.size), _p(an), C.c_int(nQ), _p(out),
+                                       _stream(stream)), "tree_split_sums")
+    return out
+
+
 class Mmf:
     """htkamd_mmf holder: LoadHMMSet / SaveHMMSet for text model definitions (htk_amd/host/mmf.c)."""
 
@@ -1086,6 +1146,37 @@ class Mmf:
         if states is not None:
             sel = np.zeros(self.desc.numStates, np.uint8); sel[list(states)] = 1
         check(lib().htkamd_mmf_mixup(self.h, C.c_int(target), _p(sel) if sel is not None else None), "mmf_mixup")
+
+    def item_list(self, text: str):
+        """An HHEd item list of state items, "{ pat.state[i] }": [(physical model, state number)] in the order of the reference's list."""
+        n = C.c_int(0)
+        check(lib().htkamd_mmf_item_list(self.h, text.encode(), None, None, C.c_int(0), C.byref(n)), "mmf_item_list")
+        ph = np.zeros(max(n.value, 1), np.int32); st = np.zeros(max(n.value, 1), np.int32)
+        check(lib().htkamd_mmf_item_list(self.h, text.encode(), _p(ph), _p(st), C.c_int(n.value), C.byref(n)), "mmf_item_list")
+        return list(zip(ph[:n.value].tolist(), st[:n.value].tolist()))
+
+    def question_answers(self, name: str, patterns) -> np.ndarray:
+        """A QS question's answer per physical model (uint8[numPhys])."""
+        qs, keep = _tree_questions([(name, patterns)])
+        ans = np.zeros(max(self.desc.numPhys, 1), np.uint8)
+        check(lib().htkamd_mmf_question_answers(self.h, qs, _p(ans)), "mmf_question_answers")
+        return ans[:self.desc.numPhys]
+
+    def tree_cluster(self, occ, questions, specs, outlier: float = -1.0, merge: bool = True, leaf_stats: bool = True, trees_path=None, stream=None):
+        """HHEd's RO / QS / TB / ST on the loaded set (htkamd_mmf_tree_cluster): `occ` the state occupations (read_stats), `questions`
+        [(name, [pattern, ...])] in QS order, `specs` [(threshold, macro root, item list)] in TB order.  packed() / write() reflect the
+        tied set afterwards.  Returns the warning the call left (a dropped question) or None."""
+        occ = np.ascontiguousarray(occ, np.float32)
+        if occ.shape != (self.desc.numStates,):
+            raise HtkAmdError("tree_cluster: %s occupations for %d states" % (occ.shape, self.desc.numStates))
+        qs, keepq = _tree_questions(questions)
+        keep = [(str(m).encode(), str(i).encode()) for (_, m, i) in specs]
+        ts = (TreeSpec * max(len(specs), 1))(*[TreeSpec(float(specs[k][0]), keep[k][0], keep[k][1]) for k in range(len(specs))])
+        flags = (TREE_MERGE if merge else 0) | (TREE_LEAFSTATS if leaf_stats else 0)
+        check(lib().htkamd_mmf_tree_cluster(self.h, _p(occ), C.c_float(outlier), qs, C.c_int(len(questions)), ts, C.c_int(len(specs)), C.c_int(flags),
+                                            str(trees_path).encode() if trees_path else None, _stream(stream)), "mmf_tree_cluster")
+        msg = lib().htkamd_last_error().decode()
+        return msg if "warning" in msg else None
 
     def write(self, params: dict, one_file=None, out_dir=None, binary=False):
         g = params.get("gconst")

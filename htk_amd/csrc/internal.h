@@ -32,6 +32,23 @@ void   htkamd_host_fix_diag_gconst_ms(int D, const float *var, const int *dimStr
 int    htkamd_host_trans_is_lr(int N, const float *tp);                        /* left-to-right, no skips (fb_lr.hip) */
 double htkamd_host_min_log_exp(void);                                          /* HMath.c:1680 */
 
+/* ---- decision-tree clustering: the device side (csrc/treeclust.hip) as host/treeclust.c drives it ----
+ * A node is its item list: idx[offA .. offA+nA), then idx[offB .. offB+nB) (nB > 0: "list a, then list b" of a merge candidate).
+ * C = 2D+1 floats per accumulator: occ, sum[D], sqr[D].  htkamd_tree_dev_split leaves every node's [nQ+1][2][C] block (question q: no
+ * side, yes side; the last entry is "no question" = the node's total on the no side) on the device and returns one record per node:
+ *   rec[0] = number of candidate questions (an int; more than HTKAMD_TREE_MAXCAND: fetch the block with htkamd_tree_dev_block),
+ *   rec[1 .. MAXCAND] = their numbers in question order (ints), then the total [C], then the candidates' [2][C] sums. */
+#define HTKAMD_TREE_MAXCAND 8
+#define HTKAMD_TREE_REC(C) (1 + HTKAMD_TREE_MAXCAND + (C) + HTKAMD_TREE_MAXCAND * 2 * (C))
+typedef struct { int offA, nA, offB, nB; } htkamd_tree_node;
+typedef struct htkamd_tree_dev htkamd_tree_dev;
+int  htkamd_tree_dev_open(htkamd_tree_dev **out, const float *itemStats, int nItems, int D, const int *itemCol /*[nItems] or NULL = the item itself*/,
+                          const unsigned char *answers /*[nQ][nCols]*/, int nCols, int nQ, void *stream);
+int  htkamd_tree_dev_split(htkamd_tree_dev *t, const htkamd_tree_node *nodes, int nNodes, const int *idx, int nIdx, float outlierThresh, int *rec /*[nNodes][HTKAMD_TREE_REC(C)]*/);
+int  htkamd_tree_dev_totals(htkamd_tree_dev *t, const htkamd_tree_node *nodes, int nNodes, const int *idx, int nIdx, float *tot /*[nNodes][C]*/);
+int  htkamd_tree_dev_block(htkamd_tree_dev *t, int node, float *blk /*[nQ+1][2][C]*/);      /* of the last htkamd_tree_dev_split */
+void htkamd_tree_dev_close(htkamd_tree_dev *t);
+
 /* device LAdd table: 4 intervals per unit of d over [minLogExp, 0] = [-23.03, 0], degree-10 Taylor rows (8 KB) */
 #define LADD_INV_H 4
 #define LADD_DEG   10

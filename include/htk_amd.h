@@ -207,6 +207,38 @@ int  htkamd_mmf_create(htkamd_mmf **out);
    state with stateSel[state] != 0 (NULL = all) goes to `target` components, or gains -target if target < 0; afterwards
    htkamd_mmf_desc / htkamd_mmf_write reflect the new set.  The step between single-Gaussian and mixture systems in a recipe. */
 int  htkamd_mmf_mixup(htkamd_mmf *s, int target, const unsigned char *stateSel);
+/* Decision-tree state clustering as HHEd's RO / QS / TB / ST commands do it (BuildTree HHEd.c:2961) for state items of one-stream,
+   single-Gaussian DIAGC sets: the step between cloned single-Gaussian triphones plus an HERest -s statistics file and a tied-state set.
+     stats_read_file  : LoadStatsFile (HUtil.c:1291): occ[state] = the occupation of every state a model of the file owns (a float, as
+                        the reference keeps it), count[phys] = the model's number of examples (may be NULL); states of models the file
+                        does not list keep 0.  A name that is not in the set or a wrong number of counts is refused.
+     mmf_tree_cluster : `outlierThresh` is RO's (< 0: none), `q` the QS commands in order (a name and model-name patterns with * and ?;
+                        a question no model answers is dropped, htkamd_last_error then holds a warning), `t` the TB commands in order
+                        (threshold, macro name, item list "{ pat.state[i] }" / "{ (pat,pat).state[i] }" with a single state index;
+                        trees must not overlap).  All trees are built together on the device (the sums of every node over every
+                        question, in the reference's order and bit for bit) with the deciding likelihoods evaluated on the host; then
+                        the leaves are tied in order: ~s macros `macRoot` + number.  With HTKAMD_TREE_LEAFSTATS the tied state's mean
+                        and variance come from the leaf's statistics, floored by varFloor1; every gConst is then refreshed, as HHEd does
+                        before it saves (FixAllGConsts, HHEd.c:6469).  Afterwards htkamd_mmf_desc / htkamd_mmf_write reflect the tied set
+                        (fewer states; state numbers change).  `treesPath`: the ST command's file, or NULL.
+     trees_write      : ShowTreesCommand (HHEd.c:3263) for trees given as tables: node n asks question quest[n]; no[n] / yes[n] >= 0 is
+                        a node, < 0 the leaf -1-k whose macro is leafMacro[k]; nNodes = 0: the single leaf leafMacro[0].
+     mmf_item_list / mmf_question_answers / tree_split_sums : test aids -- an item list's (model, state number) pairs in the order of the
+                        reference's list; a question's answer per physical model; the raw sums of one node on the device. */
+typedef struct { const char *name; const char *const *patterns; int nPatterns; } htkamd_tree_question;
+typedef struct { float threshold; const char *macRoot; const char *itemList; } htkamd_tree_spec;
+typedef struct { const char *name; int state; int nNodes; const int *quest, *no, *yes; const char *const *leafMacro; int nLeaves; } htkamd_tree_desc;
+#define HTKAMD_TREE_MERGE      1   /* TREEMERGE (default T in the reference)    */
+#define HTKAMD_TREE_LEAFSTATS  2   /* USELEAFSTATS (default T in the reference) */
+int  htkamd_stats_read_file(const htkamd_mmf *s, const char *path, float *occ /*[numStates]*/, int *count /*[numPhys]*/);
+int  htkamd_mmf_tree_cluster(htkamd_mmf *s, const float *occ /*[numStates]*/, float outlierThresh, const htkamd_tree_question *q, int nQ,
+                             const htkamd_tree_spec *t, int nT, int flags, const char *treesPath, void *stream);
+int  htkamd_trees_write(const char *path, const htkamd_tree_question *q, int nQ, const htkamd_tree_desc *t, int nT);
+int  htkamd_mmf_item_list(const htkamd_mmf *s, const char *itemList, int *phys /*[cap]*/, int *state /*[cap]*/, int cap, int *n);
+int  htkamd_mmf_question_answers(const htkamd_mmf *s, const htkamd_tree_question *q, unsigned char *answers /*[numPhys]*/);
+/* the raw split sums of one node, [nQ][2][2D+1] floats (no side, then yes side; occ, sum[D], sqr[D]) */
+int  htkamd_tree_split_sums(const float *itemStats /*[nItems][2D+1]*/, int nItems, int D, const int *nodeItems, int n,
+                            const unsigned char *answers /*[nQ][nItems]*/, int nQ, float *out, void *stream);
 /* HCompV's PutVFloor (HCompV.c:359-389): "~v varFloor1 <Variance> D" with scale*var, written like WriteVector(" %e"). */
 int  htkamd_mmf_write_vfloors(const char *path, const float *var, int D, float scale);
 void htkamd_mmf_destroy(htkamd_mmf *s);
