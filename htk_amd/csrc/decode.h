@@ -1,4 +1,5 @@
-// decode.h -- what the network decoder's kernels (decode.hip: 1-best; decode_n.hip: N-best token sets + lattice) and their host code share.
+// decode.h -- what the network decoder's kernels (decode.hip: 1-best; decode_n.hip: N-best token sets + lattice) and their host code share
+// (the kernels' shared DEVICE code: decode_dev.h, decode_ord.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <functional>
@@ -85,13 +86,17 @@ struct DecArgs {
    int *tieFlag;                       // [nUtt] k_decode: two tokens of exactly equal likelihood and different histories met at a node (see decode_ord.hip)
 };
 
-// Exact-order decoding (decode_ord.hip): the utterances k_decode flagged, or every utterance of an N-best run.
-struct OrdArgs {
-   DecArgs d;                          // utt = the selected utterances' descriptors (idx = slot in the outputs)
+// Exact-order decoding (decode_ord.hip, k_decode_ord_n of decode_n.hip): HRec's instance list and the Path records it needs
+struct OrdList {
    int *seq; int seqCap;               // [nSel * 2 * seqCap] the instance list as an array (two buffers per utterance)
    int *pos; unsigned char *ooo;       // [sum nNodes] (at DecUtt.node0) position of the node's instance in seq (-1: none); NetInst.ooo
    int *pathNode, *pathFrame;          // [paths] (at DecUtt.path0) Path records are allocated one by one here
    int pathExtra;                      // records per utterance beyond (T + 1) * nWordNodes
+};
+// k_decode_ord: the utterances k_decode flagged, or every utterance of a run in HTKAMD_ORDER_EXACT
+struct OrdArgs {
+   DecArgs d;                          // utt = the selected utterances' descriptors (idx = slot in the outputs)
+   OrdList list;
    int keepFast;                       // the outputs hold k_decode's result of the same utterance (HTKAMD_ORDER_AUTO): a walk that runs out of one of its
                                        // fixed capacities (-4 path records, -5 list appends of a frame, -6 nesting of zero-time nodes) leaves it standing
 };

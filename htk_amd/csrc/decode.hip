@@ -33,14 +33,13 @@
 #include "kernels.h"
 
 #include "decode.h"
-
-__device__ __forceinline__ Tok null_tok() { Tok t; t.like = LZERO; t.lm = 0.0f; t.path = -1; return t; }
+#include "decode_dev.h"
 
 // entry token of node n: best over predecessors (SetEntryState over StepInst2's sends), first maximum wins.
 // *tie is set when a second token of EXACTLY the winner's likelihood and another history (path or LM share) was met: which of the two
 // the reference keeps depends on the order of its instance list (decode_ord.hip decodes such utterances again, in that order).
 struct PullAcc { Tok best; int arg; bool tb; };
-__device__ __forceinline__ PullAcc pull_start() { PullAcc p; p.best = null_tok(); p.arg = 0x7fffffff; p.tb = false; return p; }
+__device__ __forceinline__ PullAcc pull_start() { PullAcc p; p.best = dec_null(); p.arg = 0x7fffffff; p.tb = false; return p; }
 // one predecessor: its exit token e, the link (ps: node | bit 31 for a word / null predecessor; lm), its position k in the list
 __device__ __forceinline__ void pull_fold(PullAcc &p, const DecArgs &a, const Tok e, const int ps, const float lm, const int k, const float gT, const float wT)
 {
@@ -96,24 +95,11 @@ __device__ __forceinline__ void block_max2(double &v, double &w, double *red, do
    for (int i = 1; i < NTHR / 64; i++) { v = (red[i] > v) ? red[i] : v; w = (red2[i] > w) ? red2[i] : w; }
 }
 
-template <int NTHR>
-__device__ __forceinline__ double block_max(double v, double *red)
-{
-#pragma unroll
-   for (int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o); v = (w > v) ? w : v; }
-   const int wv = threadIdx.x >> 6;
-   __syncthreads();
-   if ((threadIdx.x & 63) == 0) red[wv] = v;
-   __syncthreads();
-   double r = red[0];
-   for (int i = 1; i < NTHR / 64; i++) r = (red[i] > r) ? red[i] : r;
-   return r;
-}
-
 #define DEC_LDS_TP 4096            /* floats of transition matrices cached in LDS (all of them, else global memory) */
 
 // StepHMM1 (HRec.c:642) on one model instance: s[1 .. NS-1] = the state tokens on entry (s[1] the entry token) and the new ones on
 // return (s[1] null: the entry is consumed); exT = the exit token, mx = the instance's maximum, wordTop raised by exit + LikeToWord.
+// SLOTS (k_decode's register-resident models): the CreateSEIndex ranges `se` and the score slots sl2 .. sl4 come with the model's records.
 template <int MX, bool SLOTS = false>
 __device__ __forceinline__ void hmm_step1(const DecArgs &a, const DecUtt &ud, const int4 ni, const float *tp, Tok (&s)[MX], const float gT, const int t,
                                           const float wdlk, Tok &exT, double &mx, double &wordTop, const int sl2 = 0, const int sl3 = 0, const int sl4 = 0, const int se = 0)
@@ -131,7 +117,7 @@ __device__ __forceinline__ void hmm_step1(const DecArgs &a, const DecUtt &ud, co
          const int slj[3] = {sl2, sl3, sl4};
 #pragma unroll
          for (int j = 2; j < 5; j++) {
-            nw[j] = null_tok();
+            nw[j] = dec_null();
             const double c1 = s[j - 1].like + tIn[j - 2], c2 = s[j].like + tSelf[j - 2];
             Tok best = s[j - 1]; double bl = c1;
             if (c2 > bl) { best = s[j]; bl = c2; }
@@ -149,7 +135,7 @@ __device__ __forceinline__ void hmm_step1(const DecArgs &a, const DecUtt &ud, co
             const double w = best.like + wdlk;
             if (w > wordTop) wordTop = w;
          }
-         s[1] = null_tok();
+         s[1] = dec_null();
 #pragma unroll
          for (int j = 2; j < 5; j++) s[j] = nw[j];
          return;
@@ -157,7 +143,7 @@ __device__ __forceinline__ void hmm_step1(const DecArgs &a, const DecUtt &ud, co
    }
 #pragma unroll
    for (int j = 2; j < MX; j++) {
-      nw[j] = null_tok();
+      nw[j] = dec_null();
       if (j < NS) {
          // CreateSEIndex (HRec.c:1403): predecessor range with a transition, first maximum wins
          int lo = 1, hi = NS - 1;
@@ -207,7 +193,7 @@ __device__ __forceinline__ void hmm_step1(const DecArgs &a, const DecUtt &ud, co
          if (w > wordTop) wordTop = w;
       }
    }
-   s[1] = null_tok();                                      // entry consumed
+   s[1] = dec_null();                                      // entry consumed
 #pragma unroll
    for (int j = 2; j < MX; j++) if (j < NS) s[j] = nw[j];
 }
@@ -261,7 +247,7 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
    if (tpInLds) for (int i = tid; i < N.nTpFloats; i += NTHR) ltp[i] = N.transP[i];
    if constexpr (EXL) {
       for (int i = tid; i < N.nWordNodes; i += NTHR) wl[i] = LZERO;
-      for (int i = tid; i < DEC_NULL_LDS; i += NTHR) nullL[i] = null_tok();
+      for (int i = tid; i < DEC_NULL_LDS; i += NTHR) nullL[i] = dec_null();
    }
    // the LDS copy of a zero-time node's exit token (every store to ex[] of such a node comes through here)
    // (a node with a slot is read from LDS by every pull of this kernel: its token stays out of memory -- 96 KB per utterance and frame on
@@ -285,15 +271,15 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
    if constexpr (NPT > 0) {
 #pragma unroll
       for (int k = 0; k < NPT; k++) {
-         xs[k * NTHR + tid] = null_tok();
+         xs[k * NTHR + tid] = dec_null();
          rmax(k) = (float)LZERO;
 #pragma unroll
-         for (int i = 0; i < DEC_MAXR - 2; i++) rs[k][i] = null_tok();
+         for (int i = 0; i < DEC_MAXR - 2; i++) rs[k][i] = dec_null();
       }
    }
 
-   for (int i = tid; i < N.nTok; i += NTHR) tok[i] = null_tok();
-   for (int i = tid; i < N.nNodes; i += NTHR) { ex[i] = null_tok(); imax[i] = LZERO; }
+   for (int i = tid; i < N.nTok; i += NTHR) tok[i] = dec_null();
+   for (int i = tid; i < N.nNodes; i += NTHR) { ex[i] = dec_null(); imax[i] = LZERO; }
    if (tid == 0) { thr[0] = (float)LSMALL; thr[1] = (float)LSMALL; }
    __syncthreads();
 
@@ -302,70 +288,37 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
          // ---- maximum-model pruning (ProcessObservation HRec.c:1966-1985): when more than maxActive instances are attached, those
          // whose max (a float, NetInst.max) lies below the (maxActive+1)-th largest are detached before pass 1.  An instance is
          // attached when its max reached the previous frame's threshold (imax carries the pass-1 maximum raised by any token that
-         // entered in pass 2; word / null nodes hold the token they were given).  Selection: radix select on the float keys.
+         // entered in pass 2; word / null nodes hold the token they were given).  The threshold: dec_prune_threshold (decode_dev.h).
          const float gTp = thr[0];
-         if (tid == 0) usel[0] = 0;
-         __syncthreads();
-         int cnt = 0;
-         for (int n = tid; n < N.nNodes; n += NTHR) { const double v = imax[n]; if (v >= gTp && v > LSMALL) cnt++; }
-         if (cnt) atomicAdd(&usel[0], (unsigned)cnt);
-         __syncthreads();
-         const int nact = (int)usel[0];
-         if (nact > a.maxActive) {
-            if (tid == 0) { usel[1] = 0; usel[2] = (unsigned)a.maxActive; }
-            unsigned int mask = 0;
-            for (int pass = 0; pass < 4; pass++) {
-               const int shift = 24 - 8 * pass;
-               for (int i = tid; i < 256; i += NTHR) uhist[i] = 0;
-               __syncthreads();
-               const unsigned int prefix = usel[1];
-               for (int n = tid; n < N.nNodes; n += NTHR) {
-                  const double v = imax[n];
-                  if (!(v >= gTp && v > LSMALL)) continue;
-                  unsigned int k = __float_as_uint((float)v);
-                  k ^= (k >> 31) ? 0xFFFFFFFFu : 0x80000000u;          // ascending order of the floats
-                  if ((k & mask) == prefix) atomicAdd(&uhist[(k >> shift) & 255], 1);
-               }
-               __syncthreads();
-               if (tid == 0) {
-                  unsigned int skip = usel[2], cum = 0; int b = 255;
-                  for (; b > 0; b--) { if (cum + (unsigned)uhist[b] > skip) break; cum += (unsigned)uhist[b]; }
-                  usel[1] = prefix | ((unsigned)b << shift); usel[2] = skip - cum;
-               }
-               mask |= 255u << shift;
-               __syncthreads();
-            }
-            unsigned int kk = usel[1];
-            kk ^= (kk >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-            const float uth = __uint_as_float(kk);
-            if (uth > (float)LSMALL) {
-               if constexpr (NPT > 0) {                                // the tokens that live in registers: their owners drop them (before imax changes)
+         const float uth = dec_prune_threshold<NTHR>(N.nNodes, a.maxActive, usel, uhist,
+                                                     [&](const int n, float &key) { const double v = imax[n]; key = (float)v; return v >= gTp && v > LSMALL; });
+         if (uth > (float)LSMALL) {
+            if constexpr (NPT > 0) {                                // the tokens that live in registers: their owners drop them (before imax changes)
 #pragma unroll
-                  for (int k = 0; k < NPT; k++) {
-                     const int hk = tid + k * NTHR;
-                     if (hk < nReg) {
-                        const double v = imax[N.hmmNodes[hk]];
-                        if (v >= gTp && v > LSMALL && v < (double)uth) {
-                           xs[k * NTHR + tid] = null_tok();
-                           rmax(k) = (float)LZERO;
+               for (int k = 0; k < NPT; k++) {
+                  const int hk = tid + k * NTHR;
+                  if (hk < nReg) {
+                     const double v = imax[N.hmmNodes[hk]];
+                     if (v >= gTp && v > LSMALL && v < (double)uth) {
+                        xs[k * NTHR + tid] = dec_null();
+                        rmax(k) = (float)LZERO;
 #pragma unroll
-                           for (int i = 0; i < DEC_MAXR - 2; i++) rs[k][i] = null_tok();
-                        }
+                        for (int i = 0; i < DEC_MAXR - 2; i++) rs[k][i] = dec_null();
                      }
                   }
-                  __syncthreads();
                }
-               for (int n = tid; n < N.nNodes; n += NTHR) {
-                  const double v = imax[n];
-                  if (!(v >= gTp && v > LSMALL) || !(v < (double)uth)) continue;
-                  imax[n] = LZERO; put_ex(n, null_tok(), EXL ? N.zl[n] : -1);      // DetachInst: every token of the instance goes, the entry token too
-                  const int4 ni = N.nodeInfo[n];
-                  const int nt = ((ni.x & 15) == HTKAMD_NODE_HMM) ? ((ni.x >> 4) & 255) - 1 : 1;
-                  for (int i = 0; i < nt; i++) tok[ni.y + i] = null_tok();
-               }
+               __syncthreads();
             }
-            __syncthreads();
+            for (int n = tid; n < N.nNodes; n += NTHR) {
+               const double v = imax[n];
+               if (!(v >= gTp && v > LSMALL) || !(v < (double)uth)) continue;
+               imax[n] = LZERO; put_ex(n, dec_null(), EXL ? N.zl[n] : -1);      // DetachInst: every token of the instance goes, the entry token too
+               const int4 ni = N.nodeInfo[n];
+               const int nt = ((ni.x & 15) == HTKAMD_NODE_HMM) ? ((ni.x >> 4) & 255) - 1 : 1;
+               for (int i = 0; i < nt; i++) tok[ni.y + i] = dec_null();
+            }
          }
+         if (uth > -INFINITY) __syncthreads();                  // (more than maxActive were attached)
       }
       if (t >= 1) {
          const float gT = thr[0];                         // threshold of the previous frame
@@ -383,15 +336,15 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
                   Tok s[DEC_MAXR];
                   const bool detached = rmax(k) < gT;     // DetachInst of the previous frame's pass 2
                   bool live = false;
-                  s[0] = null_tok();
+                  s[0] = dec_null();
 #pragma unroll
                   for (int i = 1; i < DEC_MAXR; i++) {
-                     s[i] = null_tok();
+                     s[i] = dec_null();
                      if (i < NS && (i == 1 || !detached)) s[i] = (i == 1) ? xs[k * NTHR + tid] : rs[k][i - 2];
                   }
 #pragma unroll
                   for (int i = 1; i < DEC_MAXR; i++) if (i < NS && s[i].like > LSMALL) live = true;
-                  Tok exT = null_tok();
+                  Tok exT = dec_null();
                   double mx = LZERO;
                   if (live) {
                      hmm_step1<DEC_MAXR, true>(a, ud, ni, tpBase + ni.z, s, gT, t, N.regRecF[hk].x, exT, mx, myWord, rb.x, rb.y, rb.z, rb.w >> 1);
@@ -400,7 +353,7 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
                   } else {
                      nDead++;
 #pragma unroll
-                     for (int i = 1; i < DEC_MAXR; i++) s[i] = null_tok();
+                     for (int i = 1; i < DEC_MAXR; i++) s[i] = dec_null();
                   }
 #pragma unroll
                   for (int i = 2; i < DEC_MAXR; i++) rs[k][i - 2] = s[i];
@@ -420,16 +373,16 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
             Tok s[DEC_MAXN];
             const bool detached = imax[n] < gT;           // DetachInst of the previous frame's pass 2
             bool live = false;
-            s[0] = null_tok();
+            s[0] = dec_null();
 #pragma unroll
             for (int i = 1; i < DEC_MAXN; i++) {
-               s[i] = null_tok();
+               s[i] = dec_null();
                // the entry token (i == 1) was pulled at the end of the previous frame's level phase
                if (i < NS && (i == 1 || !detached)) s[i] = tok[t0 + i - 1];
             }
 #pragma unroll
             for (int i = 1; i < DEC_MAXN; i++) if (i < NS && s[i].like > LSMALL) live = true;
-            Tok exT = null_tok();
+            Tok exT = dec_null();
             double mx = LZERO;
             if (live) {
                hmm_step1<DEC_MAXN>(a, ud, ni, tpBase + ni.z, s, gT, t, N.wdlk[n], exT, mx, myWord);
@@ -437,7 +390,7 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
                for (int j = 1; j < DEC_MAXN; j++) if (j < NS) tok[t0 + j - 1] = s[j];
                if (mx > myGen) myGen = mx;
             } else if (detached) {
-               for (int i = 1; i < NS; i++) tok[t0 + i - 1] = null_tok();
+               for (int i = 1; i < NS; i++) tok[t0 + i - 1] = dec_null();
             }
             ex[n] = exT; imax[n] = (double)(float)mx;         // inst->max is a LogFloat (HRec.c:138)
          }
@@ -464,12 +417,12 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
                   if (n >= 0) {
                      const Tok e0 = xs[k * NTHR + tid];
                      const float lm = N.regRecF[hk].y;
-                     Tok st = null_tok();
+                     Tok st = dec_null();
                      if (e0.like > gT) {                   // pull_range over the one predecessor (a model: no word-end beam on its token)
                         const double c = e0.like + lm * a.lmScale;
                         if (c > gT) { st.like = c; st.lm = e0.lm + lm; st.path = e0.path; }
                      }
-                     Tok e = null_tok();
+                     Tok e = dec_null();
                      if (st.like > LSMALL) {
                         e = st;
                         if (fr.w >= 0) {                      // StepWord2 (word_step2 with the node's constants from the record)
@@ -499,13 +452,13 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
             int ak;
             Tok st = pull_range<EXL>(a, ex, N.predOff[n], N.predOff[n + 1], 1, gT, wT, &ak, &tie, wl, nullL, t * N.nWordNodes);
             if (t == 0 && n == N.initial) { st.like = 0.0; st.lm = 0.0f; st.path = -1; }
-            Tok e = null_tok();
+            Tok e = dec_null();
             if (kind == HTKAMD_NODE_HMM) {                 // tee model: StepHMM2
                const int NS = (ni.x >> 4) & 255;
                tok[ni.y] = st;
                e = ex[n];
                const double m2 = (st.like > imax[n]) ? (double)(float)st.like : imax[n];      // SetEntryState raises the instance's max
-               if (t >= 1 && m2 < gT) { e = null_tok(); imax[n] = LZERO; }
+               if (t >= 1 && m2 < gT) { e = dec_null(); imax[n] = LZERO; }
                else {
                   imax[n] = m2;
                   if (st.like > LSMALL) {
@@ -542,9 +495,9 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
                   if (red[i] > red[bw] || (red[i] == red[bw] && redk[i] < redk[bw])) bw = i;
                }
                Tok b; b.like = red[bw]; b.lm = __int_as_float(__double2hiint(red2[bw])); b.path = __double2loint(red2[bw]);
-               if (redk[bw] == 0x7fffffff) b = null_tok();
+               if (redk[bw] == 0x7fffffff) b = dec_null();
                if (t == 0 && n == N.initial) { b.like = 0.0; b.lm = 0.0f; b.path = -1; }
-               Tok e = null_tok();
+               Tok e = dec_null();
                imax[n] = (b.like > LSMALL) ? (double)(float)b.like : LZERO;
                if (b.like > LSMALL) e = (N.kind[n] == HTKAMD_NODE_WORD) ? word_step2(a, ud, n, t, b) : b;
                put_ex(n, e, EXL ? N.zl[n] : -1);
@@ -650,39 +603,7 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
             else fin = nullL[zf];
          }
       }
-      const int fp = fin.path;
-      int nW = 0;
-      a.total[u] = LZERO; a.finalLm[u] = 0.0f;
-      if (fp >= 0) {
-         a.total[u] = fin.like; a.finalLm[u] = fin.lm;
-         for (int p = fp; p >= 0; p = a.pathPrev[ud.path0 + p]) nW++;
-         if (nW > a.maxWords) nW = -3;
-         else {
-            int w = nW;
-            for (int p = fp; p >= 0;) {
-               const int prev = a.pathPrev[ud.path0 + p];
-               const int widx = p % N.nWordNodes, frame = p / N.nWordNodes;
-               const double prlk = (prev >= 0) ? a.pathLike[ud.path0 + prev] : 0.0;
-               const double wp = a.wordPen;
-               const float plm = a.pathLm[ud.path0 + p];
-               float aclike = (float)(a.pathLike[ud.path0 + p] - prlk - plm * a.lmScale - wp);
-               const int node = N.wordNode[widx];
-               const float pr = N.pronProb[node];
-               aclike -= pr * a.prScale;
-               const float sc = (float)((double)((aclike * 1.0f + plm * a.lmScale) + pr * a.prScale) + (double)a.wordPen);
-               w--;
-               a.wordPron[ud.out0 + w] = N.model[node];
-               a.wordEnd[ud.out0 + w] = frame;
-               a.wordStart[ud.out0 + w] = (prev >= 0) ? prev / N.nWordNodes : 0;
-               a.wordScore[ud.out0 + w] = sc;
-               a.wordLm[ud.out0 + w] = plm;
-               a.wordAc[ud.out0 + w] = aclike;
-               a.wordLike[ud.out0 + w] = a.pathLike[ud.path0 + p];
-               p = prev;
-            }
-         }
-      } else nW = -1;
-      a.nWords[u] = nW;
+      dec_traceback(a, ud, u, fin, PathView{nullptr, nullptr, N.nWordNodes, N.wordNode});
    }
 }
 
@@ -1215,8 +1136,8 @@ extern "C" int htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_con
                OrdArgs oa;
                oa.d = a; oa.d.utt = (const DecUtt *)dSel; oa.d.nUtt = nSel;
                oa.d.pathPrev = (int *)oPrev; oa.d.pathLike = (double *)oLike; oa.d.pathLm = (float *)oLm;
-               oa.seq = (int *)dSeq; oa.seqCap = seqCap; oa.pos = (int *)dPos; oa.ooo = (unsigned char *)dOoo;
-               oa.pathNode = (int *)oNode; oa.pathFrame = (int *)oFrame; oa.pathExtra = pathExtra;
+               oa.list.seq = (int *)dSeq; oa.list.seqCap = seqCap; oa.list.pos = (int *)dPos; oa.list.ooo = (unsigned char *)dOoo;
+               oa.list.pathNode = (int *)oNode; oa.list.pathFrame = (int *)oFrame; oa.list.pathExtra = pathExtra;
                oa.keepFast = orderMode == HTKAMD_ORDER_AUTO ? 1 : 0;
                // (the path capacity the kernel assumes per utterance is 3 (T + 1) nWordNodes + pathExtra: see opath above)
                rc = htkamd_launch_decode_ord(oa, nSel, s);

@@ -38,6 +38,9 @@ struct __attribute__((aligned(16))) TSet {
    float rl[NT], rlm[NT]; int rp[NT];  // relative tokens; [0] mirrors the best (like 0)
    int ra[NT];                         // RelToken.align (-DPHNALG)
 };
+// a wide node's partial set in LDS (k_decode_n): a token set without the alignment fields, which that kernel never makes -- 1024 whole
+// TSets are all 160 KB of a workgroup's LDS and leave none for the kernel's other arrays: the launch was refused
+struct __attribute__((aligned(8))) PSet { double like; float lm; int path; int n; float rl[NT], rlm[NT]; int rp[NT]; };
 struct __attribute__((aligned(8))) AlignRec { int node, state, frame, prev; double like; };      // Align (HRec.c:150-164)
 
 struct NArgs {
@@ -51,8 +54,7 @@ struct NArgs {
    int *mark;                                                  // [paths] MarkPaths' usage numbers
    int *stack;                                                 // [nUtt * 2*maxLatNodes] depth-first stack
    int *nodePath;                                              // [nUtt * maxLatNodes] the Path record of a lattice node
-   // k_decode_ord_n: the instance list (decode_ord.h) and Path records allocated one by one
-   int *seq; int seqCap; int *pos; unsigned char *ooo; int *pathNode, *pathFrame; int pathExtra;
+   OrdList list;                                               // k_decode_ord_n: the instance list and Path records allocated one by one
    // ... and alignment records (HVite -n with -m: alignMode & 1 = pri->models, -f: & 2 = pri->states)
    int alignMode; AlignRec *al; int alCap; int *alCount;          // [nUtt * alCap] records, [nUtt] records made
    int *pathAlign, *altAlign;                                     // Path.align [paths], NxtPath.align [paths * (NT-1)]
@@ -60,7 +62,6 @@ struct NArgs {
    float genBeam, wordBeam, nBeam, lmScale, wordPen, prScale;
    int nToks, maxActive;
    int maxLatNodes, maxLatArcs;
-   size_t *pathBase;                   // unused
    int *latN;                          // [nUtt*2] nodes, arcs (or -1 / -3)
    int *nodeFrame, *nodeNet;           // [nUtt*maxLatNodes]
    double *nodeLike;
@@ -68,6 +69,8 @@ struct NArgs {
    double *total;
 };
 
+// (StepWord1 / a token under the beam: the best token goes, the relative tokens stay as they are)
+__device__ __forceinline__ void ts_null_head(TSet &s) { s.like = LZERO; s.lm = 0.0f; s.path = -1; s.align = -1; s.n = 1; }
 __device__ __forceinline__ void ts_null(TSet &s) { s.like = LZERO; s.lm = 0.0f; s.path = -1; s.n = 1; s.align = -1; s.rl[0] = 0.0f; s.rlm[0] = 0.0f; s.rp[0] = -1; s.ra[0] = -1; }
 // the word-end node a path ends in (TokSetMerge compares path->node): the dense table's column, or -- Path records allocated one by one
 // (k_decode_ord_n) -- the record's node
@@ -134,19 +137,6 @@ __device__ void pull_sets(const NArgs &a, const TSet *ex, int k0, int k1, float 
    }
 }
 
-__device__ __forceinline__ double block_max_n(double v, double *red)
-{
-#pragma unroll
-   for (int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o); v = (w > v) ? w : v; }
-   const int wv = threadIdx.x >> 6;
-   __syncthreads();
-   if ((threadIdx.x & 63) == 0) red[wv] = v;
-   __syncthreads();
-   double r = red[0];
-   for (int i = 1; i < DEC_THREADS / 64; i++) r = (red[i] > r) ? red[i] : r;
-   return r;
-}
-
 // StepWord2 for the token set `st` that entered word node n at frame t: the Path record and the exit set
 __device__ void word_exit(const NArgs &a, const DecUtt &ud, int n, int t, const TSet &st, TSet &e)
 {
@@ -206,13 +196,7 @@ __device__ int emit_lalign(const NArgs &a, int sel, size_t outBase, int at, int 
 }
 
 // CompleteRecognition (HRec.c:2054) -> CreateLattice (:1679): MarkPaths (:1664) numbers the Path records reachable from the final token
-// set depth first, LatFromPaths (:1512) makes every Path / NxtPath an arc.  By ONE thread.  Where a Path record lies: the dense
-// [frame][word node] table of k_decode_n, or records allocated one by one with their frame and node beside them (k_decode_ord_n).
-struct PathView {
-   const int *pathFrame, *pathNode; int nW; const int *wordNode;
-   __device__ __forceinline__ int frame(int p) const { return pathFrame ? pathFrame[p] : p / nW; }
-   __device__ __forceinline__ int node(int p) const { return pathNode ? pathNode[p] : wordNode[p % nW]; }
-};
+// set depth first, LatFromPaths (:1512) makes every Path / NxtPath an arc.  By ONE thread.  Where a Path record lies: PathView (decode_dev.h).
 
 __device__ void build_lattice(const NArgs &a, const DecUtt &ud, int u, const TSet &fin, const PathView pv, const int sel = 0)
 {
@@ -298,14 +282,85 @@ __device__ void build_lattice(const NArgs &a, const DecUtt &ud, int u, const TSe
    latN[0] = nn; latN[1] = ln;
 }
 
+// NewNRefAlign (HRec.c:598-622): records are allocated one by one per utterance (any thread; their numbers are not part of any result)
+__device__ __forceinline__ int new_align(const NArgs &a, int sel, int node, int state, double like, int frame, int prev)
+{
+   const int i = atomicAdd(&a.alCount[sel], 1);
+   if (i >= a.alCap) return -1;                          // (counted: the utterance ends as "did not fit")
+   AlignRec r; r.node = node; r.state = state; r.frame = frame; r.prev = prev; r.like = like;
+   a.al[(size_t)sel * a.alCap + i] = r;
+   return i;
+}
+
+// StepHMM1 (HRec.c:642) on the token sets of model instance n, from the CreateSEIndex ranges to the exit set: cur = the sets on entry,
+// nxt = the new column (the entry set consumed); exS = the exit set, mx = the instance's maximum, wordTop raised by exit + LikeToWord.
+// A set under the beam loses its best token only (HRec sets tok.like: the relative tokens stay as they are; nothing reads them).
+// ALIGN (k_decode_ord_n): the alignment records of HVite -m / -f, as a.alignMode asks for them.
+template <bool ALIGN>
+__device__ __forceinline__ void set_step1(const NArgs &a, const DecUtt &ud, const int sel, const int n, const int4 ni, const float *tp, const TSet *cur, TSet *nxt,
+                                          const float gT, const float nT, const int t, const KeyOf ko, TSet &exS, double &mx, double &wordTop)
+{
+   const DecNet &N = a.net;
+   const int NS = (ni.x >> 4) & 255, t0 = ni.y;
+   for (int j = 2; j < NS; j++) {
+      int lo = 1, hi = NS - 1;                              // CreateSEIndex (HRec.c:1403)
+      while (lo < NS && !(tp[(lo - 1) * NS + (j - 1)] > LSMALL)) lo++;
+      while (hi > 1 && !(tp[(hi - 1) * NS + (j - 1)] > LSMALL)) hi--;
+      if (lo > hi) { lo = 1; hi = NS - 1; }
+      TSet res = cur[t0 + lo - 1];
+      res.like += tp[(lo - 1) * NS + (j - 1)];
+      for (int i = lo + 1; i <= hi; i++) {
+         const TSet &si = cur[t0 + i - 1];
+         ts_merge(res, si.like + tp[(i - 1) * NS + (j - 1)], si.lm, si.path, si, nT, a.nToks, ko, si.align);
+      }
+      if (res.like > gT) {
+         const int st = N.hmmState[ni.w + (j - 2)];
+         const float outp = a.score[ud.score0 + (size_t)(t - 1) * a.ns + N.stateSlot[st]];
+         res.like += outp;
+         if (res.like > mx) mx = res.like;
+         if constexpr (ALIGN)
+            if (a.alignMode & 2) {                          // pri->states (HRec.c:680-704, -DPHNALG): a record where a token enters state j
+               const double alk = res.like - outp - res.lm * a.lmScale;
+               const AlignRec *AL = a.al + (size_t)sel * a.alCap;
+               if (res.align < 0 || AL[res.align].state != j || AL[res.align].node != n) { res.align = new_align(a, sel, n, j, alk, t - 1, res.align); res.ra[0] = res.align; }
+               for (int q = 1; q < res.n; q++)
+                  if (res.ra[q] < 0 || AL[res.ra[q]].state != j || AL[res.ra[q]].node != n) res.ra[q] = new_align(a, sel, n, j, alk, t - 1, res.ra[q]);
+            }
+      } else ts_null_head(res);
+      nxt[t0 + j - 1] = res;
+   }
+   { TSet z = cur[t0]; ts_null_head(z); nxt[t0] = z; }     // entry consumed
+   int lo = 2, hi = NS - 1;
+   while (lo < NS && !(tp[(lo - 1) * NS + (NS - 1)] > LSMALL)) lo++;
+   while (hi > 1 && !(tp[(hi - 1) * NS + (NS - 1)] > LSMALL)) hi--;
+   if (lo > hi) { lo = 2; hi = NS - 1; }
+   TSet res = nxt[t0 + lo - 1];
+   res.like += tp[(lo - 1) * NS + (NS - 1)];
+   for (int i = lo + 1; i <= hi; i++) {
+      const TSet &si = nxt[t0 + i - 1];
+      ts_merge(res, si.like + tp[(i - 1) * NS + (NS - 1)], si.lm, si.path, si, nT, a.nToks, ko, si.align);
+   }
+   if (res.like > LSMALL) {
+      const double w = res.like + N.wdlk[n];
+      if (w > wordTop) wordTop = w;
+      if constexpr (ALIGN)
+         if ((a.alignMode & 1) && !((ni.x >> 12) & 1)) {    // pri->models, not a tee model (HRec.c:762-776): the model's exit record per token
+            const double alk = res.like - res.lm * a.lmScale;
+            res.align = new_align(a, sel, n, -1, alk, t, res.align); res.ra[0] = res.align;
+            for (int q = 1; q < res.n; q++) res.ra[q] = new_align(a, sel, n, -1, alk, t, res.ra[q]);
+         }
+   } else ts_null_head(res);
+   exS = res;
+}
+
 __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
 {
    __shared__ double red[DEC_THREADS / 64];
    __shared__ double red2[DEC_THREADS / 64];
    __shared__ float thr[3];
-   __shared__ unsigned int usel[3], uhist[256];
-   extern __shared__ unsigned char dynLds[];           // partial sets of a wide node: DEC_THREADS x TSet
-   TSet *part = (TSet *)dynLds;
+   __shared__ unsigned int usel[3]; __shared__ int uhist[256];
+   extern __shared__ unsigned char dynLds[];           // partial sets of a wide node: DEC_THREADS x PSet
+   PSet *part = (PSet *)dynLds;
    const int u = blockIdx.x, tid = threadIdx.x;
    if (u >= a.nUtt) return;
    const DecUtt ud = a.utt[u];
@@ -324,55 +379,22 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
 
    for (int t = 0; t <= T; t++) {
       if (t >= 1 && a.maxActive > 0) {
-         // ---- maximum-model pruning (ProcessObservation HRec.c:1966-1985), as in decode.hip: when more than maxActive instances are
-         // attached, those whose max (a float) lies below the (maxActive+1)-th largest lose every token set before pass 1
+         // ---- maximum-model pruning (ProcessObservation HRec.c:1966-1985; dec_prune_threshold, decode_dev.h): when more than maxActive
+         // instances are attached, those whose max (a float) lies below the (maxActive+1)-th largest lose every token set before pass 1
          const float gTp = thr[0];
-         if (tid == 0) usel[0] = 0;
-         __syncthreads();
-         int cnt = 0;
-         for (int n = tid; n < N.nNodes; n += DEC_THREADS) { const double v = imax[n]; if (v >= gTp && v > LSMALL) cnt++; }
-         if (cnt) atomicAdd(&usel[0], (unsigned)cnt);
-         __syncthreads();
-         const int nact = (int)usel[0];
-         if (nact > a.maxActive) {
-            if (tid == 0) { usel[1] = 0; usel[2] = (unsigned)a.maxActive; }
-            unsigned int mask = 0;
-            for (int pass = 0; pass < 4; pass++) {
-               const int shift = 24 - 8 * pass;
-               for (int i = tid; i < 256; i += DEC_THREADS) uhist[i] = 0;
-               __syncthreads();
-               const unsigned int prefix = usel[1];
-               for (int n = tid; n < N.nNodes; n += DEC_THREADS) {
-                  const double v = imax[n];
-                  if (!(v >= gTp && v > LSMALL)) continue;
-                  unsigned int k = __float_as_uint((float)v);
-                  k ^= (k >> 31) ? 0xFFFFFFFFu : 0x80000000u;          // ascending order of the floats
-                  if ((k & mask) == prefix) atomicAdd(&uhist[(k >> shift) & 255], 1);
-               }
-               __syncthreads();
-               if (tid == 0) {
-                  unsigned int skip = usel[2], cum = 0; int b = 255;
-                  for (; b > 0; b--) { if (cum + (unsigned)uhist[b] > skip) break; cum += (unsigned)uhist[b]; }
-                  usel[1] = prefix | ((unsigned)b << shift); usel[2] = skip - cum;
-               }
-               mask |= 255u << shift;
-               __syncthreads();
+         const float uth = dec_prune_threshold<DEC_THREADS>(N.nNodes, a.maxActive, usel, uhist,
+                                                            [&](const int n, float &key) { const double v = imax[n]; key = (float)v; return v >= gTp && v > LSMALL; });
+         if (uth > (float)LSMALL)
+            for (int n = tid; n < N.nNodes; n += DEC_THREADS) {
+               const double v = imax[n];
+               if (!(v >= gTp && v > LSMALL) || !(v < (double)uth)) continue;
+               TSet z; ts_null(z);
+               imax[n] = LZERO; ex[n] = z;
+               const int4 ni = N.nodeInfo[n];
+               const int nt = ((ni.x & 15) == HTKAMD_NODE_HMM) ? ((ni.x >> 4) & 255) - 1 : 1;
+               for (int i = 0; i < nt; i++) cur[ni.y + i] = z;
             }
-            unsigned int kk = usel[1];
-            kk ^= (kk >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-            const float uth = __uint_as_float(kk);
-            if (uth > (float)LSMALL)
-               for (int n = tid; n < N.nNodes; n += DEC_THREADS) {
-                  const double v = imax[n];
-                  if (!(v >= gTp && v > LSMALL) || !(v < (double)uth)) continue;
-                  TSet z; ts_null(z);
-                  imax[n] = LZERO; ex[n] = z;
-                  const int4 ni = N.nodeInfo[n];
-                  const int nt = ((ni.x & 15) == HTKAMD_NODE_HMM) ? ((ni.x >> 4) & 255) - 1 : 1;
-                  for (int i = 0; i < nt; i++) cur[ni.y + i] = z;
-               }
-            __syncthreads();
-         }
+         __syncthreads();
       }
       if (t >= 1) {
          const float gT = thr[0], nT = thr[2];             // thresholds of the previous frame
@@ -381,7 +403,6 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
             const int n = N.hmmNodes[hk];
             const int4 ni = N.nodeInfo[n];
             const int NS = (ni.x >> 4) & 255, t0 = ni.y;
-            const float *tp = tpBase + ni.z;
             const bool detached = imax[n] < gT;
             bool live = false;
             for (int i = 1; i < NS; i++) {
@@ -391,42 +412,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
             TSet exS; ts_null(exS);
             double mx = LZERO;
             if (live) {
-               for (int j = 2; j < NS; j++) {
-                  int lo = 1, hi = NS - 1;
-                  while (lo < NS && !(tp[(lo - 1) * NS + (j - 1)] > LSMALL)) lo++;
-                  while (hi > 1 && !(tp[(hi - 1) * NS + (j - 1)] > LSMALL)) hi--;
-                  if (lo > hi) { lo = 1; hi = NS - 1; }
-                  TSet res = cur[t0 + lo - 1];
-                  res.like += tp[(lo - 1) * NS + (j - 1)];
-                  for (int i = lo + 1; i <= hi; i++) {
-                     const TSet &si = cur[t0 + i - 1];
-                     ts_merge(res, si.like + tp[(i - 1) * NS + (j - 1)], si.lm, si.path, si, nT, a.nToks, KeyOf{nullptr, nW});
-                  }
-                  if (res.like > gT) {
-                     const int st = N.hmmState[ni.w + (j - 2)];
-                     res.like += a.score[ud.score0 + (size_t)(t - 1) * a.ns + N.stateSlot[st]];
-                     if (res.like > mx) mx = res.like;
-                  } else ts_null(res);
-                  nxt[t0 + j - 1] = res;
-               }
-               { TSet z; ts_null(z); nxt[t0] = z; }          // entry consumed
-               {
-                  int lo = 2, hi = NS - 1;
-                  while (lo < NS && !(tp[(lo - 1) * NS + (NS - 1)] > LSMALL)) lo++;
-                  while (hi > 1 && !(tp[(hi - 1) * NS + (NS - 1)] > LSMALL)) hi--;
-                  if (lo > hi) { lo = 2; hi = NS - 1; }
-                  TSet res = nxt[t0 + lo - 1];
-                  res.like += tp[(lo - 1) * NS + (NS - 1)];
-                  for (int i = lo + 1; i <= hi; i++) {
-                     const TSet &si = nxt[t0 + i - 1];
-                     ts_merge(res, si.like + tp[(i - 1) * NS + (NS - 1)], si.lm, si.path, si, nT, a.nToks, KeyOf{nullptr, nW});
-                  }
-                  if (res.like > LSMALL) {
-                     exS = res;
-                     const double w = res.like + N.wdlk[n];
-                     if (w > myWord) myWord = w;
-                  }
-               }
+               set_step1<false>(a, ud, 0, n, ni, tpBase + ni.z, cur, nxt, gT, nT, t, KeyOf{nullptr, nW}, exS, mx, myWord);
                if (mx > myGen) myGen = mx;
             } else {
                TSet z; ts_null(z);
@@ -434,8 +420,8 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
             }
             ex[n] = exS; imax[n] = (double)(float)mx;
          }
-         const double genMax = block_max_n(myGen, red);
-         const double wordMax = block_max_n(myWord, red2);
+         const double genMax = dec_block_max<DEC_THREADS>(myGen, red);
+         const double wordMax = dec_block_max<DEC_THREADS>(myWord, red2);
          if (tid == 0) {
             float w = (float)(wordMax - a.wordBeam); if (w < (float)LSMALL) w = (float)LSMALL;
             float g = (float)(genMax - a.genBeam); if (g < (float)LSMALL) g = (float)LSMALL;
@@ -481,13 +467,19 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
             TSet mine; ts_null(mine);
             const int b0 = p0 + tid * per, b1 = (b0 + per < p1) ? b0 + per : p1;
             if (b0 < p1) pull_sets(a, ex, b0, b1, gT, wT, nT, mine);
-            part[tid] = mine;
+            {
+               PSet &pm = part[tid];
+               pm.like = mine.like; pm.lm = mine.lm; pm.path = mine.path; pm.n = mine.n;
+               for (int i = 0; i < mine.n; i++) { pm.rl[i] = mine.rl[i]; pm.rlm[i] = mine.rlm[i]; pm.rp[i] = mine.rp[i]; }
+            }
             __syncthreads();
             if (tid == 0) {
                TSet st; ts_null(st);
                for (int q = 0; q < DEC_THREADS; q++) {
-                  const TSet &pq = part[q];
-                  if (!(pq.like > LSMALL)) continue;
+                  if (!(part[q].like > LSMALL)) continue;
+                  TSet pq; ts_null(pq);
+                  pq.like = part[q].like; pq.lm = part[q].lm; pq.path = part[q].path; pq.n = part[q].n;
+                  for (int i = 0; i < pq.n; i++) { pq.rl[i] = part[q].rl[i]; pq.rlm[i] = part[q].rlm[i]; pq.rp[i] = part[q].rp[i]; pq.ra[i] = -1; }
                   ts_merge(st, pq.like, pq.lm, pq.path, pq, nT, a.nToks, KeyOf{nullptr, nW});
                }
                if (t == 0 && n == N.initial) { st.like = 0.0; st.lm = 0.0f; st.path = -1; st.n = 1; st.rl[0] = 0.0f; st.rlm[0] = 0.0f; st.rp[0] = -1; }
@@ -525,19 +517,9 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
 // k_decode_ord_n -- N-best token passing in the order of HRec's instance list (decode_ord.hip has the design; this is its token-set
 // form).  In N-best mode the list's order decides more than exact ties: every TokSetMerge re-bases its relative tokens as floats
 // (HRec.c:361-364), so the order in which a node's senders are stepped is in the last bit of every alternative's likelihood -- and in
-// which of two alternatives of nearly equal likelihood survives.  The run therefore always walks the list.  Pass 1 = k_decode_n's
-// StepHMM1 over the list's instances; pass 2 = the walk of k_decode_ord with token sets pushed along the links in link order, each
+// which of two alternatives of nearly equal likelihood survives.  The run therefore always walks the list.  Pass 1 = set_step1
+// over the list's instances; pass 2 = the walk of k_decode_ord with token sets pushed along the links in link order, each
 // merge by one lane on the set in global memory; StepWord2 allocates its Path record (+ NxtPaths) per call.
-// NewNRefAlign (HRec.c:598-622): records are allocated one by one per utterance (any thread; their numbers are not part of any result)
-__device__ __forceinline__ int new_align(const NArgs &a, int sel, int node, int state, double like, int frame, int prev)
-{
-   const int i = atomicAdd(&a.alCount[sel], 1);
-   if (i >= a.alCap) return -1;                          // (counted: the utterance ends as "did not fit")
-   AlignRec r; r.node = node; r.state = state; r.frame = frame; r.prev = prev; r.like = like;
-   a.al[(size_t)sel * a.alCap + i] = r;
-   return i;
-}
-
 __device__ void word_exit_ord(const NArgs &a, const DecUtt &ud, int n, int t, const TSet &st, TSet &e, int pid, int *pathNode, int *pathFrame)
 {
    const DecNet &N = a.net;
@@ -562,7 +544,7 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
    __shared__ double red[ORD_THREADS / 64];
    __shared__ double red2[ORD_THREADS / 64];
    __shared__ float thr[3];
-   __shared__ unsigned int usel[3], uhist[256];
+   __shared__ unsigned int usel[3]; __shared__ int uhist[256];
    __shared__ int scan[ORD_THREADS / 64 + 1];
    __shared__ OrdShared sh;
    const int sel = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -572,11 +554,11 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
    const int T = ud.T, u = ud.idx;
    TSet *cur = a.tokA + ud.tok0, *nxt = a.tokB + ud.tok0, *ex = a.ex + ud.node0;
    volatile double *imax = a.imax + ud.node0;
-   volatile int *pos = a.pos + ud.node0;
-   volatile unsigned char *ooo = a.ooo + ud.node0;
-   int *seqA = a.seq + (size_t)sel * 2 * a.seqCap, *seqB = seqA + a.seqCap;
-   const size_t pathCap = 3 * ((size_t)(T + 1) * N.nWordNodes) + (size_t)a.pathExtra;
-   int *pathNode = a.pathNode + ud.path0, *pathFrame = a.pathFrame + ud.path0;
+   volatile int *pos = a.list.pos + ud.node0;
+   volatile unsigned char *ooo = a.list.ooo + ud.node0;
+   int *seqA = a.list.seq + (size_t)sel * 2 * a.list.seqCap, *seqB = seqA + a.list.seqCap;
+   const size_t pathCap = 3 * ((size_t)(T + 1) * N.nWordNodes) + (size_t)a.list.pathExtra;
+   int *pathNode = a.list.pathNode + ud.path0, *pathFrame = a.list.pathFrame + ud.path0;
    const float *tpBase = N.transP;
    const KeyOf ko{pathNode, 0};
 
@@ -587,7 +569,7 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
    if (tid == 0) { thr[0] = (float)LSMALL; thr[1] = (float)LSMALL; thr[2] = (float)LSMALL; sh.tail = 0; sh.nPath = 0; sh.status = 0; sh.base = 0; sh.cn = 0; if (a.alignMode) a.alCount[sel] = 0; }
    __syncthreads();
    OrdCtx c;
-   c.N = &N; c.seq = seqA; c.pos = pos; c.ooo = ooo; c.imax = imax; c.seqCap = a.seqCap; c.sh = &sh;
+   c.N = &N; c.seq = seqA; c.pos = pos; c.ooo = ooo; c.imax = imax; c.seqCap = a.list.seqCap; c.sh = &sh;
    if (tid == 0) {                                          // StartRecognition (HRec.c:1884)
       o_attach(c, N.initial);
       TSet &s0 = cur[N.nodeInfo[N.initial].y];
@@ -599,146 +581,48 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
 
    for (int t = 0; t <= T; t++) {
       if (t >= 1) {
-         if (a.maxActive > 0 && sh.tail > a.maxActive) {    // maximum-model pruning (HRec.c:1966-1985), as in k_decode_ord
-            int cnt = 0;
-            if (tid == 0) usel[0] = 0;
-            __syncthreads();
-            for (int i = tid; i < sh.tail; i += ORD_THREADS) if (c.seq[i] >= 0) cnt++;
-            if (cnt) atomicAdd(&usel[0], (unsigned)cnt);
-            __syncthreads();
-            if ((int)usel[0] > a.maxActive) {
-               if (tid == 0) { usel[1] = 0; usel[2] = (unsigned)a.maxActive; }
-               unsigned int mask = 0;
-               for (int pass = 0; pass < 4; pass++) {
-                  const int shift = 24 - 8 * pass;
-                  for (int i = tid; i < 256; i += ORD_THREADS) uhist[i] = 0;
-                  __syncthreads();
-                  const unsigned int prefix = usel[1];
-                  for (int i = tid; i < sh.tail; i += ORD_THREADS) {
-                     const int n = c.seq[i];
-                     if (n < 0) continue;
-                     unsigned int k = __float_as_uint((float)imax[n]);
-                     k ^= (k >> 31) ? 0xFFFFFFFFu : 0x80000000u;
-                     if ((k & mask) == prefix) atomicAdd(&uhist[(k >> shift) & 255], 1);
-                  }
-                  __syncthreads();
-                  if (tid == 0) {
-                     unsigned int skip = usel[2], cum = 0; int b = 255;
-                     for (; b > 0; b--) { if (cum + (unsigned)uhist[b] > skip) break; cum += (unsigned)uhist[b]; }
-                     usel[1] = prefix | ((unsigned)b << shift); usel[2] = skip - cum;
-                  }
-                  mask |= 255u << shift;
-                  __syncthreads();
+         if (a.maxActive > 0 && sh.tail > a.maxActive) {    // maximum-model pruning (HRec.c:1966-1985; dec_prune_threshold, decode_dev.h)
+            const float uth = dec_prune_threshold<ORD_THREADS>(sh.tail, a.maxActive, usel, uhist, [&](const int i, float &key) {
+               const int n = c.seq[i];
+               if (n < 0) return false;
+               key = (float)imax[n];
+               return true;
+            });
+            if (uth > (float)LSMALL)
+               for (int i = tid; i < sh.tail; i += ORD_THREADS) {
+                  const int n = c.seq[i];
+                  if (n < 0 || !((float)imax[n] < uth)) continue;
+                  TSet z; ts_null(z);
+                  c.seq[i] = -1; pos[n] = -1; imax[n] = LZERO; ex[n] = z;
+                  const int4 ni = N.nodeInfo[n];
+                  const int nt = ((ni.x & 15) == HTKAMD_NODE_HMM) ? ((ni.x >> 4) & 255) - 1 : 1;
+                  for (int q = 0; q < nt; q++) { cur[ni.y + q] = z; nxt[ni.y + q] = z; }
                }
-               unsigned int kk = usel[1];
-               kk ^= (kk >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-               const float uth = __uint_as_float(kk);
-               if (uth > (float)LSMALL)
-                  for (int i = tid; i < sh.tail; i += ORD_THREADS) {
-                     const int n = c.seq[i];
-                     if (n < 0 || !((float)imax[n] < uth)) continue;
-                     TSet z; ts_null(z);
-                     c.seq[i] = -1; pos[n] = -1; imax[n] = LZERO; ex[n] = z;
-                     const int4 ni = N.nodeInfo[n];
-                     const int nt = ((ni.x & 15) == HTKAMD_NODE_HMM) ? ((ni.x >> 4) & 255) - 1 : 1;
-                     for (int q = 0; q < nt; q++) { cur[ni.y + q] = z; nxt[ni.y + q] = z; }
-                  }
-            }
             __syncthreads();
          }
-         {  // the blanks out of the list
-            int *src = (int *)c.seq, *dst = (src == seqA) ? seqB : seqA;
-            const int tl = sh.tail;
-            int outBase = 0;
-            for (int b0 = 0; b0 < tl; b0 += ORD_THREADS) {
-               const int i = b0 + tid;
-               const int n = (i < tl) ? src[i] : -1;
-               const unsigned long long m = __ballot(n >= 0);
-               if (lane == 0) scan[wv] = __popcll(m);
-               __syncthreads();
-               int off = outBase;
-               for (int w = 0; w < wv; w++) off += scan[w];
-               int tot = 0;
-               for (int w = 0; w < ORD_THREADS / 64; w++) tot += scan[w];
-               if (n >= 0) { const int o = off + __popcll(m & ((1ull << lane) - 1ull)); dst[o] = n; pos[n] = o; }
-               outBase += tot;
-               __syncthreads();
-            }
-            c.seq = dst;
-            if (tid == 0) sh.tail = outBase;
-            __syncthreads();
-         }
-         // ---- pass 1 over the list's instances (k_decode_n's StepHMM1; StepWord1 for the rest)
+         ord_compact(c, seqA, seqB, scan);
+         // ---- pass 1 over the list's instances (set_step1; StepWord1 for the rest)
          const float gT = thr[0], nT = thr[2];
          double myGen = LZERO, myWord = LZERO;
          const int nLive = sh.tail;
          for (int li = tid; li < nLive; li += ORD_THREADS) {
             const int n = c.seq[li];
             const int4 ni = N.nodeInfo[n];
-            const int NS = (ni.x >> 4) & 255, t0 = ni.y;
             if ((ni.x & 15) != HTKAMD_NODE_HMM) {             // StepWord1 (HRec.c:1038): the sets' relative tokens stay as they are
-               TSet z = cur[t0]; z.like = LZERO; z.lm = 0.0f; z.path = -1; z.align = -1; z.n = 1; nxt[t0] = z;
-               TSet ze = ex[n]; ze.like = LZERO; ze.lm = 0.0f; ze.path = -1; ze.align = -1; ze.n = 1; ex[n] = ze;
+               const int t0 = ni.y;
+               TSet z = cur[t0]; ts_null_head(z); nxt[t0] = z;
+               TSet ze = ex[n]; ts_null_head(ze); ex[n] = ze;
                imax[n] = LZERO;
                continue;
             }
-            const float *tp = tpBase + ni.z;
             TSet exS; ts_null(exS);
             double mx = LZERO;
-            for (int j = 2; j < NS; j++) {
-               int lo = 1, hi = NS - 1;
-               while (lo < NS && !(tp[(lo - 1) * NS + (j - 1)] > LSMALL)) lo++;
-               while (hi > 1 && !(tp[(hi - 1) * NS + (j - 1)] > LSMALL)) hi--;
-               if (lo > hi) { lo = 1; hi = NS - 1; }
-               TSet res = cur[t0 + lo - 1];
-               res.like += tp[(lo - 1) * NS + (j - 1)];
-               for (int i = lo + 1; i <= hi; i++) {
-                  const TSet &si = cur[t0 + i - 1];
-                  ts_merge(res, si.like + tp[(i - 1) * NS + (j - 1)], si.lm, si.path, si, nT, a.nToks, ko, si.align);
-               }
-               if (res.like > gT) {
-                  const int st = N.hmmState[ni.w + (j - 2)];
-                  const float outp = a.score[ud.score0 + (size_t)(t - 1) * a.ns + N.stateSlot[st]];
-                  res.like += outp;
-                  if (res.like > mx) mx = res.like;
-                  if (a.alignMode & 2) {                       // pri->states (HRec.c:680-704, -DPHNALG): a record where a token enters state j
-                     const double alk = res.like - outp - res.lm * a.lmScale;
-                     const AlignRec *AL = a.al + (size_t)sel * a.alCap;
-                     if (res.align < 0 || AL[res.align].state != j || AL[res.align].node != n) { res.align = new_align(a, sel, n, j, alk, t - 1, res.align); res.ra[0] = res.align; }
-                     for (int q = 1; q < res.n; q++)
-                        if (res.ra[q] < 0 || AL[res.ra[q]].state != j || AL[res.ra[q]].node != n) res.ra[q] = new_align(a, sel, n, j, alk, t - 1, res.ra[q]);
-                  }
-               } else { res.like = LZERO; res.lm = 0.0f; res.path = -1; res.align = -1; res.n = 1; }
-               nxt[t0 + j - 1] = res;
-            }
-            { TSet z = cur[t0]; z.like = LZERO; z.lm = 0.0f; z.path = -1; z.align = -1; z.n = 1; nxt[t0] = z; }          // entry consumed
-            {
-               int lo = 2, hi = NS - 1;
-               while (lo < NS && !(tp[(lo - 1) * NS + (NS - 1)] > LSMALL)) lo++;
-               while (hi > 1 && !(tp[(hi - 1) * NS + (NS - 1)] > LSMALL)) hi--;
-               if (lo > hi) { lo = 2; hi = NS - 1; }
-               TSet res = nxt[t0 + lo - 1];
-               res.like += tp[(lo - 1) * NS + (NS - 1)];
-               for (int i = lo + 1; i <= hi; i++) {
-                  const TSet &si = nxt[t0 + i - 1];
-                  ts_merge(res, si.like + tp[(i - 1) * NS + (NS - 1)], si.lm, si.path, si, nT, a.nToks, ko, si.align);
-               }
-               if (res.like > LSMALL) {
-                  const double w = res.like + N.wdlk[n];
-                  if (w > myWord) myWord = w;
-                  if ((a.alignMode & 1) && !((ni.x >> 12) & 1)) {      // pri->models, not a tee model (HRec.c:762-776): the model's exit record per token
-                     const double alk = res.like - res.lm * a.lmScale;
-                     res.align = new_align(a, sel, n, -1, alk, t, res.align); res.ra[0] = res.align;
-                     for (int q = 1; q < res.n; q++) res.ra[q] = new_align(a, sel, n, -1, alk, t, res.ra[q]);
-                  }
-                  exS = res;
-               } else { exS = res; exS.like = LZERO; exS.lm = 0.0f; exS.path = -1; exS.align = -1; exS.n = 1; }
-            }
+            set_step1<true>(a, ud, sel, n, ni, tpBase + ni.z, cur, nxt, gT, nT, t, ko, exS, mx, myWord);
             if (mx > myGen) myGen = mx;
             ex[n] = exS; imax[n] = (double)(float)mx;
          }
-         const double genMax = o_block_max(myGen, red);
-         const double wordMax = o_block_max(myWord, red2);
+         const double genMax = dec_block_max<ORD_THREADS>(myGen, red);
+         const double wordMax = dec_block_max<ORD_THREADS>(myWord, red2);
          if (tid == 0) {
             float w = (float)(wordMax - a.wordBeam); if (w < (float)LSMALL) w = (float)LSMALL;
             float g = (float)(genMax - a.genBeam); if (g < (float)LSMALL) g = (float)LSMALL;
@@ -936,8 +820,8 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
       a.arcScore = (double *)ws.get(8 * (size_t)nu * maxLatArcs); a.total = (double *)ws.get(8 * (size_t)nu);
       if (listOrder) {
          ws.seek(WS_LIST);
-         a.seq = (int *)ws.get(sizeof(int) * (size_t)nu * 2 * seqCap); a.seqCap = seqCap; a.pos = (int *)ws.get(sizeof(int) * node); a.ooo = (unsigned char *)ws.get(node);
-         a.pathNode = (int *)ws.get(path * 4); a.pathFrame = (int *)ws.get(path * 4); a.pathExtra = (int)pathExtra;
+         a.list.seq = (int *)ws.get(sizeof(int) * (size_t)nu * 2 * seqCap); a.list.seqCap = seqCap; a.list.pos = (int *)ws.get(sizeof(int) * node); a.list.ooo = (unsigned char *)ws.get(node);
+         a.list.pathNode = (int *)ws.get(path * 4); a.list.pathFrame = (int *)ws.get(path * 4); a.list.pathExtra = (int)pathExtra;
       }
       if (alignMode) {
          ws.seek(WS_ALIGN);
@@ -958,7 +842,7 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
          a.net = N; a.utt = (const DecUtt *)dUtt; a.nUtt = nu; a.score = (const float *)dScoreT; a.ns = ns;
          a.genBeam = cfg->genBeam; a.wordBeam = cfg->wordBeam; a.nBeam = nBeam; a.lmScale = cfg->lmScale; a.wordPen = cfg->wordPen; a.prScale = cfg->prScale;
          a.nToks = nToks; a.maxActive = cfg->maxActive > 0 ? cfg->maxActive : 0; a.maxLatNodes = maxLatNodes; a.maxLatArcs = maxLatArcs;
-         const size_t lds = sizeof(TSet) * DEC_THREADS;
+         const size_t lds = sizeof(PSet) * DEC_THREADS;
          hipError_t e = hipSuccess;
          if (listOrder) { hipLaunchKernelGGL(k_decode_ord_n, dim3(nu), dim3(ORD_THREADS), 0, s, a); e = hipGetLastError(); d->lastTied += nu; }
          else {

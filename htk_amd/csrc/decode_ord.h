@@ -1,25 +1,12 @@
 // decode_ord.h -- HRec's instance list on the device: what the exact-order kernels (decode_ord.hip: 1-best; decode_n.hip: k_decode_ord_n,
-// token sets) share.  See decode_ord.hip for the design.
+// token sets) share -- the list and its upkeep.  See decode_ord.hip for the design.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "decode.h"
+#include "decode_dev.h"
 
 #define ORD_THREADS 256
 #define ORD_STACK 64               /* depth of ReOrderList's recursion (a chain of zero-time nodes) */
-
-__device__ __forceinline__ Tok o_null() { Tok t; t.like = LZERO; t.lm = 0.0f; t.path = -1; return t; }
-
-__device__ __forceinline__ double o_block_max(double v, double *red)
-{
-#pragma unroll
-   for (int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o); v = (w > v) ? w : v; }
-   __syncthreads();
-   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-   __syncthreads();
-   double r = red[0];
-   for (int i = 1; i < ORD_THREADS / 64; i++) r = (red[i] > r) ? red[i] : r;
-   return r;
-}
 
 // what the walking wavefront shares: LDS, written by lane 0 or by all lanes with the same value
 struct OrdShared {
@@ -95,3 +82,29 @@ __device__ __forceinline__ void o_attach(const OrdCtx &c, int n)
    else c.ooo[n] = 0;
 }
 
+// The blanks out of the list (its order stays): seq -> the other of the utterance's two buffers.  By the whole workgroup; scan:
+// ORD_THREADS / 64 ints of LDS.
+__device__ __forceinline__ void ord_compact(OrdCtx &c, int *seqA, int *seqB, int *scan)
+{
+   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+   int *src = (int *)c.seq, *dst = (src == seqA) ? seqB : seqA;
+   const int tl = c.sh->tail;
+   int outBase = 0;
+   for (int b0 = 0; b0 < tl; b0 += ORD_THREADS) {
+      const int i = b0 + tid;
+      const int n = (i < tl) ? src[i] : -1;
+      const unsigned long long m = __ballot(n >= 0);
+      if (lane == 0) scan[wv] = __popcll(m);
+      __syncthreads();
+      int off = outBase;
+      for (int w = 0; w < wv; w++) off += scan[w];
+      int tot = 0;
+      for (int w = 0; w < ORD_THREADS / 64; w++) tot += scan[w];
+      if (n >= 0) { const int o = off + __popcll(m & ((1ull << lane) - 1ull)); dst[o] = n; c.pos[n] = o; }
+      outBase += tot;
+      __syncthreads();
+   }
+   c.seq = dst;
+   if (tid == 0) c.sh->tail = outBase;
+   __syncthreads();
+}

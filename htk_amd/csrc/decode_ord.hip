@@ -20,7 +20,8 @@
 // stepped are the lanes (the tokens a node sends go to different nodes; attaching, which appends, is taken link by link).  Tokens,
 // exit tokens and instance maxima are the arrays k_decode uses; Path records are allocated one by one (StepWord2 may run twice on a node
 // in one frame -- "may be repeated", HRec.c:1046 -- and both records can stay referenced).
-// Output probabilities come from the same score block (K1, exact mode).  Tested against HVite on the tie files and sweeps
+// The list and its compaction are decode_ord.h's (shared with k_decode_ord_n, which has this walk in its token-set form); the pruning
+// threshold and the traceback are decode_dev.h's.  Output probabilities come from the same score block (K1, exact mode).  Tested against HVite on the tie files and sweeps
 // (tests/test_gpu_decode.py, tests/fuzz_parity.py) and against oracle/orc_decode.c, which walks the same list (oracle/orc_ilist.h).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -50,22 +51,22 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
    const int T = ud.T, u = ud.idx;
    Tok *tok = a.tok + ud.tok0, *ex = a.ex + ud.node0;
    volatile double *imax = a.imax + ud.node0;
-   volatile int *pos = oa.pos + ud.node0;
-   volatile unsigned char *ooo = oa.ooo + ud.node0;
-   int *seqA = oa.seq + (size_t)sel * 2 * oa.seqCap, *seqB = seqA + oa.seqCap;
-   const size_t pathCap = 3 * ((size_t)(T + 1) * N.nWordNodes) + (size_t)oa.pathExtra;      // as the host laid the records out (decode.hip)
-   int *pathPrev = a.pathPrev + ud.path0, *pathNode = oa.pathNode + ud.path0, *pathFrame = oa.pathFrame + ud.path0;
+   volatile int *pos = oa.list.pos + ud.node0;
+   volatile unsigned char *ooo = oa.list.ooo + ud.node0;
+   int *seqA = oa.list.seq + (size_t)sel * 2 * oa.list.seqCap, *seqB = seqA + oa.list.seqCap;
+   const size_t pathCap = 3 * ((size_t)(T + 1) * N.nWordNodes) + (size_t)oa.list.pathExtra;      // as the host laid the records out (decode.hip)
+   int *pathPrev = a.pathPrev + ud.path0, *pathNode = oa.list.pathNode + ud.path0, *pathFrame = oa.list.pathFrame + ud.path0;
    double *pathLike = a.pathLike + ud.path0; float *pathLm = a.pathLm + ud.path0;
    const bool tpInLds = N.nTpFloats <= 2048;
    if (tpInLds) for (int i = tid; i < N.nTpFloats; i += ORD_THREADS) ltp[i] = N.transP[i];
    const float *tpBase = tpInLds ? ltp : N.transP;
 
-   for (int i = tid; i < N.nTok; i += ORD_THREADS) tok[i] = o_null();
-   for (int i = tid; i < N.nNodes; i += ORD_THREADS) { ex[i] = o_null(); imax[i] = LZERO; pos[i] = -1; ooo[i] = 0; }
+   for (int i = tid; i < N.nTok; i += ORD_THREADS) tok[i] = dec_null();
+   for (int i = tid; i < N.nNodes; i += ORD_THREADS) { ex[i] = dec_null(); imax[i] = LZERO; pos[i] = -1; ooo[i] = 0; }
    if (tid == 0) { thr[0] = (float)LSMALL; thr[1] = (float)LSMALL; sh.tail = 0; sh.nPath = 0; sh.status = 0; sh.base = 0; sh.cn = 0; }
    __syncthreads();
    OrdCtx c;
-   c.N = &N; c.seq = seqA; c.pos = pos; c.ooo = ooo; c.imax = imax; c.seqCap = oa.seqCap; c.sh = &sh;
+   c.N = &N; c.seq = seqA; c.pos = pos; c.ooo = ooo; c.imax = imax; c.seqCap = oa.list.seqCap; c.sh = &sh;
    if (tid == 0) {                                          // StartRecognition (HRec.c:1884): the initial node's instance, a token of likelihood 0
       o_attach(c, N.initial);
       Tok z; z.like = 0.0; z.lm = 0.0f; z.path = -1;
@@ -76,76 +77,26 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
    for (int t = 0; t <= T; t++) {
       if (t >= 1) {
          // ---- maximum-model pruning (ProcessObservation HRec.c:1966-1985): more than maxActive instances on the list -> those whose max
-         // lies below the (maxActive + 1)-th largest (as floats) are detached.  Radix select on the float keys, as in k_decode.
+         // lies below the (maxActive + 1)-th largest (as floats) are detached (the threshold: dec_prune_threshold, decode_dev.h)
          if (a.maxActive > 0 && sh.tail > a.maxActive) {
-            int cnt = 0;
-            if (tid == 0) usel[0] = 0;
-            __syncthreads();
-            for (int i = tid; i < sh.tail; i += ORD_THREADS) if (c.seq[i] >= 0) cnt++;
-            if (cnt) atomicAdd(&usel[0], (unsigned)cnt);
-            __syncthreads();
-            if ((int)usel[0] > a.maxActive) {
-               if (tid == 0) { usel[1] = 0; usel[2] = (unsigned)a.maxActive; }
-               unsigned int mask = 0;
-               for (int pass = 0; pass < 4; pass++) {
-                  const int shift = 24 - 8 * pass;
-                  for (int i = tid; i < 256; i += ORD_THREADS) uhist[i] = 0;
-                  __syncthreads();
-                  const unsigned int prefix = usel[1];
-                  for (int i = tid; i < sh.tail; i += ORD_THREADS) {
-                     const int n = c.seq[i];
-                     if (n < 0) continue;
-                     unsigned int k = __float_as_uint((float)imax[n]);
-                     k ^= (k >> 31) ? 0xFFFFFFFFu : 0x80000000u;
-                     if ((k & mask) == prefix) atomicAdd(&uhist[(k >> shift) & 255], 1);
-                  }
-                  __syncthreads();
-                  if (tid == 0) {
-                     unsigned int skip = usel[2], cum = 0; int b = 255;
-                     for (; b > 0; b--) { if (cum + (unsigned)uhist[b] > skip) break; cum += (unsigned)uhist[b]; }
-                     usel[1] = prefix | ((unsigned)b << shift); usel[2] = skip - cum;
-                  }
-                  mask |= 255u << shift;
-                  __syncthreads();
+            const float uth = dec_prune_threshold<ORD_THREADS>(sh.tail, a.maxActive, usel, uhist, [&](const int i, float &key) {
+               const int n = c.seq[i];
+               if (n < 0) return false;
+               key = (float)imax[n];
+               return true;
+            });
+            if (uth > (float)LSMALL)
+               for (int i = tid; i < sh.tail; i += ORD_THREADS) {
+                  const int n = c.seq[i];
+                  if (n < 0 || !((float)imax[n] < uth)) continue;
+                  c.seq[i] = -1; pos[n] = -1; imax[n] = LZERO; ex[n] = dec_null();
+                  const int4 ni = N.nodeInfo[n];
+                  const int nt = ((ni.x & 15) == HTKAMD_NODE_HMM) ? ((ni.x >> 4) & 255) - 1 : 1;
+                  for (int q = 0; q < nt; q++) tok[ni.y + q] = dec_null();
                }
-               unsigned int kk = usel[1];
-               kk ^= (kk >> 31) ? 0x80000000u : 0xFFFFFFFFu;
-               const float uth = __uint_as_float(kk);
-               if (uth > (float)LSMALL)
-                  for (int i = tid; i < sh.tail; i += ORD_THREADS) {
-                     const int n = c.seq[i];
-                     if (n < 0 || !((float)imax[n] < uth)) continue;
-                     c.seq[i] = -1; pos[n] = -1; imax[n] = LZERO; ex[n] = o_null();
-                     const int4 ni = N.nodeInfo[n];
-                     const int nt = ((ni.x & 15) == HTKAMD_NODE_HMM) ? ((ni.x >> 4) & 255) - 1 : 1;
-                     for (int q = 0; q < nt; q++) tok[ni.y + q] = o_null();
-                  }
-            }
             __syncthreads();
          }
-         // ---- the blanks out of the list (its order stays): seq -> the other buffer
-         {
-            int *src = (int *)c.seq, *dst = (src == seqA) ? seqB : seqA;
-            const int tl = sh.tail;
-            int outBase = 0;
-            for (int b0 = 0; b0 < tl; b0 += ORD_THREADS) {
-               const int i = b0 + tid;
-               const int n = (i < tl) ? src[i] : -1;
-               const unsigned long long m = __ballot(n >= 0);
-               if (lane == 0) scan[wv] = __popcll(m);
-               __syncthreads();
-               int off = outBase;
-               for (int w = 0; w < wv; w++) off += scan[w];
-               int tot = 0;
-               for (int w = 0; w < ORD_THREADS / 64; w++) tot += scan[w];
-               if (n >= 0) { const int o = off + __popcll(m & ((1ull << lane) - 1ull)); dst[o] = n; pos[n] = o; }
-               outBase += tot;
-               __syncthreads();
-            }
-            c.seq = dst;
-            if (tid == 0) sh.tail = outBase;
-            __syncthreads();
-         }
+         ord_compact(c, seqA, seqB, scan);
          // ---- pass 1: StepInst1 on every instance (no order in it: the beams' tops are maxima)
          const float gT = thr[0];                           // threshold of the previous frame
          double myGen = LZERO, myWord = LZERO;
@@ -153,22 +104,22 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
          for (int i = tid; i < nLive; i += ORD_THREADS) {
             const int n = c.seq[i];
             const int4 ni = N.nodeInfo[n];
-            if ((ni.x & 15) != HTKAMD_NODE_HMM) { tok[ni.y] = o_null(); ex[n] = o_null(); imax[n] = LZERO; continue; }     // StepWord1 (HRec.c:1038)
+            if ((ni.x & 15) != HTKAMD_NODE_HMM) { tok[ni.y] = dec_null(); ex[n] = dec_null(); imax[n] = LZERO; continue; }     // StepWord1 (HRec.c:1038)
             const int NS = (ni.x >> 4) & 255, t0 = ni.y;
             const float *tp = tpBase + ni.z;
             Tok s[DEC_MAXN];
             bool live = false;
 #pragma unroll
-            for (int q = 1; q < DEC_MAXN; q++) { s[q] = o_null(); if (q < NS) s[q] = tok[t0 + q - 1]; }
+            for (int q = 1; q < DEC_MAXN; q++) { s[q] = dec_null(); if (q < NS) s[q] = tok[t0 + q - 1]; }
 #pragma unroll
             for (int q = 1; q < DEC_MAXN; q++) if (q < NS && s[q].like > LSMALL) live = true;
-            Tok exT = o_null();
+            Tok exT = dec_null();
             double mx = LZERO;
             if (live) {
                Tok nw[DEC_MAXN];
 #pragma unroll
                for (int j = 2; j < DEC_MAXN; j++) {
-                  nw[j] = o_null();
+                  nw[j] = dec_null();
                   if (j < NS) {
                      int lo = 1, hi = NS - 1;                 // CreateSEIndex (HRec.c:1403)
                      while (lo < NS && !(tp[(lo - 1) * NS + (j - 1)] > LSMALL)) lo++;
@@ -209,15 +160,15 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
                      if (w > myWord) myWord = w;
                   }
                }
-               tok[t0] = o_null();                            // entry consumed
+               tok[t0] = dec_null();                            // entry consumed
 #pragma unroll
                for (int j = 2; j < DEC_MAXN; j++) if (j < NS) tok[t0 + j - 1] = nw[j];
                if (mx > myGen) myGen = mx;
             }
             ex[n] = exT; imax[n] = (double)(float)mx;         // inst->max is a LogFloat (HRec.c:138)
          }
-         const double genMax = o_block_max(myGen, red);
-         const double wordMax = o_block_max(myWord, red2);
+         const double genMax = dec_block_max<ORD_THREADS>(myGen, red);
+         const double wordMax = dec_block_max<ORD_THREADS>(myWord, red2);
          if (tid == 0) {
             float w = (float)(wordMax - a.wordBeam); if (w < (float)LSMALL) w = (float)LSMALL;
             float g = (float)(genMax - a.genBeam); if (g < (float)LSMALL) g = (float)LSMALL;
@@ -248,9 +199,9 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
                const int4 ni = N.nodeInfo[n];
                const int kind = ni.x & 15, NS = (ni.x >> 4) & 255, t0 = ni.y;
                if (nmax < gT) {                               // DetachInst (HRec.c:1270): every token of the instance goes
-                  if (lane == 0) { o_blank(c, n); pos[n] = -1; imax[n] = LZERO; ex[n] = o_null(); }
+                  if (lane == 0) { o_blank(c, n); pos[n] = -1; imax[n] = LZERO; ex[n] = dec_null(); }
                   const int nt = (kind == HTKAMD_NODE_HMM) ? NS - 1 : 1;
-                  if (lane < nt) tok[t0 + lane] = o_null();
+                  if (lane < nt) tok[t0 + lane] = dec_null();
                   __threadfence_block();
                   continue;
                }
@@ -281,7 +232,7 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
                   }
                }
                Tok tk = e;
-               if (kind != HTKAMD_NODE_HMM && tk.like < wT) tk = o_null();
+               if (kind != HTKAMD_NODE_HMM && tk.like < wT) tk = dec_null();
                if (tk.like > gT) {
                   const int k0 = N.linkOff[n], k1 = N.linkOff[n + 1];
                   const bool dup = N.dupDest[n] != 0;
@@ -335,47 +286,13 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
       if (sh.status != 0) break;
    }
 
-   // ---- CompleteRecognition (HRec.c:2054) + LatFromPaths (:1512) + TranscriptionFromLattice (:2176) for the 1-best chain
+   // ---- CompleteRecognition: the 1-best chain (dec_traceback, decode_dev.h)
    if (tid == 0) {
-      int nW = 0;
-      // (ADVICE r04: a capacity of the LIST walk is no reason to lose an answer the batch kernel has already given -- a tie-free order is
+      // (a capacity of the LIST walk is no reason to lose an answer the batch kernel has already given -- a tie-free order is
       // one valid order of HRec's; the status codes -4 / -5 / -6 then never reach the caller in the default mode)
       if (sh.status != 0 && oa.keepFast && a.nWords[u] >= 0) return;
-      a.total[u] = LZERO; a.finalLm[u] = 0.0f;
-      if (sh.status != 0) nW = sh.status;
-      else {
-         const Tok fin = (pos[N.final] >= 0) ? ex[N.final] : o_null();
-         const int fp = fin.path;
-         if (fp >= 0) {
-            a.total[u] = fin.like; a.finalLm[u] = fin.lm;
-            for (int p = fp; p >= 0; p = pathPrev[p]) nW++;
-            if (nW > a.maxWords) nW = -3;
-            else {
-               int w = nW;
-               for (int p = fp; p >= 0;) {
-                  const int prev = pathPrev[p];
-                  const double prlk = (prev >= 0) ? pathLike[prev] : 0.0;
-                  const double wp = a.wordPen;
-                  const float plm = pathLm[p];
-                  float aclike = (float)(pathLike[p] - prlk - plm * a.lmScale - wp);
-                  const int node = pathNode[p];
-                  const float pr = N.pronProb[node];
-                  aclike -= pr * a.prScale;
-                  const float sc = (float)((double)((aclike * 1.0f + plm * a.lmScale) + pr * a.prScale) + (double)a.wordPen);
-                  w--;
-                  a.wordPron[ud.out0 + w] = N.model[node];
-                  a.wordEnd[ud.out0 + w] = pathFrame[p];
-                  a.wordStart[ud.out0 + w] = (prev >= 0) ? pathFrame[prev] : 0;
-                  a.wordScore[ud.out0 + w] = sc;
-                  a.wordLm[ud.out0 + w] = plm;
-                  a.wordAc[ud.out0 + w] = aclike;
-                  a.wordLike[ud.out0 + w] = pathLike[p];
-                  p = prev;
-               }
-            }
-         } else nW = -1;
-      }
-      a.nWords[u] = nW;
+      if (sh.status != 0) { a.total[u] = LZERO; a.finalLm[u] = 0.0f; a.nWords[u] = sh.status; }
+      else dec_traceback(a, ud, u, (pos[N.final] >= 0) ? ex[N.final] : dec_null(), PathView{pathFrame, pathNode, N.nWordNodes, N.wordNode});
    }
 }
 

@@ -12,6 +12,8 @@ from decode_util import GOLD, load_decode_case, parse_opts
 
 NB = os.path.join(GOLD, "nbest")
 TAGS = json.load(open(os.path.join(NB, "index.json")))
+# the tags without alignment records (-m / -f): the static pull order (ORDER_FAST) can run them
+STATIC_TAGS = [t for t in TAGS if not {"-m", "-f"} & set(json.load(open(os.path.join(NB, t, "nbest.json")))["opts"].split())]
 
 
 def _case(native, tag):
@@ -95,6 +97,36 @@ def test_token_set_kernel_equals_oracle_and_hvite(native, oracle, tag, tmp_path)
         _check_files(native, got, net, meta, tag, u, tmp_path, mmf)
 
 
+def _arc_key(l):
+    """Arcs by what they join -- (start frame, start net node, end frame, end net node, arcLm) -- with arcAc last: the order in which the
+    arcs are listed and the numbering of the lattice nodes are not part of the lattice."""
+    return sorted(zip(l["nodeFrame"][l["arcStart"]].tolist(), l["nodeNet"][l["arcStart"]].tolist(), l["nodeFrame"][l["arcEnd"]].tolist(),
+                      l["nodeNet"][l["arcEnd"]].tolist(), l["arcLm"].tolist(), l["arcAc"].tolist()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", STATIC_TAGS)
+def test_token_set_kernel_static_order_matches_oracle(native, oracle, tag):
+    """k_decode_n, the token-set kernel in the static pull order (ORDER_FAST): the oracle's best token exactly (a double, whatever the order
+    of the merges), the oracle's arcs, and their acoustic scores to 1e-3 (relative likelihoods re-based in another association, as in
+    test_token_set_kernel_wide_fan_in).  The three -u tags are the only cover of this kernel's pruning select."""
+    meta, mmf, net, feats, p = _case(native, tag)
+    model = native.Model(mmf.packed())
+    om = oracle.Model(mmf.packed())
+    dec = native.Decoder(model, net, lmScale=p["lmScale"])
+    dec.set_order(native.ORDER_FAST)
+    lats = dec.run_lattice(feats, meta["nToks"], **p)
+    assert dec.last_tied() == 0                                      # no utterance went through the list kernel
+    for u, X in enumerate(feats):
+        ref = oracle.decode_nbest(om, X, net.arrays(), meta["nToks"], **p)
+        got = lats[u]
+        assert got is not None and ref is not None
+        assert got["total"] == ref["total"], (tag, u)
+        g, r = _arc_key(got), _arc_key(ref)
+        assert [x[:5] for x in g] == [x[:5] for x in r], (tag, u)
+        assert np.allclose([x[5] for x in g], [x[5] for x in r], atol=1e-3), (tag, u)
+
+
 @pytest.mark.gpu
 def test_token_set_kernel_edge_cases(native):
     mmf, net, feats, _ = load_decode_case(native, "bigram")
@@ -138,13 +170,15 @@ def test_token_set_kernel_wide_fan_in(native, oracle, tmp_path):
     mmf = native.Mmf(files=[str(d / "MMF")], hmm_list=str(d / "hmmlist"))
     net = native.Net(str(d / "net.slf"), str(d / "dict"), mmf)
     model = native.Model(mmf.packed()); om = oracle.Model(mmf.packed())
-    lats = native.Decoder(model, net).run_lattice(s.feats, 3, genBeam=150.0)
-    for u, got in enumerate(lats):
-        ref = oracle.decode_nbest(om, s.feats[u], net.arrays(), 3, genBeam=150.0)
-        assert got is not None and ref is not None and got["total"] == ref["total"]
-        key = lambda l: sorted(zip(l["nodeFrame"][l["arcStart"]].tolist(), l["nodeNet"][l["arcStart"]].tolist(), l["nodeFrame"][l["arcEnd"]].tolist(),
-                                   l["nodeNet"][l["arcEnd"]].tolist(), l["arcLm"].tolist(), l["arcAc"].tolist()))
-        g, r = key(got), key(ref)
-        assert len(g) == len(r) and len(g) > 50
-        assert [x[:5] for x in g] == [x[:5] for x in r]
-        assert np.allclose([x[5] for x in g], [x[5] for x in r], atol=1e-3)
+    dec = native.Decoder(model, net)
+    refs = [oracle.decode_nbest(om, X, net.arrays(), 3, genBeam=150.0) for X in s.feats]
+    # the list kernel, then the static order (k_decode_n: the only shape that reaches its partial sets of a wide node)
+    for order in (native.ORDER_AUTO, native.ORDER_FAST):
+        dec.set_order(order)
+        lats = dec.run_lattice(s.feats, 3, genBeam=150.0)
+        for got, ref in zip(lats, refs):
+            assert got is not None and ref is not None and got["total"] == ref["total"]
+            g, r = _arc_key(got), _arc_key(ref)
+            assert len(g) == len(r) and len(g) > 50
+            assert [x[:5] for x in g] == [x[:5] for x in r]
+            assert np.allclose([x[5] for x in g], [x[5] for x in r], atol=1e-3)

@@ -19,7 +19,6 @@ def main():
     model = capi.Model(pk)
     d = tempfile.mkdtemp()
     names = ["p%d" % i for i in range(V)]
-    synth.write_mmf_packed(os.path.join(d, "MMF"), pk, names) if False else None
     # the network needs only name -> physical index: write a tiny stand-in HMM list + dict and reuse the packed model
     # (the Mmf object is only used by the builder for name lookup)
     t0 = time.time()
