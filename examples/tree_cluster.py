@@ -3,7 +3,8 @@ statistics file and a tied-state set ready for mix-up.
 
     python examples/tree_cluster.py tree.hed hmmdefs triphones stats -o tied.mmf [--trees trees] [--no-merge] [--no-leaf-stats]
 
-The edit script may hold RO, TR, QS, TB and ST only; any other command is refused by name.  --no-merge / --no-leaf-stats are HHEd's
+The edit script may hold RO, LS, TR, QS, TB and ST, and for data-driven clustering TC, NC and TI (furthest-neighbour clustering of the
+listed states on the device; a script needs no TB then); any other command is refused by name.  --no-merge / --no-leaf-stats are HHEd's
 configuration variables TREEMERGE = F / USELEAFSTATS = F.  The trees file is what the reference's LT + AU read to synthesise unseen
 triphones (not built here)."""
 import argparse
@@ -27,10 +28,10 @@ def main(argv=None):
     mmf = capi.Mmf([a.mmf], hmm_list=a.hmmlist)
     before = mmf.desc.numStates
     warn = treeclust.run_script(mmf, sc, stats_path=a.stats, merge=not a.no_merge, leaf_stats=not a.no_leaf_stats, base_dir=os.path.dirname(os.path.abspath(a.script)))
-    if warn:
+    if isinstance(warn, str):
         print(warn, file=sys.stderr)
     mmf.write(mmf.packed(), one_file=a.out)
-    print("tree_cluster: %d trees, %d states -> %d" % (len(sc.specs), before, mmf.desc.numStates))
+    print("tree_cluster: %d trees, %d TC / NC commands, %d states -> %d" % (len(sc.specs), sum(c[0] in ("TC", "NC") for c in sc.commands), before, mmf.desc.numStates))
 
 
 if __name__ == "__main__":

@@ -1070,6 +1070,36 @@ def tree_split_sums(item_stats, node_items, answers, stream=None) -> np.ndarray:
     return out
 
 
+class ClusterSpec(C.Structure):
+    _fields_ = [("byCount", C.c_int), ("value", C.c_float), ("macro", C.c_char_p), ("items", C.c_char_p)]
+
+
+def cluster_merges(idist, num_req: int = 1, threshold: float = 1.0e15, occ=None, outlier: float = 0.0) -> np.ndarray:
+    """Test aid (htkamd_cluster_merges): the merge loop of HHEd's Clustering (and RemOutliers when `occ` is given) on a symmetric distance
+    matrix; int32[nMerges, 2], the groups (i, j) of every merge, 1-based in the numbering current at that merge."""
+    d = np.ascontiguousarray(idist, np.float32)
+    N = d.shape[0]
+    if d.shape != (N, N):
+        raise HtkAmdError("cluster_merges: a square matrix is expected, got %s" % (d.shape,))
+    oc = None if occ is None else np.ascontiguousarray(occ, np.float32)
+    if oc is not None and oc.shape != (N,):
+        raise HtkAmdError("cluster_merges: %s occupations for %d items" % (oc.shape, N))
+    out = np.zeros((max(N, 1), 2), np.int32); n = C.c_int(0)
+    check(lib().htkamd_cluster_merges(_p(d), C.c_int(N), _p(oc) if oc is not None else None, C.c_int(num_req), C.c_float(threshold), C.c_float(outlier),
+                                      _p(out), C.byref(n)), "cluster_merges")
+    return out[:n.value].copy()
+
+
+def state_distances(mmf: "Mmf", items: str, stream=None) -> np.ndarray:
+    """Test aid (htkamd_state_distances): HHEd's StateDistance between the states of an item list, float32[n, n] in the list's order."""
+    n = C.c_int(0)
+    check(lib().htkamd_state_distances(mmf.h, items.encode(), None, C.c_int(0), C.byref(n), _stream(stream)), "state_distances")
+    out = np.zeros((n.value, n.value), np.float32)
+    if n.value:
+        check(lib().htkamd_state_distances(mmf.h, items.encode(), _p(out), C.c_int(out.size), C.byref(n), _stream(stream)), "state_distances")
+    return out
+
+
 class Mmf:
     """htkamd_mmf holder: LoadHMMSet / SaveHMMSet for text model definitions (htk_amd/host/mmf.c)."""
 
@@ -1177,6 +1207,32 @@ class Mmf:
                                             str(trees_path).encode() if trees_path else None, _stream(stream)), "mmf_tree_cluster")
         msg = lib().htkamd_last_error().decode()
         return msg if "warning" in msg else None
+
+    def data_cluster(self, occ, specs, outlier: float = -1.0, stream=None):
+        """HHEd's TC / NC commands on the loaded set (htkamd_mmf_data_cluster): `occ` the state occupations (read_stats) or None when no
+        statistics are loaded (no outlier phase), `specs` [("TC", threshold, macro, item list) | ("NC", count, macro, item list)] in
+        script order.  Returns the number of clusters per command; `last_warning` holds the call's warning (an empty list) or None."""
+        if occ is not None:
+            occ = np.ascontiguousarray(occ, np.float32)
+            if occ.shape != (self.desc.numStates,):
+                raise HtkAmdError("data_cluster: %s occupations for %d states" % (occ.shape, self.desc.numStates))
+        for sp in specs:
+            if sp[0] not in ("TC", "NC"):
+                raise HtkAmdError("data_cluster: command %s (TC or NC expected)" % (sp[0],))
+        keep = [(str(m).encode(), str(i).encode()) for (_, _, m, i) in specs]
+        cs = (ClusterSpec * max(len(specs), 1))(*[ClusterSpec(1 if specs[k][0] == "NC" else 0, float(specs[k][1]), keep[k][0], keep[k][1]) for k in range(len(specs))])
+        nc = np.zeros(max(len(specs), 1), np.int32)
+        check(lib().htkamd_mmf_data_cluster(self.h, _p(occ) if occ is not None else None, C.c_float(outlier), cs, C.c_int(len(specs)), _p(nc), _stream(stream)),
+              "mmf_data_cluster")
+        msg = lib().htkamd_last_error().decode()
+        self.last_warning = msg if "warning" in msg else None
+        return nc[:len(specs)].tolist()
+
+    def tie(self, macro: str, items: str):
+        """HHEd's TI command for .state[i] and .transP item lists (htkamd_mmf_tie); host only."""
+        check(lib().htkamd_mmf_tie(self.h, str(macro).encode(), str(items).encode()), "mmf_tie")
+        msg = lib().htkamd_last_error().decode()
+        self.last_warning = msg if "warning" in msg else None
 
     def write(self, params: dict, one_file=None, out_dir=None, binary=False):
         g = params.get("gconst")

@@ -49,6 +49,23 @@ int  htkamd_tree_dev_totals(htkamd_tree_dev *t, const htkamd_tree_node *nodes, i
 int  htkamd_tree_dev_block(htkamd_tree_dev *t, int node, float *blk /*[nQ+1][2][C]*/);      /* of the last htkamd_tree_dev_split */
 void htkamd_tree_dev_close(htkamd_tree_dev *t);
 
+/* ---- data-driven clustering: the device side (csrc/datacluster.hip) as host/treeclust.c drives it ----
+ * The commands of a call own consecutive item ranges (off = the items before it).  The distances come from exactly one of: idist (the
+ * caller's [n][n] matrices, command after command), mean / var (a row of V values per item: Divergence), or desc / itemState (the set
+ * and every item's state: GDistance over the exact scoring path).  merges: per command at 2 * off the pairs (i, j), 1-based in the
+ * numbering current at that merge; nMerges[command] how many. */
+#define HTKAMD_DC_MAXITEMS 3000                        /* items of one command: five words of LDS each */
+typedef struct { int off, n, numReq; float threshold; } htkamd_dc_cmd;
+typedef struct {
+   int nCmds; const htkamd_dc_cmd *cmds; int nItems;
+   const float *idist;
+   const float *mean, *var; int V;
+   const htkamd_model_desc *desc; const int *itemState;
+   const float *occ; float outlierThresh;              /* occ: per item, or NULL = no outlier phase */
+   int noMerge;                                        /* distances only */
+} htkamd_dc_job;
+int  htkamd_dc_dev_run(const htkamd_dc_job *job, float *idistOut /* or NULL */, int *merges /*[2 * nItems]*/, int *nMerges /*[nCmds]*/, void *stream);
+
 /* device LAdd table: 4 intervals per unit of d over [minLogExp, 0] = [-23.03, 0], degree-10 Taylor rows (8 KB) */
 #define LADD_INV_H 4
 #define LADD_DEG   10

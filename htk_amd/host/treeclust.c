@@ -18,12 +18,13 @@
 #include "mmf_priv.h"
 
 /* The device side is in the HIP part of the library.  The host files are also built on their own (the sanitizer build of
-   tests/test_host_sanitizers.py): there the five entry points are absent, and a call that needs them says so. */
+   tests/test_host_sanitizers.py): there the device entry points are absent, and a call that needs them says so. */
 #pragma weak htkamd_tree_dev_open
 #pragma weak htkamd_tree_dev_split
 #pragma weak htkamd_tree_dev_totals
 #pragma weak htkamd_tree_dev_block
 #pragma weak htkamd_tree_dev_close
+#pragma weak htkamd_dc_dev_run
 
 #define GROW_INT(p, n, cap) do { if ((n) + 1 > (cap)) { (cap) = (cap) * 2 + 16; (p) = (int *)realloc((p), sizeof(int) * (size_t)(cap)); } } while (0)
 
@@ -152,8 +153,9 @@ static void tc_ident(const struct htkamd_mmf *s, const int *walk, const char *pa
 /* The items of "{ hname.state[i] , ... }" in the order of the reference's list.  A set's models are collected by prepending (PHIdent ->
    AddItem), PState walks that list and prepends again: within a set the items stand in walk order, and a later set stands BEFORE an
    earlier one.  Anything but single-index state items is refused. */
-static int tc_parse_items(const struct htkamd_mmf *s, const char *text, tc_item **out, int *nOut)
+static int tc_parse_items_typed(const struct htkamd_mmf *s, const char *text, tc_item **out, int *nOut, char *type /* NULL: states only; else 's' or 't' comes back */)
 {
+   char seen = 0;
    tc_src r = { text };
    tc_item *items = NULL; int nI = 0;
    int *walk = tc_logical_walk(s);
@@ -188,8 +190,13 @@ static int tc_parse_items(const struct htkamd_mmf *s, const char *text, tc_item 
          char key[16]; int n = 0;
          while (isalpha((unsigned char)*r.p) && n < 15) key[n++] = (char)toupper((unsigned char)*r.p++);
          key[n] = 0;
-         if (strcmp(key, "STATE")) why = "only .state[i] items are clustered (transP and the like are not)";
+         if (type && !strcmp(key, "TRANSP")) {             /* AddTransP (HUtil.c:767): an item per model, j = 0 */
+            if (seen == 's') why = "items of different types in one list";
+            seen = 't';
+         } else if (strcmp(key, "STATE")) why = "only .state[i] items are clustered (transP and the like are not)";
+         else if (seen == 't') why = "items of different types in one list";
          else {
+            seen = 's';
             tc_skip(&r);
             if (*r.p != '[') why = "[ expected after state";
             else {
@@ -211,13 +218,14 @@ static int tc_parse_items(const struct htkamd_mmf *s, const char *text, tc_item 
       if (why) { free(phys); TC_BAD("item list \"%s\": %s", text, why); }
       /* this set's items go in front of the earlier sets' */
       int add = 0;
-      for (int k = 0; k < nP; k++) if (j >= 2 && j < s->hm[phys[k]].N) add++;
+      for (int k = 0; k < nP; k++) if (seen == 't' || (j >= 2 && j < s->hm[phys[k]].N)) add++;
       tc_item *ni = (tc_item *)malloc(sizeof(tc_item) * (size_t)(nI + add + 1));
       int m = 0;
-      for (int k = 0; k < nP; k++) if (j >= 2 && j < s->hm[phys[k]].N) { ni[m].phys = phys[k]; ni[m].j = j; m++; }
+      for (int k = 0; k < nP; k++) if (seen == 't' || (j >= 2 && j < s->hm[phys[k]].N)) { ni[m].phys = phys[k]; ni[m].j = j; m++; }
       if (nI) memcpy(ni + m, items, sizeof(tc_item) * (size_t)nI);
       free(items); free(phys);
       items = ni; nI += add;
+      tc_skip(&r);
       if (*r.p == ',') { r.p++; continue; }
       if (*r.p != '}') TC_BAD("item list: } expected in \"%s\"", text);
       break;
@@ -227,8 +235,11 @@ done:
    free(walk);
    if (rc) { free(items); items = NULL; nI = 0; }
    *out = items; *nOut = nI;
+   if (type) *type = seen;
    return rc;
 }
+
+static int tc_parse_items(const struct htkamd_mmf *s, const char *text, tc_item **out, int *nOut) { return tc_parse_items_typed(s, text, out, nOut, NULL); }
 
 int htkamd_mmf_item_list(const htkamd_mmf *s, const char *itemList, int *phys, int *state, int cap, int *n)
 {
@@ -733,4 +744,269 @@ done:
    free(tr); free(kq); free(ans); free(owner); free(stats); free(itemCol); free(idx); free(rec); free(slotTree); free(slotNode); free(newSeq); free(batch); free(tots);
    if (!rc && warn[0]) htkamd_set_error("%s", warn);
    return rc;
+}
+
+/* ------------------------------------------------------------------------------------------ data-driven clustering: TC / NC / TI
+ * Restated from the reference: ClusterCommand (HHEd.c:4239), Clustering :2005 (BuildCVec :1901, SetIDist :1845, MergeGroups :1887, RemOutliers :1975),
+ * TieCommand :4102, ApplyTie :1515, TieState :1021 with TypicalState :990, TieTrans :1049.  The distances and the merge loop run on the
+ * device (csrc/datacluster.hip); the host resolves the item lists, replays the merge log into member chains and ties. */
+
+/* TieState on the holder: the listed states (list order) become one ~s macro, the typical one is kept */
+static void dc_tie_states(struct htkamd_mmf *s, const tc_item *il, int cnt, const char *macName, int *seq, int *newSeq)
+{
+   float gmax = LZERO; int imax = -1;
+   for (int k = 0; k < cnt; k++) {
+      const mmf_state *st = &s->st[s->hm[il[k].phys].state[il[k].j - 1]];
+      float gsum = 0;
+      for (int m = 0; m < st->nMix; m++)
+         if (s->wt[st->comp0 + m] > MINMIX) gsum += s->gconst[s->cg[st->comp0 + m]]; else gsum -= 200.0;
+      if (gsum > gmax) { gmax = gsum; imax = k; }
+   }
+   if (imax < 0) imax = 0;
+   const int keep = s->hm[il[imax].phys].state[il[imax].j - 1];
+   s->st[keep].name = strdup(macName);
+   s->st[keep].src = 0;
+   newSeq[keep] = (*seq)++;
+   for (int k = 0; k < cnt; k++) s->hm[il[k].phys].state[il[k].j - 1] = keep;
+}
+
+static void dc_fix_gconsts(struct htkamd_mmf *s)        /* FixAllGConsts (Clustering :2019, TieState :1027) */
+{
+   for (int g = 0; g < s->nG; g++) { htkamd_host_fix_diag_gconst(s->vecSize, s->var + (size_t)g * s->vecSize, s->gconst + g); s->hasG[g] = 1; }
+   s->d.gconst = s->gconst;
+}
+
+static int dc_check_set(const struct htkamd_mmf *s, const char *who)
+{
+   if (s->nStreams > 1) { htkamd_set_error("%s: a set with more than one stream (%d) is not supported", who, s->nStreams); return HTKAMD_EMODEL; }
+   if (s->fullc) { htkamd_set_error("%s: FULLC sets are not supported", who); return HTKAMD_EMODEL; }
+   if (s->tiedMix) { htkamd_set_error("%s: tied-mixture sets are not supported (TDistance)", who); return HTKAMD_EMODEL; }
+   if (strstr(s->kind, "DISCRETE")) { htkamd_set_error("%s: discrete sets are not supported (DDistance)", who); return HTKAMD_EMODEL; }
+   return HTKAMD_OK;
+}
+
+static int dc_check_state_item(const struct htkamd_mmf *s, const tc_item *it, const char *who)
+{
+   const mmf_state *st = &s->st[s->hm[it->phys].state[it->j - 1]];
+   if (st->name) {
+      htkamd_set_error("%s: state %d of model %s is the ~s macro %s already: tying tied states is not supported", who, it->j, s->hm[it->phys].name, st->name);
+      return HTKAMD_EMODEL;
+   }
+   for (int m = 0; m < st->nMix; m++) {
+      const int g = s->cg[st->comp0 + m];
+      if ((g < s->capGN && s->gName[g]) || (g < s->capMac && (s->gMeanMac[g] >= 0 || s->gVarMac[g] >= 0))) {
+         htkamd_set_error("%s: state %d of model %s shares its pdf or its vectors (~m / ~u / ~v macros): not supported", who, it->j, s->hm[it->phys].name);
+         return HTKAMD_EMODEL;
+      }
+   }
+   return HTKAMD_OK;
+}
+
+static int dc_max_mixes(const struct htkamd_mmf *s)      /* MaxMixInSet */
+{
+   int mx = 0;
+   for (int h = 0; h < s->nHm; h++) for (int i = 1; i < s->hm[h].N - 1; i++) if (s->st[s->hm[h].state[i]].nMix > mx) mx = s->st[s->hm[h].state[i]].nMix;
+   return mx;
+}
+
+/* the device job of item lists over the set: Divergence rows for a single-Gaussian set, else the set and the items' states */
+static int dc_run(struct htkamd_mmf *s, const tc_item *items, int nItems, const htkamd_dc_cmd *cmds, int nCmds, const float *occ, float outlierThresh, int noMerge,
+                  float *idistOut, int *merges, int *nMerges, void *stream, const char *who)
+{
+   if (!htkamd_dc_dev_run) { htkamd_set_error("%s: no HIP device: this build holds the host files only", who); return HTKAMD_ENODEV; }
+   const int D = s->vecSize, single = dc_max_mixes(s) == 1;
+   htkamd_dc_job job;
+   memset(&job, 0, sizeof(job));
+   job.nCmds = nCmds; job.cmds = cmds; job.nItems = nItems; job.outlierThresh = outlierThresh; job.noMerge = noMerge;
+   float *mean = NULL, *var = NULL, *iocc = NULL; int *ist = (int *)malloc(sizeof(int) * (size_t)nItems);
+   for (int i = 0; i < nItems; i++) ist[i] = s->hm[items[i].phys].state[items[i].j - 1];
+   if (single) {
+      mean = (float *)malloc(sizeof(float) * (size_t)nItems * D); var = (float *)malloc(sizeof(float) * (size_t)nItems * D);
+      for (int i = 0; i < nItems; i++) {
+         const int g = s->cg[s->st[ist[i]].comp0];
+         memcpy(mean + (size_t)i * D, s->mean + (size_t)g * D, sizeof(float) * (size_t)D);
+         memcpy(var + (size_t)i * D, s->var + (size_t)g * D, sizeof(float) * (size_t)D);
+      }
+      job.mean = mean; job.var = var; job.V = D;
+   } else { job.desc = &s->d; job.itemState = ist; }
+   if (occ) {
+      iocc = (float *)malloc(sizeof(float) * (size_t)nItems);
+      for (int i = 0; i < nItems; i++) iocc[i] = occ[ist[i]];
+      job.occ = iocc;
+   }
+   const int rc = htkamd_dc_dev_run(&job, idistOut, merges, nMerges, stream);
+   free(mean); free(var); free(iocc); free(ist);
+   return rc;
+}
+
+int htkamd_state_distances(htkamd_mmf *s, const char *items, float *dist, int cap, int *n, void *stream)
+{
+   if (!s || !s->finished || !items || !n) { htkamd_set_error("state_distances: bad argument"); return HTKAMD_EINVAL; }
+   int rc = dc_check_set(s, "state_distances");
+   if (rc) return rc;
+   tc_item *it; int nI;
+   if ((rc = tc_parse_items(s, items, &it, &nI))) return rc;
+   *n = nI;
+   if (!dist || nI == 0) { free(it); return HTKAMD_OK; }
+   if ((long long)cap < (long long)nI * nI) { free(it); htkamd_set_error("state_distances: room for %d values, %d x %d needed", cap, nI, nI); return HTKAMD_EINVAL; }
+   dc_fix_gconsts(s);
+   const htkamd_dc_cmd cmd = { 0, nI, 1, 0.0f };
+   rc = dc_run(s, it, nI, &cmd, 1, NULL, 0.0f, 1, dist, NULL, NULL, stream, "state_distances");
+   free(it);
+   return rc;
+}
+
+int htkamd_cluster_merges(const float *idist, int N, const float *occ, int numReq, float threshold, float outlierThresh, int *merges, int *nMerges)
+{
+   if (!idist || N < 1 || numReq < 1 || !merges || !nMerges) { htkamd_set_error("cluster_merges: bad argument"); return HTKAMD_EINVAL; }
+   if (!htkamd_dc_dev_run) { htkamd_set_error("cluster_merges: no HIP device: this build holds the host files only"); return HTKAMD_ENODEV; }
+   const htkamd_dc_cmd cmd = { 0, N, numReq, threshold };
+   htkamd_dc_job job;
+   memset(&job, 0, sizeof(job));
+   job.nCmds = 1; job.cmds = &cmd; job.nItems = N; job.idist = idist; job.occ = occ; job.outlierThresh = outlierThresh;
+   int *log = (int *)malloc(sizeof(int) * 2 * (size_t)N);
+   const int rc = htkamd_dc_dev_run(&job, NULL, log, nMerges, NULL);
+   if (!rc) memcpy(merges, log, sizeof(int) * 2 * (size_t)*nMerges);
+   free(log);
+   return rc;
+}
+
+int htkamd_mmf_data_cluster(htkamd_mmf *s, const float *occ, float outlierThresh, const htkamd_cluster_spec *specs, int nSpecs, int *numClusters, void *stream)
+{
+   if (!s || !s->finished || !specs || nSpecs < 1 || !numClusters) { htkamd_set_error("mmf_data_cluster: bad argument"); return HTKAMD_EINVAL; }
+   int rc = dc_check_set(s, "mmf_data_cluster");
+   if (rc) return rc;
+   htkamd_set_error("%s", "");
+   char warn[512] = "";
+   tc_item *items = NULL; int nItems = 0, nCmds = 0;
+   htkamd_dc_cmd *cmds = (htkamd_dc_cmd *)malloc(sizeof(htkamd_dc_cmd) * (size_t)nSpecs);
+   int *cmdSpec = (int *)malloc(sizeof(int) * (size_t)nSpecs);
+   int *owner = (int *)malloc(sizeof(int) * (size_t)(s->nSt + 1));
+   int *merges = NULL, *nMerges = NULL, *newSeq = NULL, *next = NULL, *cvec = NULL;
+   for (int i = 0; i < s->nSt; i++) owner[i] = -1;
+   for (int t = 0; t < nSpecs && !rc; t++) {
+      const htkamd_cluster_spec *sp = &specs[t];
+      numClusters[t] = 0;
+      if (!sp->macro || !sp->items) { htkamd_set_error("mmf_data_cluster: command %d has no macro name or no item list", t); rc = HTKAMD_EINVAL; break; }
+      if (strlen(sp->macro) > 20) { htkamd_set_error("mmf_data_cluster: %s is rather long for a macro name (over 20 characters)", sp->macro); rc = HTKAMD_EINVAL; break; }
+      if (sp->byCount ? !(sp->value >= 1.0f) : !(sp->value >= 0.0f)) { htkamd_set_error("mmf_data_cluster: command %d (%s): bad %s %g", t, sp->macro, sp->byCount ? "cluster count" : "threshold", sp->value); rc = HTKAMD_EINVAL; break; }
+      tc_item *it; int nI;
+      if ((rc = tc_parse_items(s, sp->items, &it, &nI))) break;
+      if (nI == 0) { snprintf(warn, sizeof(warn), "mmf_data_cluster: warning: no items to cluster for %s: skipped", sp->macro); free(it); continue; }
+      if (nI > HTKAMD_DC_MAXITEMS) { htkamd_set_error("mmf_data_cluster: %d items for %s (at most %d in one command)", nI, sp->macro, HTKAMD_DC_MAXITEMS); rc = HTKAMD_EINVAL; free(it); break; }
+      for (int i = 0; i < nI && !rc; i++) {
+         const int si = s->hm[it[i].phys].state[it[i].j - 1];
+         if (owner[si] >= 0) {
+            htkamd_set_error("mmf_data_cluster: state %d of model %s is selected twice (by %s and %s): commands must not overlap", it[i].j, s->hm[it[i].phys].name,
+                             specs[owner[si]].macro, sp->macro); rc = HTKAMD_EINVAL;
+         } else rc = dc_check_state_item(s, &it[i], "mmf_data_cluster");
+         owner[si] = t;
+      }
+      if (rc) { free(it); break; }
+      items = (tc_item *)realloc(items, sizeof(tc_item) * (size_t)(nItems + nI));
+      memcpy(items + nItems, it, sizeof(tc_item) * (size_t)nI);
+      free(it);
+      cmds[nCmds].off = nItems; cmds[nCmds].n = nI;
+      cmds[nCmds].numReq = sp->byCount ? (int)sp->value : 1;
+      cmds[nCmds].threshold = sp->byCount ? 1.0E15f : sp->value;
+      cmdSpec[nCmds++] = t;
+      nItems += nI;
+   }
+   if (rc || !nCmds) goto done;
+   dc_fix_gconsts(s);
+   merges = (int *)malloc(sizeof(int) * 2 * (size_t)nItems); nMerges = (int *)malloc(sizeof(int) * (size_t)nCmds);
+   if ((rc = dc_run(s, items, nItems, cmds, nCmds, occ, outlierThresh, 0, NULL, merges, nMerges, stream, "mmf_data_cluster"))) goto done;
+   {
+      int seq = 0, maxN = 0;
+      for (int c = 0; c < nCmds; c++) if (cmds[c].n > maxN) maxN = cmds[c].n;
+      newSeq = (int *)malloc(sizeof(int) * (size_t)(s->nSt + 1));
+      for (int i = 0; i < s->nSt; i++) newSeq[i] = -1;
+      next = (int *)malloc(sizeof(int) * (size_t)maxN); cvec = (int *)malloc(sizeof(int) * (size_t)maxN);
+      tc_item *il = (tc_item *)malloc(sizeof(tc_item) * (size_t)maxN);
+      for (int c = 0; c < nCmds && !rc; c++) {
+         const int n = cmds[c].n; int nc = n;
+         const int *log = merges + 2 * (size_t)cmds[c].off;
+         for (int i = 0; i < n; i++) { next[i] = -1; cvec[i] = i; }
+         for (int m = 0; m < nMerges[c]; m++) {                /* MergeGroups (:1887) */
+            const int i = log[2 * m] - 1, j = log[2 * m + 1] - 1;
+            if (i < 0 || j < 0 || i >= nc || j >= nc || i == j) { htkamd_set_error("mmf_data_cluster: merge %d of %s names groups %d and %d of %d", m, specs[cmdSpec[c]].macro, i + 1, j + 1, nc); rc = HTKAMD_EHIP; break; }
+            int p = cvec[i];
+            while (next[p] >= 0) p = next[p];
+            next[p] = cvec[j];
+            for (int k = j; k < nc - 1; k++) cvec[k] = cvec[k + 1];
+            nc--;
+         }
+         if (rc) break;
+         numClusters[cmdSpec[c]] = nc;
+         for (int k = 0; k < nc; k++) {                       /* the chain reversed (:2068), then ApplyTie */
+            int cnt = 0;
+            for (int p = cvec[k]; p >= 0; p = next[p]) cnt++;
+            int w = cnt;
+            for (int p = cvec[k]; p >= 0; p = next[p]) il[--w] = items[cmds[c].off + p];
+            char buf[64];
+            snprintf(buf, sizeof(buf), "%s%d", specs[cmdSpec[c]].macro, k + 1);
+            dc_tie_states(s, il, cnt, buf, &seq, newSeq);
+         }
+      }
+      free(il);
+      if (!rc) tc_compact(s, newSeq, seq);
+   }
+done:
+   free(items); free(cmds); free(cmdSpec); free(owner); free(merges); free(nMerges); free(newSeq); free(next); free(cvec);
+   if (!rc && warn[0]) htkamd_set_error("%s", warn);
+   return rc;
+}
+
+int htkamd_mmf_tie(htkamd_mmf *s, const char *macro, const char *items)
+{
+   if (!s || !s->finished || !macro || !items) { htkamd_set_error("mmf_tie: bad argument"); return HTKAMD_EINVAL; }
+   if (strlen(macro) > 20) { htkamd_set_error("mmf_tie: %s is rather long for a macro name (over 20 characters)", macro); return HTKAMD_EINVAL; }
+   tc_item *it; int nI; char type = 0;
+   int rc = tc_parse_items_typed(s, items, &it, &nI, &type);
+   if (rc) return rc;
+   htkamd_set_error("%s", "");
+   if (nI == 0) { free(it); htkamd_set_error("mmf_tie: warning: macro %s has nothing to tie", macro); return HTKAMD_OK; }      /* ApplyTie's -2631 */
+   if (type == 't') {                                   /* TieTrans: the first item's matrix */
+      const int t0 = s->hm[it[0].phys].trans;
+      if (s->tr[t0].name) { htkamd_set_error("mmf_tie: the transition matrix of model %s is the ~t macro %s already: tying tied matrices is not supported", s->hm[it[0].phys].name, s->tr[t0].name); free(it); return HTKAMD_EMODEL; }
+      for (int t = 0; t < s->nTr; t++) if (s->tr[t].name && !strcmp(s->tr[t].name, macro)) { htkamd_set_error("mmf_tie: ~t macro %s exists already", macro); free(it); return HTKAMD_EINVAL; }
+      for (int k = 0; k < nI; k++) if (s->hm[it[k].phys].N != s->hm[it[0].phys].N) {
+         htkamd_set_error("mmf_tie: model %s has %d states, %s has %d: their transition matrices cannot be tied", s->hm[it[k].phys].name, s->hm[it[k].phys].N, s->hm[it[0].phys].name, s->hm[it[0].phys].N);
+         free(it); return HTKAMD_EMODEL;
+      }
+      /* the macro is a new record behind the others (NewMacro's order decides its place in the saved file), with the matrix's values */
+      const int N = s->tr[t0].N, t1 = s->nTr;
+      s->tr = (mmf_trans *)realloc(s->tr, sizeof(mmf_trans) * (size_t)(s->nTr + 1)); s->capTr = s->nTr + 1;
+      s->tp = (float *)realloc(s->tp, sizeof(float) * (size_t)(s->nTp + N * N)); s->capTp = s->nTp + N * N;
+      memcpy(s->tp + s->nTp, s->tp + s->tr[t0].off, sizeof(float) * (size_t)N * N);
+      s->tr[t1].name = strdup(macro); s->tr[t1].N = N; s->tr[t1].off = s->nTp; s->tr[t1].src = 0;
+      s->nTp += N * N; s->nTr++;
+      for (int h = 0; h < s->nHm; h++) if (s->hm[h].trans == t0) s->hm[h].trans = t1;
+      for (int k = 0; k < nI; k++) s->hm[it[k].phys].trans = t1;
+      s->transN = (int *)realloc(s->transN, sizeof(int) * (size_t)s->nTr);
+      s->transOff = (int *)realloc(s->transOff, sizeof(int) * ((size_t)s->nTr + 1));
+      for (int t = 0; t < s->nTr; t++) { s->transN[t] = s->tr[t].N; s->transOff[t] = s->tr[t].off; }
+      s->transOff[s->nTr] = s->nTp;
+      for (int h = 0; h < s->nHm; h++) s->hmmTrans[h] = s->hm[h].trans;
+      s->d.numTrans = s->nTr; s->d.transN = s->transN; s->d.transOff = s->transOff; s->d.transP = s->tp;
+      free(it);
+      return HTKAMD_OK;
+   }
+   if ((rc = dc_check_set(s, "mmf_tie"))) { free(it); return rc; }
+   for (int i = 0; i < nI && !rc; i++) {
+      rc = dc_check_state_item(s, &it[i], "mmf_tie");
+      for (int k = 0; k < i && !rc; k++)
+         if (s->hm[it[k].phys].state[it[k].j - 1] == s->hm[it[i].phys].state[it[i].j - 1]) {
+            htkamd_set_error("mmf_tie: state %d of model %s is selected twice", it[i].j, s->hm[it[i].phys].name); rc = HTKAMD_EINVAL;
+         }
+   }
+   for (int i = 0; i < s->nSt && !rc; i++) if (s->st[i].name && !strcmp(s->st[i].name, macro)) { htkamd_set_error("mmf_tie: ~s macro %s exists already", macro); rc = HTKAMD_EINVAL; }
+   if (rc) { free(it); return rc; }
+   dc_fix_gconsts(s);
+   int seq = 0, *newSeq = (int *)malloc(sizeof(int) * (size_t)(s->nSt + 1));
+   for (int i = 0; i < s->nSt; i++) newSeq[i] = -1;
+   dc_tie_states(s, it, nI, macro, &seq, newSeq);
+   tc_compact(s, newSeq, seq);
+   free(newSeq); free(it);
+   return HTKAMD_OK;
 }

@@ -239,6 +239,35 @@ int  htkamd_mmf_question_answers(const htkamd_mmf *s, const htkamd_tree_question
 /* the raw split sums of one node, [nQ][2][2D+1] floats (no side, then yes side; occ, sum[D], sqr[D]) */
 int  htkamd_tree_split_sums(const float *itemStats /*[nItems][2D+1]*/, int nItems, int D, const int *nodeItems, int n,
                             const unsigned char *answers /*[nQ][nItems]*/, int nQ, float *out, void *stream);
+/* Data-driven state clustering as HHEd's TC / NC commands do it (Clustering HHEd.c:2005: furthest-neighbour agglomeration of the listed
+   states, then one ~s macro per cluster), and the TI command.  One-stream DIAGC sets; the distances (Divergence :1749 for a set whose
+   largest mixture has one component, else GDistance :1771 over the library's exact scores) and the merge loops run on the device,
+   bit for bit the reference's; all commands of a call run together, one workgroup each.
+     data_cluster     : `occ` NULL = no statistics loaded (no outlier phase), else the occupations of htkamd_stats_read_file and RO's
+                        threshold: groups below it are merged into their nearest group (RemOutliers :1975).  A command is
+                        NC (byCount 1, value = number of clusters) or TC (byCount 0, value = threshold on the group distance);
+                        cluster k of a command becomes the macro "<macro>k", k from 1, tied to its typical state (TypicalState :990).
+                        numClusters[c]: what command c ended with.  A command whose list is empty is skipped (numClusters 0) and
+                        htkamd_last_error then holds a warning (the reference's -2631).  States nobody refers to any more are dropped;
+                        htkamd_mmf_desc / htkamd_mmf_write reflect the tied set afterwards (state numbers change).
+                        Refused before a device is touched (HTKAMD_EINVAL / HTKAMD_EMODEL and the reason): items that are not
+                        .state[i]; a state that is a ~s macro already; an item selected by two commands of the call; sets with more
+                        than one stream, FULLC, tied-mixture and discrete sets; more than 3000 items in one command; and a macro name
+                        over 20 characters -- the reference only warns there (-2639), this library refuses.
+     tie              : TI for a list of .state[i] items (TieState :1021) or of .transP items (TieTrans :1049: the first item's matrix);
+                        host only.  Every other item type is refused by name, and so are a state or a matrix that is a macro already
+                        and a macro name over 20 characters.
+   Diagnostic entry points (test aids, as htkamd_tree_split_sums is one):
+     state_distances  : the item-distance matrix [n][n] of an item list, in the list's order (dist NULL: only *n is set).
+     cluster_merges   : the merge loop alone on a caller's symmetric matrix idist[N][N]: merges[2m], merges[2m+1] = the groups (i, j)
+                        of merge m, 1-based in the numbering current at that merge (room for N - 1 pairs); occ NULL = no outlier phase. */
+typedef struct { int byCount; float value; const char *macro; const char *items; } htkamd_cluster_spec;
+int  htkamd_mmf_data_cluster(htkamd_mmf *s, const float *occ /*[numStates] or NULL*/, float outlierThresh, const htkamd_cluster_spec *specs, int nSpecs,
+                             int *numClusters /*[nSpecs]*/, void *stream);
+int  htkamd_mmf_tie(htkamd_mmf *s, const char *macro, const char *items);
+int  htkamd_state_distances(htkamd_mmf *s, const char *items, float *dist /*[n][n] or NULL*/, int cap, int *n, void *stream);
+int  htkamd_cluster_merges(const float *idist, int N, const float *occ /*[N] or NULL*/, int numReq, float threshold, float outlierThresh,
+                           int *merges /*[2(N-1)]*/, int *nMerges);
 /* HCompV's PutVFloor (HCompV.c:359-389): "~v varFloor1 <Variance> D" with scale*var, written like WriteVector(" %e"). */
 int  htkamd_mmf_write_vfloors(const char *path, const float *var, int D, float scale);
 void htkamd_mmf_destroy(htkamd_mmf *s);
