@@ -85,6 +85,14 @@ def lib():
         L.htkamd_last_error.restype = C.c_char_p
         L.htkamd_fb_frame_states.restype = C.c_longlong
         L.htkamd_fb_frame_states.argtypes = [C.c_void_p]
+        # the decoder set (a network per utterance): create(model, nets[], nNets, lmScale, out), run(set, cfg, dX, frameOff, netOf, nUtt, maxWords, out, stream)
+        if hasattr(L, "htkamd_decoder_set_create"):      # (a build of the host code alone has no decoders)
+            L.htkamd_decoder_set_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]; L.htkamd_decoder_set_create.restype = C.c_int
+            L.htkamd_decoder_set_destroy.argtypes = [C.c_void_p]; L.htkamd_decoder_set_destroy.restype = None
+            L.htkamd_decoder_set_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+            L.htkamd_decoder_set_run.restype = C.c_int
+            L.htkamd_decoder_set_last_tied.argtypes = [C.c_void_p]; L.htkamd_decoder_set_last_tied.restype = C.c_int
+            L.htkamd_decoder_set_set_order.argtypes = [C.c_void_p, C.c_int]; L.htkamd_decoder_set_set_order.restype = C.c_int
         _lib = L
     return _lib
 
@@ -1625,5 +1633,65 @@ class Decoder:
         try:
             if self.h:
                 lib().htkamd_decoder_destroy(self.h); self.h = C.c_void_p()
+        except Exception:
+            pass
+
+
+class DecodeOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("nWords", "wordPron", "wordStart", "wordEnd", "wordScore", "wordLm", "wordAc", "wordLike", "total", "finalLm")]
+
+
+class DecoderSet:
+    """htkamd_decoder_set holder: a batch in which utterance u is decoded against nets[net_of[u]] -- HVite -a from word-level
+    transcriptions, HVite -w with a lattice per file (DoAlignment, HVite.c:830) -- in one launch."""
+
+    def __init__(self, model: "Model", nets, lmScale: float = 1.0):
+        self.h = C.c_void_p()
+        self.model, self.nets, self.lmScale = model, list(nets), float(lmScale)
+        arr = (C.POINTER(NetDesc) * max(len(self.nets), 1))(*[C.pointer(n.desc) for n in self.nets])
+        check(lib().htkamd_decoder_set_create(model.h, arr, C.c_int(len(self.nets)), C.c_float(lmScale), C.byref(self.h)), "decoder_set_create")
+
+    def set_order(self, mode: int):
+        check(lib().htkamd_decoder_set_set_order(self.h, C.c_int(mode)), "decoder_set_set_order")
+
+    def last_tied(self) -> int:
+        return int(lib().htkamd_decoder_set_last_tied(self.h))
+
+    def run_arrays(self, feats, net_of, genBeam=1.0e10, wordBeam=1.0e10, lmScale=None, wordPen=0.0, prScale=1.0, maxWords=1024, scoreMode=0, maxActive=0):
+        """Every output array of htkamd_decoder_set_run (htkamd_decode_out's fields, [nUtt] / [nUtt, maxWords])."""
+        lmScale = self.lmScale if lmScale is None else float(lmScale)
+        if lmScale != self.lmScale:
+            raise HtkAmdError("DecoderSet.run: the LM scale is fixed at creation (LikeToWord look-ahead)")
+        nU = len(feats)
+        if len(net_of) != nU:
+            raise HtkAmdError("DecoderSet.run: %d utterances, %d network indices" % (nU, len(net_of)))
+        X = np.ascontiguousarray(np.concatenate(feats) if nU else np.zeros((0, self.model.D)), np.float32)
+        frameOff = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int32)
+        netOf = np.ascontiguousarray(np.asarray(net_of, np.int64).astype(np.int32) if nU else np.zeros(1, np.int32))
+        dX = DevArray(X) if X.size else DevArray(nbytes=4)
+        n1 = max(nU, 1)
+        o = dict(nWords=np.zeros(n1, np.int32), wordPron=np.zeros((n1, maxWords), np.int32), wordStart=np.zeros((n1, maxWords), np.int32),
+                 wordEnd=np.zeros((n1, maxWords), np.int32), wordScore=np.zeros((n1, maxWords), np.float32), wordLm=np.zeros((n1, maxWords), np.float32),
+                 wordAc=np.zeros((n1, maxWords), np.float32), wordLike=np.zeros((n1, maxWords), np.float64), total=np.zeros(n1, np.float64),
+                 finalLm=np.zeros(n1, np.float32))
+        out = DecodeOut(*[_p(o[n]) for n, _ in DecodeOut._fields_])
+        cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
+        check(lib().htkamd_decoder_set_run(self.h, C.byref(cfg), dX.ptr, _p(frameOff), _p(netOf), C.c_int(nU), C.c_int(maxWords), C.byref(out), None), "decoder_set_run")
+        return dict((k, v[:nU]) for k, v in o.items())
+
+    def run(self, feats, net_of, **p):
+        """feats: list of [T, D] arrays; net_of[u]: index into the set's networks.  Returns what Decoder.run returns per utterance -- (list of
+        (pron, startFrame, endFrame, score) or None, total), pron indexing nets[net_of[u]] -- and sets last_lm and last_status."""
+        o = self.run_arrays(feats, net_of, **p)
+        nW = o["nWords"]
+        self.last_status = [int(x) for x in nW]
+        self.last_lm = [[float(o["wordLm"][u, i]) for i in range(max(int(nW[u]), 0))] for u in range(len(feats))]
+        return [((None if nW[u] < 0 else [(int(o["wordPron"][u, i]), int(o["wordStart"][u, i]), int(o["wordEnd"][u, i]), float(o["wordScore"][u, i])) for i in range(nW[u])]),
+                 float(o["total"][u])) for u in range(len(feats))]
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().htkamd_decoder_set_destroy(self.h); self.h = C.c_void_p()
         except Exception:
             pass

@@ -9,6 +9,7 @@
 
 #define DEC_THREADS 1024
 #define DEC_MAXN 8              /* states per model incl. entry/exit */
+#define DEC_SET_THREADS 256     /* workgroup of the kernel that takes a network per utterance (alignment networks: tens to hundreds of nodes) */
 #define DEC_WIDE 96             /* fan-in from which a node is reduced by the whole workgroup */
 
 struct DecNet {
@@ -67,6 +68,7 @@ struct DecUtt {
    size_t node0;       // exit-token / instance-max arrays base
    size_t path0;       // path table base: (t*nWordNodes + w)
    size_t out0;        // word output base
+   int net, ns;        // k_decode<.., SET> (decode_set.hip): the utterance's network in DecArgs::nets and the rows of its score columns; 0 elsewhere
 };
 
 struct __attribute__((aligned(16))) Tok { double like; float lm; int path; };   // one 16-byte load/store per token
@@ -84,6 +86,7 @@ struct DecArgs {
    int *nWords, *wordPron, *wordStart, *wordEnd; float *wordScore, *wordLm, *wordAc; double *wordLike; double *total; float *finalLm;
    unsigned long long *liveCnt;        // [nUtt][2] k_decode<NPT > 0>: register-resident model instances stepped with a live token / with none (htkamd_decoder_last_live)
    int *tieFlag;                       // [nUtt] k_decode: two tokens of exactly equal likelihood and different histories met at a node (see decode_ord.hip)
+   const DecNet *nets;                 // k_decode<.., SET>: a network per utterance, nets[DecUtt::net] (net and ns above are then not read); NULL elsewhere
 };
 
 // Exact-order decoding (decode_ord.hip, k_decode_ord_n of decode_n.hip): HRec's instance list and the Path records it needs
@@ -103,7 +106,8 @@ struct OrdArgs {
 int htkamd_launch_decode_ord(const OrdArgs &a, int nSel, hipStream_t s);
 // K1 writes a score block state-major (a state's frames are a lane's stores); the token loops read a COLUMN per frame: one 128-byte line per
 // state and frame -- 640 KB per utterance and frame on the 5k-state set.  Transposed once (tiles through LDS), a frame's column is 20 KB.
-int htkamd_launch_score_transpose(const float *in, float *out, const DecUtt *dUtt, int nUtt, int maxT, int ns, hipStream_t s);
+// ns > 0: rows per utterance (one network); ns = 0: DecUtt::ns rows, at most maxNs (a network per utterance)
+int htkamd_launch_score_transpose(const float *in, float *out, const DecUtt *dUtt, int nUtt, int maxT, int ns, hipStream_t s, int maxNs = 0);
 
 
 // The decoders' device workspace: a fixed table of buffers kept between calls and grown (never shrunk) when a batch needs more -- the score
@@ -141,10 +145,27 @@ struct DecBatch {
 // uttBytes(T): the estimate for an utterance of T frames; DecUtt::out0 = k * outStride; path records per utterance: pathMul * (T + 1) * nWordNodes + pathExtra
 void htkamd_decoder_plan(const DecNet &N, const int *frameOff, int u0, int nUtt, int ns, int FR, int SL, const std::function<size_t(size_t)> &uttBytes,
                          size_t outStride, size_t pathMul, size_t pathExtra, DecBatch &b);
+// The same with a network per utterance (decode_set.hip): what utterance u decodes against, as the plan needs it
+struct DecUttNet { const DecNet *N; int net, ns, slot0; };      // slot0: the network's first entry in the scorer's slotState
+void htkamd_decoder_plan_nets(const std::function<DecUttNet(int)> &netOf, const int *frameOff, int u0, int nUtt, int FR, int SL,
+                              const std::function<size_t(size_t, const DecUttNet &)> &uttBytes, size_t outStride, size_t pathMul, size_t pathExtra, DecBatch &b);
 // Uploads the batch's descriptors and tasks (dTasks: room for the tasks and the queue's counter behind them), scores the network's states
 // for the batch's frames into dScore (state-major) and transposes that into dScoreT.  evScore (may be NULL): recorded before the scoring launch.
 int htkamd_decoder_score(const htkamd_decoder *d, int scoreMode, const float *dX, int nRows, const DecBatch &b, int ns, void *dUtt, void *dTasks,
                          float *dScore, float *dScoreT, hipEvent_t evScore, const char *who, hipStream_t s);
+// ... for the model m and the slot table dUsedStates; ns = 0: a network per utterance (DecUtt::ns rows, at most maxNs)
+int htkamd_decoder_score_slots(const htkamd_model *m, const int *dUsedStates, int scoreMode, const float *dX, int nRows, const DecBatch &b, int ns, int maxNs,
+                               void *dUtt, void *dTasks, float *dScore, float *dScoreT, hipEvent_t evScore, const char *who, hipStream_t s);
+
+// One network's device tables as htkamd_decoder_create builds them (decode.hip), handed table by table to `put` in the order of the single
+// decoder's uploads: put(data, bytes, where) stores the table's device address at *where (now, or before the tables are used).
+// noReg: no register-resident models (DecNet::nReg = 0: what the kernels that keep every token in memory read).  hmmState (the same for
+// every network of a model set) is left NULL when withHmmState is false; usedStates (the tied states in slot order) is uploaded too where
+// dUsedStates is not NULL.
+typedef std::function<int(const void *, size_t, const void **)> DecPut;
+int htkamd_decoder_pack(htkamd_model *m, const htkamd_net_desc *nd, float lmScale, bool noReg, bool withHmmState, const DecPut &put, DecNet &N,
+                        std::vector<int> &usedStates, const int **dUsedStates);
+int htkamd_launch_decode_set(const DecArgs &a, int nUtt, hipStream_t s);      // k_decode<0, DEC_SET_THREADS, true, false, true>
 
 struct htkamd_decoder {
    htkamd_model *m;

@@ -221,7 +221,8 @@ __device__ __forceinline__ Tok word_step2(const DecArgs &a, const DecUtt &ud, co
 // utterances, 563 MB of live state against 256 MB of Infinity Cache; what is left in memory here: exit tokens of the word nodes, instance
 // maxima, Path records, the score column.
 #define DEC_MAXR 5                 /* states of a register-resident model incl. entry / exit */
-template <int NPT, int NTHR, bool HASG, bool EXL = false>       // HASG: model nodes outside the registers exist (tee models, more than three emitting states, overflow); EXL: see DecNet::zl
+// SET (decode_set.hip's launch below): the utterance's network and the rows of its score columns come from its descriptor
+template <int NPT, int NTHR, bool HASG, bool EXL = false, bool SET = false>       // HASG: model nodes outside the registers exist (tee models, more than three emitting states, overflow); EXL: see DecNet::zl
 __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
 {
    __shared__ double red[NTHR / 64];
@@ -235,6 +236,8 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
    const int u = blockIdx.x, tid = threadIdx.x;
    if (u >= a.nUtt) return;
    const DecUtt ud = a.utt[u];
+   // (the record is uniform over the workgroup and read before the kernel's first store: scalar loads, held in scalar registers)
+   if constexpr (SET) { a.net = a.nets[ud.net]; a.ns = ud.ns; }
    const DecNet &N = a.net;
    const int T = ud.T;
    Tok *tok = a.tok + ud.tok0, *ex = a.ex + ud.node0;
@@ -608,12 +611,15 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
 }
 
 // state-major score block -> frame-major, per utterance: 32 x 32 tiles through LDS (both sides in whole lines)
-__global__ __launch_bounds__(256) void k_score_transpose(const float *__restrict__ in, float *__restrict__ out, const DecUtt *utt, int ns)
+// PERUTT: the utterance's own number of rows (DecUtt::ns: a network per utterance), the grid covers the largest
+template <bool PERUTT>
+__global__ __launch_bounds__(256) void k_score_transpose(const float *__restrict__ in, float *__restrict__ out, const DecUtt *utt, int nsAll)
 {
    __shared__ float tile[32][33];
    const DecUtt ud = utt[blockIdx.z];
+   const int ns = PERUTT ? ud.ns : nsAll;
    const int T = ud.T, f0 = blockIdx.x * 32, s0 = blockIdx.y * 32;
-   if (f0 >= T) return;
+   if (f0 >= T || s0 >= ns) return;
    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
    for (int r = ty; r < 32; r += 8) {
       const int sl = s0 + r, f = f0 + tx;
@@ -626,25 +632,18 @@ __global__ __launch_bounds__(256) void k_score_transpose(const float *__restrict
    }
 }
 
-int htkamd_launch_score_transpose(const float *in, float *out, const DecUtt *dUtt, int nUtt, int maxT, int ns, hipStream_t s)
+int htkamd_launch_score_transpose(const float *in, float *out, const DecUtt *dUtt, int nUtt, int maxT, int ns, hipStream_t s, int maxNs)
 {
-   if (nUtt <= 0 || maxT <= 0 || ns <= 0) return HTKAMD_OK;
-   hipLaunchKernelGGL(k_score_transpose, dim3((maxT + 31) / 32, (ns + 31) / 32, nUtt), dim3(256), 0, s, in, out, dUtt, ns);
+   if (nUtt <= 0 || maxT <= 0 || (ns <= 0 && maxNs <= 0)) return HTKAMD_OK;
+   if (ns > 0) hipLaunchKernelGGL(k_score_transpose<false>, dim3((maxT + 31) / 32, (ns + 31) / 32, nUtt), dim3(256), 0, s, in, out, dUtt, ns);
+   else hipLaunchKernelGGL(k_score_transpose<true>, dim3((maxT + 31) / 32, (maxNs + 31) / 32, nUtt), dim3(256), 0, s, in, out, dUtt, 0);
    hipError_t e = hipGetLastError();
    if (e != hipSuccess) { htkamd_set_error("score_transpose: launch: %s", hipGetErrorString(e)); return HTKAMD_EHIP; }
    return HTKAMD_OK;
 }
 
 // ------------------------------------------------------------------------------------ host side
-template <typename T> static int upv(htkamd_decoder *d, const std::vector<T> &v, const T **out)
-{
-   T *p = nullptr;
-   HIPCHECK(hipMalloc((void **)&p, sizeof(T) * (v.size() ? v.size() : 1)));
-   if (!v.empty()) HIPCHECK(hipMemcpy(p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice));
-   d->owned.push_back(p);
-   *out = p;
-   return HTKAMD_OK;
-}
+template <typename T> static int upv(const DecPut &put, const std::vector<T> &v, const T **out) { return put(v.data(), sizeof(T) * v.size(), (const void **)out); }
 
 void *DecArena::get(size_t n)
 {
@@ -671,9 +670,17 @@ int htkamd_decoder_order(const htkamd_decoder *d)
 void htkamd_decoder_plan(const DecNet &N, const int *frameOff, int u0, int nUtt, int ns, int FR, int SL, const std::function<size_t(size_t)> &uttBytes,
                          size_t outStride, size_t pathMul, size_t pathExtra, DecBatch &b)
 {
+   const DecUttNet one = {&N, 0, ns, 0};
+   htkamd_decoder_plan_nets([&](int) { return one; }, frameOff, u0, nUtt, FR, SL, [&](size_t T, const DecUttNet &) { return uttBytes(T); }, outStride, pathMul, pathExtra, b);
+   for (DecUtt &ud : b.utt) ud.ns = 0;      // (one network: the kernels take it and its rows from their arguments)
+}
+
+void htkamd_decoder_plan_nets(const std::function<DecUttNet(int)> &netOf, const int *frameOff, int u0, int nUtt, int FR, int SL,
+                              const std::function<size_t(size_t, const DecUttNet &)> &uttBytes, size_t outStride, size_t pathMul, size_t pathExtra, DecBatch &b)
+{
    size_t bytes = 0; int u1 = u0;
    while (u1 < nUtt) {
-      const size_t ub = uttBytes((size_t)(frameOff[u1 + 1] - frameOff[u1]));
+      const size_t ub = uttBytes((size_t)(frameOff[u1 + 1] - frameOff[u1]), netOf(u1));
       if (u1 > u0 && bytes + ub > ((size_t)24 << 30)) break;
       bytes += ub; u1++;
    }
@@ -682,9 +689,13 @@ void htkamd_decoder_plan(const DecNet &N, const int *frameOff, int u0, int nUtt,
    b.utt.assign(nu, DecUtt()); b.tasks.clear();
    for (int k = 0; k < nu; k++) {
       DecUtt &ud = b.utt[k];
+      const DecUttNet un = netOf(u0 + k);
+      const DecNet &N = *un.N;
+      const int ns = un.ns;
+      ud.net = un.net; ud.ns = ns;
       ud.T = frameOff[u0 + k + 1] - frameOff[u0 + k]; ud.frame0 = frameOff[u0 + k]; ud.status = HTKAMD_UTT_OK; ud.idx = k;
       ud.score0 = b.score; ud.tok0 = b.tok; ud.node0 = b.node; ud.path0 = b.path; ud.out0 = (size_t)k * outStride;
-      htkamd_tile_tasks(b.tasks, ud.frame0, ud.T, 0, ns, ud.score0, ud.T, FR, SL);
+      htkamd_tile_tasks(b.tasks, ud.frame0, ud.T, un.slot0, ns, ud.score0, ud.T, FR, SL);
       b.maxT = std::max(b.maxT, ud.T);
       b.score += (size_t)ns * ud.T; b.tok += (size_t)N.nTok; b.node += (size_t)N.nNodes; b.path += pathMul * ((size_t)(ud.T + 1) * N.nWordNodes) + pathExtra;
    }
@@ -693,7 +704,12 @@ void htkamd_decoder_plan(const DecNet &N, const int *frameOff, int u0, int nUtt,
 int htkamd_decoder_score(const htkamd_decoder *d, int scoreMode, const float *dX, int nRows, const DecBatch &b, int ns, void *dUtt, void *dTasks,
                          float *dScore, float *dScoreT, hipEvent_t evScore, const char *who, hipStream_t s)
 {
-   const htkamd_model *m = d->m;
+   return htkamd_decoder_score_slots(d->m, d->d_usedStates, scoreMode, dX, nRows, b, ns, 0, dUtt, dTasks, dScore, dScoreT, evScore, who, s);
+}
+
+int htkamd_decoder_score_slots(const htkamd_model *m, const int *dUsedStates, int scoreMode, const float *dX, int nRows, const DecBatch &b, int ns, int maxNs,
+                               void *dUtt, void *dTasks, float *dScore, float *dScoreT, hipEvent_t evScore, const char *who, hipStream_t s)
+{
    const int nu = (int)b.utt.size();
    hipError_t e;
    if ((e = hipMemcpyAsync(dUtt, b.utt.data(), sizeof(DecUtt) * nu, hipMemcpyHostToDevice, s)) != hipSuccess ||
@@ -702,7 +718,7 @@ int htkamd_decoder_score(const htkamd_decoder *d, int scoreMode, const float *dX
    }
    if (evScore) (void)hipEventRecord(evScore, s);
    ScoreArgs sa = htkamd_score_args(m);
-   sa.tasks = (const ScoreTask *)dTasks; sa.nTasks = (int)b.tasks.size(); sa.X = dX; sa.slotState = d->d_usedStates; sa.out = dScore;
+   sa.tasks = (const ScoreTask *)dTasks; sa.nTasks = (int)b.tasks.size(); sa.X = dX; sa.slotState = dUsedStates; sa.out = dScore;
    sa.taskCounter = (int *)((char *)dTasks + sizeof(ScoreTask) * b.tasks.size());
    int rc;
    if (m->NSt > 1 && scoreMode != HTKAMD_SCORE_EXACT) { htkamd_set_error("%s: multi-stream sets are scored in the exact mode only", who); return HTKAMD_EINVAL; }
@@ -710,7 +726,7 @@ int htkamd_decoder_score(const htkamd_decoder *d, int scoreMode, const float *dX
    else if (scoreMode != HTKAMD_SCORE_EXACT && scoreMode != HTKAMD_SCORE_MFMA && scoreMode != HTKAMD_SCORE_BF16) { htkamd_set_error("%s: unknown score mode %d", who, scoreMode); return HTKAMD_EINVAL; }
    else rc = htkamd_launch_score(scoreMode, m, sa, s);   // exact: the decoded path is the reference's; matrix-core modes: tolerance class
    if (rc) return rc;
-   return htkamd_launch_score_transpose(dScore, dScoreT, (const DecUtt *)dUtt, nu, b.maxT, ns, s);
+   return htkamd_launch_score_transpose(dScore, dScoreT, (const DecUtt *)dUtt, nu, b.maxT, ns, s, maxNs);
 }
 
 extern "C" int htkamd_decoder_set_order(htkamd_decoder *d, int mode)
@@ -774,31 +790,30 @@ static float like_to_word(const htkamd_net_desc *nd, const htkamd_model *m, cons
    return best;
 }
 
-extern "C" int htkamd_decoder_create(htkamd_model *m, const htkamd_net_desc *nd, float lmScale, htkamd_decoder **out)
+int htkamd_decoder_pack(htkamd_model *m, const htkamd_net_desc *nd, float lmScale, bool noReg, bool withHmmState, const DecPut &put, DecNet &N,
+                        std::vector<int> &usedStates, const int **dUsedStates)
 {
-   if (!m || !nd || !out) { htkamd_set_error("decoder_create: NULL argument"); return HTKAMD_EINVAL; }
    const int nN = nd->nNodes;
    std::vector<int> kind(nd->kind, nd->kind + nN), model(nd->model, nd->model + nN), tok0(nN), nodeN(nN, 2), nodeTp(nN, 0), nodeSt(nN, 0), wordIdx(nN, -1), hmmNodes;
    std::vector<float> pron(nd->pronProb, nd->pronProb + nN), wdlk(nN, (float)LZERO);
    std::vector<unsigned char> tee(nN, 0);
    std::vector<int> stateSlot(m->S, -1), wordNode;
-   htkamd_decoder *d = new htkamd_decoder();
-   d->m = m; d->d_usedStates = nullptr; d->hostModel = model;
+   usedStates.clear();
    int nTok = 0, nW = 0;
    for (int n = 0; n < nN; n++) {
       tok0[n] = nTok;
       if (kind[n] == HTKAMD_NODE_HMM) {
          const int h = model[n];
-         if (h < 0 || h >= m->H) { htkamd_set_error("decoder_create: node %d names model %d of %d", n, h, m->H); delete d; return HTKAMD_EINVAL; }
+         if (h < 0 || h >= m->H) { htkamd_set_error("decoder_create: node %d names model %d of %d", n, h, m->H); return HTKAMD_EINVAL; }
          const int ti = m->h_hmmTrans[h], NS = m->h_transN[ti];
-         if (NS > DEC_MAXN) { htkamd_set_error("decoder_create: model with %d states (max %d)", NS, DEC_MAXN); delete d; return HTKAMD_EMODEL; }
+         if (NS > DEC_MAXN) { htkamd_set_error("decoder_create: model with %d states (max %d)", NS, DEC_MAXN); return HTKAMD_EMODEL; }
          nodeN[n] = NS; nodeTp[n] = m->h_transOff[ti]; nodeSt[n] = m->h_hmmStateOff[h] / m->NSt;      // several streams: the table below lists a state's FIRST element only
          tee[n] = m->h_transP[m->h_transOff[ti] + (NS - 1)] > (float)LSMALL;
          nTok += NS - 1;
          hmmNodes.push_back(n);
          for (int j = 0; j < NS - 2; j++) {
             const int s = m->h_hmmState[m->h_hmmStateOff[h] + j * m->NSt];
-            if (stateSlot[s] < 0) { stateSlot[s] = (int)d->usedStates.size(); d->usedStates.push_back(s); }
+            if (stateSlot[s] < 0) { stateSlot[s] = (int)usedStates.size(); usedStates.push_back(s); }
          }
       } else {
          nTok += 1;
@@ -823,7 +838,7 @@ extern "C" int htkamd_decoder_create(htkamd_model *m, const htkamd_net_desc *nd,
       }
    }
    { int nz = 0; for (int n = 0; n < nN; n++) if (zt(n)) nz++;
-     if ((int)queue.size() != nz) { htkamd_set_error("decoder_create: the network has a loop of word/null/tee nodes"); delete d; return HTKAMD_EMODEL; } }
+     if ((int)queue.size() != nz) { htkamd_set_error("decoder_create: the network has a loop of word/null/tee nodes"); return HTKAMD_EMODEL; } }
    // Reverse CSR.  A node keeps the FIRST of several equally likely tokens (SetEntryState HRec.c:1303, strict >), so the order of a
    // node's predecessors is the order in which the senders are stepped within a frame: the emitting models' exit tokens go out first
    // (node order), then the zero-time nodes in their propagation order (HRec keeps its instance list in that order, ReOrderList
@@ -852,7 +867,7 @@ extern "C" int htkamd_decoder_create(htkamd_model *m, const htkamd_net_desc *nd,
    std::vector<float> regFusedLike;
    std::vector<unsigned char> regNoEx, isFused(nN, 0);
    int nReg = 0;
-   if (!getenv("HTKAMD_DECODE_NOREG")) {
+   if (!noReg && !getenv("HTKAMD_DECODE_NOREG")) {
       std::vector<int> reg, rest;
       for (int n : hmmNodes) ((!tee[n] && nodeN[n] <= 5 && (int)reg.size() < DEC_REG_MAXNPT * DEC_REG_THREADS) ? reg : rest).push_back(n);
       nReg = (int)reg.size();
@@ -883,7 +898,7 @@ extern "C" int htkamd_decoder_create(htkamd_model *m, const htkamd_net_desc *nd,
       for (int n = 0; n < nN; n++) if (zt(n) && level[n] == L && predOff[n + 1] - predOff[n] < DEC_WIDE && !isFused[n]) levelNodes.push_back(n);
       levelWide[L] = (int)levelNodes.size();
       for (int n = 0; n < nN; n++) if (zt(n) && level[n] == L && predOff[n + 1] - predOff[n] >= DEC_WIDE) {
-         if (kind[n] == HTKAMD_NODE_HMM) { htkamd_set_error("decoder_create: tee model with %d predecessors", predOff[n + 1] - predOff[n]); delete d; return HTKAMD_EMODEL; }
+         if (kind[n] == HTKAMD_NODE_HMM) { htkamd_set_error("decoder_create: tee model with %d predecessors", predOff[n + 1] - predOff[n]); return HTKAMD_EMODEL; }
          levelNodes.push_back(n);
       }
    }
@@ -932,7 +947,6 @@ extern "C" int htkamd_decoder_create(htkamd_model *m, const htkamd_net_desc *nd,
    }
    std::vector<int4> nodeInfo(nN);
    for (int n = 0; n < nN; n++) nodeInfo[n] = make_int4(kind[n] | (nodeN[n] << 4) | ((int)tee[n] << 12), tok0[n], nodeTp[n], nodeSt[n]);
-   DecNet &N = d->net;
    memset(&N, 0, sizeof(N));
    int rc0 = HTKAMD_OK;
    N.nReg = nReg;
@@ -969,25 +983,23 @@ extern "C" int htkamd_decoder_create(htkamd_model *m, const htkamd_net_desc *nd,
          regFusedRec[k] = make_int4(w, zl[w], pb, kind[w] == HTKAMD_NODE_WORD ? wordIdx[w] : -1);
       }
    N.nNullLds = nNullLds;
-   if ((rc0 = upv(d, predRec, &N.predRec)) || (rc0 = upv(d, predRecL, &N.predRecL)) || (rc0 = upv(d, zl, &N.zl)) || (rc0 = upv(d, regFusedZl, &N.regFusedZl)) || (rc0 = upv(d, regFusedRec, &N.regFusedRec)) || (rc0 = upv(d, predRecReg, &N.predRecReg)) || (rc0 = upv(d, predRecRegL, &N.predRecRegL)) ||
-       (nReg > 0 && (rc0 = upv(d, regPred, &N.regPred)))) { htkamd_decoder_destroy(d); return rc0; }
-   if (nReg > 0 && ((rc0 = upv(d, regFused, &N.regFused)) || (rc0 = upv(d, regFusedLike, &N.regFusedLike)) || (rc0 = upv(d, regNoEx, &N.regNoEx)) || (rc0 = upv(d, regRecA, &N.regRecA)) || (rc0 = upv(d, regRecB, &N.regRecB)) || (rc0 = upv(d, regRecF, &N.regRecF)))) { htkamd_decoder_destroy(d); return rc0; }
+   if ((rc0 = upv(put, predRec, &N.predRec)) || (rc0 = upv(put, predRecL, &N.predRecL)) || (rc0 = upv(put, zl, &N.zl)) || (rc0 = upv(put, regFusedZl, &N.regFusedZl)) || (rc0 = upv(put, regFusedRec, &N.regFusedRec)) || (rc0 = upv(put, predRecReg, &N.predRecReg)) || (rc0 = upv(put, predRecRegL, &N.predRecRegL)) ||
+       (nReg > 0 && (rc0 = upv(put, regPred, &N.regPred)))) return rc0;
+   if (nReg > 0 && ((rc0 = upv(put, regFused, &N.regFused)) || (rc0 = upv(put, regFusedLike, &N.regFusedLike)) || (rc0 = upv(put, regNoEx, &N.regNoEx)) || (rc0 = upv(put, regRecA, &N.regRecA)) || (rc0 = upv(put, regRecB, &N.regRecB)) || (rc0 = upv(put, regRecF, &N.regRecF)))) return rc0;
    N.nNodes = nN; N.nHmm = (int)hmmNodes.size(); N.nLevels = nLevels; N.nWordNodes = nW > 0 ? nW : 1; N.initial = nd->initial; N.final = nd->final; N.nTok = nTok; N.nTpFloats = m->h_transOff[m->nT];
    int rc;
-   if ((rc = upv(d, kind, &N.kind)) || (rc = upv(d, model, &N.model)) || (rc = upv(d, pron, &N.pronProb)) || (rc = upv(d, predOff, &N.predOff)) ||
-       (rc = upv(d, predSrc, &N.predSrc)) || (rc = upv(d, predLike, &N.predLike)) || (rc = upv(d, tok0, &N.tok0)) || (rc = upv(d, hmmNodes, &N.hmmNodes)) ||
-       (rc = upv(d, nodeN, &N.nodeN)) || (rc = upv(d, nodeTp, &N.nodeTp)) || (rc = upv(d, nodeSt, &N.nodeSt)) || (rc = upv(d, tee, &N.nodeTee)) ||
-       (rc = upv(d, wdlk, &N.wdlk)) || (rc = upv(d, wordIdx, &N.wordIdx)) || (rc = upv(d, levelOff, &N.levelOff)) || (rc = upv(d, levelNodes, &N.levelNodes)) ||
-       (rc = upv(d, levelWide, &N.levelWide)) || (rc = upv(d, levelOffA, &N.levelOffAll)) || (rc = upv(d, levelNodesA, &N.levelNodesAll)) || (rc = upv(d, levelWideA, &N.levelWideAll)) || (rc = upv(d, stateSlot, &N.stateSlot)) || (rc = upv(d, wordNode, &N.wordNode)) ||
-       (rc = upv(d, nodeInfo, &N.nodeInfo))) { htkamd_decoder_destroy(d); return rc; }
-   {
+   if ((rc = upv(put, kind, &N.kind)) || (rc = upv(put, model, &N.model)) || (rc = upv(put, pron, &N.pronProb)) || (rc = upv(put, predOff, &N.predOff)) ||
+       (rc = upv(put, predSrc, &N.predSrc)) || (rc = upv(put, predLike, &N.predLike)) || (rc = upv(put, tok0, &N.tok0)) || (rc = upv(put, hmmNodes, &N.hmmNodes)) ||
+       (rc = upv(put, nodeN, &N.nodeN)) || (rc = upv(put, nodeTp, &N.nodeTp)) || (rc = upv(put, nodeSt, &N.nodeSt)) || (rc = upv(put, tee, &N.nodeTee)) ||
+       (rc = upv(put, wdlk, &N.wdlk)) || (rc = upv(put, wordIdx, &N.wordIdx)) || (rc = upv(put, levelOff, &N.levelOff)) || (rc = upv(put, levelNodes, &N.levelNodes)) ||
+       (rc = upv(put, levelWide, &N.levelWide)) || (rc = upv(put, levelOffA, &N.levelOffAll)) || (rc = upv(put, levelNodesA, &N.levelNodesAll)) || (rc = upv(put, levelWideA, &N.levelWideAll)) || (rc = upv(put, stateSlot, &N.stateSlot)) || (rc = upv(put, wordNode, &N.wordNode)) ||
+       (rc = upv(put, nodeInfo, &N.nodeInfo))) return rc;
+   if (withHmmState) {
       std::vector<int> hs((size_t)(m->h_hmmStateOff[m->H] / m->NSt));
       for (size_t i = 0; i < hs.size(); i++) hs[i] = m->h_hmmState[i * m->NSt];      // a state's first (state, stream) element: the scorer sums its streams (ScoreArgs::NSt)
-      if ((rc = upv(d, hs, &N.hmmState))) { htkamd_decoder_destroy(d); return rc; }
-      const int *us = nullptr;
-      if ((rc = upv(d, d->usedStates, &us))) { htkamd_decoder_destroy(d); return rc; }
-      d->d_usedStates = (int *)us;
+      if ((rc = upv(put, hs, &N.hmmState))) return rc;
    }
+   if (dUsedStates && (rc = upv(put, usedStates, dUsedStates))) return rc;
    {
       // the network's own link order for the exact-order kernels (decode_ord.hip)
       std::vector<int> lo(nd->linkOff, nd->linkOff + nN + 1), ld(nd->linkDest, nd->linkDest + nd->nLinks), nTr0(nN, 0);
@@ -1001,13 +1013,45 @@ extern "C" int htkamd_decoder_create(htkamd_model *m, const htkamd_net_desc *nd,
          std::sort(ds.begin(), ds.end());
          dup[n] = std::adjacent_find(ds.begin(), ds.end()) != ds.end();
       }
-      if ((rc = upv(d, lo, &N.linkOff)) || (rc = upv(d, ld, &N.linkDest)) || (rc = upv(d, ll, &N.linkLike)) || (rc = upv(d, nTr0, &N.nTr0)) ||
-          (rc = upv(d, dup, &N.dupDest))) { htkamd_decoder_destroy(d); return rc; }
+      if ((rc = upv(put, lo, &N.linkOff)) || (rc = upv(put, ld, &N.linkDest)) || (rc = upv(put, ll, &N.linkLike)) || (rc = upv(put, nTr0, &N.nTr0)) ||
+          (rc = upv(put, dup, &N.dupDest))) return rc;
    }
    N.transP = m->d_transP;
+   return HTKAMD_OK;
+}
+
+extern "C" int htkamd_decoder_create(htkamd_model *m, const htkamd_net_desc *nd, float lmScale, htkamd_decoder **out)
+{
+   if (!m || !nd || !out) { htkamd_set_error("decoder_create: NULL argument"); return HTKAMD_EINVAL; }
+   htkamd_decoder *d = new htkamd_decoder();
+   d->m = m; d->d_usedStates = nullptr; d->hostModel.assign(nd->model, nd->model + nd->nNodes);
+   // every table an allocation of its own, as it is made
+   const DecPut put = [d](const void *data, size_t bytes, const void **where) -> int {
+      void *p = nullptr;
+      HIPCHECK(hipMalloc(&p, bytes ? bytes : 1));
+      d->owned.push_back(p);
+      if (bytes) HIPCHECK(hipMemcpy(p, data, bytes, hipMemcpyHostToDevice));
+      *where = p;
+      return HTKAMD_OK;
+   };
+   const int *us = nullptr;
+   const int rc = htkamd_decoder_pack(m, nd, lmScale, false, true, put, d->net, d->usedStates, &us);
+   if (rc) { htkamd_decoder_destroy(d); return rc; }
+   d->d_usedStates = (int *)us;
    *out = d;
    return HTKAMD_OK;
 }
+
+int htkamd_launch_decode_set(const DecArgs &a, int nUtt, hipStream_t s)
+{
+   if (nUtt <= 0) return HTKAMD_OK;
+   hipLaunchKernelGGL((k_decode<0, DEC_SET_THREADS, true, false, true>), dim3(nUtt), dim3(DEC_SET_THREADS), 0, s, a);
+   hipError_t e = hipGetLastError();
+   if (e != hipSuccess) { htkamd_set_error("decoder_set_run: launch: %s", hipGetErrorString(e)); return HTKAMD_EHIP; }
+   return HTKAMD_OK;
+}
+
+
 
 extern "C" int htkamd_decoder_run(htkamd_decoder *d, const htkamd_decode_config *cfg, const float *dX, const int *frameOff, int nUtt,
                                   int maxWords, int *nWords, int *wordPron, int *wordStart, int *wordEnd, float *wordScore, float *wordLm,

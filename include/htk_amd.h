@@ -867,6 +867,26 @@ typedef struct {
 int  htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_config *cfg, const float *dX, const int *frameOff, int nUtt,
                             int maxWords, const htkamd_decode_out *out, void *stream);
 
+/* A batch in which every utterance has a network of its own -- DoAlignment (HVite.c:830): HVite -a from word-level transcriptions
+ * (htkamd_net_build_words per file) and HVite -w without a network name, a lattice per file (-L dir -X ext; htkamd_net_build_ex per file).
+ * The set holds the tables of nNets networks over one model set in one device allocation; htkamd_decoder_set_run decodes utterance u
+ * against nets[netOf[u]] (0 .. nNets-1, repeats allowed) in ONE launch of a token kernel that reads its network from the utterance's
+ * descriptor.  Outputs, status codes and every number are those of htkamd_decoder_run_out on a decoder created for nets[netOf[u]]
+ * alone, bit for bit; wordPron[u] indexes THAT network's pronunciations.  The limits are the single decoder's (models of up to 8 states,
+ * tee models with at most 95 predecessors: the same messages from htkamd_decoder_set_create).  cfg->maxActive (HVite -u) is carried
+ * through.  A netOf[u] out of range is refused before anything is launched.  Exact ties go through the list kernel as in the single
+ * decoder (htkamd_decoder_set_order's modes; HTKAMD_DECODE_ORDER overrides), a launch per network that has such utterances.
+ * N-best and lattice output (htkamd_decoder_run_lattice*) exist for the single decoder only.  The descriptors may be freed after
+ * htkamd_decoder_set_create. */
+typedef struct htkamd_decoder_set htkamd_decoder_set;
+int  htkamd_decoder_set_create(htkamd_model *m, const htkamd_net_desc *const *nets, int nNets, float lmScale, htkamd_decoder_set **out);
+void htkamd_decoder_set_destroy(htkamd_decoder_set *d);
+int  htkamd_decoder_set_run(htkamd_decoder_set *d, const htkamd_decode_config *cfg, const float *dX, const int *frameOff,
+                            const int *netOf /*[nUtt], 0..nNets-1, repeats allowed*/, int nUtt, int maxWords,
+                            const htkamd_decode_out *out, void *stream);
+int  htkamd_decoder_set_last_tied(const htkamd_decoder_set *d);
+int  htkamd_decoder_set_set_order(htkamd_decoder_set *d, int mode);      /* HTKAMD_ORDER_* */
+
 /* ------------------------------------------------------------------------------------------
  * Waveform -> MFCC(+_0/_E)(+_D)(+_A)(+_Z) on the device: replaces what OpenBuffer (HParm.h, HParm.c:4357)
  * does for a waveform source with maxObs == 0 (whole file converted into a table):

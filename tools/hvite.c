@@ -2,6 +2,8 @@
  *
  *   hvite [options] -w net.slf dict hmmList dataFiles...          recognition over a word network
  *   hvite [options] -a [-b sil] dict hmmList dataFiles...         alignment of each file's word-level transcription
+ *   hvite [options] -w -L dir -X ext dict hmmList dataFiles...    each file against its own lattice dir/<file>.ext (rescoring)
+ * The last two are DoAlignment (HVite.c:830): --batch files at a time, a network per file, one launch per batch (htkamd_decoder_set_*).
  *
  * Options (the subset of HTKBook ref.tex "HVite" that SURVEY.md 8(b) lists; same letters, meaning and defaults, HVite.c:227-420):
  *   -C cf        configuration file (TARGETKIND, DELTAWINDOW, ACCWINDOW, THIRDWINDOW, V1COMPAT, SIMPLEDIFFS)
@@ -11,7 +13,8 @@
  *                CMEANDIR / CMEANMASK [/ CMEANPATHMASK] and VARSCALEDIR / VARSCALEMASK [/ VARSCALEPATHMASK] / VARSCALEFN: side-based mean and
  *                variance normalisation behind the qualifiers, as HParm does (files and waveforms alike); --help lists the variables
  *   -S scp       script file with further data files            -H mmf / -d dir / -x ext   model sources
- *   -w net       recognition network (SLF word lattice)         -a            align against the label files instead
+ *   -w [net]     recognition network (SLF word lattice); without a name (or ""): a lattice per file, -L dir / -X ext
+ *   -a           align against the label files instead
  *   -b word      alignment: boundary word at both ends          -L dir / -X ext / -I mlf   transcriptions to align (default .lab)
  *   -i mlf       write one master label file                    -l dir / -y ext            or one label file per input (default .rec)
  *   -m           model-level labels                             -f            state-level labels (implies model level as auxiliary)
@@ -38,22 +41,13 @@ static int out_flags(const char *s)
    return f;
 }
 
-/* labels of one decoded utterance -> transcription, at word / model / state level */
-static void emit(htkamd_trans *tr, const htkamd_net *net, const htkamd_mmf *mmf, htkamd_viterbi *vit, const float *dX, int D, int frame0, int T,
-                 int nW, const int *wPron, const int *wStart, const int *wEnd, const float *wScore, const float *wLm,
-                 double period, int models, int states, float lmScale, float wordPen, float alignBeam)
+/* the model chain of one decoded utterance's pronunciations (-m / -f): aligned against the same frames -- for a fixed word sequence the LM
+   terms are constants, so the best alignment of the chain is the decoder's path (include/htk_amd.h, htkamd_decoder_run) */
+typedef struct { int nQ, *chain, *wordOfQ; } model_chain;
+static void build_chain(const htkamd_net *net, int nW, const int *wPron, model_chain *c)
 {
-   if (!models && !states) {
-      for (int w = 0; w < nW; w++) {
-         const char *sym = htkamd_net_out_sym(net, wPron[w]);
-         if (!sym || !sym[0]) continue;                        /* words without output symbol leave no label (HRec.c:2342-2356) */
-         CHECK(htkamd_trans_add(tr, wStart[w] * period, wEnd[w] * period, sym, wScore[w], NULL, 0, NULL, 0));
-      }
-      return;
-   }
-   /* the model chain of the recognised pronunciations, aligned against the same frames: for a fixed word sequence the LM terms are
-      constants, so the best alignment of the chain is the decoder's path (include/htk_amd.h, htkamd_decoder_run) */
-   int nQ = 0, cap = 0, *chain = NULL, *wordOfQ = NULL;
+   int cap = 0;
+   c->nQ = 0; c->chain = NULL; c->wordOfQ = NULL;
    for (int w = 0; w < nW; w++) {
       int tmp[256], prev = -1, next = -1;                      /* neighbours with phones: cross-word networks name a word's edge models by them */
       for (int z = w - 1; z >= 0 && prev < 0; z--) if (htkamd_net_pron_models(net, wPron[z], tmp, 0) > 0) prev = wPron[z];
@@ -61,21 +55,30 @@ static void emit(htkamd_trans *tr, const htkamd_net *net, const htkamd_mmf *mmf,
       const int n = htkamd_net_seq_models(net, wPron[w], prev, next, tmp, 256);
       if (n < 0) DIE("%s", htkamd_last_error());
       if (n > 256) DIE("pronunciation with %d models", n);
-      if (nQ + n > cap) { cap = (nQ + n) * 2 + 64; chain = (int *)realloc(chain, sizeof(int) * (size_t)cap); wordOfQ = (int *)realloc(wordOfQ, sizeof(int) * (size_t)cap); }
-      for (int k = 0; k < n; k++) { chain[nQ] = tmp[k]; wordOfQ[nQ] = (k == 0) ? w : -1; nQ++; }
+      if (c->nQ + n > cap) { cap = (c->nQ + n) * 2 + 64; c->chain = (int *)realloc(c->chain, sizeof(int) * (size_t)cap); c->wordOfQ = (int *)realloc(c->wordOfQ, sizeof(int) * (size_t)cap); }
+      for (int k = 0; k < n; k++) { c->chain[c->nQ] = tmp[k]; c->wordOfQ[c->nQ] = (k == 0) ? w : -1; c->nQ++; }
    }
-   if (nQ == 0) { free(chain); free(wordOfQ); return; }
-   int frameOff[2] = {0, T}, labOff[2] = {0, nQ};
-   htkamd_batch_desc b = {1, dX + (size_t)frame0 * D, frameOff, labOff, chain};
-   CHECK(htkamd_viterbi_align(vit, &b, alignBeam, NULL));
-   size_t nSeg, nMod; CHECK(htkamd_viterbi_sizes(vit, &nSeg, &nMod));
-   int *segS = (int *)malloc(sizeof(int) * nSeg), *segE = (int *)malloc(sizeof(int) * nSeg), *modS = (int *)malloc(sizeof(int) * nMod), *modE = (int *)malloc(sizeof(int) * nMod), st;
-   double *segSc = (double *)malloc(sizeof(double) * nSeg), *modSc = (double *)malloc(sizeof(double) * nMod), tot;
-   CHECK(htkamd_viterbi_results(vit, segS, segE, segSc, modS, modE, modSc, &tot, &st, NULL));
+}
+
+/* word-level labels of one decoded utterance */
+static void emit_words(htkamd_trans *tr, const htkamd_net *net, int nW, const int *wPron, const int *wStart, const int *wEnd, const float *wScore, double period)
+{
+   for (int w = 0; w < nW; w++) {
+      const char *sym = htkamd_net_out_sym(net, wPron[w]);
+      if (!sym || !sym[0]) continue;                        /* words without output symbol leave no label (HRec.c:2342-2356) */
+      CHECK(htkamd_trans_add(tr, wStart[w] * period, wEnd[w] * period, sym, wScore[w], NULL, 0, NULL, 0));
+   }
+}
+
+/* model- / state-level labels of one utterance from its chain's alignment: seg* the chain's states, mod* its models (htkamd_viterbi_results) */
+static void emit_chain(htkamd_trans *tr, const htkamd_net *net, const htkamd_mmf *mmf, const model_chain *c, const int *wPron, const float *wLm,
+                       const int *segS, const int *segE, const double *segSc, const int *modS, const int *modE, const double *modSc,
+                       double period, int models, int states, float lmScale, float wordPen)
+{
    const htkamd_model_desc *d = htkamd_mmf_desc(mmf);
    size_t k = 0;
-   for (int q = 0; q < nQ; q++) {
-      const int h = chain[q], ns = d->hmmStateOff[h + 1] - d->hmmStateOff[h], w = wordOfQ[q];
+   for (int q = 0; q < c->nQ; q++) {
+      const int h = c->chain[q], ns = d->hmmStateOff[h + 1] - d->hmmStateOff[h], w = c->wordOfQ[q];
       const char *mname = htkamd_mmf_phys_name(mmf, h);
       const char *wname = (w >= 0) ? htkamd_net_word_name(net, wPron[w]) : NULL;     /* -m / -f label the first model of a word with the word's NAME */
       /* LArcTotLMLike (HNet.h:252): lmlike*lmscale + wdpenalty, in float then double as the reference evaluates it */
@@ -96,7 +99,23 @@ static void emit(htkamd_trans *tr, const htkamd_net *net, const htkamd_mmf *mmf,
          first = 0;
       }
    }
-   free(segS); free(segE); free(modS); free(modE); free(segSc); free(modSc); free(chain); free(wordOfQ);
+}
+
+/* 1-best decoding of utterances u0 .. u1 of a batch, each against its own network (decoder set) or all against one (decoder) */
+static void decode_range(htkamd_decoder *dec, htkamd_decoder_set *set, const htkamd_decode_config *dc, const obs_batch *ob, const int *netOf, int u0, int u1, int maxWords,
+                         int *nWords, int *wPron, int *wStart, int *wEnd, float *wScore, float *wLm, double *total)
+{
+   const int n = u1 - u0;
+   int *fo = (int *)malloc(sizeof(int) * (size_t)(n + 1));
+   for (int u = 0; u <= n; u++) fo[u] = ob->frameOff[u0 + u] - ob->frameOff[u0];
+   const float *dX = ob->dX + (size_t)ob->frameOff[u0] * ob->cols;
+   const size_t o = (size_t)u0 * maxWords;
+   if (set) {
+      htkamd_decode_out out; memset(&out, 0, sizeof(out));
+      out.nWords = nWords + u0; out.wordPron = wPron + o; out.wordStart = wStart + o; out.wordEnd = wEnd + o; out.wordScore = wScore + o; out.wordLm = wLm + o; out.total = total + u0;
+      CHECK(htkamd_decoder_set_run(set, dc, dX, fo, netOf + u0, n, maxWords, &out, NULL));
+   } else CHECK(htkamd_decoder_run(dec, dc, dX, fo, n, maxWords, nWords + u0, wPron + o, wStart + o, wEnd + o, wScore + o, wLm + o, total + u0, NULL));
+   free(fo);
 }
 
 /* HShell's argument classes (NextArg, HShell.c:1158-1200): an argument is a number when the whole of it parses as one; *isInt: no
@@ -131,7 +150,7 @@ int main(int argc, char **argv)
    float genBeam = 0.0f, wordBeam = 0.0f, lmScale = 1.0f, wordPen = 0.0f, prScale = 1.0f;
    float genBeamInc = 0.0f, genBeamLim = 0.0f, tmBeam = 10.0f;             /* -t f [i l]: alignment retries a file with wider beams (HVite.c:308-322, 900-913) */
    int align = 0, models = 0, states = 0, oflags = 0, trace = 0, scoreMode = HTKAMD_SCORE_EXACT, batchN = 1024, maxActive = 0;
-   int nToks = 0, nTrans = 1, latFmt = 0;
+   int nToks = 0, nTrans = 1, latFmt = 0, latPerFile = 0;
    const char *latExt = NULL;
    const char *sw;
 
@@ -143,7 +162,7 @@ int main(int argc, char **argv)
             scoreMode = !strcmp(m, "exact") ? HTKAMD_SCORE_EXACT : !strcmp(m, "fast") ? HTKAMD_SCORE_MFMA : !strcmp(m, "fastest") ? HTKAMD_SCORE_BF16 : -1;
             if (scoreMode < 0) DIE("--score: exact | fast | fastest");
          } else if (!strcmp(lo, "batch")) batchN = atoi(str_arg(&a, "-batch"));
-         else if (!strcmp(lo, "help")) { printf("USAGE: hvite [options] -w net.slf | -a [-b sil] dict hmmList dataFiles...   (the options: the comment at the head of tools/hvite.c)\n"); print_config_help(stdout); return 0; }
+         else if (!strcmp(lo, "help")) { printf("USAGE: hvite [options] -w net.slf | -w -L dir -X ext | -a [-b sil] dict hmmList dataFiles...   (the options: the comment at the head of tools/hvite.c)\n"); print_config_help(stdout); return 0; }
          else DIE("unknown option --%s", lo);
          continue;
       }
@@ -159,7 +178,10 @@ int main(int argc, char **argv)
       case 'H': sl_add(&mmfs, str_arg(&a, sw)); break;
       case 'd': hmmDir = str_arg(&a, sw); break;
       case 'x': hmmExt = str_arg(&a, sw); break;
-      case 'w': netPath = str_arg(&a, sw); break;
+      case 'w':                                             /* no string argument behind it (or ""): a lattice per file from -L dir -X ext (HVite.c:324-334) */
+         if (a.at < a.argc && a.argv[a.at][0] && !is_switch(a.argv[a.at]) && !is_number(a.argv[a.at], NULL)) netPath = str_arg(&a, sw);
+         else { latPerFile = 1; if (a.at < a.argc && !a.argv[a.at][0]) a.at++; }
+         break;
       case 'a': align = 1; break;
       case 'b': boundary = str_arg(&a, sw); break;
       case 'L': labDir = str_arg(&a, sw); break;
@@ -209,7 +231,9 @@ int main(int argc, char **argv)
    const char *dictPath = a.argv[a.at++], *hmmList = a.argv[a.at++];
    while (a.at < a.argc) sl_add(&files, a.argv[a.at++]);
    if (files.n == 0) DIE("hvite: no data files");
-   if (!align && !netPath) DIE("hvite: either -w net or -a");
+   if (!align && !netPath && !latPerFile) DIE("hvite: either -w net or -a");
+   if (align && latPerFile) DIE("hvite: -w without a network name takes a lattice per file: not together with -a");      /* HVite.c:453 */
+   if (nToks > 1 && latPerFile) DIE("hvite: -n with a lattice per file is not supported");
    if (nToks == 1 || nToks > 8) DIE("hvite -n: 2..8 tokens per state");
    if (nToks > 1 && align) DIE("hvite: alignment using multiple tokens is not supported");       /* HVite.c:448 (-m / -f with -n: as the reference built with -DPHNALG, alignment records inside the lattice arcs) */
    if (latExt && nToks < 2) DIE("hvite -z: lattices need -n i with i > 1");
@@ -238,7 +262,8 @@ int main(int argc, char **argv)
    htkamd_net *net = NULL; htkamd_decoder *dec = NULL;
    const int netFlags = (cfg_bool(&cfg, "ALLOWXWRDEXP", 0) ? HTKAMD_NET_ALLOWXWRDEXP : 0) | (cfg_bool(&cfg, "FORCECXTEXP", 0) ? HTKAMD_NET_FORCECXTEXP : 0) |
                         (cfg_bool(&cfg, "FORCELEFTBI", 0) ? HTKAMD_NET_FORCELEFTBI : 0) | (cfg_bool(&cfg, "FORCERIGHTBI", 0) ? HTKAMD_NET_FORCERIGHTBI : 0);     /* HNet.c:122-127 */
-   if (!align) { CHECK(htkamd_net_build_ex(netPath, dictPath, mmf, netFlags, &net)); CHECK(htkamd_decoder_create(model, htkamd_net_get(net), lmScale, &dec)); }
+   const int perFile = align || latPerFile;                 /* DoAlignment (HVite.c:830): a network per file, a decoder set per batch */
+   if (!perFile) { CHECK(htkamd_net_build_ex(netPath, dictPath, mmf, netFlags, &net)); CHECK(htkamd_decoder_create(model, htkamd_net_get(net), lmScale, &dec)); }
    htkamd_mlf *mlf = NULL; if (mlfIn) CHECK(htkamd_mlf_read(mlfIn, &mlf));
    htkamd_mlf_out *mout = NULL; if (mlfOut) CHECK(htkamd_mlf_out_open(mlfOut, &mout));
    htkamd_decode_config dc; memset(&dc, 0, sizeof(dc));
@@ -246,25 +271,43 @@ int main(int argc, char **argv)
    dc.lmScale = lmScale; dc.wordPen = wordPen; dc.prScale = prScale; dc.scoreMode = scoreMode; dc.maxActive = maxActive;
    const int maxWords = 4096;
 
-   for (int first = 0; first < files.n; first += (align ? 1 : batchN)) {
-      const int count = align ? 1 : ((files.n - first < batchN) ? files.n - first : batchN);
+   for (int first = 0; first < files.n; first += batchN) {
+      const int count = (files.n - first < batchN) ? files.n - first : batchN;
       obs_batch ob; memset(&ob, 0, sizeof(ob));
       load_observations(&files, first, count, targetKind, &cfg, &ob);
       if (ob.cols != D) DIE("observations have %d components, the models %d", ob.cols, D);
-      htkamd_net *unet = net; htkamd_decoder *udec = dec;
-      if (align) {                                              /* DoAlignment (HVite.c:830): the network of this file's transcription */
-         char lab[2048];
-         make_fn(files.v[first], labDir, labExt, lab, sizeof(lab));
-         htkamd_labels *L = NULL; const htkamd_labels *Lc = NULL;
-         if (mlf) { Lc = htkamd_mlf_find(mlf, lab); if (!Lc) DIE("%s: no entry in the master label file %s", lab, mlfIn); }
-         else { CHECK(htkamd_labels_read(lab, &L)); Lc = L; }
-         const int n = htkamd_labels_count(Lc);
-         const char **words = (const char **)malloc(sizeof(char *) * (size_t)(n ? n : 1));
-         for (int i = 0; i < n; i++) words[i] = htkamd_labels_name(Lc, i);
-         CHECK(htkamd_net_build_words(words, n, boundary, dictPath, mmf, &unet));
-         CHECK(htkamd_decoder_create(model, htkamd_net_get(unet), lmScale, &udec));
-         free(words);
-         if (L) htkamd_labels_free(L);
+      /* a network per file: the file's transcription (-a), or its lattice (-w without a name; files that name the same lattice share a network) */
+      htkamd_net **unets = NULL; char **upaths = NULL; int nNets = 0, *netOf = NULL;
+      htkamd_decoder_set *set = NULL;
+      if (perFile) {
+         unets = (htkamd_net **)calloc((size_t)count, sizeof(*unets)); upaths = (char **)calloc((size_t)count, sizeof(*upaths)); netOf = (int *)malloc(sizeof(int) * (size_t)count);
+         for (int u = 0; u < count; u++) {
+            char lab[2048];
+            make_fn(files.v[first + u], labDir, labExt, lab, sizeof(lab));
+            if (latPerFile) {
+               int g = 0;
+               while (g < nNets && strcmp(upaths[g], lab)) g++;
+               netOf[u] = g;
+               if (g < nNets) continue;
+               upaths[nNets] = strdup(lab);
+               CHECK(htkamd_net_build_ex(lab, dictPath, mmf, netFlags, &unets[nNets++]));
+               continue;
+            }
+            htkamd_labels *L = NULL; const htkamd_labels *Lc = NULL;
+            if (mlf) { Lc = htkamd_mlf_find(mlf, lab); if (!Lc) DIE("%s: no entry in the master label file %s", lab, mlfIn); }
+            else { CHECK(htkamd_labels_read(lab, &L)); Lc = L; }
+            const int n = htkamd_labels_count(Lc);
+            const char **words = (const char **)malloc(sizeof(char *) * (size_t)(n ? n : 1));
+            for (int i = 0; i < n; i++) words[i] = htkamd_labels_name(Lc, i);
+            netOf[u] = nNets;
+            CHECK(htkamd_net_build_words(words, n, boundary, dictPath, mmf, &unets[nNets++]));
+            free(words);
+            if (L) htkamd_labels_free(L);
+         }
+         const htkamd_net_desc **descs = (const htkamd_net_desc **)malloc(sizeof(*descs) * (size_t)nNets);
+         for (int g = 0; g < nNets; g++) descs[g] = htkamd_net_get(unets[g]);
+         CHECK(htkamd_decoder_set_create(model, descs, nNets, lmScale, &set));
+         free(descs);
       }
       if (nToks > 1) {
          /* ---- N-best: token sets on the device, lattice per file, then WriteLattice / the N most likely transcriptions on the host */
@@ -346,26 +389,79 @@ int main(int argc, char **argv)
       int *wStart = (int *)malloc(sizeof(int) * (size_t)count * maxWords), *wEnd = (int *)malloc(sizeof(int) * (size_t)count * maxWords);
       float *wScore = (float *)malloc(sizeof(float) * (size_t)count * maxWords), *wLm = (float *)malloc(sizeof(float) * (size_t)count * maxWords);
       double *total = (double *)malloc(sizeof(double) * (size_t)count);
-      CHECK(htkamd_decoder_run(udec, &dc, ob.dX, ob.frameOff, count, maxWords, nWords, wPron, wStart, wEnd, wScore, wLm, total, NULL));
-      float usedBeam = dc.genBeam;
-      if (align && genBeamInc > 0.0f) {                       /* DoAlignment's retries (HVite.c:900-913): wider beams while nothing reaches the final node */
+      float *usedBeam = (float *)malloc(sizeof(float) * (size_t)count);       /* the beam each file finished at */
+      int *nRetry = (int *)calloc((size_t)count, sizeof(int));
+      decode_range(dec, set, &dc, &ob, netOf, 0, count, maxWords, nWords, wPron, wStart, wEnd, wScore, wLm, total);
+      for (int u = 0; u < count; u++) usedBeam[u] = dc.genBeam;
+      if (perFile && genBeamInc > 0.0f) {
+         /* DoAlignment's retries (HVite.c:900-913): wider beams while nothing reaches the final node -- the files that failed only, every run of
+            neighbours among them one call */
          htkamd_decode_config dr = dc;
          float cur = dc.genBeam + genBeamInc;
-         while (nWords[0] < 0 && cur <= genBeamLim - genBeamInc) {
-            if (trace & 1) printf("No tokens survived to final node of network at beam %.1f\n", cur - genBeamInc);
-            dr.genBeam = usedBeam = cur;
-            CHECK(htkamd_decoder_run(udec, &dr, ob.dX, ob.frameOff, count, maxWords, nWords, wPron, wStart, wEnd, wScore, wLm, total, NULL));
+         for (int last = 0; !last;) {
+            last = !(cur <= genBeamLim - genBeamInc);
+            int any = 0;
+            dr.genBeam = cur;
+            for (int u = 0; u < count;) {
+               if (nWords[u] >= 0) { u++; continue; }
+               int v = u;
+               while (v < count && nWords[v] < 0) { usedBeam[v] = cur; nRetry[v] += last ? 0 : 1; v++; }
+               decode_range(dec, set, &dr, &ob, netOf, u, v, maxWords, nWords, wPron, wStart, wEnd, wScore, wLm, total);
+               any = 1; u = v;
+            }
+            if (!any) break;
             cur += genBeamInc;
          }
-         if (nWords[0] < 0) { dr.genBeam = usedBeam = cur; CHECK(htkamd_decoder_run(udec, &dr, ob.dX, ob.frameOff, count, maxWords, nWords, wPron, wStart, wEnd, wScore, wLm, total, NULL)); }
+      }
+      /* -m / -f: the chains of the whole batch aligned together -- one call per run of neighbouring files that have a chain and finished at one beam */
+      model_chain *chains = NULL; size_t *segAt = NULL, *modAt = NULL;
+      int *segS = NULL, *segE = NULL, *modS = NULL, *modE = NULL; double *segSc = NULL, *modSc = NULL;
+      if (models || states) {
+         chains = (model_chain *)calloc((size_t)count, sizeof(*chains)); segAt = (size_t *)calloc((size_t)count, sizeof(size_t)); modAt = (size_t *)calloc((size_t)count, sizeof(size_t));
+         const htkamd_model_desc *md = htkamd_mmf_desc(mmf);
+         size_t nSegAll = 0, nModAll = 0;
+         for (int u = 0; u < count; u++) {
+            if (nWords[u] < 0) continue;
+            build_chain(perFile ? unets[netOf[u]] : net, nWords[u], wPron + (size_t)u * maxWords, &chains[u]);
+            segAt[u] = nSegAll; modAt[u] = nModAll;
+            for (int q = 0; q < chains[u].nQ; q++) nSegAll += (size_t)(md->hmmStateOff[chains[u].chain[q] + 1] - md->hmmStateOff[chains[u].chain[q]]);
+            nModAll += (size_t)chains[u].nQ;
+         }
+         segS = (int *)malloc(sizeof(int) * (nSegAll + 1)); segE = (int *)malloc(sizeof(int) * (nSegAll + 1)); segSc = (double *)malloc(sizeof(double) * (nSegAll + 1));
+         modS = (int *)malloc(sizeof(int) * (nModAll + 1)); modE = (int *)malloc(sizeof(int) * (nModAll + 1)); modSc = (double *)malloc(sizeof(double) * (nModAll + 1));
+         for (int u = 0; u < count;) {
+            if (chains[u].nQ == 0) { u++; continue; }
+            int v = u, nQ = 0;
+            while (v < count && chains[v].nQ > 0 && usedBeam[v] == usedBeam[u]) nQ += chains[v++].nQ;
+            const int n = v - u;
+            int *fo = (int *)malloc(sizeof(int) * (size_t)(n + 1)), *lo = (int *)malloc(sizeof(int) * (size_t)(n + 1)), *labs = (int *)malloc(sizeof(int) * (size_t)nQ), *st = (int *)malloc(sizeof(int) * (size_t)n);
+            double *tot = (double *)malloc(sizeof(double) * (size_t)n);
+            fo[0] = lo[0] = 0;
+            for (int k = 0; k < n; k++) {
+               fo[k + 1] = ob.frameOff[u + k + 1] - ob.frameOff[u]; lo[k + 1] = lo[k] + chains[u + k].nQ;
+               memcpy(labs + lo[k], chains[u + k].chain, sizeof(int) * (size_t)chains[u + k].nQ);
+            }
+            htkamd_batch_desc b = {n, ob.dX + (size_t)ob.frameOff[u] * D, fo, lo, labs};
+            CHECK(htkamd_viterbi_align(vit, &b, usedBeam[u], NULL));
+            size_t nSeg, nMod; CHECK(htkamd_viterbi_sizes(vit, &nSeg, &nMod));
+            if (nMod != (size_t)nQ || segAt[u] + nSeg > nSegAll) DIE("hvite: the aligner returned %zu models for %d", nMod, nQ);
+            CHECK(htkamd_viterbi_results(vit, segS + segAt[u], segE + segAt[u], segSc + segAt[u], modS + modAt[u], modE + modAt[u], modSc + modAt[u], tot, st, NULL));
+            free(fo); free(lo); free(labs); free(st); free(tot);
+            u = v;
+         }
       }
       for (int u = 0; u < count; u++) {
          const char *fn = files.v[first + u];
          const int T = ob.frameOff[u + 1] - ob.frameOff[u];
+         const htkamd_net *unet = perFile ? unets[netOf[u]] : net;
+         if (trace & 1) { float cur = dc.genBeam + genBeamInc; for (int r = 0; r < nRetry[u]; r++, cur += genBeamInc) printf("No tokens survived to final node of network at beam %.1f\n", cur - genBeamInc); }
          if (nWords[u] < 0) { fprintf(stderr, "No tokens survived to final node of network: %s\n", fn); continue; }
+         const size_t o = (size_t)u * maxWords;
          htkamd_trans *tr; CHECK(htkamd_trans_create((models ? 1 : 0) + (states ? 1 : 0), &tr));
-         emit(tr, unet, mmf, vit, ob.dX, D, ob.frameOff[u], T, nWords[u], wPron + (size_t)u * maxWords, wStart + (size_t)u * maxWords, wEnd + (size_t)u * maxWords,
-              wScore + (size_t)u * maxWords, wLm + (size_t)u * maxWords, (double)ob.period, models, states, lmScale, wordPen, usedBeam);
+         if (!models && !states) emit_words(tr, unet, nWords[u], wPron + o, wStart + o, wEnd + o, wScore + o, (double)ob.period);
+         else if (chains[u].nQ > 0)
+            emit_chain(tr, unet, mmf, &chains[u], wPron + o, wLm + o, segS + segAt[u], segE + segAt[u], segSc + segAt[u], modS + modAt[u], modE + modAt[u], modSc + modAt[u],
+                       (double)ob.period, models, states, lmScale, wordPen);
          CHECK(htkamd_trans_format(tr, (double)ob.period, states, models, oflags));
          char out[2048];
          make_fn(fn, outDir, outExt, out, sizeof(out));
@@ -373,8 +469,12 @@ int main(int argc, char **argv)
          htkamd_trans_free(tr);
          if (trace & 1) printf("File: %s\n==  [%d frames] %.4f [Ac=%.1f]\n", fn, T, total[u] / T, total[u]);
       }
-      free(nWords); free(wPron); free(wStart); free(wEnd); free(wScore); free(wLm); free(total);
-      if (align) { htkamd_decoder_destroy(udec); htkamd_net_destroy(unet); }
+      if (chains) for (int u = 0; u < count; u++) { free(chains[u].chain); free(chains[u].wordOfQ); }
+      free(chains); free(segAt); free(modAt); free(segS); free(segE); free(segSc); free(modS); free(modE); free(modSc);
+      free(nWords); free(wPron); free(wStart); free(wEnd); free(wScore); free(wLm); free(total); free(usedBeam); free(nRetry);
+      if (set) htkamd_decoder_set_destroy(set);
+      for (int g = 0; g < nNets; g++) { htkamd_net_destroy(unets[g]); free(upaths[g]); }
+      free(unets); free(upaths); free(netOf);
       free_observations(&ob);
    }
    if (mout) htkamd_mlf_out_close(mout);
