@@ -104,6 +104,12 @@ struct OrdArgs {
                                        // fixed capacities (-4 path records, -5 list appends of a frame, -6 nesting of zero-time nodes) leaves it standing
 };
 int htkamd_launch_decode_ord(const OrdArgs &a, int nSel, hipStream_t s);
+// The capacities the list kernels (k_decode_ord, k_decode_ord_n) assume per utterance.  Path records: StepWord2 "may be repeated"
+// (HRec.c:1046), so the list kernels get room for every word node thrice per frame and some more (the static order: pathMul = 1, pathExtra = 0).
+enum { DEC_ORD_PATH_MUL = 3, DEC_ORD_PATH_EXTRA = 64 };
+inline size_t htkamd_dec_path_records(size_t pathMul, size_t T, int nWordNodes, size_t pathExtra) { return pathMul * (T + 1) * (size_t)nWordNodes + pathExtra; }
+// ... and the instance list: appends of one frame's pass 2 (attaches + moves) on top of the live instances
+inline int htkamd_dec_ord_seq_cap(int nNodes) { return 8 * nNodes + 1024; }
 // K1 writes a score block state-major (a state's frames are a lane's stores); the token loops read a COLUMN per frame: one 128-byte line per
 // state and frame -- 640 KB per utterance and frame on the 5k-state set.  Transposed once (tiles through LDS), a frame's column is 20 KB.
 // ns > 0: rows per utterance (one network); ns = 0: DecUtt::ns rows, at most maxNs (a network per utterance)
@@ -132,9 +138,11 @@ struct DecArena {
    void release() { for (int i = 0; i < SLOTS; i++) { if (ptr[i]) (void)hipFree(ptr[i]); ptr[i] = nullptr; cap[i] = 0; } }
 };
 
-// What the two decoders do alike before their token kernels run (decode.hip).
-int htkamd_decoder_order(const htkamd_decoder *d);      // the decoder's order mode, HTKAMD_DECODE_ORDER (fast | exact | anything else: auto) overriding it
-// Utterances u0 .. u1 of a batch: as many as stay under ~24 GB of per-utterance work space by the caller's estimate (at least one), their
+// What the decoders do alike (decode.hip).
+int htkamd_decoder_order(int mode);      // a decoder's order mode, HTKAMD_DECODE_ORDER (fast | exact | anything else: auto) overriding it
+// The per-utterance work space a chunk of a batch may take by the caller's estimate (htkamd_decoder_plan_nets; HTKAMD_DECODE_CHUNK_BYTES overrides)
+constexpr size_t DEC_CHUNK_BYTES = (size_t)24 << 30;
+// Utterances u0 .. u1 of a batch: as many as stay under DEC_CHUNK_BYTES of per-utterance work space by the caller's estimate (at least one), their
 // descriptors, the score block's tasks and the sizes of the per-utterance arrays in elements.
 struct DecBatch {
    int u1, maxT;
@@ -142,7 +150,7 @@ struct DecBatch {
    std::vector<ScoreTask> tasks;
    size_t score, tok, node, path;
 };
-// uttBytes(T): the estimate for an utterance of T frames; DecUtt::out0 = k * outStride; path records per utterance: pathMul * (T + 1) * nWordNodes + pathExtra
+// uttBytes(T): the estimate for an utterance of T frames; DecUtt::out0 = k * outStride; path records per utterance: htkamd_dec_path_records
 void htkamd_decoder_plan(const DecNet &N, const int *frameOff, int u0, int nUtt, int ns, int FR, int SL, const std::function<size_t(size_t)> &uttBytes,
                          size_t outStride, size_t pathMul, size_t pathExtra, DecBatch &b);
 // The same with a network per utterance (decode_set.hip): what utterance u decodes against, as the plan needs it
@@ -165,7 +173,30 @@ int htkamd_decoder_score_slots(const htkamd_model *m, const int *dUsedStates, in
 typedef std::function<int(const void *, size_t, const void **)> DecPut;
 int htkamd_decoder_pack(htkamd_model *m, const htkamd_net_desc *nd, float lmScale, bool noReg, bool withHmmState, const DecPut &put, DecNet &N,
                         std::vector<int> &usedStates, const int **dUsedStates);
+// The token kernel's launch.  One network N: tokens of its plain models in registers where it has such models (DecNet::nReg).
+int htkamd_launch_decode(const DecArgs &a, const DecNet &N, int nUtt, hipStream_t s);
 int htkamd_launch_decode_set(const DecArgs &a, int nUtt, hipStream_t s);      // k_decode<0, DEC_SET_THREADS, true, false, true>
+
+// A 1-best run (htkamd_decoder_run_out, htkamd_decoder_set_run): the batch in chunks under DEC_CHUNK_BYTES, each scored, decoded by `launch`,
+// decoded again in exact order where the mode asks for it (k_decode_ord, a launch per network among the chosen utterances) and copied into
+// the caller's arrays.  What the two callers differ in:
+struct DecRun {
+   const char *who;                                    // the name errors start with
+   DecArena *ws;
+   const htkamd_model *m; const int *dUsedStates;      // the scorer's slot table ...
+   int maxNs;                                          // ... and the most rows a network takes of it (0: one network)
+   std::function<DecUttNet(int)> netOf;                // what utterance u decodes against
+   const DecNet *nets; const int *ns;                  // host side, by DecUttNet::net: the record with its device pointers, the tied states
+   const DecNet *dNets;                                // DecArgs::nets; NULL: one network, handed over in DecArgs::net / ns (DecUtt::ns = 0)
+   std::function<int(const DecArgs &, int, hipStream_t)> launch;
+   int orderMode;
+   int *lastTied;                                      // utterances that went through k_decode_ord
+   hipEvent_t *ev;                                     // [4] or NULL: around the scoring kernels and around the token kernel ...
+   float *scoreMs, *tokenMs;                           // ... whose times are added up over the chunks here
+   long long *live;                                    // [2] or NULL: DecArgs::liveCnt summed over the batch
+};
+int htkamd_decoder_run_1best(const DecRun &r, const htkamd_decode_config *cfg, const float *dX, const int *frameOff, int nUtt, int maxWords,
+                             const htkamd_decode_out *out, hipStream_t s);
 
 struct htkamd_decoder {
    htkamd_model *m;

@@ -661,10 +661,10 @@ void *DecArena::get(size_t n)
    return ptr[i];
 }
 
-int htkamd_decoder_order(const htkamd_decoder *d)
+int htkamd_decoder_order(int mode)
 {
    if (const char *ev = getenv("HTKAMD_DECODE_ORDER")) return !strcmp(ev, "fast") ? HTKAMD_ORDER_FAST : !strcmp(ev, "exact") ? HTKAMD_ORDER_EXACT : HTKAMD_ORDER_AUTO;
-   return d->orderMode;
+   return mode;
 }
 
 void htkamd_decoder_plan(const DecNet &N, const int *frameOff, int u0, int nUtt, int ns, int FR, int SL, const std::function<size_t(size_t)> &uttBytes,
@@ -678,10 +678,12 @@ void htkamd_decoder_plan(const DecNet &N, const int *frameOff, int u0, int nUtt,
 void htkamd_decoder_plan_nets(const std::function<DecUttNet(int)> &netOf, const int *frameOff, int u0, int nUtt, int FR, int SL,
                               const std::function<size_t(size_t, const DecUttNet &)> &uttBytes, size_t outStride, size_t pathMul, size_t pathExtra, DecBatch &b)
 {
+   size_t budget = DEC_CHUNK_BYTES;
+   if (const char *ev = getenv("HTKAMD_DECODE_CHUNK_BYTES")) { const unsigned long long v = strtoull(ev, nullptr, 10); if (v > 0) budget = (size_t)v; }
    size_t bytes = 0; int u1 = u0;
    while (u1 < nUtt) {
       const size_t ub = uttBytes((size_t)(frameOff[u1 + 1] - frameOff[u1]), netOf(u1));
-      if (u1 > u0 && bytes + ub > ((size_t)24 << 30)) break;
+      if (u1 > u0 && bytes + ub > budget) break;
       bytes += ub; u1++;
    }
    const int nu = u1 - u0;
@@ -697,7 +699,7 @@ void htkamd_decoder_plan_nets(const std::function<DecUttNet(int)> &netOf, const 
       ud.score0 = b.score; ud.tok0 = b.tok; ud.node0 = b.node; ud.path0 = b.path; ud.out0 = (size_t)k * outStride;
       htkamd_tile_tasks(b.tasks, ud.frame0, ud.T, un.slot0, ns, ud.score0, ud.T, FR, SL);
       b.maxT = std::max(b.maxT, ud.T);
-      b.score += (size_t)ns * ud.T; b.tok += (size_t)N.nTok; b.node += (size_t)N.nNodes; b.path += pathMul * ((size_t)(ud.T + 1) * N.nWordNodes) + pathExtra;
+      b.score += (size_t)ns * ud.T; b.tok += (size_t)N.nTok; b.node += (size_t)N.nNodes; b.path += htkamd_dec_path_records(pathMul, (size_t)ud.T, N.nWordNodes, pathExtra);
    }
 }
 
@@ -1051,7 +1053,172 @@ int htkamd_launch_decode_set(const DecArgs &a, int nUtt, hipStream_t s)
    return HTKAMD_OK;
 }
 
+int htkamd_launch_decode(const DecArgs &a, const DecNet &N, int nUtt, hipStream_t s)
+{
+   // tokens of the plain models in registers where the network has such models (DecNet::nReg), NPT of them per thread
+   const int npt = (N.nReg + DEC_REG_THREADS - 1) / DEC_REG_THREADS;
+   const bool hasG = N.nReg < N.nHmm;
+   // ... and the exit tokens they pull in LDS where xs, the word ends' likelihoods and the transition matrices fit beside the static 3 KB
+#define DEC_LAUNCH_REG(NPT_) do { \
+      const size_t ldsX_ = sizeof(Tok) * (size_t)(NPT_) * DEC_REG_THREADS + sizeof(double) * (size_t)N.nWordNodes + sizeof(float) * (size_t)N.nTpFloats; \
+      const bool exl_ = ldsX_ + 3072 <= 160 * 1024 && !getenv("HTKAMD_DECODE_NOEXL"); \
+      const size_t lds_ = exl_ ? ldsX_ : (sizeof(Tok) + sizeof(float)) * (size_t)(NPT_) * DEC_REG_THREADS; \
+      const void *fn_ = exl_ ? (hasG ? (const void *)k_decode<NPT_, DEC_REG_THREADS, true, true> : (const void *)k_decode<NPT_, DEC_REG_THREADS, false, true>) \
+                             : (hasG ? (const void *)k_decode<NPT_, DEC_REG_THREADS, true, false> : (const void *)k_decode<NPT_, DEC_REG_THREADS, false, false>); \
+      (void)hipFuncSetAttribute(fn_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
+      void *args_[] = {(void *)&a}; \
+      (void)hipLaunchKernel(fn_, dim3(nUtt), dim3(DEC_REG_THREADS), args_, lds_, s); } while (0)
+   if (npt == 0) hipLaunchKernelGGL((k_decode<0, DEC_THREADS, true>), dim3(nUtt), dim3(DEC_THREADS), 0, s, a);
+   else if (npt <= 2) DEC_LAUNCH_REG(2);
+   else if (npt <= 4) DEC_LAUNCH_REG(4);
+   else DEC_LAUNCH_REG(DEC_REG_MAXNPT);
+#undef DEC_LAUNCH_REG
+   hipError_t e = hipGetLastError();
+   if (e != hipSuccess) { htkamd_set_error("decoder_run: launch: %s", hipGetErrorString(e)); return HTKAMD_EHIP; }
+   return HTKAMD_OK;
+}
 
+int htkamd_decoder_run_1best(const DecRun &r, const htkamd_decode_config *cfg, const float *dX, const int *frameOff, int nUtt, int maxWords,
+                             const htkamd_decode_out *out, hipStream_t s)
+{
+   *r.lastTied = 0;
+   if (r.ev) *r.scoreMs = *r.tokenMs = 0.0f;
+   if (r.live) r.live[0] = r.live[1] = 0;
+   const bool one = !r.dNets;
+   // (the matrix-core kernels build their frames' operand once per task: four times as many states per task for them, as in forward-backward)
+   const int FR = SCORE_TILE_FRAMES, SL = (cfg->scoreMode & (HTKAMD_SCORE_BF16 | HTKAMD_SCORE_MFMA)) ? SCORE_TASK_SLOTS_WIDE : SCORE_TASK_SLOTS;
+   DecArena &ws = *r.ws;
+   enum { WS_ORDER = 16 };      // first slot of the exact-order pass's buffers
+   DecBatch bt;
+   // chunk the batch so that the per-utterance work space (scores, tokens, path table) stays under DEC_CHUNK_BYTES
+   for (int u0 = 0; u0 < nUtt; u0 = bt.u1) {
+      htkamd_decoder_plan_nets(r.netOf, frameOff, u0, nUtt, FR, SL,
+                               [](size_t T, const DecUttNet &un) { return (size_t)un.ns * T * 8 + (size_t)un.N->nTok * 16 + (size_t)un.N->nNodes * 24 + (T + 1) * (size_t)un.N->nWordNodes * 16; },
+                               (size_t)maxWords, 1, 0, bt);
+      if (one) for (DecUtt &ud : bt.utt) ud.ns = 0;      // (the kernels take the network and its rows from their arguments)
+      const int nu = bt.u1 - u0;
+      const size_t node = bt.node, path = bt.path, nW = (size_t)nu * maxWords, nOut = 3 * nW + nu;
+      // host ends of the chunk's asynchronous copies: they live until the synchronisation that ends the chunk (and are sized while the kernels run)
+      std::vector<DecUtt> sel;
+      std::vector<int> flags(nu, 1), hI;
+      std::vector<float> hF;
+      std::vector<double> hT, hD;
+      std::vector<unsigned long long> hLive;
+      ws.begin(s, r.who);
+      void *dScore = ws.get(bt.score * 4), *dScoreT = ws.get(bt.score * 4), *dTok = ws.get(bt.tok * sizeof(Tok)), *dEx = ws.get(node * sizeof(Tok)), *dImax = ws.get(node * 8);
+      void *dPPrev = ws.get(path * 4), *dPLike = ws.get(path * 8), *dPLm = ws.get(path * 4);
+      void *dUtt = ws.get(sizeof(DecUtt) * nu), *dTasks = ws.get(sizeof(ScoreTask) * bt.tasks.size() + sizeof(int));
+      void *dOutI = ws.get(sizeof(int) * nOut), *dOutF = ws.get(sizeof(float) * nOut), *dTot = ws.get(sizeof(double) * nu);
+      void *dOutD = ws.get(sizeof(double) * nW);
+      // the tie flags and, where they are asked for, the live-instance counters behind them
+      const size_t tieBytes = r.live ? (sizeof(int) * nu + 7) & ~(size_t)7 : sizeof(int) * nu, liveBytes = r.live ? sizeof(unsigned long long) * 2 * (size_t)nu : 0;
+      void *dTie = ws.get(tieBytes + liveBytes);
+      int rc = ws.rc;
+      if (!rc) rc = htkamd_decoder_score_slots(r.m, r.dUsedStates, cfg->scoreMode, dX, frameOff[bt.u1], bt, one ? r.ns[0] : 0, r.maxNs, dUtt, dTasks, (float *)dScore,
+                                               (float *)dScoreT, r.ev ? r.ev[0] : nullptr, r.who, s);
+      if (!rc && r.ev) { (void)hipEventRecord(r.ev[1], s); (void)hipEventRecord(r.ev[2], s); }
+      DecArgs a;
+      memset(&a, 0, sizeof(a));
+      if (!rc) {
+         if (one) { a.net = r.nets[0]; a.ns = r.ns[0]; } else a.nets = r.dNets;
+         a.utt = (const DecUtt *)dUtt; a.nUtt = nu; a.score = (const float *)dScoreT;
+         a.tok = (Tok *)dTok; a.ex = (Tok *)dEx; a.imax = (double *)dImax;
+         a.pathPrev = (int *)dPPrev; a.pathLike = (double *)dPLike; a.pathLm = (float *)dPLm;
+         a.genBeam = cfg->genBeam; a.wordBeam = cfg->wordBeam; a.lmScale = cfg->lmScale; a.wordPen = cfg->wordPen; a.prScale = cfg->prScale; a.maxActive = cfg->maxActive;
+         a.maxWords = maxWords;
+         // the packed outputs: nWords | wordPron | wordStart | wordEnd and wordScore | wordLm | wordAc | finalLm
+         a.nWords = (int *)dOutI; a.wordPron = a.nWords + nu; a.wordStart = a.wordPron + nW; a.wordEnd = a.wordStart + nW;
+         a.wordScore = (float *)dOutF; a.wordLm = a.wordScore + nW; a.wordAc = a.wordLm + nW; a.finalLm = a.wordAc + nW;
+         a.total = (double *)dTot; a.wordLike = (double *)dOutD;
+         a.tieFlag = (int *)dTie;
+         if (r.live) a.liveCnt = (unsigned long long *)((char *)dTie + tieBytes);
+         (void)hipMemsetAsync(dTie, 0, tieBytes + liveBytes, s);
+         rc = r.launch(a, nu, s);
+         if (!rc && r.ev) (void)hipEventRecord(r.ev[3], s);
+      }
+      if (!rc && r.orderMode != HTKAMD_ORDER_FAST) {
+         // the utterances in which two equally likely tokens with different histories met (or all of them: HTKAMD_ORDER_EXACT) once more,
+         // in the order of HRec's instance list (decode_ord.hip); their results replace k_decode's.  k_decode_ord takes ONE network from
+         // its arguments, so the chosen utterances are sorted by network and each network's run of them is a launch
+         if (r.orderMode == HTKAMD_ORDER_AUTO) {
+            hipError_t e;
+            if ((e = hipMemcpyAsync(flags.data(), dTie, sizeof(int) * nu, hipMemcpyDeviceToHost, s)) != hipSuccess || (e = hipStreamSynchronize(s)) != hipSuccess) {
+               htkamd_set_error("%s: %s", r.who, hipGetErrorString(e)); rc = HTKAMD_EHIP;
+            }
+         }
+         std::vector<int> pick;
+         for (int k = 0; k < nu && !rc; k++) if (flags[k]) pick.push_back(k);
+         std::stable_sort(pick.begin(), pick.end(), [&](int x, int y) { return bt.utt[x].net < bt.utt[y].net; });
+         if (!pick.empty()) {
+            const int nSel = (int)pick.size();
+            struct Group { int first, n, net, seqCap; size_t seq0; };
+            std::vector<Group> groups;
+            size_t opath = 0, seqTotal = 0;
+            for (int k : pick) {
+               DecUtt ud = bt.utt[k];
+               const DecNet &N = r.nets[ud.net];
+               ud.path0 = opath;
+               opath += htkamd_dec_path_records(DEC_ORD_PATH_MUL, (size_t)ud.T, N.nWordNodes, DEC_ORD_PATH_EXTRA);
+               if (groups.empty() || groups.back().net != ud.net) groups.push_back(Group{(int)sel.size(), 0, ud.net, htkamd_dec_ord_seq_cap(N.nNodes), seqTotal});
+               groups.back().n++;
+               seqTotal += 2 * (size_t)groups.back().seqCap;
+               sel.push_back(ud);
+            }
+            ws.seek(WS_ORDER);
+            void *dSel = ws.get(sizeof(DecUtt) * nSel), *dSeq = ws.get(sizeof(int) * seqTotal), *dPos = ws.get(sizeof(int) * node), *dOoo = ws.get(node);
+            void *oPrev = ws.get(opath * 4), *oLike = ws.get(opath * 8), *oLm = ws.get(opath * 4), *oNode = ws.get(opath * 4), *oFrame = ws.get(opath * 4);
+            rc = ws.rc;
+            if (!rc) {
+               hipError_t e = hipMemcpyAsync(dSel, sel.data(), sizeof(DecUtt) * nSel, hipMemcpyHostToDevice, s);
+               if (e != hipSuccess) { htkamd_set_error("%s: %s", r.who, hipGetErrorString(e)); rc = HTKAMD_EHIP; }
+            }
+            for (size_t g = 0; g < groups.size() && !rc; g++) {
+               const Group &G = groups[g];
+               OrdArgs oa;
+               oa.d = a; oa.d.net = r.nets[G.net]; oa.d.ns = r.ns[G.net]; oa.d.nets = nullptr;
+               oa.d.utt = (const DecUtt *)dSel + G.first; oa.d.nUtt = G.n;
+               oa.d.pathPrev = (int *)oPrev; oa.d.pathLike = (double *)oLike; oa.d.pathLm = (float *)oLm;
+               oa.list.seq = (int *)dSeq + G.seq0; oa.list.seqCap = G.seqCap; oa.list.pos = (int *)dPos; oa.list.ooo = (unsigned char *)dOoo;
+               oa.list.pathNode = (int *)oNode; oa.list.pathFrame = (int *)oFrame; oa.list.pathExtra = DEC_ORD_PATH_EXTRA;
+               oa.keepFast = r.orderMode == HTKAMD_ORDER_AUTO ? 1 : 0;
+               rc = htkamd_launch_decode_ord(oa, G.n, s);
+            }
+            if (!rc) *r.lastTied += nSel;
+         }
+      }
+      if (!rc) {
+         hLive.assign(liveBytes / sizeof(unsigned long long), 0); hI.resize(nOut); hF.resize(nOut); hT.resize(nu); hD.resize(nW);
+         hipError_t e = hipSuccess;
+         if (r.live) e = hipMemcpyAsync(hLive.data(), (char *)dTie + tieBytes, liveBytes, hipMemcpyDeviceToHost, s);
+         if (e != hipSuccess ||
+             (e = hipMemcpyAsync(hI.data(), dOutI, sizeof(int) * hI.size(), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+             (e = hipMemcpyAsync(hF.data(), dOutF, sizeof(float) * hF.size(), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+             (e = hipMemcpyAsync(hT.data(), dTot, sizeof(double) * nu, hipMemcpyDeviceToHost, s)) != hipSuccess ||
+             (e = hipMemcpyAsync(hD.data(), dOutD, sizeof(double) * hD.size(), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+             (e = hipStreamSynchronize(s)) != hipSuccess) { htkamd_set_error("%s: %s", r.who, hipGetErrorString(e)); rc = HTKAMD_EHIP; }
+      } else (void)hipStreamSynchronize(s);
+      if (rc) return rc;
+      if (r.ev) {
+         float ms = 0.0f;
+         if (hipEventElapsedTime(&ms, r.ev[0], r.ev[1]) == hipSuccess) *r.scoreMs += ms;
+         if (hipEventElapsedTime(&ms, r.ev[2], r.ev[3]) == hipSuccess) *r.tokenMs += ms;
+      }
+      for (size_t k = 0; k < hLive.size(); k++) r.live[k & 1] += (long long)hLive[k];
+      for (int k = 0; k < nu; k++) {
+         out->nWords[u0 + k] = hI[k]; out->total[u0 + k] = hT[k];
+         if (out->finalLm) out->finalLm[u0 + k] = hF[3 * nW + k];
+         const size_t o = (size_t)(u0 + k) * maxWords, si = (size_t)k * maxWords;
+         for (int w = 0; w < maxWords; w++) {
+            out->wordPron[o + w] = hI[nu + si + w]; out->wordStart[o + w] = hI[nu + nW + si + w];
+            out->wordEnd[o + w] = hI[nu + 2 * nW + si + w]; out->wordScore[o + w] = hF[si + w];
+            if (out->wordLm) out->wordLm[o + w] = hF[nW + si + w];
+            if (out->wordAc) out->wordAc[o + w] = hF[2 * nW + si + w];
+            if (out->wordLike) out->wordLike[o + w] = hD[si + w];
+         }
+      }
+   }
+   return HTKAMD_OK;
+}
 
 extern "C" int htkamd_decoder_run(htkamd_decoder *d, const htkamd_decode_config *cfg, const float *dX, const int *frameOff, int nUtt,
                                   int maxWords, int *nWords, int *wordPron, int *wordStart, int *wordEnd, float *wordScore, float *wordLm,
@@ -1066,158 +1233,15 @@ extern "C" int htkamd_decoder_run(htkamd_decoder *d, const htkamd_decode_config 
 extern "C" int htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_config *cfg, const float *dX, const int *frameOff, int nUtt,
                                       int maxWords, const htkamd_decode_out *out, void *stream)
 {
-   if (!out) { htkamd_set_error("decoder_run: bad argument"); return HTKAMD_EINVAL; }
-   int *nWords = out->nWords, *wordPron = out->wordPron, *wordStart = out->wordStart, *wordEnd = out->wordEnd;
-   float *wordScore = out->wordScore, *wordLm = out->wordLm, *wordAc = out->wordAc;
-   double *total = out->total, *wordLike = out->wordLike;
-   float *finalLm = out->finalLm;
-   if (!d || !cfg || !frameOff || nUtt < 0 || maxWords < 1 || !nWords || !wordPron || !wordStart || !wordEnd || !wordScore || !total) {
+   if (!d || !cfg || !out || !frameOff || nUtt < 0 || maxWords < 1 || !out->nWords || !out->wordPron || !out->wordStart || !out->wordEnd || !out->wordScore || !out->total) {
       htkamd_set_error("decoder_run: bad argument"); return HTKAMD_EINVAL;
    }
    if (nUtt == 0) return HTKAMD_OK;
-   hipStream_t s = (hipStream_t)stream;
-   const DecNet &N = d->net;
-   const int ns = (int)d->usedStates.size();
-   // (the matrix-core kernels build their frames' operand once per task: four times as many states per task for them, as in forward-backward)
-   const int FR = SCORE_TILE_FRAMES, SL = (cfg->scoreMode & (HTKAMD_SCORE_BF16 | HTKAMD_SCORE_MFMA)) ? SCORE_TASK_SLOTS_WIDE : SCORE_TASK_SLOTS;
    if (!d->ev[0]) for (int i = 0; i < 4; i++) HIPCHECK(hipEventCreate(&d->ev[i]));
-   d->lastScoreMs = d->lastTokenMs = 0.0f;
-   d->lastLive[0] = d->lastLive[1] = 0;
-   const int orderMode = htkamd_decoder_order(d);
-   d->lastTied = 0;
-   DecArena &ws = d->ws;
-   enum { WS_ORDER = 16 };      // first slot of the exact-order pass's buffers
-   DecBatch bt;
-   // chunk the batch so that the per-utterance work space (scores, tokens, path table) stays under ~24 GB
-   int u0 = 0;
-   while (u0 < nUtt) {
-      htkamd_decoder_plan(N, frameOff, u0, nUtt, ns, FR, SL,
-                          [&](size_t T) { return (size_t)ns * T * 8 + (size_t)N.nTok * 16 + (size_t)N.nNodes * 24 + (T + 1) * (size_t)N.nWordNodes * 16; },
-                          (size_t)maxWords, 1, 0, bt);
-      const int u1 = bt.u1, nu = u1 - u0;
-      const size_t score = bt.score, tok = bt.tok, node = bt.node, path = bt.path;
-      ws.begin(s, "decoder_run");
-      void *dScore = ws.get(score * 4), *dScoreT = ws.get(score * 4), *dTok = ws.get(tok * sizeof(Tok)), *dEx = ws.get(node * sizeof(Tok)), *dImax = ws.get(node * 8);
-      void *dPPrev = ws.get(path * 4), *dPLike = ws.get(path * 8), *dPLm = ws.get(path * 4);
-      void *dUtt = ws.get(sizeof(DecUtt) * nu), *dTasks = ws.get(sizeof(ScoreTask) * bt.tasks.size() + sizeof(int));
-      void *dOutI = ws.get(sizeof(int) * ((size_t)nu * maxWords * 3 + nu)), *dOutF = ws.get(sizeof(float) * ((size_t)nu * maxWords * 3 + nu)), *dTot = ws.get(sizeof(double) * nu);
-      void *dOutD = ws.get(sizeof(double) * (size_t)nu * maxWords);
-      const size_t tieBytes = (sizeof(int) * nu + 7) & ~(size_t)7;
-      void *dTie = ws.get(tieBytes + sizeof(unsigned long long) * (2 * (size_t)nu));
-      int rc = ws.rc;
-      std::vector<int> hI; std::vector<float> hF; std::vector<double> hT, hD;
-      if (!rc) rc = htkamd_decoder_score(d, cfg->scoreMode, dX, frameOff[u1], bt, ns, dUtt, dTasks, (float *)dScore, (float *)dScoreT, d->ev[0], "decoder_run", s);
-      if (!rc) { (void)hipEventRecord(d->ev[1], s); (void)hipEventRecord(d->ev[2], s); }
-      DecArgs a;
-      memset(&a, 0, sizeof(a));
-      if (!rc) {
-         a.net = N; a.utt = (const DecUtt *)dUtt; a.nUtt = nu; a.score = (const float *)dScoreT; a.ns = ns;
-         a.tok = (Tok *)dTok; a.ex = (Tok *)dEx; a.imax = (double *)dImax;
-         a.pathPrev = (int *)dPPrev; a.pathLike = (double *)dPLike; a.pathLm = (float *)dPLm;
-         a.genBeam = cfg->genBeam; a.wordBeam = cfg->wordBeam; a.lmScale = cfg->lmScale; a.wordPen = cfg->wordPen; a.prScale = cfg->prScale; a.maxActive = cfg->maxActive;
-         a.maxWords = maxWords;
-         int *oi = (int *)dOutI;
-         a.nWords = oi; a.wordPron = oi + nu; a.wordStart = a.wordPron + (size_t)nu * maxWords; a.wordEnd = a.wordStart + (size_t)nu * maxWords;
-         a.wordScore = (float *)dOutF; a.wordLm = (float *)dOutF + (size_t)nu * maxWords; a.wordAc = (float *)dOutF + (size_t)nu * maxWords * 2; a.finalLm = (float *)dOutF + (size_t)nu * maxWords * 3; a.total = (double *)dTot;
-         a.wordLike = (double *)dOutD;
-         a.tieFlag = (int *)dTie;
-         a.liveCnt = (unsigned long long *)((char *)dTie + tieBytes);
-         (void)hipMemsetAsync(dTie, 0, tieBytes + sizeof(unsigned long long) * (2 * (size_t)nu), s);
-         // tokens of the plain models in registers where the network has such models (DecNet::nReg), NPT of them per thread
-         const int npt = (N.nReg + DEC_REG_THREADS - 1) / DEC_REG_THREADS;
-         const bool hasG = N.nReg < N.nHmm;
-         // ... and the exit tokens they pull in LDS where xs, the word ends' likelihoods and the transition matrices fit beside the static 3 KB
-#define DEC_LAUNCH_REG(NPT_) do { \
-            const size_t ldsX_ = sizeof(Tok) * (size_t)(NPT_) * DEC_REG_THREADS + sizeof(double) * (size_t)N.nWordNodes + sizeof(float) * (size_t)N.nTpFloats; \
-            const bool exl_ = ldsX_ + 3072 <= 160 * 1024 && !getenv("HTKAMD_DECODE_NOEXL"); \
-            const size_t lds_ = exl_ ? ldsX_ : (sizeof(Tok) + sizeof(float)) * (size_t)(NPT_) * DEC_REG_THREADS; \
-            const void *fn_ = exl_ ? (hasG ? (const void *)k_decode<NPT_, DEC_REG_THREADS, true, true> : (const void *)k_decode<NPT_, DEC_REG_THREADS, false, true>) \
-                                   : (hasG ? (const void *)k_decode<NPT_, DEC_REG_THREADS, true, false> : (const void *)k_decode<NPT_, DEC_REG_THREADS, false, false>); \
-            (void)hipFuncSetAttribute(fn_, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_); \
-            void *args_[] = {(void *)&a}; \
-            (void)hipLaunchKernel(fn_, dim3(nu), dim3(DEC_REG_THREADS), args_, lds_, s); } while (0)
-         if (npt == 0) hipLaunchKernelGGL((k_decode<0, DEC_THREADS, true>), dim3(nu), dim3(DEC_THREADS), 0, s, a);
-         else if (npt <= 2) DEC_LAUNCH_REG(2);
-         else if (npt <= 4) DEC_LAUNCH_REG(4);
-         else DEC_LAUNCH_REG(DEC_REG_MAXNPT);
-#undef DEC_LAUNCH_REG
-         hipError_t e = hipGetLastError();
-         if (e != hipSuccess) { htkamd_set_error("decoder_run: launch: %s", hipGetErrorString(e)); rc = HTKAMD_EHIP; }
-         (void)hipEventRecord(d->ev[3], s);
-      }
-      if (!rc && orderMode != HTKAMD_ORDER_FAST) {
-         // the utterances in which two equally likely tokens with different histories met (or all of them: HTKAMD_ORDER_EXACT) once more,
-         // in the order of HRec's instance list (decode_ord.hip); their results replace k_decode's
-         std::vector<int> flags(nu, 1);
-         if (orderMode == HTKAMD_ORDER_AUTO) {
-            hipError_t e;
-            if ((e = hipMemcpyAsync(flags.data(), dTie, sizeof(int) * nu, hipMemcpyDeviceToHost, s)) != hipSuccess || (e = hipStreamSynchronize(s)) != hipSuccess) {
-               htkamd_set_error("decoder_run: %s", hipGetErrorString(e)); rc = HTKAMD_EHIP;
-            }
-         }
-         std::vector<DecUtt> sel;
-         size_t opath = 0;
-         const int pathExtra = 64;
-         for (int k = 0; k < nu && !rc; k++)
-            if (flags[k]) {
-               DecUtt ud = bt.utt[k];
-               ud.path0 = opath;
-               opath += 3 * ((size_t)(ud.T + 1) * N.nWordNodes) + pathExtra;      // StepWord2 "may be repeated" (HRec.c:1046): room for every word node thrice per frame
-               sel.push_back(ud);
-            }
-         if (!rc && !sel.empty()) {
-            const int nSel = (int)sel.size();
-            const int seqCap = 8 * N.nNodes + 1024;          // appends of one frame's pass 2 (attaches + moves) on top of the live instances
-            ws.seek(WS_ORDER);
-            void *dSel = ws.get(sizeof(DecUtt) * nSel), *dSeq = ws.get(sizeof(int) * (size_t)nSel * 2 * seqCap), *dPos = ws.get(sizeof(int) * node), *dOoo = ws.get(node);
-            void *oPrev = ws.get(opath * 4), *oLike = ws.get(opath * 8), *oLm = ws.get(opath * 4), *oNode = ws.get(opath * 4), *oFrame = ws.get(opath * 4);
-            rc = ws.rc;
-            if (!rc) {
-               hipError_t e = hipMemcpyAsync(dSel, sel.data(), sizeof(DecUtt) * nSel, hipMemcpyHostToDevice, s);
-               if (e != hipSuccess) { htkamd_set_error("decoder_run: %s", hipGetErrorString(e)); rc = HTKAMD_EHIP; }
-            }
-            if (!rc) {
-               OrdArgs oa;
-               oa.d = a; oa.d.utt = (const DecUtt *)dSel; oa.d.nUtt = nSel;
-               oa.d.pathPrev = (int *)oPrev; oa.d.pathLike = (double *)oLike; oa.d.pathLm = (float *)oLm;
-               oa.list.seq = (int *)dSeq; oa.list.seqCap = seqCap; oa.list.pos = (int *)dPos; oa.list.ooo = (unsigned char *)dOoo;
-               oa.list.pathNode = (int *)oNode; oa.list.pathFrame = (int *)oFrame; oa.list.pathExtra = pathExtra;
-               oa.keepFast = orderMode == HTKAMD_ORDER_AUTO ? 1 : 0;
-               // (the path capacity the kernel assumes per utterance is 3 (T + 1) nWordNodes + pathExtra: see opath above)
-               rc = htkamd_launch_decode_ord(oa, nSel, s);
-            }
-            d->lastTied += nSel;
-         }
-      }
-      std::vector<unsigned long long> hLive(2 * (size_t)nu, 0);
-      if (!rc) (void)hipMemcpyAsync(hLive.data(), (char *)dTie + tieBytes, sizeof(unsigned long long) * hLive.size(), hipMemcpyDeviceToHost, s);
-      if (!rc) {
-         hI.resize((size_t)nu * maxWords * 3 + nu); hF.resize((size_t)nu * maxWords * 3 + nu); hT.resize(nu); hD.resize((size_t)nu * maxWords);
-         hipError_t e;
-         if ((e = hipMemcpyAsync(hI.data(), dOutI, sizeof(int) * hI.size(), hipMemcpyDeviceToHost, s)) != hipSuccess ||
-             (e = hipMemcpyAsync(hF.data(), dOutF, sizeof(float) * hF.size(), hipMemcpyDeviceToHost, s)) != hipSuccess ||
-             (e = hipMemcpyAsync(hT.data(), dTot, sizeof(double) * nu, hipMemcpyDeviceToHost, s)) != hipSuccess ||
-             (e = hipMemcpyAsync(hD.data(), dOutD, sizeof(double) * hD.size(), hipMemcpyDeviceToHost, s)) != hipSuccess ||
-             (e = hipStreamSynchronize(s)) != hipSuccess) { htkamd_set_error("decoder_run: %s", hipGetErrorString(e)); rc = HTKAMD_EHIP; }
-      } else (void)hipStreamSynchronize(s);
-      if (rc) return rc;
-      { float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, d->ev[0], d->ev[1]) == hipSuccess) d->lastScoreMs += ms;
-        if (hipEventElapsedTime(&ms, d->ev[2], d->ev[3]) == hipSuccess) d->lastTokenMs += ms; }
-      for (int k = 0; k < nu; k++) { d->lastLive[0] += (long long)hLive[2 * k]; d->lastLive[1] += (long long)hLive[2 * k + 1]; }
-      for (int k = 0; k < nu; k++) {
-         nWords[u0 + k] = hI[k]; total[u0 + k] = hT[k];
-         if (finalLm) finalLm[u0 + k] = hF[(size_t)nu * maxWords * 3 + k];
-         const size_t o = (size_t)(u0 + k) * maxWords, si = (size_t)k * maxWords;
-         for (int w = 0; w < maxWords; w++) {
-            wordPron[o + w] = hI[nu + si + w]; wordStart[o + w] = hI[nu + (size_t)nu * maxWords + si + w];
-            wordEnd[o + w] = hI[nu + (size_t)nu * maxWords * 2 + si + w]; wordScore[o + w] = hF[si + w];
-            if (wordLm) wordLm[o + w] = hF[(size_t)nu * maxWords + si + w];
-            if (wordAc) wordAc[o + w] = hF[(size_t)nu * maxWords * 2 + si + w];
-            if (wordLike) wordLike[o + w] = hD[si + w];
-         }
-      }
-      u0 = u1;
-   }
-   return HTKAMD_OK;
+   const int ns = (int)d->usedStates.size();
+   const DecUttNet one = {&d->net, 0, ns, 0};
+   const DecRun r = {"decoder_run", &d->ws, d->m, d->d_usedStates, 0, [&](int) { return one; }, &d->net, &ns, nullptr,
+                     [&](const DecArgs &a, int nu, hipStream_t s) { return htkamd_launch_decode(a, d->net, nu, s); },
+                     htkamd_decoder_order(d->orderMode), &d->lastTied, d->ev, &d->lastScoreMs, &d->lastTokenMs, d->lastLive};
+   return htkamd_decoder_run_1best(r, cfg, dX, frameOff, nUtt, maxWords, out, (hipStream_t)stream);
 }

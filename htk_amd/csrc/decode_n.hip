@@ -788,11 +788,11 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
    const int FR = SCORE_TILE_FRAMES, SL = SCORE_TASK_SLOTS;
    // the list kernel (k_decode_ord_n) unless the static order was asked for: in N-best mode the order of the merges is in every
    // alternative's likelihood, so "exact" is the default here, not a fallback
-   const int orderMode = htkamd_decoder_order(d);
+   const int orderMode = htkamd_decoder_order(d->orderMode);
    if (alignMode && orderMode == HTKAMD_ORDER_FAST) { htkamd_set_error("decoder_run_lattice_align: alignment records need the list kernel (not HTKAMD_ORDER_FAST)"); return HTKAMD_EINVAL; }
    const bool listOrder = orderMode != HTKAMD_ORDER_FAST;
-   const size_t pathMul = listOrder ? 3 : 1, pathExtra = listOrder ? 64 : 0;       // StepWord2 "may be repeated" (HRec.c:1046)
-   const int seqCap = 8 * N.nNodes + 1024;
+   const size_t pathMul = listOrder ? DEC_ORD_PATH_MUL : 1, pathExtra = listOrder ? DEC_ORD_PATH_EXTRA : 0;
+   const int seqCap = htkamd_dec_ord_seq_cap(N.nNodes);
    d->lastTied = 0;
    DecArena &ws = d->wsN;
    enum { WS_LIST = 32, WS_ALIGN = 40 };      // first slots of the list kernel's buffers and of the alignment records
@@ -801,7 +801,7 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
    while (u0 < nUtt) {
       htkamd_decoder_plan(N, frameOff, u0, nUtt, ns, FR, SL,
                           [&](size_t T) { return (size_t)ns * T * 8 + (size_t)N.nTok * 2 * sizeof(TSet) + (size_t)N.nNodes * (sizeof(TSet) + 8) +
-                                                 (pathMul * (T + 1) * (size_t)N.nWordNodes + pathExtra) * (24 + 16 * (NT - 1) + 8) + (listOrder ? (size_t)seqCap * 8 : 0); },
+                                                 htkamd_dec_path_records(pathMul, T, N.nWordNodes, pathExtra) * (24 + 16 * (NT - 1) + 8) + (listOrder ? (size_t)seqCap * 8 : 0); },
                           0, pathMul, pathExtra, bt);
       const int u1 = bt.u1, nu = u1 - u0, maxT = bt.maxT;
       const size_t score = bt.score, tok = bt.tok, node = bt.node, path = bt.path;

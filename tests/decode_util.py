@@ -64,3 +64,36 @@ def format_model_labels(words, lms, align, pron_models, phys_names, out_syms, lm
     # a score column is written when any label of the file has a non-zero score in it (SaveHTKLabels HLabel.c:1493-1517)
     any_aux = any(a is not None and a != 0.0 for _, a in rows)
     return [ln + (" %f" % a if (a is not None and any_aux) else "") for ln, a in rows]
+
+
+# HTKAMD_DECODE_CHUNK_BYTES, the work-space budget by which htkamd_decoder_plan_nets cuts a batch into chunks: 1 puts one utterance in each
+# chunk (the planner always takes at least one), the others cut the small fixtures into uneven chunks of several utterances, up to one chunk
+CHUNK_BUDGETS = (1, 4 << 10, 16 << 10, 64 << 10, 256 << 10, 1 << 20, 4 << 20, 16 << 20)
+
+
+def runs_under_chunk_budgets(monkeypatch, run):
+    """[(budget, run())]: first with HTKAMD_DECODE_CHUNK_BYTES unset (budget None), then once per CHUNK_BUDGETS."""
+    monkeypatch.delenv("HTKAMD_DECODE_CHUNK_BYTES", raising=False)
+    out = [(None, run())]
+    for b in CHUNK_BUDGETS:
+        monkeypatch.setenv("HTKAMD_DECODE_CHUNK_BYTES", str(b))
+        out.append((b, run()))
+    monkeypatch.delenv("HTKAMD_DECODE_CHUNK_BYTES")
+    return out
+
+
+def assert_same_decode_out(got, ref, what):
+    """Two sets of htkamd_decode_out arrays ([nUtt] / [nUtt, maxWords]): == on the ints, array_equal on the floats and doubles, over the
+    columns [:nWords] of every utterance (what follows them is work space nobody wrote); a failed utterance's nWords and total only."""
+    assert len(got["nWords"]) == len(ref["nWords"]), what
+    for u in range(len(ref["nWords"])):
+        n = int(ref["nWords"][u])
+        assert int(got["nWords"][u]) == n, (what, u)
+        assert np.array_equal(got["total"][u], ref["total"][u]), (what, u)
+        if n < 0:
+            continue
+        assert np.array_equal(got["finalLm"][u], ref["finalLm"][u]), (what, u)
+        for f in ("wordPron", "wordStart", "wordEnd"):
+            assert [int(x) for x in got[f][u, :n]] == [int(x) for x in ref[f][u, :n]], (what, u, f)
+        for f in ("wordScore", "wordLm", "wordAc", "wordLike"):
+            assert got[f].dtype == ref[f].dtype and np.array_equal(got[f][u, :n], ref[f][u, :n]), (what, u, f)

@@ -426,3 +426,38 @@ def test_token_kernel_variants_agree(native, case, monkeypatch):
             assert native.Decoder(model, net, lmScale=p["lmScale"]).run(feats, **kw) == ref, (case, opts, extra, "NOEXL")
             monkeypatch.setenv("HTKAMD_DECODE_NOREG", "1")
             assert native.Decoder(model, net, lmScale=p["lmScale"]).run(feats, **kw) == ref, (case, opts, extra, "NOREG")
+
+
+# ----------------------------------------------------------------------------------------- chunks of a batch
+def _single_under_budgets(native, case, order, monkeypatch):
+    """The single decoder's every output array and last_tied with the chunk budget unset and under each of CHUNK_BUDGETS: all the same."""
+    from decode_util import assert_same_decode_out, runs_under_chunk_budgets
+    from test_gpu_decoder_set import single_arrays
+    mmf, net, feats, expected = load_decode_case(native, case)
+    model = native.Model(mmf.packed())
+    p = parse_opts(next(iter(expected)))
+    assert len(feats) >= 2
+    runs = runs_under_chunk_budgets(monkeypatch, lambda: single_arrays(native, model, net, feats, order=order, **p))
+    (ref, tied) = runs[0][1]
+    for budget, (got, t) in runs[1:]:
+        assert_same_decode_out(got, ref, (case, order, budget))
+        assert t == tied, (case, order, budget)
+    return ref, tied
+
+
+@pytest.mark.parametrize("order", ["fast", "auto", "exact"])
+def test_chunk_boundaries_change_nothing(native, order, monkeypatch):
+    """htkamd_decoder_run_out on the `loop` case with one utterance per chunk, with uneven chunks of several and with one chunk: the outputs
+    of the run nobody cut (which the tests above hold to HVite), to the last bit, in every order mode."""
+    mode = dict(fast=native.ORDER_FAST, auto=native.ORDER_AUTO, exact=native.ORDER_EXACT)[order]
+    ref, tied = _single_under_budgets(native, "loop", mode, monkeypatch)
+    assert all(int(n) > 0 for n in ref["nWords"])
+    if order != "auto":
+        assert tied == (len(ref["nWords"]) if order == "exact" else 0)
+
+
+@pytest.mark.parametrize("case", TIES2)
+def test_chunk_boundaries_change_nothing_for_exact_ties(native, case, monkeypatch):
+    """... and the exact-order pass of a chunk after the first (budget 1: a chunk per utterance) gives what it gives in an uncut batch."""
+    ref, tied = _single_under_budgets(native, case, native.ORDER_AUTO, monkeypatch)
+    assert tied >= 1

@@ -155,6 +155,25 @@ def test_set_equals_single_decoder_bit_for_bit(native, model_sets, order):
     assert min(sizes) < 20 <= max(sizes) and len(sizes) >= 6          # from a three-word alignment network to the loop case's
 
 
+@pytest.mark.parametrize("order", ["auto", "exact"])
+def test_set_chunk_boundaries_change_nothing(native, model_sets, order, monkeypatch):
+    """The batches of the test above with one utterance per chunk, with uneven chunks of several and with one chunk (decode_util.CHUNK_BUDGETS):
+    the outputs and last_tied of the run nobody cut.  In exact order a chunk of several utterances is grouped by network for the list kernel."""
+    from decode_util import assert_same_decode_out, runs_under_chunk_budgets
+    mode = dict(auto=native.ORDER_AUTO, exact=native.ORDER_EXACT)[order]
+    for gi, (model, nets, utts) in enumerate(model_sets):
+        perm = np.random.default_rng(5 + gi).permutation(len(utts))
+        feats, net_of = [utts[i][0] for i in perm], [utts[i][1] for i in perm]
+        ds = native.DecoderSet(model, nets)
+        ds.set_order(mode)
+        runs = runs_under_chunk_budgets(monkeypatch, lambda: (ds.run_arrays(feats, net_of, genBeam=250.0), ds.last_tied()))
+        ref, tied = runs[0][1]
+        assert tied == len(feats) or order == "auto"
+        for budget, (got, t) in runs[1:]:
+            assert_same_decode_out(got, ref, (order, gi, budget))
+            assert t == tied, (order, gi, budget)
+
+
 @pytest.mark.parametrize("case", ["ties2/tie_122", "ties2/tie_220"])
 def test_set_exact_ties_go_through_the_list_kernel(native, case):
     mmf, net, feats, expected = load_decode_case(native, case)

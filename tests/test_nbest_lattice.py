@@ -182,3 +182,22 @@ def test_token_set_kernel_wide_fan_in(native, oracle, tmp_path):
             assert len(g) == len(r) and len(g) > 50
             assert [x[:5] for x in g] == [x[:5] for x in r]
             assert np.allclose([x[5] for x in g], [x[5] for x in r], atol=1e-3)
+
+
+@pytest.mark.gpu
+def test_lattices_do_not_depend_on_the_chunks_of_the_batch(native, monkeypatch):
+    """htkamd_decoder_run_lattice shares the 1-best decoders' planner: with one utterance per chunk, with several and with one chunk
+    (decode_util.CHUNK_BUDGETS) every array of every lattice, over its nNodes / nArcs entries, is that of the run nobody cut."""
+    from decode_util import runs_under_chunk_budgets
+    tag = "tee_n3_t2500"                                                # the smallest case: a 24-line network, 33 to 75 frames
+    meta, mmf, net, feats, p = _case(native, tag)
+    dec = native.Decoder(native.Model(mmf.packed()), net, lmScale=p["lmScale"])
+    runs = runs_under_chunk_budgets(monkeypatch, lambda: (dec.run_lattice(feats, meta["nToks"], **p), dec.last_tied()))
+    ref, tied = runs[0][1]
+    assert len(ref) >= 2 and all(l is not None and len(l["arcStart"]) > 0 for l in ref)
+    for budget, (got, t) in runs[1:]:
+        assert t == tied, budget
+        for u, (g, r) in enumerate(zip(got, ref)):
+            assert sorted(g) == sorted(r), (budget, u)
+            for k in r:
+                assert np.array_equal(g[k], r[k]) and np.asarray(g[k]).dtype == np.asarray(r[k]).dtype, (budget, u, k)
