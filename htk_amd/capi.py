@@ -92,6 +92,13 @@ def lib():
             L.htkamd_decoder_set_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
             L.htkamd_decoder_set_run.restype = C.c_int
             L.htkamd_decoder_set_last_tied.argtypes = [C.c_void_p]; L.htkamd_decoder_set_last_tied.restype = C.c_int
+            # (cfg, nToks, nBeam, [alignMode,] dX, frameOff, netOf, nUtt, maxLatNodes, maxLatArcs, [maxAlign,] out, [alOut,] stream)
+            L.htkamd_decoder_set_run_lattice.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                         C.c_void_p]
+            L.htkamd_decoder_set_run_lattice.restype = C.c_int
+            L.htkamd_decoder_set_run_lattice_align.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.htkamd_decoder_set_run_lattice_align.restype = C.c_int
             L.htkamd_decoder_set_set_order.argtypes = [C.c_void_p, C.c_int]; L.htkamd_decoder_set_set_order.restype = C.c_int
         _lib = L
     return _lib
@@ -1534,6 +1541,48 @@ def lattice_nbest_align(lat: dict, net: "Net", mmf: "Mmf", N: int, states=False,
     return out
 
 
+class _LatticeRun:
+    """The host side of one htkamd_decoder_run_lattice[_align] / htkamd_decoder_set_run_lattice[_align] call: the batch on the device, the
+    output arrays and their per-utterance unpacking."""
+
+    def __init__(self, feats, D, maxNodes, maxArcs, align, maxAlign):
+        self.nU, self.maxNodes, self.maxArcs, self.align, self.maxAlign = len(feats), maxNodes, maxArcs, align, maxAlign
+        nU = self.nU
+        X = np.ascontiguousarray(np.concatenate(feats) if nU else np.zeros((0, D)), np.float32)
+        self.frameOff = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int32)
+        self.dX = DevArray(X) if X.size else DevArray(nbytes=4)
+        n1 = max(nU, 1)
+        self.nn = np.zeros(n1, np.int32); self.na = np.zeros(n1, np.int32); self.tot = np.zeros(n1, np.float64)
+        self.nF = np.zeros(n1 * maxNodes, np.int32); self.nP = np.zeros_like(self.nF); self.nNet = np.zeros_like(self.nF); self.nL = np.zeros(n1 * maxNodes, np.float64)
+        self.aS = np.zeros(n1 * maxArcs, np.int32); self.aE = np.zeros_like(self.aS); self.aAc = np.zeros(n1 * maxArcs, np.float32); self.aLm = np.zeros_like(self.aAc)
+        self.aPr = np.zeros_like(self.aAc); self.aSc = np.zeros(n1 * maxArcs, np.float64)
+        self.out = LatticeOut(_p(self.nn), _p(self.na), _p(self.nF), _p(self.nP), _p(self.nNet), _p(self.nL), _p(self.aS), _p(self.aE), _p(self.aAc), _p(self.aLm), _p(self.aPr),
+                              _p(self.aSc), _p(self.tot))
+        if align:
+            self.aOff = np.zeros(n1 * (maxArcs + 1), np.int32); self.alS = np.zeros(n1 * maxAlign, np.int32); self.alM = np.zeros_like(self.alS); self.alD = np.zeros_like(self.alS)
+            self.alL = np.zeros(n1 * maxAlign, np.float32)
+            self.alo = LatticeAlignOut(_p(self.aOff), _p(self.alS), _p(self.alM), _p(self.alD), _p(self.alL))
+
+    def unpack(self, who, lmScale, wordPen, prScale):
+        nn, na, maxNodes, maxArcs, maxAlign, align = self.nn, self.na, self.maxNodes, self.maxArcs, self.maxAlign, self.align
+        res = []
+        for u in range(self.nU):
+            if nn[u] == -1:
+                res.append(None); continue
+            if nn[u] < 0:
+                raise HtkAmdError("%s: the lattice of utterance %d does not fit (%d)" % (who, u, nn[u]))
+            n, a_, o, q = int(nn[u]), int(na[u]), u * maxNodes, u * maxArcs
+            res.append(dict(nodeFrame=self.nF[o:o + n].copy(), nodePron=self.nP[o:o + n].copy(), nodeNet=self.nNet[o:o + n].copy(), nodeLike=self.nL[o:o + n].copy(),
+                            arcStart=self.aS[q:q + a_].copy(), arcEnd=self.aE[q:q + a_].copy(), arcAc=self.aAc[q:q + a_].copy(), arcLm=self.aLm[q:q + a_].copy(),
+                            arcPr=self.aPr[q:q + a_].copy(), arcScore=self.aSc[q:q + a_].copy(), total=float(self.tot[u]), lmScale=lmScale, wordPen=float(wordPen),
+                            prScale=float(prScale)))
+            if align:
+                off = self.aOff[u * (maxArcs + 1):u * (maxArcs + 1) + a_ + 1].copy(); k = int(off[-1]); b = u * maxAlign
+                res[-1].update(arcAlignOff=off, alState=self.alS[b:b + k].copy(), alModel=self.alM[b:b + k].copy(), alDur=self.alD[b:b + k].copy(),
+                               alLike=self.alL[b:b + k].copy(), alignModels=bool(align & 1))
+        return res
+
+
 class Decoder:
     """htkamd_decoder holder: HVite -w (1-best word labels) for a batch of utterances on the device."""
 
@@ -1592,42 +1641,16 @@ class Decoder:
         lmScale = self.lmScale if lmScale is None else float(lmScale)
         if lmScale != self.lmScale:
             raise HtkAmdError("Decoder.run_lattice: the LM scale is fixed at creation (LikeToWord look-ahead)")
-        nU = len(feats)
-        X = np.ascontiguousarray(np.concatenate(feats) if nU else np.zeros((0, self.model.D)), np.float32)
-        frameOff = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int32)
-        dX = DevArray(X) if X.size else DevArray(nbytes=4)
-        n1 = max(nU, 1)
-        nn = np.zeros(n1, np.int32); na = np.zeros(n1, np.int32); tot = np.zeros(n1, np.float64)
-        nF = np.zeros(n1 * maxNodes, np.int32); nP = np.zeros_like(nF); nNet = np.zeros_like(nF); nL = np.zeros(n1 * maxNodes, np.float64)
-        aS = np.zeros(n1 * maxArcs, np.int32); aE = np.zeros_like(aS); aAc = np.zeros(n1 * maxArcs, np.float32); aLm = np.zeros_like(aAc); aPr = np.zeros_like(aAc)
-        aSc = np.zeros(n1 * maxArcs, np.float64)
-        out = LatticeOut(_p(nn), _p(na), _p(nF), _p(nP), _p(nNet), _p(nL), _p(aS), _p(aE), _p(aAc), _p(aLm), _p(aPr), _p(aSc), _p(tot))
+        b = _LatticeRun(feats, self.model.D, maxNodes, maxArcs, align, maxAlign)
         cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
         if align:                                            # HVite -n with -m (1) / -f (2): lAlign of every arc
-            aOff = np.zeros(n1 * (maxArcs + 1), np.int32); alS = np.zeros(n1 * maxAlign, np.int32); alM = np.zeros_like(alS); alD = np.zeros_like(alS)
-            alL = np.zeros(n1 * maxAlign, np.float32)
-            alo = LatticeAlignOut(_p(aOff), _p(alS), _p(alM), _p(alD), _p(alL))
-            check(lib().htkamd_decoder_run_lattice_align(self.h, C.byref(cfg), C.c_int(nToks), C.c_float(genBeam if nBeam is None else nBeam), C.c_int(int(align)), dX.ptr,
-                                                         _p(frameOff), C.c_int(nU), C.c_int(maxNodes), C.c_int(maxArcs), C.c_int(maxAlign), C.byref(out), C.byref(alo), None),
+            check(lib().htkamd_decoder_run_lattice_align(self.h, C.byref(cfg), C.c_int(nToks), C.c_float(genBeam if nBeam is None else nBeam), C.c_int(int(align)), b.dX.ptr,
+                                                         _p(b.frameOff), C.c_int(b.nU), C.c_int(maxNodes), C.c_int(maxArcs), C.c_int(maxAlign), C.byref(b.out), C.byref(b.alo), None),
                   "decoder_run_lattice_align")
         else:
-            check(lib().htkamd_decoder_run_lattice(self.h, C.byref(cfg), C.c_int(nToks), C.c_float(genBeam if nBeam is None else nBeam), dX.ptr, _p(frameOff), C.c_int(nU),
-                                                   C.c_int(maxNodes), C.c_int(maxArcs), C.byref(out), None), "decoder_run_lattice")
-        res = []
-        for u in range(nU):
-            if nn[u] == -1:
-                res.append(None); continue
-            if nn[u] < 0:
-                raise HtkAmdError("decoder_run_lattice: the lattice of utterance %d does not fit (%d)" % (u, nn[u]))
-            n, a_, o, q = int(nn[u]), int(na[u]), u * maxNodes, u * maxArcs
-            res.append(dict(nodeFrame=nF[o:o + n].copy(), nodePron=nP[o:o + n].copy(), nodeNet=nNet[o:o + n].copy(), nodeLike=nL[o:o + n].copy(),
-                            arcStart=aS[q:q + a_].copy(), arcEnd=aE[q:q + a_].copy(), arcAc=aAc[q:q + a_].copy(), arcLm=aLm[q:q + a_].copy(), arcPr=aPr[q:q + a_].copy(),
-                            arcScore=aSc[q:q + a_].copy(), total=float(tot[u]), lmScale=lmScale, wordPen=float(wordPen), prScale=float(prScale)))
-            if align:
-                off = aOff[u * (maxArcs + 1):u * (maxArcs + 1) + a_ + 1].copy(); k = int(off[-1]); b = u * maxAlign
-                res[-1].update(arcAlignOff=off, alState=alS[b:b + k].copy(), alModel=alM[b:b + k].copy(), alDur=alD[b:b + k].copy(), alLike=alL[b:b + k].copy(),
-                               alignModels=bool(align & 1))
-        return res
+            check(lib().htkamd_decoder_run_lattice(self.h, C.byref(cfg), C.c_int(nToks), C.c_float(genBeam if nBeam is None else nBeam), b.dX.ptr, _p(b.frameOff), C.c_int(b.nU),
+                                                   C.c_int(maxNodes), C.c_int(maxArcs), C.byref(b.out), None), "decoder_run_lattice")
+        return b.unpack("decoder_run_lattice", lmScale, wordPen, prScale)
 
     def __del__(self):
         try:
@@ -1688,6 +1711,28 @@ class DecoderSet:
         self.last_lm = [[float(o["wordLm"][u, i]) for i in range(max(int(nW[u]), 0))] for u in range(len(feats))]
         return [((None if nW[u] < 0 else [(int(o["wordPron"][u, i]), int(o["wordStart"][u, i]), int(o["wordEnd"][u, i]), float(o["wordScore"][u, i])) for i in range(nW[u])]),
                  float(o["total"][u])) for u in range(len(feats))]
+
+    def run_lattice(self, feats, net_of, nToks, genBeam=1.0e10, wordBeam=1.0e10, nBeam=None, lmScale=None, wordPen=0.0, prScale=1.0, maxNodes=20000, maxArcs=80000,
+                    scoreMode=0, maxActive=0, align=0, maxAlign=400000):
+        """HVite -n nToks together with -a or a lattice per file: what Decoder.run_lattice returns per utterance, utterance u over
+        nets[net_of[u]] (nodeNet / nodePron index that network) -- htkamd_decoder_set_run_lattice[_align], one launch for the batch."""
+        lmScale = self.lmScale if lmScale is None else float(lmScale)
+        if lmScale != self.lmScale:
+            raise HtkAmdError("DecoderSet.run_lattice: the LM scale is fixed at creation (LikeToWord look-ahead)")
+        if len(net_of) != len(feats):
+            raise HtkAmdError("DecoderSet.run_lattice: %d utterances, %d network indices" % (len(feats), len(net_of)))
+        b = _LatticeRun(feats, self.model.D, maxNodes, maxArcs, align, maxAlign)
+        netOf = np.ascontiguousarray(np.asarray(net_of, np.int64).astype(np.int32) if b.nU else np.zeros(1, np.int32))
+        cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
+        nB = C.c_float(genBeam if nBeam is None else nBeam)
+        if align:
+            check(lib().htkamd_decoder_set_run_lattice_align(self.h, C.byref(cfg), C.c_int(nToks), nB, C.c_int(int(align)), b.dX.ptr, _p(b.frameOff), _p(netOf), C.c_int(b.nU),
+                                                             C.c_int(maxNodes), C.c_int(maxArcs), C.c_int(maxAlign), C.byref(b.out), C.byref(b.alo), None),
+                  "decoder_set_run_lattice_align")
+        else:
+            check(lib().htkamd_decoder_set_run_lattice(self.h, C.byref(cfg), C.c_int(nToks), nB, b.dX.ptr, _p(b.frameOff), _p(netOf), C.c_int(b.nU), C.c_int(maxNodes),
+                                                       C.c_int(maxArcs), C.byref(b.out), None), "decoder_set_run_lattice")
+        return b.unpack("decoder_set_run_lattice", lmScale, wordPen, prScale)
 
     def __del__(self):
         try:

@@ -10,6 +10,7 @@
 #define DEC_THREADS 1024
 #define DEC_MAXN 8              /* states per model incl. entry/exit */
 #define DEC_SET_THREADS 256     /* workgroup of the kernel that takes a network per utterance (alignment networks: tens to hundreds of nodes) */
+#define DEC_MAX_TOKS 8          /* capacity of a token set (HVite -n up to 8; decode_n.hip) */
 #define DEC_WIDE 96             /* fan-in from which a node is reduced by the whole workgroup */
 
 struct DecNet {
@@ -197,6 +198,29 @@ struct DecRun {
 };
 int htkamd_decoder_run_1best(const DecRun &r, const htkamd_decode_config *cfg, const float *dX, const int *frameOff, int nUtt, int maxWords,
                              const htkamd_decode_out *out, hipStream_t s);
+
+// An N-best run (htkamd_decoder_run_lattice[_align], htkamd_decoder_set_run_lattice[_align]; decode_n.hip): the batch in chunks under
+// DEC_CHUNK_BYTES, each scored, decoded to token sets and lattices by ONE launch (`launch`: the list kernel k_decode_ord_n, or the
+// static order k_decode_n with listOrder false) and copied into the caller's arrays.  What the two callers differ in:
+struct NArgs;                                          // the token-set kernels' arguments (decode_n.hip)
+struct DecNRun {
+   const char *who;                                    // the name errors start with (who + "_align" where the alignment records are concerned)
+   DecArena *ws;
+   const htkamd_model *m; const int *dUsedStates;      // the scorer's slot table ...
+   int maxNs;                                          // ... and the most rows a network takes of it (0: one network)
+   std::function<DecUttNet(int)> netOf;                // what utterance u decodes against
+   const DecNet *nets; const int *ns;                  // host side, by DecUttNet::net: the record with its device pointers, the tied states
+   const DecNet *dNets;                                // NArgs::nets; NULL: one network, handed over in NArgs::net / ns (DecUtt::ns = 0)
+   const std::vector<int> *hostModel;                  // by DecUttNet::net: [nNodes] htkamd_net_desc.model, for nodePron / alModel
+   std::function<int(const NArgs &, int, bool, hipStream_t)> launch;
+   int orderMode;                                      // the list kernel unless HTKAMD_ORDER_FAST
+   int *lastTied;                                      // utterances that went through the list kernel
+};
+int htkamd_launch_decode_n(const NArgs &a, int nUtt, bool listOrder, hipStream_t s);          // k_decode_ord_n<false> / k_decode_n<DEC_THREADS, false>
+int htkamd_launch_decode_n_set(const NArgs &a, int nUtt, bool listOrder, hipStream_t s);      // k_decode_ord_n<true> / k_decode_n<DEC_SET_THREADS, true>
+// alignMode 0: no alignment records (maxAlign and alOut are not read)
+int htkamd_decoder_run_nbest(const DecNRun &r, const htkamd_decode_config *cfg, int nToks, float nBeam, const float *dX, const int *frameOff, int nUtt, int maxLatNodes,
+                             int maxLatArcs, const htkamd_lattice_out *out, int alignMode, int maxAlign, const htkamd_lattice_align_out *alOut, hipStream_t s);
 
 struct htkamd_decoder {
    htkamd_model *m;

@@ -30,7 +30,7 @@
 #include "decode.h"
 #include "decode_ord.h"
 
-#define NT 8                        /* capacity of a token set (HVite -n up to 8) */
+#define NT DEC_MAX_TOKS             /* capacity of a token set (HVite -n up to 8) */
 
 struct __attribute__((aligned(16))) TSet {
    double like; float lm; int path;    // the best token
@@ -67,6 +67,7 @@ struct NArgs {
    double *nodeLike;
    int *arcStart, *arcEnd; float *arcAc, *arcLm, *arcPr; double *arcScore;     // [nUtt*maxLatArcs]
    double *total;
+   const DecNet *nets;                 // k_decode_n / k_decode_ord_n<SET>: a network per utterance, nets[DecUtt::net], and DecUtt::ns rows (net and ns above are then not read)
 };
 
 // (StepWord1 / a token under the beam: the best token goes, the relative tokens stay as they are)
@@ -353,17 +354,23 @@ __device__ __forceinline__ void set_step1(const NArgs &a, const DecUtt &ud, cons
    exS = res;
 }
 
-__global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
+// NTHR: the workgroup (DEC_THREADS for one wide recognition network; DEC_SET_THREADS for a network per utterance: alignment and rescoring
+// networks of tens to hundreds of nodes, whose NTHR partial sets are 30 KB of LDS, not 120, so that several utterances share a CU).
+// SET: the utterance's network and the rows of its score columns come from its descriptor, as in k_decode (decode.hip)
+template <int NTHR, bool SET>
+__global__ __launch_bounds__(NTHR) void k_decode_n(NArgs a)
 {
-   __shared__ double red[DEC_THREADS / 64];
-   __shared__ double red2[DEC_THREADS / 64];
+   __shared__ double red[NTHR / 64];
+   __shared__ double red2[NTHR / 64];
    __shared__ float thr[3];
    __shared__ unsigned int usel[3]; __shared__ int uhist[256];
-   extern __shared__ unsigned char dynLds[];           // partial sets of a wide node: DEC_THREADS x PSet
+   extern __shared__ unsigned char dynLds[];           // partial sets of a wide node: NTHR x PSet
    PSet *part = (PSet *)dynLds;
    const int u = blockIdx.x, tid = threadIdx.x;
    if (u >= a.nUtt) return;
    const DecUtt ud = a.utt[u];
+   // (the record is uniform over the workgroup and read before the kernel's first store, as in k_decode)
+   if constexpr (SET) { a.net = a.nets[ud.net]; a.ns = ud.ns; }
    const DecNet &N = a.net;
    const int T = ud.T, nW = N.nWordNodes;
    TSet *cur = a.tokA + ud.tok0, *nxt = a.tokB + ud.tok0, *ex = a.ex + ud.node0;
@@ -371,9 +378,9 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
    const float *tpBase = N.transP;
 
    { TSet z; ts_null(z);
-     for (int i = tid; i < N.nTok; i += DEC_THREADS) { cur[i] = z; nxt[i] = z; }
-     for (int i = tid; i < N.nNodes; i += DEC_THREADS) { ex[i] = z; imax[i] = LZERO; } }
-   for (size_t i = tid; i < (size_t)(T + 1) * nW; i += DEC_THREADS) a.mark[ud.path0 + i] = 0;
+     for (int i = tid; i < N.nTok; i += NTHR) { cur[i] = z; nxt[i] = z; }
+     for (int i = tid; i < N.nNodes; i += NTHR) { ex[i] = z; imax[i] = LZERO; } }
+   for (size_t i = tid; i < (size_t)(T + 1) * nW; i += NTHR) a.mark[ud.path0 + i] = 0;
    if (tid == 0) { thr[0] = (float)LSMALL; thr[1] = (float)LSMALL; thr[2] = (float)LSMALL; }
    __syncthreads();
 
@@ -382,10 +389,10 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
          // ---- maximum-model pruning (ProcessObservation HRec.c:1966-1985; dec_prune_threshold, decode_dev.h): when more than maxActive
          // instances are attached, those whose max (a float) lies below the (maxActive+1)-th largest lose every token set before pass 1
          const float gTp = thr[0];
-         const float uth = dec_prune_threshold<DEC_THREADS>(N.nNodes, a.maxActive, usel, uhist,
+         const float uth = dec_prune_threshold<NTHR>(N.nNodes, a.maxActive, usel, uhist,
                                                             [&](const int n, float &key) { const double v = imax[n]; key = (float)v; return v >= gTp && v > LSMALL; });
          if (uth > (float)LSMALL)
-            for (int n = tid; n < N.nNodes; n += DEC_THREADS) {
+            for (int n = tid; n < N.nNodes; n += NTHR) {
                const double v = imax[n];
                if (!(v >= gTp && v > LSMALL) || !(v < (double)uth)) continue;
                TSet z; ts_null(z);
@@ -399,7 +406,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
       if (t >= 1) {
          const float gT = thr[0], nT = thr[2];             // thresholds of the previous frame
          double myGen = LZERO, myWord = LZERO;
-         for (int hk = tid; hk < N.nHmm; hk += DEC_THREADS) {
+         for (int hk = tid; hk < N.nHmm; hk += NTHR) {
             const int n = N.hmmNodes[hk];
             const int4 ni = N.nodeInfo[n];
             const int NS = (ni.x >> 4) & 255, t0 = ni.y;
@@ -420,8 +427,8 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
             }
             ex[n] = exS; imax[n] = (double)(float)mx;
          }
-         const double genMax = dec_block_max<DEC_THREADS>(myGen, red);
-         const double wordMax = dec_block_max<DEC_THREADS>(myWord, red2);
+         const double genMax = dec_block_max<NTHR>(myGen, red);
+         const double wordMax = dec_block_max<NTHR>(myWord, red2);
          if (tid == 0) {
             float w = (float)(wordMax - a.wordBeam); if (w < (float)LSMALL) w = (float)LSMALL;
             float g = (float)(genMax - a.genBeam); if (g < (float)LSMALL) g = (float)LSMALL;
@@ -434,7 +441,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
       const float gT = thr[0], wT = thr[1], nT = thr[2];
       for (int L = 0; L < N.nLevels; L++) {
          const int l0 = N.levelOffAll[L], lw = N.levelWideAll[L], l1 = N.levelOffAll[L + 1];
-         for (int k = l0 + tid; k < lw; k += DEC_THREADS) {
+         for (int k = l0 + tid; k < lw; k += NTHR) {
             const int n = N.levelNodesAll[k];
             const int4 ni = N.nodeInfo[n];
             const int kind = ni.x & 15;
@@ -463,7 +470,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
          for (int k = lw; k < l1; k++) {                   // wide fan-in: contiguous runs per thread, then thread 0 in run order
             const int n = N.levelNodesAll[k];
             const int p0 = N.predOff[n], p1 = N.predOff[n + 1];
-            const int per = (p1 - p0 + DEC_THREADS - 1) / DEC_THREADS;
+            const int per = (p1 - p0 + NTHR - 1) / NTHR;
             TSet mine; ts_null(mine);
             const int b0 = p0 + tid * per, b1 = (b0 + per < p1) ? b0 + per : p1;
             if (b0 < p1) pull_sets(a, ex, b0, b1, gT, wT, nT, mine);
@@ -475,7 +482,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
             __syncthreads();
             if (tid == 0) {
                TSet st; ts_null(st);
-               for (int q = 0; q < DEC_THREADS; q++) {
+               for (int q = 0; q < NTHR; q++) {
                   if (!(part[q].like > LSMALL)) continue;
                   TSet pq; ts_null(pq);
                   pq.like = part[q].like; pq.lm = part[q].lm; pq.path = part[q].path; pq.n = part[q].n;
@@ -496,7 +503,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_decode_n(NArgs a)
          __syncthreads();
       }
       if (t < T) {
-         for (int hk = tid; hk < N.nHmm; hk += DEC_THREADS) {
+         for (int hk = tid; hk < N.nHmm; hk += NTHR) {
             const int n = N.hmmNodes[hk];
             const int4 ni = N.nodeInfo[n];
             if ((ni.x >> 12) & 1) continue;
@@ -539,6 +546,7 @@ __device__ void word_exit_ord(const NArgs &a, const DecUtt &ud, int n, int t, co
    e.n = 1; e.rp[0] = e.path;                            // rl[0] / rlm[0] / ra[0] stay what the exit set held (AttachInst's rmax: 0, 0, NULL)
 }
 
+template <bool SET>      // SET: a network per utterance, as in k_decode_n
 __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
 {
    __shared__ double red[ORD_THREADS / 64];
@@ -550,6 +558,7 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
    const int sel = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
    if (sel >= a.nUtt) return;
    const DecUtt ud = a.utt[sel];
+   if constexpr (SET) { a.net = a.nets[ud.net]; a.ns = ud.ns; }
    const DecNet &N = a.net;
    const int T = ud.T, u = ud.idx;
    TSet *cur = a.tokA + ud.tok0, *nxt = a.tokB + ud.tok0, *ex = a.ex + ud.node0;
@@ -757,55 +766,79 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
 }
 
 // ------------------------------------------------------------------------------------ host side
-static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, int nToks, float nBeam, const float *dX, const int *frameOff, int nUtt,
-                            int maxLatNodes, int maxLatArcs, const htkamd_lattice_out *out, int alignMode, int maxAlign, const htkamd_lattice_align_out *alOut, void *stream);
+// The launches.  One network (htkamd_decoder): k_decode_ord_n<false> / k_decode_n<DEC_THREADS, false>, the network in NArgs::net.  A network
+// per utterance (htkamd_decoder_set): ONE launch of the SET forms serves every network of the chunk -- in alignment every utterance has a
+// network of its own, and a launch per network would be a launch per utterance.
+template <int NTHR, bool SET>
+static int launch_n(const NArgs &a, int nUtt, bool listOrder, const char *who, hipStream_t s)
+{
+   hipError_t e = hipSuccess;
+   if (listOrder) { hipLaunchKernelGGL((k_decode_ord_n<SET>), dim3(nUtt), dim3(ORD_THREADS), 0, s, a); e = hipGetLastError(); }
+   else {
+      const size_t lds = sizeof(PSet) * NTHR;
+      e = hipFuncSetAttribute((const void *)k_decode_n<NTHR, SET>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e == hipSuccess) { hipLaunchKernelGGL((k_decode_n<NTHR, SET>), dim3(nUtt), dim3(NTHR), lds, s, a); e = hipGetLastError(); }
+   }
+   if (e != hipSuccess) { htkamd_set_error("%s: launch: %s", who, hipGetErrorString(e)); return HTKAMD_EHIP; }
+   return HTKAMD_OK;
+}
+int htkamd_launch_decode_n(const NArgs &a, int nUtt, bool listOrder, hipStream_t s) { return launch_n<DEC_THREADS, false>(a, nUtt, listOrder, "decoder_run_lattice", s); }
+int htkamd_launch_decode_n_set(const NArgs &a, int nUtt, bool listOrder, hipStream_t s) { return launch_n<DEC_SET_THREADS, true>(a, nUtt, listOrder, "decoder_set_run_lattice", s); }
 
 extern "C" int htkamd_decoder_run_lattice(htkamd_decoder *d, const htkamd_decode_config *cfg, int nToks, float nBeam, const float *dX, const int *frameOff, int nUtt,
                                           int maxLatNodes, int maxLatArcs, const htkamd_lattice_out *out, void *stream)
 {
-   return run_lattice_impl(d, cfg, nToks, nBeam, dX, frameOff, nUtt, maxLatNodes, maxLatArcs, out, 0, 0, nullptr, stream);
+   return htkamd_decoder_run_lattice_align(d, cfg, nToks, nBeam, 0, dX, frameOff, nUtt, maxLatNodes, maxLatArcs, 0, out, nullptr, stream);
 }
 
 extern "C" int htkamd_decoder_run_lattice_align(htkamd_decoder *d, const htkamd_decode_config *cfg, int nToks, float nBeam, int alignMode, const float *dX, const int *frameOff,
                                                 int nUtt, int maxLatNodes, int maxLatArcs, int maxAlign, const htkamd_lattice_out *out, const htkamd_lattice_align_out *alOut,
                                                 void *stream)
 {
-   if (alignMode < 0 || alignMode > 3 || (alignMode && (maxAlign < 1 || !alOut || !alOut->arcAlignOff || !alOut->alState || !alOut->alModel || !alOut->alDur || !alOut->alLike))) {
-      htkamd_set_error("decoder_run_lattice_align: bad argument"); return HTKAMD_EINVAL;
-   }
-   return run_lattice_impl(d, cfg, nToks, nBeam, dX, frameOff, nUtt, maxLatNodes, maxLatArcs, out, alignMode, maxAlign, alOut, stream);
+   if (!d || !frameOff) { htkamd_set_error("decoder_run_lattice: bad argument"); return HTKAMD_EINVAL; }
+   const int ns = (int)d->usedStates.size();
+   const DecUttNet one = {&d->net, 0, ns, 0};
+   const DecNRun r = {"decoder_run_lattice", &d->wsN, d->m, d->d_usedStates, 0, [&](int) { return one; }, &d->net, &ns, nullptr, &d->hostModel, htkamd_launch_decode_n,
+                      htkamd_decoder_order(d->orderMode), &d->lastTied};
+   return htkamd_decoder_run_nbest(r, cfg, nToks, nBeam, dX, frameOff, nUtt, maxLatNodes, maxLatArcs, out, alignMode, maxAlign, alOut, (hipStream_t)stream);
 }
 
-static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, int nToks, float nBeam, const float *dX, const int *frameOff, int nUtt,
-                            int maxLatNodes, int maxLatArcs, const htkamd_lattice_out *out, int alignMode, int maxAlign, const htkamd_lattice_align_out *alOut, void *stream)
+int htkamd_decoder_run_nbest(const DecNRun &r, const htkamd_decode_config *cfg, int nToks, float nBeam, const float *dX, const int *frameOff, int nUtt, int maxLatNodes,
+                             int maxLatArcs, const htkamd_lattice_out *out, int alignMode, int maxAlign, const htkamd_lattice_align_out *alOut, hipStream_t s)
 {
-   if (!d || !cfg || !frameOff || nUtt < 0 || !out || !out->nNodes || !out->nArcs || maxLatNodes < 2 || maxLatArcs < 1) { htkamd_set_error("decoder_run_lattice: bad argument"); return HTKAMD_EINVAL; }
-   if (nToks < 2 || nToks > NT) { htkamd_set_error("decoder_run_lattice: nToks = %d (2..%d tokens per state)", nToks, NT); return HTKAMD_EINVAL; }
+   if (!cfg || nUtt < 0 || !out || !out->nNodes || !out->nArcs || maxLatNodes < 2 || maxLatArcs < 1) { htkamd_set_error("%s: bad argument", r.who); return HTKAMD_EINVAL; }
+   if (alignMode < 0 || alignMode > 3 || (alignMode && (maxAlign < 1 || !alOut || !alOut->arcAlignOff || !alOut->alState || !alOut->alModel || !alOut->alDur || !alOut->alLike))) {
+      htkamd_set_error("%s_align: bad argument", r.who); return HTKAMD_EINVAL;
+   }
+   if (nToks < 2 || nToks > NT) { htkamd_set_error("%s: nToks = %d (2..%d tokens per state)", r.who, nToks, NT); return HTKAMD_EINVAL; }
    if (nUtt == 0) return HTKAMD_OK;
-   hipStream_t s = (hipStream_t)stream;
-   const DecNet &N = d->net;
-   const int ns = (int)d->usedStates.size();
-   const int FR = SCORE_TILE_FRAMES, SL = SCORE_TASK_SLOTS;
    // the list kernel (k_decode_ord_n) unless the static order was asked for: in N-best mode the order of the merges is in every
    // alternative's likelihood, so "exact" is the default here, not a fallback
-   const int orderMode = htkamd_decoder_order(d->orderMode);
-   if (alignMode && orderMode == HTKAMD_ORDER_FAST) { htkamd_set_error("decoder_run_lattice_align: alignment records need the list kernel (not HTKAMD_ORDER_FAST)"); return HTKAMD_EINVAL; }
-   const bool listOrder = orderMode != HTKAMD_ORDER_FAST;
+   if (alignMode && r.orderMode == HTKAMD_ORDER_FAST) { htkamd_set_error("%s_align: alignment records need the list kernel (not HTKAMD_ORDER_FAST)", r.who); return HTKAMD_EINVAL; }
+   *r.lastTied = 0;
+   const bool one = !r.dNets;
+   const int FR = SCORE_TILE_FRAMES, SL = SCORE_TASK_SLOTS;
+   const bool listOrder = r.orderMode != HTKAMD_ORDER_FAST;
    const size_t pathMul = listOrder ? DEC_ORD_PATH_MUL : 1, pathExtra = listOrder ? DEC_ORD_PATH_EXTRA : 0;
-   const int seqCap = htkamd_dec_ord_seq_cap(N.nNodes);
-   d->lastTied = 0;
-   DecArena &ws = d->wsN;
+   DecArena &ws = *r.ws;
    enum { WS_LIST = 32, WS_ALIGN = 40 };      // first slots of the list kernel's buffers and of the alignment records
    DecBatch bt;
    int u0 = 0;
    while (u0 < nUtt) {
-      htkamd_decoder_plan(N, frameOff, u0, nUtt, ns, FR, SL,
-                          [&](size_t T) { return (size_t)ns * T * 8 + (size_t)N.nTok * 2 * sizeof(TSet) + (size_t)N.nNodes * (sizeof(TSet) + 8) +
-                                                 htkamd_dec_path_records(pathMul, T, N.nWordNodes, pathExtra) * (24 + 16 * (NT - 1) + 8) + (listOrder ? (size_t)seqCap * 8 : 0); },
-                          0, pathMul, pathExtra, bt);
+      htkamd_decoder_plan_nets(r.netOf, frameOff, u0, nUtt, FR, SL,
+                               [&](size_t T, const DecUttNet &un) {
+                                  const DecNet &N = *un.N;
+                                  return (size_t)un.ns * T * 8 + (size_t)N.nTok * 2 * sizeof(TSet) + (size_t)N.nNodes * (sizeof(TSet) + 8) +
+                                         htkamd_dec_path_records(pathMul, T, N.nWordNodes, pathExtra) * (24 + 16 * (NT - 1) + 8) +
+                                         (listOrder ? (size_t)htkamd_dec_ord_seq_cap(N.nNodes) * 8 : 0); },
+                               0, pathMul, pathExtra, bt);
+      if (one) for (DecUtt &ud : bt.utt) ud.ns = 0;      // (the kernels take the network and its rows from their arguments)
       const int u1 = bt.u1, nu = u1 - u0, maxT = bt.maxT;
       const size_t score = bt.score, tok = bt.tok, node = bt.node, path = bt.path;
-      ws.begin(s, "decoder_run_lattice");
+      // what the chunk's kernels size alike for every utterance: the largest of its networks' (no utterance gets less than the single decoder gives its network)
+      int seqCap = 0, maxHmm = 0;
+      for (const DecUtt &ud : bt.utt) { seqCap = std::max(seqCap, htkamd_dec_ord_seq_cap(r.nets[ud.net].nNodes)); maxHmm = std::max(maxHmm, r.nets[ud.net].nHmm); }
+      ws.begin(s, r.who);
       NArgs a; memset(&a, 0, sizeof(a));
       void *dScore = ws.get(score * 4), *dScoreT = ws.get(score * 4);
       a.tokA = (TSet *)ws.get(tok * sizeof(TSet)); a.tokB = (TSet *)ws.get(tok * sizeof(TSet)); a.ex = (TSet *)ws.get(node * sizeof(TSet)); a.imax = (double *)ws.get(node * 8);
@@ -827,7 +860,7 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
          ws.seek(WS_ALIGN);
          // Align records: one per token of a set where it enters a state (-f) and where it leaves a model (-m), never freed within an
          // utterance (the reference collects garbage; here the utterance must fit): frames x model nodes x tokens x (states + 1), capped
-         size_t cap = (size_t)(maxT + 1) * (size_t)N.nHmm * (size_t)nToks * (size_t)((alignMode & 2 ? 3 : 0) + (alignMode & 1 ? 1 : 0));
+         size_t cap = (size_t)(maxT + 1) * (size_t)maxHmm * (size_t)nToks * (size_t)((alignMode & 2 ? 3 : 0) + (alignMode & 1 ? 1 : 0));
          if (cap > ((size_t)1 << 27)) cap = (size_t)1 << 27;
          if (cap * (size_t)nu * sizeof(AlignRec) > ((size_t)16 << 30)) cap = ((size_t)16 << 30) / ((size_t)nu * sizeof(AlignRec));
          a.alignMode = alignMode; a.alCap = (int)cap; a.al = (AlignRec *)ws.get(sizeof(AlignRec) * cap * nu); a.alCount = (int *)ws.get(sizeof(int) * nu);
@@ -837,19 +870,15 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
          a.alLike = (float *)ws.get(sizeof(float) * (size_t)nu * maxAlign);
       }
       int rc = ws.rc;
-      if (!rc) rc = htkamd_decoder_score(d, cfg->scoreMode, dX, frameOff[u1], bt, ns, dUtt, dTasks, (float *)dScore, (float *)dScoreT, nullptr, "decoder_run_lattice", s);
+      if (!rc) rc = htkamd_decoder_score_slots(r.m, r.dUsedStates, cfg->scoreMode, dX, frameOff[u1], bt, one ? r.ns[0] : 0, r.maxNs, dUtt, dTasks, (float *)dScore, (float *)dScoreT,
+                                               nullptr, r.who, s);
       if (!rc) {
-         a.net = N; a.utt = (const DecUtt *)dUtt; a.nUtt = nu; a.score = (const float *)dScoreT; a.ns = ns;
+         if (one) { a.net = r.nets[0]; a.ns = r.ns[0]; } else a.nets = r.dNets;
+         a.utt = (const DecUtt *)dUtt; a.nUtt = nu; a.score = (const float *)dScoreT;
          a.genBeam = cfg->genBeam; a.wordBeam = cfg->wordBeam; a.nBeam = nBeam; a.lmScale = cfg->lmScale; a.wordPen = cfg->wordPen; a.prScale = cfg->prScale;
          a.nToks = nToks; a.maxActive = cfg->maxActive > 0 ? cfg->maxActive : 0; a.maxLatNodes = maxLatNodes; a.maxLatArcs = maxLatArcs;
-         const size_t lds = sizeof(PSet) * DEC_THREADS;
-         hipError_t e = hipSuccess;
-         if (listOrder) { hipLaunchKernelGGL(k_decode_ord_n, dim3(nu), dim3(ORD_THREADS), 0, s, a); e = hipGetLastError(); d->lastTied += nu; }
-         else {
-            e = hipFuncSetAttribute((const void *)k_decode_n, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e == hipSuccess) { hipLaunchKernelGGL(k_decode_n, dim3(nu), dim3(DEC_THREADS), lds, s, a); e = hipGetLastError(); }
-         }
-         if (e != hipSuccess) { htkamd_set_error("decoder_run_lattice: launch: %s", hipGetErrorString(e)); rc = HTKAMD_EHIP; }
+         rc = r.launch(a, nu, listOrder, s);
+         if (!rc && listOrder) *r.lastTied += nu;
       }
       std::vector<int> hN(2 * nu), hNF, hNN, hAS, hAE; std::vector<double> hNL, hSc, hT(nu); std::vector<float> hAc, hLm, hPr;
       if (!rc) {
@@ -859,7 +888,7 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
 #define D2H(h, dptr) ((e = hipMemcpyAsync((h).data(), (dptr), sizeof((h)[0]) * (h).size(), hipMemcpyDeviceToHost, s)) != hipSuccess)
          if (D2H(hN, a.latN) || D2H(hNF, a.nodeFrame) || D2H(hNN, a.nodeNet) || D2H(hNL, a.nodeLike) || D2H(hAS, a.arcStart) || D2H(hAE, a.arcEnd) ||
              D2H(hAc, a.arcAc) || D2H(hLm, a.arcLm) || D2H(hPr, a.arcPr) || D2H(hSc, a.arcScore) || D2H(hT, a.total) ||
-             (e = hipStreamSynchronize(s)) != hipSuccess) { htkamd_set_error("decoder_run_lattice: %s", hipGetErrorString(e)); rc = HTKAMD_EHIP; }
+             (e = hipStreamSynchronize(s)) != hipSuccess) { htkamd_set_error("%s: %s", r.who, hipGetErrorString(e)); rc = HTKAMD_EHIP; }
 #undef D2H
       } else (void)hipStreamSynchronize(s);
       if (rc) return rc;
@@ -870,20 +899,22 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
              (e = hipMemcpy(hSt.data(), a.alState, sizeof(int) * hSt.size(), hipMemcpyDeviceToHost)) != hipSuccess ||
              (e = hipMemcpy(hNd.data(), a.alNode, sizeof(int) * hNd.size(), hipMemcpyDeviceToHost)) != hipSuccess ||
              (e = hipMemcpy(hDu.data(), a.alDur, sizeof(int) * hDu.size(), hipMemcpyDeviceToHost)) != hipSuccess ||
-             (e = hipMemcpy(hLk.data(), a.alLike, sizeof(float) * hLk.size(), hipMemcpyDeviceToHost)) != hipSuccess) { htkamd_set_error("decoder_run_lattice_align: %s", hipGetErrorString(e)); return HTKAMD_EHIP; }
+             (e = hipMemcpy(hLk.data(), a.alLike, sizeof(float) * hLk.size(), hipMemcpyDeviceToHost)) != hipSuccess) { htkamd_set_error("%s_align: %s", r.who, hipGetErrorString(e)); return HTKAMD_EHIP; }
          for (int k = 0; k < nu; k++) {
             const int uu = u0 + k;
+            const std::vector<int> &hostModel = r.hostModel[bt.utt[k].net];
             const int na = hN[2 * k] > 0 ? hN[2 * k + 1] : 0;
             for (int i = 0; i <= na; i++) alOut->arcAlignOff[(size_t)uu * (maxLatArcs + 1) + i] = hOff[(size_t)k * (maxLatArcs + 1) + i];
             const int nr = na > 0 ? hOff[(size_t)k * (maxLatArcs + 1) + na] : 0;
             for (int i = 0; i < nr; i++) {
                const size_t o = (size_t)uu * maxAlign + i, si = (size_t)k * maxAlign + i;
-               alOut->alState[o] = hSt[si]; alOut->alModel[o] = d->hostModel[hNd[si]]; alOut->alDur[o] = hDu[si]; alOut->alLike[o] = hLk[si];
+               alOut->alState[o] = hSt[si]; alOut->alModel[o] = hostModel[hNd[si]]; alOut->alDur[o] = hDu[si]; alOut->alLike[o] = hLk[si];
             }
          }
       }
       for (int k = 0; k < nu; k++) {
          const int uu = u0 + k;
+         const std::vector<int> &hostModel = r.hostModel[bt.utt[k].net];      // (nodeNet / nodePron index the utterance's own network)
          out->nNodes[uu] = hN[2 * k]; out->nArcs[uu] = hN[2 * k + 1];
          if (out->total) out->total[uu] = hT[k];
          const int nn = hN[2 * k] > 0 ? hN[2 * k] : 0, na = hN[2 * k] > 0 ? hN[2 * k + 1] : 0;
@@ -891,7 +922,7 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
             const size_t o = (size_t)uu * maxLatNodes + i, si = (size_t)k * maxLatNodes + i;
             if (out->nodeFrame) out->nodeFrame[o] = hNF[si];
             if (out->nodeNet) out->nodeNet[o] = hNN[si];
-            if (out->nodePron) out->nodePron[o] = hNN[si] >= 0 ? d->hostModel[hNN[si]] : -1;
+            if (out->nodePron) out->nodePron[o] = hNN[si] >= 0 ? hostModel[hNN[si]] : -1;
             if (out->nodeLike) out->nodeLike[o] = hNL[si];
          }
          for (int i = 0; i < na; i++) {
@@ -908,3 +939,4 @@ static int run_lattice_impl(htkamd_decoder *d, const htkamd_decode_config *cfg, 
    }
    return HTKAMD_OK;
 }
+

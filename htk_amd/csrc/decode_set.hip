@@ -10,6 +10,8 @@
 // Running.  htkamd_decoder_set_run checks its arguments and hands the single decoder's driver (htkamd_decoder_run_1best, decode.hip) the
 // set's networks, slot table and launch: chunks, work space, the exact-order pass for ties (k_decode_ord takes a network per launch, so the
 // driver groups the chosen utterances by network) and the outputs are that one code for both.
+// N-best.  htkamd_decoder_set_run_lattice[_align] do the same with the N-best driver (htkamd_decoder_run_nbest, decode_n.hip) and the SET
+// forms of the token-set kernels: one launch per chunk whatever the number of networks in it.
 #include <hip/hip_runtime.h>
 #include <cstring>
 #include <vector>
@@ -27,7 +29,8 @@ struct htkamd_decoder_set {
    char *d_tables = nullptr;           // every network's tables
    DecNet *d_nets = nullptr;
    int *d_used = nullptr;
-   DecArena ws;
+   std::vector<std::vector<int>> hostModel;     // per network: [nNodes] htkamd_net_desc.model (WORD nodes: the pronunciation)
+   DecArena ws, wsN;                   // workspaces of htkamd_decoder_set_run and of htkamd_decoder_set_run_lattice, as htkamd_decoder's
    int orderMode = HTKAMD_ORDER_AUTO, lastTied = 0;
 };
 
@@ -38,6 +41,7 @@ extern "C" void htkamd_decoder_set_destroy(htkamd_decoder_set *d)
    if (d->d_nets) (void)hipFree(d->d_nets);
    if (d->d_used) (void)hipFree(d->d_used);
    d->ws.release();
+   d->wsN.release();
    delete d;
 }
 
@@ -47,7 +51,8 @@ extern "C" int htkamd_decoder_set_create(htkamd_model *m, const htkamd_net_desc 
    for (int i = 0; i < nNets; i++) if (!nets[i]) { htkamd_set_error("decoder_set_create: network %d is NULL", i); return HTKAMD_EINVAL; }
    htkamd_decoder_set *d = new htkamd_decoder_set();
    d->m = m;
-   d->nets.resize(nNets); d->ns.resize(nNets); d->usedOff.resize(nNets);
+   d->nets.resize(nNets); d->ns.resize(nNets); d->usedOff.resize(nNets); d->hostModel.resize(nNets);
+   for (int i = 0; i < nNets; i++) d->hostModel[i].assign(nets[i]->model, nets[i]->model + nets[i]->nNodes);
    std::vector<char> host;
    std::vector<const void **> fix;            // pointer fields of d->nets holding offset + 1 into `host`
    const DecPut put = [&](const void *data, size_t bytes, const void **where) -> int {
@@ -105,4 +110,27 @@ extern "C" int htkamd_decoder_set_run(htkamd_decoder_set *d, const htkamd_decode
    const DecRun r = {"decoder_set_run", &d->ws, d->m, d->d_used, d->maxNs, uttNet, d->nets.data(), d->ns.data(), d->d_nets, htkamd_launch_decode_set,
                      htkamd_decoder_order(d->orderMode), &d->lastTied, nullptr, nullptr, nullptr, nullptr};
    return htkamd_decoder_run_1best(r, cfg, dX, frameOff, nUtt, maxWords, out, (hipStream_t)stream);
+}
+
+// HVite -n i [N] [-z ext] with a network per utterance: the token sets and the lattice of utterance u over nets[netOf[u]]
+extern "C" int htkamd_decoder_set_run_lattice(htkamd_decoder_set *d, const htkamd_decode_config *cfg, int nToks, float nBeam, const float *dX, const int *frameOff,
+                                              const int *netOf, int nUtt, int maxLatNodes, int maxLatArcs, const htkamd_lattice_out *out, void *stream)
+{
+   return htkamd_decoder_set_run_lattice_align(d, cfg, nToks, nBeam, 0, dX, frameOff, netOf, nUtt, maxLatNodes, maxLatArcs, 0, out, nullptr, stream);
+}
+
+extern "C" int htkamd_decoder_set_run_lattice_align(htkamd_decoder_set *d, const htkamd_decode_config *cfg, int nToks, float nBeam, int alignMode, const float *dX,
+                                                    const int *frameOff, const int *netOf, int nUtt, int maxLatNodes, int maxLatArcs, int maxAlign,
+                                                    const htkamd_lattice_out *out, const htkamd_lattice_align_out *alOut, void *stream)
+{
+   // (what needs no set is checked first: a set cannot be made without a device)
+   if (nToks < 2 || nToks > DEC_MAX_TOKS) { htkamd_set_error("decoder_set_run_lattice: nToks = %d (2..%d tokens per state)", nToks, DEC_MAX_TOKS); return HTKAMD_EINVAL; }
+   if (!d || nUtt < 0 || (nUtt > 0 && (!frameOff || !netOf))) { htkamd_set_error("decoder_set_run_lattice: bad argument"); return HTKAMD_EINVAL; }
+   const int nNets = (int)d->nets.size();
+   for (int u = 0; u < nUtt; u++)
+      if (netOf[u] < 0 || netOf[u] >= nNets) { htkamd_set_error("decoder_set_run_lattice: utterance %d names network %d of %d", u, netOf[u], nNets); return HTKAMD_EINVAL; }
+   const auto uttNet = [&](int u) { const int g = netOf[u]; return DecUttNet{&d->nets[g], g, d->ns[g], d->usedOff[g]}; };
+   const DecNRun r = {"decoder_set_run_lattice", &d->wsN, d->m, d->d_used, d->maxNs, uttNet, d->nets.data(), d->ns.data(), d->d_nets, d->hostModel.data(),
+                      htkamd_launch_decode_n_set, htkamd_decoder_order(d->orderMode), &d->lastTied};
+   return htkamd_decoder_run_nbest(r, cfg, nToks, nBeam, dX, frameOff, nUtt, maxLatNodes, maxLatArcs, out, alignMode, maxAlign, alOut, (hipStream_t)stream);
 }

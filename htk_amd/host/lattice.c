@@ -99,7 +99,9 @@ int htkamd_lattice_write_align(const htkamd_lattice *lat, const htkamd_lattice_a
       const int a = order[i];
       fprintf(f, "J=%-5d S=%-4d E=%-4d ", i, rorder[lat->arcStart[a]], rorder[lat->arcEnd[a]]);
       if (format & HTKAMD_LAT_ACLIKE) fprintf(f, "a=%-9.2f ", lat->arcAc[a]);
-      if (format & HTKAMD_LAT_LMLIKE) fprintf(f, "l=%-7.3f ", lat->arcLm[a]);
+      /* a lattice without an lmname (made in DoAlignment) has its scale and penalty inside l= (HNet.c:609-615) */
+      if ((format & HTKAMD_LAT_LMLIKE) && !lmName) { const float tl = lat->arcLm[a] * lat->lmScale; fprintf(f, "l=%-8.2f ", (float)(tl + lat->wordPen)); }
+      else if (format & HTKAMD_LAT_LMLIKE) fprintf(f, "l=%-7.3f ", lat->arcLm[a]);
       if (format & HTKAMD_LAT_PRLIKE) fprintf(f, "r=%-6.2f ", lat->arcPr[a]);
       if (al && (format & HTKAMD_LAT_ALIGN) && al->arcAlignOff[a + 1] > al->arcAlignOff[a]) {      /* OutputAlign (HNet.c:503-516) */
          fprintf(f, "d=:");

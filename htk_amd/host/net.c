@@ -402,11 +402,9 @@ static int expand_lattice(lnode *ln, int NN, larc *la, int NA, dpron *pr, int nP
       for (int i = 0; i < NN && !rc; i++) {
          firstOf[i] = nInst; cntOf[i] = 0;
          const int isNull = !strcmp(ln[i].word, "!NULL");
-         int sel[256], nSel = 0, found = 0;
+         int sel[256], nSel = 0;
          for (int k = 0; k < nPr && !isNull; k++) {
             if (strcmp(pr[k].word, ln[i].word)) continue;
-            found++;
-            if (ln[i].var > 0 && found != ln[i].var) continue;
             int dup = 0;
             for (int z = 0; z < nSel && !dup; z++) {
                const dpron *o = &pr[sel[z]];
@@ -726,11 +724,10 @@ static int expand_lattice(lnode *ln, int NN, larc *la, int NA, dpron *pr, int nP
       /* pronunciations of the word, in the order of the reference's PronHolder list: InitPronHolders (HNet.c:2293) drops a
          pronunciation that repeats an earlier one (same phones, same probability: remDupPron) and PREPENDS each holder, so the list --
          and with it the order of every link made per holder -- runs from the last pronunciation of the dictionary to the first */
-      int sel[256], nSel = 0, found = 0;
+      int sel[256], nSel = 0;
       for (int k = 0; k < nPr && !isNull; k++) {
          if (strcmp(pr[k].word, ln[i].word)) continue;
-         found++;
-         if (ln[i].var > 0 && found != ln[i].var) continue;     /* v= selects one pronunciation */
+         /* (a node's v= is read and not used: InitPronHolders gives every node every pronunciation of its word) */
          int dup = 0;
          for (int z = 0; z < nSel && !dup; z++) {
             const dpron *o = &pr[sel[z]];

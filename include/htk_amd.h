@@ -794,7 +794,9 @@ typedef struct {
    double frameDur;                     /* seconds per frame */
 } htkamd_lattice;
 /* WriteLattice (HNet.c:631): the SLF text file, byte for byte the reference's for the supported fields.  format = HVite -q letters as
- * bits; 0 = HTKAMD_LAT_DEFAULT (t v a l).  utterance / lmName / vocabName: header lines (NULL = left out). */
+ * bits; 0 = HTKAMD_LAT_DEFAULT (t v a l).  utterance / lmName / vocabName: header lines (NULL = left out).  Without an lmName -- a lattice
+ * made in DoAlignment, a network per file -- the lmscale / wdpenalty line is left out too and l= holds lmlike * lmScale + wordPen to two
+ * decimals, as WriteLattice writes a lattice that has no network (HNet.c:609-615). */
 #define HTKAMD_LAT_ALABS  0x0001
 #define HTKAMD_LAT_LBIN   0x0002
 #define HTKAMD_LAT_TIMES  0x0008
@@ -876,14 +878,25 @@ int  htkamd_decoder_run_out(htkamd_decoder *d, const htkamd_decode_config *cfg, 
  * tee models with at most 95 predecessors: the same messages from htkamd_decoder_set_create).  cfg->maxActive (HVite -u) is carried
  * through.  A netOf[u] out of range is refused before anything is launched.  Exact ties go through the list kernel as in the single
  * decoder (htkamd_decoder_set_order's modes; HTKAMD_DECODE_ORDER overrides), a launch per network that has such utterances.
- * N-best and lattice output (htkamd_decoder_run_lattice*) exist for the single decoder only.  The descriptors may be freed after
- * htkamd_decoder_set_create. */
+ * The descriptors may be freed after htkamd_decoder_set_create.
+ * N-best token sets and lattices (HVite -n i [N] [-z ext] together with -a or a lattice per file): htkamd_decoder_set_run_lattice and
+ * _align are htkamd_decoder_run_lattice and _align with utterance u over nets[netOf[u]] -- the same arguments, outputs and status codes
+ * (nNodes[u] = -1: no token reached the final node; a lattice that does not fit: the single decoder's code), every number that of a
+ * decoder created for nets[netOf[u]] alone, bit for bit in list order; nodeNet / nodePron index THAT network.  One launch per chunk serves
+ * every network in it.  Order modes: the list kernel unless HTKAMD_ORDER_FAST, which _align refuses; htkamd_decoder_set_last_tied
+ * counts the utterances that went through the list kernel.  nToks outside 2..8 and a netOf[u] out of range are HTKAMD_EINVAL before a
+ * device is needed; nUtt = 0 is HTKAMD_OK. */
 typedef struct htkamd_decoder_set htkamd_decoder_set;
 int  htkamd_decoder_set_create(htkamd_model *m, const htkamd_net_desc *const *nets, int nNets, float lmScale, htkamd_decoder_set **out);
 void htkamd_decoder_set_destroy(htkamd_decoder_set *d);
 int  htkamd_decoder_set_run(htkamd_decoder_set *d, const htkamd_decode_config *cfg, const float *dX, const int *frameOff,
                             const int *netOf /*[nUtt], 0..nNets-1, repeats allowed*/, int nUtt, int maxWords,
                             const htkamd_decode_out *out, void *stream);
+int  htkamd_decoder_set_run_lattice(htkamd_decoder_set *d, const htkamd_decode_config *cfg, int nToks, float nBeam, const float *dX, const int *frameOff,
+                                    const int *netOf, int nUtt, int maxLatNodes, int maxLatArcs, const htkamd_lattice_out *out, void *stream);
+int  htkamd_decoder_set_run_lattice_align(htkamd_decoder_set *d, const htkamd_decode_config *cfg, int nToks, float nBeam, int alignMode, const float *dX,
+                                          const int *frameOff, const int *netOf, int nUtt, int maxLatNodes, int maxLatArcs, int maxAlign,
+                                          const htkamd_lattice_out *out, const htkamd_lattice_align_out *alOut, void *stream);
 int  htkamd_decoder_set_last_tied(const htkamd_decoder_set *d);
 int  htkamd_decoder_set_set_order(htkamd_decoder_set *d, int mode);      /* HTKAMD_ORDER_* */
 

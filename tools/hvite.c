@@ -4,6 +4,8 @@
  *   hvite [options] -a [-b sil] dict hmmList dataFiles...         alignment of each file's word-level transcription
  *   hvite [options] -w -L dir -X ext dict hmmList dataFiles...    each file against its own lattice dir/<file>.ext (rescoring)
  * The last two are DoAlignment (HVite.c:830): --batch files at a time, a network per file, one launch per batch (htkamd_decoder_set_*).
+ * With -n i [N] [-z ext] all three decode with i tokens per state and write a lattice per file (-z, into the -l directory) and / or the N
+ * most likely transcriptions; -a -n i -z ext gives the lattice of the pronunciation alternatives of the file's word sequence.
  *
  * Options (the subset of HTKBook ref.tex "HVite" that SURVEY.md 8(b) lists; same letters, meaning and defaults, HVite.c:227-420):
  *   -C cf        configuration file (TARGETKIND, DELTAWINDOW, ACCWINDOW, THIRDWINDOW, V1COMPAT, SIMPLEDIFFS)
@@ -233,9 +235,11 @@ int main(int argc, char **argv)
    if (files.n == 0) DIE("hvite: no data files");
    if (!align && !netPath && !latPerFile) DIE("hvite: either -w net or -a");
    if (align && latPerFile) DIE("hvite: -w without a network name takes a lattice per file: not together with -a");      /* HVite.c:453 */
-   if (nToks > 1 && latPerFile) DIE("hvite: -n with a lattice per file is not supported");
    if (nToks == 1 || nToks > 8) DIE("hvite -n: 2..8 tokens per state");
-   if (nToks > 1 && align) DIE("hvite: alignment using multiple tokens is not supported");       /* HVite.c:448 (-m / -f with -n: as the reference built with -DPHNALG, alignment records inside the lattice arcs) */
+   /* (the reference only warns here, "nbest recognition with no nbest output", HVite.c:455, and decodes with token sets to write the 1-best labels) */
+   if (nToks > 1 && latPerFile && !latExt && nTrans < 2) DIE("hvite: -n %d with a lattice per file gives neither lattices nor alternatives: add -z ext, or -n %d N with N > 1", nToks, nToks);
+   /* (-m / -f with -n, -a included: as the reference built with -DPHNALG, alignment records inside the lattice arcs -- HVite.c:447-450) */
+   if (nToks > 1 && (align || latPerFile) && genBeamInc > 0.0f) DIE("hvite: -t f i l (DoAlignment's retries with wider beams) together with -n is not supported");
    if (latExt && nToks < 2) DIE("hvite -z: lattices need -n i with i > 1");
    if (waveform_source(&cfg) && cfg_get(&cfg, "TARGETKIND")) check_waveform_kind(kind_parse(cfg_get(&cfg, "TARGETKIND")));
    if (waveform_source(&cfg)) check_waveform_warp(&cfg);
@@ -330,11 +334,19 @@ int main(int argc, char **argv)
             if (alMode) {
                ao.arcAlignOff = (int *)malloc(sizeof(int) * (size_t)nb * (maxA + 1)); ao.alState = (int *)malloc(sizeof(int) * (size_t)nb * maxAl);
                ao.alModel = (int *)malloc(sizeof(int) * (size_t)nb * maxAl); ao.alDur = (int *)malloc(sizeof(int) * (size_t)nb * maxAl); ao.alLike = (float *)malloc(sizeof(float) * (size_t)nb * maxAl);
-               CHECK(htkamd_decoder_run_lattice_align(dec, &dc, nToks, dc.genBeam, alMode, ob.dX + (size_t)ob.frameOff[b0] * ob.cols, fo, nb, maxN, maxA, maxAl, &lo, &ao, NULL));
-            } else
-            CHECK(htkamd_decoder_run_lattice(dec, &dc, nToks, dc.genBeam, ob.dX + (size_t)ob.frameOff[b0] * ob.cols, fo, nb, maxN, maxA, &lo, NULL));   /* nBeam = genBeam (HVite.c:546) */
+            }
+            /* nBeam = genBeam (HVite.c:546); a network per file (DoAlignment -> ProcessFile, HVite.c:769-802): the decoder set, one launch for the nb files */
+            const float *dXb = ob.dX + (size_t)ob.frameOff[b0] * ob.cols;
+            if (perFile) {
+               if (alMode) CHECK(htkamd_decoder_set_run_lattice_align(set, &dc, nToks, dc.genBeam, alMode, dXb, fo, netOf + b0, nb, maxN, maxA, maxAl, &lo, &ao, NULL));
+               else CHECK(htkamd_decoder_set_run_lattice(set, &dc, nToks, dc.genBeam, dXb, fo, netOf + b0, nb, maxN, maxA, &lo, NULL));
+            } else if (alMode) CHECK(htkamd_decoder_run_lattice_align(dec, &dc, nToks, dc.genBeam, alMode, dXb, fo, nb, maxN, maxA, maxAl, &lo, &ao, NULL));
+            else CHECK(htkamd_decoder_run_lattice(dec, &dc, nToks, dc.genBeam, dXb, fo, nb, maxN, maxA, &lo, NULL));
             for (int u = 0; u < nb; u++) {
                const char *fn = files.v[first + b0 + u];
+               /* the file's own network names its words; a lattice made in DoAlignment has no lmname / lmscale lines (its network was never read from a named file) */
+               const htkamd_net *unet = perFile ? unets[netOf[b0 + u]] : net;
+               const char *lmName = perFile ? NULL : netPath;
                if (nN[u] == -1) { fprintf(stderr, "No tokens survived to final node of network: %s\n", fn); continue; }
                if (nN[u] < 0) DIE("the lattice of %s does not fit (%d nodes / %d arcs of room)", fn, maxN, maxA);
                htkamd_lattice lat; memset(&lat, 0, sizeof(lat));
@@ -349,22 +361,22 @@ int main(int argc, char **argv)
                }
                if (latExt) {
                   make_fn(fn, outDir, latExt, out, sizeof(out));
-                  if (alMode) CHECK(htkamd_lattice_write_align(&lat, &la, mmf, net, out, fn, netPath, dictPath, latFmt ? latFmt : HTKAMD_LAT_DEFAULT_ALIGN));
-                  else CHECK(htkamd_lattice_write(&lat, net, out, fn, netPath, dictPath, latFmt ? latFmt : HTKAMD_LAT_DEFAULT));
+                  if (alMode) CHECK(htkamd_lattice_write_align(&lat, &la, mmf, unet, out, fn, lmName, dictPath, latFmt ? latFmt : HTKAMD_LAT_DEFAULT_ALIGN));
+                  else CHECK(htkamd_lattice_write(&lat, unet, out, fn, lmName, dictPath, latFmt ? latFmt : HTKAMD_LAT_DEFAULT));
                }
                /* "only output 1-best transcription if generating lattices" (HVite.c:797) */
                const int want = (nTrans > 1 && latExt) ? 1 : nTrans;
                int nAlt = 0, *altLen = (int *)malloc(sizeof(int) * (size_t)want), *altArcs = (int *)malloc(sizeof(int) * (size_t)want * maxWords);
-               CHECK(htkamd_lattice_nbest(&lat, net, want, maxWords, &nAlt, altLen, altArcs));
+               CHECK(htkamd_lattice_nbest(&lat, unet, want, maxWords, &nAlt, altLen, altArcs));
                htkamd_trans *head = NULL;
                for (int i = 0; i < nAlt; i++) {
                   htkamd_trans *tr = NULL;
-                  if (alMode) CHECK(htkamd_lattice_align_trans(&lat, &la, mmf, net, altArcs + (size_t)i * maxWords, altLen[i], &tr));      /* model / state labels from the arcs' records */
+                  if (alMode) CHECK(htkamd_lattice_align_trans(&lat, &la, mmf, unet, altArcs + (size_t)i * maxWords, altLen[i], &tr));      /* model / state labels from the arcs' records */
                   if (tr) { if (!head) head = tr; else CHECK(htkamd_trans_append_alternative(head, tr)); continue; }
                   CHECK(htkamd_trans_create(0, &tr));
                   for (int j = 0; j < altLen[i]; j++) {
                      const int arc = altArcs[(size_t)i * maxWords + j], pron = lat.nodePron[lat.arcEnd[arc]];
-                     const char *sym = pron >= 0 ? htkamd_net_out_sym(net, pron) : NULL;
+                     const char *sym = pron >= 0 ? htkamd_net_out_sym(unet, pron) : NULL;
                      if (!sym || !sym[0]) continue;
                      CHECK(htkamd_trans_add(tr, (double)lat.nodeFrame[lat.arcStart[arc]] * ob.period, (double)lat.nodeFrame[lat.arcEnd[arc]] * ob.period, sym,
                                             htkamd_lattice_arc_score(&lat, arc), NULL, 0, NULL, 0));
@@ -382,6 +394,9 @@ int main(int argc, char **argv)
             free(nN); free(nA); free(nodeFrame); free(nodePron); free(nodeLike); free(aS); free(aE); free(aAc); free(aLm); free(aPr); free(fo);
             free(ao.arcAlignOff); free(ao.alState); free(ao.alModel); free(ao.alDur); free(ao.alLike);
          }
+         if (set) htkamd_decoder_set_destroy(set);
+         for (int g = 0; g < nNets; g++) { htkamd_net_destroy(unets[g]); free(upaths[g]); }
+         free(unets); free(upaths); free(netOf);
          free_observations(&ob);
          continue;
       }
