@@ -5,8 +5,9 @@ statistics file and a tied-state set ready for mix-up.
 
 The edit script may hold RO, LS, TR, QS, TB and ST, and for data-driven clustering TC, NC and TI (furthest-neighbour clustering of the
 listed states on the device; a script needs no TB then); any other command is refused by name.  --no-merge / --no-leaf-stats are HHEd's
-configuration variables TREEMERGE = F / USELEAFSTATS = F.  The trees file is what the reference's LT + AU read to synthesise unseen
-triphones (not built here)."""
+configuration variables TREEMERGE = F / USELEAFSTATS = F.  LT, AU and CO are taken, too: "... TB ... AU fulllist CO tiedlist ST trees"
+synthesises the unseen triphones of fulllist from the trees on the device and compacts the set; in a second run "LT trees AU fulllist
+CO tiedlist" does the same from a saved trees file (MU inside a script stays refused)."""
 import argparse
 import os
 import sys
@@ -22,7 +23,7 @@ def main(argv=None):
     ap.add_argument("--trees", help="trees file (overrides the script's ST)")
     ap.add_argument("--no-merge", action="store_true"); ap.add_argument("--no-leaf-stats", action="store_true")
     a = ap.parse_args(argv)
-    sc = treeclust.parse_script(open(a.script).read())
+    sc = treeclust.parse_script(open(a.script).read(), synth=True)
     if a.trees:
         sc.trees_path = os.path.abspath(a.trees)
     mmf = capi.Mmf([a.mmf], hmm_list=a.hmmlist)
@@ -31,6 +32,8 @@ def main(argv=None):
     if isinstance(warn, str):
         print(warn, file=sys.stderr)
     mmf.write(mmf.packed(), one_file=a.out)
+    for c, r in zip([c for c in sc.commands if c[0] in ("AU", "CO")], [r for r in (warn if isinstance(warn, list) else []) if isinstance(r, tuple)]):
+        print("tree_cluster: %s %s: %s" % (c[0], c[1], "%d seen, %d unseen" % r if c[0] == "AU" else "%d logical, %d physical" % r))
     print("tree_cluster: %d trees, %d TC / NC commands, %d states -> %d" % (len(sc.specs), sum(c[0] in ("TC", "NC") for c in sc.commands), before, mmf.desc.numStates))
 
 

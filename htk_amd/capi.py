@@ -1072,6 +1072,24 @@ def trees_write(path: str, questions, trees):
     check(lib().htkamd_trees_write(str(path).encode(), qs, C.c_int(len(questions)), td, C.c_int(len(trees))), "trees_write")
 
 
+def name_question_answers(names, questions, stream=None) -> np.ndarray:
+    """Test aid (htkamd_name_question_answers): the answers of model names to QS questions [(name, [pattern, ...])] on the device,
+    uint8[nQ, N] -- DoMatch's * and ? over every pattern of a question."""
+    qs, keep = _tree_questions(questions)
+    N = len(names)
+    na = (C.c_char_p * max(N, 1))(*[str(x).encode() for x in names])
+    out = np.zeros((max(len(questions), 1), max(N, 1)), np.uint8)
+    check(lib().htkamd_name_question_answers(na, C.c_int(N), qs, C.c_int(len(questions)), _p(out), _stream(stream)), "name_question_answers")
+    return out[:len(questions), :N]
+
+
+def synth_last_kernel_ms():
+    """(matching, walking): the device time of the last add_unseen / tree_descend / name_question_answers call's kernels in ms."""
+    ms = (C.c_float * 2)()
+    lib().htkamd_synth_last_kernel_ms(ms)
+    return float(ms[0]), float(ms[1])
+
+
 def tree_split_sums(item_stats, node_items, answers, stream=None) -> np.ndarray:
     """Test aid (htkamd_tree_split_sums): the yes / no sums of one node on the device, float32[nQ, 2, 2D+1] (no side first)."""
     st = np.ascontiguousarray(item_stats, np.float32); it = np.ascontiguousarray(node_items, np.int32); an = np.ascontiguousarray(answers, np.uint8)
@@ -1130,12 +1148,8 @@ class Mmf:
             check(L.htkamd_mmf_read(self.h, str(f).encode(), None), "mmf_read")
         check(L.htkamd_mmf_finish(self.h, hmm_list.encode() if hmm_list else None, hmm_dir.encode() if hmm_dir else None,
                                   ext.encode() if ext else None), "mmf_finish")
-        self.desc = L.htkamd_mmf_desc(self.h).contents
         self.kind = L.htkamd_mmf_parm_kind(self.h).decode()
-        H = self.desc.numPhys
-        self.phys_names = [L.htkamd_mmf_phys_name(self.h, C.c_int(h)).decode() for h in range(H)]
-        n = L.htkamd_mmf_num_logical(self.h)
-        self.logical = {L.htkamd_mmf_logical_name(self.h, C.c_int(i)).decode(): L.htkamd_mmf_logical_phys(self.h, C.c_int(i)) for i in range(n)}
+        self._refresh_names()
         vf = L.htkamd_mmf_var_floor(self.h)
         self.var_floor = np.ctypeslib.as_array(vf, (self.desc.vecSize,)).copy() if vf else None
         L.htkamd_mmf_inv_cov.restype = C.POINTER(C.c_float)
@@ -1148,6 +1162,15 @@ class Mmf:
         self.set_id = L.htkamd_mmf_set_id(self.h).decode()
         xf = L.htkamd_mmf_inputxform(self.h)
         self.input_xform = InputXForm(C.c_void_p(xf), False, keep=self) if xf else None      # <INPUTXFORM>: owned by the set
+
+    def _refresh_names(self):
+        """The description and the models' names as the holder has them now (at load, and after add_unseen / compact changed the models)."""
+        L = lib()
+        self.desc = L.htkamd_mmf_desc(self.h).contents
+        self.phys_names = [L.htkamd_mmf_phys_name(self.h, C.c_int(h)).decode() for h in range(self.desc.numPhys)]
+        n = L.htkamd_mmf_num_logical(self.h)
+        self.logical_names = [L.htkamd_mmf_logical_name(self.h, C.c_int(i)).decode() for i in range(n)]
+        self.logical = {self.logical_names[i]: L.htkamd_mmf_logical_phys(self.h, C.c_int(i)) for i in range(n)}
 
     def refuse_input_xform(self, who: str):
         """For a caller that prepares its observations without looking at the set's transform: a set with <INPUTXFORM> would be trained
@@ -1222,6 +1245,57 @@ class Mmf:
                                             str(trees_path).encode() if trees_path else None, _stream(stream)), "mmf_tree_cluster")
         msg = lib().htkamd_last_error().decode()
         return msg if "warning" in msg else None
+
+    def load_trees(self, path: str):
+        """HHEd's LT command (htkamd_mmf_load_trees): the questions and state trees of an ST file join the trees the holder keeps."""
+        check(lib().htkamd_mmf_load_trees(self.h, str(path).encode()), "mmf_load_trees")
+
+    def save_trees(self, path: str):
+        """HHEd's ST command for the trees the holder keeps -- left by tree_cluster or loaded by load_trees (htkamd_mmf_save_trees)."""
+        check(lib().htkamd_mmf_save_trees(self.h, str(path).encode()), "mmf_save_trees")
+
+    def add_unseen(self, list_path: str, stream=None):
+        """HHEd's AU command (htkamd_mmf_add_unseen): the set's models become the names of the list file, the unseen ones synthesised from
+        the held trees on the device.  Returns (seen, unseen); phys_names / logical / packed() / write() reflect the new set afterwards."""
+        a, b = C.c_int(0), C.c_int(0)
+        check(lib().htkamd_mmf_add_unseen(self.h, str(list_path).encode(), C.byref(a), C.byref(b), _stream(stream)), "mmf_add_unseen")
+        self._refresh_names()
+        return a.value, b.value
+
+    def compact(self, list_path=None):
+        """HHEd's CO command (htkamd_mmf_compact): identical models become one physical model, `list_path` gets the tied list.  Returns
+        (logical, physical)."""
+        a, b = C.c_int(0), C.c_int(0)
+        check(lib().htkamd_mmf_compact(self.h, str(list_path).encode() if list_path else None, C.byref(a), C.byref(b)), "mmf_compact")
+        self._refresh_names()
+        return a.value, b.value
+
+    def trees(self):
+        """The held trees: [dict(name, state, nodes, leaves=[~s macro, ...])] in the order of HHEd's tree list."""
+        L = lib()
+        L.htkamd_mmf_tree_info.restype = C.c_char_p; L.htkamd_mmf_tree_leaf.restype = C.c_char_p
+        out = []
+        for t in range(L.htkamd_mmf_num_trees(self.h)):
+            st, nn, nl = C.c_int(0), C.c_int(0), C.c_int(0)
+            name = L.htkamd_mmf_tree_info(self.h, C.c_int(t), C.byref(st), C.byref(nn), C.byref(nl)).decode()
+            out.append(dict(name=name, state=st.value, nodes=nn.value, leaves=[L.htkamd_mmf_tree_leaf(self.h, C.c_int(t), C.c_int(k)).decode() for k in range(nl.value)]))
+        return out
+
+    def tree_descend(self, names, first_state: int, n_states: int, stream=None):
+        """Test aid (htkamd_tree_descend): for every name and state number first_state .. first_state+n_states-1 the held tree of the name's
+        base phone (-1: none) and the leaf the walk ends in (-1 without a tree): (int32[N, n_states], int32[N, n_states])."""
+        N = len(names)
+        na = (C.c_char_p * max(N, 1))(*[str(x).encode() for x in names])
+        tree = np.zeros((max(N, 1), n_states), np.int32); leaf = np.zeros((max(N, 1), n_states), np.int32)
+        check(lib().htkamd_tree_descend(self.h, na, C.c_int(N), C.c_int(first_state), C.c_int(n_states), _p(tree), _p(leaf), _stream(stream)), "tree_descend")
+        return tree[:N], leaf[:N]
+
+    def state_macro(self, state: int):
+        """The ~s macro name of state `state` of the description, None for an un-named state."""
+        L = lib()
+        L.htkamd_mmf_state_macro.restype = C.c_char_p
+        r = L.htkamd_mmf_state_macro(self.h, C.c_int(state))
+        return r.decode() if r else None
 
     def data_cluster(self, occ, specs, outlier: float = -1.0, stream=None):
         """HHEd's TC / NC commands on the loaded set (htkamd_mmf_data_cluster): `occ` the state occupations (read_stats) or None when no

@@ -66,6 +66,19 @@ typedef struct {
 } htkamd_dc_job;
 int  htkamd_dc_dev_run(const htkamd_dc_job *job, float *idistOut /* or NULL */, int *merges /*[2 * nItems]*/, int *nMerges /*[nCmds]*/, void *stream);
 
+/* ---- unseen models from the trees: the device side (csrc/treesynth.hip) as host/treeclust.c drives it ----
+ * Names and patterns are NUL-terminated strings in byte pools: name n at namePool + nameOff[n] (nameOff[N] = the pool's size), pattern k
+ * at patPool + patOff[k], question q owns patterns qPat[q] .. qPat[q+1]-1.  The trees' node tables lie behind one another (tree t: nodes
+ * treeOff[t] .. treeOff[t+1]-1, none = a single leaf; a child >= 0 a node of the tree, < 0 the leaf -1-k, k < treeLeaves[t]); a pair is
+ * (name, tree), tree -1 = none.  answers [nQ][N] bytes and leaf [nPairs] come back (either may be NULL when not wanted). */
+typedef struct {
+   int N; const char *namePool; const int *nameOff;
+   int nQ; const char *patPool; const int *patOff, *qPat;
+   int nTrees; const int *treeOff, *quest, *no, *yes, *treeLeaves;
+   int nPairs; const int *pairName, *pairTree;
+} htkamd_synth_job;
+int  htkamd_synth_dev_run(const htkamd_synth_job *job, unsigned char *answers, int *leaf, void *stream);
+
 /* device LAdd table: 4 intervals per unit of d over [minLogExp, 0] = [-23.03, 0], degree-10 Taylor rows (8 KB) */
 #define LADD_INV_H 4
 #define LADD_DEG   10

@@ -1118,7 +1118,20 @@ void htkamd_mmf_destroy(struct htkamd_mmf *s)
    for (int i = 0; i < s->nJm; i++) htkamd_inputxform_free(s->jm[i]);
    free(s->jm);
    free(s->stateCompOff); free(s->transN); free(s->transOff); free(s->hmmTrans); free(s->hmmStateOff); free(s->hmmState);
+   htkamd_mmf_trees_free(s->trees);
+   free(s->hmCreate); free(s->logCreate);
    free(s);
+}
+
+void htkamd_mmf_trees_free(mmf_trees *t)
+{
+   if (!t) return;
+   for (int i = 0; i < t->nQ; i++) { for (int k = 0; k < t->q[i].nPat; k++) free(t->q[i].pat[k]); free(t->q[i].pat); free(t->q[i].name); }
+   for (int i = 0; i < t->nT; i++) {
+      for (int k = 0; k < t->t[i].nLeaves; k++) free(t->t[i].leaf[k]);
+      free(t->t[i].leaf); free(t->t[i].quest); free(t->t[i].no); free(t->t[i].yes); free(t->t[i].name);
+   }
+   free(t->q); free(t->t); free(t);
 }
 
 /* ------------------------------------------------------------------------------------------ writer */
@@ -1453,7 +1466,7 @@ static int write_macros(const struct htkamd_mmf *s, const float *mean, const flo
       macro_order(names, nN, ord);
       for (int k = 0; k < nN; k++) { const int i = idx[ord[k]]; put_name(f, 's', s->st[i].name); put_state(s, f, i, mean, var, gconst, compWeight); }
       nN = 0;
-      for (int h = 0; h < s->nHm; h++) if (SRC(s->hm[h].src)) { names[nN] = s->hm[h].name; idx[nN++] = h; }
+      for (int k = 0; k < s->nHm; k++) { const int h = s->hmCreate ? s->hmCreate[k] : k; if (SRC(s->hm[h].src)) { names[nN] = s->hm[h].name; idx[nN++] = h; } }
       macro_order(names, nN, ord);
       for (int k = 0; k < nN; k++) put_hmm(s, f, idx[ord[k]], 1, mean, var, gconst, compWeight, transP);
       free(names); free(idx); free(ord);

@@ -1,5 +1,5 @@
 /* mmf_priv.h -- the model-set holder of mmf.c (struct htkamd_mmf) for the host files that edit a loaded set in place (mmf.c itself:
- * MU; treeclust.c: RO/QS/TB/ST).  Not part of the public interface. */
+ * MU; treeclust.c: RO/QS/TB/ST, TC/NC/TI, LT/AU/CO).  Not part of the public interface. */
 #ifndef HTKAMD_MMF_PRIV_H
 #define HTKAMD_MMF_PRIV_H
 #include "../csrc/internal.h"
@@ -8,6 +8,13 @@ typedef struct { char *name; int nMix; int comp0; int inlineOwner; int src; int 
    several streams: nMix = all components of the state, sMix[s] those of stream s (consecutive from comp0), sw = <SWEIGHTS> or NULL; dur: its duration vector (dm[]) or -1 */
 typedef struct { char *name; int N; int off; int src; } mmf_trans;
 typedef struct { char *name; int N; int *state; int trans; int src; int dur; } mmf_hmm;     /* src: index of the file it came from; dur: the model's duration vector (dm[]) or -1 */
+
+/* The trees HHEd keeps between commands (treeList and the question list, HHEd.c:2421 / qHead): left by TB, read by LT, used by AU and ST.
+   A question's patterns stand in QS order (htkamd_trees_write's convention: the file shows them last first); node n of a tree asks question
+   quest[n], no[n] / yes[n] >= 0 is a node, < 0 the leaf -1-k whose ~s macro is leaf[k]; nNodes = 0: the single leaf leaf[0]. */
+typedef struct { char *name; int nPat; char **pat; } mmf_quest;
+typedef struct { char *name; int state, nNodes, nLeaves; int *quest, *no, *yes; char **leaf; } mmf_tree;
+typedef struct { mmf_quest *q; int nQ; mmf_tree *t; int nT; } mmf_trees;
 
 struct htkamd_mmf {
    int vecSize, streamWidth, hasOpts;
@@ -47,6 +54,27 @@ struct htkamd_mmf {
    struct htkamd_inputxform **jm; int nJm, capJm;
    struct htkamd_inputxform *xf; int xfInline;
    int finished, nFiles;
+   /* HHEd's synthesis commands (treeclust.c: LT / AU / CO).  hmCreate / logCreate: the physical / logical models in the order their
+      macros were made, where that is no longer the order of hm[] / logName[] (SwapLists and CompactCommand re-make them); NULL = array order.
+      The reference's scan of the macro table (htkamd_hmm_scan_order) takes the names in this order. */
+   mmf_trees *trees;
+   int *hmCreate, *logCreate;
 };
+
+void htkamd_mmf_trees_free(mmf_trees *t);
+
+/* treeclust.c's helpers that treesynth.c shares (library-internal names) */
+#define tc_match        htkamd_tc_match
+#define tc_rewrite      htkamd_tc_rewrite
+#define tc_logical_walk htkamd_tc_logical_walk
+#define tc_compact      htkamd_tc_compact
+#define dc_fix_gconsts  htkamd_dc_fix_gconsts
+#define st_hold         htkamd_st_hold
+int  tc_match(const char *s, const char *p);                      /* DoMatch */
+void tc_rewrite(const char *s, char q, char *d);                  /* ReWriteString */
+int *tc_logical_walk(const struct htkamd_mmf *s);                 /* the logical names in the macro table's order (malloc'd) */
+void tc_compact(struct htkamd_mmf *s, const int *newSeq, int nNew);   /* drops states nobody uses, rebuilds the state side of the description */
+void dc_fix_gconsts(struct htkamd_mmf *s);                        /* FixAllGConsts (DIAGC) */
+void st_hold(struct htkamd_mmf *s, const htkamd_tree_question *q, int nQ, const htkamd_tree_desc *t, int nT);   /* TB's trees stay on the holder */
 
 #endif

@@ -7,6 +7,7 @@
  *   BuildTree (HHEd.c:2961) with InitTreeAccs :2535, ValidProbNode :2671, AccSumProb :2574, ClusterLogL :2611, FindBestSplit :2768,
  *     SplitTreeNode :2723, MergeLeaves / MergeNode / MergeCost :2785-2868, TieLeafNodes :2871, TieState :1021, TypicalState :990
  *   ShowTreesCommand (HHEd.c:3263), DownTree :3252, ReWriteString (HShell.c:1303)
+ *   (LoadTreesCommand, AddUnseenCommand and CompactCommand: treesynth.c)
  * The sums over a node's items are made on the device (csrc/treeclust.hip) in list order; every likelihood that decides something is
  * evaluated HERE, with the C library's log, from the device's sums (bit-equal to the reference's by construction).  All trees of a call
  * advance together: one batch of nodes per round. */
@@ -30,7 +31,7 @@
 
 /* ------------------------------------------------------------------------------------------ small helpers */
 /* DoMatch / RMatch (HShell.c:1787-1816): '*' any run (also empty), '?' one character */
-static int tc_match(const char *s, const char *p)
+int tc_match(const char *s, const char *p)
 {
    const char *star = NULL, *back = NULL;
    while (*s) {
@@ -46,7 +47,7 @@ static int tc_match(const char *s, const char *p)
 static int tc_has_wild(const char *p) { return strpbrk(p, "*?%") != NULL; }      /* PHIdent :1013 */
 
 /* ReWriteString (HShell.c:1303) with q = '\'', '"' or '\\' */
-static void tc_rewrite(const char *s, char q, char *d)
+void tc_rewrite(const char *s, char q, char *d)
 {
    if (q != '\\') *d++ = q;
    for (const unsigned char *p = (const unsigned char *)s; *p; p++) {
@@ -60,10 +61,15 @@ static void tc_rewrite(const char *s, char q, char *d)
 
 /* the logical names in the order PHIdent's walk over the macro table meets them (:1027): the hash order mmf.c writes macros in,
    over the list's names in list order ('l' macros are made in list order, MakeHMMSet HModel.c:3580) */
-static int *tc_logical_walk(const struct htkamd_mmf *s)
+int *tc_logical_walk(const struct htkamd_mmf *s)
 {
    int *order = (int *)malloc(sizeof(int) * (size_t)(s->nLog ? s->nLog : 1));
-   htkamd_hmm_scan_order((const char *const *)s->logName, s->nLog, order);
+   if (!s->logCreate) { htkamd_hmm_scan_order((const char *const *)s->logName, s->nLog, order); return order; }
+   const char **nm = (const char **)malloc(sizeof(char *) * (size_t)(s->nLog ? s->nLog : 1));      /* after AU / CO: the order the 'l' macros were re-made in */
+   for (int k = 0; k < s->nLog; k++) nm[k] = s->logName[s->logCreate[k]];
+   htkamd_hmm_scan_order(nm, s->nLog, order);
+   for (int k = 0; k < s->nLog; k++) order[k] = s->logCreate[order[k]];
+   free(nm);
    return order;
 }
 
@@ -468,7 +474,7 @@ static void tc_tie_leaf(struct htkamd_mmf *s, tc_tree *t, tc_node *n, const char
 
 /* The pools after the ties: states nobody uses any more go, the new ~s macros stand behind the older states in the order they were made
    (NewMacro's order decides their place in the saved file's hash chains), components and Gaussians follow their states. */
-static void tc_compact(struct htkamd_mmf *s, const int *newSeq, int nNew)
+void tc_compact(struct htkamd_mmf *s, const int *newSeq, int nNew)
 {
    const int D = s->vecSize, nSt0 = s->nSt;
    unsigned char *used = (unsigned char *)calloc((size_t)nSt0 + 1, 1);
@@ -731,6 +737,7 @@ int htkamd_mmf_tree_cluster(htkamd_mmf *s, const float *occ, float outlierThresh
       }
       tc_compact(s, newSeq, seq);
       for (int g = 0; g < s->nG; g++) htkamd_host_fix_diag_gconst(D, s->var + (size_t)g * D, s->gconst + g);      /* FixAllGConsts before HHEd saves (:6469) */
+      st_hold(s, kq, nKept, td, nT);                  /* treeList and the questions outlive the command (LT / AU / ST below) */
       if (treesPath) rc = htkamd_trees_write(treesPath, kq, nKept, td, nT);
       for (int t = 0; t < nT; t++) {
          for (int k = 0; k < td[t].nLeaves; k++) free((char *)td[t].leafMacro[k]);
@@ -770,7 +777,7 @@ static void dc_tie_states(struct htkamd_mmf *s, const tc_item *il, int cnt, cons
    for (int k = 0; k < cnt; k++) s->hm[il[k].phys].state[il[k].j - 1] = keep;
 }
 
-static void dc_fix_gconsts(struct htkamd_mmf *s)        /* FixAllGConsts (Clustering :2019, TieState :1027) */
+void dc_fix_gconsts(struct htkamd_mmf *s)        /* FixAllGConsts (Clustering :2019, TieState :1027) */
 {
    for (int g = 0; g < s->nG; g++) { htkamd_host_fix_diag_gconst(s->vecSize, s->var + (size_t)g * s->vecSize, s->gconst + g); s->hasG[g] = 1; }
    s->d.gconst = s->gconst;

@@ -1,5 +1,6 @@
-"""HHEd edit scripts restricted to state clustering and tying: RO, LS, TR, QS, TB, ST (tree-based) and TC, NC, TI (data-driven)
-(examples/tree_cluster.py, tools/tree_bench.py).
+"""HHEd edit scripts restricted to state clustering and tying: RO, LS, TR, QS, TB, ST (tree-based) and TC, NC, TI (data-driven), and -- for
+a caller that asks for them, parse_script(text, synth=True) -- LT, AU, CO: the unseen triphones from the trees and the compacted set
+(examples/tree_cluster.py, tools/tree_bench.py, tools/synth_bench.py).
 
     script = parse_script(open("tree.hed").read())
     run_script(mmf, script, stats_path)           # mmf: capi.Mmf; ties its states, writes script.trees_path if the script has an ST
@@ -13,6 +14,7 @@ from . import capi
 
 COMMANDS = ("RO", "TR", "QS", "TB", "ST", "TC", "NC", "TI", "LS")
 TREE_ONLY = ("RO", "TR", "QS", "TB", "ST")
+SYNTH = ("LT", "AU", "CO")
 
 
 class Script:
@@ -23,7 +25,8 @@ class Script:
         self.specs = []              # [(threshold, macro root, item list text)] in TB order
         self.trees_path = None       # ST's file name
         self.commands = []           # every command in script order: ("RO", threshold, file | None), ("LS", file), ("QS", name, patterns),
-                                     # ("TB", threshold, macro, items), ("TC" | "NC", value, macro, items), ("TI", macro, items), ("ST", file)
+                                     # ("TB", threshold, macro, items), ("TC" | "NC", value, macro, items), ("TI", macro, items), ("ST", file),
+                                     # and with synth=True ("LT", file), ("AU", file), ("CO", file)
 
 
 def _unquote(s: str) -> str:
@@ -40,9 +43,9 @@ def _item_list(rest: str, what: str):
     return rest[:a].strip(), rest[a:b + 1]
 
 
-def parse_script(text: str) -> Script:
+def parse_script(text: str, synth: bool = False) -> Script:
     """One command per line, as HHEd scripts are written; the commands are kept in script order (Script.commands).  Any command but
-    RO, LS, TR, QS, TB, ST, TC, NC and TI is refused by name."""
+    RO, LS, TR, QS, TB, ST, TC, NC and TI is refused by name -- and with synth=True LT, AU and CO are taken, too."""
     sc = Script()
     for raw in text.splitlines():
         line = raw.strip()
@@ -52,6 +55,11 @@ def parse_script(text: str) -> Script:
         if len(cmd) != 2 or not cmd.isalpha():
             raise capi.HtkAmdError("edit script: command expected in '%s'" % line)
         cmd = cmd.upper()
+        if synth and cmd in SYNTH:
+            if not rest.strip():
+                raise capi.HtkAmdError("%s: file name expected" % cmd)
+            sc.commands.append((cmd, _unquote(rest)))
+            continue
         if cmd not in COMMANDS:
             raise capi.HtkAmdError("edit script: command %s is not supported (only %s: state clustering and tying)" % (cmd, ", ".join(COMMANDS)))
         rest = rest.strip()
@@ -99,7 +107,9 @@ def parse_script(text: str) -> Script:
 def run_script(mmf: "capi.Mmf", sc: Script, stats_path=None, merge: bool = True, leaf_stats: bool = True, base_dir: str = ".", stream=None):
     """Apply a parsed script to a loaded set.  stats_path overrides RO's file name; relative file names of the script are taken under base_dir.
     A script of RO TR QS TB ST alone is one tree_cluster call.  Otherwise the commands run in script order, consecutive TC / NC commands
-    as one device call and consecutive TB commands as another; returns the list of what the calls returned."""
+    as one device call and consecutive TB commands as another; returns the list of what the calls returned.  In a script with LT, AU or
+    CO (parse_script(.., synth=True)) the trees stay on the set as in HHEd: AU after TB or LT uses them, ST writes all of them where it
+    stands; AU returns (seen, unseen), CO (logical, physical)."""
     if all(c[0] in TREE_ONLY for c in sc.commands):
         if not sc.specs:
             raise capi.HtkAmdError("edit script: no TB command")
@@ -111,7 +121,8 @@ def run_script(mmf: "capi.Mmf", sc: Script, stats_path=None, merge: bool = True,
         return mmf.tree_cluster(occ, sc.questions, sc.specs, outlier=sc.outlier, merge=merge, leaf_stats=leaf_stats, trees_path=trees, stream=stream)
     cmds = sc.commands
     tb_groups = sum(1 for k, c in enumerate(cmds) if c[0] == "TB" and (k == 0 or cmds[k - 1][0] != "TB"))
-    if tb_groups > 1 and sc.trees_path:
+    synth = any(c[0] in SYNTH for c in cmds)
+    if tb_groups > 1 and sc.trees_path and not synth:
         raise capi.HtkAmdError("edit script: ST after TB commands that other commands separate is not supported (the trees of one run of TB commands are written)")
     loaded, outlier, questions, out = None, -1.0, [], []
 
@@ -139,7 +150,7 @@ def run_script(mmf: "capi.Mmf", sc: Script, stats_path=None, merge: bool = True,
             if c[0] == "TB":
                 if not loaded:
                     raise capi.HtkAmdError("edit script: no stats loaded (no RO or LS command names a statistics file before TB and none was given)")
-                trees = os.path.join(base_dir, sc.trees_path) if sc.trees_path else None
+                trees = os.path.join(base_dir, sc.trees_path) if sc.trees_path and not synth else None
                 out.append(mmf.tree_cluster(occupations(), list(questions), [x[1:] for x in cmds[k:e]], outlier=outlier, merge=merge, leaf_stats=leaf_stats,
                                             trees_path=trees, stream=stream))
             else:
@@ -148,5 +159,13 @@ def run_script(mmf: "capi.Mmf", sc: Script, stats_path=None, merge: bool = True,
             continue
         elif c[0] == "TI":
             out.append(mmf.tie(c[1], c[2]))
+        elif c[0] == "LT":
+            mmf.load_trees(os.path.join(base_dir, c[1]))
+        elif c[0] == "AU":
+            out.append(mmf.add_unseen(os.path.join(base_dir, c[1]), stream=stream))
+        elif c[0] == "CO":
+            out.append(mmf.compact(os.path.join(base_dir, c[1])))
+        elif c[0] == "ST" and synth:
+            mmf.save_trees(os.path.join(base_dir, c[1]))
         k += 1
     return out

@@ -268,6 +268,57 @@ int  htkamd_mmf_tie(htkamd_mmf *s, const char *macro, const char *items);
 int  htkamd_state_distances(htkamd_mmf *s, const char *items, float *dist /*[n][n] or NULL*/, int cap, int *n, void *stream);
 int  htkamd_cluster_merges(const float *idist, int N, const float *occ /*[N] or NULL*/, int numReq, float threshold, float outlierThresh,
                            int *merges /*[2(N-1)]*/, int *nMerges);
+/* Unseen triphones from the trees and the compacted set: HHEd's LT / AU / CO commands (and ST for trees that were loaded).
+   htkamd_mmf_tree_cluster leaves its trees on the holder, as HHEd's treeList and question list outlive TB: the kept questions with their
+   patterns and per tree the base phone, the state number, the node table and the leaves' ~s macros.  Trees of further calls are added.
+     load_trees  : LoadTreesCommand (HHEd.c:3433) with LoadQuestion :417 and LoadTree :3346: the QS lines, then state trees "base[i]" as a
+                   node table "{ -n 'question' no yes ... }" or as a single leaf.  The patterns of a question are prepended as they are
+                   read, so a file that is loaded and saved again shows every question's patterns in the opposite order -- as with HHEd;
+                   a second round gives the first file back.  Refused with the reason: a question named twice or already held
+                   (HTKAMD_EINVAL, the reference's 2661 "Question name invalid"); a node's question or a leaf's macro that is not recognised
+                   (HTKAMD_EMODEL, 2661; a leaf must be a ~s macro of the set); a node number that is not in the tree, named by two parents
+                   or never defined (HTKAMD_EINVAL, 2661); a file without questions when none are held (HTKAMD_EINVAL, 2660
+                   "Questions Expected") or without trees; model trees -- a name without [i], the reference's 'h' trees -- which are
+                   not built (HTKAMD_EMODEL); text that cannot be parsed (HTKAMD_EIO).  A refused file leaves the held trees as they were.
+     save_trees  : ShowTreesCommand (HHEd.c:3263) for the held trees, through htkamd_trees_write.
+     add_unseen  : AddUnseenCommand (HHEd.c:5082) with TreeFilter :3219, SynthModel :3180, AssignStructure :3115, FindProtoModel :3160 and
+                   SwapLists :3497.  `hmmListPath` lists one model name per line.  A name the set knows as a logical model keeps its model;
+                   every other name becomes a new physical model: the number of states, the duration and the transition matrix of its
+                   proto -- the first model in the reference's macro-table scan (htkamd_hmm_scan_order; models synthesised earlier in the
+                   call take part, as they do there) whose name without contexts (TriStrip) is the new name's -- the matrix shared when it
+                   is a ~t macro and copied otherwise, and as state i the leaf that the walk down tree "base[i]" ends in.  The wildcard
+                   matching of all new names against the questions the trees ask and the walks run on the device (csrc/treesynth.hip);
+                   HTKAMD_ENODEV without one.  Afterwards the set's models, physical and logical, are exactly the list's, in list order
+                   (SwapLists): htkamd_mmf_desc, _num_logical, _logical_name, _find_logical, _phys_name and htkamd_mmf_write reflect it
+                   (model and state numbers change; states nobody uses any more are dropped; every gConst is refreshed as before HHEd
+                   saves).  Refused as the reference fails: no trees held (2662); a new name without a proto (2662 "no proto for ..");
+                   a new name whose base has no tree for an emitting state (2662 "cannot find tree for .. state i") -- the first such
+                   name in the reference's order of work; and with the reason: a list line with a physical name of its own, a name
+                   twice in the list, names of more than HTKAMD_SYNTH_MAXNAME characters (TriStrip's buffer), sets with more than one
+                   stream, tied-mixture and discrete sets (HTKAMD_EMODEL).  Any number of mixture components per state.
+     compact     : CompactCommand (HHEd.c:4340) with EquivHMM :685 and SaveHMMList (HModel.c:5029).  Two models are one when they have the
+                   same number of states, the SAME transition matrix (identity, not value) and state for state the same state -- or,
+                   when the set has ~m macros or both ~u and ~v macros (varFloor macros count, as there), states whose components name the
+                   same mean and variance vectors with the same weights (EquivState :670).  The first of a group in the macro-table scan
+                   stays, the others become logical names of it.  One pass with a hash over (matrix, states ..) in place of the
+                   reference's list walk; host only.  `listPath`: the list file "logical [physical]" in the scan's order, or NULL.
+     name_question_answers / tree_descend / mmf_num_trees / mmf_tree_info / mmf_tree_leaf / mmf_state_macro : test aids -- answers[q][n]
+                   of any names against any questions on the device; for names against the HELD trees, per name and state number
+                   firstState .. firstState+nStates-1 the tree (-1: none for that base and state) and the leaf the walk ends in (-1 with
+                   no tree); the held trees' names, sizes and leaf macros; the ~s macro name of a state of the set (NULL: un-named). */
+#define HTKAMD_SYNTH_MAXNAME 99
+int  htkamd_mmf_load_trees(htkamd_mmf *s, const char *path);
+int  htkamd_mmf_save_trees(const htkamd_mmf *s, const char *path);
+int  htkamd_mmf_add_unseen(htkamd_mmf *s, const char *hmmListPath, int *nSeen, int *nUnseen, void *stream);
+int  htkamd_mmf_compact(htkamd_mmf *s, const char *listPath, int *nLog, int *nPhys);
+int  htkamd_name_question_answers(const char *const *names, int N, const htkamd_tree_question *q, int nQ, unsigned char *answers /*[nQ][N]*/, void *stream);
+int  htkamd_tree_descend(const htkamd_mmf *s, const char *const *names, int N, int firstState, int nStates, int *tree /*[N][nStates]*/,
+                         int *leaf /*[N][nStates]*/, void *stream);
+int  htkamd_mmf_num_trees(const htkamd_mmf *s);
+const char *htkamd_mmf_tree_info(const htkamd_mmf *s, int t, int *state, int *nNodes, int *nLeaves);      /* the base phone's name */
+const char *htkamd_mmf_tree_leaf(const htkamd_mmf *s, int t, int leaf);
+const char *htkamd_mmf_state_macro(const htkamd_mmf *s, int state);
+void htkamd_synth_last_kernel_ms(float *ms /*[2]*/);      /* the device time of the last call's matching and walking kernels (tools/synth_bench.py) */
 /* HCompV's PutVFloor (HCompV.c:359-389): "~v varFloor1 <Variance> D" with scale*var, written like WriteVector(" %e"). */
 int  htkamd_mmf_write_vfloors(const char *path, const float *var, int D, float scale);
 void htkamd_mmf_destroy(htkamd_mmf *s);
