@@ -1133,6 +1133,93 @@ def state_distances(mmf: "Mmf", items: str, stream=None) -> np.ndarray:
     return out
 
 
+# ---- HInit on the device (htkamd_hinit, htkamd_flat_cluster)
+HINIT_OK, HINIT_EFEWSEGS, HINIT_ESHORT, HINIT_ENOMIX, HINIT_ENOPATH, HINIT_EZEROOCC, HINIT_ECLUSTER = 0, 2121, 2122, 2125, 2126, 2127, 7120
+MINMIX = 1.0e-5
+
+
+class HInitConfig(C.Structure):
+    _fields_ = [("maxIter", C.c_int), ("epsilon", C.c_float), ("minVar", C.c_float), ("minSeg", C.c_int), ("mixWeightFloor", C.c_float),
+                ("uFlags", C.c_int), ("newModel", C.c_int)]
+
+
+def hinit_config(max_iter=20, epsilon=1.0e-4, min_var=1.0e-2, min_seg=3, mix_weight_floor=0.0, uflags=UPALL, new_model=True) -> HInitConfig:
+    """HInit's switches -i -e -v -m -w (as MINMIX * f) -u -n (new_model False = -n: no uniform segmentation)."""
+    return HInitConfig(int(max_iter), float(epsilon), float(min_var), int(min_seg), float(mix_weight_floor), int(uflags), int(bool(new_model)))
+
+
+def _hinit_tokens(tokens):
+    t = np.ascontiguousarray(tokens, np.int32).reshape(-1, 3)
+    return [np.ascontiguousarray(t[:, k]) for k in range(3)]
+
+
+def hinit_check(pk: dict, n_frames: int, tokens, cfg: HInitConfig, models):
+    """Everything htkamd_hinit refuses before it touches a device, on a packed description (htkamd_hinit_check).  tokens: rows of
+    (first frame, frames, physical model)."""
+    d, keep = _desc_from_packed(pk)
+    fr, ln, md = _hinit_tokens(tokens)
+    mo = np.ascontiguousarray(models, np.int32)
+    check(lib().htkamd_hinit_check(C.byref(d), C.c_int(int(n_frames)), C.c_int(len(fr)), _p(fr), _p(ln), _p(md), C.byref(cfg), C.c_int(len(mo)), _p(mo)), "hinit_check")
+
+
+def hinit(model, dX_ptr, n_frames: int, tokens, models, cfg: HInitConfig = None, stream=None):
+    """Viterbi training of the listed physical models from labelled tokens in one call (htkamd_hinit).  `model`: a Model, or a packed
+    description (checked first, then made a Model: the refusals need no device); tokens: rows of (first frame in the table, frames,
+    physical model), the reference's order within each model.  Returns (model, results): results[k] for models[k] is a dict of status
+    (HINIT_*), passes, converged and logP (the average log probability of every pass).  The estimates are in the model."""
+    cfg = cfg or hinit_config()
+    fr, ln, md = _hinit_tokens(tokens)
+    mo = np.ascontiguousarray(models, np.int32)
+    if not isinstance(model, Model):
+        hinit_check(model, n_frames, tokens, cfg, mo)
+        model = Model(model)
+    n = len(mo)
+    status = np.zeros(max(n, 1), np.int32); passes = np.zeros(max(n, 1), np.int32); conv = np.zeros(max(n, 1), np.int32)
+    logp = np.zeros((max(n, 1), max(cfg.maxIter, 1)), np.float32)
+    ptr = dX_ptr if isinstance(dX_ptr, C.c_void_p) else C.c_void_p(int(dX_ptr) if dX_ptr else 0)
+    check(lib().htkamd_hinit(model.h, ptr, C.c_int(int(n_frames)), C.c_int(len(fr)), _p(fr), _p(ln), _p(md), C.byref(cfg), C.c_int(n), _p(mo),
+                             _p(status), _p(passes), _p(conv), _p(logp), _stream(stream)), "hinit")
+    res = [dict(status=int(status[k]), passes=int(passes[k]), converged=bool(conv[k]), logP=[float(x) for x in logp[k, :passes[k]]]) for k in range(n)]
+    return model, res
+
+
+def hinit_uniform_states(n_emit: int, tok_len) -> np.ndarray:
+    """UCollectData's rule as the kernels apply it (htkamd_hinit_uniform_states): the 0-based emitting state of every frame of the tokens."""
+    ln = np.ascontiguousarray(tok_len, np.int32)
+    out = np.zeros(max(int(ln.sum()), 1), np.int32)
+    check(lib().htkamd_hinit_uniform_states(C.c_int(int(n_emit)), C.c_int(len(ln)), _p(ln), _p(out)), "hinit_uniform_states")
+    return out[:int(ln.sum())]
+
+
+def flat_cluster(dX_ptr, n_rows: int, D: int, pools, nc, min_var: float = 0.0, stream=None):
+    """FlatCluster (HTrain.c:763) of several pools in one launch (htkamd_flat_cluster).  pools: a list of row-number arrays into the
+    device table dX [n_rows, D]; nc: clusters per pool.  Returns a list of dicts per pool: status, size [nc], centre / var [nc, D],
+    assign [items] (a failed pool: status HINIT_ECLUSTER and nothing else)."""
+    pools = [np.ascontiguousarray(p, np.int32).reshape(-1) for p in pools]
+    ncs = np.ascontiguousarray(nc, np.int32).reshape(-1)
+    if len(ncs) != len(pools):
+        raise HtkAmdError("flat_cluster: %d cluster counts for %d pools" % (len(ncs), len(pools)))
+    off = np.concatenate([[0], np.cumsum([len(p) for p in pools])]).astype(np.int32)
+    items = np.ascontiguousarray(np.concatenate(pools) if pools else np.zeros(0), np.int32)
+    if items.size == 0:
+        items = np.zeros(1, np.int32)
+    tot = max(int(np.clip(ncs, 0, None).sum()), 1)
+    size = np.zeros(tot, np.int32); ctr = np.zeros((tot, D), np.float32); var = np.zeros((tot, D), np.float32)
+    assign = np.zeros(max(int(off[-1]), 1), np.int32); status = np.zeros(max(len(pools), 1), np.int32)
+    ptr = dX_ptr if isinstance(dX_ptr, C.c_void_p) else C.c_void_p(int(dX_ptr) if dX_ptr else 0)
+    check(lib().htkamd_flat_cluster(ptr, C.c_int(int(n_rows)), C.c_int(int(D)), C.c_int(len(pools)), _p(off), _p(items), _p(ncs), C.c_float(min_var),
+                                    _p(size), _p(ctr), _p(var), _p(assign), _p(status), _stream(stream)), "flat_cluster")
+    out, c0 = [], 0
+    for p in range(len(pools)):
+        k = int(ncs[p])
+        if status[p] != HINIT_OK:
+            out.append(dict(status=int(status[p])))
+        else:
+            out.append(dict(status=0, size=size[c0:c0 + k].copy(), centre=ctr[c0:c0 + k].copy(), var=var[c0:c0 + k].copy(), assign=assign[off[p]:off[p + 1]].copy()))
+        c0 += k
+    return out
+
+
 class Mmf:
     """htkamd_mmf holder: LoadHMMSet / SaveHMMSet for text model definitions (htk_amd/host/mmf.c)."""
 

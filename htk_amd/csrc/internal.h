@@ -79,6 +79,11 @@ typedef struct {
 } htkamd_synth_job;
 int  htkamd_synth_dev_run(const htkamd_synth_job *job, unsigned char *answers, int *leaf, void *stream);
 
+/* ---- the aligner's results where they lie on the device (csrc/viterbi.hip), for csrc/hinit.hip: per chain state in utterance order
+ * segStart / segEnd, per utterance total and status.  Valid until the handle aligns again. */
+typedef struct { const int *segStart, *segEnd; const double *total; const int *status; } htkamd_viterbi_dev;
+int  htkamd_viterbi_device_results(htkamd_viterbi *v, htkamd_viterbi_dev *out);
+
 /* device LAdd table: 4 intervals per unit of d over [minLogExp, 0] = [-23.03, 0], degree-10 Taylor rows (8 KB) */
 #define LADD_INV_H 4
 #define LADD_DEG   10

@@ -634,3 +634,13 @@ extern "C" int htkamd_viterbi_results(htkamd_viterbi *v, int *segStart, int *seg
    if (status) HIPCHECK(hipMemcpy(status, v->d_status.p, 4 * (size_t)v->nUtt, hipMemcpyDeviceToHost));
    return HTKAMD_OK;
 }
+
+// Where the last alignment's results lie on the device, for a caller that goes on with them there (csrc/hinit.hip): segments per chain
+// state in utterance order, totals and status per utterance.  Valid until the next alignment with this handle.
+int htkamd_viterbi_device_results(htkamd_viterbi *v, htkamd_viterbi_dev *out)
+{
+   if (!v || !out) { htkamd_set_error("viterbi_device_results: NULL"); return HTKAMD_EINVAL; }
+   out->segStart = (const int *)v->d_segStart.p; out->segEnd = (const int *)v->d_segEnd.p;
+   out->total = (const double *)v->d_total.p; out->status = (const int *)v->d_status.p;
+   return HTKAMD_OK;
+}

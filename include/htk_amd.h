@@ -1201,6 +1201,72 @@ int  htkamd_inputxform_apply_cols(const htkamd_inputxform *x, const htkamd_parm_
 int  htkamd_inputxform_apply(const htkamd_inputxform *x, const float *dStatic, const int *frameOff, int nUtt,
                              const htkamd_parm_quals *q, float *dOut, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Viterbi training from labelled tokens: replaces HInit (HTKTools/HInit.c) for every model of a list in ONE call, on one-stream
+ * DIAGC continuous-density sets (csrc/hinit.hip; the checks and the host twin of the pool listing: host/hinit.c).
+ *   EstimateModel (HInit.c:1192)   htkamd_hinit: per model the reference's loop, all models side by side
+ *   UCollectData (:505)            pools of frames per (model, emitting state): count, scan, fill kernels; frame j (1-based) of a token
+ *                                  of L frames goes to state (int)((float)(j-1) / ((float)L / (float)(N-2)) + 2), the sum in float
+ *   FlatCluster (HTrain.c:763)     one workgroup per pool (htkamd_flat_cluster is that launch on its own): Euclidean distance, diagonal
+ *                                  cluster covariances; BiggestCluster / Perturb / AllocateVectors / FullestCluster / FindCentres /
+ *                                  FindCovariance in the reference's float / double mix and item order, so sizes, centres and
+ *                                  variances are the reference's bits
+ *   ViterbiAlign (:792)            htkamd_viterbi_align_mode(HTKAMD_SCORE_SOUTP | HTKAMD_SCORE_DIAGC), one single-model utterance per
+ *                                  token, every token of the models still running in one call per pass
+ *   FindBestMixes (:739)           a lane per frame: MOutP of every component in DOutP's form, the first maximum
+ *   UpdateCounts (:878)            a wavefront per (token, state): counts and fp64 sums of x - mean and its square (atomic adds: the
+ *                                  order of the sums is not fixed), transition counts along the state sequence
+ *   UpWeights / UpMeans / UpVars / UpTrans (:997-1097)   a workgroup per model; only what uFlags selects is written, then 1/variance,
+ *                                  gConst, log weights and the scoring rows of the model's Gaussians are rebuilt in place
+ * The host reads one (log probability sum, status) pair per running model per pass and decides convergence as the reference does:
+ * newP = sum / tokens in float, |newP - totalP| < epsilon from the second pass on.
+ * Tokens: tokFrame / tokLen / tokModel [nTokens] on the host -- first row in dX, frames, physical model --, in the reference's order
+ * within each model (file order, then label order; FlatCluster's float sums run in that order).  Tokens of models that are not in
+ * `models` are ignored.
+ * Per model: status[k] (HTKAMD_HINIT_*; a model with a status other than OK keeps the parameters it had), nPass[k], converged[k] and
+ * logP[k * maxIter + pass] ("Iteration k: Average LogP").  Every other model is trained exactly as if it had been called alone.
+ * Refused before a device is touched (HTKAMD_EMODEL / HTKAMD_EINVAL and the reason; htkamd_hinit_check is these checks on a set's
+ * description): FULLC, tied-mixture and multi-stream sets; sets with ~u / ~v sharing; models to be trained that use a state, a Gaussian
+ * or a transition matrix twice, among or within them (HInit trains in isolation: shared structure would make the result depend on the
+ * order); a model named twice or out of range; a token outside the table or of an unknown model; maxIter < 1, minSeg < 1.
+ * mixWeightFloor is carried for the reference's -w; UpWeights (HInit.c:997) applies it to discrete sets only, so no continuous weight
+ * is ever floored.  On return the device arrays hold the estimates, the derived tables follow as after htkamd_model_update_device, and
+ * the host mirror is current.  Synchronises `stream`.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+   int   maxIter;          /* -i, 20                                                               */
+   float epsilon;          /* -e, 1.0e-4                                                           */
+   float minVar;           /* -v, 1.0e-2                                                           */
+   int   minSeg;           /* -m, 3                                                                */
+   float mixWeightFloor;   /* -w f: MINMIX * f (carried, see above)                                */
+   int   uFlags;           /* -u: HTKAMD_UPMEANS | _UPVARS | _UPTRANS | _UPMIXES                   */
+   int   newModel;         /* 1 (default): uniform segmentation + FlatCluster first; 0: -n, skip it */
+} htkamd_hinit_config;
+#define HTKAMD_HINIT_OK         0
+#define HTKAMD_HINIT_EFEWSEGS   2121   /* fewer than minSeg tokens                                              */
+#define HTKAMD_HINIT_ESHORT     2122   /* a token with fewer frames than emitting states                        */
+#define HTKAMD_HINIT_ENOMIX     2125   /* FindBestMixes: no best mix                                            */
+#define HTKAMD_HINIT_ENOPATH    2126   /* ViterbiAlign: no path in a token                                      */
+#define HTKAMD_HINIT_EZEROOCC   2127   /* a component nobody chose, or a state no token left                    */
+#define HTKAMD_HINIT_ECLUSTER   7120   /* a pool with fewer items than components, or one FlatCluster cannot split */
+int htkamd_hinit_check(const htkamd_model_desc *d, int nFrames, int nTokens, const int *tokFrame, const int *tokLen, const int *tokModel,
+                       const htkamd_hinit_config *cfg, int nModels, const int *models);
+int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int nTokens, const int *tokFrame, const int *tokLen, const int *tokModel,
+                 const htkamd_hinit_config *cfg, int nModels, const int *models,
+                 int *status /*[nModels]*/, int *nPass /*[nModels]*/, int *converged /*[nModels]*/, float *logP /*[nModels * maxIter]*/, void *stream);
+/* The pool listing of UCollectData on the host, as the kernels make it (test aid): for tokens of ONE model with nEmit emitting states,
+   state[k] = 0-based emitting state of the k-th frame of the tokens behind one another; returns 0, or HTKAMD_EINVAL for a token shorter
+   than nEmit. */
+int htkamd_hinit_uniform_states(int nEmit, int nTokens, const int *tokLen, int *state);
+/* FlatCluster (HTrain.c:763, NULLC distance, DIAGC cluster covariances) over nPools pools in one launch.  dX [nRows x D] on the device;
+   pool p owns items[poolOff[p] .. poolOff[p+1]) (row numbers, host) and is split into nc[p] clusters, which lie behind one another:
+   cluster c of pool p is entry cOff[p] + c, cOff = prefix sum of nc.  Outputs (host): size [sum nc], centre and var [sum nc x D] (var
+   floored at minVar), assign [items] = cluster of every item, status [nPools] = HTKAMD_HINIT_OK or HTKAMD_HINIT_ECLUSTER (that pool's
+   other outputs are then undefined, the other pools unaffected).  HTKAMD_EINVAL: a row outside the table, nc < 1, sizes that do not fit
+   the workgroup's LDS (nc x D floats). */
+int htkamd_flat_cluster(const float *dX, int nRows, int D, int nPools, const int *poolOff, const int *items, const int *nc, float minVar,
+                        int *size, float *centre, float *var, int *assign, int *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
