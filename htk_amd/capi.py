@@ -1220,6 +1220,63 @@ def flat_cluster(dX_ptr, n_rows: int, D: int, pools, nc, min_var: float = 0.0, s
     return out
 
 
+# ---- HRest on the device (htkamd_hrest)
+HREST_OK, HREST_EFEWSEGS, HREST_EZEROOCC, HREST_EFLOORSUM, HREST_ENOUSABLE = 0, 2221, 2222, 2223, 2226
+
+
+class HRestConfig(C.Structure):
+    _fields_ = [("maxIter", C.c_int), ("epsilon", C.c_float), ("minVar", C.c_float), ("minSeg", C.c_int), ("mixWeightFloor", C.c_float),
+                ("uFlags", C.c_int), ("segReject", C.c_int), ("vDefunct", C.c_float)]
+
+
+def hrest_config(max_iter=20, epsilon=1.0e-4, min_var=0.0, min_seg=3, mix_weight_floor=0.0, uflags=UPALL, seg_reject=True, v_defunct=0.0) -> HRestConfig:
+    """HRest's switches -i -e -v -m -w (as MINMIX * f) -u -t (seg_reject False = -t) and HREST: VDEFUNCT."""
+    return HRestConfig(int(max_iter), float(epsilon), float(min_var), int(min_seg), float(mix_weight_floor), int(uflags), int(bool(seg_reject)), float(v_defunct))
+
+
+def hrest_check(pk: dict, n_frames: int, tokens, cfg: HRestConfig, models):
+    """Everything htkamd_hrest refuses before it touches a device, on a packed description (htkamd_hrest_check).  tokens: rows of
+    (first frame, frames, physical model)."""
+    d, keep = _desc_from_packed(pk)
+    fr, ln, md = _hinit_tokens(tokens)
+    mo = np.ascontiguousarray(models, np.int32)
+    check(lib().htkamd_hrest_check(C.byref(d), C.c_int(int(n_frames)), C.c_int(len(fr)), _p(fr), _p(ln), _p(md), C.byref(cfg), C.c_int(len(mo)), _p(mo)), "hrest_check")
+
+
+def hrest_token_counts(pk: dict, tokens, cfg: HRestConfig, models):
+    """LoadFile's short-token rejection and main's -m test as the call does them (htkamd_hrest_token_counts, no device): returns
+    (keep [tokens] bool, kept [models], status [models])."""
+    fr, ln, md = _hinit_tokens(tokens)
+    mo = np.ascontiguousarray(models, np.int32)
+    off = np.ascontiguousarray(pk["hmmStateOff"], np.int32)
+    keep = np.zeros(max(len(ln), 1), np.int32); kept = np.zeros(max(len(mo), 1), np.int32); status = np.zeros(max(len(mo), 1), np.int32)
+    check(lib().htkamd_hrest_token_counts(_p(off), C.c_int(len(off) - 1), C.c_int(len(ln)), _p(ln), _p(md), C.byref(cfg), C.c_int(len(mo)), _p(mo),
+                                          _p(keep), _p(kept), _p(status)), "hrest_token_counts")
+    return keep[:len(ln)].astype(bool), kept[:len(mo)], status[:len(mo)]
+
+
+def hrest(model, dX_ptr, n_frames: int, tokens, models, cfg: HRestConfig = None, stream=None):
+    """Baum-Welch re-estimation of the listed physical models from labelled tokens in one call (htkamd_hrest).  `model`: a Model, or a
+    packed description (checked first, then made a Model: the refusals need no device); tokens: rows of (first frame in the table,
+    frames, physical model), the reference's order within each model.  Returns (model, results): results[k] for models[k] is a dict of
+    status (HREST_*), passes, converged, logP ("Ave LogProb" of every pass) and used ("using N examples").  The estimates are in the model."""
+    cfg = cfg or hrest_config()
+    fr, ln, md = _hinit_tokens(tokens)
+    mo = np.ascontiguousarray(models, np.int32)
+    if not isinstance(model, Model):
+        hrest_check(model, n_frames, tokens, cfg, mo)
+        model = Model(model)
+    n = len(mo)
+    status = np.zeros(max(n, 1), np.int32); passes = np.zeros(max(n, 1), np.int32); conv = np.zeros(max(n, 1), np.int32)
+    logp = np.zeros((max(n, 1), max(cfg.maxIter, 1)), np.float32); used = np.zeros((max(n, 1), max(cfg.maxIter, 1)), np.int32)
+    ptr = dX_ptr if isinstance(dX_ptr, C.c_void_p) else C.c_void_p(int(dX_ptr) if dX_ptr else 0)
+    check(lib().htkamd_hrest(model.h, ptr, C.c_int(int(n_frames)), C.c_int(len(fr)), _p(fr), _p(ln), _p(md), C.byref(cfg), C.c_int(n), _p(mo),
+                             _p(status), _p(passes), _p(conv), _p(logp), _p(used), _stream(stream)), "hrest")
+    res = [dict(status=int(status[k]), passes=int(passes[k]), converged=bool(conv[k]), logP=[float(x) for x in logp[k, :passes[k]]],
+                used=[int(x) for x in used[k, :passes[k]]]) for k in range(n)]
+    return model, res
+
+
 class Mmf:
     """htkamd_mmf holder: LoadHMMSet / SaveHMMSet for text model definitions (htk_amd/host/mmf.c)."""
 

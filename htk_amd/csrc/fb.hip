@@ -840,7 +840,7 @@ static int fb_execute_impl(htkamd_fb *fb, const htkamd_fb_config *cfg, htkamd_ac
       return HTKAMD_EINVAL;
    }
    const ScoreArgs sa = fb_score_args(fb, cfg);
-   if (cfg->scoreMode & ~(HTKAMD_SCORE_MFMA | HTKAMD_SCORE_FASTLADD | HTKAMD_SCORE_BF16 | HTKAMD_SCORE_F16 | HTKAMD_SCORE_SOUTP)) { htkamd_set_error("fb_execute: unknown score mode %d", cfg->scoreMode); return HTKAMD_EINVAL; }
+   if (cfg->scoreMode & ~(HTKAMD_SCORE_MFMA | HTKAMD_SCORE_FASTLADD | HTKAMD_SCORE_BF16 | HTKAMD_SCORE_F16 | HTKAMD_SCORE_SOUTP | HTKAMD_SCORE_DIAGC)) { htkamd_set_error("fb_execute: unknown score mode %d", cfg->scoreMode); return HTKAMD_EINVAL; }
    const bool fastLadd = (cfg->scoreMode & HTKAMD_SCORE_FASTLADD) != 0;
    FbArgs fa = fb_args(fb, cfg, accs);
    const LdsSizes lds = fb_lds_sizes(fa);
@@ -1123,5 +1123,13 @@ extern "C" int htkamd_fb_get_trellis(htkamd_fb *fb, int u, double *beta, double 
             for (int j = 2; j < mN[q - 1]; j++)
                outp[((size_t)t * Q + (q - 1)) * maxN + (j - 1)] = o[(size_t)(mS[q - 1] + j - 2) * T + t];
    }
+   return HTKAMD_OK;
+}
+
+// the last pass's results where they lie (internal.h): for csrc/hrest.hip, which sums them per model on the device
+int htkamd_fb_device_results(htkamd_fb *fb, htkamd_fb_dev *out)
+{
+   if (!fb || !out || fb->nUtt <= 0 || !fb->d_pr.p) { htkamd_set_error("fb_device_results: no pass to read"); return HTKAMD_EINVAL; }
+   out->pr = (const double *)fb->d_pr.p; out->status = (const int *)((const char *)fb->d_pr.p + fb->res().status());
    return HTKAMD_OK;
 }

@@ -29,6 +29,7 @@
 #include "hipcheck.h"
 #include "devbuf.h"
 #include "hinit_seg.h"
+#include "gauss_derive.h"
 
 #define HI_THREADS     256
 #define FC_MIN_CLUST   3                                  // MIN_CLUST_SIZE, HTrain.c:69
@@ -339,29 +340,10 @@ __global__ void k_hi_fill(HiArgs a)
 // 1/variance, gConst, the exact kernels' rows and the log weights of one model's Gaussians, by the whole workgroup (after a barrier)
 static __device__ void hi_derive(const HiArgs &a, const HiModel &m)
 {
-   const int D = a.D;
-   for (int s = 0; s < m.ne; s++) {
-      const int st = a.hmmState[m.st0 + s], c0 = a.stateCompOff[st], M = a.stateCompOff[st + 1] - c0;
-      for (int k = threadIdx.x; k < M; k += HI_THREADS) {
-         const int g = a.compGauss[c0 + k];
-         float *row = a.gparam + (size_t)g * a.PS;
-         float sum = a.logTpiD;
-         for (int d = 0; d < D; d++) {
-            const float v = a.var[(size_t)g * D + d];
-            float vc = v;
-            if (vc > 1.0E+30f) vc = 1.0E+30f;
-            if (vc < 1.0E-30f) vc = 1.0E-30f;
-            const float iv = __fdiv_rn(1.0f, vc);
-            a.ivar[(size_t)g * D + d] = iv;
-            row[2 * d] = a.mean[(size_t)g * D + d]; row[2 * d + 1] = iv;
-            const float z = ((double)v <= MINLARG) ? (float)LZERO : (float)log((double)v);
-            sum = __fadd_rn(sum, z);
-         }
-         a.gconst[g] = sum; row[2 * D] = sum;
-         const float w = a.compWeight[c0 + k];
-         a.compLogWt[c0 + k] = ((double)w < MINMIX) ? (float)LZERO : (float)log((double)w);
-      }
-   }
+   GaussTables g;
+   g.D = a.D; g.PS = a.PS; g.logTpiD = a.logTpiD; g.stateCompOff = a.stateCompOff; g.compGauss = a.compGauss;
+   g.mean = a.mean; g.var = a.var; g.compWeight = a.compWeight; g.ivar = a.ivar; g.gconst = a.gconst; g.gparam = a.gparam; g.compLogWt = a.compLogWt;
+   for (int s = 0; s < m.ne; s++) htkamd_derive_state(g, a.hmmState[m.st0 + s], HI_THREADS);
 }
 
 struct FcOut { const int *size; const float *centre, *var; const int *status, *cOff; };

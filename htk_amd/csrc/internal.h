@@ -84,6 +84,11 @@ int  htkamd_synth_dev_run(const htkamd_synth_job *job, unsigned char *answers, i
 typedef struct { const int *segStart, *segEnd; const double *total; const int *status; } htkamd_viterbi_dev;
 int  htkamd_viterbi_device_results(htkamd_viterbi *v, htkamd_viterbi_dev *out);
 
+/* ---- a forward-backward pass's results where they lie on the device (csrc/fb.hip), for csrc/hrest.hip: per utterance the log
+ * probability and the status word.  Valid until the handle is prepared again; written by the pass in stream order. */
+typedef struct { const double *pr; const int *status; } htkamd_fb_dev;
+int  htkamd_fb_device_results(htkamd_fb *fb, htkamd_fb_dev *out);
+
 /* device LAdd table: 4 intervals per unit of d over [minLogExp, 0] = [-23.03, 0], degree-10 Taylor rows (8 KB) */
 #define LADD_INV_H 4
 #define LADD_DEG   10

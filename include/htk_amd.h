@@ -448,7 +448,7 @@ int htkamd_outp_block(htkamd_model *m, const float *dX, int T, const int *dState
  * instead of ShStrP's / cSOutP's float after every component: what OutP / POutP / SOutP return to a direct caller (HRest, HInit).
  * Bit-identical to the reference's SOutP. */
 #define HTKAMD_SCORE_SOUTP 8
-/* htkamd_outp_block_mode only, may be or-ed with HTKAMD_SCORE_SOUTP: DOutP's form for DIAGC sets (HModel.c:5347: xmm*xmm/var, the float
+/* htkamd_outp_block_mode, htkamd_viterbi_align_mode and htkamd_fb_config.scoreMode; may be or-ed with HTKAMD_SCORE_SOUTP: DOutP's form for DIAGC sets (HModel.c:5347: xmm*xmm/var, the float
  * division) -- what MOutP dispatches to when the set has not been through ConvDiagC, as in HRest / HInit.  Bit-identical to DOutP. */
 #define HTKAMD_SCORE_DIAGC 16
 /* The expanded form on the FP16 matrix pipe, both operands split into TWO fp16 pieces (11 + 11 significant bits and the signs: fp32's 24)
@@ -626,7 +626,8 @@ typedef struct {
    double pruneInit, pruneInc, pruneLim;   /* HERest -t f [i l]; HTKAMD_NOPRUNE = off (HERest.c:121-123) */
    float  minFrwdP;                        /* HFB MINFORPROB / HERest -c, default 10.0 (HFB.c:83)        */
    int    uFlags;                          /* HTKAMD_UP* bits                                            */
-   int    scoreMode;                       /* HTKAMD_SCORE_EXACT (0, default), or HTKAMD_SCORE_MFMA | HTKAMD_SCORE_FASTLADD bits */
+   int    scoreMode;                       /* HTKAMD_SCORE_EXACT (0, default), or HTKAMD_SCORE_MFMA | HTKAMD_SCORE_FASTLADD bits; the EXACT
+                                              family's HTKAMD_SCORE_SOUTP | HTKAMD_SCORE_DIAGC for HRest's arithmetic (htkamd_hrest) */
 } htkamd_fb_config;
 
 typedef struct {
@@ -1266,6 +1267,67 @@ int htkamd_hinit_uniform_states(int nEmit, int nTokens, const int *tokLen, int *
    the workgroup's LDS (nc x D floats). */
 int htkamd_flat_cluster(const float *dX, int nRows, int D, int nPools, const int *poolOff, const int *items, const int *nc, float minVar,
                         int *size, float *centre, float *var, int *assign, int *status, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Isolated-unit Baum-Welch re-estimation: replaces HRest (HTKTools/HRest.c) for every model of a list in ONE call, on one-stream DIAGC
+ * continuous-density sets (csrc/hrest.hip; the checks and the token bookkeeping: host/hrest.c).
+ *   LoadFile (HRest.c:458)         tokens shorter than the model's emitting states are dropped once (segReject, :500), then the -m test
+ *                                  (main :295) on what is left
+ *   ReEstimateModel (:1309)        htkamd_hrest: per model the reference's loop, all models side by side.  A pass is ONE forward-backward
+ *                                  batch (htkamd_fb_*, no beam, MINFORPROB out of the way, HTKAMD_SCORE_SOUTP | HTKAMD_SCORE_DIAGC: what
+ *                                  OutP gives HRest) over every kept token of every model still running, one single-model utterance each;
+ *                                  the running tokens are listed on the device (count, scan, fill) and their rows gathered
+ *   ZeroAccs (HTrain.c)            once per pass, the running models' statistics only
+ *   newP (:1328)                   a lane per running model: the float sum of its usable tokens' log probabilities in token order and
+ *                                  their count ("Example skipped": a token whose alpha pass gives no more than LSMALL)
+ *   UpdateTheModel (:1287)         a workgroup per running model: RestTransP (:1015), RestMixWeights (:1124), RestMean (:1165) and
+ *                                  RestCoVar (:1185) of the components whose new weight exceeds MINMIX (floor first, then vDefunct),
+ *                                  FloorMixes (:1043); only what uFlags selects is re-estimated; then 1/variance, gConst, log weights and
+ *                                  the scoring rows of the model's Gaussians are rebuilt in place.  As in the reference the model is
+ *                                  updated in every pass, the one that meets epsilon included
+ * The host reads one (log probability sum, tokens used, status) triple per running model per pass and decides as the reference does:
+ * newP = sum / used in float, delta = newP - oldP with oldP starting at LZERO, stop on |delta| < epsilon or after maxIter passes.  A model
+ * that has stopped is frozen: later passes neither score its tokens nor touch its parameters.
+ * Tokens as for htkamd_hinit.  Per model: status[k] (HTKAMD_HREST_*; a model with a status other than OK keeps exactly the parameters it
+ * came with), nPass[k], converged[k], logP[k * maxIter + pass] ("Ave LogProb at iter") and nUsed[k * maxIter + pass] ("using N examples").
+ * Every other model is trained as if it had been called alone.  A defunct component (the reference's warning -2225: a floored variance
+ * below vDefunct in a state of several components) gets weight 0 and the model goes on.
+ * Refused before a device is touched (HTKAMD_EMODEL / HTKAMD_EINVAL and the reason): FULLC, tied-mixture, multi-stream and discrete sets;
+ * models to be trained that use a state, a Gaussian or a transition matrix twice, among or within them; a model named twice or out of
+ * range; a token outside the table or of an unknown model; maxIter < 1, minSeg < 1 -- htkamd_hrest_check is exactly these checks on a
+ * set's description.  A description does not say which mean / variance vectors are tied, so the refusal of ~u / ~v sharing
+ * (htkamd_model_set_sharing) is htkamd_hrest's own, on the handle, also before the call looks for a device.  minVar is the floor of every
+ * dimension (SetVFloor without a varFloor1 macro).
+ * On return the device arrays hold the estimates, the derived tables follow as after htkamd_model_update_device, and the host mirror
+ * is current.  Synchronises `stream`.  A call that ends in an error (a negative return: a failed allocation, a HIP error) puts every model
+ * of the call back to the parameters it came with before it returns; status / nPass / converged / logP / nUsed are then undefined.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct {
+   int   maxIter;          /* -i, 20                                                                               */
+   float epsilon;          /* -e, 1.0e-4                                                                           */
+   float minVar;           /* -v, 0.0                                                                              */
+   int   minSeg;           /* -m, 3                                                                                */
+   float mixWeightFloor;   /* -w f: MINMIX * f -- HRest DOES floor continuous weights (FloorMixes HRest.c:1043)    */
+   int   uFlags;           /* -u: HTKAMD_UPMEANS | _UPVARS | _UPTRANS | _UPMIXES                                   */
+   int   segReject;        /* 1 (default): drop tokens shorter than the model's emitting states; 0: -t             */
+   float vDefunct;         /* HREST: VDEFUNCT, 0.0                                                                 */
+} htkamd_hrest_config;
+#define HTKAMD_HREST_OK         0
+#define HTKAMD_HREST_EFEWSEGS   2221   /* fewer than minSeg tokens after the short ones were dropped            */
+#define HTKAMD_HREST_EZEROOCC   2222   /* zero occupation of a state, a mean, a variance or a weight set        */
+#define HTKAMD_HREST_EFLOORSUM  2223   /* FloorMixes: floor sum too large                                       */
+#define HTKAMD_HREST_ENOUSABLE  2226   /* a pass in which no token was usable                                   */
+int htkamd_hrest_check(const htkamd_model_desc *d, int nFrames, int nTokens, const int *tokFrame, const int *tokLen, const int *tokModel,
+                       const htkamd_hrest_config *cfg, int nModels, const int *models);
+int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int nTokens, const int *tokFrame, const int *tokLen, const int *tokModel,
+                 const htkamd_hrest_config *cfg, int nModels, const int *models,
+                 int *status /*[nModels]*/, int *nPass /*[nModels]*/, int *converged /*[nModels]*/, float *logP /*[nModels * maxIter]*/,
+                 int *nUsed /*[nModels * maxIter]*/, void *stream);
+/* The token bookkeeping of LoadFile and main on the host, as the call does it (needs no device): hmmStateOff [numPhys + 1] as in
+   htkamd_model_desc; keep[k] (may be NULL) = 1 for a token of a listed model that is not dropped, nKept[m] the kept tokens of
+   models[m], status[m] = HTKAMD_HREST_EFEWSEGS where they are fewer than minSeg, else HTKAMD_HREST_OK. */
+int htkamd_hrest_token_counts(const int *hmmStateOff, int numPhys, int nTokens, const int *tokLen, const int *tokModel, const htkamd_hrest_config *cfg,
+                              int nModels, const int *models, int *keep /*[nTokens]*/, int *nKept /*[nModels]*/, int *status /*[nModels]*/);
 
 #ifdef __cplusplus
 }
