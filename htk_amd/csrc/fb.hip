@@ -257,7 +257,11 @@ static int prep_utterance(htkamd_fb *fb, const htkamd_batch_desc *b, int u, Prep
       d.outp0 = C.outp; d.beta0 = C.beta; d.gam0 = C.gam;
       unsigned char &flags = fb->uttFlags[u];
       flags = UTT_NO_TEE | UTT_ALL_LR;              // (until a model of the chain says otherwise)
-      if (T <= 0 || Q <= 0) { d.status = HTKAMD_UTT_SKIPPED; d.nCells = d.nSlots = 0; d.thr0 = (int)C.thrCell.size(); d.nThr = 0; return HTKAMD_OK; }
+      if (T <= 0 || Q <= 0) {
+         // (frames without a transcription: the per-frame words are cleared as for every utterance that stops below)
+         for (int t = 0; t < T; t++) { fb->taperLo[d.frame0 + t] = 0; fb->taperHi[d.frame0 + t] = 0; fb->qBeamNP[d.frame0 + t] = 1; }
+         d.status = HTKAMD_UTT_SKIPPED; d.nCells = d.nSlots = 0; d.thr0 = (int)C.thrCell.size(); d.nThr = 0; return HTKAMD_OK;
+      }
       int nCells = 0, nSlots = 0, qt = 0, prevDm = 1;
       for (int q = 1; q <= Q; q++) {
          const int h = labs[q - 1];
