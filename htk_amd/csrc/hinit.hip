@@ -1,5 +1,7 @@
 // hinit.hip -- Viterbi training from labelled tokens (HTKTools/HInit.c) for every model of a list in one call, and FlatCluster
-// (HTKLib/HTrain.c:763) for any number of pools in one launch.  The refusals and the host twin of the pool listing: host/hinit.c.
+// (HTKLib/HTrain.c:763) for any number of pools in one launch.  The refusals and the host twin of the pool listing: host/hinit.c.  What the
+// call shares with htkamd_hrest -- the model / token tables, the snapshot and k_unit_restore, the block scan, the gather, the float
+// transition row, the way out of the call, an error's included -- is unit_train.h; here is HInit's own arithmetic.
 //
 // k_hi_count / k_hi_scan / k_hi_pooloff / k_hi_fill: UCollectData (HInit.c:505).  A pool is the frames of one (model, emitting state) in
 //   token order, then frame order; the states of a token's frames never decrease, so a token's share of a pool is one run of rows:
@@ -18,8 +20,8 @@
 //   htkamd_viterbi_align_mode call; k_hi_logp: a lane per model, the float sum of its tokens' log probabilities in token order;
 //   k_hi_best: a lane per frame, FindBestMixes (:739); k_hi_acc: a wavefront per (token, state) segment, UpdateCounts (:878) into fp64
 //   sums with atomic adds (lanes are dimensions; a run of frames with the same component is summed in registers first); k_hi_update: a
-//   workgroup per model, UpWeights / UpMeans / UpVars / UpTrans (:997-1097).  hi_derive rebuilds 1/variance (ConvDiagC HUtil.c:413),
-//   gConst (FixDiagGConst HModel.c:5641), log weights (MixLogWeight :5288) and the exact kernels' rows for the model's Gaussians.
+//   workgroup per model, UpWeights / UpMeans / UpVars / UpTrans (:997-1097).  Whoever writes a model's parameters rebuilds the derived
+//   tables of its Gaussians behind a barrier (gauss_derive.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdlib.h>
@@ -27,9 +29,8 @@
 #include <vector>
 #include "internal.h"
 #include "hipcheck.h"
-#include "devbuf.h"
 #include "hinit_seg.h"
-#include "gauss_derive.h"
+#include "unit_train.h"
 
 #define HI_THREADS     256
 #define FC_MIN_CLUST   3                                  // MIN_CLUST_SIZE, HTrain.c:69
@@ -174,15 +175,6 @@ __global__ __launch_bounds__(HI_THREADS) void k_flat_cluster(FcArgs a)
 namespace {
 constexpr char hiOwner[] = "hinit";
 typedef DevBufT<hiOwner> DevBuf;
-
-template <typename T> int hi_upload(DevBuf &b, const T *src, size_t n, hipStream_t s)
-{
-   const int rc = b.reserve(sizeof(T) * (n ? n : 1));
-   if (rc) return rc;
-   if (n) HIPCHECK(hipMemcpyAsync(b.p, src, sizeof(T) * n, hipMemcpyHostToDevice, s));
-   return HTKAMD_OK;
-}
-template <typename T> int hi_upload(DevBuf &b, const std::vector<T> &v, hipStream_t s) { return hi_upload(b, v.data(), v.size(), s); }
 }
 
 static size_t fc_lds_bytes(int nc, int D) { return sizeof(float) * (size_t)nc * D + (sizeof(float) + sizeof(int)) * (size_t)nc; }
@@ -208,8 +200,8 @@ extern "C" int htkamd_flat_cluster(const float *dX, int nRows, int D, int nPools
    hipStream_t s = (hipStream_t)stream;
    DevBuf dOff, dItems, dNc, dCOff, dSize, dCtr, dVar, dAssign, dCost, dStatus;
    int rc;
-   if ((rc = hi_upload(dOff, poolOff, (size_t)nPools + 1, s)) || (rc = hi_upload(dItems, items, (size_t)nItems, s)) || (rc = hi_upload(dNc, nc, (size_t)nPools, s)) ||
-       (rc = hi_upload(dCOff, cOff, s)) || (rc = dSize.reserve(sizeof(int) * (size_t)nClust)) || (rc = dCtr.reserve(sizeof(float) * (size_t)nClust * D)) ||
+   if ((rc = unit_upload(dOff, poolOff, (size_t)nPools + 1, s)) || (rc = unit_upload(dItems, items, (size_t)nItems, s)) || (rc = unit_upload(dNc, nc, (size_t)nPools, s)) ||
+       (rc = unit_upload(dCOff, cOff, s)) || (rc = dSize.reserve(sizeof(int) * (size_t)nClust)) || (rc = dCtr.reserve(sizeof(float) * (size_t)nClust * D)) ||
        (rc = dVar.reserve(sizeof(float) * (size_t)nClust * D)) || (rc = dAssign.reserve(sizeof(int) * (size_t)(nItems ? nItems : 1))) ||
        (rc = dCost.reserve(sizeof(float) * (size_t)(nItems ? nItems : 1))) || (rc = dStatus.reserve(sizeof(int) * (size_t)nPools)))
       return rc;
@@ -233,18 +225,13 @@ extern "C" int htkamd_flat_cluster(const float *dX, int nRows, int D, int nPools
 }
 
 // ------------------------------------------------------------------------------------------ HInit: tables
-struct HiModel { int h, ne, N, tok0, nTok, pool0, tp0, st0, occ0; };      // tp0: first element of its transition matrix; st0: of its state list; occ0: of its row counts
-
 struct HiArgs {
-   // the model's arrays
-   int D, PS, uFlags;
-   float minVar, logTpiD;
-   const int *stateCompOff, *compGauss, *hmmState;
-   float *mean, *var, *ivar, *gconst, *gparam, *compWeight, *compLogWt, *transP;
-   const float *bakMean, *bakVar, *bakWeight, *bakTransP;
+   UnitParams p;                                           // the model's arrays and their snapshot
+   int uFlags;
+   float minVar;
    // the call's
    const float *X;
-   const HiModel *mdl; int nMdl, maxNe;
+   const UnitModel *mdl; int nMdl, maxNe;
    const int *tokFrame, *tokLen, *tokMdl; int nTok;
    int *tokCnt, *tokPos;                                   // [nTok][maxNe]
    const int *poolMdl, *poolState; int nPools;
@@ -263,23 +250,6 @@ struct HiArgs {
    float *logpOut; int *statOut;                           // [nRun]
 };
 
-static __device__ int hi_block_excl_scan(int v, int *lds, int *total)
-{
-   const int t = threadIdx.x;
-   lds[t] = v;
-   __syncthreads();
-   for (int o = 1; o < HI_THREADS; o <<= 1) {
-      const int x = t >= o ? lds[t - o] : 0;
-      __syncthreads();
-      lds[t] += x;
-      __syncthreads();
-   }
-   const int incl = lds[t];
-   *total = lds[HI_THREADS - 1];
-   __syncthreads();
-   return incl - v;
-}
-
 __global__ void k_hi_count(HiArgs a)
 {
    const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -294,13 +264,13 @@ __global__ __launch_bounds__(HI_THREADS) void k_hi_scan(HiArgs a)
 {
    __shared__ int lds[HI_THREADS];
    const int p = blockIdx.x, s = a.poolState[p];
-   const HiModel m = a.mdl[a.poolMdl[p]];
+   const UnitModel m = a.mdl[a.poolMdl[p]];
    int base = 0;
    for (int k0 = 0; k0 < m.nTok; k0 += HI_THREADS) {
       const int k = k0 + threadIdx.x;
       const int v = k < m.nTok ? a.tokCnt[(size_t)(m.tok0 + k) * a.maxNe + s] : 0;
       int tot;
-      const int ex = hi_block_excl_scan(v, lds, &tot);
+      const int ex = unit_block_excl_scan<HI_THREADS>(v, lds, &tot);
       if (k < m.nTok) a.tokPos[(size_t)(m.tok0 + k) * a.maxNe + s] = base + ex;
       base += tot;
    }
@@ -315,7 +285,7 @@ __global__ __launch_bounds__(HI_THREADS) void k_hi_pooloff(HiArgs a)
       const int p = p0 + threadIdx.x;
       const int v = p < a.nPools ? a.poolSize[p] : 0;
       int tot;
-      const int ex = hi_block_excl_scan(v, lds, &tot);
+      const int ex = unit_block_excl_scan<HI_THREADS>(v, lds, &tot);
       if (p < a.nPools) a.poolOff[p] = base + ex;
       base += tot;
    }
@@ -326,7 +296,7 @@ __global__ void k_hi_fill(HiArgs a)
 {
    const int k = blockIdx.x * blockDim.x + threadIdx.x;
    if (k >= a.nTok) return;
-   const HiModel m = a.mdl[a.tokMdl[k]];
+   const UnitModel m = a.mdl[a.tokMdl[k]];
    const int L = a.tokLen[k], f0 = a.tokFrame[k];
    const int *pos = a.tokPos + (size_t)k * a.maxNe;
    int prev = -1, run = 0;
@@ -337,46 +307,34 @@ __global__ void k_hi_fill(HiArgs a)
    }
 }
 
-// 1/variance, gConst, the exact kernels' rows and the log weights of one model's Gaussians, by the whole workgroup (after a barrier)
-static __device__ void hi_derive(const HiArgs &a, const HiModel &m)
-{
-   GaussTables g;
-   g.D = a.D; g.PS = a.PS; g.logTpiD = a.logTpiD; g.stateCompOff = a.stateCompOff; g.compGauss = a.compGauss;
-   g.mean = a.mean; g.var = a.var; g.compWeight = a.compWeight; g.ivar = a.ivar; g.gconst = a.gconst; g.gparam = a.gparam; g.compLogWt = a.compLogWt;
-   for (int s = 0; s < m.ne; s++) htkamd_derive_state(g, a.hmmState[m.st0 + s], HI_THREADS);
-}
-
 struct FcOut { const int *size; const float *centre, *var; const int *status, *cOff; };
 
 __global__ __launch_bounds__(HI_THREADS) void k_hi_init(HiArgs a, FcOut f)
 {
-   const HiModel m = a.mdl[blockIdx.x];
-   const int D = a.D, t = threadIdx.x;
+   const UnitModel m = a.mdl[blockIdx.x];
+   const int D = a.p.g.D, t = threadIdx.x;
    bool fail = false;
    for (int s = 0; s < m.ne; s++) if (f.status[m.pool0 + s] != HTKAMD_HINIT_OK) fail = true;
    if (fail) { if (t == 0) a.mstatus[blockIdx.x] = HTKAMD_HINIT_ECLUSTER; return; }
    for (int s = 0; s < m.ne; s++) {
-      const int p = m.pool0 + s, st = a.hmmState[m.st0 + s], c0 = a.stateCompOff[st], M = a.stateCompOff[st + 1] - c0, k0 = f.cOff[p];
+      const int p = m.pool0 + s, st = a.p.hmmState[m.st0 + s], c0 = a.p.g.stateCompOff[st], M = a.p.g.stateCompOff[st + 1] - c0, k0 = f.cOff[p];
       const int n = a.poolOff[p + 1] - a.poolOff[p];
       for (int e = t; e < M * D; e += HI_THREADS) {
-         const int k = e / D, d = e - k * D, g = a.compGauss[c0 + k];
-         if (a.uFlags & HTKAMD_UPMEANS) a.mean[(size_t)g * D + d] = f.centre[(size_t)k0 * D + e];
-         if (a.uFlags & HTKAMD_UPVARS) a.var[(size_t)g * D + d] = f.var[(size_t)k0 * D + e];
+         const int k = e / D, d = e - k * D, g = a.p.g.compGauss[c0 + k];
+         if (a.uFlags & HTKAMD_UPMEANS) a.p.mean[(size_t)g * D + d] = f.centre[(size_t)k0 * D + e];
+         if (a.uFlags & HTKAMD_UPVARS) a.p.var[(size_t)g * D + d] = f.var[(size_t)k0 * D + e];
       }
-      if (a.uFlags & HTKAMD_UPMIXES) for (int k = t; k < M; k += HI_THREADS) a.compWeight[c0 + k] = __fdiv_rn((float)f.size[k0 + k], (float)n);
+      if (a.uFlags & HTKAMD_UPMIXES) for (int k = t; k < M; k += HI_THREADS) a.p.compWeight[c0 + k] = __fdiv_rn((float)f.size[k0 + k], (float)n);
    }
    __syncthreads();
-   hi_derive(a, m);
+   for (int s = 0; s < m.ne; s++) htkamd_derive_state(a.p.g, a.p.hmmState[m.st0 + s], HI_THREADS);
 }
 
 // ------------------------------------------------------------------------------------------ HInit: a pass
 __global__ __launch_bounds__(HI_THREADS) void k_hi_gather(HiArgs a)
 {
-   const int u = blockIdx.x, D = a.D;
-   const size_t n = (size_t)(a.uFrame0[u + 1] - a.uFrame0[u]) * D;
-   const float *src = a.X + (size_t)a.uSrc[u] * D;
-   float *dst = a.Xg + (size_t)a.uFrame0[u] * D;
-   for (size_t e = threadIdx.x; e < n; e += HI_THREADS) dst[e] = src[e];
+   const int u = blockIdx.x, D = a.p.g.D;
+   unit_gather_rows<HI_THREADS>(a.Xg + (size_t)a.uFrame0[u] * D, a.X + (size_t)a.uSrc[u] * D, (size_t)(a.uFrame0[u + 1] - a.uFrame0[u]) * D);
 }
 
 __global__ void k_hi_logp(HiArgs a)
@@ -403,21 +361,21 @@ __global__ void k_hi_best(HiArgs a)
    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (a.uFrame0[mid] <= f) lo = mid; else hi = mid - 1; }
    const int u = lo, r = a.uMdl[u];
    if (!a.updFlag[r]) return;
-   const HiModel m = a.mdl[r];
-   const int tl = f - a.uFrame0[u], D = a.D;
+   const UnitModel m = a.mdl[r];
+   const int tl = f - a.uFrame0[u], D = a.p.g.D;
    int j = -1;
    for (int s = 0; s < m.ne; s++) { const int st = a.segStart[a.uSeg0[u] + s]; if (st >= 0 && st <= tl && tl < a.segEnd[a.uSeg0[u] + s]) j = s; }
    int comp = -1;
    if (j >= 0) {
-      const int st = a.hmmState[m.st0 + j], c0 = a.stateCompOff[st], M = a.stateCompOff[st + 1] - c0;
+      const int st = a.p.hmmState[m.st0 + j], c0 = a.p.g.stateCompOff[st], M = a.p.g.stateCompOff[st + 1] - c0;
       if (M == 1) comp = c0;
       else {
          const float *x = a.Xg + (size_t)f * D;
          float bestP = (float)LZERO; int best = -1;
          for (int k = 0; k < M; k++) {
-            const int g = a.compGauss[c0 + k];
-            const float *mu = a.mean + (size_t)g * D, *va = a.var + (size_t)g * D;
-            float sum = a.gconst[g];
+            const int g = a.p.g.compGauss[c0 + k];
+            const float *mu = a.p.mean + (size_t)g * D, *va = a.p.var + (size_t)g * D;
+            float sum = a.p.g.gconst[g];
             for (int d = 0; d < D; d++) { const float xmm = __fsub_rn(x[d], mu[d]); sum = __fadd_rn(sum, __fdiv_rn(__fmul_rn(xmm, xmm), va[d])); }
             const float pr = __fmul_rn(-0.5f, sum);
             if (pr > bestP) { bestP = pr; best = k; }
@@ -436,8 +394,8 @@ __global__ __launch_bounds__(HI_THREADS) void k_hi_acc(HiArgs a)
    if (w >= a.nSeg) return;
    const int u = a.segUtt[w], j = a.segJ[w], r = a.uMdl[u];
    if (!a.updFlag[r]) return;
-   const HiModel m = a.mdl[r];
-   const int D = a.D, st = a.segStart[w], en = a.segEnd[w], f0 = a.uFrame0[u];
+   const UnitModel m = a.mdl[r];
+   const int D = a.p.g.D, st = a.segStart[w], en = a.segEnd[w], f0 = a.uFrame0[u];
    if (st >= 0 && (a.uFlags & (HTKAMD_UPMEANS | HTKAMD_UPVARS | HTKAMD_UPMIXES)))
       for (int d0 = 0; d0 < D; d0 += 64) {
          const int d = d0 + lane;
@@ -452,7 +410,7 @@ __global__ __launch_bounds__(HI_THREADS) void k_hi_acc(HiArgs a)
                   if (d == 0) atomicAdd(a.accCnt + cur, run);
                }
                cur = c; run = 0; sm = 0.0; sv = 0.0;
-               if (c >= 0) { g = a.compGauss[c]; mu = d < D ? a.mean[(size_t)g * D + d] : 0.0f; }
+               if (c >= 0) { g = a.p.g.compGauss[c]; mu = d < D ? a.p.mean[(size_t)g * D + d] : 0.0f; }
             }
             if (c >= 0) {
                if (d < D) { const double x = (double)__fsub_rn(a.Xg[(size_t)f * D + d], mu); sm += x; sv += x * x; }
@@ -477,11 +435,11 @@ __global__ __launch_bounds__(HI_THREADS) void k_hi_acc(HiArgs a)
 // UpdateParameters: a workgroup per model
 __global__ __launch_bounds__(HI_THREADS) void k_hi_update(HiArgs a)
 {
-   const int r = a.updList[blockIdx.x], t = threadIdx.x, D = a.D;
-   const HiModel m = a.mdl[r];
+   const int r = a.updList[blockIdx.x], t = threadIdx.x, D = a.p.g.D;
+   const UnitModel m = a.mdl[r];
    bool fail = a.mstatus[r] != HTKAMD_HINIT_OK;
    for (int s = 0; s < m.ne && !fail; s++) {
-      const int st = a.hmmState[m.st0 + s], c0 = a.stateCompOff[st], M = a.stateCompOff[st + 1] - c0;
+      const int st = a.p.hmmState[m.st0 + s], c0 = a.p.g.stateCompOff[st], M = a.p.g.stateCompOff[st + 1] - c0;
       int tot = 0;
       for (int k = 0; k < M; k++) {
          const int n = a.accCnt[c0 + k];
@@ -493,58 +451,31 @@ __global__ __launch_bounds__(HI_THREADS) void k_hi_update(HiArgs a)
    if (a.uFlags & HTKAMD_UPTRANS) for (int i = 1; i < m.N && !fail; i++) if (a.occCnt[m.occ0 + i - 1] == 0) fail = true;     // UpTrans: zero occ
    if (fail) { if (t == 0) atomicCAS(a.mstatus + r, HTKAMD_HINIT_OK, HTKAMD_HINIT_EZEROOCC); return; }
    for (int s = 0; s < m.ne; s++) {
-      const int st = a.hmmState[m.st0 + s], c0 = a.stateCompOff[st], M = a.stateCompOff[st + 1] - c0;
+      const int st = a.p.hmmState[m.st0 + s], c0 = a.p.g.stateCompOff[st], M = a.p.g.stateCompOff[st + 1] - c0;
       if (a.uFlags & (HTKAMD_UPMEANS | HTKAMD_UPVARS))
          for (int e = t; e < M * D; e += HI_THREADS) {
-            const int k = e / D, d = e - k * D, g = a.compGauss[c0 + k];
-            const double occ = (double)a.accCnt[c0 + k], old = (double)a.mean[(size_t)g * D + d];
+            const int k = e / D, d = e - k * D, g = a.p.g.compGauss[c0 + k];
+            const double occ = (double)a.accCnt[c0 + k], old = (double)a.p.mean[(size_t)g * D + d];
             const double nm = old + a.accMu[(size_t)g * D + d] / occ;
             const double x = (a.uFlags & HTKAMD_UPMEANS) ? nm - old : 0.0;
             if (a.uFlags & HTKAMD_UPVARS) {
                const float z = (float)(a.accVa[(size_t)g * D + d] / occ - x * x);
-               a.var[(size_t)g * D + d] = z < a.minVar ? a.minVar : z;
+               a.p.var[(size_t)g * D + d] = z < a.minVar ? a.minVar : z;
             }
-            if (a.uFlags & HTKAMD_UPMEANS) a.mean[(size_t)g * D + d] = (float)nm;
+            if (a.uFlags & HTKAMD_UPMEANS) a.p.mean[(size_t)g * D + d] = (float)nm;
          }
       if (M > 1 && (a.uFlags & HTKAMD_UPMIXES)) {
          int tot = 0;
          for (int k = 0; k < M; k++) tot += a.accCnt[c0 + k];
-         for (int k = t; k < M; k += HI_THREADS) a.compWeight[c0 + k] = __fdiv_rn((float)a.accCnt[c0 + k], (float)tot);
+         for (int k = t; k < M; k += HI_THREADS) a.p.compWeight[c0 + k] = __fdiv_rn((float)a.accCnt[c0 + k], (float)tot);
       }
    }
-   if ((a.uFlags & HTKAMD_UPTRANS) && t >= 1 && t < m.N) {             // UpTrans: row t, renormalised, logged
-      const int i = t, N = m.N;
-      float *row = a.transP + m.tp0 + (i - 1) * N;
-      const float occi = (float)a.occCnt[m.occ0 + i - 1];
-      float sum = 0.0f;
-      for (int j = 2; j <= N; j++) sum = __fadd_rn(sum, __fdiv_rn((float)a.trCnt[m.tp0 + (i - 1) * N + j - 1], occi));
-      row[0] = (float)LZERO;
-      for (int j = 2; j <= N; j++) {
-         const float x = __fdiv_rn(__fdiv_rn((float)a.trCnt[m.tp0 + (i - 1) * N + j - 1], occi), sum);
-         row[j - 1] = ((double)x < MINLARG) ? (float)LZERO : (float)log((double)x);
-      }
+   if ((a.uFlags & HTKAMD_UPTRANS) && t >= 1 && t < m.N) {             // UpTrans: row t from the integer counts
+      const int *cnt = a.trCnt + m.tp0 + (t - 1) * m.N;
+      unit_trans_row(a.p.transP + m.tp0 + (t - 1) * m.N, m.N, [cnt](int j) { return (float)cnt[j]; }, (float)a.occCnt[m.occ0 + t - 1]);
    }
    __syncthreads();
-   hi_derive(a, m);
-}
-
-// a model that ended with a status takes back the parameters it came with
-__global__ __launch_bounds__(HI_THREADS) void k_hi_restore(HiArgs a)
-{
-   const int r = blockIdx.x, t = threadIdx.x, D = a.D;
-   if (a.mstatus[r] == HTKAMD_HINIT_OK) return;
-   const HiModel m = a.mdl[r];
-   for (int s = 0; s < m.ne; s++) {
-      const int st = a.hmmState[m.st0 + s], c0 = a.stateCompOff[st], M = a.stateCompOff[st + 1] - c0;
-      for (int e = t; e < M * D; e += HI_THREADS) {
-         const size_t x = (size_t)a.compGauss[c0 + e / D] * D + e % D;
-         a.mean[x] = a.bakMean[x]; a.var[x] = a.bakVar[x];
-      }
-      for (int k = t; k < M; k += HI_THREADS) a.compWeight[c0 + k] = a.bakWeight[c0 + k];
-   }
-   for (int e = t; e < m.N * m.N; e += HI_THREADS) a.transP[m.tp0 + e] = a.bakTransP[m.tp0 + e];
-   __syncthreads();
-   hi_derive(a, m);
+   for (int s = 0; s < m.ne; s++) htkamd_derive_state(a.p.g, a.p.hmmState[m.st0 + s], HI_THREADS);
 }
 
 // ------------------------------------------------------------------------------------------ HInit: the call
@@ -553,18 +484,9 @@ extern "C" int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int n
                             int *status, int *nPass, int *converged, float *logP, void *stream)
 {
    if (!m || !cfg || !status || !nPass || !converged || !logP) { htkamd_set_error("hinit: NULL argument"); return HTKAMD_EINVAL; }
-   if (m->fullc) { htkamd_set_error("hinit: a FULLC set (HInit on full covariances is not supported)"); return HTKAMD_EMODEL; }
-   if (m->h_meanLeader) { htkamd_set_error("hinit: a set with shared mean / variance vectors (~u / ~v)"); return HTKAMD_EMODEL; }
-   if (m->h_rawLogWt) { htkamd_set_error("hinit: HTKAMD_COMPAT_SHARED_LOGWT is set (mixtures that share pdfs)"); return HTKAMD_EMODEL; }
    int rc;
-   {  // the refusals, on the description the model was made from
-      htkamd_model_desc d;
-      memset(&d, 0, sizeof(d));
-      d.vecSize = m->D; d.numStates = m->S / m->NSt; d.numComp = m->C; d.numGauss = m->G; d.numTrans = m->nT; d.numPhys = m->H;
-      d.stateCompOff = m->h_stateCompOff; d.compGauss = m->h_compGauss; d.var = m->h_var; d.hmmTrans = m->h_hmmTrans;
-      d.hmmStateOff = m->h_hmmStateOff; d.hmmState = m->h_hmmState; d.numStreams = m->NSt; d.hsKind = m->tiedMix ? HTKAMD_HS_TIED : HTKAMD_HS_PLAIN;
-      if ((rc = htkamd_hinit_check(&d, nFrames, nTokens, tokFrame, tokLen, tokModel, cfg, nModels, models))) return rc;
-   }
+   htkamd_model_desc d;
+   if ((rc = unit_refuse_handle(m, "hinit", "HInit", &d)) || (rc = htkamd_hinit_check(&d, nFrames, nTokens, tokFrame, tokLen, tokModel, cfg, nModels, models))) return rc;
    if (!dX && nTokens > 0) { htkamd_set_error("hinit: no feature table"); return HTKAMD_EINVAL; }
    if (htkamd_device_count() <= 0) { htkamd_set_error("hinit: no HIP device"); return HTKAMD_ENODEV; }
    hipStream_t s = (hipStream_t)stream;
@@ -573,38 +495,33 @@ extern "C" int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int n
    for (size_t i = 0; i < (size_t)nModels * maxIter; i++) logP[i] = 0.0f;
 
    // ---- the models that can be trained, their tokens behind one another (the given order within a model), their pools
-   std::vector<int> ofPhys((size_t)m->H, -1);
-   for (int k = 0; k < nModels; k++) ofPhys[models[k]] = k;
-   std::vector<std::vector<int>> toks((size_t)nModels);
-   for (int k = 0; k < nTokens; k++) if (ofPhys[tokModel[k]] >= 0) toks[ofPhys[tokModel[k]]].push_back(k);
-   std::vector<HiModel> mdl; std::vector<int> mdlOf;                       // mdlOf[r] = its place in `models`
-   std::vector<int> aFrame, aLen, aMdl, poolMdl, poolState, poolNc, cOff(1, 0);
+   UnitTables tb;
+   std::vector<int> poolMdl, poolState, poolNc, cOff(1, 0);
    int maxNe = 1, maxNc = 1;
-   for (int k = 0; k < nModels; k++) {
-      const int h = models[k], ti = m->h_hmmTrans[h], N = m->h_transN[ti], ne = N - 2;
-      if ((int)toks[k].size() < cfg->minSeg) { status[k] = HTKAMD_HINIT_EFEWSEGS; continue; }
-      bool tooShort = false;
-      for (int t : toks[k]) if (tokLen[t] < ne) tooShort = true;
-      if (tooShort || ne < 1) { status[k] = HTKAMD_HINIT_ESHORT; continue; }
-      HiModel x;
-      x.h = h; x.ne = ne; x.N = N; x.tok0 = (int)aFrame.size(); x.nTok = (int)toks[k].size(); x.pool0 = (int)poolMdl.size();
-      x.tp0 = m->h_transOff[ti]; x.st0 = m->h_hmmStateOff[h]; x.occ0 = m->h_trOccOff[ti];
-      for (int t : toks[k]) { aFrame.push_back(tokFrame[t]); aLen.push_back(tokLen[t]); aMdl.push_back((int)mdl.size()); }
-      for (int j = 0; j < ne; j++) {
-         const int st = m->h_hmmState[x.st0 + j], M = m->h_stateCompOff[st + 1] - m->h_stateCompOff[st];
-         if (M > FC_MAX_NC || fc_lds_bytes(M, D) > FC_MAX_LDS) { htkamd_set_error("hinit: state %d of model %d has %d components of %d values: more than a workgroup clusters", j + 2, h, M, D); return HTKAMD_EMODEL; }
-         poolMdl.push_back((int)mdl.size()); poolState.push_back(j); poolNc.push_back(M); cOff.push_back(cOff.back() + M);
-         if (M > maxNc) maxNc = M;
-      }
-      if (ne > maxNe) maxNe = ne;
-      mdl.push_back(x); mdlOf.push_back(k);
-   }
+   rc = unit_tables("hinit", m, nTokens, tokFrame, tokLen, tokModel, nullptr, nModels, models,
+      [&](int k, int ne, const std::vector<int> &toks) {                   // main :276 (-m), UCollectData :516
+         if ((int)toks.size() < cfg->minSeg) { status[k] = HTKAMD_HINIT_EFEWSEGS; return false; }
+         bool tooShort = false;
+         for (int t : toks) if (tokLen[t] < ne) tooShort = true;
+         if (tooShort || ne < 1) { status[k] = HTKAMD_HINIT_ESHORT; return false; }
+         return true;
+      },
+      [&](UnitModel &x, int r) -> int {                                    // a pool per emitting state
+         x.pool0 = (int)poolMdl.size();
+         for (int j = 0; j < x.ne; j++) {
+            const int st = m->h_hmmState[x.st0 + j], M = m->h_stateCompOff[st + 1] - m->h_stateCompOff[st];
+            if (M > FC_MAX_NC || fc_lds_bytes(M, D) > FC_MAX_LDS) { htkamd_set_error("hinit: state %d of model %d has %d components of %d values: more than a workgroup clusters", j + 2, x.h, M, D); return HTKAMD_EMODEL; }
+            poolMdl.push_back(r); poolState.push_back(j); poolNc.push_back(M); cOff.push_back(cOff.back() + M);
+            if (M > maxNc) maxNc = M;
+         }
+         if (x.ne > maxNe) maxNe = x.ne;
+         return HTKAMD_OK;
+      }, tb);
+   if (rc || tb.mdl.empty()) return rc;
+   const std::vector<UnitModel> &mdl = tb.mdl;
+   const std::vector<int> &mdlOf = tb.mdlOf, &aFrame = tb.aFrame, &aLen = tb.aLen;
+   const long long totFrames = tb.totFrames;
    const int nMdl = (int)mdl.size(), nTok = (int)aFrame.size(), nPools = (int)poolMdl.size(), nClust = cOff.back();
-   if (nMdl == 0) return HTKAMD_OK;
-   long long totFrames = 0;
-   for (int L : aLen) totFrames += L;
-   if (totFrames >= ((long long)1 << 31)) { htkamd_set_error("hinit: %lld frames in the tokens (the tables index with 32 bits)", totFrames); return HTKAMD_EINVAL; }
-   if ((rc = htkamd_model_sync_host(m)) || (rc = htkamd_model_device_tables(m))) return rc;
 
    htkamd_viterbi *vit = nullptr;
    if ((rc = htkamd_viterbi_create(m, &vit))) return rc;
@@ -613,30 +530,20 @@ extern "C" int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int n
    DevBuf bMdl, bTokFrame, bTokLen, bTokMdl, bTokCnt, bTokPos, bPoolMdl, bPoolState, bPoolNc, bCOff, bPoolSize, bPoolOff, bItems, bMstatus;
    DevBuf bFcSize, bFcCtr, bFcVar, bFcAssign, bFcCost, bFcStatus, bBak, bXg, bUtt, bSeg, bRun, bUpd, bFrameComp, bAcc, bOut;
    const size_t nGD = (size_t)m->G * D, nTp = (size_t)m->h_transOff[m->nT], nOcc = (size_t)m->h_trOccOff[m->nT];
-   if ((rc = hi_upload(bMdl, mdl, s)) || (rc = hi_upload(bTokFrame, aFrame, s)) || (rc = hi_upload(bTokLen, aLen, s)) || (rc = hi_upload(bTokMdl, aMdl, s)) ||
-       (rc = hi_upload(bPoolMdl, poolMdl, s)) || (rc = hi_upload(bPoolState, poolState, s)) || (rc = hi_upload(bPoolNc, poolNc, s)) || (rc = hi_upload(bCOff, cOff, s)) ||
+   if ((rc = unit_upload(bMdl, mdl, s)) || (rc = unit_upload(bTokFrame, aFrame, s)) || (rc = unit_upload(bTokLen, aLen, s)) || (rc = unit_upload(bTokMdl, tb.aMdl, s)) ||
+       (rc = unit_upload(bPoolMdl, poolMdl, s)) || (rc = unit_upload(bPoolState, poolState, s)) || (rc = unit_upload(bPoolNc, poolNc, s)) || (rc = unit_upload(bCOff, cOff, s)) ||
        (rc = bTokCnt.reserve(sizeof(int) * (size_t)nTok * maxNe)) || (rc = bTokPos.reserve(sizeof(int) * (size_t)nTok * maxNe)) ||
        (rc = bPoolSize.reserve(sizeof(int) * (size_t)nPools)) || (rc = bPoolOff.reserve(sizeof(int) * ((size_t)nPools + 1))) ||
        (rc = bItems.reserve(sizeof(int) * (size_t)totFrames)) || (rc = bMstatus.reserve(sizeof(int) * (size_t)nMdl)) ||
-       (rc = bBak.reserve(sizeof(float) * (2 * nGD + (size_t)m->C + nTp))) || (rc = bXg.reserve(sizeof(float) * (size_t)totFrames * D)) ||
-       (rc = bFrameComp.reserve(sizeof(int) * (size_t)totFrames)) ||
+       (rc = bXg.reserve(sizeof(float) * (size_t)totFrames * D)) || (rc = bFrameComp.reserve(sizeof(int) * (size_t)totFrames)) ||
        (rc = bAcc.reserve(sizeof(double) * 2 * nGD + sizeof(int) * ((size_t)m->C + nTp + nOcc))) || (rc = bOut.reserve(8 * (size_t)nMdl)))
       return rc;
    HIPCHECK(hipMemsetAsync(bMstatus.p, 0, sizeof(int) * (size_t)nMdl, s));
-   float *bak = (float *)bBak.p;
-   HIPCHECK(hipMemcpyAsync(bak, m->d_mean, sizeof(float) * nGD, hipMemcpyDeviceToDevice, s));
-   HIPCHECK(hipMemcpyAsync(bak + nGD, m->d_var, sizeof(float) * nGD, hipMemcpyDeviceToDevice, s));
-   HIPCHECK(hipMemcpyAsync(bak + 2 * nGD, m->d_compWeight, sizeof(float) * (size_t)m->C, hipMemcpyDeviceToDevice, s));
-   HIPCHECK(hipMemcpyAsync(bak + 2 * nGD + m->C, m->d_transP, sizeof(float) * nTp, hipMemcpyDeviceToDevice, s));
-
    HiArgs a;
    memset(&a, 0, sizeof(a));
-   a.D = D; a.PS = m->PS; a.uFlags = cfg->uFlags; a.minVar = cfg->minVar; a.logTpiD = (float)(D * log(HTK_TPI));
-   a.stateCompOff = m->d_stateCompOff; a.compGauss = m->d_compGauss; a.hmmState = m->d_hmmState;
-   a.mean = m->d_mean; a.var = m->d_var; a.ivar = m->d_ivar; a.gconst = m->d_gconst; a.gparam = m->d_gparam; a.compWeight = m->d_compWeight;
-   a.compLogWt = m->d_compLogWt; a.transP = m->d_transP;
-   a.bakMean = bak; a.bakVar = bak + nGD; a.bakWeight = bak + 2 * nGD; a.bakTransP = bak + 2 * nGD + m->C;
-   a.X = dX; a.mdl = (const HiModel *)bMdl.p; a.nMdl = nMdl; a.maxNe = maxNe;
+   if ((rc = unit_snapshot(m, bBak, s, &a.p))) return rc;
+   a.uFlags = cfg->uFlags; a.minVar = cfg->minVar;
+   a.X = dX; a.mdl = (const UnitModel *)bMdl.p; a.nMdl = nMdl; a.maxNe = maxNe;
    a.tokFrame = (const int *)bTokFrame.p; a.tokLen = (const int *)bTokLen.p; a.tokMdl = (const int *)bTokMdl.p; a.nTok = nTok;
    a.tokCnt = (int *)bTokCnt.p; a.tokPos = (int *)bTokPos.p; a.poolMdl = (const int *)bPoolMdl.p; a.poolState = (const int *)bPoolState.p; a.nPools = nPools;
    a.poolSize = (int *)bPoolSize.p; a.poolOff = (int *)bPoolOff.p; a.items = (int *)bItems.p; a.mstatus = (int *)bMstatus.p;
@@ -647,126 +554,128 @@ extern "C" int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int n
    const unsigned tokBlocks = (unsigned)((nTok + HI_THREADS - 1) / HI_THREADS);
    std::vector<int> mstat((size_t)nMdl, 0);
 
-   // ---- UniformSegment: pools, FlatCluster, the first parameters
-   if (cfg->newModel) {
-      if ((rc = bFcSize.reserve(sizeof(int) * (size_t)nClust)) || (rc = bFcCtr.reserve(sizeof(float) * (size_t)nClust * D)) || (rc = bFcVar.reserve(sizeof(float) * (size_t)nClust * D)) ||
-          (rc = bFcAssign.reserve(sizeof(int) * (size_t)totFrames)) || (rc = bFcCost.reserve(sizeof(float) * (size_t)totFrames)) || (rc = bFcStatus.reserve(sizeof(int) * (size_t)nPools)))
-         return rc;
-      hipLaunchKernelGGL(k_hi_count, dim3(tokBlocks), dim3(HI_THREADS), 0, s, a);
-      hipLaunchKernelGGL(k_hi_scan, dim3((unsigned)nPools), dim3(HI_THREADS), 0, s, a);
-      hipLaunchKernelGGL(k_hi_pooloff, dim3(1), dim3(HI_THREADS), 0, s, a);
-      hipLaunchKernelGGL(k_hi_fill, dim3(tokBlocks), dim3(HI_THREADS), 0, s, a);
-      HIPCHECK(hipGetLastError());
-      FcArgs f;
-      f.X = dX; f.D = D; f.poolOff = a.poolOff; f.items = a.items; f.nc = (const int *)bPoolNc.p; f.cOff = (const int *)bCOff.p;
-      // UniformSegment floors with vFloor (:592) where it copies, and only under UPVARS
-      f.minVar = cfg->minVar; f.size = (int *)bFcSize.p; f.centre = (float *)bFcCtr.p; f.var = (float *)bFcVar.p; f.assign = (int *)bFcAssign.p;
-      f.cost = (float *)bFcCost.p; f.status = (int *)bFcStatus.p;
-      hipLaunchKernelGGL(k_flat_cluster, dim3((unsigned)nPools), dim3(HI_THREADS), fc_lds_bytes(maxNc, D), s, f);
-      HIPCHECK(hipGetLastError());
-      FcOut fo;
-      fo.size = f.size; fo.centre = f.centre; fo.var = f.var; fo.status = f.status; fo.cOff = f.cOff;
-      hipLaunchKernelGGL(k_hi_init, dim3((unsigned)nMdl), dim3(HI_THREADS), 0, s, a, fo);
-      HIPCHECK(hipGetLastError());
+   auto train = [&]() -> int {
+      // ---- UniformSegment: pools, FlatCluster, the first parameters
+      if (cfg->newModel) {
+         if ((rc = bFcSize.reserve(sizeof(int) * (size_t)nClust)) || (rc = bFcCtr.reserve(sizeof(float) * (size_t)nClust * D)) || (rc = bFcVar.reserve(sizeof(float) * (size_t)nClust * D)) ||
+             (rc = bFcAssign.reserve(sizeof(int) * (size_t)totFrames)) || (rc = bFcCost.reserve(sizeof(float) * (size_t)totFrames)) || (rc = bFcStatus.reserve(sizeof(int) * (size_t)nPools)))
+            return rc;
+         hipLaunchKernelGGL(k_hi_count, dim3(tokBlocks), dim3(HI_THREADS), 0, s, a);
+         hipLaunchKernelGGL(k_hi_scan, dim3((unsigned)nPools), dim3(HI_THREADS), 0, s, a);
+         hipLaunchKernelGGL(k_hi_pooloff, dim3(1), dim3(HI_THREADS), 0, s, a);
+         hipLaunchKernelGGL(k_hi_fill, dim3(tokBlocks), dim3(HI_THREADS), 0, s, a);
+         HIPCHECK(hipGetLastError());
+         FcArgs f;
+         f.X = dX; f.D = D; f.poolOff = a.poolOff; f.items = a.items; f.nc = (const int *)bPoolNc.p; f.cOff = (const int *)bCOff.p;
+         // UniformSegment floors with vFloor (:592) where it copies, and only under UPVARS
+         f.minVar = cfg->minVar; f.size = (int *)bFcSize.p; f.centre = (float *)bFcCtr.p; f.var = (float *)bFcVar.p; f.assign = (int *)bFcAssign.p;
+         f.cost = (float *)bFcCost.p; f.status = (int *)bFcStatus.p;
+         hipLaunchKernelGGL(k_flat_cluster, dim3((unsigned)nPools), dim3(HI_THREADS), fc_lds_bytes(maxNc, D), s, f);
+         HIPCHECK(hipGetLastError());
+         FcOut fo;
+         fo.size = f.size; fo.centre = f.centre; fo.var = f.var; fo.status = f.status; fo.cOff = f.cOff;
+         hipLaunchKernelGGL(k_hi_init, dim3((unsigned)nMdl), dim3(HI_THREADS), 0, s, a, fo);
+         HIPCHECK(hipGetLastError());
+         HIPCHECK(hipMemcpyAsync(mstat.data(), bMstatus.p, sizeof(int) * (size_t)nMdl, hipMemcpyDeviceToHost, s));
+         HIPCHECK(hipStreamSynchronize(s));
+      }
+
+      // ---- EstimateModel's passes
+      std::vector<int> running, iter((size_t)nMdl, 0);
+      std::vector<float> totalP((size_t)nMdl, (float)LZERO);
+      for (int r = 0; r < nMdl; r++) { if (mstat[r]) status[mdlOf[r]] = mstat[r]; else running.push_back(r); }
+      bool changed = true;
+      std::vector<int> uMdl, uFrame0, uSrc, uSeg0, segUtt, segJ, labs, labOff, runUtt0, updFlag((size_t)nMdl), updList;
+      std::vector<float> outHost;
+      while (!running.empty()) {
+         if (changed) {                                      // the batch of the models still running
+            uMdl.clear(); uFrame0.assign(1, 0); uSrc.clear(); uSeg0.clear(); segUtt.clear(); segJ.clear(); labs.clear(); runUtt0.assign(1, 0);
+            for (int r : running) {
+               const UnitModel &x = mdl[r];
+               for (int k = x.tok0; k < x.tok0 + x.nTok; k++) {
+                  const int u = (int)uMdl.size();
+                  uMdl.push_back(r); uSrc.push_back(aFrame[k]); uSeg0.push_back((int)segUtt.size()); uFrame0.push_back(uFrame0.back() + aLen[k]); labs.push_back(x.h);
+                  for (int j = 0; j < x.ne; j++) { segUtt.push_back(u); segJ.push_back(j); }
+               }
+               runUtt0.push_back((int)uMdl.size());
+            }
+            labOff.resize(uMdl.size() + 1);
+            for (size_t u = 0; u <= uMdl.size(); u++) labOff[u] = (int)u;
+            const size_t nU = uMdl.size();
+            std::vector<int> pack;                          // one upload: uMdl, uFrame0, uSrc, uSeg0 | segUtt, segJ | running, runUtt0
+            pack.insert(pack.end(), uMdl.begin(), uMdl.end()); pack.insert(pack.end(), uFrame0.begin(), uFrame0.end());
+            pack.insert(pack.end(), uSrc.begin(), uSrc.end()); pack.insert(pack.end(), uSeg0.begin(), uSeg0.end());
+            if ((rc = unit_upload(bUtt, pack, s))) return rc;
+            a.uMdl = (const int *)bUtt.p; a.uFrame0 = a.uMdl + nU; a.uSrc = a.uFrame0 + nU + 1; a.uSeg0 = a.uSrc + nU;
+            a.nUtt = (int)nU; a.nFrames = uFrame0.back();
+            pack.assign(segUtt.begin(), segUtt.end()); pack.insert(pack.end(), segJ.begin(), segJ.end());
+            if ((rc = unit_upload(bSeg, pack, s))) return rc;
+            a.segUtt = (const int *)bSeg.p; a.segJ = a.segUtt + segUtt.size(); a.nSeg = (int)segUtt.size();
+            pack.assign(running.begin(), running.end()); pack.insert(pack.end(), runUtt0.begin(), runUtt0.end());
+            if ((rc = unit_upload(bRun, pack, s))) return rc;
+            a.runMdl = (const int *)bRun.p; a.runUtt0 = a.runMdl + running.size(); a.nRun = (int)running.size();
+            hipLaunchKernelGGL(k_hi_gather, dim3((unsigned)nU), dim3(HI_THREADS), 0, s, a);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipStreamSynchronize(s));              // (pack goes)
+            changed = false;
+         }
+         htkamd_batch_desc b;
+         b.nUtt = a.nUtt; b.dX = a.Xg; b.frameOff = uFrame0.data(); b.labOff = labOff.data(); b.labs = labs.data();
+         if ((rc = htkamd_viterbi_align_mode(vit, &b, 1.0e10f, HTKAMD_SCORE_SOUTP | HTKAMD_SCORE_DIAGC, s))) return rc;
+         htkamd_viterbi_dev vr;
+         if ((rc = htkamd_viterbi_device_results(vit, &vr))) return rc;
+         a.segStart = vr.segStart; a.segEnd = vr.segEnd; a.total = vr.total; a.uttStatus = vr.status;
+         hipLaunchKernelGGL(k_hi_logp, dim3((unsigned)((a.nRun + 63) / 64)), dim3(64), 0, s, a);
+         HIPCHECK(hipGetLastError());
+         outHost.resize(2 * (size_t)nMdl);
+         HIPCHECK(hipMemcpyAsync(outHost.data(), bOut.p, 8 * (size_t)nMdl, hipMemcpyDeviceToHost, s));
+         HIPCHECK(hipStreamSynchronize(s));
+         const int *statHost = (const int *)(outHost.data() + nMdl);
+         std::vector<int> next;
+         updList.clear();
+         std::fill(updFlag.begin(), updFlag.end(), 0);
+         for (size_t q = 0; q < running.size(); q++) {
+            const int r = running[q], k = mdlOf[r];
+            if (statHost[q] != HTKAMD_HINIT_OK) { status[k] = statHost[q]; mstat[r] = statHost[q]; changed = true; continue; }
+            const int it = ++iter[r];
+            const float newP = outHost[q] / (float)mdl[r].nTok;
+            const float delta = newP - totalP[r];
+            const bool conv = it > 1 && fabs((double)delta) < (double)cfg->epsilon;
+            logP[(size_t)k * maxIter + it - 1] = newP; nPass[k] = it; totalP[r] = newP;
+            if (conv) { converged[k] = 1; changed = true; continue; }
+            updList.push_back(r); updFlag[r] = 1;
+            if (it < maxIter) next.push_back(r); else changed = true;
+         }
+         if (!updList.empty()) {
+            std::vector<int> pack(updFlag);
+            pack.insert(pack.end(), updList.begin(), updList.end());
+            if ((rc = unit_upload(bUpd, pack, s))) return rc;
+            a.updFlag = (const int *)bUpd.p; a.updList = a.updFlag + nMdl; a.nUpd = (int)updList.size();
+            HIPCHECK(hipMemsetAsync(bAcc.p, 0, accBytes, s));
+            hipLaunchKernelGGL(k_hi_best, dim3((unsigned)((a.nFrames + HI_THREADS - 1) / HI_THREADS)), dim3(HI_THREADS), 0, s, a);
+            hipLaunchKernelGGL(k_hi_acc, dim3((unsigned)((a.nSeg + HI_THREADS / 64 - 1) / (HI_THREADS / 64))), dim3(HI_THREADS), 0, s, a);
+            hipLaunchKernelGGL(k_hi_update, dim3((unsigned)a.nUpd), dim3(HI_THREADS), 0, s, a);
+            HIPCHECK(hipGetLastError());
+            HIPCHECK(hipStreamSynchronize(s));              // (pack goes)
+         }
+         running.swap(next);
+      }
+
+      // ---- statuses raised by the last updates; the models that ended with one take back the parameters they came with
       HIPCHECK(hipMemcpyAsync(mstat.data(), bMstatus.p, sizeof(int) * (size_t)nMdl, hipMemcpyDeviceToHost, s));
       HIPCHECK(hipStreamSynchronize(s));
+      bool anyBad = false;
+      for (int r = 0; r < nMdl; r++) if (mstat[r]) { status[mdlOf[r]] = mstat[r]; converged[mdlOf[r]] = 0; anyBad = true; }
+      if (anyBad) { hipLaunchKernelGGL(k_unit_restore<HI_THREADS>, dim3((unsigned)nMdl), dim3(HI_THREADS), 0, s, a.p, a.mdl, a.mstatus); HIPCHECK(hipGetLastError()); }
+      return HTKAMD_OK;
+   };
+   const int rcTrain = train();
+   if (rcTrain) {
+      // a call that ends in an error leaves no model half trained: every model of the call goes back to its snapshot (as far as the
+      // device still answers), then the mirror follows as below and the error is returned; status / nPass / logP are then undefined
+      hipLaunchKernelGGL(k_unit_restore<HI_THREADS>, dim3((unsigned)nMdl), dim3(HI_THREADS), 0, s, a.p, a.mdl, (const int *)nullptr);
+      (void)hipGetLastError();
    }
-
-   // ---- EstimateModel's passes
-   std::vector<int> running, iter((size_t)nMdl, 0);
-   std::vector<float> totalP((size_t)nMdl, (float)LZERO);
-   for (int r = 0; r < nMdl; r++) { if (mstat[r]) status[mdlOf[r]] = mstat[r]; else running.push_back(r); }
-   bool changed = true;
-   std::vector<int> uMdl, uFrame0, uSrc, uSeg0, segUtt, segJ, labs, labOff, runUtt0, updFlag((size_t)nMdl), updList;
-   std::vector<float> outHost;
-   while (!running.empty()) {
-      if (changed) {                                      // the batch of the models still running
-         uMdl.clear(); uFrame0.assign(1, 0); uSrc.clear(); uSeg0.clear(); segUtt.clear(); segJ.clear(); labs.clear(); runUtt0.assign(1, 0);
-         for (int r : running) {
-            const HiModel &x = mdl[r];
-            for (int k = x.tok0; k < x.tok0 + x.nTok; k++) {
-               const int u = (int)uMdl.size();
-               uMdl.push_back(r); uSrc.push_back(aFrame[k]); uSeg0.push_back((int)segUtt.size()); uFrame0.push_back(uFrame0.back() + aLen[k]); labs.push_back(x.h);
-               for (int j = 0; j < x.ne; j++) { segUtt.push_back(u); segJ.push_back(j); }
-            }
-            runUtt0.push_back((int)uMdl.size());
-         }
-         labOff.resize(uMdl.size() + 1);
-         for (size_t u = 0; u <= uMdl.size(); u++) labOff[u] = (int)u;
-         const size_t nU = uMdl.size();
-         std::vector<int> pack;                          // one upload: uMdl, uFrame0, uSrc, uSeg0 | segUtt, segJ | running, runUtt0
-         pack.insert(pack.end(), uMdl.begin(), uMdl.end()); pack.insert(pack.end(), uFrame0.begin(), uFrame0.end());
-         pack.insert(pack.end(), uSrc.begin(), uSrc.end()); pack.insert(pack.end(), uSeg0.begin(), uSeg0.end());
-         if ((rc = hi_upload(bUtt, pack, s))) return rc;
-         a.uMdl = (const int *)bUtt.p; a.uFrame0 = a.uMdl + nU; a.uSrc = a.uFrame0 + nU + 1; a.uSeg0 = a.uSrc + nU;
-         a.nUtt = (int)nU; a.nFrames = uFrame0.back();
-         pack.assign(segUtt.begin(), segUtt.end()); pack.insert(pack.end(), segJ.begin(), segJ.end());
-         if ((rc = hi_upload(bSeg, pack, s))) return rc;
-         a.segUtt = (const int *)bSeg.p; a.segJ = a.segUtt + segUtt.size(); a.nSeg = (int)segUtt.size();
-         pack.assign(running.begin(), running.end()); pack.insert(pack.end(), runUtt0.begin(), runUtt0.end());
-         if ((rc = hi_upload(bRun, pack, s))) return rc;
-         a.runMdl = (const int *)bRun.p; a.runUtt0 = a.runMdl + running.size(); a.nRun = (int)running.size();
-         hipLaunchKernelGGL(k_hi_gather, dim3((unsigned)nU), dim3(HI_THREADS), 0, s, a);
-         HIPCHECK(hipGetLastError());
-         HIPCHECK(hipStreamSynchronize(s));              // (pack goes)
-         changed = false;
-      }
-      htkamd_batch_desc b;
-      b.nUtt = a.nUtt; b.dX = a.Xg; b.frameOff = uFrame0.data(); b.labOff = labOff.data(); b.labs = labs.data();
-      if ((rc = htkamd_viterbi_align_mode(vit, &b, 1.0e10f, HTKAMD_SCORE_SOUTP | HTKAMD_SCORE_DIAGC, s))) return rc;
-      htkamd_viterbi_dev vr;
-      if ((rc = htkamd_viterbi_device_results(vit, &vr))) return rc;
-      a.segStart = vr.segStart; a.segEnd = vr.segEnd; a.total = vr.total; a.uttStatus = vr.status;
-      hipLaunchKernelGGL(k_hi_logp, dim3((unsigned)((a.nRun + 63) / 64)), dim3(64), 0, s, a);
-      HIPCHECK(hipGetLastError());
-      outHost.resize(2 * (size_t)nMdl);
-      HIPCHECK(hipMemcpyAsync(outHost.data(), bOut.p, 8 * (size_t)nMdl, hipMemcpyDeviceToHost, s));
-      HIPCHECK(hipStreamSynchronize(s));
-      const int *statHost = (const int *)(outHost.data() + nMdl);
-      std::vector<int> next;
-      updList.clear();
-      std::fill(updFlag.begin(), updFlag.end(), 0);
-      for (size_t q = 0; q < running.size(); q++) {
-         const int r = running[q], k = mdlOf[r];
-         if (statHost[q] != HTKAMD_HINIT_OK) { status[k] = statHost[q]; mstat[r] = statHost[q]; changed = true; continue; }
-         const int it = ++iter[r];
-         const float newP = outHost[q] / (float)mdl[r].nTok;
-         const float delta = newP - totalP[r];
-         const bool conv = it > 1 && fabs((double)delta) < (double)cfg->epsilon;
-         logP[(size_t)k * maxIter + it - 1] = newP; nPass[k] = it; totalP[r] = newP;
-         if (conv) { converged[k] = 1; changed = true; continue; }
-         updList.push_back(r); updFlag[r] = 1;
-         if (it < maxIter) next.push_back(r); else changed = true;
-      }
-      if (!updList.empty()) {
-         std::vector<int> pack(updFlag);
-         pack.insert(pack.end(), updList.begin(), updList.end());
-         if ((rc = hi_upload(bUpd, pack, s))) return rc;
-         a.updFlag = (const int *)bUpd.p; a.updList = a.updFlag + nMdl; a.nUpd = (int)updList.size();
-         HIPCHECK(hipMemsetAsync(bAcc.p, 0, accBytes, s));
-         hipLaunchKernelGGL(k_hi_best, dim3((unsigned)((a.nFrames + HI_THREADS - 1) / HI_THREADS)), dim3(HI_THREADS), 0, s, a);
-         hipLaunchKernelGGL(k_hi_acc, dim3((unsigned)((a.nSeg + HI_THREADS / 64 - 1) / (HI_THREADS / 64))), dim3(HI_THREADS), 0, s, a);
-         hipLaunchKernelGGL(k_hi_update, dim3((unsigned)a.nUpd), dim3(HI_THREADS), 0, s, a);
-         HIPCHECK(hipGetLastError());
-         HIPCHECK(hipStreamSynchronize(s));              // (pack goes)
-      }
-      running.swap(next);
-   }
-
-   // ---- statuses raised by the last updates; failed models take their parameters back; the host mirror and the derived tables follow
-   HIPCHECK(hipMemcpyAsync(mstat.data(), bMstatus.p, sizeof(int) * (size_t)nMdl, hipMemcpyDeviceToHost, s));
-   HIPCHECK(hipStreamSynchronize(s));
-   bool anyBad = false;
-   for (int r = 0; r < nMdl; r++) if (mstat[r]) { status[mdlOf[r]] = mstat[r]; converged[mdlOf[r]] = 0; anyBad = true; }
-   if (anyBad) { hipLaunchKernelGGL(k_hi_restore, dim3((unsigned)nMdl), dim3(HI_THREADS), 0, s, a); HIPCHECK(hipGetLastError()); }
-   if ((rc = htkamd_model_params_changed(m, s, 1))) return rc;
-   HIPCHECK(hipMemcpyAsync(m->h_transP, m->d_transP, sizeof(float) * nTp, hipMemcpyDeviceToHost, s));
-   HIPCHECK(hipStreamSynchronize(s));
-   for (int t = 0; t < m->nT; t++) {
-      const int md = htkamd_host_min_dur(m->h_transN[t], m->h_transP + m->h_transOff[t]);
-      if (md != m->h_minDur[t]) { m->h_minDur[t] = md; m->topoVersion++; }
-      const unsigned char lr = (unsigned char)htkamd_host_trans_is_lr(m->h_transN[t], m->h_transP + m->h_transOff[t]);
-      if (lr != m->h_transLR[t]) { m->h_transLR[t] = lr; m->topoVersion++; }
-   }
-   return htkamd_model_sync_host(m);
+   rc = unit_finish(m, s);                                   // the host mirror and the derived tables follow
+   return rcTrain ? rcTrain : rc;
 }

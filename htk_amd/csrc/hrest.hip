@@ -1,5 +1,6 @@
 // hrest.hip -- isolated-unit Baum-Welch re-estimation (HTKTools/HRest.c) for every model of a list in one call.  The refusals and the
-// token bookkeeping: host/hrest.c.
+// token bookkeeping: host/hrest.c.  What the call shares with htkamd_hinit -- the model / token tables, the snapshot with unit_restore and
+// k_unit_restore, the block scan, the gather, the float transition row, the way out of the call -- is unit_train.h; here is HRest's own.
 //
 // A pass (ReEstimateModel HRest.c:1309) is one forward-backward batch (htkamd_fb_*) over the kept tokens of the models still running,
 // one single-model utterance per token, with these kernels around it:
@@ -22,24 +23,19 @@
 #include <vector>
 #include "internal.h"
 #include "hipcheck.h"
-#include "devbuf.h"
-#include "gauss_derive.h"
+#include "unit_train.h"
 
 #define HR_THREADS 256
 
-struct HrModel { int h, ne, N, tok0, nTok, tp0, st0, occ0; };      // tok0: its first kept token; tp0 / occ0: first element of its transition matrix / row occupations; st0: of its state list
 struct HrOut { float sum; int used, status; };                     // per running model and pass
 
 struct HrArgs {
-   GaussTables g;
+   UnitParams p;                                            // the model's arrays and their snapshot
    int uFlags;
    float minVar, vDefunct, mixWeightFloor;
-   const int *hmmState;
-   float *mean, *var, *compWeight, *transP;
-   const float *bakMean, *bakVar, *bakWeight, *bakTransP;
    double *acc; htkamd_accs_layout lay;
    const float *X; float *Xg;
-   const HrModel *mdl; int nMdl;
+   const UnitModel *mdl; int nMdl;                          // (tok0: its first kept token)
    const int *tokFrame, *tokLen, *tokMdl; int nTok;
    const int *runFlag;                                      // [nMdl]
    int *uTok, *uFrame0, *mdlUtt0, *nUttOut;                 // uFrame0 [nTok+1]; nUttOut: utterances, frames
@@ -48,23 +44,6 @@ struct HrArgs {
    int *mstatus;                                            // [nMdl]
    HrOut *out;                                              // [nRun]
 };
-
-static __device__ int hr_block_excl_scan(int v, int *lds, int *total)
-{
-   const int t = threadIdx.x;
-   lds[t] = v;
-   __syncthreads();
-   for (int o = 1; o < HR_THREADS; o <<= 1) {
-      const int x = t >= o ? lds[t - o] : 0;
-      __syncthreads();
-      lds[t] += x;
-      __syncthreads();
-   }
-   const int incl = lds[t];
-   *total = lds[HR_THREADS - 1];
-   __syncthreads();
-   return incl - v;
-}
 
 // (INVARIANT shared with the host loop of htkamd_hrest: utterance u is the u-th kept token of a running model in the order of the token
 // arrays; the host lays out the same list for htkamd_fb_prepare and compares the two totals written here)
@@ -78,8 +57,8 @@ __global__ __launch_bounds__(HR_THREADS) void k_hr_compact(HrArgs a)
       const int r = in ? a.tokMdl[k] : 0;
       const int run = in ? a.runFlag[r] : 0, len = run ? a.tokLen[k] : 0;
       int totU, totF;
-      const int exU = hr_block_excl_scan(run, lds, &totU);
-      const int exF = hr_block_excl_scan(len, lds, &totF);
+      const int exU = unit_block_excl_scan<HR_THREADS>(run, lds, &totU);
+      const int exF = unit_block_excl_scan<HR_THREADS>(len, lds, &totF);
       if (in && k == a.mdl[r].tok0) a.mdlUtt0[r] = baseU + exU;
       if (run) { a.uTok[baseU + exU] = k; a.uFrame0[baseU + exU] = baseF + exF; }
       baseU += totU; baseF += totF;
@@ -89,26 +68,23 @@ __global__ __launch_bounds__(HR_THREADS) void k_hr_compact(HrArgs a)
 
 __global__ __launch_bounds__(HR_THREADS) void k_hr_gather(HrArgs a)
 {
-   const int u = blockIdx.x, D = a.g.D;
+   const int u = blockIdx.x, D = a.p.g.D;
    if (u >= a.nUttOut[0]) return;
-   const size_t n = (size_t)(a.uFrame0[u + 1] - a.uFrame0[u]) * D;
-   const float *src = a.X + (size_t)a.tokFrame[a.uTok[u]] * D;
-   float *dst = a.Xg + (size_t)a.uFrame0[u] * D;
-   for (size_t e = threadIdx.x; e < n; e += HR_THREADS) dst[e] = src[e];
+   unit_gather_rows<HR_THREADS>(a.Xg + (size_t)a.uFrame0[u] * D, a.X + (size_t)a.tokFrame[a.uTok[u]] * D, (size_t)(a.uFrame0[u + 1] - a.uFrame0[u]) * D);
 }
 
 __global__ __launch_bounds__(HR_THREADS) void k_hr_zero(HrArgs a)
 {
-   const HrModel m = a.mdl[a.runMdl[blockIdx.x]];
-   const int D = a.g.D, t = threadIdx.x;
+   const UnitModel m = a.mdl[a.runMdl[blockIdx.x]];
+   const int D = a.p.g.D, t = threadIdx.x;
    for (int s = 0; s < m.ne; s++) {
-      const int st = a.hmmState[m.st0 + s], c0 = a.g.stateCompOff[st], M = a.g.stateCompOff[st + 1] - c0;
+      const int st = a.p.hmmState[m.st0 + s], c0 = a.p.g.stateCompOff[st], M = a.p.g.stateCompOff[st + 1] - c0;
       for (int e = t; e < M * D; e += HR_THREADS) {
-         const size_t x = (size_t)a.g.compGauss[c0 + e / D] * D + e % D;
+         const size_t x = (size_t)a.p.g.compGauss[c0 + e / D] * D + e % D;
          a.acc[a.lay.mu + x] = 0.0; a.acc[a.lay.va + x] = 0.0;
       }
       for (int k = t; k < M; k += HR_THREADS) {
-         const int g = a.g.compGauss[c0 + k];
+         const int g = a.p.g.compGauss[c0 + k];
          a.acc[a.lay.muOcc + g] = 0.0; a.acc[a.lay.vaOcc + g] = 0.0; a.acc[a.lay.wt + c0 + k] = 0.0;
       }
       if (t == 0) a.acc[a.lay.wtOcc + st] = 0.0;
@@ -133,47 +109,25 @@ __global__ void k_hr_logp(HrArgs a)
 
 #define ACCF(off, idx) ((float)a.acc[(off) + (size_t)(idx)])
 
-// the parameters of one model from the snapshot taken before the first pass, by the whole workgroup
-static __device__ void hr_restore(const HrArgs &a, const HrModel &m)
-{
-   const int D = a.g.D, t = threadIdx.x;
-   for (int s = 0; s < m.ne; s++) {
-      const int st = a.hmmState[m.st0 + s], c0 = a.g.stateCompOff[st], M = a.g.stateCompOff[st + 1] - c0;
-      for (int e = t; e < M * D; e += HR_THREADS) {
-         const size_t x = (size_t)a.g.compGauss[c0 + e / D] * D + e % D;
-         a.mean[x] = a.bakMean[x]; a.var[x] = a.bakVar[x];
-      }
-      for (int k = t; k < M; k += HR_THREADS) a.compWeight[c0 + k] = a.bakWeight[c0 + k];
-   }
-   for (int e = t; e < m.N * m.N; e += HR_THREADS) a.transP[m.tp0 + e] = a.bakTransP[m.tp0 + e];
-}
-
 __global__ __launch_bounds__(HR_THREADS) void k_hr_update(HrArgs a)
 {
    extern __shared__ int firstBad[];                        // [maxM] per component of the state in hand: the first dimension below vDefunct
    __shared__ int sFail;
-   const int q = blockIdx.x, r = a.runMdl[q], t = threadIdx.x, D = a.g.D;
-   const HrModel m = a.mdl[r];
+   const int q = blockIdx.x, r = a.runMdl[q], t = threadIdx.x, D = a.p.g.D;
+   const UnitModel m = a.mdl[r];
    const int incoming = a.mstatus[r];                       // k_hr_logp's 2226 (uniform: every thread reads the same word, nobody writes it before the last barrier)
    if (t == 0) sFail = 0;
    __syncthreads();
-   if (!incoming && (a.uFlags & HTKAMD_UPTRANS))            // RestTransP: row i by one thread
+   if (!incoming && (a.uFlags & HTKAMD_UPTRANS))            // RestTransP: row i by one thread, from the fp64 sums rounded to float
       for (int i = 1 + t; i < m.N; i += HR_THREADS) {
-         const int N = m.N;
-         float *row = a.transP + m.tp0 + (i - 1) * N;
          const float occi = ACCF(a.lay.trOcc, m.occ0 + i - 1);
          if (occi == 0.0f) { atomicCAS(&sFail, 0, HTKAMD_HREST_EZEROOCC); continue; }
-         float sum = 0.0f;
-         for (int j = 2; j <= N; j++) sum = __fadd_rn(sum, __fdiv_rn(ACCF(a.lay.tr, m.tp0 + (i - 1) * N + j - 1), occi));
-         row[0] = (float)LZERO;
-         for (int j = 2; j <= N; j++) {
-            const float x = __fdiv_rn(__fdiv_rn(ACCF(a.lay.tr, m.tp0 + (i - 1) * N + j - 1), occi), sum);
-            row[j - 1] = ((double)x < MINLARG) ? (float)LZERO : (float)log((double)x);
-         }
+         const double *tr = a.acc + a.lay.tr + (size_t)(m.tp0 + (i - 1) * m.N);
+         unit_trans_row(a.p.transP + m.tp0 + (i - 1) * m.N, m.N, [tr](int j) { return (float)tr[j]; }, occi);
       }
    if (!incoming && (a.uFlags & (HTKAMD_UPMEANS | HTKAMD_UPVARS | HTKAMD_UPMIXES)))
       for (int s = 0; s < m.ne; s++) {                      // RestStream
-         const int st = a.hmmState[m.st0 + s], c0 = a.g.stateCompOff[st], M = a.g.stateCompOff[st + 1] - c0;
+         const int st = a.p.hmmState[m.st0 + s], c0 = a.p.g.stateCompOff[st], M = a.p.g.stateCompOff[st + 1] - c0;
          for (int k = t; k < M; k += HR_THREADS) firstBad[k] = D;
          if (a.uFlags & HTKAMD_UPMIXES) {                   // RestMixWeights
             const float occ = ACCF(a.lay.wtOcc, st);
@@ -182,21 +136,21 @@ __global__ __launch_bounds__(HR_THREADS) void k_hr_update(HrArgs a)
                for (int k = t; k < M; k += HR_THREADS) {
                   float x = __fdiv_rn(ACCF(a.lay.wt, c0 + k), occ);
                   if (x > 1.0f) x = 1.0f;                   // (the fp64 sums of a component cannot exceed the state's but by their rounding to float)
-                  a.compWeight[c0 + k] = ((double)x > MINMIX) ? x : 0.0f;
+                  a.p.compWeight[c0 + k] = ((double)x > MINMIX) ? x : 0.0f;
                }
          }
          __syncthreads();
          for (int e = t; e < M * D; e += HR_THREADS) {      // RestMean, RestCoVar: a thread per (component, dimension)
-            const int k = e / D, d = e - k * D, g = a.g.compGauss[c0 + k];
-            if (!((double)a.compWeight[c0 + k] > MINMIX)) continue;
+            const int k = e / D, d = e - k * D, g = a.p.g.compGauss[c0 + k];
+            if (!((double)a.p.compWeight[c0 + k] > MINMIX)) continue;
             const size_t x = (size_t)g * D + d;
-            const float old = a.mean[x];
+            const float old = a.p.mean[x];
             float nm = old;
             if (a.uFlags & HTKAMD_UPMEANS) {
                const float occ = ACCF(a.lay.muOcc, g);
                if (occ == 0.0f) { atomicCAS(&sFail, 0, HTKAMD_HREST_EZEROOCC); continue; }
                nm = __fadd_rn(old, __fdiv_rn(ACCF(a.lay.mu, x), occ));
-               a.mean[x] = nm;
+               a.p.mean[x] = nm;
             }
             if (a.uFlags & HTKAMD_UPVARS) {
                const float occ = ACCF(a.lay.vaOcc, g);
@@ -205,33 +159,33 @@ __global__ __launch_bounds__(HR_THREADS) void k_hr_update(HrArgs a)
                float v = __fsub_rn(__fdiv_rn(ACCF(a.lay.va, x), occ), __fmul_rn(muDiff, muDiff));
                if (v < a.minVar) v = a.minVar;
                if (v < a.vDefunct) atomicMin(firstBad + k, d);
-               a.g.gparam[(size_t)g * a.g.PS + 2 * d] = v;   // parked in the row that is rebuilt below: written once the component's first defunct dimension is known
+               a.p.g.gparam[(size_t)g * a.p.g.PS + 2 * d] = v;   // parked in the row that is rebuilt below: written once the component's first defunct dimension is known
             }
          }
          __syncthreads();
          if (a.uFlags & HTKAMD_UPVARS)
             for (int e = t; e < M * D; e += HR_THREADS) {
-               const int k = e / D, d = e - k * D, g = a.g.compGauss[c0 + k];
-               if (!((double)a.compWeight[c0 + k] > MINMIX)) continue;
-               if (d < firstBad[k]) a.var[(size_t)g * D + d] = a.g.gparam[(size_t)g * a.g.PS + 2 * d];       // RestCoVar returns at the first one
+               const int k = e / D, d = e - k * D, g = a.p.g.compGauss[c0 + k];
+               if (!((double)a.p.compWeight[c0 + k] > MINMIX)) continue;
+               if (d < firstBad[k]) a.p.var[(size_t)g * D + d] = a.p.g.gparam[(size_t)g * a.p.g.PS + 2 * d];       // RestCoVar returns at the first one
             }
          __syncthreads();
          if (t == 0) {
             for (int k = 0; k < M; k++)
-               if (firstBad[k] < D && (double)a.compWeight[c0 + k] > MINMIX) {
-                  if (M > 1) a.compWeight[c0 + k] = 0.0f;   // "Defunct Mix"
+               if (firstBad[k] < D && (double)a.p.compWeight[c0 + k] > MINMIX) {
+                  if (M > 1) a.p.compWeight[c0 + k] = 0.0f;   // "Defunct Mix"
                   else atomicCAS(&sFail, 0, HTKAMD_HREST_EZEROOCC);     // "Zero Covariance"
                }
             if (M > 1) {                                    // FloorMixes, whatever uFlags says (RestStream :1270)
                const float floor = a.mixWeightFloor;
                float sum = 0.0f, fsum = 0.0f;
                for (int k = 0; k < M; k++) {
-                  if (a.compWeight[c0 + k] > floor) sum = __fadd_rn(sum, a.compWeight[c0 + k]);
-                  else { fsum = __fadd_rn(fsum, floor); a.compWeight[c0 + k] = floor; }
+                  if (a.p.compWeight[c0 + k] > floor) sum = __fadd_rn(sum, a.p.compWeight[c0 + k]);
+                  else { fsum = __fadd_rn(fsum, floor); a.p.compWeight[c0 + k] = floor; }
                }
                if ((double)fsum > 1.0) atomicCAS(&sFail, 0, HTKAMD_HREST_EFLOORSUM);
                const float scale = (float)((1.0 - (double)fsum) / (double)sum);
-               for (int k = 0; k < M; k++) if (a.compWeight[c0 + k] > floor) a.compWeight[c0 + k] = __fmul_rn(a.compWeight[c0 + k], scale);
+               for (int k = 0; k < M; k++) if (a.p.compWeight[c0 + k] > floor) a.p.compWeight[c0 + k] = __fmul_rn(a.p.compWeight[c0 + k], scale);
             }
          }
          __syncthreads();
@@ -239,33 +193,16 @@ __global__ __launch_bounds__(HR_THREADS) void k_hr_update(HrArgs a)
    __syncthreads();
    const int fail = incoming ? incoming : sFail;
    if (fail) {                                              // the model keeps what it came with, whichever pass it failed in
-      hr_restore(a, m);
+      unit_restore<HR_THREADS>(a.p, m);
       if (t == 0) { a.mstatus[r] = fail; a.out[q].status = fail; }
    }
    __syncthreads();
-   for (int s = 0; s < m.ne; s++) htkamd_derive_state(a.g, a.hmmState[m.st0 + s], HR_THREADS);
-}
-
-// every model of the call back to its snapshot: the way out of a call that ends in an error
-__global__ __launch_bounds__(HR_THREADS) void k_hr_restore_all(HrArgs a)
-{
-   const HrModel m = a.mdl[blockIdx.x];
-   hr_restore(a, m);
-   __syncthreads();
-   for (int s = 0; s < m.ne; s++) htkamd_derive_state(a.g, a.hmmState[m.st0 + s], HR_THREADS);
+   for (int s = 0; s < m.ne; s++) htkamd_derive_state(a.p.g, a.p.hmmState[m.st0 + s], HR_THREADS);
 }
 
 namespace {
 constexpr char hrOwner[] = "hrest";
 typedef DevBufT<hrOwner> DevBuf;
-
-template <typename T> int hr_upload(DevBuf &b, const std::vector<T> &v, hipStream_t s)
-{
-   const int rc = b.reserve(sizeof(T) * (v.size() ? v.size() : 1));
-   if (rc) return rc;
-   if (!v.empty()) HIPCHECK(hipMemcpyAsync(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s));
-   return HTKAMD_OK;
-}
 }
 
 extern "C" int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int nTokens, const int *tokFrame, const int *tokLen, const int *tokModel,
@@ -273,18 +210,9 @@ extern "C" int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int n
                             int *status, int *nPass, int *converged, float *logP, int *nUsed, void *stream)
 {
    if (!m || !cfg || !status || !nPass || !converged || !logP || !nUsed) { htkamd_set_error("hrest: NULL argument"); return HTKAMD_EINVAL; }
-   if (m->fullc) { htkamd_set_error("hrest: a FULLC set (HRest on full covariances is not supported)"); return HTKAMD_EMODEL; }
-   if (m->h_meanLeader) { htkamd_set_error("hrest: a set with shared mean / variance vectors (~u / ~v)"); return HTKAMD_EMODEL; }
-   if (m->h_rawLogWt) { htkamd_set_error("hrest: HTKAMD_COMPAT_SHARED_LOGWT is set (mixtures that share pdfs)"); return HTKAMD_EMODEL; }
    int rc;
-   {  // the refusals, on the description the model was made from
-      htkamd_model_desc d;
-      memset(&d, 0, sizeof(d));
-      d.vecSize = m->D; d.numStates = m->S / m->NSt; d.numComp = m->C; d.numGauss = m->G; d.numTrans = m->nT; d.numPhys = m->H;
-      d.stateCompOff = m->h_stateCompOff; d.compGauss = m->h_compGauss; d.var = m->h_var; d.hmmTrans = m->h_hmmTrans;
-      d.hmmStateOff = m->h_hmmStateOff; d.hmmState = m->h_hmmState; d.numStreams = m->NSt; d.hsKind = m->tiedMix ? HTKAMD_HS_TIED : HTKAMD_HS_PLAIN;
-      if ((rc = htkamd_hrest_check(&d, nFrames, nTokens, tokFrame, tokLen, tokModel, cfg, nModels, models))) return rc;
-   }
+   htkamd_model_desc d;
+   if ((rc = unit_refuse_handle(m, "hrest", "HRest", &d)) || (rc = htkamd_hrest_check(&d, nFrames, nTokens, tokFrame, tokLen, tokModel, cfg, nModels, models))) return rc;
    if (!dX && nTokens > 0) { htkamd_set_error("hrest: no feature table"); return HTKAMD_EINVAL; }
    if (htkamd_device_count() <= 0) { htkamd_set_error("hrest: no HIP device"); return HTKAMD_ENODEV; }
    hipStream_t s = (hipStream_t)stream;
@@ -295,62 +223,40 @@ extern "C" int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int n
    // ---- short-token rejection and the -m test, once; the kept tokens of the models that go on, behind one another per model
    std::vector<int> keep((size_t)(nTokens ? nTokens : 1)), nKept((size_t)nModels);
    if ((rc = htkamd_hrest_token_counts(m->h_hmmStateOff, m->H, nTokens, tokLen, tokModel, cfg, nModels, models, keep.data(), nKept.data(), status))) return rc;
-   std::vector<int> ofPhys((size_t)m->H, -1);
-   for (int k = 0; k < nModels; k++) ofPhys[models[k]] = k;
-   std::vector<std::vector<int>> toks((size_t)nModels);
-   for (int k = 0; k < nTokens; k++) if (keep[k]) toks[ofPhys[tokModel[k]]].push_back(k);
-   std::vector<HrModel> mdl; std::vector<int> mdlOf;        // mdlOf[r] = its place in `models`
-   std::vector<int> aFrame, aLen, aMdl;
+   UnitTables tb;
    int maxM = 1;
-   for (int k = 0; k < nModels; k++) {
-      if (status[k] != HTKAMD_HREST_OK) continue;
-      const int h = models[k], ti = m->h_hmmTrans[h];
-      HrModel x;
-      x.h = h; x.N = m->h_transN[ti]; x.ne = m->h_hmmStateOff[h + 1] - m->h_hmmStateOff[h]; x.tok0 = (int)aFrame.size(); x.nTok = (int)toks[k].size();
-      x.tp0 = m->h_transOff[ti]; x.st0 = m->h_hmmStateOff[h]; x.occ0 = m->h_trOccOff[ti];
-      for (int t : toks[k]) { aFrame.push_back(tokFrame[t]); aLen.push_back(tokLen[t]); aMdl.push_back((int)mdl.size()); }
-      for (int j = 0; j < x.ne; j++) {
-         const int st = m->h_hmmState[x.st0 + j], M = m->h_stateCompOff[st + 1] - m->h_stateCompOff[st];
-         if (M > maxM) maxM = M;
-      }
-      mdl.push_back(x); mdlOf.push_back(k);
-   }
-   const int nMdl = (int)mdl.size(), nTok = (int)aFrame.size();
-   if (nMdl == 0) return HTKAMD_OK;
-   long long totFrames = 0;
-   for (int L : aLen) totFrames += L;
-   if (totFrames >= ((long long)1 << 31)) { htkamd_set_error("hrest: %lld frames in the tokens (the tables index with 32 bits)", totFrames); return HTKAMD_EINVAL; }
-   if ((rc = htkamd_model_sync_host(m)) || (rc = htkamd_model_device_tables(m))) return rc;
+   rc = unit_tables("hrest", m, nTokens, tokFrame, tokLen, tokModel, keep.data(), nModels, models,
+      [&](int k, int, const std::vector<int> &) { return status[k] == HTKAMD_HREST_OK; },
+      [&](UnitModel &x, int) -> int {                          // the widest state: k_hr_update's LDS
+         for (int j = 0; j < x.ne; j++) {
+            const int st = m->h_hmmState[x.st0 + j], M = m->h_stateCompOff[st + 1] - m->h_stateCompOff[st];
+            if (M > maxM) maxM = M;
+         }
+         return HTKAMD_OK;
+      }, tb);
+   if (rc || tb.mdl.empty()) return rc;
+   const std::vector<UnitModel> &mdl = tb.mdl;
+   const std::vector<int> &mdlOf = tb.mdlOf, &aLen = tb.aLen;
+   const long long totFrames = tb.totFrames;
+   const int nMdl = (int)mdl.size(), nTok = (int)aLen.size();
 
    htkamd_fb *fb = nullptr; htkamd_accs *accs = nullptr;
    struct Guard { htkamd_fb *&f; htkamd_accs *&a; ~Guard() { if (f) htkamd_fb_destroy(f); if (a) htkamd_accs_destroy(a); } } guard{fb, accs};
    if ((rc = htkamd_fb_create(m, &fb)) || (rc = htkamd_accs_create(m, &accs)) || (rc = htkamd_accs_zero(accs, s))) return rc;
 
    DevBuf bMdl, bTokFrame, bTokLen, bTokMdl, bRunFlag, bUTok, bUFrame0, bMdlUtt0, bNUtt, bRun, bMstatus, bBak, bXg, bOut;
-   const size_t nGD = (size_t)m->G * D, nTp = (size_t)m->h_transOff[m->nT];
-   if ((rc = hr_upload(bMdl, mdl, s)) || (rc = hr_upload(bTokFrame, aFrame, s)) || (rc = hr_upload(bTokLen, aLen, s)) || (rc = hr_upload(bTokMdl, aMdl, s)) ||
+   if ((rc = unit_upload(bMdl, mdl, s)) || (rc = unit_upload(bTokFrame, tb.aFrame, s)) || (rc = unit_upload(bTokLen, aLen, s)) || (rc = unit_upload(bTokMdl, tb.aMdl, s)) ||
        (rc = bRunFlag.reserve(sizeof(int) * (size_t)nMdl)) || (rc = bUTok.reserve(sizeof(int) * (size_t)nTok)) || (rc = bUFrame0.reserve(sizeof(int) * ((size_t)nTok + 1))) ||
        (rc = bMdlUtt0.reserve(sizeof(int) * (size_t)nMdl)) || (rc = bNUtt.reserve(2 * sizeof(int))) || (rc = bRun.reserve(sizeof(int) * (size_t)nMdl)) ||
-       (rc = bMstatus.reserve(sizeof(int) * (size_t)nMdl)) || (rc = bBak.reserve(sizeof(float) * (2 * nGD + (size_t)m->C + nTp))) ||
-       (rc = bXg.reserve(sizeof(float) * (size_t)totFrames * D)) || (rc = bOut.reserve(sizeof(HrOut) * (size_t)nMdl)))
+       (rc = bMstatus.reserve(sizeof(int) * (size_t)nMdl)) || (rc = bXg.reserve(sizeof(float) * (size_t)totFrames * D)) || (rc = bOut.reserve(sizeof(HrOut) * (size_t)nMdl)))
       return rc;
    HIPCHECK(hipMemsetAsync(bMstatus.p, 0, sizeof(int) * (size_t)nMdl, s));
-   float *bak = (float *)bBak.p;                            // the snapshot a failed model is put back to
-   HIPCHECK(hipMemcpyAsync(bak, m->d_mean, sizeof(float) * nGD, hipMemcpyDeviceToDevice, s));
-   HIPCHECK(hipMemcpyAsync(bak + nGD, m->d_var, sizeof(float) * nGD, hipMemcpyDeviceToDevice, s));
-   HIPCHECK(hipMemcpyAsync(bak + 2 * nGD, m->d_compWeight, sizeof(float) * (size_t)m->C, hipMemcpyDeviceToDevice, s));
-   HIPCHECK(hipMemcpyAsync(bak + 2 * nGD + m->C, m->d_transP, sizeof(float) * nTp, hipMemcpyDeviceToDevice, s));
-
    HrArgs a;
    memset(&a, 0, sizeof(a));
-   a.g.D = D; a.g.PS = m->PS; a.g.logTpiD = (float)(D * log(HTK_TPI)); a.g.stateCompOff = m->d_stateCompOff; a.g.compGauss = m->d_compGauss;
-   a.g.mean = m->d_mean; a.g.var = m->d_var; a.g.compWeight = m->d_compWeight; a.g.ivar = m->d_ivar; a.g.gconst = m->d_gconst; a.g.gparam = m->d_gparam;
-   a.g.compLogWt = m->d_compLogWt;
+   if ((rc = unit_snapshot(m, bBak, s, &a.p))) return rc;      // the snapshot a failed model is put back to
    a.uFlags = cfg->uFlags; a.minVar = cfg->minVar; a.vDefunct = cfg->vDefunct; a.mixWeightFloor = cfg->mixWeightFloor;
-   a.hmmState = m->d_hmmState; a.mean = m->d_mean; a.var = m->d_var; a.compWeight = m->d_compWeight; a.transP = m->d_transP;
-   a.bakMean = bak; a.bakVar = bak + nGD; a.bakWeight = bak + 2 * nGD; a.bakTransP = bak + 2 * nGD + m->C;
    a.acc = accs->d_vec; a.lay = accs->lay;
-   a.X = dX; a.Xg = (float *)bXg.p; a.mdl = (const HrModel *)bMdl.p; a.nMdl = nMdl;
+   a.X = dX; a.Xg = (float *)bXg.p; a.mdl = (const UnitModel *)bMdl.p; a.nMdl = nMdl;
    a.tokFrame = (const int *)bTokFrame.p; a.tokLen = (const int *)bTokLen.p; a.tokMdl = (const int *)bTokMdl.p; a.nTok = nTok;
    a.runFlag = (const int *)bRunFlag.p; a.uTok = (int *)bUTok.p; a.uFrame0 = (int *)bUFrame0.p; a.mdlUtt0 = (int *)bMdlUtt0.p; a.nUttOut = (int *)bNUtt.p;
    a.runMdl = (const int *)bRun.p; a.mstatus = (int *)bMstatus.p; a.out = (HrOut *)bOut.p;
@@ -382,7 +288,7 @@ extern "C" int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int n
             const int nU = (int)labs.size();
             labOff.resize((size_t)nU + 1);
             for (int u = 0; u <= nU; u++) labOff[u] = u;
-            if ((rc = hr_upload(bRunFlag, runFlag, s)) || (rc = hr_upload(bRun, running, s))) return rc;
+            if ((rc = unit_upload(bRunFlag, runFlag, s)) || (rc = unit_upload(bRun, running, s))) return rc;
             a.nRun = nRun;
             hipLaunchKernelGGL(k_hr_compact, dim3(1), dim3(HR_THREADS), 0, s, a);
             hipLaunchKernelGGL(k_hr_gather, dim3((unsigned)nU), dim3(HR_THREADS), 0, s, a);
@@ -431,23 +337,9 @@ extern "C" int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int n
    if (rcPass) {
       // a call that ends in an error leaves no model half re-estimated: every model of the call goes back to its snapshot (as far as the
       // device still answers), then the mirror follows as below and the error is returned; status / nPass / logP are then undefined
-      hipLaunchKernelGGL(k_hr_restore_all, dim3((unsigned)nMdl), dim3(HR_THREADS), 0, s, a);
+      hipLaunchKernelGGL(k_unit_restore<HR_THREADS>, dim3((unsigned)nMdl), dim3(HR_THREADS), 0, s, a.p, a.mdl, (const int *)nullptr);
       (void)hipGetLastError();
    }
-
-   // ---- the host mirror and the derived tables follow
-   rc = [&]() -> int {
-      const int rcTab = htkamd_model_params_changed(m, s, 1);
-      if (rcTab) return rcTab;
-      HIPCHECK(hipMemcpyAsync(m->h_transP, m->d_transP, sizeof(float) * nTp, hipMemcpyDeviceToHost, s));
-      HIPCHECK(hipStreamSynchronize(s));
-      for (int t = 0; t < m->nT; t++) {
-         const int md = htkamd_host_min_dur(m->h_transN[t], m->h_transP + m->h_transOff[t]);
-         if (md != m->h_minDur[t]) { m->h_minDur[t] = md; m->topoVersion++; }
-         const unsigned char lr = (unsigned char)htkamd_host_trans_is_lr(m->h_transN[t], m->h_transP + m->h_transOff[t]);
-         if (lr != m->h_transLR[t]) { m->h_transLR[t] = lr; m->topoVersion++; }
-      }
-      return htkamd_model_sync_host(m);
-   }();
+   rc = unit_finish(m, s);                                  // the host mirror and the derived tables follow
    return rcPass ? rcPass : rc;
 }

@@ -89,6 +89,12 @@ int  htkamd_viterbi_device_results(htkamd_viterbi *v, htkamd_viterbi_dev *out);
 typedef struct { const double *pr; const int *status; } htkamd_fb_dev;
 int  htkamd_fb_device_results(htkamd_fb *fb, htkamd_fb_dev *out);
 
+/* ---- the refusals htkamd_hinit_check and htkamd_hrest_check share (host/unit_train.c): the fields both configurations have, the prefix
+ * and the tool's name as the messages carry them */
+typedef struct { int maxIter, minSeg, uFlags; } htkamd_unit_cfg;
+__attribute__((visibility("hidden"))) int htkamd_unit_check(const char *pfx, const char *tool, const htkamd_model_desc *d, int nFrames, int nTokens, const int *tokFrame, const int *tokLen,
+                       const int *tokModel, const htkamd_unit_cfg *cfg /* NULL: the caller had none */, int nModels, const int *models);
+
 /* device LAdd table: 4 intervals per unit of d over [minLogExp, 0] = [-23.03, 0], degree-10 Taylor rows (8 KB) */
 #define LADD_INV_H 4
 #define LADD_DEG   10
@@ -223,6 +229,7 @@ int htkamd_model_f16_flag(struct htkamd_model *m, void *stream, int *flag);   /*
 int htkamd_model_device_tables(struct htkamd_model *m);      /* model.hip: uploads d_var etc. once */
 static inline size_t htkamd_tri_size(int D) { return (size_t)D * (D + 1) / 2; }
 int htkamd_model_sync_host(struct htkamd_model *m);          /* model.hip: device -> host parameter copies when stale */
+void htkamd_model_refresh_topology(struct htkamd_model *m);  /* model.hip: minimum durations and left-to-right flags from h_transP; topoVersion moves where one changed */
 int htkamd_update_models(struct htkamd_model *m, const htkamd_accs_layout *lay, const double *acc,
                          const htkamd_update_config *cfg, htkamd_update_stats *st);   /* host/update.c */
 

@@ -284,6 +284,17 @@ static int fullc_refresh(htkamd_model *m)
    return rc;
 }
 
+// What the host derives from its transition matrices, after any change of h_transP: minimum durations (CreateInsts) and left-to-right flags
+extern "C" void htkamd_model_refresh_topology(htkamd_model *m)
+{
+   for (int t = 0; t < m->nT; t++) {
+      const int md = htkamd_host_min_dur(m->h_transN[t], m->h_transP + m->h_transOff[t]);
+      if (md != m->h_minDur[t]) { m->h_minDur[t] = md; m->topoVersion++; }
+      const unsigned char lr = (unsigned char)htkamd_host_trans_is_lr(m->h_transN[t], m->h_transP + m->h_transOff[t]);
+      if (lr != m->h_transLR[t]) { m->h_transLR[t] = lr; m->topoVersion++; }
+   }
+}
+
 // (Re)derive ivar / log weights / min durations / the interleaved scoring table and push them.
 static int model_refresh(htkamd_model *m, bool derive = true)
 {
@@ -296,12 +307,7 @@ static int model_refresh(htkamd_model *m, bool derive = true)
       for (int c = 0; c < m->C; c++)
          m->h_compLogWt[c] = (m->h_rawLogWt && m->h_rawLogWt[c]) ? m->h_compWeight[c] : htkamd_host_mix_log_weight(m->h_compWeight[c]);
    }
-   for (int t = 0; t < m->nT; t++) {
-      const int md = htkamd_host_min_dur(m->h_transN[t], m->h_transP + m->h_transOff[t]);
-      if (md != m->h_minDur[t]) { m->h_minDur[t] = md; m->topoVersion++; }
-      const unsigned char lr = (unsigned char)htkamd_host_trans_is_lr(m->h_transN[t], m->h_transP + m->h_transOff[t]);
-      if (lr != m->h_transLR[t]) { m->h_transLR[t] = lr; m->topoVersion++; }
-   }
+   htkamd_model_refresh_topology(m);
    float *gp = (float *)calloc((size_t)m->G * PS, sizeof(float));
    for (int g = 0; g < m->G; g++) {
       float *p = gp + (size_t)g * PS;

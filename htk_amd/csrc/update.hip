@@ -741,12 +741,7 @@ extern "C" int htkamd_model_update_device_end(htkamd_model *m, htkamd_update_sta
    int hst[16];
    memcpy(m->h_transP, m->h_updPin, sizeof(float) * nTp);
    memcpy(hst, (const float *)m->h_updPin + nTp, sizeof(hst));
-   for (int t = 0; t < m->nT; t++) {
-      const int md = htkamd_host_min_dur(m->h_transN[t], m->h_transP + m->h_transOff[t]);
-      if (md != m->h_minDur[t]) { m->h_minDur[t] = md; m->topoVersion++; }
-      const unsigned char lr = (unsigned char)htkamd_host_trans_is_lr(m->h_transN[t], m->h_transP + m->h_transOff[t]);
-      if (lr != m->h_transLR[t]) { m->h_transLR[t] = lr; m->topoVersion++; }
-   }
+   htkamd_model_refresh_topology(m);
    if (stats) {
       stats->nFloorVar = hst[0]; stats->nFloorVarMix = hst[1]; stats->nSkippedHmm = hst[2];
       stats->nNoTransOut = hst[3]; stats->nNoMixUse = hst[4]; stats->nNoVarUse = hst[5]; stats->nWeightAboveOne = hst[6];

@@ -170,6 +170,23 @@ def test_a_model_with_too_few_tokens_keeps_its_prototype(native, demo_all):
         check_against_reference(native, mmf, pk, p, res, name, os.path.join(hu.DEMO, "hinit_hrest.log"), os.path.join(hu.DEMO, "hmm0"))
 
 
+def test_a_model_whose_pools_cannot_be_clustered_is_put_back(native):
+    """the restore inside a real call: V keeps two tokens of 3 frames, so each of its three pools has 2 items -- fewer than the 3 components
+    of the middle state, and too few for two clusters of MIN_CLUST_SIZE 3 in the others.  k_hi_init raises the status and writes nothing;
+    the call's end puts the model back from the snapshot and rebuilds its derived tables, beside four models that train as ever"""
+    def two_short_of_v(mmf, tok):
+        v = np.flatnonzero(tok[:, 2] == mmf.logical["V"])
+        tok = np.delete(tok, v[2:], axis=0)
+        tok[tok[:, 2] == mmf.logical["V"], 1] = 3
+        return tok
+    gold = os.path.join(hu.DEMO, "hinit_mix")
+    mmf, pk, p, res = run_demo(native, os.path.join(gold, "proto"), tokens=two_short_of_v, min_seg=2)
+    assert res["V"]["status"] == native.HINIT_ECLUSTER and res["V"]["passes"] == 0 and not res["V"]["converged"]
+    assert hu.model_params_equal(p, native.Model(pk).get_params(), pk, mmf.logical["V"])
+    for name in "SCNL":
+        check_against_reference(native, mmf, pk, p, res, name, os.path.join(gold, "hinit.log"), os.path.join(gold, "hmm0"), weights=True)
+
+
 # ------------------------------------------------------------------------------------------ corners (tests/golden/hinit_set)
 RUNS = {"plain": ({}, []), "umv": (dict(uflags=1 | 2), ["-u", "mv"]), "vfloor": (dict(min_var=0.5), ["-v", "0.5"]),
         "wfloor": (dict(mix_weight_floor=9000 * 1.0e-5), ["-w", "9000"])}
