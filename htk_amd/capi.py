@@ -1597,6 +1597,12 @@ class Mlf:
         p = lib().htkamd_mlf_find(self.h, lab_file.encode())
         return None if not p else _labels_to_list(C.c_void_p(p))
 
+    def entries(self):
+        """(pattern, labels handle) of every entry in file order; the handles live as long as this object."""
+        L = lib()
+        L.htkamd_mlf_pattern.restype = C.c_char_p; L.htkamd_mlf_entry.restype = C.c_void_p
+        return [(L.htkamd_mlf_pattern(self.h, C.c_int(i)).decode(), C.c_void_p(L.htkamd_mlf_entry(self.h, C.c_int(i)))) for i in range(L.htkamd_mlf_count(self.h))]
+
     def __del__(self):
         try:
             if self.h:
@@ -1956,5 +1962,134 @@ class DecoderSet:
         try:
             if self.h:
                 lib().htkamd_decoder_set_destroy(self.h); self.h = C.c_void_p()
+        except Exception:
+            pass
+
+
+# ---- scoring recognition output (HResults): htkamd_results_* ----------------------------------------------------------------------
+
+RES_ALIGN, RES_CONF, RES_FULL, RES_TRANS, RES_PSTATS = 1, 2, 4, 8, 16
+RES_HIT, RES_SUB, RES_DEL, RES_INS = 0, 1, 2, 3
+
+
+class ResultsConfig(C.Structure):
+    _fields_ = [("nullName", C.c_char_p), ("ignoreCase", C.c_int), ("stripContexts", C.c_int), ("nist", C.c_int), ("nEquiv", C.c_int),
+                ("equivClass", C.POINTER(C.c_char_p)), ("equivLabel", C.POINTER(C.c_char_p)), ("nList", C.c_int), ("list", C.POINTER(C.c_char_p)),
+                ("refLevel", C.c_int), ("testLevel", C.c_int)]
+
+
+class ResultsReport(C.Structure):
+    _fields_ = [("flags", C.c_int), ("refId", C.c_char_p), ("nRecId", C.c_int), ("recId", C.POINTER(C.c_char_p)), ("nFiles", C.c_int),
+                ("recFile", C.POINTER(C.c_char_p)), ("labFile", C.POINTER(C.c_char_p)), ("counts", C.c_void_p), ("alnOff", C.c_void_p), ("aln", C.c_void_p),
+                ("totals", C.c_void_p), ("conf", C.c_void_p)]
+
+
+def _strs(names):
+    names = [n.encode() if isinstance(n, str) else n for n in names]
+    return (C.c_char_p * max(len(names), 1))(*names)
+
+
+def results_check_switch(sw: str):
+    check(lib().htkamd_results_check_switch(sw.encode()), "results_check_switch")
+
+
+class Results:
+    """htkamd_results holder: HResults for K hypothesis sets x U utterances in one call.  equiv: (class, label) pairs in -e order."""
+
+    def __init__(self, null_name=None, equiv=(), ignore_case=False, strip=False, nist=False, label_list=(), ref_level=0, test_level=0):
+        self.h = C.c_void_p()
+        self.label_list = list(label_list)
+        L = lib()
+        L.htkamd_results_label_name.restype = C.c_char_p
+        L.htkamd_results_last_kernel_ms.restype = C.c_double
+        cfg = ResultsConfig(None if null_name is None else null_name.encode(), int(ignore_case), int(strip), int(nist), len(equiv), _strs([e[0] for e in equiv]),
+                            _strs([e[1] for e in equiv]), len(self.label_list), _strs(self.label_list), int(ref_level), int(test_level))
+        check(L.htkamd_results_create(C.byref(cfg), C.byref(self.h)), "results_create")
+
+    def label_id(self, name: str) -> int:
+        i = lib().htkamd_results_label_id(self.h, name.encode())
+        if i < 0:
+            check(i, "results_label_id")
+        return i
+
+    def label_name(self, i: int):
+        s = lib().htkamd_results_label_name(self.h, C.c_int(i))
+        return None if s is None else s.decode()
+
+    def num_labels(self) -> int:
+        return int(lib().htkamd_results_num_labels(self.h))
+
+    def add_ref(self, utt: str, names) -> int:
+        i = lib().htkamd_results_add_ref(self.h, utt.encode(), C.c_int(len(names)), _strs(names))
+        if i < 0:
+            check(i, "results_add_ref")
+        return i
+
+    def ref_for(self, rec_file: str, mlfs=(), lab_dir=None, lab_ext=None):
+        """(reference index, its file name as HResults forms it)."""
+        buf = C.create_string_buffer(1024)
+        arr = (C.c_void_p * max(len(mlfs), 1))(*[m.h for m in mlfs])
+        i = lib().htkamd_results_ref_for(self.h, rec_file.encode(), arr, C.c_int(len(mlfs)), None if lab_dir is None else lab_dir.encode(),
+                                         None if lab_ext is None else lab_ext.encode(), buf, C.c_size_t(1024))
+        if i < 0:
+            check(i, "results_ref_for")
+        return i, buf.value.decode()
+
+    def ids(self, labels_handle) -> np.ndarray:
+        n = lib().htkamd_labels_count(labels_handle)
+        out = np.zeros(max(n, 1), np.int32)
+        check(lib().htkamd_results_ids(self.h, labels_handle, _p(out)), "results_ids")
+        return out[:n]
+
+    def ids_of(self, names) -> np.ndarray:
+        return np.array([self.label_id(n) for n in names], np.int32).reshape(-1)
+
+    def score(self, utt_ref, hyps, align=False, conf=False):
+        """hyps[k][u]: id array of set k's hypothesis for utterance u (reference utt_ref[u]).  Returns a dict: counts [K, U, 6] (H D S I N
+        status), totals [K, 7] (H D S I N sentences correct), aln: per set, per utterance an [n, 3] array of (op, refId, testId), conf
+        [K, V+1, V+1], kernel_ms."""
+        K, U = len(hyps), len(utt_ref)
+        flat = [np.asarray(h, np.int32).reshape(-1) for hs in hyps for h in hs]
+        if len(flat) != K * U:
+            raise HtkAmdError("Results.score: every set needs %d hypotheses" % U)
+        hypOff = np.concatenate([[0], np.cumsum([len(h) for h in flat])]).astype(np.int32)
+        hypIds = np.ascontiguousarray(np.concatenate(flat + [np.zeros(1, np.int32)]), np.int32)
+        uttRef = np.ascontiguousarray(np.asarray(list(utt_ref) + [0], np.int64).astype(np.int32))
+        refLen = [int(lib().htkamd_results_ref_len(self.h, C.c_int(int(u)))) for u in utt_ref]
+        V = len(self.label_list)
+        counts = np.zeros((max(K * U, 1), 6), np.int32)
+        totals = np.zeros((max(K, 1), 7), np.int64)
+        cap = int(sum(max(r, 0) for r in refLen) * K + hypOff[-1]) if align else 0
+        alnOff = np.zeros(K * U + 1, np.int32)
+        aln = np.zeros((max(cap, 1), 3), np.int32)
+        cm = np.zeros((max(K, 1), V + 1, V + 1), np.int32)
+        flags = (RES_ALIGN if align else 0) | (RES_CONF if conf else 0)
+        check(lib().htkamd_results_score(self.h, C.c_int(K), C.c_int(U), _p(uttRef), _p(hypOff), _p(hypIds), C.c_int(flags), _p(counts),
+                                         _p(alnOff) if align else None, _p(aln) if align else None, C.c_longlong(cap), _p(totals), _p(cm) if conf else None, None),
+              "results_score")
+        out = dict(counts=counts[:K * U].reshape(K, U, 6), totals=totals[:K], kernel_ms=float(lib().htkamd_results_last_kernel_ms(self.h)),
+                   alnOff=alnOff, alnFlat=aln)
+        if align:
+            out["aln"] = [[aln[alnOff[k * U + u]:alnOff[k * U + u + 1]] for u in range(U)] for k in range(K)]
+        if conf:
+            out["conf"] = cm[:K]
+        return out
+
+    def write(self, flags, ref_id, rec_ids, rec_files, lab_files, counts, totals, aln_off=None, aln=None, conf=None, path=None, append=False):
+        """HResults' text for ONE set: counts [nFiles, 6], totals [7], aln_off [nFiles + 1] into aln [n, 3], conf [V+1, V+1]."""
+        n = len(rec_files)
+        counts = np.ascontiguousarray(np.asarray(counts, np.int32).reshape(-1, 6) if n else np.zeros((1, 6), np.int32))
+        totals = np.ascontiguousarray(totals, np.int64)
+        aln_off = None if aln_off is None else np.ascontiguousarray(aln_off, np.int32)
+        aln = None if aln is None else np.ascontiguousarray(aln, np.int32)
+        conf = None if conf is None else np.ascontiguousarray(conf, np.int32)
+        rep = ResultsReport(int(flags), None if ref_id is None else ref_id.encode(), len(rec_ids), _strs(rec_ids), n, _strs(rec_files), _strs(lab_files),
+                            _p(counts), _p(aln_off), _p(aln), _p(totals), _p(conf))
+        check(lib().htkamd_results_write(self.h, C.byref(rep), None if path is None else path.encode(), C.c_int(int(append))), "results_write")
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().htkamd_results_destroy(self.h); self.h = C.c_void_p()
         except Exception:
             pass

@@ -152,6 +152,11 @@ const struct htkamd_labels *htkamd_mlf_find(const struct htkamd_mlf *m, const ch
    return NULL;
 }
 
+/* the entries in file order (HResults scores a hypothesis MLF entry by entry: main HResults.c:294) */
+int htkamd_mlf_count(const struct htkamd_mlf *m) { return m ? m->n : 0; }
+const char *htkamd_mlf_pattern(const struct htkamd_mlf *m, int i) { return (m && i >= 0 && i < m->n) ? m->pattern[i] : NULL; }
+const struct htkamd_labels *htkamd_mlf_entry(const struct htkamd_mlf *m, int i) { return (m && i >= 0 && i < m->n) ? m->lab[i] : NULL; }
+
 /* ---- script files (-S): the list of data files of a tool run ------------------------------------------------------------
  * ScriptWord (HShell.c:661-688): words separated by white space, or enclosed in single / double quotes (no escapes);
  * RegisterExtFileName (HShell.c:86-140): a word may be an extended file name  logical=physical[start,end]  (either part optional):

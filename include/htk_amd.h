@@ -409,6 +409,9 @@ float htkamd_labels_score(const htkamd_labels *l, int i);
 int  htkamd_mlf_read(const char *path, htkamd_mlf **out);
 void htkamd_mlf_free(htkamd_mlf *m);
 const htkamd_labels *htkamd_mlf_find(const htkamd_mlf *m, const char *labFile);   /* first matching pattern, or NULL */
+int  htkamd_mlf_count(const htkamd_mlf *m);                                          /* the entries in file order */
+const char *htkamd_mlf_pattern(const htkamd_mlf *m, int i);
+const htkamd_labels *htkamd_mlf_entry(const htkamd_mlf *m, int i);
 
 /* ------------------------------------------------------------------------------------------
  * GMM scoring: replaces the state output-probability calls
@@ -1328,6 +1331,83 @@ int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int nTokens, con
    models[m], status[m] = HTKAMD_HREST_EFEWSEGS where they are fewer than minSeg, else HTKAMD_HREST_OK. */
 int htkamd_hrest_token_counts(const int *hmmStateOff, int numPhys, int nTokens, const int *tokLen, const int *tokModel, const htkamd_hrest_config *cfg,
                               int nModels, const int *models, int *keep /*[nTokens]*/, int *nKept /*[nModels]*/, int *status /*[nModels]*/);
+
+/* ------------------------------------------------------------------------------------------
+ * Scoring recognition output: replaces HResults (HTKTools/HResults.c) for K hypothesis sets x U utterances in ONE call
+ * (csrc/results.hip; names, references, refusals and every line of text: host/results.c).
+ *   AddEquiv / NormaliseName (:346)  htkamd_results_label_id: a label's name -> its id.  -s strips the contexts first (l-c+r -> c), then
+ *                                    the -e equivalences in the reference's order (the last one given first), then -c upper-cases a name
+ *                                    that has a lower-case letter.  Id 0 is the null class (-z, "???"); ids 1..nList are the label list's
+ *                                    names as they stand (ReadHMMList :1121), later names follow in order of first use
+ *   MatchFiles (:1720)               htkamd_results_ref_for: the reference of a hypothesis file (MakeFN with -L / -X, looked up in the
+ *                                    -I files first); a missing reference is HTKAMD_EIO and names the file
+ *   CreateGrid / DoCompare /         htkamd_results_score: a wavefront per (reference, hypothesis) pair, lanes along an anti-diagonal of
+ *   DoCompareNIST (:835-1020)        the grid; per pair H, D, S, I, N = H+D+S and whether HResults counts it: a pair whose reference or
+ *                                    hypothesis is EMPTY is aligned (its counts are the edge cell's) but, as in MatchFiles :1728 and
+ *                                    MatchRecFiles :1308, left out of the totals, the text and the confusion matrix (status 0)
+ *   AppendCell / CollectStats        the traceback from (nTest, nRef): (op, refId, testId) triples in the order -t prints them, -1 for
+ *   (:1050, :1259)                   the side an insertion / deletion lacks; steps that involve the null class are dropped as both drop them
+ *   RecordFileStats (:530)           totals per set: H D S I N, sentences, correct sentences; the -p matrix [V+1][V+1] (V = nList):
+ *                                    [r][t] label r recognised as t, [r][0] deletions of r, [0][t] insertions of t
+ *   Print* / OutTrans / OutConMat    htkamd_results_write: the reference's text from those numbers, no device involved
+ * Not supported, each refused with a message that names it (htkamd_results_check_switch for a tool's command line): word spotting
+ * (-w, -u), per-speaker results (-k), the NIST output format (-h), N-best scoring (-d), file limits (-m, -j), renaming the phrase and
+ * phone labels (-a, -b); label levels other than 0 (refLevel / testLevel).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct htkamd_results htkamd_results;
+typedef struct {
+   const char *nullName;                 /* -z; NULL = "???"                                                        */
+   int ignoreCase, stripContexts, nist;  /* -c, -s, -n (penalties 4 / 3 / 3 and DoCompareNIST's tie order)          */
+   int nEquiv;                           /* -e class label, in command-line order                                   */
+   const char *const *equivClass, *const *equivLabel;
+   int nList; const char *const *list;   /* the label list; only the confusion matrix needs it (at most 200 names)  */
+   int refLevel, testLevel;              /* REFLEVEL / TESTLEVEL: must be 0                                         */
+} htkamd_results_config;
+#define HTKAMD_RES_ALIGN   1             /* score: return the alignment triples                                     */
+#define HTKAMD_RES_CONF    2             /* score: fill the confusion matrices (runs the traceback too)             */
+#define HTKAMD_RES_FULL    4             /* write: -f, a line per file                                              */
+#define HTKAMD_RES_TRANS   8             /* write: -t, the aligned transcriptions of the files with an error        */
+#define HTKAMD_RES_PSTATS 16             /* write: -p, the confusion matrix                                         */
+#define HTKAMD_RES_HIT 0
+#define HTKAMD_RES_SUB 1
+#define HTKAMD_RES_DEL 2
+#define HTKAMD_RES_INS 3
+int  htkamd_results_create(const htkamd_results_config *cfg, htkamd_results **out);
+void htkamd_results_destroy(htkamd_results *r);
+int  htkamd_results_check_switch(const char *sw);                     /* "-w" ...: HTKAMD_OK for a switch this path has, HTKAMD_EINVAL and the reason otherwise */
+int  htkamd_results_label_id(htkamd_results *r, const char *name);    /* >= 0, or a negative HTKAMD_E* code                                          */
+const char *htkamd_results_label_name(const htkamd_results *r, int id);
+int  htkamd_results_num_labels(const htkamd_results *r);              /* ids 0 .. n-1 exist                                                         */
+/* A reference transcription by utterance name: returns its index (>= 0; a name given again keeps its first transcription) or HTKAMD_E*. */
+int  htkamd_results_add_ref(htkamd_results *r, const char *utt, int n, const char *const *names);
+int  htkamd_results_find_ref(const htkamd_results *r, const char *utt);       /* index or -1 */
+int  htkamd_results_ref_len(const htkamd_results *r, int ref);
+/* The reference of hypothesis file `recFile`: its name (directory labDir or the file's own, extension labExt or "lab") goes to labFile;
+   taken from the first of the nMlf master label files that has it, else from that file; added under that name and its index returned. */
+int  htkamd_results_ref_for(htkamd_results *r, const char *recFile, const htkamd_mlf *const *mlfs, int nMlf, const char *labDir, const char *labExt,
+                            char *labFile, size_t labFileLen);
+int  htkamd_results_ids(htkamd_results *r, const htkamd_labels *l, int *ids /*[htkamd_labels_count(l)]*/);
+/* Pair p = k * U + u: hypothesis hypIds[hypOff[p] .. hypOff[p+1]) of set k against reference uttRef[u].  counts [K*U][6]: H D S I N status.
+   With HTKAMD_RES_ALIGN: pair p's triples are aln[3 * alnOff[p] .. 3 * alnOff[p+1]); alnCap (in triples) must hold the sum of nRef + nTest
+   over all pairs.  totals [K][7]: H D S I N sentences correct.  conf [K][(V+1)*(V+1)] with HTKAMD_RES_CONF (a label outside the list is
+   HTKAMD_EINVAL and named, Index :1151).  Outputs that are not wanted may be NULL.  Synchronises `stream`. */
+int  htkamd_results_score(htkamd_results *r, int K, int U, const int *uttRef, const int *hypOff, const int *hypIds, int flags,
+                          int *counts, int *alnOff, int *aln, long long alnCap, long long *totals, int *conf, void *stream);
+double htkamd_results_last_kernel_ms(const htkamd_results *r);       /* device time of the last call's kernels (events around them) */
+int  htkamd_results_dir_tile(void);                                   /* grid cells (nRef * nTest) whose `dir` bytes a wavefront keeps in LDS; a larger pair uses global scratch */
+typedef struct {
+   int flags;                            /* HTKAMD_RES_FULL | _TRANS | _PSTATS                                       */
+   const char *refId;                    /* "Ref :": the last -I file, else the -L directory, else NULL              */
+   int nRecId; const char *const *recId; /* "Rec :": the hypothesis arguments (the first five are printed)           */
+   int nFiles;
+   const char *const *recFile, *const *labFile;   /* per file, as HResults names them                               */
+   const int *counts;                    /* [nFiles][6]                                                              */
+   const int *alnOff, *aln;              /* -t                                                                       */
+   const long long *totals;              /* [7]                                                                      */
+   const int *conf;                      /* -p: [(V+1)*(V+1)]                                                        */
+} htkamd_results_report;
+/* path NULL = stdout; append: add to the file instead of replacing it */
+int  htkamd_results_write(const htkamd_results *r, const htkamd_results_report *rep, const char *path, int append);
 
 #ifdef __cplusplus
 }
