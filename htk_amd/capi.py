@@ -2093,3 +2093,178 @@ class Results:
                 lib().htkamd_results_destroy(self.h); self.h = C.c_void_p()
         except Exception:
             pass
+
+
+class LatScales(C.Structure):
+    _fields_ = [("acScale", C.c_float), ("lmScale", C.c_float), ("wordPen", C.c_float), ("prScale", C.c_float)]
+
+
+class LatSetView(C.Structure):
+    _fields_ = [("nNodes", C.c_int), ("nArcs", C.c_int), ("start", C.c_int), ("end", C.c_int), ("nodeTime", C.POINTER(C.c_double)), ("nodeWord", C.POINTER(C.c_int)),
+                ("nodeVar", C.POINTER(C.c_int)), ("arcStart", C.POINTER(C.c_int)), ("arcEnd", C.POINTER(C.c_int)), ("arcAc", C.POINTER(C.c_float)),
+                ("arcLm", C.POINTER(C.c_float)), ("arcPr", C.POINTER(C.c_float)), ("topOrder", C.POINTER(C.c_int)), ("fwdArcs", C.POINTER(C.c_int)),
+                ("bwdArcs", C.POINTER(C.c_int))]
+
+
+class LatBestOut(C.Structure):
+    _fields_ = [("nPath", C.c_void_p), ("status", C.c_void_p), ("pathArcs", C.c_void_p), ("totals", C.c_void_p)]
+
+
+class LatFbOut(C.Structure):
+    _fields_ = [("fw", C.c_void_p), ("bw", C.c_void_p), ("best", C.c_void_p)]
+
+
+LAT_FORMAT = dict(A=0x1, B=0x2, t=0x8, v=0x10, a=0x20, l=0x40, d=0x80, m=0x100, n=0x200, r=0x400)      # the letters of -q
+
+
+def latset_check_switch(sw: str):
+    check(lib().htkamd_latset_check_switch(sw.encode()), "latset_check_switch")
+
+
+def latset_tile() -> int:
+    return int(lib().htkamd_latset_tile())
+
+
+def lat_scales(settings):
+    """settings: rows of (acscale -a, lmscale -s, wdpenalty -p, prscale -r), narrowed to float as HLRescore's assignments narrow them."""
+    rows = np.asarray(settings, np.float64).reshape(-1, 4)
+    return (LatScales * len(rows))(*[LatScales(*[float(np.float32(x)) for x in r]) for r in rows])
+
+
+class LatSet:
+    """htkamd_latset holder: HLRescore for U lattices under K settings in one call.  Per-node results of K settings come back per lattice
+    as [nNodes, K] arrays (the library's interleaved layout)."""
+
+    def __init__(self, dictionary: str = None, start_word=None, end_word=None, like: "LatSet" = None):
+        self.h = C.c_void_p()
+        L = lib()
+        L.htkamd_latset_word_name.restype = C.c_char_p
+        L.htkamd_latset_last_kernel_ms.restype = C.c_double
+        if like is not None:
+            check(L.htkamd_latset_create_like(like.h, C.byref(self.h)), "latset_create_like")
+        else:
+            check(L.htkamd_latset_create(dictionary.encode(), None if start_word is None else start_word.encode(), None if end_word is None else end_word.encode(),
+                                         C.byref(self.h)), "latset_create")
+
+    def __len__(self):
+        return int(lib().htkamd_latset_count(self.h))
+
+    def add_file(self, path: str) -> int:
+        i = lib().htkamd_latset_add_file(self.h, path.encode())
+        if i < 0:
+            check(i, "latset_add_file")
+        return i
+
+    def add(self, lat: dict, net: "Net", frame_dur=0.01) -> int:
+        """A lattice of Decoder.run_lattice / DecoderSet.run_lattice."""
+        st, keep = _lattice_struct(lat, frame_dur)
+        i = lib().htkamd_latset_add(self.h, C.byref(st), net.h)
+        if i < 0:
+            check(i, "latset_add")
+        return i
+
+    def add_pruned(self, src: "LatSet", u: int, keep_node, keep_arc) -> int:
+        kn, ka = np.ascontiguousarray(keep_node, np.uint8), np.ascontiguousarray(keep_arc, np.uint8)
+        v = src.view(u)
+        if len(kn) != v["nNodes"] or len(ka) != v["nArcs"]:
+            raise HtkAmdError("LatSet.add_pruned: the flags do not fit lattice %d" % u)
+        i = lib().htkamd_latset_add_pruned(self.h, src.h, C.c_int(u), _p(kn), _p(ka))
+        if i < 0:
+            check(i, "latset_add_pruned")
+        return i
+
+    def view(self, u: int) -> dict:
+        v = LatSetView()
+        check(lib().htkamd_latset_get(self.h, C.c_int(u), C.byref(v)), "latset_get")
+        nn, na = v.nNodes, v.nArcs
+        out = dict(nNodes=nn, nArcs=na, start=v.start, end=v.end)
+        for f, n in (("nodeTime", nn), ("nodeWord", nn), ("nodeVar", nn), ("topOrder", nn), ("arcStart", na), ("arcEnd", na), ("arcAc", na), ("arcLm", na), ("arcPr", na),
+                     ("fwdArcs", na), ("bwdArcs", na)):
+            out[f] = np.ctypeslib.as_array(getattr(v, f), shape=(max(n, 1),))[:n].copy()
+        out["nullEnd"] = out["nodeWord"][out["arcEnd"]] == 0
+        return out
+
+    def word_name(self, w: int):
+        s = lib().htkamd_latset_word_name(self.h, C.c_int(int(w)))
+        return None if s is None else s.decode()
+
+    def sizes(self):
+        """(nodes, arcs) per lattice as two int arrays."""
+        v = LatSetView()
+        nn, na = [], []
+        for u in range(len(self)):
+            check(lib().htkamd_latset_get(self.h, C.c_int(u), C.byref(v)), "latset_get")
+            nn.append(v.nNodes); na.append(v.nArcs)
+        return np.array(nn, np.int64), np.array(na, np.int64)
+
+    def _offsets(self):
+        nn, na = self.sizes()
+        return nn, na, np.concatenate([[0], np.cumsum(nn)]), np.concatenate([[0], np.cumsum(na)])
+
+    def kernel_ms(self) -> float:
+        return float(lib().htkamd_latset_last_kernel_ms(self.h))
+
+    def best(self, settings, stream=None) -> dict:
+        """LatFindBest for every (setting, lattice): paths[k][u] (arc numbers, start to end), totals [K, U, 4] (ac lm pr tot), status [K, U]."""
+        sc = lat_scales(settings); K, U = len(sc), len(self)
+        nn, _, noff, _ = self._offsets()
+        TN = int(noff[-1])
+        nPath, status = np.zeros(max(K * U, 1), np.int32), np.zeros(max(K * U, 1), np.int32)
+        arcs, totals = np.zeros(max(K * TN, 1), np.int32), np.zeros((max(K * U, 1), 4), np.float64)
+        out = LatBestOut(_p(nPath), _p(status), _p(arcs), _p(totals))
+        check(lib().htkamd_latset_best(self.h, C.c_int(K), sc, C.byref(out), _stream(stream)), "latset_best")
+        paths = [[arcs[k * TN + noff[u]:k * TN + noff[u] + nPath[k * U + u]].copy() for u in range(U)] for k in range(K)]
+        return dict(paths=paths, totals=totals[:K * U].reshape(K, U, 4), status=status[:K * U].reshape(K, U), nPath=nPath, pathArcs=arcs, kernel_ms=self.kernel_ms())
+
+    def fb_max(self, settings, stream=None) -> dict:
+        """LatForwBackw(LATFB_MAX): fw[u], bw[u] as [nNodes, K] arrays, best [K, U]."""
+        sc = lat_scales(settings); K, U = len(sc), len(self)
+        nn, _, noff, _ = self._offsets()
+        TN = int(noff[-1])
+        fw, bw, best = np.zeros(max(K * TN, 1)), np.zeros(max(K * TN, 1)), np.zeros(max(K * U, 1))
+        out = LatFbOut(_p(fw), _p(bw), _p(best))
+        check(lib().htkamd_latset_fb_max(self.h, C.c_int(K), sc, C.byref(out), _stream(stream)), "latset_fb_max")
+        cut = lambda a: [a[K * noff[u]:K * noff[u + 1]].reshape(int(nn[u]), K) for u in range(U)]
+        return dict(fw=cut(fw), bw=cut(bw), best=best[:K * U].reshape(K, U), kernel_ms=self.kernel_ms())
+
+    def prune(self, settings, thresh, arcs_per_sec=None, stream=None) -> dict:
+        """LatPrune's survivors: keep_node[k][u], keep_arc[k][u] as boolean arrays."""
+        sc = lat_scales(settings); K, U = len(sc), len(self)
+        _, _, noff, aoff = self._offsets()
+        TN, TA = int(noff[-1]), int(aoff[-1])
+        th = np.ascontiguousarray(np.broadcast_to(np.asarray(thresh, np.float64), (K,)))
+        aps = np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if arcs_per_sec is None else arcs_per_sec, np.float32), (K,)))
+        kn, ka = np.zeros(max(K * TN, 1), np.uint8), np.zeros(max(K * TA, 1), np.uint8)
+        check(lib().htkamd_latset_prune(self.h, C.c_int(K), sc, _p(th), _p(aps), _p(kn), _p(ka), _stream(stream)), "latset_prune")
+        return dict(keep_node=[[kn[k * TN + noff[u]:k * TN + noff[u + 1]].astype(bool) for u in range(U)] for k in range(K)],
+                    keep_arc=[[ka[k * TA + aoff[u]:k * TA + aoff[u + 1]].astype(bool) for u in range(U)] for k in range(K)], kernel_ms=self.kernel_ms())
+
+    def trans(self, u: int, setting, arcs) -> "Trans":
+        """LatFindBest's label list for a path of lattice u."""
+        a = np.ascontiguousarray(arcs, np.int32)
+        t = Trans.__new__(Trans)
+        t.h = C.c_void_p()
+        check(lib().htkamd_latset_trans(self.h, C.c_int(u), lat_scales([setting]), _p(a), C.c_int(len(a)), C.byref(t.h)), "latset_trans")
+        return t
+
+    def best_ids(self, results: "Results", best: dict):
+        """The K x U best paths as hyps[k][u] id arrays for Results.score."""
+        U = len(self); K = len(best["paths"])
+        cap = int(best["nPath"].sum()) + 1
+        off, ids = np.zeros(K * U + 1, np.int32), np.zeros(cap, np.int32)
+        n = lib().htkamd_latset_best_ids(self.h, results.h, C.c_int(K), _p(best["nPath"]), _p(best["pathArcs"]), _p(off), _p(ids), C.c_int(cap))
+        if n < 0:
+            check(n, "latset_best_ids")
+        return [[ids[off[k * U + u]:off[k * U + u + 1]].copy() for u in range(U)] for k in range(K)]
+
+    def write(self, u: int, setting, path: str, node_score=None, fmt: str = None):
+        ns = None if node_score is None else np.ascontiguousarray(node_score, np.float64)
+        bits = 0 if fmt is None else sum(LAT_FORMAT.get(c, 0) for c in fmt)
+        check(lib().htkamd_latset_write(self.h, C.c_int(u), lat_scales([setting]), _p(ns), path.encode(), C.c_int(bits)), "latset_write")
+
+    def __del__(self):
+        try:
+            if self.h:
+                lib().htkamd_latset_destroy(self.h); self.h = C.c_void_p()
+        except Exception:
+            pass

@@ -4,6 +4,7 @@
 
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
 #include "../../include/htk_amd.h"
 
 #ifdef __cplusplus
@@ -20,6 +21,10 @@ extern "C" {
 #define LMINMIX  (-11.5129254649702)
 
 void htkamd_set_error(const char *fmt, ...);
+
+/* ---- the SLF text both lattice writers share (htk_amd/host/slfout.c) ---- */
+void htkamd_slf_put_word(FILE *f, const char *s);                               /* "W=%-19s ", quoted only when needed */
+void htkamd_slf_sort_arcs(int *order, int nArcs, const int *arcStart, const int *arcEnd, const int *nodeRank);   /* QSCmpArcs (HNet.c:466) */
 
 /* ---- host-side preparation (htk_amd/host/prep.c) ---- */
 void   htkamd_host_fix_diag_gconst(int D, const float *var, float *gconst);   /* HModel.c:5641 */

@@ -13,9 +13,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../csrc/internal.h"
+#include "../csrc/latrescore.h"
 
 static const htkamd_lattice *g_lat;                /* qsort context (the reference's `slat`) */
-static const int *g_rank;
 
 static int cmp_nodes(const void *v1, const void *v2)
 {
@@ -24,33 +24,13 @@ static int cmp_nodes(const void *v1, const void *v2)
    if (tdiff == 0.0) { if (sdiff == 0.0) return s1 - s2; return sdiff > 0.0 ? 1 : -1; }
    return tdiff > 0.0 ? 1 : -1;
 }
-static int cmp_arcs(const void *v1, const void *v2)
-{
-   const int s1 = *(const int *)v1, s2 = *(const int *)v2;
-   const int j = g_rank[g_lat->arcEnd[s1]] - g_rank[g_lat->arcEnd[s2]], k = g_rank[g_lat->arcStart[s1]] - g_rank[g_lat->arcStart[s2]];
-   if (k == 0 && j == 0) return s1 - s2;
-   return j == 0 ? k : j;
-}
-
-static void put_word(FILE *f, const char *s)          /* "W=%-19s " with ReWriteString(.., NULL, ESCAPE_CHAR): quotes only when needed */
-{
-   char buf[1100]; int n = 0, need = 0;
-   for (const char *p = s; *p; p++) if (*p == ' ' || *p == '"' || *p == '\'' || *p == '\\' || (unsigned char)*p < 33 || (unsigned char)*p > 126) need = 1;
-   if (!need) { fprintf(f, "W=%-19s ", s); return; }
-   buf[n++] = '"';
-   for (const char *p = s; *p && n < 1090; p++) { if (*p == '"' || *p == '\\') buf[n++] = '\\'; buf[n++] = *p; }
-   buf[n++] = '"'; buf[n] = 0;
-   fprintf(f, "W=%-19s ", buf);
-}
-
 /* LArcTotLike (HNet.h:257): the three scaled likelihoods summed in float, the word penalty added in DOUBLE (the macro's `? 0.0 :
    wdpenalty` makes the last operand a double) -- TranscriptionFromLattice accumulates that double in its backward scores and in the
    A* search (HRec.c:2176-2290); only the label's score is a float */
 static double arc_total_like(const htkamd_lattice *lat, int arc)
 {
    const int pron = lat->nodePron[lat->arcEnd[arc]];
-   const float ac = lat->arcAc[arc] * 1.0f, lm = lat->arcLm[arc] * lat->lmScale, pr = lat->arcPr[arc] * lat->prScale;
-   return (double)((ac + lm) + pr) + (pron < 0 ? 0.0 : (double)lat->wordPen);
+   return htkamd_larc_tot_like(lat->arcAc[arc], lat->arcLm[arc], lat->arcPr[arc], 1.0f, lat->lmScale, lat->prScale, lat->wordPen, pron < 0);
 }
 
 float htkamd_lattice_arc_score(const htkamd_lattice *lat, int arc) { return (float)arc_total_like(lat, arc); }
@@ -87,14 +67,12 @@ int htkamd_lattice_write_align(const htkamd_lattice *lat, const htkamd_lattice_a
       fprintf(f, "I=%-4d ", i);
       if (format & HTKAMD_LAT_TIMES) fprintf(f, "t=%-5.2f ", (float)(lat->nodeFrame[n] * lat->frameDur));
       if (pron >= 0) {
-         put_word(f, htkamd_net_word_name(net, pron));
+         htkamd_slf_put_word(f, htkamd_net_word_name(net, pron));
          if (format & HTKAMD_LAT_PRON) fprintf(f, "v=%-2d ", htkamd_net_pron_num(net, pron));
       } else fprintf(f, "W=%-19s ", "!NULL");
       fprintf(f, "\n");
    }
-   for (int i = 0; i < na; i++) order[i] = i;
-   g_rank = rorder;
-   qsort(order, (size_t)na, sizeof(int), cmp_arcs);
+   htkamd_slf_sort_arcs(order, na, lat->arcStart, lat->arcEnd, rorder);
    for (int i = 0; i < na; i++) {
       const int a = order[i];
       fprintf(f, "J=%-5d S=%-4d E=%-4d ", i, rorder[lat->arcStart[a]], rorder[lat->arcEnd[a]]);
@@ -118,7 +96,7 @@ int htkamd_lattice_write_align(const htkamd_lattice *lat, const htkamd_lattice_a
       fprintf(f, "\n");
    }
    free(order); free(rorder);
-   g_lat = NULL; g_rank = NULL;
+   g_lat = NULL;
    if (fclose(f)) { htkamd_set_error("lattice_write: write error on %s", path); return HTKAMD_EIO; }
    return HTKAMD_OK;
 }

@@ -1409,6 +1409,71 @@ typedef struct {
 /* path NULL = stdout; append: add to the file instead of replacing it */
 int  htkamd_results_write(const htkamd_results *r, const htkamd_results_report *rep, const char *path, int append);
 
+/* ------------------------------------------------------------------------------------------
+ * Rescoring lattices: replaces HLRescore (HTKTools/HLRescore.c) -f / -t / -u / -w for U lattices under a grid of K settings
+ * {acscale -a, lmscale -s, wdpenalty -p, prscale -r} in ONE call (csrc/latrescore.hip; files, orders, labels and text: host/latrescore.c).
+ *   ReadLattice (HNet.c:1230)         htkamd_latset_add_file: header, I= lines with t= W= v=, J= lines with S= E= W= v= a= l= r= d= (the alignment
+ *                                     records travel with their arcs); what ReadLattice refuses is refused with its reason; sub-lattices (SUBLAT=, L=) and
+ *                                     binary fields (~) are refused by name.  htkamd_latset_add: a lattice from the decoder's arrays
+ *   LatStartNode / LatEndNode /       done once per lattice when it is added: the node order of the depth-first walk from the end node
+ *   LatTopSort (HLat.c:367-455)       over the pred lists (an arc joins the FRONT of its nodes' lists as its J= line is read), the order in
+ *                                     which the forward loop meets arcs (nodes in that order, each foll list front to back) and its mirror;
+ *                                     a cyclic lattice is HTKAMD_EMODEL with LatTopSort's message
+ *   LatFindBest (HLat.c:575)          htkamd_latset_best: per (k, u) the best path's arcs, start to end, and the ac lm pr tot sums of -T 4;
+ *                                     of two equally good arcs into a node the first met stays (score > end->score)
+ *   LatForwBackw (.., LATFB_MAX :490) htkamd_latset_fb_max: Fw, Bw per node and best = Bw[first node of the order]
+ *   LatPrune (HLat.c:711)             htkamd_latset_prune: keep flags per node and arc (beamPruneArcs = T, HLat.c:77), the arcs-per-second
+ *                                     histogram included; htkamd_latset_add_pruned compacts the survivors into another set
+ *   LatSetScores (HLat.c:688)         htkamd_latset_fb_max on the pruned set: score = Fw + Bw
+ *   WriteLattice (HNet.c:631)         htkamd_latset_write
+ * LArcTotLike (HNet.h:257) is float arithmetic plus a double word penalty, added to fp64 node scores in the reference's order: every
+ * number compares bit for bit.  Per-node arrays of K settings are INTERLEAVED: node n of lattice u under setting k stands at
+ * K * nodeOff[u] + n * K + k (nodeOff = the nodes of the lattices before u), so that a wavefront's lanes touch neighbouring addresses.
+ * Not served, each refused by name (htkamd_latset_check_switch): -n / -wn (LatExpand), -m, -c, -I, -d, -P, FIXBADLATS; LATFB_SUM
+ * is reached by no switch of the tool.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct htkamd_latset htkamd_latset;
+typedef struct { float acScale, lmScale, wordPen, prScale; } htkamd_lat_scales;
+int  htkamd_latset_create(const char *dictPath, const char *startWord, const char *endWord, htkamd_latset **out);
+int  htkamd_latset_create_like(const htkamd_latset *src, htkamd_latset **out);      /* an empty set over the same dictionary */
+void htkamd_latset_destroy(htkamd_latset *s);
+int  htkamd_latset_add_file(htkamd_latset *s, const char *path);                    /* returns the lattice's index (>= 0) or HTKAMD_E* */
+int  htkamd_latset_add(htkamd_latset *s, const htkamd_lattice *lat, const htkamd_net *net);
+/* LatPrune's new lattice: the nodes and arcs of src's lattice u whose flags are set, in their order, renumbered */
+int  htkamd_latset_add_pruned(htkamd_latset *dst, const htkamd_latset *src, int u, const unsigned char *keepNode, const unsigned char *keepArc);
+int  htkamd_latset_count(const htkamd_latset *s);
+int  htkamd_latset_check_switch(const char *sw);
+int  htkamd_latset_tile(void);            /* nodes of a lattice whose scores a lane keeps in LDS; a larger lattice goes through global scratch */
+typedef struct {
+   int nNodes, nArcs, start, end;
+   const double *nodeTime; const int *nodeWord, *nodeVar;      /* nodeWord: index for htkamd_latset_word_name, 0 = !NULL */
+   const int *arcStart, *arcEnd; const float *arcAc, *arcLm, *arcPr;
+   const int *topOrder;                   /* [nNodes] LatTopSort */
+   const int *fwdArcs, *bwdArcs;          /* [nArcs] arcs as the forward / backward loop meets them */
+} htkamd_latset_view;
+int  htkamd_latset_get(const htkamd_latset *s, int u, htkamd_latset_view *out);
+const char *htkamd_latset_word_name(const htkamd_latset *s, int word);
+/* Outputs for pair (k, u): nPath / status [k * U + u] (status 1, or 0 where no arc leads into the end node: an empty path), the path's arcs
+ * at pathArcs[k * totalNodes + nodeOff[u] ..], totals [4 * (k * U + u)] = ac lm pr tot.  Synchronises `stream`. */
+typedef struct { int *nPath, *status, *pathArcs; double *totals; } htkamd_latset_best_out;
+int  htkamd_latset_best(htkamd_latset *s, int K, const htkamd_lat_scales *scales, const htkamd_latset_best_out *out, void *stream);
+/* fw, bw: [K * totalNodes], interleaved (above); best [K * U] */
+typedef struct { double *fw, *bw, *best; } htkamd_latset_fb_out;
+int  htkamd_latset_fb_max(htkamd_latset *s, int K, const htkamd_lat_scales *scales, const htkamd_latset_fb_out *out, void *stream);
+/* keepNode [k * totalNodes + nodeOff[u] + n], keepArc [k * totalArcs + arcOff[u] + a]; thresh / arcsPerSec [K]: -t f [a] */
+int  htkamd_latset_prune(htkamd_latset *s, int K, const htkamd_lat_scales *scales, const double *thresh, const float *arcsPerSec,
+                         unsigned char *keepNode, unsigned char *keepArc, void *stream);
+double htkamd_latset_last_kernel_ms(const htkamd_latset *s);
+/* LatFindBest's label list for one path: outSym of the pronunciation v=, the word's name where that variant is missing; null words and
+ * empty output symbols give no label; times = node time * 1e7; score = (float)LArcTotLike */
+int  htkamd_latset_trans(const htkamd_latset *s, int u, const htkamd_lat_scales *sc, const int *arcs, int nArcs, htkamd_trans **out);
+/* K x U best paths -> the hypOff [K*U + 1] / hypIds arrays of htkamd_results_score (pair k * U + u); returns the number of ids, which may
+ * exceed cap (nothing past cap is written), or HTKAMD_E* */
+int  htkamd_latset_best_ids(const htkamd_latset *s, htkamd_results *r, int K, const int *nPath, const int *pathArcs, int *hypOff, int *hypIds, int cap);
+/* WriteLattice with the header scales as HLRescore sets them; nodeScore [nNodes] (LatSetScores) or NULL = zeros (SORTLATTICE = F);
+ * format: HTKAMD_LAT_* bits, 0 = HLRescore's default (HLAT_DEFAULT | HLAT_PRLIKE: t v a l d m n r) */
+int  htkamd_latset_write(const htkamd_latset *s, int u, const htkamd_lat_scales *sc, const double *nodeScore, const char *path, int format);
+
 #ifdef __cplusplus
 }
 #endif
