@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../csrc/internal.h"
+#include "htktext.h"
 
 #define MACHASHSIZE 250007                      /* HModel.h:50 */
 
@@ -133,17 +134,16 @@ static int acc_walk(FILE *f, int wr, const htkamd_model_desc *d, const htkamd_ac
    for (k = 0; k < d->numPhys; k++) {
       const int h = order[k], ti = d->hmmTrans[h], N = d->transN[ti];
       if (wr) {
-         const char *p;
-         fputc('"', f);
-         for (p = names[h]; *p; p++) { if (*p == '"' || *p == '\\') fputc('\\', f); fputc(*p, f); }
-         fputc('"', f); fputc('\n', f);
+         htx_write_string(f, names[h], '"', 0); fputc('\n', f);      /* WriteString(.., DBL_QUOTE) HTrain.c:1369 */
          put_i(f, (int)(vec[lay->nEgs + h] + 0.5));
       } else {
-         char buf[512]; int n = 0, ch, negs;
-         if (fgetc(f) != '"') { rc = HTKAMD_EINVAL; goto bad; }
-         while ((ch = fgetc(f)) != EOF && ch != '"' && n < 510) { if (ch == '\\') ch = fgetc(f); buf[n++] = (char)ch; }
-         buf[n] = 0;
-         if (ch != '"' || fgetc(f) != '\n' || strcmp(buf, names[h]) != 0) {      /* CheckPName HTrain.c:1600 */
+         char buf[1024] = "", *line = NULL; size_t capLine = 0; int negs;
+         const ssize_t got = getline(&line, &capLine, f);      /* the name's line: WriteString leaves no raw newline inside it */
+         htx_src src = {line, line + (got > 0 ? got : 0), 0};
+         const int ok = got > 0 && htx_read_string(&src, HTX_LINE, NULL, buf, sizeof(buf)) == HTX_GOT && src.wasQuoted && src.p + 1 == src.end;
+         free(line);
+         if (got <= 0) { rc = HTKAMD_EINVAL; goto bad; }
+         if (!ok || strcmp(buf, names[h]) != 0) {      /* CheckPName HTrain.c:1600 */
             htkamd_set_error("accs_load_file: %s: expected HMM \"%s\", found \"%s\"", path, names[h], buf);
             rc = HTKAMD_EINVAL; goto bad2;
          }
@@ -260,11 +260,9 @@ int htkamd_stats_write_file(const htkamd_model_desc *d, const double *vec, const
    htkamd_hmm_scan_order(names, d->numPhys, order);
    for (int k = 0; k < d->numPhys; k++) {
       const int h = order[k], N = d->transN[d->hmmTrans[h]];
-      char buf[1024]; int n = 0;
-      buf[n++] = '"';
-      for (const char *p = names[h]; *p && n < 1000; p++) { if (*p == '"' || *p == '\\') buf[n++] = '\\'; buf[n++] = *p; }
-      buf[n++] = '"'; buf[n] = 0;
-      fprintf(f, "%4d %14s %4d ", k + 1, buf, (int)(vec[lay.nEgs + h] + 0.5));
+      fprintf(f, "%4d ", k + 1);
+      htx_write_string(f, names[h], '"', 14);
+      fprintf(f, " %4d ", (int)(vec[lay.nEgs + h] + 0.5));
       const int NS = d->numStreams > 1 ? d->numStreams : 1;
       for (int j = 0; j < N - 2; j++) fprintf(f, " %10f", (float)vec[lay.wtOcc + (size_t)d->hmmState[d->hmmStateOff[h] + j] * NS]);      /* the first stream's WtAcc (PrintStats HERest.c:690) */
       fprintf(f, "\n");

@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../csrc/internal.h"
+#include "htktext.h"
 
 struct htkamd_labels {
    int n;
@@ -33,22 +34,25 @@ static int is_number(const char *t)
    return *e == 0;
 }
 
-/* one label line -> appended to L; returns 0, or 1 for the alternative separator */
-static int add_line(struct htkamd_labels *L, int *cap, char *line)
+/* One label line, split as LoadHTKList (HLabel.c:748) splits it: [start [end]] name [score] {aux}, every token a ReadString string; a token
+   that stood in quotes is never a number.  Appended to L; returns 0, 1 for the alternative separator, or an error code. */
+static int add_line(struct htkamd_labels *L, int *cap, htx_src *s, const char *path)
 {
-   char *tok[8]; int nt = 0;
-   for (char *p = strtok(line, " \t\r\n"); p && nt < 8; p = strtok(NULL, " \t\r\n")) tok[nt++] = p;
+   char tok[8][1024]; int quoted[8], nt = 0, r;
+   while (nt < 8 && (r = htx_read_string(s, HTX_LINE, NULL, tok[nt], sizeof(tok[nt]))) == HTX_GOT) quoted[nt++] = s->wasQuoted;
+   if (nt < 8 && r < 0) { htkamd_set_error("%s: label %d: %s", path, L->n + 1, htx_result_text(r)); return HTKAMD_EMODEL; }
+   htx_skip_line(s);
    if (nt == 0) return 0;
-   if (!strcmp(tok[0], "///")) return 1;
+   if (!quoted[0] && !strcmp(tok[0], "///")) return 1;
+#define IS_NUM(k) (!quoted[k] && is_number(tok[k]))
    long long st = -1, en = -1; float sc = 0.0f; int k = 0;
-   if (nt >= 2 && is_number(tok[0]) && (isdigit((unsigned char)tok[0][0]) || tok[0][0] == '-')) {
+   if (nt >= 2 && IS_NUM(0) && (isdigit((unsigned char)tok[0][0]) || tok[0][0] == '-')) {
       st = atoll(tok[k++]);
-      if (nt >= 3 && is_number(tok[1])) en = atoll(tok[k++]);
+      if (nt >= 3 && IS_NUM(1)) en = atoll(tok[k++]);
    }
-   char *name = tok[k++];
-   size_t L0 = strlen(name);
-   if (L0 >= 2 && (name[0] == '"' || name[0] == '\'') && name[L0 - 1] == name[0]) { name[L0 - 1] = 0; name++; }
-   if (k < nt && is_number(tok[k])) sc = strtof(tok[k], NULL);
+   const char *name = tok[k++];
+   if (k < nt && IS_NUM(k)) sc = strtof(tok[k], NULL);
+#undef IS_NUM
    if (L->n + 1 > *cap) {
       *cap = *cap * 2 + 32;
       L->name = (char **)realloc(L->name, sizeof(char *) * (size_t)*cap);
@@ -58,6 +62,31 @@ static int add_line(struct htkamd_labels *L, int *cap, char *line)
    }
    L->name[L->n] = strdup(name); L->start[L->n] = st; L->end[L->n] = en; L->score[L->n] = sc; L->n++;
    return 0;
+}
+
+/* the label lines up to the end of the text or, inside an MLF, up to a line that holds a single "."; only the first alternative is kept */
+static int read_list(struct htkamd_labels *L, htx_src *s, int mlf, const char *path)
+{
+   int cap = 0, alt = 0;
+   while (s->p < s->end) {
+      const char *q = s->p;
+      while (q < s->end && isspace((unsigned char)*q) && *q != '\n') q++;
+      if (mlf && q < s->end && *q == '.' && (q + 1 == s->end || isspace((unsigned char)q[1]))) { htx_skip_line(s); break; }
+      if (alt) { htx_skip_line(s); continue; }
+      const int r = add_line(L, &cap, s, path);
+      if (r < 0) return r;
+      alt = r;
+   }
+   return HTKAMD_OK;
+}
+
+static char *read_text(const char *path, const char *who, size_t *len, int *rc)
+{
+   int why;
+   char *txt = htx_read_file(path, len, &why);
+   if (!txt && why == HTX_ENOMEM) { htkamd_set_error("%s: out of memory reading %s", who, path); *rc = HTKAMD_ENOMEM; }
+   else if (!txt) { htkamd_set_error("%s: cannot open %s", who, path); *rc = HTKAMD_EIO; }
+   return txt;
 }
 
 void htkamd_labels_free(struct htkamd_labels *L)
@@ -70,16 +99,14 @@ void htkamd_labels_free(struct htkamd_labels *L)
 int htkamd_labels_read(const char *path, struct htkamd_labels **out)
 {
    if (!path || !out) { htkamd_set_error("labels_read: NULL argument"); return HTKAMD_EINVAL; }
-   FILE *f = fopen(path, "r");
-   if (!f) { htkamd_set_error("labels_read: cannot open %s", path); return HTKAMD_EIO; }
+   size_t len; int rc;
+   char *txt = read_text(path, "labels_read", &len, &rc);
+   if (!txt) return rc;
    struct htkamd_labels *L = (struct htkamd_labels *)calloc(1, sizeof(*L));
-   int cap = 0, alt = 0;
-   char line[2048];
-   while (fgets(line, sizeof(line), f)) {
-      if (alt) continue;
-      if (add_line(L, &cap, line)) alt = 1;
-   }
-   fclose(f);
+   htx_src s = {txt, txt + len, 0};
+   rc = read_list(L, &s, 0, path);
+   free(txt);
+   if (rc) { htkamd_labels_free(L); return rc; }
    *out = L;
    return HTKAMD_OK;
 }
@@ -110,35 +137,34 @@ void htkamd_mlf_free(struct htkamd_mlf *m)
 int htkamd_mlf_read(const char *path, struct htkamd_mlf **out)
 {
    if (!path || !out) { htkamd_set_error("mlf_read: NULL argument"); return HTKAMD_EINVAL; }
-   FILE *f = fopen(path, "r");
-   if (!f) { htkamd_set_error("mlf_read: cannot open %s", path); return HTKAMD_EIO; }
-   char line[2048];
-   if (!fgets(line, sizeof(line), f) || strncmp(line, "#!MLF!#", 7)) { fclose(f); htkamd_set_error("mlf_read: %s has no #!MLF!# header", path); return HTKAMD_EMODEL; }
+   size_t len; int rc;
+   char *txt = read_text(path, "mlf_read", &len, &rc);
+   if (!txt) return rc;
+   if (strncmp(txt, "#!MLF!#", 7)) { free(txt); htkamd_set_error("mlf_read: %s has no #!MLF!# header", path); return HTKAMD_EMODEL; }
+   htx_src s = {txt, txt + len, 0};
+   htx_skip_line(&s);
    struct htkamd_mlf *m = (struct htkamd_mlf *)calloc(1, sizeof(*m));
    int capM = 0;
-   while (fgets(line, sizeof(line), f)) {
-      char *p = line;
-      while (isspace((unsigned char)*p)) p++;
-      if (!*p) continue;
-      char *e = p + strlen(p);
-      while (e > p && isspace((unsigned char)e[-1])) *--e = 0;
-      if (strstr(p, "->") || strstr(p, "=>")) { fclose(f); htkamd_mlf_free(m); htkamd_set_error("mlf_read: %s: sub-directory entries are not supported", path); return HTKAMD_EMODEL; }
-      if ((*p == '"' || *p == '\'') && e > p + 1 && e[-1] == *p) { e[-1] = 0; p++; }
+   char pattern[1024];
+   rc = HTKAMD_OK;
+   while (!rc) {
+      while (s.p < s.end && isspace((unsigned char)*s.p)) s.p++;
+      if (s.p >= s.end) break;
+      const char *eol = (const char *)memchr(s.p, '\n', (size_t)(s.end - s.p));
+      if (!eol) eol = s.end;
+      for (const char *q = s.p; q + 1 < eol && !rc; q++)
+         if ((q[0] == '-' || q[0] == '=') && q[1] == '>') { htkamd_set_error("mlf_read: %s: sub-directory entries are not supported", path); rc = HTKAMD_EMODEL; }
+      if (rc) break;
+      const int r = htx_read_string(&s, HTX_LINE, NULL, pattern, sizeof(pattern));      /* a ReadString string (HLabel.c:1203) */
+      if (r != HTX_GOT) { htkamd_set_error("mlf_read: %s: pattern %d: %s", path, m->n + 1, htx_result_text(r)); rc = HTKAMD_EMODEL; break; }
+      htx_skip_line(&s);
       if (m->n + 1 > capM) { capM = capM * 2 + 32; m->pattern = (char **)realloc(m->pattern, sizeof(char *) * (size_t)capM); m->lab = (struct htkamd_labels **)realloc(m->lab, sizeof(void *) * (size_t)capM); }
-      char *pattern = strdup(p);                     /* `line` is reused for the label lines below */
       struct htkamd_labels *L = (struct htkamd_labels *)calloc(1, sizeof(*L));
-      int cap = 0, alt = 0, closed = 0;
-      while (fgets(line, sizeof(line), f)) {
-         char *q = line;
-         while (isspace((unsigned char)*q)) q++;
-         if (q[0] == '.' && (q[1] == 0 || isspace((unsigned char)q[1]))) { closed = 1; break; }
-         if (alt) continue;
-         if (add_line(L, &cap, line)) alt = 1;
-      }
-      (void)closed;                                  /* a last entry may end at EOF without '.' */
-      m->pattern[m->n] = pattern; m->lab[m->n] = L; m->n++;
+      m->pattern[m->n] = strdup(pattern); m->lab[m->n] = L; m->n++;
+      rc = read_list(L, &s, 1, path);                /* a last entry may end at EOF without '.' */
    }
-   fclose(f);
+   free(txt);
+   if (rc) { htkamd_mlf_free(m); return rc; }
    *out = m;
    return HTKAMD_OK;
 }
@@ -327,18 +353,7 @@ int htkamd_trans_format(struct htkamd_trans *t, double frameDur, int states, int
    return HTKAMD_OK;
 }
 
-static void write_name(FILE *f, const char *s)               /* WriteString with q = 0 (HShell.c:1268): quote only names that start with one */
-{
-   int q = 0;
-   if (s[0] == '"') q = '\''; else if (s[0] == '\'') q = '"';
-   if (q) fputc(q, f);
-   for (const unsigned char *p = (const unsigned char *)s; *p; p++) {
-      if (*p == '\\' || (q && *p == q)) { fputc('\\', f); fputc(*p, f); }
-      else if (*p >= 32 && *p < 127) fputc(*p, f);
-      else fprintf(f, "\\%c%c%c", ((*p / 64) % 8) + '0', ((*p / 8) % 8) + '0', (*p % 8) + '0');
-   }
-   if (q) fputc(q, f);
-}
+static void write_name(FILE *f, const char *s) { htx_write_string(f, s, 0, 0); }      /* WriteString with q = 0 (HShell.c:1268) */
 
 static void trans_print_one(FILE *f, const struct htkamd_trans *t);
 static void trans_print(FILE *f, const struct htkamd_trans *t)

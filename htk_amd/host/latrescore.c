@@ -12,76 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../csrc/latrescore.h"
-
-/* ------------------------------------------------------------------------------------------ source text */
-typedef struct { const char *p, *end; } src_t;
-enum { F_FIELD = 1, F_EOL = 0, F_EOF = -1, F_DOT = 2, F_ERR = -2 };
-
-/* ReadString (HShell.c): a quoted string, or up to white space; a backslash takes the next character (or three octal digits) literally */
-static int read_string(src_t *s, char *buf, size_t nb)
-{
-   size_t n = 0;
-   while (s->p < s->end && isspace((unsigned char)*s->p) && *s->p != '\n') s->p++;
-   if (s->p >= s->end || *s->p == '\n') return 0;
-   char q = 0;
-   if (*s->p == '"' || *s->p == '\'') q = *s->p++;
-   while (s->p < s->end) {
-      char c = *s->p;
-      if (q ? c == q : isspace((unsigned char)c)) break;
-      if (q && c == '\n') break;
-      s->p++;
-      if (c == '\\' && s->p < s->end) {
-         c = *s->p++;
-         if (c >= '0' && c <= '7' && s->p + 1 < s->end && s->p[0] >= '0' && s->p[0] <= '7' && s->p[1] >= '0' && s->p[1] <= '7') {
-            c = (char)(((c - '0') << 6) | ((s->p[0] - '0') << 3) | (s->p[1] - '0'));
-            s->p += 2;
-         }
-      }
-      if (n + 1 < nb) buf[n++] = c;
-   }
-   if (q && s->p < s->end && *s->p == q) s->p++;
-   buf[n] = 0;
-   return 1;
-}
-
-/* GetNextFieldName + GetFieldValue (HNet.c:707-767) */
-static int next_field(src_t *s, const char *path, char *name, size_t nn, char *val, size_t nv)
-{
-   while (s->p < s->end && isspace((unsigned char)*s->p) && *s->p != '\n') s->p++;
-   if (s->p >= s->end) return F_EOF;
-   if (*s->p == '\n') { s->p++; return F_EOL; }
-   if (*s->p == '.') { s->p++; return F_DOT; }
-   if (!isalnum((unsigned char)*s->p)) {
-      if (*s->p != '#') { htkamd_set_error("%s: GetNextFieldName: Field name expected (8250)", path); return F_ERR; }
-      while (s->p < s->end && *s->p != '\n') s->p++;
-      if (s->p < s->end) s->p++;
-      return F_EOL;
-   }
-   size_t n = 0;
-   while (s->p < s->end && isalnum((unsigned char)*s->p)) { if (n + 1 < nn) name[n++] = *s->p; s->p++; }
-   name[n] = 0;
-   if (s->p >= s->end) { htkamd_set_error("%s: GetNextFieldName: EOF whilst reading field name (8250)", path); return F_ERR; }
-   if (*s->p == '~') { htkamd_set_error("%s: field %s is binary (~): binary lattices are not supported", path, name); return F_ERR; }
-   if (*s->p != '=') { htkamd_set_error("%s: GetNextFieldName: Field delimiter expected %s|%c| (8250)", path, name, *s->p); return F_ERR; }
-   s->p++;
-   if (s->p >= s->end || isspace((unsigned char)*s->p)) { htkamd_set_error("%s: GetFieldValue: Field value expected (8250)", path); return F_ERR; }
-   read_string(s, val, nv);
-   return F_FIELD;
-}
-
-/* ParseNumber (HNet.c:770) */
-static int parse_number(const char *buf, double *out, int wantInt, const char *path, char field)
-{
-   char *e;
-   if (!(isdigit((unsigned char)buf[0]) || ((buf[0] == '-' || buf[0] == '+') && isdigit((unsigned char)buf[1])))) {
-      htkamd_set_error("%s: %s: %c field expects numeric value (%s) (8250)", path, wantInt ? "GetIntField" : "GetFltField", field, buf);
-      return HTKAMD_EMODEL;
-   }
-   *out = strtod(buf, &e);
-   if (wantInt && !(*out >= -2147483647.0 && *out <= 2147483647.0)) { htkamd_set_error("%s: GetIntField: %c field value out of range (%s) (8250)", path, field, buf); return HTKAMD_EMODEL; }
-   if (wantInt && strchr(buf, '.')) { htkamd_set_error("%s: GetIntField: %c field expects integer value (%s) (8250)", path, field, buf); return HTKAMD_EMODEL; }
-   return HTKAMD_OK;
-}
+#include "htktext.h"
 
 static void align_free(htkamd_lat_align *al, int n) { for (int i = 0; al && i < n; i++) free(al[i].label); free(al); }
 
@@ -178,68 +109,37 @@ static void dict_release(htkamd_lat_dict *d)
    free(d->word); free(d->hash); free(d);
 }
 
-static char *read_file(const char *path, size_t *len)
-{
-   FILE *f = fopen(path, "rb");
-   if (!f) return NULL;
-   size_t cap = 1 << 16, n = 0;
-   char *b = (char *)malloc(cap + 1);
-   while (b) {
-      const size_t got = fread(b + n, 1, cap - n, f);
-      n += got;
-      if (got == 0) break;
-      if (n == cap) { char *nb = (char *)realloc(b, 2 * cap + 1); if (!nb) { free(b); b = NULL; break; } b = nb; cap *= 2; }
-   }
-   fclose(f);
-   if (!b) { *len = 0; return NULL; }
-   b[n] = 0; *len = n;
-   return b;
-}
-
 /* ReadDict / ReadDictWord (HDict.c:224-327): WORD ['['OUTSYM']'] [PRONPROB] PHONE ...; a pronunciation's number is its place in its
    word's list (NewPron :151) */
 static int dict_read(htkamd_lat_dict *d, const char *path)
 {
-   size_t len;
-   char *txt = read_file(path, &len);
-   if (!txt) { htkamd_set_error("latset_create: ReadDict: Can't open file %s (8010) (or out of memory)", path); return HTKAMD_EIO; }
-   src_t s = {txt, txt + len};
-   char buf[1024], word[1024];
-   int rc = HTKAMD_OK;
-   while (s.p < s.end && !rc) {
-      if (!read_string(&s, word, sizeof(word))) { if (s.p < s.end) s.p++; continue; }
-      char *outSym = NULL; int haveOut = 0, nPhones = 0, haveProb = 0;
-      while (read_string(&s, buf, sizeof(buf))) {
-         const size_t bl = strlen(buf);
-         if (bl >= 2 && buf[0] == '[' && buf[bl - 1] == ']') {
-            if (haveOut || nPhones) { htkamd_set_error("%s: ReadDict: Only single outsym allowed for word %s (8050)", path, word); rc = HTKAMD_EMODEL; break; }
-            buf[bl - 1] = 0; haveOut = 1;
-            free(outSym); outSym = buf[1] ? strdup(buf + 1) : NULL;
-            if (buf[1] && !outSym) { htkamd_set_error("latset_create: out of memory"); rc = HTKAMD_ENOMEM; break; }
-            continue;
-         }
-         char *e = buf;
-         double v = 0.0;
-         if (nPhones == 0 && !haveProb) v = strtod(buf, &e);
-         if (e != buf) {
-            if (v <= 0.0 || v > 1.0 || *e) { htkamd_set_error("%s: ReadDict: Probability malformed %s (8050)", path, buf); rc = HTKAMD_EMODEL; break; }
-            haveProb = 1;
-         } else nPhones++;
-      }
-      if (rc) { free(outSym); break; }
-      const int w = dict_word(d, word);
-      if (w < 0) { free(outSym); htkamd_set_error("latset_create: out of memory"); rc = HTKAMD_ENOMEM; break; }
+   size_t len; int why;
+   char *txt = htx_read_file(path, &len, &why);
+   if (!txt) {
+      if (why == HTX_ENOMEM) { htkamd_set_error("latset_create: out of memory"); return HTKAMD_ENOMEM; }
+      htkamd_set_error("latset_create: ReadDict: Can't open file %s (8010)", path); return HTKAMD_EIO;
+   }
+   htx_src s = {txt, txt + len, 0};
+   htx_dict_entry e = {0};
+   int rc;
+   while ((rc = htx_dict_next(&s, path, &e)) == HTX_GOT) {
+      rc = HTKAMD_ENOMEM;
+      const int w = dict_word(d, e.word);
+      if (w < 0) break;
       htkamd_lat_word *W = &d->word[w];
       htkamd_lat_pron *np = (htkamd_lat_pron *)realloc(W->pron, sizeof(htkamd_lat_pron) * (size_t)(W->nProns + 1));
-      if (!haveOut) outSym = strdup(word);
-      if (!np || (!haveOut && !outSym)) { if (np) W->pron = np; free(outSym); htkamd_set_error("latset_create: out of memory"); rc = HTKAMD_ENOMEM; break; }
+      if (!np) break;
       W->pron = np;
+      char *outSym = e.outKind == HTX_OUT_EMPTY ? NULL : strdup(e.outKind == HTX_OUT_GIVEN ? e.outSym : e.word);
+      if (e.outKind != HTX_OUT_EMPTY && !outSym) break;
       W->pron[W->nProns].pnum = W->nProns + 1;
       W->pron[W->nProns].outSym = outSym;
       W->nProns++;
    }
+   if (rc == HTKAMD_ENOMEM) htkamd_set_error("latset_create: out of memory");
+   htx_dict_free(&e);
    free(txt);
-   return rc;
+   return rc == HTX_NONE ? HTKAMD_OK : rc;
 }
 
 /* ------------------------------------------------------------------------------------------ the set */
@@ -408,10 +308,13 @@ static int set_push(struct htkamd_latset *s, htkamd_lat_one *l)
 int htkamd_latset_add_file(struct htkamd_latset *s, const char *path)
 {
    if (!s || !path) { htkamd_set_error("latset_add_file: NULL argument"); return HTKAMD_EINVAL; }
-   size_t len;
-   char *txt = read_file(path, &len);
-   if (!txt) { htkamd_set_error("HLRescore: Cannot open Lattice file %s (4010) (or out of memory)", path); return HTKAMD_EIO; }
-   src_t src = {txt, txt + len};
+   size_t len; int why;
+   char *txt = htx_read_file(path, &len, &why);
+   if (!txt) {
+      if (why == HTX_ENOMEM) { htkamd_set_error("latset: out of memory"); return HTKAMD_ENOMEM; }
+      htkamd_set_error("HLRescore: Cannot open Lattice file %s (4010)", path); return HTKAMD_EIO;
+   }
+   htx_src src = {txt, txt + len, 0};
    char name[132], val[4200];
    htkamd_lat_one l;
    memset(&l, 0, sizeof(l));
@@ -422,20 +325,20 @@ int htkamd_latset_add_file(struct htkamd_latset *s, const char *path)
    int *lineOrder = NULL, *seenNode = NULL, *seenArc = NULL, nLines = 0, nodesLeft = 0, arcsLeft = 0, alabs = 1;
    /* header (HNet.c:904-948): ends at the first end of line after both N and L are known */
    while (!rc) {
-      t = next_field(&src, path, name, sizeof(name), val, sizeof(val));
-      if (t == F_ERR) { rc = HTKAMD_EMODEL; break; }
-      if (t == F_EOF || t == F_DOT) { htkamd_set_error("%s: ReadLattice: Premature end of lattice file before header (8250)", path); rc = HTKAMD_EMODEL; break; }
-      if (t == F_EOL) { if (na != 0 && nn != 0) break; continue; }
-      if (!strcmp(name, "N")) { if (!(rc = parse_number(val, &v, 1, path, 'N'))) nn = (int)v; }
-      else if (!strcmp(name, "L")) { if (!(rc = parse_number(val, &v, 1, path, 'L'))) na = (int)v; }
+      t = htx_slf_next_field(&src, path, name, sizeof(name), val, sizeof(val));
+      if (t == HTX_F_ERR) { rc = HTKAMD_EMODEL; break; }
+      if (t == HTX_F_EOF || t == HTX_F_DOT) { htkamd_set_error("%s: ReadLattice: Premature end of lattice file before header (8250)", path); rc = HTKAMD_EMODEL; break; }
+      if (t == HTX_F_EOL) { if (na != 0 && nn != 0) break; continue; }
+      if (!strcmp(name, "N")) { if (!(rc = htx_slf_number(val, &v, 1, path, 'N'))) nn = (int)v; }
+      else if (!strcmp(name, "L")) { if (!(rc = htx_slf_number(val, &v, 1, path, 'L'))) na = (int)v; }
       else if (!strcmp(name, "UTTERANCE")) { free(utt); utt = strdup(val); }
       else if (!strcmp(name, "SUBLAT")) { htkamd_set_error("%s: SUBLAT=%s: multi-level lattices (sub-lattices) are not supported", path, val); rc = HTKAMD_EMODEL; }
       else if (!strcmp(name, "vocab")) { free(voc); voc = strdup(val); }
       else if (!strcmp(name, "hmms")) { free(hmms); hmms = strdup(val); }
       else if (!strcmp(name, "lmname")) { free(lmn); lmn = strdup(val); }
-      else if (!strcmp(name, "base")) { if (!(rc = parse_number(val, &v, 0, path, 'b'))) logbase = (float)v; }
-      else if (!strcmp(name, "tscale")) { if (!(rc = parse_number(val, &v, 0, path, 't'))) tscale = (float)v; }
-      else if (!strcmp(name, "wdpenalty") || !strcmp(name, "lmscale") || !strcmp(name, "prscale") || !strcmp(name, "acscale")) rc = parse_number(val, &v, 0, path, name[0] == 'w' ? 'p' : (name[0] == 'a' ? 'a' : 's'));
+      else if (!strcmp(name, "base")) { if (!(rc = htx_slf_number(val, &v, 0, path, 'b'))) logbase = (float)v; }
+      else if (!strcmp(name, "tscale")) { if (!(rc = htx_slf_number(val, &v, 0, path, 't'))) tscale = (float)v; }
+      else if (!strcmp(name, "wdpenalty") || !strcmp(name, "lmscale") || !strcmp(name, "prscale") || !strcmp(name, "acscale")) rc = htx_slf_number(val, &v, 0, path, name[0] == 'w' ? 'p' : (name[0] == 'a' ? 'a' : 's'));
    }
    if (!rc && (nn < 0 || na < 0)) { htkamd_set_error("%s: ReadLattice: N=%d L=%d", path, nn, na); rc = HTKAMD_EMODEL; }
    if (!rc && logbase < 0.0f) { htkamd_set_error("%s: ReadLattice: Illegal log base in lattice (8251)", path); rc = HTKAMD_EMODEL; }
@@ -450,33 +353,33 @@ int htkamd_latset_add_file(struct htkamd_latset *s, const char *path)
    }
    /* body (HNet.c:1004-1208) */
    while (!rc) {
-      t = next_field(&src, path, name, sizeof(name), val, sizeof(val));
-      if (t == F_ERR) { rc = HTKAMD_EMODEL; break; }
-      if (t == F_EOF || t == F_DOT) break;
-      if (t == F_EOL) continue;
+      t = htx_slf_next_field(&src, path, name, sizeof(name), val, sizeof(val));
+      if (t == HTX_F_ERR) { rc = HTKAMD_EMODEL; break; }
+      if (t == HTX_F_EOF || t == HTX_F_DOT) break;
+      if (t == HTX_F_EOL) continue;
       const int isNode = !strcmp(name, "I"), isArc = !strcmp(name, "J");
       int n = -1;
       if (isNode || isArc) {
-         if ((rc = parse_number(val, &v, 1, path, 'I'))) break;
+         if ((rc = htx_slf_number(val, &v, 1, path, 'I'))) break;
          n = (int)v;
       }
       if (isNode) {
          if (n < 0 || n >= nn) { htkamd_set_error("%s: ReadLattice: Lattice does not contain node %d (8251)", path, n); rc = HTKAMD_EMODEL; break; }
          if (seenNode[n]) { htkamd_set_error("%s: ReadLattice: Duplicate info info for node %d (8251)", path, n); rc = HTKAMD_EMODEL; break; }
          double time = 0.0; int word = 0, var = -1;
-         while (!rc && (t = next_field(&src, path, name, sizeof(name), val, sizeof(val))) == F_FIELD) {
+         while (!rc && (t = htx_slf_next_field(&src, path, name, sizeof(name), val, sizeof(val))) == HTX_F_FIELD) {
             switch (name[0]) {
-            case 't': if (!(rc = parse_number(val, &v, 0, path, 't'))) { time = v; time *= tscale; } break;
+            case 't': if (!(rc = htx_slf_number(val, &v, 0, path, 't'))) { time = v; time *= tscale; } break;
             case 'W':
                word = dict_find(s->dict, val);
                if (word < 0) { htkamd_set_error("%s: ReadLattice: Word %s not in dict (8251)", path, val); rc = HTKAMD_EMODEL; }
                break;
             case 'L': htkamd_set_error("%s: node %d names the sub-lattice %s: multi-level lattices are not supported", path, n, val); rc = HTKAMD_EMODEL; break;
-            case 'v': if (!(rc = parse_number(val, &v, 1, path, 'v'))) var = (int)v; break;
+            case 'v': if (!(rc = htx_slf_number(val, &v, 1, path, 'v'))) var = (int)v; break;
             default: break;                                         /* s= (a tag) and anything else is passed over */
             }
          }
-         if (t == F_ERR) rc = HTKAMD_EMODEL;
+         if (t == HTX_F_ERR) rc = HTKAMD_EMODEL;
          if (rc) break;
          if (word != 0) alabs = 0;
          l.nodeTime[n] = time; l.nodeWord[n] = word; l.nodeVar[n] = var;
@@ -486,15 +389,15 @@ int htkamd_latset_add_file(struct htkamd_latset *s, const char *path)
          if (seenArc[n]) { htkamd_set_error("%s: ReadLattice: Duplicate info for arc %d (8251)", path, n); rc = HTKAMD_EMODEL; break; }
          int st = -1, en = -1, word = -1, var = -1;
          double ac = 0.0, lm = 0.0, pr = 0.0;
-         while (!rc && (t = next_field(&src, path, name, sizeof(name), val, sizeof(val))) == F_FIELD) {
+         while (!rc && (t = htx_slf_next_field(&src, path, name, sizeof(name), val, sizeof(val))) == HTX_F_FIELD) {
             switch (name[0]) {
             case 'S':
-               if ((rc = parse_number(val, &v, 1, path, 'S'))) break;
+               if ((rc = htx_slf_number(val, &v, 1, path, 'S'))) break;
                st = (int)v;
                if (st < 0 || st >= nn) { htkamd_set_error("%s: ReadLattice: Lattice does not contain start node %d (8251)", path, st); rc = HTKAMD_EMODEL; }
                break;
             case 'E':
-               if ((rc = parse_number(val, &v, 1, path, 'E'))) break;
+               if ((rc = htx_slf_number(val, &v, 1, path, 'E'))) break;
                en = (int)v;
                if (en < 0 || en >= nn) { htkamd_set_error("%s: ReadLattice: Lattice does not contain end node %d (8251)", path, en); rc = HTKAMD_EMODEL; }
                break;
@@ -502,10 +405,10 @@ int htkamd_latset_add_file(struct htkamd_latset *s, const char *path)
                word = dict_find(s->dict, val);
                if (word < 0 || word == 1) { htkamd_set_error("%s: ReadLattice: Word %s not in dict (8251)", path, val); rc = HTKAMD_EMODEL; }
                break;
-            case 'v': if (!(rc = parse_number(val, &v, 1, path, 'v'))) var = (int)v; break;
-            case 'a': if (!(rc = parse_number(val, &v, 0, path, 'a'))) ac = from_base(logbase, v); break;
-            case 'l': if (!(rc = parse_number(val, &v, 0, path, 'l'))) lm = from_base(logbase, v); break;
-            case 'r': if (!(rc = parse_number(val, &v, 0, path, 'r'))) pr = from_base(logbase, v); break;
+            case 'v': if (!(rc = htx_slf_number(val, &v, 1, path, 'v'))) var = (int)v; break;
+            case 'a': if (!(rc = htx_slf_number(val, &v, 0, path, 'a'))) ac = from_base(logbase, v); break;
+            case 'l': if (!(rc = htx_slf_number(val, &v, 0, path, 'l'))) lm = from_base(logbase, v); break;
+            case 'r': if (!(rc = htx_slf_number(val, &v, 0, path, 'r'))) pr = from_base(logbase, v); break;
             case 'd': {
                htkamd_lat_align *al; int nal;
                if ((rc = read_align(val, &al, &nal, path))) break;
@@ -520,7 +423,7 @@ int htkamd_latset_add_file(struct htkamd_latset *s, const char *path)
             default: break;
             }
          }
-         if (t == F_ERR) rc = HTKAMD_EMODEL;
+         if (t == HTX_F_ERR) rc = HTKAMD_EMODEL;
          if (rc) break;
          if (st < 0 || en < 0 || (word < 0 && alabs)) { htkamd_set_error("%s: ReadLattice: Need to know S,E [and W] for arc %d (8250)", path, n); rc = HTKAMD_EMODEL; break; }
          if (alabs && l.nodeWord[en] == 0) { l.nodeWord[en] = word; l.nodeVar[en] = var; }
@@ -531,10 +434,10 @@ int htkamd_latset_add_file(struct htkamd_latset *s, const char *path)
          l.arcStart[n] = st; l.arcEnd[n] = en; l.arcAc[n] = (float)ac; l.arcLm[n] = (float)lm; l.arcPr[n] = (float)pr;
          seenArc[n] = 1; lineOrder[nLines++] = n; arcsLeft--;
       } else {                                                      /* an unknown line: passed over */
-         while ((t = next_field(&src, path, name, sizeof(name), val, sizeof(val))) == F_FIELD) {}
-         if (t == F_ERR) rc = HTKAMD_EMODEL;
+         while ((t = htx_slf_next_field(&src, path, name, sizeof(name), val, sizeof(val))) == HTX_F_FIELD) {}
+         if (t == HTX_F_ERR) rc = HTKAMD_EMODEL;
       }
-      if (t == F_EOF || t == F_DOT) break;
+      if (t == HTX_F_EOF || t == HTX_F_DOT) break;
    }
    if (!rc && (arcsLeft != 0 || (nodesLeft != 0 && nodesLeft != nn))) {
       htkamd_set_error("%s: ReadLattice: %d Arcs unseen and %d Nodes unseen (8250)", path, arcsLeft, nodesLeft); rc = HTKAMD_EMODEL;

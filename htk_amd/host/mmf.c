@@ -24,6 +24,7 @@
 #include "../csrc/internal.h"
 
 #include "mmf_priv.h"
+#include "htktext.h"
 
 /* ------------------------------------------------------------------------------------------ tokenizer */
 typedef struct { FILE *f; const char *path; int line; int pushed; char tok[256]; int kind; int bin; } rd;   /* bin: the last keyword was a binary symbol, so its numbers are binary too (Token.binForm, HModel.c:505,570) */
@@ -930,32 +931,29 @@ int htkamd_mmf_finish(struct htkamd_mmf *s, const char *hmmList, const char *dir
    if (!s) { htkamd_set_error("mmf_finish: NULL"); return HTKAMD_EINVAL; }
    if (s->finished) return HTKAMD_OK;
    if (hmmList) {
-      FILE *f = fopen(hmmList, "r");
-      if (!f) { htkamd_set_error("mmf_finish: cannot open HMM list %s", hmmList); return HTKAMD_EIO; }
-      char line[1024], a[512], b[512];
+      size_t len; int why, r;
+      char *txt = htx_read_file(hmmList, &len, &why);
+      if (!txt) { htkamd_set_error(why == HTX_ENOMEM ? "mmf_finish: out of memory reading HMM list %s" : "mmf_finish: cannot open HMM list %s", hmmList); return why == HTX_ENOMEM ? HTKAMD_ENOMEM : HTKAMD_EIO; }
+      htx_src src = {txt, txt + len, 0};
+      char lo[1024], b[1024];
       int cap = 0;
-      while (fgets(line, sizeof(line), f)) {
-         int n = sscanf(line, "%511s %511s", a, b);
-         if (n < 1) continue;
-         char *lo = a, *ph = (n == 2) ? b : a;
-         for (int q = 0; q < 2; q++) {                 /* strip quotes */
-            char *t = q ? ph : lo; size_t L = strlen(t);
-            if (L >= 2 && (t[0] == '"' || t[0] == '\'') && t[L - 1] == t[0]) { memmove(t, t + 1, L - 2); t[L - 2] = 0; }
-         }
+      while ((r = htx_hmmlist_next(&src, lo, sizeof(lo), b, sizeof(b))) == HTX_GOT) {
+         const char *ph = b[0] ? b : lo;
          int h = find_hmm(s, ph);
          if (h < 0) {
             char path[1400];
             if (ext && *ext) snprintf(path, sizeof(path), "%s/%s.%s", dir ? dir : ".", ph, ext);
             else snprintf(path, sizeof(path), "%s/%s", dir ? dir : ".", ph);
             int rc = htkamd_mmf_read(s, path, ph);
-            if (rc) { fclose(f); return rc; }
+            if (rc) { free(txt); return rc; }
             h = find_hmm(s, ph);
-            if (h < 0) { fclose(f); htkamd_set_error("mmf_finish: %s does not define %s", path, ph); return HTKAMD_EMODEL; }
+            if (h < 0) { free(txt); htkamd_set_error("mmf_finish: %s does not define %s", path, ph); return HTKAMD_EMODEL; }
          }
          if (s->nLog + 1 > cap) { cap = cap * 2 + 64; s->logName = (char **)realloc(s->logName, sizeof(char *) * (size_t)cap); s->logPhys = (int *)realloc(s->logPhys, sizeof(int) * (size_t)cap); }
          s->logName[s->nLog] = strdup(lo); s->logPhys[s->nLog] = h; s->nLog++;
       }
-      fclose(f);
+      free(txt);
+      if (r < 0) { htkamd_set_error("mmf_finish: HMM list %s, entry %d: %s", hmmList, s->nLog + 1, htx_result_text(r)); return HTKAMD_EMODEL; }
    } else {
       s->logName = (char **)malloc(sizeof(char *) * (size_t)(s->nHm ? s->nHm : 1));
       s->logPhys = (int *)malloc(sizeof(int) * (size_t)(s->nHm ? s->nHm : 1));
@@ -1210,10 +1208,8 @@ static void put_float(FILE *f, float v)
 static void put_nl(FILE *f) { if (!g_bin) fputc('\n', f); }
 static void put_name(FILE *f, char type, const char *name)
 {
-   /* ReWriteString(.., DBL_QUOTE): quotes always, backslash before quote/backslash */
-   fprintf(f, "~%c \"", type);
-   for (const char *p = name; *p; p++) { if (*p == '"' || *p == '\\') fputc('\\', f); fputc(*p, f); }
-   fprintf(f, "\"");
+   fprintf(f, "~%c ", type);
+   htx_write_string(f, name, '"', 0);                /* ReWriteString(.., DBL_QUOTE) */
    put_nl(f);
 }
 static void put_int32(FILE *f, int v) { if (g_bin) { fputc((v >> 24) & 255, f); fputc((v >> 16) & 255, f); fputc((v >> 8) & 255, f); fputc(v & 255, f); } else fprintf(f, " %d", v); }
@@ -1304,9 +1300,8 @@ static void put_state(const struct htkamd_mmf *s, FILE *f, int si, const float *
       if (NS > 1) { put_sym(f, "STREAM", 18); put_short(f, k + 1); put_nl(f); }
       if (s->tiedMix) {                                                   /* PutTiedMixtures / PutTiedWeights (HModel.c:2706,2620): runs of up to 256 equal weights */
          put_sym(f, "TMIX", 16);
-         fprintf(f, " \"");
-         for (const char *p = s->tmName[k]; *p; p++) { if (*p == '"' || *p == '\\') fputc('\\', f); fputc(*p, f); }
-         fprintf(f, "\"");
+         fputc(' ', f);
+         htx_write_string(f, s->tmName[k], '"', 0);
          put_nl(f);
          for (int m = 0; m < M; ) {
             int run = 1;

@@ -65,13 +65,11 @@ void htkamd_mmf_trees_free(mmf_trees *t);
 
 /* treeclust.c's helpers that treesynth.c shares (library-internal names) */
 #define tc_match        htkamd_tc_match
-#define tc_rewrite      htkamd_tc_rewrite
 #define tc_logical_walk htkamd_tc_logical_walk
 #define tc_compact      htkamd_tc_compact
 #define dc_fix_gconsts  htkamd_dc_fix_gconsts
 #define st_hold         htkamd_st_hold
 int  tc_match(const char *s, const char *p);                      /* DoMatch */
-void tc_rewrite(const char *s, char q, char *d);                  /* ReWriteString */
 int *tc_logical_walk(const struct htkamd_mmf *s);                 /* the logical names in the macro table's order (malloc'd) */
 void tc_compact(struct htkamd_mmf *s, const int *newSeq, int nNew);   /* drops states nobody uses, rebuilds the state side of the description */
 void dc_fix_gconsts(struct htkamd_mmf *s);                        /* FixAllGConsts (DIAGC) */

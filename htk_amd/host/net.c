@@ -20,6 +20,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../csrc/internal.h"
+#include "htktext.h"
 
 typedef struct { char *word, *outSym; float prob; int nPhones; int *phone; char **phoneName; } dpron;   /* phone = physical model index (filled by resolve_models) */
 
@@ -36,24 +37,6 @@ struct htkamd_net {
    char **depName; int nDep;                  /* base names that have context-dependent models */
    int sLeft, sRight;
 };
-
-static char *rd_word(char **pp)
-{
-   /* ReadString-style token: optional quotes, backslash escapes */
-   char *p = *pp, buf[512]; int n = 0;
-   while (isspace((unsigned char)*p)) p++;
-   if (!*p) { *pp = p; return NULL; }
-   if (*p == '"' || *p == '\'') {
-      const char q = *p++;
-      while (*p && *p != q && n < 510) { if (*p == '\\' && p[1]) p++; buf[n++] = *p++; }
-      if (*p == q) p++;
-   } else {
-      while (*p && !isspace((unsigned char)*p) && n < 510) { if (*p == '\\' && p[1]) p++; buf[n++] = *p++; }
-   }
-   buf[n] = 0; *pp = p;
-   return strdup(buf);
-}
-
 
 /* ---- phones -> models.  ExpandWordNet (HNet.c:3438) first asks whether every phone of the WHOLE dictionary is a model name
  * (ClosedDict :1876): then pronunciations are chains of exactly those models.  Otherwise the model set defines contexts
@@ -136,165 +119,137 @@ static int resolve_models(dpron *pr, int nPr, const struct htkamd_mmf *hmms, con
          for (int q = 0; q < pr[k].nPhones; q++) pr[k].phone[q] = htkamd_mmf_find_logical(hmms, pr[k].phoneName[q]);
       return HTKAMD_OK;
    }
-   /* DefineContexts */
-   strset cxs = {0}, dep = {0};                      /* contexts seen; base names that have a context-dependent model */
-   int sLeft = 0, sRight = 0;
-   const int nLog = htkamd_mmf_num_logical(hmms);
-   char buf[1600], base[512];
-   for (int i = 0; i < nLog; i++) {
-      const char *nm = htkamd_mmf_logical_name(hmms, i);
-      const char *mi = strchr(nm, '-'), *pl = strchr(nm, '+');
-      if (mi) { snprintf(buf, sizeof(buf), "%.*s", (int)(mi - nm), nm); set_add(&cxs, buf); sLeft = 1; }
-      if (pl) { set_add(&cxs, pl + 1); sRight = 1; }
-      if (mi || pl) { tri_strip(nm, base, sizeof(base)); set_add(&dep, base); }
-   }
+   hci_t hc; hci_define(&hc, hmms);
+   char tried[1600];
    int rc = HTKAMD_OK, internal = 1;
-   const int allowX = (flags & HTKAMD_NET_ALLOWXWRDEXP) != 0 && cxs.n > 0;
+   const int allowX = (flags & HTKAMD_NET_ALLOWXWRDEXP) != 0 && hc.cxs.n > 0;
    for (int k = 0; k < nPr && !rc; k++) {
       dpron *d = &pr[k];
       for (int q = 0; q < d->nPhones && !rc; q++) {
-         /* contexts: previous / next phone inside the word; a phone that is nobody's context is a word boundary (0) */
-         const char *lc = NULL, *rcx = NULL;
-         if (q > 0) { tri_strip(d->phoneName[q - 1], base, sizeof(base)); if (set_has(&cxs, base)) lc = d->phoneName[q - 1]; }
-         if (q + 1 < d->nPhones) { tri_strip(d->phoneName[q + 1], base, sizeof(base)); if (set_has(&cxs, base)) rcx = d->phoneName[q + 1]; }
-         char lcs[256] = "", rcs[256] = "";
-         if (lc) tri_strip(lc, lcs, sizeof(lcs));
-         if (rcx) tri_strip(rcx, rcs, sizeof(rcs));
-         const char *nm = d->phoneName[q];
-         const int ci = !set_has(&dep, nm);                   /* IsHCIContextInd: only the bare model exists */
-         if ((!lc && !rcx) || ci) snprintf(buf, sizeof(buf), "%s", nm);
-         else if ((!lc || !sLeft) && rcx) snprintf(buf, sizeof(buf), "%s+%s", nm, rcs);
-         else if ((!rcx || !sRight) && lc) snprintf(buf, sizeof(buf), "%s-%s", lcs, nm);
-         else snprintf(buf, sizeof(buf), "%s-%s+%s", lcs, nm, rcs);
-         int h = htkamd_mmf_find_logical(hmms, buf);
-         if (h < 0) h = htkamd_mmf_find_logical(hmms, nm);      /* "then try the name itself" */
+         /* contexts: previous / next phone inside the word; a phone that is nobody's context is a word boundary */
+         const int lc = q > 0 ? hci_context(&hc.cxs, d->phoneName[q - 1]) : -1, rcx = q + 1 < d->nPhones ? hci_context(&hc.cxs, d->phoneName[q + 1]) : -1;
+         const int h = find_model_ctx(hmms, &hc.cxs, &hc.dep, hc.sLeft, hc.sRight, flags, lc, d->phoneName[q], rcx, tried, sizeof(tried));
          if (h < 0 && allowX) internal = 0;                     /* InternalDict (HNet.c:2142) fails: cross-word models are needed */
-         else if (h < 0) { htkamd_set_error("%s: word %s: no model %s (nor %s) in the model set", dictPath, d->word, buf, nm); rc = HTKAMD_EMODEL; }
+         else if (h < 0) { htkamd_set_error("%s: word %s: no model %s (nor %s) in the model set", dictPath, d->word, tried, d->phoneName[q]); rc = HTKAMD_EMODEL; }
          d->phone[q] = h;
       }
    }
    if (!rc && allowX && (force || !internal) && xwrd) *xwrd = 1;
    else if (!rc && !internal) { htkamd_set_error("%s: the dictionary needs cross-word models", dictPath); rc = HTKAMD_EMODEL; }
-   set_free(&cxs); set_free(&dep);
+   hci_free(&hc);
    return rc;
+}
+
+static void prons_free(dpron *pr, int n)
+{
+   for (int i = 0; i < n; i++) {
+      for (int q = 0; q < pr[i].nPhones; q++) free(pr[i].phoneName[q]);
+      free(pr[i].phoneName); free(pr[i].word); free(pr[i].outSym); free(pr[i].phone);
+   }
+   free(pr);
+}
+
+static char *read_text(const char *path, const char *what, size_t *len, int *rc)
+{
+   int why;
+   char *txt = htx_read_file(path, len, &why);
+   if (!txt && why == HTX_ENOMEM) { htkamd_set_error("net_build: out of memory reading %s %s", what, path); *rc = HTKAMD_ENOMEM; }
+   else if (!txt) { htkamd_set_error("net_build: cannot open %s %s", what, path); *rc = HTKAMD_EIO; }
+   return txt;
 }
 
 static int read_dict(const char *path, const struct htkamd_mmf *hmms, int flags, int *xwrd, dpron **out, int *nOut)
 {
-   FILE *f = fopen(path, "r");
-   if (!f) { htkamd_set_error("net_build: cannot open dictionary %s", path); return HTKAMD_EIO; }
-   dpron *pr = NULL; int n = 0, cap = 0, lineNo = 0;
-   char line[4096];
-   while (fgets(line, sizeof(line), f)) {
-      lineNo++;
-      char *p = line;
-      char *w = rd_word(&p);
-      if (!w) continue;
+   size_t len; int rc;
+   char *txt = read_text(path, "dictionary", &len, &rc);
+   if (!txt) return rc;
+   htx_src s = {txt, txt + len, 0};
+   htx_dict_entry e = {0};
+   dpron *pr = NULL; int n = 0, cap = 0;
+   while ((rc = htx_dict_next(&s, path, &e)) == HTX_GOT) {
       if (n + 1 > cap) { cap = cap * 2 + 256; pr = (dpron *)realloc(pr, sizeof(dpron) * (size_t)cap); }
-      dpron *d = &pr[n];
+      dpron *d = &pr[n++];
       memset(d, 0, sizeof(*d));
-      d->word = w; d->prob = 0.0f;
-      while (isspace((unsigned char)*p)) p++;
-      if (*p == '[') {                                       /* output symbol */
-         char *e = strchr(p, ']');
-         if (!e) { fclose(f); htkamd_set_error("%s:%d: unterminated [outsym]", path, lineNo); return HTKAMD_EMODEL; }
-         *e = 0; d->outSym = strdup(p + 1); p = e + 1;
-      } else d->outSym = strdup(w);
-      int capP = 0;
-      for (;;) {
-         char *t = rd_word(&p);
-         if (!t) break;
-         if (d->nPhones == 0) {                              /* optional pronunciation probability (HDict.c:262-275) */
-            char *e; double v = strtod(t, &e);
-            if (*e == 0 && (isdigit((unsigned char)t[0]) || t[0] == '.')) {
-               if (v <= 0.0 || v > 1.0) { fclose(f); htkamd_set_error("%s:%d: pronunciation probability out of range", path, lineNo); return HTKAMD_EMODEL; }
-               /* the reference keeps the probability as a FLOAT before taking the log (ReadDictWord's `float v`, NewPron HDict.c:144-150),
-                  and treats anything below MINPRONPROB = 1e-6 as log-zero */
-               const float vf = (float)v;
-               d->prob = (vf >= 1.0E-6f) ? (float)log((double)vf) : (float)LZERO;
-               free(t); continue;
-            }
-         }
-         if (d->nPhones + 1 > capP) { capP = capP * 2 + 8; d->phone = (int *)realloc(d->phone, sizeof(int) * (size_t)capP); d->phoneName = (char **)realloc(d->phoneName, sizeof(char *) * (size_t)capP); }
-         d->phoneName[d->nPhones] = t; d->phone[d->nPhones] = -1; d->nPhones++;
-      }
-      n++;
+      d->word = strdup(e.word);
+      d->outSym = strdup(e.outKind == HTX_OUT_ABSENT ? e.word : e.outSym);
+      /* the reference keeps the probability as a FLOAT before taking the log (ReadDictWord's `float v`, NewPron HDict.c:144-150),
+         and treats anything below MINPRONPROB = 1e-6 as log-zero */
+      if (e.hasProb) d->prob = (e.prob >= 1.0E-6f) ? (float)log((double)e.prob) : (float)LZERO;
+      d->nPhones = e.nPhones;
+      d->phone = (int *)malloc(sizeof(int) * (size_t)(e.nPhones + 1)); d->phoneName = (char **)malloc(sizeof(char *) * (size_t)(e.nPhones + 1));
+      for (int q = 0; q < e.nPhones; q++) { d->phoneName[q] = strdup(e.phone[q]); d->phone[q] = -1; }
    }
-   fclose(f);
+   htx_dict_free(&e);
+   free(txt);
+   if (!rc) rc = resolve_models(pr, n, hmms, path, flags, xwrd);
+   if (rc) { prons_free(pr, n); return rc; }
    *out = pr; *nOut = n;
-   return resolve_models(pr, n, hmms, path, flags, xwrd);
+   return HTKAMD_OK;
 }
 
 typedef struct { char *word; int var; } lnode;
 typedef struct { int s, e; float l; } larc;
 
-static const char *field(const char *line, const char *key, char *buf, size_t nb)
-{
-   /* value of "key=" in a line of blank-separated fields */
-   const size_t kl = strlen(key);
-   for (const char *p = line; *p;) {
-      while (isspace((unsigned char)*p)) p++;
-      if (!strncmp(p, key, kl) && p[kl] == '=') {
-         p += kl + 1;
-         size_t n = 0;
-         if (*p == '"') { p++; while (*p && *p != '"' && n + 1 < nb) buf[n++] = *p++; }
-         else while (*p && !isspace((unsigned char)*p) && n + 1 < nb) buf[n++] = *p++;
-         buf[n] = 0;
-         return buf;
-      }
-      while (*p && !isspace((unsigned char)*p)) p++;
-   }
-   return NULL;
-}
+static void lnodes_free(lnode *ln, int n) { for (int i = 0; ln && i < n; i++) free(ln[i].word); free(ln); }
 
+/* ReadLattice (HNet.c:878) as far as a network needs it: the header's N and L, then per I= line W and v, per J= line S, E and l; the body's
+   fields go by their first letter as the reference's do */
 static int read_slf(const char *path, lnode **nodes, int *nn, larc **arcs, int *na)
 {
-   FILE *f = fopen(path, "r");
-   if (!f) { htkamd_set_error("net_build: cannot open lattice %s", path); return HTKAMD_EIO; }
-   char line[4096], v[512];
-   int N = -1, L = -1, gotA = 0;
+   size_t len; int rc = HTKAMD_OK;
+   char *txt = read_text(path, "lattice", &len, &rc);
+   if (!txt) return rc;
+   htx_src src = {txt, txt + len, 0};
+   char name[132], val[4200];
+   int N = -1, L = -1, gotA = 0, t;
+   double v;
    lnode *ln = NULL; larc *la = NULL;
-   while (fgets(line, sizeof(line), f)) {
-      const char *p = line;
-      while (isspace((unsigned char)*p)) p++;
-      if (*p == '#' || !*p) continue;
-      if (!strncmp(p, "SUBLAT", 6)) { fclose(f); free(ln); free(la); htkamd_set_error("%s: a multi-level lattice (SUBLAT) must be expanded before a network is made of it (the reference says the same: InitPronHolders HNet.c:2358, 'Expand lattice before making network'; HBuild -x expands)", path); return HTKAMD_EMODEL; }
-      if (N < 0) {
-         if (field(p, "N", v, sizeof(v)) || field(p, "NODES", v, sizeof(v))) {
-            N = atoi(v);
-            if (!(field(p, "L", v, sizeof(v)) || field(p, "LINKS", v, sizeof(v)))) { fclose(f); htkamd_set_error("%s: N= without L=", path); return HTKAMD_EMODEL; }
-            L = atoi(v);
-            if (N <= 0 || L < 0) { fclose(f); htkamd_set_error("%s: bad size line", path); return HTKAMD_EMODEL; }
-            ln = (lnode *)calloc((size_t)N, sizeof(lnode)); la = (larc *)calloc((size_t)(L ? L : 1), sizeof(larc));
-         }
-         continue;                                            /* other header fields (VERSION, lmscale, ...) */
+#define SLF_BAD(...) do { htkamd_set_error(__VA_ARGS__); rc = HTKAMD_EMODEL; goto done; } while (0)
+#define SLF_INT(dst, letter) do { if ((rc = htx_slf_number(val, &v, 1, path, (letter)))) goto done; (dst) = (int)v; } while (0)
+   for (;;) {                                                /* the header ends with the line that makes both sizes known */
+      t = htx_slf_next_field(&src, path, name, sizeof(name), val, sizeof(val));
+      if (t == HTX_F_ERR) { rc = HTKAMD_EMODEL; goto done; }
+      if (t == HTX_F_EOF || t == HTX_F_DOT) SLF_BAD("%s: no N= L= line", path);
+      if (t == HTX_F_EOL) { if (N >= 0 && L >= 0) break; continue; }
+      if (!strcmp(name, "SUBLAT")) SLF_BAD("%s: a multi-level lattice (SUBLAT) must be expanded before a network is made of it (the reference says the same: InitPronHolders HNet.c:2358, 'Expand lattice before making network'; HBuild -x expands)", path);
+      if (!strcmp(name, "N")) SLF_INT(N, 'N');
+      else if (!strcmp(name, "L")) SLF_INT(L, 'L');
+   }
+   if (N <= 0 || L < 0) SLF_BAD("%s: bad size line", path);
+   ln = (lnode *)calloc((size_t)N, sizeof(lnode)); la = (larc *)calloc((size_t)(L ? L : 1), sizeof(larc));
+   for (;;) {
+      t = htx_slf_next_field(&src, path, name, sizeof(name), val, sizeof(val));
+      if (t == HTX_F_ERR) { rc = HTKAMD_EMODEL; goto done; }
+      if (t == HTX_F_EOF || t == HTX_F_DOT) break;
+      if (t == HTX_F_EOL) continue;
+      const int isNode = !strcmp(name, "I"), isArc = !strcmp(name, "J");
+      int i = -1;
+      if (isNode || isArc) SLF_INT(i, name[0]);
+      if (isNode && (i < 0 || i >= N)) SLF_BAD("%s: node index %d out of range", path, i);
+      if (isArc && (i < 0 || i >= L)) SLF_BAD("%s: arc index %d out of range", path, i);
+      if (isNode) { free(ln[i].word); ln[i].word = NULL; ln[i].var = 0; }
+      if (isArc) { la[i].s = la[i].e = -1; la[i].l = 0.0f; }
+      while ((t = htx_slf_next_field(&src, path, name, sizeof(name), val, sizeof(val))) == HTX_F_FIELD) {
+         if (isNode && name[0] == 'W') { free(ln[i].word); ln[i].word = strdup(val); }
+         else if (isNode && name[0] == 'v') SLF_INT(ln[i].var, 'v');
+         else if (isArc && name[0] == 'S') SLF_INT(la[i].s, 'S');
+         else if (isArc && name[0] == 'E') SLF_INT(la[i].e, 'E');
+         else if (isArc && name[0] == 'l') { if ((rc = htx_slf_number(val, &v, 0, path, 'l'))) goto done; la[i].l = strtof(val, NULL); }
       }
-      if (p[0] == 'I' && p[1] == '=') {
-         const int i = atoi(field(p, "I", v, sizeof(v)));
-         if (i < 0 || i >= N) { fclose(f); htkamd_set_error("%s: node index %d out of range", path, i); return HTKAMD_EMODEL; }
-         const char *w = field(p, "W", v, sizeof(v));
-         if (!w) w = field(p, "WORD", v, sizeof(v));
-         free(ln[i].word);
-         ln[i].word = strdup(w ? w : "!NULL");
-         const char *pv = field(p, "v", v, sizeof(v));
-         ln[i].var = pv ? atoi(pv) : 0;
-      } else if (p[0] == 'J' && p[1] == '=') {
-         const int j = atoi(field(p, "J", v, sizeof(v)));
-         if (j < 0 || j >= L) { fclose(f); htkamd_set_error("%s: arc index %d out of range", path, j); return HTKAMD_EMODEL; }
-         const char *s = field(p, "S", v, sizeof(v)); if (!s) s = field(p, "START", v, sizeof(v));
-         la[j].s = s ? atoi(s) : -1;
-         const char *e = field(p, "E", v, sizeof(v)); if (!e) e = field(p, "END", v, sizeof(v));
-         la[j].e = e ? atoi(e) : -1;
-         const char *l = field(p, "l", v, sizeof(v)); if (!l) l = field(p, "language", v, sizeof(v));
-         la[j].l = l ? strtof(l, NULL) : 0.0f;
-         if (la[j].s < 0 || la[j].s >= N || la[j].e < 0 || la[j].e >= N) { fclose(f); htkamd_set_error("%s: arc %d has bad end points", path, j); return HTKAMD_EMODEL; }
+      if (t == HTX_F_ERR) { rc = HTKAMD_EMODEL; goto done; }
+      if (isArc) {
+         if (la[i].s < 0 || la[i].s >= N || la[i].e < 0 || la[i].e >= N) SLF_BAD("%s: arc %d has bad end points", path, i);
          gotA++;
       }
+      if (t == HTX_F_EOF || t == HTX_F_DOT) break;
    }
-   fclose(f);
-   if (N < 0) { htkamd_set_error("%s: no N= L= line", path); return HTKAMD_EMODEL; }
    for (int i = 0; i < N; i++) if (!ln[i].word) ln[i].word = strdup("!NULL");
-   if (gotA != L) { htkamd_set_error("%s: %d arcs announced, %d read", path, L, gotA); return HTKAMD_EMODEL; }
+   if (gotA != L) SLF_BAD("%s: %d arcs announced, %d read", path, L, gotA);
+#undef SLF_INT
+#undef SLF_BAD
+done:
+   free(txt);
+   if (rc) { lnodes_free(ln, N); free(la); return rc; }
    *nodes = ln; *nn = N; *arcs = la; *na = L;
    return HTKAMD_OK;
 }
@@ -305,11 +260,7 @@ void htkamd_net_destroy(struct htkamd_net *n)
    free(n->kind); free(n->model); free(n->linkOff); free(n->linkDest); free(n->wordOf); free(n->pronProb); free(n->linkLike);
    for (int i = 0; i < n->nWordNames; i++) free(n->wordName[i]);
    free(n->wordName);
-   for (int i = 0; i < n->nPron; i++) {
-      for (int q = 0; q < n->pron[i].nPhones; q++) free(n->pron[i].phoneName[q]);
-      free(n->pron[i].phoneName); free(n->pron[i].word); free(n->pron[i].outSym); free(n->pron[i].phone);
-   }
-   free(n->pron);
+   prons_free(n->pron, n->nPron);
    for (int i = 0; i < n->nCx; i++) free(n->cxName[i]);
    for (int i = 0; i < n->nDep; i++) free(n->depName[i]);
    free(n->cxName); free(n->depName);
@@ -329,7 +280,7 @@ int htkamd_net_build_ex(const char *slfPath, const char *dictPath, const struct 
    dpron *pr = NULL; int nPr = 0, rc, xwrd = 0;
    if ((rc = read_dict(dictPath, hmms, flags, &xwrd, &pr, &nPr))) return rc;
    lnode *ln = NULL; larc *la = NULL; int NN = 0, NA = 0;
-   if ((rc = read_slf(slfPath, &ln, &NN, &la, &NA))) return rc;
+   if ((rc = read_slf(slfPath, &ln, &NN, &la, &NA))) { prons_free(pr, nPr); return rc; }
    xwrd_t xw; xw.hmms = hmms; xw.flags = flags;
    return expand_lattice(ln, NN, la, NA, pr, nPr, slfPath, dictPath, md, xwrd ? &xw : NULL, out);
 }

@@ -1,20 +1,17 @@
 /* slfout.c -- the pieces of WriteOneLattice (HNet.c:530) that both lattice writers share (host/lattice.c: the decoder's lattices;
  * host/latrescore.c: lattices read back from files), so that the SLF text has one statement of each:
- *   htkamd_slf_put_word    "W=%-19s " with ReWriteString(.., NULL, ESCAPE_CHAR): quotes only when needed;
+ *   htkamd_slf_put_word    "W=%-19s " with ReWriteString(.., NULL, ESCAPE_CHAR): never quoted, escapes where needed;
  *   htkamd_slf_sort_arcs   QSCmpArcs (HNet.c:466): by end node's output rank, then start node's, then arc number.
  */
 #include <stdlib.h>
 #include "../csrc/internal.h"
+#include "htktext.h"
 
 void htkamd_slf_put_word(FILE *f, const char *s)
 {
-   char buf[1100]; int n = 0, need = 0;
-   for (const char *p = s; *p; p++) if (*p == ' ' || *p == '"' || *p == '\'' || *p == '\\' || (unsigned char)*p < 33 || (unsigned char)*p > 126) need = 1;
-   if (!need) { fprintf(f, "W=%-19s ", s); return; }
-   buf[n++] = '"';
-   for (const char *p = s; *p && n < 1090; p++) { if (*p == '"' || *p == '\\') buf[n++] = '\\'; buf[n++] = *p; }
-   buf[n++] = '"'; buf[n] = 0;
-   fprintf(f, "W=%-19s ", buf);
+   fputs("W=", f);
+   htx_write_string(f, s, HTX_ESCAPE, -19);
+   fputc(' ', f);
 }
 
 static const int *g_start, *g_end, *g_rank;        /* qsort context (the reference's `slat`) */

@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "mmf_priv.h"
+#include "htktext.h"
 
 /* The device side is in the HIP part of the library.  The host files are also built on their own (the sanitizer build of
    tests/test_host_sanitizers.py): there the device entry points are absent, and a call that needs them says so. */
@@ -45,19 +46,6 @@ int tc_match(const char *s, const char *p)
 }
 
 static int tc_has_wild(const char *p) { return strpbrk(p, "*?%") != NULL; }      /* PHIdent :1013 */
-
-/* ReWriteString (HShell.c:1303) with q = '\'', '"' or '\\' */
-void tc_rewrite(const char *s, char q, char *d)
-{
-   if (q != '\\') *d++ = q;
-   for (const unsigned char *p = (const unsigned char *)s; *p; p++) {
-      if (*p == '\\' || *p == (unsigned char)q || (q == '\\' && p == (const unsigned char *)s && (*p == '\'' || *p == '"'))) { *d++ = '\\'; *d++ = (char)*p; }
-      else if (isprint(*p)) *d++ = (char)*p;
-      else { const int n = *p; *d++ = '\\'; *d++ = (char)(((n / 64) % 8) + '0'); *d++ = (char)(((n / 8) % 8) + '0'); *d++ = (char)((n % 8) + '0'); }
-   }
-   if (q != '\\') *d++ = q;
-   *d = 0;
-}
 
 /* the logical names in the order PHIdent's walk over the macro table meets them (:1027): the hash order mmf.c writes macros in,
    over the list's names in list order ('l' macros are made in list order, MakeHMMSet HModel.c:3580) */
@@ -91,13 +79,11 @@ int htkamd_stats_read_file(const htkamd_mmf *s, const char *path, float *occ, in
       if (e == p) { htkamd_set_error("stats_read_file: format error in file %s line %d", path, lnum); rc = HTKAMD_EIO; break; }
       p = e;
       while (isspace((unsigned char)*p)) p++;
-      char name[512]; int n = 0;                       /* ReadString: quoted with \ escapes, or up to white space */
-      if (*p == '"' || *p == '\'') {
-         const char q = *p++;
-         while (*p && *p != q && n < 510) { if (*p == '\\' && p[1]) p++; name[n++] = *p++; }
-         if (*p == q) p++;
-      } else while (*p && !isspace((unsigned char)*p) && n < 510) { if (*p == '\\' && p[1]) p++; name[n++] = *p++; }
-      name[n] = 0;
+      char name[1024];
+      htx_src src = {p, p + strlen(p), 0};
+      const int got1 = htx_read_string(&src, HTX_LINE, NULL, name, sizeof(name));
+      if (got1 != HTX_GOT) { htkamd_set_error("stats_read_file: %s line %d: model name: %s", path, lnum, htx_result_text(got1)); rc = HTKAMD_EIO; break; }
+      p = (char *)src.p;
       const long cnt = strtol(p, &e, 10);
       if (e == p) { htkamd_set_error("stats_read_file: format error in file %s line %d", path, lnum); rc = HTKAMD_EIO; break; }
       p = e;
@@ -128,20 +114,14 @@ typedef struct { int phys, j; } tc_item;              /* model and HTK state num
 
 typedef struct { const char *p; } tc_src;
 static void tc_skip(tc_src *r) { while (isspace((unsigned char)*r->p)) r->p++; }
-/* GetAlpha (HUtil.c:660): a name up to one of ".,)}" or white space, or quoted */
+/* GetAlpha (HUtil.c:660): a name up to one of ".,)}" or white space, or quoted; < 0 when it cannot be read */
 static int tc_alpha(tc_src *r, char *out, int cap)
 {
-   int n = 0;
-   tc_skip(r);
-   if (*r->p == '"' || *r->p == '\'') {
-      const char q = *r->p++;
-      while (*r->p && *r->p != q) { if (*r->p == '\\' && r->p[1]) r->p++; if (n < cap - 1) out[n++] = *r->p; r->p++; }
-      if (*r->p != q) return -1;
-      r->p++;
-   } else
-      while (*r->p && !isspace((unsigned char)*r->p) && !strchr(".,)}", *r->p)) { if (*r->p == '\\' && r->p[1]) r->p++; if (n < cap - 1) out[n++] = *r->p; r->p++; }
-   out[n] = 0;
-   return n;
+   htx_src src = {r->p, r->p + strlen(r->p), 0};
+   const int got = htx_read_string(&src, 0, ".,)}", out, (size_t)cap);
+   r->p = src.p;
+   if (got == HTX_NONE) out[0] = 0;
+   return got < 0 ? -1 : (int)strlen(out);
 }
 
 /* PHIdent: the models one name or pattern selects, appended in walk order */
@@ -177,14 +157,14 @@ static int tc_parse_items_typed(const struct htkamd_mmf *s, const char *text, tc
       if (*r.p == '(') {
          do {
             r.p++;
-            if (tc_alpha(&r, buf, sizeof(buf)) < 0) { free(phys); TC_BAD("item list: unterminated quote in \"%s\"", text); }
+            if (tc_alpha(&r, buf, sizeof(buf)) < 0) { free(phys); TC_BAD("item list: unterminated quote or over-long name in \"%s\"", text); }
             tc_ident(s, walk, buf, &phys, &nP, &capP);
             tc_skip(&r);
          } while (*r.p == ',');
          if (*r.p != ')') { free(phys); TC_BAD("item list: ) expected in \"%s\"", text); }
          r.p++;
       } else {
-         if (tc_alpha(&r, buf, sizeof(buf)) < 0) { free(phys); TC_BAD("item list: unterminated quote in \"%s\"", text); }
+         if (tc_alpha(&r, buf, sizeof(buf)) < 0) { free(phys); TC_BAD("item list: unterminated quote or over-long name in \"%s\"", text); }
          tc_ident(s, walk, buf, &phys, &nP, &capP);
       }
       tc_skip(&r);
@@ -287,26 +267,23 @@ int htkamd_trees_write(const char *path, const htkamd_tree_question *q, int nQ, 
    if (!path || nQ < 0 || nT < 0 || (nQ && !q) || (nT && !t)) { htkamd_set_error("trees_write: bad argument"); return HTKAMD_EINVAL; }
    FILE *f = fopen(path, "w");
    if (!f) { htkamd_set_error("trees_write: cannot create %s", path); return HTKAMD_EIO; }
-   char buf[2100];
    for (int i = 0; i < nQ; i++) {                    /* LoadQuestion prepends the patterns (:453): they come out last first */
-      tc_rewrite(q[i].name, '\'', buf); fprintf(f, "QS %s ", buf);
-      for (int k = q[i].nPatterns - 1; k >= 0; k--) { tc_rewrite(q[i].patterns[k], '"', buf); fprintf(f, "%s%s", k == q[i].nPatterns - 1 ? "{ " : ",", buf); }
+      fputs("QS ", f); htx_write_string(f, q[i].name, '\'', 0); fputc(' ', f);
+      for (int k = q[i].nPatterns - 1; k >= 0; k--) { fputs(k == q[i].nPatterns - 1 ? "{ " : ",", f); htx_write_string(f, q[i].patterns[k], '"', 0); }
       fprintf(f, " }\n");
    }
    fprintf(f, "\n");
    for (int i = 0; i < nT; i++) {
       const htkamd_tree_desc *tr = &t[i];
-      tc_rewrite(tr->name, '\\', buf);
-      if (tr->state > 0) fprintf(f, "%s[%d]\n", buf, tr->state); else fprintf(f, "%s\n", tr->name);
-      if (tr->nNodes == 0) { tc_rewrite(tr->leafMacro[0], '"', buf); fprintf(f, "   %s\n\n", buf); continue; }
+      if (tr->state > 0) { htx_write_string(f, tr->name, HTX_ESCAPE, 0); fprintf(f, "[%d]\n", tr->state); } else fprintf(f, "%s\n", tr->name);
+      if (tr->nNodes == 0) { fputs("   ", f); htx_write_string(f, tr->leafMacro[0], '"', 0); fputs("\n\n", f); continue; }
       fprintf(f, "{\n");
       for (int n = 0; n < tr->nNodes; n++) {
-         tc_rewrite(q[tr->quest[n]].name, '\'', buf);
-         fprintf(f, " %3d %24s ", -n, buf);
+         fprintf(f, " %3d ", -n); htx_write_string(f, q[tr->quest[n]].name, '\'', 24); fputc(' ', f);
          for (int side = 0; side < 2; side++) {
             const int c = side ? tr->yes[n] : tr->no[n];
             if (c >= 0) fprintf(f, "  %5d    ", -c);
-            else { tc_rewrite(tr->leafMacro[-1 - c], '"', buf); fprintf(f, " %9s ", buf); }
+            else { fputc(' ', f); htx_write_string(f, tr->leafMacro[-1 - c], '"', 9); fputc(' ', f); }
          }
          fprintf(f, "\n");
       }

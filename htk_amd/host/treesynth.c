@@ -12,6 +12,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "mmf_priv.h"
+#include "htktext.h"
 
 /* the device side is absent from a build of the host files alone (treeclust.c) */
 #pragma weak htkamd_synth_dev_run
@@ -97,40 +98,13 @@ int htkamd_mmf_save_trees(const htkamd_mmf *s, const char *path)
 }
 
 /* ------------------------------------------------------------------------------------------ LT */
-typedef struct { const char *p, *end; } ts_src;
+typedef htx_src ts_src;
 
-/* one character of a string with ReadString's / ParseAlpha's escapes: \ooo or \c */
-static int ts_escaped(const char **pp, const char *end)
-{
-   const char *p = *pp;
-   int c = (unsigned char)*p;
-   if (c == '\\' && p + 1 < end) {
-      p++;
-      if (p + 2 < end && p[0] >= '0' && p[0] <= '7' && p[1] >= '0' && p[1] <= '7' && p[2] >= '0' && p[2] <= '7') { c = 64 * (p[0] - '0') + 8 * (p[1] - '0') + (p[2] - '0'); p += 2; }
-      else c = (unsigned char)*p;
-   }
-   *pp = p + 1;
-   return c;
-}
-
-/* ReadString (HShell.c:1242): white space, then a quoted string or one that ends at white space; 0 at the end of the text, -1 when a quote
-   is left open or the string does not fit */
+/* ReadString: 1, 0 at the end of the text, -1 when a quote is left open or the string does not fit */
 static int ts_string(ts_src *r, char *out, int cap)
 {
-   int n = 0;
-   while (r->p < r->end && isspace((unsigned char)*r->p)) r->p++;
-   if (r->p >= r->end) return 0;
-   char q = 0;
-   if (*r->p == '"' || *r->p == '\'') q = *r->p++;
-   for (;;) {
-      if (r->p >= r->end) { if (q) return -1; break; }
-      if (q ? *r->p == q : isspace((unsigned char)*r->p)) { if (q) r->p++; break; }
-      const int c = ts_escaped(&r->p, r->end);
-      if (n >= cap - 1) return -1;
-      out[n++] = (char)c;
-   }
-   out[n] = 0;
-   return 1;
+   const int got = htx_read_string(r, 0, NULL, out, (size_t)cap);
+   return got < 0 ? -1 : got;
 }
 
 typedef struct { int num, quest, kid[2]; } ts_line;      /* kid: >= 0 a node number, < 0 the leaf -1-k */
@@ -140,24 +114,16 @@ static int ts_cmp_state_name(const void *a, const void *b) { return strcmp(*(cha
 int htkamd_mmf_load_trees(htkamd_mmf *s, const char *path)
 {
    if (!s || !s->finished || !path) { htkamd_set_error("mmf_load_trees: bad argument"); return HTKAMD_EINVAL; }
-   FILE *f = fopen(path, "rb");
-   if (!f) { htkamd_set_error("mmf_load_trees: cannot open file %s", path); return HTKAMD_EIO; }
-   char *text = NULL; size_t len = 0, cap = 0;
-   for (;;) {
-      if (len + 65536 > cap) { cap = cap * 2 + 65536; text = (char *)realloc(text, cap + 1); }
-      const size_t got = fread(text + len, 1, 65536, f);
-      len += got;
-      if (got < 65536) break;
-   }
-   fclose(f);
-   text[len] = 0;
+   size_t len; int why;
+   char *text = htx_read_file(path, &len, &why);
+   if (!text) { htkamd_set_error(why == HTX_ENOMEM ? "mmf_load_trees: out of memory reading %s" : "mmf_load_trees: cannot open file %s", path); return why == HTX_ENOMEM ? HTKAMD_ENOMEM : HTKAMD_EIO; }
    mmf_trees *N = (mmf_trees *)calloc(1, sizeof(mmf_trees));      /* what the file holds; joins the held trees only when all of it is good */
    const mmf_trees *H = s->trees;
    const int nHeldQ = H ? H->nQ : 0;
    char **stName = (char **)malloc(sizeof(char *) * (size_t)(s->nSt + 1)); int nStName = 0;
    for (int i = 0; i < s->nSt; i++) if (s->st[i].name) stName[nStName++] = s->st[i].name;
    qsort(stName, (size_t)nStName, sizeof(char *), ts_cmp_state_name);
-   ts_src r = { text, text + len };
+   ts_src r = { text, text + len, 0 };
    char info[4200], buf[4200];
    char **pat = NULL; int nPat = 0, capPat = 0, rc = HTKAMD_OK, k;
    ts_line *ln = NULL; int nLn = 0, capLn = 0;
@@ -180,17 +146,12 @@ int htkamd_mmf_load_trees(htkamd_mmf *s, const char *path)
       p++; last--;                                      /* LoadQuestion: the closing brace stands for the last comma */
       nPat = 0;
       do {                                              /* ParseAlpha: quoted, or up to white space or one of ".,)" */
-         int n = 0; char q = 0;
-         while (p < last && isspace((unsigned char)*p)) p++;
-         if (p < last && (*p == '"' || *p == '\'')) q = *p++;
-         for (;;) {
-            if (p >= last) { if (q) LT_BAD(HTKAMD_EIO, "mmf_load_trees: %s: unterminated quote in question %s", path, qname); break; }
-            if (q ? *p == q : (isspace((unsigned char)*p) || strchr(".,)", *p))) { if (q) p++; break; }
-            const int c = ts_escaped(&p, last);
-            if (n >= (int)sizeof(buf) - 1) LT_BAD(HTKAMD_EIO, "mmf_load_trees: %s: a pattern of question %s is too long", path, qname);
-            buf[n++] = (char)c;
-         }
-         buf[n] = 0;
+         htx_src ps = {p, last, 0};
+         const int got = htx_read_string(&ps, 0, ".,)", buf, sizeof(buf));
+         if (got == HTX_OPEN) LT_BAD(HTKAMD_EIO, "mmf_load_trees: %s: unterminated quote in question %s", path, qname);
+         if (got == HTX_LONG) LT_BAD(HTKAMD_EIO, "mmf_load_trees: %s: a pattern of question %s is too long", path, qname);
+         if (got == HTX_NONE) buf[0] = 0;
+         p = ps.p;
          while (p < last && isspace((unsigned char)*p)) p++;
          if (p < last && *p != ',') LT_BAD(HTKAMD_EIO, "mmf_load_trees: %s: missing , in the item list of question %s", path, qname);
          p++;
@@ -492,8 +453,9 @@ int htkamd_mmf_add_unseen(htkamd_mmf *s, const char *hmmListPath, int *nSeen, in
    int rc = ts_check_set(s, "mmf_add_unseen");
    if (rc) return rc;
    const mmf_trees *T = s->trees;
-   FILE *f = fopen(hmmListPath, "r");
-   if (!f) { htkamd_set_error("mmf_add_unseen: cannot open HMM list %s", hmmListPath); return HTKAMD_EIO; }
+   size_t listLen; int why;
+   char *listTxt = htx_read_file(hmmListPath, &listLen, &why);
+   if (!listTxt) { htkamd_set_error(why == HTX_ENOMEM ? "mmf_add_unseen: out of memory reading HMM list %s" : "mmf_add_unseen: cannot open HMM list %s", hmmListPath); return why == HTX_ENOMEM ? HTKAMD_ENOMEM : HTKAMD_EIO; }
    char **names = NULL; int nL = 0, capL = 0;
    int *order = NULL, *phys = NULL, *sortIdx = NULL, *uOf = NULL, *proto = NULL, *pairName = NULL, *pairTree = NULL, *leaf = NULL, *pairOff = NULL;
    const char **uNames = NULL;
@@ -501,19 +463,15 @@ int htkamd_mmf_add_unseen(htkamd_mmf *s, const char *hmmListPath, int *nSeen, in
    int *baseProto = NULL; char **baseName = NULL; int nBase = 0;
    char **stName = NULL; int *stIdx = NULL;
    {
-      char line[1024], a[512], b[512];
-      while (fgets(line, sizeof(line), f)) {
-         const int n = sscanf(line, "%511s %511s", a, b);
-         if (n < 1) continue;
-         for (int q = 0; q < n; q++) {                  /* strip quotes, as the set's own list is read */
-            char *t = q ? b : a; const size_t L = strlen(t);
-            if (L >= 2 && (t[0] == '"' || t[0] == '\'') && t[L - 1] == t[0]) { memmove(t, t + 1, L - 2); t[L - 2] = 0; }
-         }
-         if (n == 2 && strcmp(a, b)) { htkamd_set_error("mmf_add_unseen: %s: model %s has the physical name %s: a list of plain names is expected", hmmListPath, a, b); rc = HTKAMD_EINVAL; break; }
+      char a[1024], b[1024]; int r;
+      htx_src src = {listTxt, listTxt + listLen, 0};
+      while ((r = htx_hmmlist_next(&src, a, sizeof(a), b, sizeof(b))) == HTX_GOT) {
+         if (b[0] && strcmp(a, b)) { htkamd_set_error("mmf_add_unseen: %s: model %s has the physical name %s: a list of plain names is expected", hmmListPath, a, b); rc = HTKAMD_EINVAL; break; }
          if (nL + 1 > capL) { capL = capL * 2 + 256; names = (char **)realloc(names, sizeof(char *) * (size_t)capL); }
          names[nL++] = strdup(a);
       }
-      fclose(f);
+      if (r < 0) { htkamd_set_error("mmf_add_unseen: HMM list %s, entry %d: %s", hmmListPath, nL + 1, htx_result_text(r)); rc = HTKAMD_EMODEL; }
+      free(listTxt);
    }
    if (!rc && nL == 0) { htkamd_set_error("mmf_add_unseen: %s lists no model", hmmListPath); rc = HTKAMD_EINVAL; }
    if (!rc) rc = ts_check_names("mmf_add_unseen", (const char *const *)names, nL);
@@ -766,12 +724,11 @@ int htkamd_mmf_compact(htkamd_mmf *s, const char *listPath, int *nLog, int *nPhy
    FILE *f = fopen(listPath, "w");
    if (!f) { htkamd_set_error("mmf_compact: cannot create HMM list file %s", listPath); return HTKAMD_EIO; }
    walk = tc_logical_walk(s);
-   char buf[2100];
    for (int k = 0; k < s->nLog; k++) {
       const int i = walk[k];
       const char *ph = s->hm[s->logPhys[i]].name;
-      tc_rewrite(s->logName[i], '\\', buf); fprintf(f, "%s", buf);
-      if (strcmp(ph, s->logName[i])) { tc_rewrite(ph, '\\', buf); fprintf(f, " %s", buf); }
+      htx_write_string(f, s->logName[i], HTX_ESCAPE, 0);
+      if (strcmp(ph, s->logName[i])) { fputc(' ', f); htx_write_string(f, ph, HTX_ESCAPE, 0); }
       fprintf(f, "\n");
    }
    free(walk);

@@ -213,7 +213,7 @@ def test_reader_and_writer_under_sanitizers(native, tmp_path):
     host = os.path.join(ROOT, "htk_amd", "host")
     subprocess.check_call(["gcc", "-O1", "-g", "-std=gnu11", "-fsanitize=address,undefined"] + static + ["-fno-omit-frame-pointer",
                            "-fno-sanitize-recover=undefined", "-ffp-contract=off", "-o", exe, os.path.join(ROOT, "tests", "inputxform_sanitize.c")] +
-                          [os.path.join(host, f) for f in ("mmf.c", "prep.c", "cepsnorm.c", "accio.c")] + ["-lm"])
+                          [os.path.join(host, f) for f in ("mmf.c", "prep.c", "cepsnorm.c", "accio.c", "htktext.c")] + ["-lm"])
     files = [os.path.join(SETS, "inline.mmf"), macro_set(tmp_path), extra_macro_set(tmp_path), os.path.join(SETS, "inline_bin.mmf"), os.path.join(SETS, "macro_bin.mmf")] + \
             [os.path.join(GOLD, "xf", f) for f in ("pre13b", "pre13b.bin", "pre13", "exp45")]
     scratch = tmp_path / "scratch"; scratch.mkdir()

@@ -287,7 +287,7 @@ int htkamd_results_label_id(htkamd_results *r, const char *name) { (void)r; (voi
 """)
     exe = str(tmp_path / "drv")
     subprocess.check_call(["gcc", "-g", "-O1", "-std=gnu11", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I" + os.path.join(ROOT, "include"),
-                           str(main_c), os.path.join(host, "latrescore.c"), os.path.join(host, "slfout.c"), os.path.join(host, "labio.c"), "-o", exe, "-lm"])
+                           str(main_c), os.path.join(host, "latrescore.c"), os.path.join(host, "slfout.c"), os.path.join(host, "labio.c"), os.path.join(host, "htktext.c"), "-o", exe, "-lm"])
     bad = []
     good = open(groups["random"]["paths"]["r20"]).read()
     for i, text in enumerate(["", "N=2", "N=2 L=1\nI=0 W=\n", "N=2 L=1\nI=7\n", "N=2 L=1\nJ=0 S=0\n", good[:len(good) // 3], good.replace(" S=", " S~", 1),
