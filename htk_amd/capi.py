@@ -11,6 +11,8 @@ import os
 
 import numpy as np
 
+from . import abi
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIBPATH = os.path.join(HERE, "libhtk_amd.so")
 
@@ -24,8 +26,8 @@ UTT_OK, UTT_SKIPPED, UTT_ETEE, UTT_EALPHA = 1, 0, -7332, -7390
 
 
 def _stream(s):
-    """A raw hipStream_t given as a Python int (torch: stream.cuda_stream) must travel as a pointer, not as a C int."""
-    return None if s is None else (s if isinstance(s, C.c_void_p) else C.c_void_p(int(s)))
+    """A stream or device address from outside (torch: stream.cuda_stream, tensor.data_ptr(); a c_void_p; None) as a void * parameter takes it."""
+    return s if s is None or isinstance(s, C.c_void_p) else int(s)
 
 
 SCORE_EXACT, SCORE_MFMA, SCORE_FASTLADD, SCORE_BF16, SCORE_SOUTP, SCORE_DIAGC, SCORE_F16 = 0, 1, 2, 4, 8, 16, 32
@@ -82,24 +84,7 @@ def lib():
         if not os.path.exists(LIBPATH):
             raise HtkAmdError("%s is missing: run `python -m htk_amd.build` (hipcc --offload-arch=gfx950)" % LIBPATH)
         L = C.CDLL(LIBPATH)
-        L.htkamd_last_error.restype = C.c_char_p
-        L.htkamd_fb_frame_states.restype = C.c_longlong
-        L.htkamd_fb_frame_states.argtypes = [C.c_void_p]
-        # the decoder set (a network per utterance): create(model, nets[], nNets, lmScale, out), run(set, cfg, dX, frameOff, netOf, nUtt, maxWords, out, stream)
-        if hasattr(L, "htkamd_decoder_set_create"):      # (a build of the host code alone has no decoders)
-            L.htkamd_decoder_set_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p]; L.htkamd_decoder_set_create.restype = C.c_int
-            L.htkamd_decoder_set_destroy.argtypes = [C.c_void_p]; L.htkamd_decoder_set_destroy.restype = None
-            L.htkamd_decoder_set_run.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-            L.htkamd_decoder_set_run.restype = C.c_int
-            L.htkamd_decoder_set_last_tied.argtypes = [C.c_void_p]; L.htkamd_decoder_set_last_tied.restype = C.c_int
-            # (cfg, nToks, nBeam, [alignMode,] dX, frameOff, netOf, nUtt, maxLatNodes, maxLatArcs, [maxAlign,] out, [alOut,] stream)
-            L.htkamd_decoder_set_run_lattice.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                                         C.c_void_p]
-            L.htkamd_decoder_set_run_lattice.restype = C.c_int
-            L.htkamd_decoder_set_run_lattice_align.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                                               C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.htkamd_decoder_set_run_lattice_align.restype = C.c_int
-            L.htkamd_decoder_set_set_order.argtypes = [C.c_void_p, C.c_int]; L.htkamd_decoder_set_set_order.restype = C.c_int
+        abi.declare(L, STRUCTS)      # every prototype of include/htk_amd.h, once: a wrong argument is a TypeError at the call
         _lib = L
     return _lib
 
@@ -115,21 +100,37 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+class _Handle:
+    """The owner of one C handle `h`: close() gives it to the class's destroy function once, and so does the finaliser."""
+    _destroy = None
+
+    def close(self):
+        if self.h:
+            getattr(lib(), self._destroy)(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DevArray:
     """A device buffer owned through the C ABI (hipMalloc)."""
 
     def __init__(self, host: np.ndarray | None = None, nbytes: int | None = None):
         self.ptr = C.c_void_p()
         self.nbytes = int(host.nbytes if host is not None else nbytes)
-        check(lib().htkamd_dev_malloc(C.byref(self.ptr), C.c_size_t(self.nbytes)), "dev_malloc")
+        check(lib().htkamd_dev_malloc(C.byref(self.ptr), self.nbytes), "dev_malloc")
         if host is not None:
             h = np.ascontiguousarray(host)
-            check(lib().htkamd_memcpy_h2d(self.ptr, _p(h), C.c_size_t(h.nbytes), None), "memcpy_h2d")
+            check(lib().htkamd_memcpy_h2d(self.ptr, _p(h), h.nbytes, None), "memcpy_h2d")
 
     def to_host(self, dtype, shape):
         out = np.empty(shape, dtype)
         assert out.nbytes <= self.nbytes
-        check(lib().htkamd_memcpy_d2h(_p(out), self.ptr, C.c_size_t(out.nbytes), None), "memcpy_d2h")
+        check(lib().htkamd_memcpy_d2h(_p(out), self.ptr, out.nbytes, None), "memcpy_d2h")
         return out
 
     def free(self):
@@ -144,30 +145,35 @@ class DevArray:
             pass
 
 
-class Model:
+def _desc_from_packed(pk: dict):
+    """(ModelDesc, keepalive) from a packed dict -- for the pure-host entry points that take a description."""
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+    k = dict(stateCompOff=i32(pk["stateCompOff"]), compWeight=f32(pk["compWeight"]), compGauss=i32(pk["compGauss"]),
+             mean=f32(pk["mean"]), var=f32(pk["var"]), gconst=f32(pk.get("gconst")),
+             transN=i32(pk["transN"]), transOff=i32(pk["transOff"]), transP=f32(pk["transP"]),
+             hmmTrans=i32(pk["hmmTrans"]), hmmStateOff=i32(pk["hmmStateOff"]), hmmState=i32(pk["hmmState"]),
+             dimStream=i32(pk["dimStream"]) if pk.get("dimStream") is not None else None, streamWeight=f32(pk.get("streamWeight")))
+    d = ModelDesc(int(pk["vecSize"]), int(pk["numStates"]), int(pk["numComp"]), int(pk["numGauss"]), int(pk["numTrans"]), int(pk["numPhys"]),
+                  _p(k["stateCompOff"]), _p(k["compWeight"]), _p(k["compGauss"]), _p(k["mean"]), _p(k["var"]), _p(k["gconst"]),
+                  _p(k["transN"]), _p(k["transOff"]), _p(k["transP"]), _p(k["hmmTrans"]), _p(k["hmmStateOff"]), _p(k["hmmState"]),
+                  int(pk.get("numStreams", 1) or 1), _p(k["dimStream"]), int(pk.get("hsKind", 0) or 0), _p(k["streamWeight"]))
+    return d, k
+
+
+class Model(_Handle):
     """htkamd_model holder.  `pk` is the packed layout dict (htk_amd.synth.SynthSet.packed() / the MMF loader)."""
+    _destroy = "htkamd_model_destroy"
 
     def __init__(self, pk: dict):
-        f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
-        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         self.pk = pk
-        self._keep = dict(stateCompOff=i32(pk["stateCompOff"]), compWeight=f32(pk["compWeight"]), compGauss=i32(pk["compGauss"]),
-                          mean=f32(pk["mean"]), var=f32(pk["var"]), gconst=f32(pk.get("gconst")),
-                          transN=i32(pk["transN"]), transOff=i32(pk["transOff"]), transP=f32(pk["transP"]),
-                          hmmTrans=i32(pk["hmmTrans"]), hmmStateOff=i32(pk["hmmStateOff"]), hmmState=i32(pk["hmmState"]),
-                          dimStream=i32(pk["dimStream"]) if pk.get("dimStream") is not None else None,
-                          streamWeight=f32(pk.get("streamWeight")))
-        k = self._keep
-        self.NS = int(pk.get("numStreams", 1) or 1)
-        d = ModelDesc(int(pk["vecSize"]), int(pk["numStates"]), int(pk["numComp"]), int(pk["numGauss"]),
-                      int(pk["numTrans"]), int(pk["numPhys"]),
-                      _p(k["stateCompOff"]), _p(k["compWeight"]), _p(k["compGauss"]), _p(k["mean"]), _p(k["var"]), _p(k["gconst"]),
-                      _p(k["transN"]), _p(k["transOff"]), _p(k["transP"]), _p(k["hmmTrans"]), _p(k["hmmStateOff"]), _p(k["hmmState"]),
-                      self.NS, _p(k["dimStream"]), int(pk.get("hsKind", 0) or 0), _p(k["streamWeight"]))
+        d, k = _desc_from_packed(pk)
+        self._keep = k
+        self.NS = d.numStreams
         self.h = C.c_void_p()
         self.full = pk.get("invCov") is not None
         if self.full:       # FULLC set: the packed inverse-covariance triangles, desc.var unused (htkamd_model_create_full)
-            k["invCov"] = f32(pk["invCov"]).reshape(-1)
+            k["invCov"] = np.ascontiguousarray(pk["invCov"], np.float32).reshape(-1)
             check(lib().htkamd_model_create_full(C.byref(d), _p(k["invCov"]), C.byref(self.h)), "model_create_full")
         else:
             check(lib().htkamd_model_create(C.byref(d), C.byref(self.h)), "model_create")
@@ -182,7 +188,7 @@ class Model:
 
     def set_compat(self, flags: int):
         """The reference's own arithmetic where the library computes something else (htkamd_model_set_compat; COMPAT_STREAM_REVISIT)."""
-        check(lib().htkamd_model_set_compat(self.h, C.c_int(int(flags))), "model_set_compat")
+        check(lib().htkamd_model_set_compat(self.h, int(flags)), "model_set_compat")
 
     def set_scan_order(self, order):
         """The order in which UpdateModels visits the physical models (htkamd_model_set_scan_order; hmm_scan_order() gives HTK's)."""
@@ -201,17 +207,19 @@ class Model:
         check(lib().htkamd_model_get_prepared(self.h, _p(ivar), _p(gc), _p(lw), _p(md)), "model_get_prepared")
         return dict(ivar=ivar, gconst=gc, compLogWt=lw, minDur=md)
 
+    def _update_config(self, minEgs, minVar, mixWeightFloor, uFlags, singleProcess, varFloor, rowNormalise, mapTau=0.0, mapMinObs=0.0):
+        """(htkamd_update_config, the array its varFloor points into)"""
+        vf = None if varFloor is None else np.ascontiguousarray(varFloor, np.float32)
+        assert vf is None or vf.shape == (self.D,)
+        return UpdateConfig(minEgs, minVar, mixWeightFloor, uFlags, int(singleProcess), None if vf is None else vf.ctypes.data_as(C.POINTER(C.c_float)),
+                            int(rowNormalise), mapTau, mapMinObs), vf
+
     def update(self, accs: "Accs", vec: np.ndarray, minEgs=3, minVar=0.0, mixWeightFloor=0.0, uFlags=UPALL, singleProcess=False, varFloor=None,
                rowNormalise=False, mapTau=20.0, mapMinObs=0.0):
         """UpdateModels (HERest.c:1326) from a host copy of the (summed) accumulator vector.  varFloor: the ~v "varFloor1" vector.
         uFlags with UPMAP: MAPUpdateModels (HMap.c:413) with prior weight mapTau."""
         vec = np.ascontiguousarray(vec, np.float64)
-        vf = None
-        if varFloor is not None:
-            vf = np.ascontiguousarray(varFloor, np.float32)
-            assert vf.shape == (self.D,)
-        cfg = UpdateConfig(minEgs, minVar, mixWeightFloor, uFlags, int(singleProcess),
-                           vf.ctypes.data_as(C.POINTER(C.c_float)) if vf is not None else None, int(rowNormalise), mapTau, mapMinObs)
+        cfg, vf = self._update_config(minEgs, minVar, mixWeightFloor, uFlags, singleProcess, varFloor, rowNormalise, mapTau, mapMinObs)
         st = UpdateStats()
         check(lib().htkamd_model_update(self.h, accs.h, _p(vec), C.byref(cfg), C.byref(st)), "model_update")
         return {n: getattr(st, n) for n, _ in UpdateStats._fields_}
@@ -219,12 +227,7 @@ class Model:
     def update_device(self, accs: "Accs", minEgs=3, minVar=0.0, mixWeightFloor=0.0, uFlags=UPALL, singleProcess=False, varFloor=None,
                       rowNormalise=False, stream=None):
         """The same update on the device, from the accumulator vector where it lies (htkamd_model_update_device)."""
-        vf = None
-        if varFloor is not None:
-            vf = np.ascontiguousarray(varFloor, np.float32)
-            assert vf.shape == (self.D,)
-        cfg = UpdateConfig(minEgs, minVar, mixWeightFloor, uFlags, int(singleProcess),
-                           vf.ctypes.data_as(C.POINTER(C.c_float)) if vf is not None else None, int(rowNormalise), 0.0, 0.0)
+        cfg, vf = self._update_config(minEgs, minVar, mixWeightFloor, uFlags, singleProcess, varFloor, rowNormalise)
         st = UpdateStats()
         check(lib().htkamd_model_update_device(self.h, accs.h, C.byref(cfg), C.byref(st), _stream(stream)), "model_update_device")
         return {n: getattr(st, n) for n, _ in UpdateStats._fields_}
@@ -232,12 +235,7 @@ class Model:
     def update_device_begin(self, accs: "Accs", minEgs=3, minVar=0.0, mixWeightFloor=0.0, uFlags=UPALL, singleProcess=False, varFloor=None,
                             rowNormalise=False, stream=None):
         """First half of update_device: every launch and the copy of what the host needs, no wait (htkamd_model_update_device_begin)."""
-        vf = None
-        if varFloor is not None:
-            vf = np.ascontiguousarray(varFloor, np.float32)
-            assert vf.shape == (self.D,)
-        cfg = UpdateConfig(minEgs, minVar, mixWeightFloor, uFlags, int(singleProcess),
-                           vf.ctypes.data_as(C.POINTER(C.c_float)) if vf is not None else None, int(rowNormalise), 0.0, 0.0)
+        cfg, vf = self._update_config(minEgs, minVar, mixWeightFloor, uFlags, singleProcess, varFloor, rowNormalise)
         check(lib().htkamd_model_update_device_begin(self.h, accs.h, C.byref(cfg), _stream(stream)), "model_update_device_begin")
 
     def update_device_end(self):
@@ -277,25 +275,15 @@ class Model:
             return np.empty((T, ns), np.float32)
         dX, dS = DevArray(X), DevArray(states)
         dO = DevArray(nbytes=4 * T * ns)
-        check(lib().htkamd_outp_block_mode(self.h, dX.ptr, C.c_int(T), dS.ptr, C.c_int(ns), dO.ptr, C.c_int(T), C.c_int(mode), None), "outp_block")
+        check(lib().htkamd_outp_block_mode(self.h, dX.ptr, T, dS.ptr, ns, dO.ptr, T, mode, None), "outp_block")
         if mode & SCORE_F16:
             check(lib().htkamd_model_f16_check(self.h, None), "model_f16_check")      # HTKAMD_ERANGE: repeat with SCORE_BF16
         out = dO.to_host(np.float32, (ns, T))
         return np.ascontiguousarray(out.T)
 
-    def close(self):
-        if self.h:
-            lib().htkamd_model_destroy(self.h)
-            self.h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Accs:
+class Accs(_Handle):
+    _destroy = "htkamd_accs_destroy"
     def __init__(self, model: Model):
         self.model = model
         self.h = C.c_void_p()
@@ -328,13 +316,13 @@ class Accs:
     def state_ranges(self, state0: int, state1: int, with_rest: bool = False):
         """htkamd_accs_state_ranges: [(offset, length)] of the vector's ranges that belong to tied states [state0, state1) (+ tr / trOcc with with_rest)"""
         off = (C.c_size_t * 7)(); ln = (C.c_size_t * 7)(); n = C.c_int(0)
-        check(lib().htkamd_accs_state_ranges(self.h, C.c_int(state0), C.c_int(state1), C.c_int(int(with_rest)), off, ln, C.byref(n)), "accs_state_ranges")
+        check(lib().htkamd_accs_state_ranges(self.h, state0, state1, int(with_rest), off, ln, C.byref(n)), "accs_state_ranges")
         return [(int(off[k]), int(ln[k])) for k in range(n.value)]
 
     def _ranges(self, fn, ranges, wire, ptr, stream):
         n = len(ranges)
         off = (C.c_size_t * max(n, 1))(*[r[0] for r in ranges]); ln = (C.c_size_t * max(n, 1))(*[r[1] for r in ranges])
-        check(fn(self.h, C.c_int(n), off, ln, C.c_int(wire), C.c_void_p(ptr), _stream(stream)), "accs ranges")
+        check(fn(self.h, n, off, ln, wire, ptr, _stream(stream)), "accs ranges")
 
     def pack_ranges(self, ranges, wire: int, dst_ptr: int, stream=None):
         """htkamd_accs_pack_ranges: the ranges one behind the other into device memory at dst_ptr, as floats (wire = 1) or doubles (0)"""
@@ -352,24 +340,14 @@ class Accs:
                     nEgs=v[L.nEgs:L.nEgs + m.H], totalPr=v[L.totalPr], totalT=v[L.totalT], nUttDone=v[L.nUttDone],
                     nUttSkipped=v[L.nUttSkipped], nEval=v[L.nEval])
 
-    def close(self):
-        if self.h:
-            lib().htkamd_accs_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def fb_config(pruneInit=NOPRUNE, pruneInc=0.0, pruneLim=NOPRUNE, minFrwdP=10.0, uFlags=UPALL, scoreMode=0):
     return FbConfig(pruneInit, pruneInc, pruneLim, minFrwdP, uFlags, scoreMode)
 
 
-class ForwardBackward:
+class ForwardBackward(_Handle):
     """htkamd_fb holder: FBFile (HFB.c:1923) over a batch of utterances."""
+    _destroy = "htkamd_fb_destroy"
 
     def __init__(self, model: Model, debug: bool = False, force_general: bool = False, no_state_path: bool = False, stats_list: str = "auto", no_lr_path: bool = False):
         """stats_list: how the mixture statistics reach the accumulators -- "auto": record list + per-Gaussian reduction,
@@ -388,7 +366,7 @@ class ForwardBackward:
         labs = np.ascontiguousarray(labs, np.int32)
         self.nUtt = len(frameOff) - 1
         self._keep = (frameOff, labOff, labs)
-        b = BatchDesc(self.nUtt, C.c_void_p(dX_ptr), _p(frameOff), _p(labOff), _p(labs))
+        b = BatchDesc(self.nUtt, dX_ptr, _p(frameOff), _p(labOff), _p(labs))
         check(lib().htkamd_fb_prepare(self.h, C.byref(b), _stream(stream)), "fb_prepare")
 
     def execute(self, cfg: FbConfig, accs: Accs, stream=None):
@@ -402,7 +380,7 @@ class ForwardBackward:
 
     def execute_mix(self, state0: int, state1: int, stream=None):
         """htkamd_fb_execute_mix: the mixture statistics of tied states [state0, state1)."""
-        check(lib().htkamd_fb_execute_mix(self.h, C.c_int(state0), C.c_int(state1), _stream(stream)), "fb_execute_mix")
+        check(lib().htkamd_fb_execute_mix(self.h, state0, state1, _stream(stream)), "fb_execute_mix")
 
     def results_begin(self, stream=None):
         """Queue the copy of the results behind the pass on its stream (htkamd_fb_results_begin); results() then only waits for it."""
@@ -426,7 +404,7 @@ class ForwardBackward:
 
     def set_event_mode(self, mode: int):
         """htkamd_fb_set_event_mode: 0 events between all kernels (default), 1 the scoring dispatch's own only (the other intervals read -1)."""
-        check(lib().htkamd_fb_set_event_mode(self.h, C.c_int(mode)), "fb_set_event_mode")
+        check(lib().htkamd_fb_set_event_mode(self.h, mode), "fb_set_event_mode")
 
     def kernel_times5(self):
         """seconds: scoring, beta, alpha, left-to-right statistics, mixture statistics (htkamd_fb_kernel_times5)"""
@@ -448,31 +426,21 @@ class ForwardBackward:
 
     def trellis(self, u: int, want_alpha: bool = True):
         T = C.c_int(); Q = C.c_int(); mN = C.c_int()
-        check(lib().htkamd_fb_get_trellis(self.h, C.c_int(u), None, None, None, None, None, None, None,
+        check(lib().htkamd_fb_get_trellis(self.h, u, None, None, None, None, None, None, None,
                                           C.byref(T), C.byref(Q), C.byref(mN), None), "fb_get_trellis")
         T, Q, mN = T.value, Q.value, mN.value
         d = dict(beta=np.empty((T, Q, mN)), alpha=np.empty((T, Q, mN)) if want_alpha else None,
                  outp=np.empty((T, Q, mN), np.float32), qLo=np.zeros(T, np.int32), qHi=np.zeros(T, np.int32),
                  aLo=np.zeros(T, np.int32), aHi=np.zeros(T, np.int32))
-        check(lib().htkamd_fb_get_trellis(self.h, C.c_int(u), _p(d["beta"]), _p(d["alpha"]), _p(d["outp"]),
+        check(lib().htkamd_fb_get_trellis(self.h, u, _p(d["beta"]), _p(d["alpha"]), _p(d["outp"]),
                                           _p(d["qLo"]), _p(d["qHi"]), _p(d["aLo"]), _p(d["aHi"]), None, None, None, None),
               "fb_get_trellis")
         return d
 
-    def close(self):
-        if self.h:
-            lib().htkamd_fb_destroy(self.h)
-            self.h = C.c_void_p()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Viterbi:
+class Viterbi(_Handle):
     """htkamd_viterbi holder: HVite -a forced alignment of a batch (HRec token passing on the label chain)."""
+    _destroy = "htkamd_viterbi_destroy"
 
     def __init__(self, model: Model):
         self.model = model
@@ -485,8 +453,8 @@ class Viterbi:
         labs = np.ascontiguousarray(labs, np.int32)
         self._keep = (frameOff, labOff, labs)
         nUtt = len(frameOff) - 1
-        b = BatchDesc(nUtt, C.c_void_p(dX_ptr), _p(frameOff), _p(labOff), _p(labs))
-        check(lib().htkamd_viterbi_align_mode(self.h, C.byref(b), C.c_float(genBeam), C.c_int(scoreMode), _stream(stream)), "viterbi_align")
+        b = BatchDesc(nUtt, dX_ptr, _p(frameOff), _p(labOff), _p(labs))
+        check(lib().htkamd_viterbi_align_mode(self.h, C.byref(b), genBeam, scoreMode, _stream(stream)), "viterbi_align")
         ns = C.c_size_t(); nm = C.c_size_t()
         check(lib().htkamd_viterbi_sizes(self.h, C.byref(ns), C.byref(nm)), "viterbi_sizes")
         r = dict(segStart=np.empty(ns.value, np.int32), segEnd=np.empty(ns.value, np.int32), segScore=np.empty(ns.value, np.float64),
@@ -509,17 +477,6 @@ class Viterbi:
                             total=r["total"][u], status=int(r["status"][u])))
             so += n; mo += len(ql)
         return out
-
-    def close(self):
-        if self.h:
-            lib().htkamd_viterbi_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def format_rec(utt: dict, names, frame_dur: int = 100000):
@@ -560,8 +517,9 @@ def mfcc_config(kind="MFCC_0_D_A", sampPeriod=625.0, winDur=250000.0, frPeriod=1
                       int("0" in q[1:]), int("E" in q[1:]), int("D" in q[1:]), int("A" in q[1:]), int("Z" in q[1:]), delWin, accWin)
 
 
-class Mfcc:
+class Mfcc(_Handle):
     """htkamd_mfcc holder: waveform -> MFCC feature matrix on the device (HParm/HSigP front end)."""
+    _destroy = "htkamd_mfcc_destroy"
 
     def __init__(self, cfg: MfccConfig):
         self.cfg = cfg
@@ -574,29 +532,18 @@ class Mfcc:
         waves = [np.ascontiguousarray(w, np.int16) for w in waves]
         sampOff = np.concatenate([[0], np.cumsum([len(w) for w in waves])]).astype(np.int32)
         allw = np.concatenate(waves) if waves else np.zeros(0, np.int16)
-        frames = [lib().htkamd_mfcc_num_frames(C.byref(self.cfg), C.c_int(len(w))) for w in waves]
+        frames = [lib().htkamd_mfcc_num_frames(C.byref(self.cfg), len(w)) for w in waves]
         total = int(sum(frames))
         dW = DevArray(allw if len(allw) else np.zeros(1, np.int16))
         dO = DevArray(nbytes=4 * max(total, 1) * self.cols)
         frameOff = np.zeros(len(waves) + 1, np.int32)
-        check(lib().htkamd_mfcc_compute(self.h, dW.ptr, _p(sampOff), C.c_int(len(waves)), _p(frameOff), dO.ptr, _stream(stream)), "mfcc_compute")
+        check(lib().htkamd_mfcc_compute(self.h, dW.ptr, _p(sampOff), len(waves), _p(frameOff), dO.ptr, _stream(stream)), "mfcc_compute")
         assert frameOff[-1] == total
         return dO, frameOff
 
     def compute_host(self, waves):
         dO, frameOff = self.compute(waves)
         return dO.to_host(np.float32, (int(frameOff[-1]), self.cols)), frameOff
-
-    def close(self):
-        if self.h:
-            lib().htkamd_mfcc_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class FrontEndConfig(C.Structure):
@@ -635,10 +582,11 @@ class Warp(C.Structure):
     _fields_ = [("warpFreq", C.c_float), ("warpLCutoff", C.c_float), ("warpUCutoff", C.c_float)]
 
 
-class FrontEnd:
+class FrontEnd(_Handle):
     """htkamd_frontend holder: waveform -> MFCC / FBANK / MELSPEC / PLP feature matrix on the device.
     warps: [(WARPFREQ, WARPLCUTOFF, WARPUCUTOFF), ...] (1..64) makes a front end with one filterbank per warp (VTLN): compute codes
     every utterance with the warp `warp_index` names for it, compute_grid every utterance under every warp."""
+    _destroy = "htkamd_frontend_destroy"
 
     def __init__(self, cfg: FrontEndConfig, warps=None):
         self.cfg = cfg
@@ -648,14 +596,14 @@ class FrontEnd:
             check(lib().htkamd_frontend_create(C.byref(cfg), C.byref(self.h)), "frontend_create")
         else:
             arr = (Warp * max(len(warps), 1))(*[Warp(*w) for w in warps])
-            check(lib().htkamd_frontend_create_warped(C.byref(cfg), arr, C.c_int(len(warps)), C.byref(self.h)), "frontend_create_warped")
+            check(lib().htkamd_frontend_create_warped(C.byref(cfg), arr, len(warps), C.byref(self.h)), "frontend_create_warped")
         self.num_warps = lib().htkamd_frontend_num_warps(self.h)
 
     def _upload(self, waves, tables=1):
         waves = [np.ascontiguousarray(w, np.int16) for w in waves]
         sampOff = np.concatenate([[0], np.cumsum([len(w) for w in waves])]).astype(np.int32)
         allw = np.concatenate(waves) if waves else np.zeros(0, np.int16)
-        frames = [lib().htkamd_frontend_num_frames(C.byref(self.cfg), C.c_int(len(w))) for w in waves]
+        frames = [lib().htkamd_frontend_num_frames(C.byref(self.cfg), len(w)) for w in waves]
         total = int(sum(frames))
         dW = DevArray(allw if len(allw) else np.zeros(1, np.int16))
         dO = DevArray(nbytes=4 * max(total, 1) * self.cols * tables)
@@ -666,13 +614,13 @@ class FrontEnd:
         Returns (DevArray features [sumT, cols], frameOff)."""
         dW, dO, sampOff, frameOff, total = self._upload(waves)
         if warp_index is None:
-            check(lib().htkamd_frontend_compute(self.h, dW.ptr, _p(sampOff), C.c_int(len(waves)), _p(frameOff), dO.ptr, _stream(stream)),
+            check(lib().htkamd_frontend_compute(self.h, dW.ptr, _p(sampOff), len(waves), _p(frameOff), dO.ptr, _stream(stream)),
                   "frontend_compute")
         else:
             idx = np.ascontiguousarray(warp_index, np.int32)
             if idx.shape != (len(waves),):
                 raise HtkAmdError("warp_index: one entry per utterance expected")
-            check(lib().htkamd_frontend_compute_warped(self.h, dW.ptr, _p(sampOff), C.c_int(len(waves)), _p(idx), _p(frameOff), dO.ptr,
+            check(lib().htkamd_frontend_compute_warped(self.h, dW.ptr, _p(sampOff), len(waves), _p(idx), _p(frameOff), dO.ptr,
                                                        _stream(stream)), "frontend_compute_warped")
         assert frameOff[-1] == total
         return dO, frameOff
@@ -685,7 +633,7 @@ class FrontEnd:
         """Every utterance under every warp.  Returns (DevArray [num_warps, sumT, cols], frameOff): table w is what compute gives with
         every utterance on warp w."""
         dW, dO, sampOff, frameOff, total = self._upload(waves, self.num_warps)
-        check(lib().htkamd_frontend_compute_grid(self.h, dW.ptr, _p(sampOff), C.c_int(len(waves)), _p(frameOff), dO.ptr, _stream(stream)),
+        check(lib().htkamd_frontend_compute_grid(self.h, dW.ptr, _p(sampOff), len(waves), _p(frameOff), dO.ptr, _stream(stream)),
               "frontend_compute_grid")
         assert frameOff[-1] == total
         return dO, frameOff
@@ -693,33 +641,6 @@ class FrontEnd:
     def compute_grid_host(self, waves):
         dO, frameOff = self.compute_grid(waves)
         return dO.to_host(np.float32, (self.num_warps, int(frameOff[-1]), self.cols)), frameOff
-
-    def close(self):
-        if self.h:
-            lib().htkamd_frontend_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _desc_from_packed(pk: dict):
-    """(ModelDesc, keepalive) from a packed dict -- for the pure-host entry points that take a description."""
-    f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
-    i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-    k = dict(stateCompOff=i32(pk["stateCompOff"]), compWeight=f32(pk["compWeight"]), compGauss=i32(pk["compGauss"]),
-             mean=f32(pk["mean"]), var=f32(pk["var"]), gconst=f32(pk.get("gconst")),
-             transN=i32(pk["transN"]), transOff=i32(pk["transOff"]), transP=f32(pk["transP"]),
-             hmmTrans=i32(pk["hmmTrans"]), hmmStateOff=i32(pk["hmmStateOff"]), hmmState=i32(pk["hmmState"]),
-             dimStream=i32(pk["dimStream"]) if pk.get("dimStream") is not None else None, streamWeight=f32(pk.get("streamWeight")))
-    d = ModelDesc(int(pk["vecSize"]), int(pk["numStates"]), int(pk["numComp"]), int(pk["numGauss"]), int(pk["numTrans"]), int(pk["numPhys"]),
-                  _p(k["stateCompOff"]), _p(k["compWeight"]), _p(k["compGauss"]), _p(k["mean"]), _p(k["var"]), _p(k["gconst"]),
-                  _p(k["transN"]), _p(k["transOff"]), _p(k["transP"]), _p(k["hmmTrans"]), _p(k["hmmStateOff"]), _p(k["hmmState"]),
-                  int(pk.get("numStreams", 1) or 1), _p(k["dimStream"]), int(pk.get("hsKind", 0) or 0), _p(k["streamWeight"]))
-    return d, k
 
 
 def _names_array(names):
@@ -736,7 +657,7 @@ def accs_layout(pk: dict) -> AccsLayout:
 
 def hmm_scan_order(names) -> np.ndarray:
     order = np.zeros(len(names), np.int32)
-    check(lib().htkamd_hmm_scan_order(_names_array(names), C.c_int(len(names)), _p(order)), "hmm_scan_order")
+    check(lib().htkamd_hmm_scan_order(_names_array(names), len(names), _p(order)), "hmm_scan_order")
     return order
 
 
@@ -745,14 +666,14 @@ def accs_dump_file(pk: dict, vec: np.ndarray, names, path: str, uFlags: int = UP
     d, keep = _desc_from_packed(pk)
     vec = np.ascontiguousarray(vec, np.float64)
     ms, vs = (None, None) if sharing is None else (np.ascontiguousarray(sharing[0], np.int32), np.ascontiguousarray(sharing[1], np.int32))
-    check(lib().htkamd_accs_dump_file_shared(C.byref(d), _p(vec), _names_array(names), C.c_int(uFlags), _p(ms), _p(vs), path.encode()), "accs_dump_file")
+    check(lib().htkamd_accs_dump_file_shared(C.byref(d), _p(vec), _names_array(names), uFlags, _p(ms), _p(vs), path.encode()), "accs_dump_file")
 
 
 def accs_load_file(pk: dict, vec: np.ndarray, names, path: str, uFlags: int = UPALL, sharing=None):
     d, keep = _desc_from_packed(pk)
     assert vec.dtype == np.float64 and vec.flags.c_contiguous
     ms, vs = (None, None) if sharing is None else (np.ascontiguousarray(sharing[0], np.int32), np.ascontiguousarray(sharing[1], np.int32))
-    check(lib().htkamd_accs_load_file_shared(C.byref(d), _p(vec), _names_array(names), C.c_int(uFlags), _p(ms), _p(vs), path.encode()), "accs_load_file")
+    check(lib().htkamd_accs_load_file_shared(C.byref(d), _p(vec), _names_array(names), uFlags, _p(ms), _p(vs), path.encode()), "accs_load_file")
 
 
 def stats_write_file(pk: dict, vec: np.ndarray, names, path: str):
@@ -778,7 +699,7 @@ WAVE_HTK, WAVE_WAV = 1, 2
 def wave_read(path: str, fmt: int = WAVE_WAV):
     """Waveform file -> (int16 samples, sampPeriod in 100 ns units) through the host C reader."""
     data = C.c_void_p(); n = C.c_long(); per = C.c_double()
-    check(lib().htkamd_wave_read(path.encode(), C.c_int(fmt), C.byref(data), C.byref(n), C.byref(per)), "wave_read")
+    check(lib().htkamd_wave_read(path.encode(), fmt, C.byref(data), C.byref(n), C.byref(per)), "wave_read")
     arr = np.ctypeslib.as_array((C.c_short * max(n.value, 1)).from_address(data.value))[:n.value].copy()
     lib().htkamd_free(data)
     return arr, per.value
@@ -786,8 +707,8 @@ def wave_read(path: str, fmt: int = WAVE_WAV):
 
 def parm_write(path: str, X: np.ndarray, sampPeriod: int, kind: int, withCrc: bool = False):
     X = np.ascontiguousarray(X, np.float32)
-    check(lib().htkamd_parm_write(path.encode(), _p(X), C.c_int(X.shape[0]), C.c_int(X.shape[1]), C.c_int(sampPeriod), C.c_int(kind),
-                                  C.c_int(int(withCrc))), "parm_write")
+    check(lib().htkamd_parm_write(path.encode(), _p(X), X.shape[0], X.shape[1], sampPeriod, kind,
+                                  int(withCrc)), "parm_write")
 
 
 def parm_add_qualifiers(stat_list, hasD=True, hasA=False, delWin=2, accWin=2) -> "DevArray":
@@ -799,21 +720,21 @@ def parm_add_qualifiers(stat_list, hasD=True, hasA=False, delWin=2, accWin=2) ->
     cols = n * (1 + int(hasD) + int(hasA))
     dIn = DevArray(stat)
     dOut = DevArray(nbytes=4 * max(stat.shape[0] * cols, 1))
-    check(lib().htkamd_parm_add_qualifiers(dIn.ptr, _p(frameOff), C.c_int(len(stat_list)), C.c_int(n), C.c_int(int(hasD)), C.c_int(int(hasA)),
-                                           C.c_int(delWin), C.c_int(accWin), dOut.ptr, None), "parm_add_qualifiers")
+    check(lib().htkamd_parm_add_qualifiers(dIn.ptr, _p(frameOff), len(stat_list), n, int(hasD), int(hasA),
+                                           delWin, accWin, dOut.ptr, None), "parm_add_qualifiers")
     return dOut, frameOff, cols
 
 
 def compv(dX_ptr, nFrames: int, D: int, minVar: float = 0.0):
     """htkamd_compv: HCompV's global mean and variance of a device table [nFrames x D]."""
     mean = np.zeros(D, np.float32); var = np.zeros(D, np.float32)
-    check(lib().htkamd_compv(dX_ptr, C.c_longlong(nFrames), C.c_int(D), C.c_float(minVar), _p(mean), _p(var), None), "compv")
+    check(lib().htkamd_compv(dX_ptr, nFrames, D, minVar, _p(mean), _p(var), None), "compv")
     return mean, var
 
 
 def write_vfloors(path: str, var: np.ndarray, scale: float):
     var = np.ascontiguousarray(var, np.float32)
-    check(lib().htkamd_mmf_write_vfloors(path.encode(), _p(var), C.c_int(len(var)), C.c_float(scale)), "mmf_write_vfloors")
+    check(lib().htkamd_mmf_write_vfloors(path.encode(), _p(var), len(var), scale), "mmf_write_vfloors")
 
 
 class ParmQuals(C.Structure):
@@ -839,14 +760,14 @@ def parm_qualify(stat_list, quals: ParmQuals):
     cols = lib().htkamd_parm_quals_cols(C.byref(quals))
     dIn = DevArray(stat)
     dOut = DevArray(nbytes=4 * max(stat.shape[0] * cols, 1))
-    check(lib().htkamd_parm_qualify(dIn.ptr, _p(frameOff), C.c_int(len(stat_list)), C.byref(quals), dOut.ptr, None), "parm_qualify")
+    check(lib().htkamd_parm_qualify(dIn.ptr, _p(frameOff), len(stat_list), C.byref(quals), dOut.ptr, None), "parm_qualify")
     return dOut, frameOff, cols
 
 
 def mask_match(mask: str, name: str):
     """htkamd_mask_match (MaskMatch): the characters the mask's % capture from `name`, or None when it does not match."""
     out = C.create_string_buffer(1024)
-    rc = lib().htkamd_mask_match(mask.encode(), name.encode(), out, C.c_int(len(out)))
+    rc = lib().htkamd_mask_match(mask.encode(), name.encode(), out, len(out))
     if rc < 0:
         check(rc, "mask_match")
     return out.value.decode() if rc == 1 else None
@@ -858,7 +779,7 @@ def parm_kind_parse(kind: str) -> int:
 
 def parm_kind_str(kind: int) -> str:
     buf = C.create_string_buffer(64)
-    check(lib().htkamd_parm_kind_str(C.c_int(kind), buf, C.c_int(len(buf))), "parm_kind_str")
+    check(lib().htkamd_parm_kind_str(kind, buf, len(buf)), "parm_kind_str")
     return buf.value.decode()
 
 
@@ -866,7 +787,7 @@ def cepsnorm_read(path: str, max_dim: int = 4096) -> dict:
     """A <CEPSNORM> side file -> {"kind": code, "nFrames": n or None, "mean": float32 [dim] or None, "var": float32 [dim] or None}."""
     kind = C.c_int(); nf = C.c_int(); dm = C.c_int(); dv = C.c_int()
     mean = np.zeros(max_dim, np.float32); var = np.zeros(max_dim, np.float32)
-    check(lib().htkamd_cepsnorm_read(path.encode(), C.byref(kind), C.byref(nf), _p(mean), C.byref(dm), _p(var), C.byref(dv), C.c_int(max_dim)), "cepsnorm_read")
+    check(lib().htkamd_cepsnorm_read(path.encode(), C.byref(kind), C.byref(nf), _p(mean), C.byref(dm), _p(var), C.byref(dv), max_dim), "cepsnorm_read")
     return {"kind": kind.value, "nFrames": nf.value if nf.value >= 0 else None,
             "mean": mean[:dm.value].copy() if dm.value else None, "var": var[:dv.value].copy() if dv.value else None}
 
@@ -876,17 +797,17 @@ def cepsnorm_write(path: str, kind: int, flags: str, nFrames: int = 0, mean=None
     mean = None if mean is None else np.ascontiguousarray(mean, np.float32)
     var = None if var is None else np.ascontiguousarray(var, np.float32)
     dim = len(mean) if mean is not None else (len(var) if var is not None else 0)
-    check(lib().htkamd_cepsnorm_write(path.encode(), C.c_int(kind), flags.encode(), C.c_int(nFrames), _p(mean), _p(var), C.c_int(dim)), "cepsnorm_write")
+    check(lib().htkamd_cepsnorm_write(path.encode(), kind, flags.encode(), nFrames, _p(mean), _p(var), dim), "cepsnorm_write")
 
 
 def varscale_read(path: str, max_dim: int = 4096) -> np.ndarray:
     v = np.zeros(max_dim, np.float32); dim = C.c_int()
-    check(lib().htkamd_varscale_read(path.encode(), _p(v), C.byref(dim), C.c_int(max_dim)), "varscale_read")
+    check(lib().htkamd_varscale_read(path.encode(), _p(v), C.byref(dim), max_dim), "varscale_read")
     return v[:dim.value].copy()
 
 
 def cepsnorm_check_kinds(targetKind: int, meanKind: int = -1, varKind: int = -1):
-    check(lib().htkamd_cepsnorm_check_kinds(C.c_int(targetKind), C.c_int(meanKind), C.c_int(varKind)), "cepsnorm_check_kinds")
+    check(lib().htkamd_cepsnorm_check_kinds(targetKind, meanKind, varKind), "cepsnorm_check_kinds")
 
 
 def cepsnorm_scale(varScale, sideVar, sideNames=None) -> np.ndarray:
@@ -895,7 +816,7 @@ def cepsnorm_scale(varScale, sideVar, sideNames=None) -> np.ndarray:
     sv = np.ascontiguousarray(np.atleast_2d(sideVar), np.float32)
     out = np.zeros(sv.shape, np.float32)
     names = None if sideNames is None else (C.c_char_p * len(sideNames))(*[n.encode() for n in sideNames])
-    check(lib().htkamd_cepsnorm_scale(_p(vs), C.c_int(len(vs)), _p(sv), C.c_int(sv.shape[1]), C.c_int(sv.shape[0]), names, _p(out)), "cepsnorm_scale")
+    check(lib().htkamd_cepsnorm_scale(_p(vs), len(vs), _p(sv), sv.shape[1], sv.shape[0], names, _p(out)), "cepsnorm_scale")
     return out
 
 
@@ -903,7 +824,7 @@ def side_stats(dX_ptr, frameOff, uttSide, nSide: int, nCols: int, D: int, stream
     """htkamd_side_stats: per side the fp64 sums and sums of squares [nSide, D] of the first D columns, and the frame counts [nSide]."""
     frameOff = np.ascontiguousarray(frameOff, np.int32); uttSide = np.ascontiguousarray(uttSide, np.int32)
     s = np.zeros((nSide, D), np.float64); q = np.zeros((nSide, D), np.float64); n = np.zeros(nSide, np.int64)
-    check(lib().htkamd_side_stats(dX_ptr, _p(frameOff), _p(uttSide), C.c_int(len(uttSide)), C.c_int(nSide), C.c_int(nCols), C.c_int(D),
+    check(lib().htkamd_side_stats(dX_ptr, _p(frameOff), _p(uttSide), len(uttSide), nSide, nCols, D,
                                   _p(s), _p(q), _p(n), _stream(stream)), "side_stats")
     return s, q, n
 
@@ -912,7 +833,7 @@ def side_stats_finish(s, q, n):
     """htkamd_side_stats_finish: (mean, var) float32 [nSide, D] from the sums."""
     s = np.ascontiguousarray(s, np.float64); q = np.ascontiguousarray(q, np.float64); n = np.ascontiguousarray(n, np.int64)
     mean = np.zeros(s.shape, np.float32); var = np.zeros(s.shape, np.float32)
-    check(lib().htkamd_side_stats_finish(_p(s), _p(q), _p(n), C.c_int(s.shape[0]), C.c_int(s.shape[1]), _p(mean), _p(var)), "side_stats_finish")
+    check(lib().htkamd_side_stats_finish(_p(s), _p(q), _p(n), s.shape[0], s.shape[1], _p(mean), _p(var)), "side_stats_finish")
     return mean, var
 
 
@@ -921,19 +842,20 @@ def parm_normalise(dX_ptr, frameOff, uttSide, nSide: int, nCols: int, mean=None,
     frameOff = np.ascontiguousarray(frameOff, np.int32); uttSide = np.ascontiguousarray(uttSide, np.int32)
     mean = None if mean is None else np.ascontiguousarray(np.atleast_2d(mean), np.float32)
     scale = None if scale is None else np.ascontiguousarray(np.atleast_2d(scale), np.float32)
-    check(lib().htkamd_parm_normalise(dX_ptr, _p(frameOff), _p(uttSide), C.c_int(len(uttSide)), C.c_int(nSide), C.c_int(nCols),
-                                      _p(mean), C.c_int(0 if mean is None else mean.shape[1]), _p(scale), C.c_int(0 if scale is None else scale.shape[1]),
+    check(lib().htkamd_parm_normalise(dX_ptr, _p(frameOff), _p(uttSide), len(uttSide), nSide, nCols,
+                                      _p(mean), 0 if mean is None else mean.shape[1], _p(scale), 0 if scale is None else scale.shape[1],
                                       _stream(stream)), "parm_normalise")
 
 
-class ParmStream:
+class ParmStream(_Handle):
     """htkamd_parm_stream holder: the qualifier step in HParm's buffer mode (rows in pushes, observations out with qwin rows of delay)."""
+    _destroy = "htkamd_parm_stream_close"
 
     def __init__(self, quals: ParmQuals, max_rows: int):
         self.h = C.c_void_p()
         self.q = quals
         self.max_rows = max_rows
-        check(lib().htkamd_parm_stream_open(C.byref(quals), C.c_int(max_rows), C.byref(self.h)), "parm_stream_open")
+        check(lib().htkamd_parm_stream_open(C.byref(quals), max_rows, C.byref(self.h)), "parm_stream_open")
         self.cols = lib().htkamd_parm_quals_cols(C.byref(quals))
         self.lookahead = lib().htkamd_parm_stream_lookahead(self.h)
 
@@ -942,19 +864,8 @@ class ParmStream:
         dIn = DevArray(rows) if rows.shape[0] else None
         dOut = DevArray(nbytes=4 * max((rows.shape[0] + self.lookahead) * self.cols, 1))
         n = C.c_int(0)
-        check(lib().htkamd_parm_stream_push(self.h, dIn.ptr if dIn else None, C.c_int(rows.shape[0]), C.c_int(int(last)), dOut.ptr, C.byref(n), None), "parm_stream_push")
+        check(lib().htkamd_parm_stream_push(self.h, dIn.ptr if dIn else None, rows.shape[0], int(last), dOut.ptr, C.byref(n), None), "parm_stream_push")
         return dOut.to_host(np.float32, (max(rows.shape[0] + self.lookahead, 1), self.cols))[:n.value].copy()
-
-    def close(self):
-        if self.h:
-            lib().htkamd_parm_stream_close(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class InputXForm:
@@ -963,11 +874,6 @@ class InputXForm:
 
     def __init__(self, handle, owned: bool, keep=None):
         L = lib()
-        for f in ("htkamd_inputxform_name", "htkamd_inputxform_mask", "htkamd_inputxform_parm_kind"):
-            getattr(L, f).restype = C.c_char_p
-        L.htkamd_inputxform_matrix.restype = C.POINTER(C.c_float)
-        L.htkamd_inputxform_bias.restype = C.POINTER(C.c_float)
-        L.htkamd_inputxform_logdet.restype = C.c_float
         self.h, self.owned, self._keep = handle, owned, keep
         self.name = L.htkamd_inputxform_name(handle).decode()
         self.mask = L.htkamd_inputxform_mask(handle).decode()
@@ -988,12 +894,12 @@ class InputXForm:
         return cls(h, True)
 
     def write(self, path: str, binary: bool = False):
-        check(lib().htkamd_inputxform_write(self.h, str(path).encode(), C.c_int(int(binary))), "inputxform_write")
+        check(lib().htkamd_inputxform_write(self.h, str(path).encode(), int(binary)), "inputxform_write")
 
     def check_against(self, srcKind: str, targetKind: str, nStat: int, setId: str = "", vecSize: int = 0):
         """htkamd_inputxform_check: the reference's checks of a transform against the data and the set it meets."""
-        check(lib().htkamd_inputxform_check(self.h, C.c_int(parm_kind_parse(srcKind)), C.c_int(parm_kind_parse(targetKind)), C.c_int(nStat),
-                                            setId.encode(), C.c_int(vecSize)), "inputxform_check")
+        check(lib().htkamd_inputxform_check(self.h, parm_kind_parse(srcKind), parm_kind_parse(targetKind), nStat,
+                                            setId.encode(), vecSize), "inputxform_check")
 
     def apply(self, stat_list, quals: ParmQuals):
         """htkamd_inputxform_apply: the qualifier step of a transformed set on the statics of several utterances, in the reference's
@@ -1004,7 +910,7 @@ class InputXForm:
         cols = lib().htkamd_inputxform_apply_cols(self.h, C.byref(quals))
         dIn = DevArray(stat)
         dOut = DevArray(nbytes=4 * max(stat.shape[0] * cols, 1))
-        check(lib().htkamd_inputxform_apply(self.h, dIn.ptr, _p(frameOff), C.c_int(len(stat_list)), C.byref(quals), dOut.ptr, None), "inputxform_apply")
+        check(lib().htkamd_inputxform_apply(self.h, dIn.ptr, _p(frameOff), len(stat_list), C.byref(quals), dOut.ptr, None), "inputxform_apply")
         return dOut, frameOff, cols
 
     def close(self):
@@ -1021,7 +927,7 @@ class InputXForm:
 
 def parm_xform(dIn_ptr, inCols: int, dOut_ptr, outCols: int, nRows: int, dMat_ptr, mrows: int, mcols: int, stream=None):
     """htkamd_parm_xform: out[r][0..mrows) = M . in[r][0..mcols) in the reference's float arithmetic; asynchronous on `stream`."""
-    check(lib().htkamd_parm_xform(dIn_ptr, C.c_int(inCols), dOut_ptr, C.c_int(outCols), C.c_longlong(nRows), dMat_ptr, C.c_int(mrows), C.c_int(mcols),
+    check(lib().htkamd_parm_xform(dIn_ptr, inCols, dOut_ptr, outCols, nRows, dMat_ptr, mrows, mcols,
                                   _stream(stream)), "parm_xform")
 
 
@@ -1069,7 +975,7 @@ def trees_write(path: str, questions, trees):
         lm = (C.c_char_p * max(len(t["leaves"]), 1))(*[str(x).encode() for x in t["leaves"]])
         keep.append((a, lm))
         td[k] = TreeDesc(str(t["name"]).encode(), int(t["state"]), n, a[0], a[1], a[2], lm, len(t["leaves"]))
-    check(lib().htkamd_trees_write(str(path).encode(), qs, C.c_int(len(questions)), td, C.c_int(len(trees))), "trees_write")
+    check(lib().htkamd_trees_write(str(path).encode(), qs, len(questions), td, len(trees)), "trees_write")
 
 
 def name_question_answers(names, questions, stream=None) -> np.ndarray:
@@ -1079,7 +985,7 @@ def name_question_answers(names, questions, stream=None) -> np.ndarray:
     N = len(names)
     na = (C.c_char_p * max(N, 1))(*[str(x).encode() for x in names])
     out = np.zeros((max(len(questions), 1), max(N, 1)), np.uint8)
-    check(lib().htkamd_name_question_answers(na, C.c_int(N), qs, C.c_int(len(questions)), _p(out), _stream(stream)), "name_question_answers")
+    check(lib().htkamd_name_question_answers(na, N, qs, len(questions), _p(out), _stream(stream)), "name_question_answers")
     return out[:len(questions), :N]
 
 
@@ -1098,7 +1004,7 @@ def tree_split_sums(item_stats, node_items, answers, stream=None) -> np.ndarray:
     if an.shape != (nQ, nItems) or Cc % 2 != 1:
         raise HtkAmdError("tree_split_sums: bad shapes %s %s" % (st.shape, an.shape))
     out = np.zeros((nQ, 2, Cc), np.float32)
-    check(lib().htkamd_tree_split_sums(_p(st), C.c_int(nItems), C.c_int((Cc - 1) // 2), _p(it), C.c_int(it.size), _p(an), C.c_int(nQ), _p(out),
+    check(lib().htkamd_tree_split_sums(_p(st), nItems, (Cc - 1) // 2, _p(it), it.size, _p(an), nQ, _p(out),
                                        _stream(stream)), "tree_split_sums")
     return out
 
@@ -1118,7 +1024,7 @@ def cluster_merges(idist, num_req: int = 1, threshold: float = 1.0e15, occ=None,
     if oc is not None and oc.shape != (N,):
         raise HtkAmdError("cluster_merges: %s occupations for %d items" % (oc.shape, N))
     out = np.zeros((max(N, 1), 2), np.int32); n = C.c_int(0)
-    check(lib().htkamd_cluster_merges(_p(d), C.c_int(N), _p(oc) if oc is not None else None, C.c_int(num_req), C.c_float(threshold), C.c_float(outlier),
+    check(lib().htkamd_cluster_merges(_p(d), N, _p(oc) if oc is not None else None, num_req, threshold, outlier,
                                       _p(out), C.byref(n)), "cluster_merges")
     return out[:n.value].copy()
 
@@ -1126,10 +1032,10 @@ def cluster_merges(idist, num_req: int = 1, threshold: float = 1.0e15, occ=None,
 def state_distances(mmf: "Mmf", items: str, stream=None) -> np.ndarray:
     """Test aid (htkamd_state_distances): HHEd's StateDistance between the states of an item list, float32[n, n] in the list's order."""
     n = C.c_int(0)
-    check(lib().htkamd_state_distances(mmf.h, items.encode(), None, C.c_int(0), C.byref(n), _stream(stream)), "state_distances")
+    check(lib().htkamd_state_distances(mmf.h, items.encode(), None, 0, C.byref(n), _stream(stream)), "state_distances")
     out = np.zeros((n.value, n.value), np.float32)
     if n.value:
-        check(lib().htkamd_state_distances(mmf.h, items.encode(), _p(out), C.c_int(out.size), C.byref(n), _stream(stream)), "state_distances")
+        check(lib().htkamd_state_distances(mmf.h, items.encode(), _p(out), out.size, C.byref(n), _stream(stream)), "state_distances")
     return out
 
 
@@ -1159,7 +1065,7 @@ def hinit_check(pk: dict, n_frames: int, tokens, cfg: HInitConfig, models):
     d, keep = _desc_from_packed(pk)
     fr, ln, md = _hinit_tokens(tokens)
     mo = np.ascontiguousarray(models, np.int32)
-    check(lib().htkamd_hinit_check(C.byref(d), C.c_int(int(n_frames)), C.c_int(len(fr)), _p(fr), _p(ln), _p(md), C.byref(cfg), C.c_int(len(mo)), _p(mo)), "hinit_check")
+    check(lib().htkamd_hinit_check(C.byref(d), int(n_frames), len(fr), _p(fr), _p(ln), _p(md), C.byref(cfg), len(mo), _p(mo)), "hinit_check")
 
 
 def hinit(model, dX_ptr, n_frames: int, tokens, models, cfg: HInitConfig = None, stream=None):
@@ -1176,8 +1082,7 @@ def hinit(model, dX_ptr, n_frames: int, tokens, models, cfg: HInitConfig = None,
     n = len(mo)
     status = np.zeros(max(n, 1), np.int32); passes = np.zeros(max(n, 1), np.int32); conv = np.zeros(max(n, 1), np.int32)
     logp = np.zeros((max(n, 1), max(cfg.maxIter, 1)), np.float32)
-    ptr = dX_ptr if isinstance(dX_ptr, C.c_void_p) else C.c_void_p(int(dX_ptr) if dX_ptr else 0)
-    check(lib().htkamd_hinit(model.h, ptr, C.c_int(int(n_frames)), C.c_int(len(fr)), _p(fr), _p(ln), _p(md), C.byref(cfg), C.c_int(n), _p(mo),
+    check(lib().htkamd_hinit(model.h, _stream(dX_ptr), int(n_frames), len(fr), _p(fr), _p(ln), _p(md), C.byref(cfg), n, _p(mo),
                              _p(status), _p(passes), _p(conv), _p(logp), _stream(stream)), "hinit")
     res = [dict(status=int(status[k]), passes=int(passes[k]), converged=bool(conv[k]), logP=[float(x) for x in logp[k, :passes[k]]]) for k in range(n)]
     return model, res
@@ -1187,7 +1092,7 @@ def hinit_uniform_states(n_emit: int, tok_len) -> np.ndarray:
     """UCollectData's rule as the kernels apply it (htkamd_hinit_uniform_states): the 0-based emitting state of every frame of the tokens."""
     ln = np.ascontiguousarray(tok_len, np.int32)
     out = np.zeros(max(int(ln.sum()), 1), np.int32)
-    check(lib().htkamd_hinit_uniform_states(C.c_int(int(n_emit)), C.c_int(len(ln)), _p(ln), _p(out)), "hinit_uniform_states")
+    check(lib().htkamd_hinit_uniform_states(int(n_emit), len(ln), _p(ln), _p(out)), "hinit_uniform_states")
     return out[:int(ln.sum())]
 
 
@@ -1206,8 +1111,7 @@ def flat_cluster(dX_ptr, n_rows: int, D: int, pools, nc, min_var: float = 0.0, s
     tot = max(int(np.clip(ncs, 0, None).sum()), 1)
     size = np.zeros(tot, np.int32); ctr = np.zeros((tot, D), np.float32); var = np.zeros((tot, D), np.float32)
     assign = np.zeros(max(int(off[-1]), 1), np.int32); status = np.zeros(max(len(pools), 1), np.int32)
-    ptr = dX_ptr if isinstance(dX_ptr, C.c_void_p) else C.c_void_p(int(dX_ptr) if dX_ptr else 0)
-    check(lib().htkamd_flat_cluster(ptr, C.c_int(int(n_rows)), C.c_int(int(D)), C.c_int(len(pools)), _p(off), _p(items), _p(ncs), C.c_float(min_var),
+    check(lib().htkamd_flat_cluster(_stream(dX_ptr), int(n_rows), int(D), len(pools), _p(off), _p(items), _p(ncs), min_var,
                                     _p(size), _p(ctr), _p(var), _p(assign), _p(status), _stream(stream)), "flat_cluster")
     out, c0 = [], 0
     for p in range(len(pools)):
@@ -1240,7 +1144,7 @@ def hrest_check(pk: dict, n_frames: int, tokens, cfg: HRestConfig, models):
     d, keep = _desc_from_packed(pk)
     fr, ln, md = _hinit_tokens(tokens)
     mo = np.ascontiguousarray(models, np.int32)
-    check(lib().htkamd_hrest_check(C.byref(d), C.c_int(int(n_frames)), C.c_int(len(fr)), _p(fr), _p(ln), _p(md), C.byref(cfg), C.c_int(len(mo)), _p(mo)), "hrest_check")
+    check(lib().htkamd_hrest_check(C.byref(d), int(n_frames), len(fr), _p(fr), _p(ln), _p(md), C.byref(cfg), len(mo), _p(mo)), "hrest_check")
 
 
 def hrest_token_counts(pk: dict, tokens, cfg: HRestConfig, models):
@@ -1250,7 +1154,7 @@ def hrest_token_counts(pk: dict, tokens, cfg: HRestConfig, models):
     mo = np.ascontiguousarray(models, np.int32)
     off = np.ascontiguousarray(pk["hmmStateOff"], np.int32)
     keep = np.zeros(max(len(ln), 1), np.int32); kept = np.zeros(max(len(mo), 1), np.int32); status = np.zeros(max(len(mo), 1), np.int32)
-    check(lib().htkamd_hrest_token_counts(_p(off), C.c_int(len(off) - 1), C.c_int(len(ln)), _p(ln), _p(md), C.byref(cfg), C.c_int(len(mo)), _p(mo),
+    check(lib().htkamd_hrest_token_counts(_p(off), len(off) - 1, len(ln), _p(ln), _p(md), C.byref(cfg), len(mo), _p(mo),
                                           _p(keep), _p(kept), _p(status)), "hrest_token_counts")
     return keep[:len(ln)].astype(bool), kept[:len(mo)], status[:len(mo)]
 
@@ -1269,23 +1173,19 @@ def hrest(model, dX_ptr, n_frames: int, tokens, models, cfg: HRestConfig = None,
     n = len(mo)
     status = np.zeros(max(n, 1), np.int32); passes = np.zeros(max(n, 1), np.int32); conv = np.zeros(max(n, 1), np.int32)
     logp = np.zeros((max(n, 1), max(cfg.maxIter, 1)), np.float32); used = np.zeros((max(n, 1), max(cfg.maxIter, 1)), np.int32)
-    ptr = dX_ptr if isinstance(dX_ptr, C.c_void_p) else C.c_void_p(int(dX_ptr) if dX_ptr else 0)
-    check(lib().htkamd_hrest(model.h, ptr, C.c_int(int(n_frames)), C.c_int(len(fr)), _p(fr), _p(ln), _p(md), C.byref(cfg), C.c_int(n), _p(mo),
+    check(lib().htkamd_hrest(model.h, _stream(dX_ptr), int(n_frames), len(fr), _p(fr), _p(ln), _p(md), C.byref(cfg), n, _p(mo),
                              _p(status), _p(passes), _p(conv), _p(logp), _p(used), _stream(stream)), "hrest")
     res = [dict(status=int(status[k]), passes=int(passes[k]), converged=bool(conv[k]), logP=[float(x) for x in logp[k, :passes[k]]],
                 used=[int(x) for x in used[k, :passes[k]]]) for k in range(n)]
     return model, res
 
 
-class Mmf:
+class Mmf(_Handle):
     """htkamd_mmf holder: LoadHMMSet / SaveHMMSet for text model definitions (htk_amd/host/mmf.c)."""
+    _destroy = "htkamd_mmf_destroy"
 
     def __init__(self, files=(), hmm_list=None, hmm_dir=None, ext=None):
         L = lib()
-        L.htkamd_mmf_desc.restype = C.POINTER(ModelDesc)
-        for f in ("htkamd_mmf_logical_name", "htkamd_mmf_phys_name", "htkamd_mmf_parm_kind"):
-            getattr(L, f).restype = C.c_char_p
-        L.htkamd_mmf_var_floor.restype = C.POINTER(C.c_float)
         self.h = C.c_void_p()
         check(L.htkamd_mmf_create(C.byref(self.h)), "mmf_create")
         for f in files:
@@ -1296,13 +1196,10 @@ class Mmf:
         self._refresh_names()
         vf = L.htkamd_mmf_var_floor(self.h)
         self.var_floor = np.ctypeslib.as_array(vf, (self.desc.vecSize,)).copy() if vf else None
-        L.htkamd_mmf_inv_cov.restype = C.POINTER(C.c_float)
         ic = L.htkamd_mmf_inv_cov(self.h)
         D = self.desc.vecSize
         self.inv_cov = np.ctypeslib.as_array(ic, (self.desc.numGauss * (D * (D + 1) // 2),)).reshape(self.desc.numGauss, -1).copy() if ic else None
         self.cov_kind = "FULLC" if self.inv_cov is not None else "DIAGC"
-        L.htkamd_mmf_inputxform.restype = C.c_void_p
-        L.htkamd_mmf_set_id.restype = C.c_char_p
         self.set_id = L.htkamd_mmf_set_id(self.h).decode()
         xf = L.htkamd_mmf_inputxform(self.h)
         self.input_xform = InputXForm(C.c_void_p(xf), False, keep=self) if xf else None      # <INPUTXFORM>: owned by the set
@@ -1311,10 +1208,10 @@ class Mmf:
         """The description and the models' names as the holder has them now (at load, and after add_unseen / compact changed the models)."""
         L = lib()
         self.desc = L.htkamd_mmf_desc(self.h).contents
-        self.phys_names = [L.htkamd_mmf_phys_name(self.h, C.c_int(h)).decode() for h in range(self.desc.numPhys)]
+        self.phys_names = [L.htkamd_mmf_phys_name(self.h, h).decode() for h in range(self.desc.numPhys)]
         n = L.htkamd_mmf_num_logical(self.h)
-        self.logical_names = [L.htkamd_mmf_logical_name(self.h, C.c_int(i)).decode() for i in range(n)]
-        self.logical = {self.logical_names[i]: L.htkamd_mmf_logical_phys(self.h, C.c_int(i)) for i in range(n)}
+        self.logical_names = [L.htkamd_mmf_logical_name(self.h, i).decode() for i in range(n)]
+        self.logical = {self.logical_names[i]: L.htkamd_mmf_logical_phys(self.h, i) for i in range(n)}
 
     def refuse_input_xform(self, who: str):
         """For a caller that prepares its observations without looking at the set's transform: a set with <INPUTXFORM> would be trained
@@ -1357,14 +1254,14 @@ class Mmf:
         sel = None
         if states is not None:
             sel = np.zeros(self.desc.numStates, np.uint8); sel[list(states)] = 1
-        check(lib().htkamd_mmf_mixup(self.h, C.c_int(target), _p(sel) if sel is not None else None), "mmf_mixup")
+        check(lib().htkamd_mmf_mixup(self.h, target, _p(sel) if sel is not None else None), "mmf_mixup")
 
     def item_list(self, text: str):
         """An HHEd item list of state items, "{ pat.state[i] }": [(physical model, state number)] in the order of the reference's list."""
         n = C.c_int(0)
-        check(lib().htkamd_mmf_item_list(self.h, text.encode(), None, None, C.c_int(0), C.byref(n)), "mmf_item_list")
+        check(lib().htkamd_mmf_item_list(self.h, text.encode(), None, None, 0, C.byref(n)), "mmf_item_list")
         ph = np.zeros(max(n.value, 1), np.int32); st = np.zeros(max(n.value, 1), np.int32)
-        check(lib().htkamd_mmf_item_list(self.h, text.encode(), _p(ph), _p(st), C.c_int(n.value), C.byref(n)), "mmf_item_list")
+        check(lib().htkamd_mmf_item_list(self.h, text.encode(), _p(ph), _p(st), n.value, C.byref(n)), "mmf_item_list")
         return list(zip(ph[:n.value].tolist(), st[:n.value].tolist()))
 
     def question_answers(self, name: str, patterns) -> np.ndarray:
@@ -1385,7 +1282,7 @@ class Mmf:
         keep = [(str(m).encode(), str(i).encode()) for (_, m, i) in specs]
         ts = (TreeSpec * max(len(specs), 1))(*[TreeSpec(float(specs[k][0]), keep[k][0], keep[k][1]) for k in range(len(specs))])
         flags = (TREE_MERGE if merge else 0) | (TREE_LEAFSTATS if leaf_stats else 0)
-        check(lib().htkamd_mmf_tree_cluster(self.h, _p(occ), C.c_float(outlier), qs, C.c_int(len(questions)), ts, C.c_int(len(specs)), C.c_int(flags),
+        check(lib().htkamd_mmf_tree_cluster(self.h, _p(occ), outlier, qs, len(questions), ts, len(specs), flags,
                                             str(trees_path).encode() if trees_path else None, _stream(stream)), "mmf_tree_cluster")
         msg = lib().htkamd_last_error().decode()
         return msg if "warning" in msg else None
@@ -1417,12 +1314,11 @@ class Mmf:
     def trees(self):
         """The held trees: [dict(name, state, nodes, leaves=[~s macro, ...])] in the order of HHEd's tree list."""
         L = lib()
-        L.htkamd_mmf_tree_info.restype = C.c_char_p; L.htkamd_mmf_tree_leaf.restype = C.c_char_p
         out = []
         for t in range(L.htkamd_mmf_num_trees(self.h)):
             st, nn, nl = C.c_int(0), C.c_int(0), C.c_int(0)
-            name = L.htkamd_mmf_tree_info(self.h, C.c_int(t), C.byref(st), C.byref(nn), C.byref(nl)).decode()
-            out.append(dict(name=name, state=st.value, nodes=nn.value, leaves=[L.htkamd_mmf_tree_leaf(self.h, C.c_int(t), C.c_int(k)).decode() for k in range(nl.value)]))
+            name = L.htkamd_mmf_tree_info(self.h, t, C.byref(st), C.byref(nn), C.byref(nl)).decode()
+            out.append(dict(name=name, state=st.value, nodes=nn.value, leaves=[L.htkamd_mmf_tree_leaf(self.h, t, k).decode() for k in range(nl.value)]))
         return out
 
     def tree_descend(self, names, first_state: int, n_states: int, stream=None):
@@ -1431,14 +1327,12 @@ class Mmf:
         N = len(names)
         na = (C.c_char_p * max(N, 1))(*[str(x).encode() for x in names])
         tree = np.zeros((max(N, 1), n_states), np.int32); leaf = np.zeros((max(N, 1), n_states), np.int32)
-        check(lib().htkamd_tree_descend(self.h, na, C.c_int(N), C.c_int(first_state), C.c_int(n_states), _p(tree), _p(leaf), _stream(stream)), "tree_descend")
+        check(lib().htkamd_tree_descend(self.h, na, N, first_state, n_states, _p(tree), _p(leaf), _stream(stream)), "tree_descend")
         return tree[:N], leaf[:N]
 
     def state_macro(self, state: int):
         """The ~s macro name of state `state` of the description, None for an un-named state."""
-        L = lib()
-        L.htkamd_mmf_state_macro.restype = C.c_char_p
-        r = L.htkamd_mmf_state_macro(self.h, C.c_int(state))
+        r = lib().htkamd_mmf_state_macro(self.h, state)
         return r.decode() if r else None
 
     def data_cluster(self, occ, specs, outlier: float = -1.0, stream=None):
@@ -1455,7 +1349,7 @@ class Mmf:
         keep = [(str(m).encode(), str(i).encode()) for (_, _, m, i) in specs]
         cs = (ClusterSpec * max(len(specs), 1))(*[ClusterSpec(1 if specs[k][0] == "NC" else 0, float(specs[k][1]), keep[k][0], keep[k][1]) for k in range(len(specs))])
         nc = np.zeros(max(len(specs), 1), np.int32)
-        check(lib().htkamd_mmf_data_cluster(self.h, _p(occ) if occ is not None else None, C.c_float(outlier), cs, C.c_int(len(specs)), _p(nc), _stream(stream)),
+        check(lib().htkamd_mmf_data_cluster(self.h, _p(occ) if occ is not None else None, outlier, cs, len(specs), _p(nc), _stream(stream)),
               "mmf_data_cluster")
         msg = lib().htkamd_last_error().decode()
         self.last_warning = msg if "warning" in msg else None
@@ -1475,7 +1369,7 @@ class Mmf:
             check(lib().htkamd_mmf_write_full(self.h, _p(np.ascontiguousarray(params["mean"], np.float32)), _p(np.ascontiguousarray(params["invCov"], np.float32)),
                                               _p(np.ascontiguousarray(g, np.float32)) if g is not None else None,
                                               _p(np.ascontiguousarray(params["compWeight"], np.float32)), _p(np.ascontiguousarray(params["transP"], np.float32)),
-                                              one_file.encode() if one_file else None, out_dir.encode() if out_dir else None, C.c_int(1 if binary else 0)), "mmf_write_full")
+                                              one_file.encode() if one_file else None, out_dir.encode() if out_dir else None, 1 if binary else 0), "mmf_write_full")
             return
         fn = lib().htkamd_mmf_write_binary if binary else lib().htkamd_mmf_write
         check(fn(self.h, _p(np.ascontiguousarray(params["mean"], np.float32)), _p(np.ascontiguousarray(params["var"], np.float32)),
@@ -1493,32 +1387,19 @@ class Mmf:
             check(lib().htkamd_mmf_write_sources_full(self.h, _p(np.ascontiguousarray(params["mean"], np.float32)), _p(np.ascontiguousarray(params["invCov"], np.float32)),
                                                       _p(np.ascontiguousarray(g, np.float32)) if g is not None else None,
                                                       _p(np.ascontiguousarray(params["compWeight"], np.float32)), _p(np.ascontiguousarray(params["transP"], np.float32)),
-                                                      arr, C.c_int(len(master_out)), out_dir.encode() if out_dir else None, C.c_int(1 if binary else 0)), "mmf_write_sources_full")
+                                                      arr, len(master_out), out_dir.encode() if out_dir else None, 1 if binary else 0), "mmf_write_sources_full")
             return
         check(lib().htkamd_mmf_write_sources(self.h, _p(np.ascontiguousarray(params["mean"], np.float32)), _p(np.ascontiguousarray(params["var"], np.float32)),
                                              _p(np.ascontiguousarray(g, np.float32)) if g is not None else None,
                                              _p(np.ascontiguousarray(params["compWeight"], np.float32)), _p(np.ascontiguousarray(params["transP"], np.float32)),
-                                             arr, C.c_int(len(master_out)), out_dir.encode() if out_dir else None, C.c_int(1 if binary else 0)), "mmf_write_sources")
-
-    def close(self):
-        if self.h:
-            lib().htkamd_mmf_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+                                             arr, len(master_out), out_dir.encode() if out_dir else None, 1 if binary else 0), "mmf_write_sources")
 
 
 def _labels_to_list(h):
     L = lib()
-    L.htkamd_labels_name.restype = C.c_char_p
-    L.htkamd_labels_start.restype = C.c_longlong; L.htkamd_labels_end.restype = C.c_longlong; L.htkamd_labels_score.restype = C.c_float
     n = L.htkamd_labels_count(h)
-    return [(L.htkamd_labels_name(h, C.c_int(i)).decode(), L.htkamd_labels_start(h, C.c_int(i)), L.htkamd_labels_end(h, C.c_int(i)),
-             L.htkamd_labels_score(h, C.c_int(i))) for i in range(n)]
+    return [(L.htkamd_labels_name(h, i).decode(), L.htkamd_labels_start(h, i), L.htkamd_labels_end(h, i),
+             L.htkamd_labels_score(h, i)) for i in range(n)]
 
 
 def labels_read(path: str):
@@ -1533,31 +1414,25 @@ def labels_read(path: str):
 OUT_FLAGS = dict(S=1, W=2, T=4, N=8, X=16, C=32, M=64)       # the letters of HVite -o
 
 
-class Trans:
+class Trans(_Handle):
     """htkamd_trans holder: a transcription being written (labels with up to two auxiliary labels), HVite's -o formatting."""
+    _destroy = "htkamd_trans_free"
 
     def __init__(self, max_aux: int = 0):
         self.h = C.c_void_p()
-        check(lib().htkamd_trans_create(C.c_int(max_aux), C.byref(self.h)), "trans_create")
+        check(lib().htkamd_trans_create(max_aux, C.byref(self.h)), "trans_create")
 
     def add(self, start, end, name, score=0.0, aux1=None, aux1_score=0.0, aux2=None, aux2_score=0.0):
-        check(lib().htkamd_trans_add(self.h, C.c_double(start), C.c_double(end), name.encode(), C.c_float(score),
-                                     aux1.encode() if aux1 is not None else None, C.c_float(aux1_score),
-                                     aux2.encode() if aux2 is not None else None, C.c_float(aux2_score)), "trans_add")
+        check(lib().htkamd_trans_add(self.h, start, end, name.encode(), score,
+                                     aux1.encode() if aux1 is not None else None, aux1_score,
+                                     aux2.encode() if aux2 is not None else None, aux2_score), "trans_add")
 
     def format(self, frame_dur=100000.0, states=False, models=False, flags=""):
         bits = sum(OUT_FLAGS[c] for c in flags)
-        check(lib().htkamd_trans_format(self.h, C.c_double(frame_dur), C.c_int(states), C.c_int(models), C.c_int(bits)), "trans_format")
+        check(lib().htkamd_trans_format(self.h, frame_dur, states, models, bits), "trans_format")
 
     def write(self, path: str):
         check(lib().htkamd_trans_write(self.h, path.encode()), "trans_write")
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().htkamd_trans_free(self.h); self.h = C.c_void_p()
-        except Exception:
-            pass
 
 
 class MlfOut:
@@ -1576,9 +1451,6 @@ class MlfOut:
 def scp_read(path: str):
     """Script file -> [(logical, physical, start, end)] (start/end -1 = whole file); extended file names are split."""
     L = lib()
-    for f in ("htkamd_scp_logical", "htkamd_scp_physical"):
-        getattr(L, f).restype = C.c_char_p
-    L.htkamd_scp_start.restype = C.c_long; L.htkamd_scp_end.restype = C.c_long
     h = C.c_void_p()
     check(L.htkamd_scp_read(path.encode(), C.byref(h)), "scp_read")
     out = [(L.htkamd_scp_logical(h, i).decode(), L.htkamd_scp_physical(h, i).decode(), int(L.htkamd_scp_start(h, i)), int(L.htkamd_scp_end(h, i)))
@@ -1587,28 +1459,20 @@ def scp_read(path: str):
     return out
 
 
-class Mlf:
+class Mlf(_Handle):
+    _destroy = "htkamd_mlf_free"
     def __init__(self, path: str):
         self.h = C.c_void_p()
         check(lib().htkamd_mlf_read(path.encode(), C.byref(self.h)), "mlf_read")
-        lib().htkamd_mlf_find.restype = C.c_void_p
 
     def find(self, lab_file: str):
         p = lib().htkamd_mlf_find(self.h, lab_file.encode())
-        return None if not p else _labels_to_list(C.c_void_p(p))
+        return None if not p else _labels_to_list(p)
 
     def entries(self):
         """(pattern, labels handle) of every entry in file order; the handles live as long as this object."""
         L = lib()
-        L.htkamd_mlf_pattern.restype = C.c_char_p; L.htkamd_mlf_entry.restype = C.c_void_p
-        return [(L.htkamd_mlf_pattern(self.h, C.c_int(i)).decode(), C.c_void_p(L.htkamd_mlf_entry(self.h, C.c_int(i)))) for i in range(L.htkamd_mlf_count(self.h))]
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().htkamd_mlf_free(self.h); self.h = C.c_void_p()
-        except Exception:
-            pass
+        return [(L.htkamd_mlf_pattern(self.h, i).decode(), C.c_void_p(L.htkamd_mlf_entry(self.h, i))) for i in range(L.htkamd_mlf_count(self.h))]
 
 
 NET_ALLOWXWRDEXP, NET_FORCECXTEXP, NET_FORCELEFTBI, NET_FORCERIGHTBI = 1, 2, 4, 8
@@ -1620,32 +1484,30 @@ class NetDesc(C.Structure):
                 ("linkOff", C.c_void_p), ("linkDest", C.c_void_p), ("linkLike", C.c_void_p)]
 
 
-class Net:
+class Net(_Handle):
     """htkamd_net holder: SLF word network + dictionary expanded over a model set (htk_amd/host/net.c)."""
+    _destroy = "htkamd_net_destroy"
 
     def __init__(self, slf: str | None, dictionary: str, mmf: "Mmf", words=None, boundary: str | None = None, flags: int = 0):
         """slf: word lattice file; or slf=None and words=[...]: the alignment network of HVite -a for that transcription.
         flags: NET_ALLOWXWRDEXP | NET_FORCECXTEXP | ... (HNet's configuration switches; cross-word context expansion)."""
         L = lib()
         self._mmf = mmf                                    # a cross-word network names models through the set it was built on
-        L.htkamd_net_get.restype = C.POINTER(NetDesc)
-        L.htkamd_net_out_sym.restype = C.c_char_p
         self.h = C.c_void_p()
         if slf is not None:
-            check(L.htkamd_net_build_ex(slf.encode(), dictionary.encode(), mmf.h, C.c_int(flags), C.byref(self.h)), "net_build")
+            check(L.htkamd_net_build_ex(slf.encode(), dictionary.encode(), mmf.h, flags, C.byref(self.h)), "net_build")
         else:
             arr = (C.c_char_p * len(words))(*[w.encode() for w in words])
-            check(L.htkamd_net_build_words(arr, C.c_int(len(words)), boundary.encode() if boundary else None, dictionary.encode(),
+            check(L.htkamd_net_build_words(arr, len(words), boundary.encode() if boundary else None, dictionary.encode(),
                                            mmf.h, C.byref(self.h)), "net_build_words")
         self.desc = L.htkamd_net_get(self.h).contents
-        self.out_syms = [L.htkamd_net_out_sym(self.h, C.c_int(k)).decode() for k in range(self.desc.nProns)]
-        L.htkamd_net_word_name.restype = C.c_char_p
-        self.word_names = [L.htkamd_net_word_name(self.h, C.c_int(k)).decode() for k in range(self.desc.nProns)]
+        self.out_syms = [L.htkamd_net_out_sym(self.h, k).decode() for k in range(self.desc.nProns)]
+        self.word_names = [L.htkamd_net_word_name(self.h, k).decode() for k in range(self.desc.nProns)]
         self.xwrd = bool(L.htkamd_net_is_xwrd(self.h))
         self.pron_models = []
         buf = (C.c_int * 256)()
         for k in range(self.desc.nProns):
-            n = L.htkamd_net_pron_models(self.h, C.c_int(k), buf, C.c_int(256))
+            n = L.htkamd_net_pron_models(self.h, k, buf, 256)
             self.pron_models.append([int(buf[i]) for i in range(min(n, 256))])
 
     def seq_models(self, prons):
@@ -1657,7 +1519,7 @@ class Net:
         for i, k in enumerate(real):
             prev = next((real[j] for j in range(i - 1, -1, -1) if self.pron_models[real[j]]), -1)
             nxt = next((real[j] for j in range(i + 1, len(real)) if self.pron_models[real[j]]), -1)
-            n = L.htkamd_net_seq_models(self.h, C.c_int(k), C.c_int(prev), C.c_int(nxt), buf, C.c_int(256))
+            n = L.htkamd_net_seq_models(self.h, k, prev, nxt, buf, 256)
             if n < 0:
                 raise HtkAmdError("net_seq_models: " + L.htkamd_last_error().decode())
             out.append([int(buf[j]) for j in range(min(n, 256))])
@@ -1670,13 +1532,6 @@ class Net:
         return dict(kind=arr(d.kind, d.nNodes, C.c_int), model=arr(d.model, d.nNodes, C.c_int), pronProb=arr(d.pronProb, d.nNodes, C.c_float),
                     linkOff=arr(d.linkOff, d.nNodes + 1, C.c_int), linkDest=arr(d.linkDest, d.nLinks, C.c_int),
                     linkLike=arr(d.linkLike, d.nLinks, C.c_float), initial=d.initial, final=d.final)
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().htkamd_net_destroy(self.h); self.h = C.c_void_p()
-        except Exception:
-            pass
 
 
 class DecodeConfig(C.Structure):
@@ -1718,24 +1573,24 @@ def lattice_write(lat: dict, net: "Net", path: str, utterance=None, lm_name=None
     if "arcAlignOff" in lat and mmf is not None:
         ka = [np.ascontiguousarray(lat[k], dt) for k, dt in (("arcAlignOff", np.int32), ("alState", np.int32), ("alModel", np.int32), ("alDur", np.int32), ("alLike", np.float32))]
         al = LatticeAlign(*[_p(x) for x in ka], 1 if lat.get("alignModels") else 0)
-        check(lib().htkamd_lattice_write_align(C.byref(st), C.byref(al), mmf.h, net.h, path.encode(), enc(utterance), enc(lm_name), enc(vocab_name), C.c_int(fmt or 0x3f8)), "lattice_write_align")
+        check(lib().htkamd_lattice_write_align(C.byref(st), C.byref(al), mmf.h, net.h, path.encode(), enc(utterance), enc(lm_name), enc(vocab_name), fmt or 0x3f8), "lattice_write_align")
         return
-    check(lib().htkamd_lattice_write(C.byref(st), net.h, path.encode(), enc(utterance), enc(lm_name), enc(vocab_name), C.c_int(fmt or 0x78)), "lattice_write")
+    check(lib().htkamd_lattice_write(C.byref(st), net.h, path.encode(), enc(utterance), enc(lm_name), enc(vocab_name), fmt or 0x78), "lattice_write")
 
 
 def lattice_nbest(lat: dict, net: "Net", N: int, frame_dur=0.01, max_len=4096):
     """htkamd_lattice_nbest: up to N alternatives, each a list of (pron, startFrame, endFrame, score) for its arcs."""
     st, keep = _lattice_struct(lat, frame_dur)
     nAlt = C.c_int(0); altLen = np.zeros(N, np.int32); arcs = np.zeros(N * max_len, np.int32)
-    check(lib().htkamd_lattice_nbest(C.byref(st), net.h, C.c_int(N), C.c_int(max_len), C.byref(nAlt), _p(altLen), _p(arcs)), "lattice_nbest")
-    L = lib(); L.htkamd_lattice_arc_score.restype = C.c_float
+    check(lib().htkamd_lattice_nbest(C.byref(st), net.h, N, max_len, C.byref(nAlt), _p(altLen), _p(arcs)), "lattice_nbest")
+    L = lib()
     out = []
     for i in range(nAlt.value):
         alt = []
         for j in range(int(altLen[i])):
             a_ = int(arcs[i * max_len + j])
             alt.append((int(lat["nodePron"][lat["arcEnd"][a_]]), int(lat["nodeFrame"][lat["arcStart"][a_]]), int(lat["nodeFrame"][lat["arcEnd"][a_]]),
-                        float(L.htkamd_lattice_arc_score(C.byref(st), C.c_int(a_)))))
+                        float(L.htkamd_lattice_arc_score(C.byref(st), a_))))
         out.append(alt)
     return out
 
@@ -1748,16 +1603,16 @@ def lattice_nbest_align(lat: dict, net: "Net", mmf: "Mmf", N: int, states=False,
     ka = [np.ascontiguousarray(lat[k], dt) for k, dt in (("arcAlignOff", np.int32), ("alState", np.int32), ("alModel", np.int32), ("alDur", np.int32), ("alLike", np.float32))]
     al = LatticeAlign(*[_p(x) for x in ka], 1 if lat.get("alignModels") else 0)
     nAlt = C.c_int(0); altLen = np.zeros(N, np.int32); arcs = np.zeros(N * max_len, np.int32)
-    check(lib().htkamd_lattice_nbest(C.byref(st), net.h, C.c_int(N), C.c_int(max_len), C.byref(nAlt), _p(altLen), _p(arcs)), "lattice_nbest")
+    check(lib().htkamd_lattice_nbest(C.byref(st), net.h, N, max_len, C.byref(nAlt), _p(altLen), _p(arcs)), "lattice_nbest")
     out = []
     L = lib()
     for i in range(nAlt.value):
         tr = C.c_void_p()
         a_i = np.ascontiguousarray(arcs[i * max_len:i * max_len + int(altLen[i])], np.int32)
-        check(L.htkamd_lattice_align_trans(C.byref(st), C.byref(al), mmf.h, net.h, _p(a_i), C.c_int(len(a_i)), C.byref(tr)), "lattice_align_trans")
+        check(L.htkamd_lattice_align_trans(C.byref(st), C.byref(al), mmf.h, net.h, _p(a_i), len(a_i), C.byref(tr)), "lattice_align_trans")
         if not tr.value:
             out.append(None); continue
-        check(L.htkamd_trans_format(tr, C.c_double(frame_dur * 1.0e7), C.c_int(int(states)), C.c_int(int(models)), C.c_int(sum(OUT_FLAGS[c] for c in flags))), "trans_format")
+        check(L.htkamd_trans_format(tr, frame_dur * 1.0e7, int(states), int(models), sum(OUT_FLAGS[c] for c in flags)), "trans_format")
         with tempfile.NamedTemporaryFile("r", suffix=".rec") as f:
             check(L.htkamd_trans_write(tr, f.name.encode()), "trans_write")
             out.append(open(f.name).read().splitlines())
@@ -1807,17 +1662,18 @@ class _LatticeRun:
         return res
 
 
-class Decoder:
+class Decoder(_Handle):
     """htkamd_decoder holder: HVite -w (1-best word labels) for a batch of utterances on the device."""
+    _destroy = "htkamd_decoder_destroy"
 
     def __init__(self, model: "Model", net: "Net", lmScale: float = 1.0):
         self.h = C.c_void_p()
         self.model, self.net, self.lmScale = model, net, float(lmScale)
-        check(lib().htkamd_decoder_create(model.h, C.byref(net.desc), C.c_float(lmScale), C.byref(self.h)), "decoder_create")
+        check(lib().htkamd_decoder_create(model.h, C.byref(net.desc), lmScale, C.byref(self.h)), "decoder_create")
 
     def set_order(self, mode: int):
         """htkamd_decoder_set_order: ORDER_AUTO (exact-tie utterances again in HRec's instance order), ORDER_FAST, ORDER_EXACT."""
-        check(lib().htkamd_decoder_set_order(self.h, C.c_int(mode)), "decoder_set_order")
+        check(lib().htkamd_decoder_set_order(self.h, mode), "decoder_set_order")
 
     def last_tied(self) -> int:
         return int(lib().htkamd_decoder_last_tied(self.h))
@@ -1847,7 +1703,7 @@ class Decoder:
         wp = np.zeros(max(nU, 1) * maxWords, np.int32); ws = np.zeros_like(wp); we = np.zeros_like(wp); sc = np.zeros(max(nU, 1) * maxWords, np.float32)
         lm = np.zeros_like(sc)
         cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
-        check(lib().htkamd_decoder_run(self.h, C.byref(cfg), dX.ptr, _p(frameOff), C.c_int(nU), C.c_int(maxWords), _p(nW), _p(wp), _p(ws), _p(we),
+        check(lib().htkamd_decoder_run(self.h, C.byref(cfg), dX.ptr, _p(frameOff), nU, maxWords, _p(nW), _p(wp), _p(ws), _p(we),
                                        _p(sc), _p(lm), _p(tot), None), "decoder_run")
         self.last_lm = [[float(lm[u * maxWords + i]) for i in range(max(int(nW[u]), 0))] for u in range(nU)]
         out = []
@@ -1868,38 +1724,32 @@ class Decoder:
         b = _LatticeRun(feats, self.model.D, maxNodes, maxArcs, align, maxAlign)
         cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
         if align:                                            # HVite -n with -m (1) / -f (2): lAlign of every arc
-            check(lib().htkamd_decoder_run_lattice_align(self.h, C.byref(cfg), C.c_int(nToks), C.c_float(genBeam if nBeam is None else nBeam), C.c_int(int(align)), b.dX.ptr,
-                                                         _p(b.frameOff), C.c_int(b.nU), C.c_int(maxNodes), C.c_int(maxArcs), C.c_int(maxAlign), C.byref(b.out), C.byref(b.alo), None),
+            check(lib().htkamd_decoder_run_lattice_align(self.h, C.byref(cfg), nToks, genBeam if nBeam is None else nBeam, int(align), b.dX.ptr,
+                                                         _p(b.frameOff), b.nU, maxNodes, maxArcs, maxAlign, C.byref(b.out), C.byref(b.alo), None),
                   "decoder_run_lattice_align")
         else:
-            check(lib().htkamd_decoder_run_lattice(self.h, C.byref(cfg), C.c_int(nToks), C.c_float(genBeam if nBeam is None else nBeam), b.dX.ptr, _p(b.frameOff), C.c_int(b.nU),
-                                                   C.c_int(maxNodes), C.c_int(maxArcs), C.byref(b.out), None), "decoder_run_lattice")
+            check(lib().htkamd_decoder_run_lattice(self.h, C.byref(cfg), nToks, genBeam if nBeam is None else nBeam, b.dX.ptr, _p(b.frameOff), b.nU,
+                                                   maxNodes, maxArcs, C.byref(b.out), None), "decoder_run_lattice")
         return b.unpack("decoder_run_lattice", lmScale, wordPen, prScale)
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().htkamd_decoder_destroy(self.h); self.h = C.c_void_p()
-        except Exception:
-            pass
 
 
 class DecodeOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("nWords", "wordPron", "wordStart", "wordEnd", "wordScore", "wordLm", "wordAc", "wordLike", "total", "finalLm")]
 
 
-class DecoderSet:
+class DecoderSet(_Handle):
     """htkamd_decoder_set holder: a batch in which utterance u is decoded against nets[net_of[u]] -- HVite -a from word-level
     transcriptions, HVite -w with a lattice per file (DoAlignment, HVite.c:830) -- in one launch."""
+    _destroy = "htkamd_decoder_set_destroy"
 
     def __init__(self, model: "Model", nets, lmScale: float = 1.0):
         self.h = C.c_void_p()
         self.model, self.nets, self.lmScale = model, list(nets), float(lmScale)
         arr = (C.POINTER(NetDesc) * max(len(self.nets), 1))(*[C.pointer(n.desc) for n in self.nets])
-        check(lib().htkamd_decoder_set_create(model.h, arr, C.c_int(len(self.nets)), C.c_float(lmScale), C.byref(self.h)), "decoder_set_create")
+        check(lib().htkamd_decoder_set_create(model.h, arr, len(self.nets), lmScale, C.byref(self.h)), "decoder_set_create")
 
     def set_order(self, mode: int):
-        check(lib().htkamd_decoder_set_set_order(self.h, C.c_int(mode)), "decoder_set_set_order")
+        check(lib().htkamd_decoder_set_set_order(self.h, mode), "decoder_set_set_order")
 
     def last_tied(self) -> int:
         return int(lib().htkamd_decoder_set_last_tied(self.h))
@@ -1923,7 +1773,7 @@ class DecoderSet:
                  finalLm=np.zeros(n1, np.float32))
         out = DecodeOut(*[_p(o[n]) for n, _ in DecodeOut._fields_])
         cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
-        check(lib().htkamd_decoder_set_run(self.h, C.byref(cfg), dX.ptr, _p(frameOff), _p(netOf), C.c_int(nU), C.c_int(maxWords), C.byref(out), None), "decoder_set_run")
+        check(lib().htkamd_decoder_set_run(self.h, C.byref(cfg), dX.ptr, _p(frameOff), _p(netOf), nU, maxWords, C.byref(out), None), "decoder_set_run")
         return dict((k, v[:nU]) for k, v in o.items())
 
     def run(self, feats, net_of, **p):
@@ -1948,22 +1798,15 @@ class DecoderSet:
         b = _LatticeRun(feats, self.model.D, maxNodes, maxArcs, align, maxAlign)
         netOf = np.ascontiguousarray(np.asarray(net_of, np.int64).astype(np.int32) if b.nU else np.zeros(1, np.int32))
         cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
-        nB = C.c_float(genBeam if nBeam is None else nBeam)
+        nB = genBeam if nBeam is None else nBeam
         if align:
-            check(lib().htkamd_decoder_set_run_lattice_align(self.h, C.byref(cfg), C.c_int(nToks), nB, C.c_int(int(align)), b.dX.ptr, _p(b.frameOff), _p(netOf), C.c_int(b.nU),
-                                                             C.c_int(maxNodes), C.c_int(maxArcs), C.c_int(maxAlign), C.byref(b.out), C.byref(b.alo), None),
+            check(lib().htkamd_decoder_set_run_lattice_align(self.h, C.byref(cfg), nToks, nB, int(align), b.dX.ptr, _p(b.frameOff), _p(netOf), b.nU,
+                                                             maxNodes, maxArcs, maxAlign, C.byref(b.out), C.byref(b.alo), None),
                   "decoder_set_run_lattice_align")
         else:
-            check(lib().htkamd_decoder_set_run_lattice(self.h, C.byref(cfg), C.c_int(nToks), nB, b.dX.ptr, _p(b.frameOff), _p(netOf), C.c_int(b.nU), C.c_int(maxNodes),
-                                                       C.c_int(maxArcs), C.byref(b.out), None), "decoder_set_run_lattice")
+            check(lib().htkamd_decoder_set_run_lattice(self.h, C.byref(cfg), nToks, nB, b.dX.ptr, _p(b.frameOff), _p(netOf), b.nU, maxNodes,
+                                                       maxArcs, C.byref(b.out), None), "decoder_set_run_lattice")
         return b.unpack("decoder_set_run_lattice", lmScale, wordPen, prScale)
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().htkamd_decoder_set_destroy(self.h); self.h = C.c_void_p()
-        except Exception:
-            pass
 
 
 # ---- scoring recognition output (HResults): htkamd_results_* ----------------------------------------------------------------------
@@ -1993,15 +1836,14 @@ def results_check_switch(sw: str):
     check(lib().htkamd_results_check_switch(sw.encode()), "results_check_switch")
 
 
-class Results:
+class Results(_Handle):
     """htkamd_results holder: HResults for K hypothesis sets x U utterances in one call.  equiv: (class, label) pairs in -e order."""
+    _destroy = "htkamd_results_destroy"
 
     def __init__(self, null_name=None, equiv=(), ignore_case=False, strip=False, nist=False, label_list=(), ref_level=0, test_level=0):
         self.h = C.c_void_p()
         self.label_list = list(label_list)
         L = lib()
-        L.htkamd_results_label_name.restype = C.c_char_p
-        L.htkamd_results_last_kernel_ms.restype = C.c_double
         cfg = ResultsConfig(None if null_name is None else null_name.encode(), int(ignore_case), int(strip), int(nist), len(equiv), _strs([e[0] for e in equiv]),
                             _strs([e[1] for e in equiv]), len(self.label_list), _strs(self.label_list), int(ref_level), int(test_level))
         check(L.htkamd_results_create(C.byref(cfg), C.byref(self.h)), "results_create")
@@ -2013,14 +1855,14 @@ class Results:
         return i
 
     def label_name(self, i: int):
-        s = lib().htkamd_results_label_name(self.h, C.c_int(i))
+        s = lib().htkamd_results_label_name(self.h, i)
         return None if s is None else s.decode()
 
     def num_labels(self) -> int:
         return int(lib().htkamd_results_num_labels(self.h))
 
     def add_ref(self, utt: str, names) -> int:
-        i = lib().htkamd_results_add_ref(self.h, utt.encode(), C.c_int(len(names)), _strs(names))
+        i = lib().htkamd_results_add_ref(self.h, utt.encode(), len(names), _strs(names))
         if i < 0:
             check(i, "results_add_ref")
         return i
@@ -2029,8 +1871,8 @@ class Results:
         """(reference index, its file name as HResults forms it)."""
         buf = C.create_string_buffer(1024)
         arr = (C.c_void_p * max(len(mlfs), 1))(*[m.h for m in mlfs])
-        i = lib().htkamd_results_ref_for(self.h, rec_file.encode(), arr, C.c_int(len(mlfs)), None if lab_dir is None else lab_dir.encode(),
-                                         None if lab_ext is None else lab_ext.encode(), buf, C.c_size_t(1024))
+        i = lib().htkamd_results_ref_for(self.h, rec_file.encode(), arr, len(mlfs), None if lab_dir is None else lab_dir.encode(),
+                                         None if lab_ext is None else lab_ext.encode(), buf, 1024)
         if i < 0:
             check(i, "results_ref_for")
         return i, buf.value.decode()
@@ -2055,7 +1897,7 @@ class Results:
         hypOff = np.concatenate([[0], np.cumsum([len(h) for h in flat])]).astype(np.int32)
         hypIds = np.ascontiguousarray(np.concatenate(flat + [np.zeros(1, np.int32)]), np.int32)
         uttRef = np.ascontiguousarray(np.asarray(list(utt_ref) + [0], np.int64).astype(np.int32))
-        refLen = [int(lib().htkamd_results_ref_len(self.h, C.c_int(int(u)))) for u in utt_ref]
+        refLen = [int(lib().htkamd_results_ref_len(self.h, int(u))) for u in utt_ref]
         V = len(self.label_list)
         counts = np.zeros((max(K * U, 1), 6), np.int32)
         totals = np.zeros((max(K, 1), 7), np.int64)
@@ -2064,8 +1906,8 @@ class Results:
         aln = np.zeros((max(cap, 1), 3), np.int32)
         cm = np.zeros((max(K, 1), V + 1, V + 1), np.int32)
         flags = (RES_ALIGN if align else 0) | (RES_CONF if conf else 0)
-        check(lib().htkamd_results_score(self.h, C.c_int(K), C.c_int(U), _p(uttRef), _p(hypOff), _p(hypIds), C.c_int(flags), _p(counts),
-                                         _p(alnOff) if align else None, _p(aln) if align else None, C.c_longlong(cap), _p(totals), _p(cm) if conf else None, None),
+        check(lib().htkamd_results_score(self.h, K, U, _p(uttRef), _p(hypOff), _p(hypIds), flags, _p(counts),
+                                         _p(alnOff) if align else None, _p(aln) if align else None, cap, _p(totals), _p(cm) if conf else None, None),
               "results_score")
         out = dict(counts=counts[:K * U].reshape(K, U, 6), totals=totals[:K], kernel_ms=float(lib().htkamd_results_last_kernel_ms(self.h)),
                    alnOff=alnOff, alnFlat=aln)
@@ -2085,14 +1927,7 @@ class Results:
         conf = None if conf is None else np.ascontiguousarray(conf, np.int32)
         rep = ResultsReport(int(flags), None if ref_id is None else ref_id.encode(), len(rec_ids), _strs(rec_ids), n, _strs(rec_files), _strs(lab_files),
                             _p(counts), _p(aln_off), _p(aln), _p(totals), _p(conf))
-        check(lib().htkamd_results_write(self.h, C.byref(rep), None if path is None else path.encode(), C.c_int(int(append))), "results_write")
-
-    def __del__(self):
-        try:
-            if self.h:
-                lib().htkamd_results_destroy(self.h); self.h = C.c_void_p()
-        except Exception:
-            pass
+        check(lib().htkamd_results_write(self.h, C.byref(rep), None if path is None else path.encode(), int(append)), "results_write")
 
 
 class LatScales(C.Structure):
@@ -2131,15 +1966,14 @@ def lat_scales(settings):
     return (LatScales * len(rows))(*[LatScales(*[float(np.float32(x)) for x in r]) for r in rows])
 
 
-class LatSet:
+class LatSet(_Handle):
     """htkamd_latset holder: HLRescore for U lattices under K settings in one call.  Per-node results of K settings come back per lattice
     as [nNodes, K] arrays (the library's interleaved layout)."""
+    _destroy = "htkamd_latset_destroy"
 
     def __init__(self, dictionary: str = None, start_word=None, end_word=None, like: "LatSet" = None):
         self.h = C.c_void_p()
         L = lib()
-        L.htkamd_latset_word_name.restype = C.c_char_p
-        L.htkamd_latset_last_kernel_ms.restype = C.c_double
         if like is not None:
             check(L.htkamd_latset_create_like(like.h, C.byref(self.h)), "latset_create_like")
         else:
@@ -2168,14 +2002,14 @@ class LatSet:
         v = src.view(u)
         if len(kn) != v["nNodes"] or len(ka) != v["nArcs"]:
             raise HtkAmdError("LatSet.add_pruned: the flags do not fit lattice %d" % u)
-        i = lib().htkamd_latset_add_pruned(self.h, src.h, C.c_int(u), _p(kn), _p(ka))
+        i = lib().htkamd_latset_add_pruned(self.h, src.h, u, _p(kn), _p(ka))
         if i < 0:
             check(i, "latset_add_pruned")
         return i
 
     def view(self, u: int) -> dict:
         v = LatSetView()
-        check(lib().htkamd_latset_get(self.h, C.c_int(u), C.byref(v)), "latset_get")
+        check(lib().htkamd_latset_get(self.h, u, C.byref(v)), "latset_get")
         nn, na = v.nNodes, v.nArcs
         out = dict(nNodes=nn, nArcs=na, start=v.start, end=v.end)
         for f, n in (("nodeTime", nn), ("nodeWord", nn), ("nodeVar", nn), ("topOrder", nn), ("arcStart", na), ("arcEnd", na), ("arcAc", na), ("arcLm", na), ("arcPr", na),
@@ -2185,7 +2019,7 @@ class LatSet:
         return out
 
     def word_name(self, w: int):
-        s = lib().htkamd_latset_word_name(self.h, C.c_int(int(w)))
+        s = lib().htkamd_latset_word_name(self.h, int(w))
         return None if s is None else s.decode()
 
     def sizes(self):
@@ -2193,7 +2027,7 @@ class LatSet:
         v = LatSetView()
         nn, na = [], []
         for u in range(len(self)):
-            check(lib().htkamd_latset_get(self.h, C.c_int(u), C.byref(v)), "latset_get")
+            check(lib().htkamd_latset_get(self.h, u, C.byref(v)), "latset_get")
             nn.append(v.nNodes); na.append(v.nArcs)
         return np.array(nn, np.int64), np.array(na, np.int64)
 
@@ -2212,7 +2046,7 @@ class LatSet:
         nPath, status = np.zeros(max(K * U, 1), np.int32), np.zeros(max(K * U, 1), np.int32)
         arcs, totals = np.zeros(max(K * TN, 1), np.int32), np.zeros((max(K * U, 1), 4), np.float64)
         out = LatBestOut(_p(nPath), _p(status), _p(arcs), _p(totals))
-        check(lib().htkamd_latset_best(self.h, C.c_int(K), sc, C.byref(out), _stream(stream)), "latset_best")
+        check(lib().htkamd_latset_best(self.h, K, sc, C.byref(out), _stream(stream)), "latset_best")
         paths = [[arcs[k * TN + noff[u]:k * TN + noff[u] + nPath[k * U + u]].copy() for u in range(U)] for k in range(K)]
         return dict(paths=paths, totals=totals[:K * U].reshape(K, U, 4), status=status[:K * U].reshape(K, U), nPath=nPath, pathArcs=arcs, kernel_ms=self.kernel_ms())
 
@@ -2223,7 +2057,7 @@ class LatSet:
         TN = int(noff[-1])
         fw, bw, best = np.zeros(max(K * TN, 1)), np.zeros(max(K * TN, 1)), np.zeros(max(K * U, 1))
         out = LatFbOut(_p(fw), _p(bw), _p(best))
-        check(lib().htkamd_latset_fb_max(self.h, C.c_int(K), sc, C.byref(out), _stream(stream)), "latset_fb_max")
+        check(lib().htkamd_latset_fb_max(self.h, K, sc, C.byref(out), _stream(stream)), "latset_fb_max")
         cut = lambda a: [a[K * noff[u]:K * noff[u + 1]].reshape(int(nn[u]), K) for u in range(U)]
         return dict(fw=cut(fw), bw=cut(bw), best=best[:K * U].reshape(K, U), kernel_ms=self.kernel_ms())
 
@@ -2235,7 +2069,7 @@ class LatSet:
         th = np.ascontiguousarray(np.broadcast_to(np.asarray(thresh, np.float64), (K,)))
         aps = np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if arcs_per_sec is None else arcs_per_sec, np.float32), (K,)))
         kn, ka = np.zeros(max(K * TN, 1), np.uint8), np.zeros(max(K * TA, 1), np.uint8)
-        check(lib().htkamd_latset_prune(self.h, C.c_int(K), sc, _p(th), _p(aps), _p(kn), _p(ka), _stream(stream)), "latset_prune")
+        check(lib().htkamd_latset_prune(self.h, K, sc, _p(th), _p(aps), _p(kn), _p(ka), _stream(stream)), "latset_prune")
         return dict(keep_node=[[kn[k * TN + noff[u]:k * TN + noff[u + 1]].astype(bool) for u in range(U)] for k in range(K)],
                     keep_arc=[[ka[k * TA + aoff[u]:k * TA + aoff[u + 1]].astype(bool) for u in range(U)] for k in range(K)], kernel_ms=self.kernel_ms())
 
@@ -2244,7 +2078,7 @@ class LatSet:
         a = np.ascontiguousarray(arcs, np.int32)
         t = Trans.__new__(Trans)
         t.h = C.c_void_p()
-        check(lib().htkamd_latset_trans(self.h, C.c_int(u), lat_scales([setting]), _p(a), C.c_int(len(a)), C.byref(t.h)), "latset_trans")
+        check(lib().htkamd_latset_trans(self.h, u, lat_scales([setting]), _p(a), len(a), C.byref(t.h)), "latset_trans")
         return t
 
     def best_ids(self, results: "Results", best: dict):
@@ -2252,7 +2086,7 @@ class LatSet:
         U = len(self); K = len(best["paths"])
         cap = int(best["nPath"].sum()) + 1
         off, ids = np.zeros(K * U + 1, np.int32), np.zeros(cap, np.int32)
-        n = lib().htkamd_latset_best_ids(self.h, results.h, C.c_int(K), _p(best["nPath"]), _p(best["pathArcs"]), _p(off), _p(ids), C.c_int(cap))
+        n = lib().htkamd_latset_best_ids(self.h, results.h, K, _p(best["nPath"]), _p(best["pathArcs"]), _p(off), _p(ids), cap)
         if n < 0:
             check(n, "latset_best_ids")
         return [[ids[off[k * U + u]:off[k * U + u + 1]].copy() for u in range(U)] for k in range(K)]
@@ -2260,11 +2094,15 @@ class LatSet:
     def write(self, u: int, setting, path: str, node_score=None, fmt: str = None):
         ns = None if node_score is None else np.ascontiguousarray(node_score, np.float64)
         bits = 0 if fmt is None else sum(LAT_FORMAT.get(c, 0) for c in fmt)
-        check(lib().htkamd_latset_write(self.h, C.c_int(u), lat_scales([setting]), _p(ns), path.encode(), C.c_int(bits)), "latset_write")
+        check(lib().htkamd_latset_write(self.h, u, lat_scales([setting]), _p(ns), path.encode(), bits), "latset_write")
 
-    def __del__(self):
-        try:
-            if self.h:
-                lib().htkamd_latset_destroy(self.h); self.h = C.c_void_p()
-        except Exception:
-            pass
+
+# Every struct of include/htk_amd.h and its mirror above: abi.declare reads the pointer returns from it, tests/test_capi_abi.py the layouts.
+STRUCTS = {"htkamd_model_desc": ModelDesc, "htkamd_accs_layout": AccsLayout, "htkamd_fb_config": FbConfig, "htkamd_update_config": UpdateConfig,
+           "htkamd_update_stats": UpdateStats, "htkamd_batch_desc": BatchDesc, "htkamd_mfcc_config": MfccConfig, "htkamd_frontend_config": FrontEndConfig,
+           "htkamd_warp": Warp, "htkamd_parm_quals": ParmQuals, "htkamd_tree_question": TreeQuestion, "htkamd_tree_spec": TreeSpec,
+           "htkamd_tree_desc": TreeDesc, "htkamd_cluster_spec": ClusterSpec, "htkamd_hinit_config": HInitConfig, "htkamd_hrest_config": HRestConfig,
+           "htkamd_net_desc": NetDesc, "htkamd_decode_config": DecodeConfig, "htkamd_lattice_out": LatticeOut, "htkamd_lattice_align_out": LatticeAlignOut,
+           "htkamd_lattice_align": LatticeAlign, "htkamd_lattice": Lattice, "htkamd_decode_out": DecodeOut, "htkamd_results_config": ResultsConfig,
+           "htkamd_results_report": ResultsReport, "htkamd_lat_scales": LatScales, "htkamd_latset_view": LatSetView, "htkamd_latset_best_out": LatBestOut,
+           "htkamd_latset_fb_out": LatFbOut}

@@ -19,7 +19,7 @@ def test_prep_functions_bit_equal(native, oracle):
         L.htkamd_host_fix_diag_gconst(C.c_int(39), var[g].ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p))
         O.orc_fix_diag_gconst(C.c_int(39), var[g].ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p))
         assert x[0] == y[0]
-    L.htkamd_host_mix_log_weight.restype = C.c_float
+    L.htkamd_host_mix_log_weight.restype = C.c_float         # (not of the C ABI: csrc/internal.h declares it, so no prototype comes from the header)
     L.htkamd_host_mix_log_weight.argtypes = [C.c_float]
     for w in (0.0, 1e-6, 0.99e-5, 1e-5, 0.3, 1.0):
         assert L.htkamd_host_mix_log_weight(w) == O.orc_mix_log_weight(w)

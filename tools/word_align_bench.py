@@ -57,7 +57,6 @@ def main():
     D = X.shape[1]
     dictp = os.path.join(SRC, "dict").encode()
     cfg = capi.DecodeConfig(a.beam, 1.0e10, 1.0, 0.0, 1.0, 0, 0)
-    L.htkamd_net_get.restype = C.POINTER(capi.NetDesc)
     p = lambda x: x.ctypes.data_as(C.c_void_p)
 
     def build_net(words):
