@@ -146,6 +146,7 @@ __device__ __forceinline__ void hmm_step1(const DecArgs &a, const DecUtt &ud, co
       nw[j] = dec_null();
       if (j < NS) {
          // CreateSEIndex (HRec.c:1403): predecessor range with a transition, first maximum wins
+         // (this kernel's own copy of dec_se_range, decode_dev.h: with the helper every instantiation of k_decode changed its scratch size)
          int lo = 1, hi = NS - 1;
          if constexpr (SLOTS) { lo = (se >> (6 * (j - 2))) & 7; hi = (se >> (6 * (j - 2) + 3)) & 7; }      // (the ranges of the register-resident models come with their records)
          else {
@@ -399,11 +400,7 @@ __global__ __launch_bounds__(NTHR) void k_decode(DecArgs a)
          }
          double genMax = myGen, wordMax = myWord;
          block_max2<NTHR>(genMax, wordMax, red, red2);
-         if (tid == 0) {
-            float w = (float)(wordMax - a.wordBeam); if (w < (float)LSMALL) w = (float)LSMALL;
-            float g = (float)(genMax - a.genBeam); if (g < (float)LSMALL) g = (float)LSMALL;
-            thr[0] = g; thr[1] = w;
-         }
+         if (tid == 0) dec_beam_thresholds(thr, genMax, wordMax, a.genBeam, a.wordBeam);
          __syncthreads();
       }
       // ---- zero-time nodes, level by level (at t = 0: StartRecognition's propagation of the initial token)
@@ -931,17 +928,11 @@ int htkamd_decoder_pack(htkamd_model *m, const htkamd_net_desc *nd, float lmScal
          const float *tp = m->h_transP + nodeTp[n];
          for (int j = 2; j <= 4; j++) {
             int lo = 1, hi = NS - 1;
-            if (j < NS) {
-               while (lo < NS && !(tp[(lo - 1) * NS + (j - 1)] > LSMALL)) lo++;
-               while (hi > 1 && !(tp[(hi - 1) * NS + (j - 1)] > LSMALL)) hi--;
-               if (lo > hi) { lo = 1; hi = NS - 1; }
-            }
+            if (j < NS) dec_se_range(tp, NS, j, 1, lo, hi);
             se |= (lo & 7) << (6 * (j - 2)) | (hi & 7) << (6 * (j - 2) + 3);
          }
-         int lo = 2, hi = NS - 1;
-         while (lo < NS && !(tp[(lo - 1) * NS + (NS - 1)] > LSMALL)) lo++;
-         while (hi > 1 && !(tp[(hi - 1) * NS + (NS - 1)] > LSMALL)) hi--;
-         if (lo > hi) { lo = 2; hi = NS - 1; }
+         int lo, hi;
+         dec_se_range(tp, NS, NS, 2, lo, hi);
          se |= (lo & 7) << 18 | (hi & 7) << 21;
       }
       regRecB[k] = make_int4(sl[0], sl[1], sl[2], (int)regNoEx[k] | (se << 1));

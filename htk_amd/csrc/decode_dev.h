@@ -1,6 +1,7 @@
 // decode_dev.h -- device code the four token-passing kernels share (k_decode: decode.hip; k_decode_ord: decode_ord.hip; k_decode_n and
-// k_decode_ord_n: decode_n.hip): the null token, the workgroup maximum, the threshold of HVite -u's maximum-model pruning and the
-// 1-best traceback.  Each is HRec.c's semantics stated ONCE; decode_ord.h adds the instance list and its walk.
+// k_decode_ord_n: decode_n.hip): the null token, the workgroup maximum, the CreateSEIndex range, the beam thresholds, the threshold of
+// HVite -u's maximum-model pruning and the 1-best traceback.  Each is HRec.c's semantics stated ONCE; decode_ord.h adds the instance list
+// and its walk: the frame loop of the two list kernels, a template over their token form.
 // Everything here is inlined into its caller: k_decode<NPT > 0> keeps its tokens in registers and spills when pushed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +22,34 @@ __device__ __forceinline__ double dec_block_max(double v, double *red)
    double r = red[0];
    for (int i = 1; i < NTHR / 64; i++) r = (red[i] > r) ? red[i] : r;
    return r;
+}
+
+// CreateSEIndex (HRec.c:1403): the range (lo, hi) of states with a transition into state j (1-based) of the NS x NS log transition matrix
+// tp -- what StepHMM1 takes its maximum over.  lo0: where the range may start, 1 for an emitting state, 2 for the exit state (j = NS), which
+// does not take from the entry state.  A column without a transition gets the whole range (lo0, NS - 1).  (Also the host's: the ranges
+// packed into the register-resident models' records, decode.hip.)
+__host__ __device__ __forceinline__ void dec_se_range(const float *tp, const int NS, const int j, const int lo0, int &lo, int &hi)
+{
+   lo = lo0; hi = NS - 1;
+   while (lo < NS && !(tp[(lo - 1) * NS + (j - 1)] > LSMALL)) lo++;
+   while (hi > 1 && !(tp[(hi - 1) * NS + (j - 1)] > LSMALL)) hi--;
+   if (lo > hi) { lo = lo0; hi = NS - 1; }
+}
+
+// The beam thresholds of the next pass from this frame's tops (ProcessObservation HRec.c:1996-2005), floats floored at LSMALL:
+// thr[0] = genMax - genBeam, thr[1] = wordMax - wordBeam.  By ONE thread.
+__device__ __forceinline__ void dec_beam_thresholds(float *thr, const double genMax, const double wordMax, const float genBeam, const float wordBeam)
+{
+   float w = (float)(wordMax - wordBeam); if (w < (float)LSMALL) w = (float)LSMALL;
+   float g = (float)(genMax - genBeam); if (g < (float)LSMALL) g = (float)LSMALL;
+   thr[0] = g; thr[1] = w;
+}
+
+// ... and the third of the N-best kernels: TokSetMerge's cut nThresh = genMax - nBeam (HRec.c:2002), floored at LSMALL / 2, not LSMALL
+__device__ __forceinline__ float dec_nbest_threshold(const double genMax, const float nBeam)
+{
+   const float nn = (float)(genMax - nBeam);
+   return (nn < (float)(LSMALL / 2)) ? (float)(LSMALL / 2) : nn;
 }
 
 // Maximum-model pruning (HVite -u; ProcessObservation HRec.c:1966-1985): when more than maxActive instances are attached, those whose

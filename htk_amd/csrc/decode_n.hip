@@ -304,7 +304,9 @@ __device__ __forceinline__ void set_step1(const NArgs &a, const DecUtt &ud, cons
    const DecNet &N = a.net;
    const int NS = (ni.x >> 4) & 255, t0 = ni.y;
    for (int j = 2; j < NS; j++) {
-      int lo = 1, hi = NS - 1;                              // CreateSEIndex (HRec.c:1403)
+      // CreateSEIndex (HRec.c:1403): dec_se_range (decode_dev.h).  The copy stays here and below: with the helper k_decode_n<256, true>
+      // went from 255 to 260 registers, one wavefront per SIMD fewer
+      int lo = 1, hi = NS - 1;
       while (lo < NS && !(tp[(lo - 1) * NS + (j - 1)] > LSMALL)) lo++;
       while (hi > 1 && !(tp[(hi - 1) * NS + (j - 1)] > LSMALL)) hi--;
       if (lo > hi) { lo = 1; hi = NS - 1; }
@@ -430,10 +432,8 @@ __global__ __launch_bounds__(NTHR) void k_decode_n(NArgs a)
          const double genMax = dec_block_max<NTHR>(myGen, red);
          const double wordMax = dec_block_max<NTHR>(myWord, red2);
          if (tid == 0) {
-            float w = (float)(wordMax - a.wordBeam); if (w < (float)LSMALL) w = (float)LSMALL;
-            float g = (float)(genMax - a.genBeam); if (g < (float)LSMALL) g = (float)LSMALL;
-            float nn = (float)(genMax - a.nBeam); if (nn < (float)(LSMALL / 2)) nn = (float)(LSMALL / 2);
-            thr[0] = g; thr[1] = w; thr[2] = nn;
+            dec_beam_thresholds(thr, genMax, wordMax, a.genBeam, a.wordBeam);
+            thr[2] = dec_nbest_threshold(genMax, a.nBeam);
          }
          __syncthreads();
          { TSet *sw = cur; cur = nxt; nxt = sw; }            // the new column is the current one from here on
@@ -524,9 +524,10 @@ __global__ __launch_bounds__(NTHR) void k_decode_n(NArgs a)
 // k_decode_ord_n -- N-best token passing in the order of HRec's instance list (decode_ord.hip has the design; this is its token-set
 // form).  In N-best mode the list's order decides more than exact ties: every TokSetMerge re-bases its relative tokens as floats
 // (HRec.c:361-364), so the order in which a node's senders are stepped is in the last bit of every alternative's likelihood -- and in
-// which of two alternatives of nearly equal likelihood survives.  The run therefore always walks the list.  Pass 1 = set_step1
-// over the list's instances; pass 2 = the walk of k_decode_ord with token sets pushed along the links in link order, each
-// merge by one lane on the set in global memory; StepWord2 allocates its Path record (+ NxtPaths) per call.
+// which of two alternatives of nearly equal likelihood survives.  The run therefore always walks the list.  The frame loop and the walk
+// are decode_ord.h's (ord_frames), the same code k_decode_ord runs; here are the form OrdSets (pass 1 = set_step1, token sets merged
+// along the links in link order, each merge by one lane on the set in global memory; StepWord2 allocates its Path record (+ NxtPaths)
+// per call), the kernel's prologue and its ending.
 __device__ void word_exit_ord(const NArgs &a, const DecUtt &ud, int n, int t, const TSet &st, TSet &e, int pid, int *pathNode, int *pathFrame)
 {
    const DecNet &N = a.net;
@@ -546,6 +547,90 @@ __device__ void word_exit_ord(const NArgs &a, const DecUtt &ud, int n, int t, co
    e.n = 1; e.rp[0] = e.path;                            // rl[0] / rlm[0] / ra[0] stay what the exit set held (AttachInst's rmax: 0, 0, NULL)
 }
 
+// The token-set form of the walk (decode_ord.h says what a form is)
+struct OrdSets {
+   typedef TSet Exit;
+   const NArgs &a; const DecUtt &ud; const DecNet &N; const int sel;
+   TSet *cur, *nxt, *ex; volatile double *imax;
+   const float *tpBase; const KeyOf ko;
+   size_t pathCap; int *pathNode, *pathFrame;
+   float nT;                    // this form only: TokSetMerge's cut nThresh = genMax - nBeam (HRec.c:2002), floored at LSMALL / 2, not LSMALL
+
+   __device__ __forceinline__ void null_exit(const int n) const { TSet z; ts_null(z); ex[n] = z; }
+   __device__ __forceinline__ void null_state(const int i) const { TSet z; ts_null(z); cur[i] = z; nxt[i] = z; }      // both columns
+   __device__ __forceinline__ void thresholds(const float *thr) { nT = thr[2]; }
+   __device__ __forceinline__ void extra_threshold(float *thr, const double genMax) const
+   {
+      thr[2] = dec_nbest_threshold(genMax, a.nBeam);
+   }
+   // this form only: pass 1 wrote the new column into nxt, which is the current one from here on
+   __device__ __forceinline__ void end_pass1() { TSet *sw = cur; cur = nxt; nxt = sw; }
+
+   __device__ __forceinline__ void step1(const int n, const int4 ni, const int t, const float gT, double &myGen, double &myWord) const
+   {
+      if ((ni.x & 15) != HTKAMD_NODE_HMM) {             // StepWord1 (HRec.c:1038): the sets' relative tokens stay as they are (ts_null_head, not ts_null)
+         const int t0 = ni.y;
+         TSet z = cur[t0]; ts_null_head(z); nxt[t0] = z;
+         TSet ze = ex[n]; ts_null_head(ze); ex[n] = ze;
+         imax[n] = LZERO;
+         return;
+      }
+      TSet exS; ts_null(exS);
+      double mx = LZERO;
+      set_step1<true>(a, ud, sel, n, ni, tpBase + ni.z, cur, nxt, gT, nT, t, ko, exS, mx, myWord);
+      if (mx > myGen) myGen = mx;
+      ex[n] = exS; imax[n] = (double)(float)mx;
+   }
+
+   // StepInst2 (HRec.c:1360): lane 0 makes the exit set, then every lane reads it
+   __device__ __forceinline__ bool step2(const int n, const int4 ni, const int t, const int lane, volatile OrdShared *vs) const
+   {
+      const int kind = ni.x & 15, NS = (ni.x >> 4) & 255, t0 = ni.y;
+      if (lane == 0) {
+         if (kind == HTKAMD_NODE_WORD) {               // StepWord2 (HRec.c:1046): a Path record (+ NxtPaths) per call
+            const int pid = vs->nPath;
+            if ((size_t)pid >= pathCap) vs->status = -4;
+            else {
+               TSet x = ex[n];
+               const TSet st = cur[t0];
+               const float r0 = x.rl[0], m0 = x.rlm[0]; const int a0 = x.ra[0];
+               word_exit_ord(a, ud, n, t, st, x, pid, pathNode, pathFrame);
+               x.rl[0] = r0; x.rlm[0] = m0; x.ra[0] = a0;
+               vs->nPath = pid + 1;
+               ex[n] = x;
+            }
+         } else if (kind == HTKAMD_NODE_NULL) ex[n] = cur[t0];
+         else if ((ni.x >> 12) & 1) {                  // tee model: StepHMM2 (HRec.c:790)
+            const TSet st = cur[t0];
+            TSet x = ex[n];
+            ts_merge(x, st.like + tpBase[ni.z + (NS - 1)], st.lm, st.path, st, nT, a.nToks, ko, st.align);
+            if (a.alignMode & 1) {                      // HRec.c:817-832
+               const double alk = x.like - x.lm * a.lmScale;
+               x.align = new_align(a, sel, n, -1, alk, t, x.align); x.ra[0] = x.align;
+               for (int q = 1; q < x.n; q++) x.ra[q] = new_align(a, sel, n, -1, alk, t, x.ra[q]);
+            }
+            ex[n] = x;
+         }
+      }
+      __threadfence_block();
+      return vs->status == 0;
+   }
+
+   __device__ __forceinline__ TSet exit_of(const int n) const { return ex[n]; }
+
+   // SetEntryState (HRec.c:1303): TokSetMerge into the destination's entry set, the relative tokens' lm shifted by the link's
+   __device__ __forceinline__ double set_entry(const TSet &e, const int d, const float lm, const double xl) const
+   {
+      const int td = N.nodeInfo[d].y;
+      TSet x = e;
+      for (int q = 0; q < x.n; q++) x.rlm[q] = e.rlm[q] + lm;
+      TSet res = cur[td];
+      ts_merge(res, xl, e.lm + lm, e.path, x, nT, a.nToks, ko, e.align);
+      cur[td] = res;
+      return res.like;
+   }
+};
+
 template <bool SET>      // SET: a network per utterance, as in k_decode_n
 __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
 {
@@ -555,7 +640,7 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
    __shared__ unsigned int usel[3]; __shared__ int uhist[256];
    __shared__ int scan[ORD_THREADS / 64 + 1];
    __shared__ OrdShared sh;
-   const int sel = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+   const int sel = blockIdx.x, tid = threadIdx.x;
    if (sel >= a.nUtt) return;
    const DecUtt ud = a.utt[sel];
    if constexpr (SET) { a.net = a.nets[ud.net]; a.ns = ud.ns; }
@@ -568,8 +653,6 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
    int *seqA = a.list.seq + (size_t)sel * 2 * a.list.seqCap, *seqB = seqA + a.list.seqCap;
    const size_t pathCap = 3 * ((size_t)(T + 1) * N.nWordNodes) + (size_t)a.list.pathExtra;
    int *pathNode = a.list.pathNode + ud.path0, *pathFrame = a.list.pathFrame + ud.path0;
-   const float *tpBase = N.transP;
-   const KeyOf ko{pathNode, 0};
 
    { TSet z; ts_null(z);
      for (int i = tid; i < N.nTok; i += ORD_THREADS) { cur[i] = z; nxt[i] = z; }
@@ -588,172 +671,10 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord_n(NArgs a)
    __threadfence_block();
    __syncthreads();
 
-   for (int t = 0; t <= T; t++) {
-      if (t >= 1) {
-         if (a.maxActive > 0 && sh.tail > a.maxActive) {    // maximum-model pruning (HRec.c:1966-1985; dec_prune_threshold, decode_dev.h)
-            const float uth = dec_prune_threshold<ORD_THREADS>(sh.tail, a.maxActive, usel, uhist, [&](const int i, float &key) {
-               const int n = c.seq[i];
-               if (n < 0) return false;
-               key = (float)imax[n];
-               return true;
-            });
-            if (uth > (float)LSMALL)
-               for (int i = tid; i < sh.tail; i += ORD_THREADS) {
-                  const int n = c.seq[i];
-                  if (n < 0 || !((float)imax[n] < uth)) continue;
-                  TSet z; ts_null(z);
-                  c.seq[i] = -1; pos[n] = -1; imax[n] = LZERO; ex[n] = z;
-                  const int4 ni = N.nodeInfo[n];
-                  const int nt = ((ni.x & 15) == HTKAMD_NODE_HMM) ? ((ni.x >> 4) & 255) - 1 : 1;
-                  for (int q = 0; q < nt; q++) { cur[ni.y + q] = z; nxt[ni.y + q] = z; }
-               }
-            __syncthreads();
-         }
-         ord_compact(c, seqA, seqB, scan);
-         // ---- pass 1 over the list's instances (set_step1; StepWord1 for the rest)
-         const float gT = thr[0], nT = thr[2];
-         double myGen = LZERO, myWord = LZERO;
-         const int nLive = sh.tail;
-         for (int li = tid; li < nLive; li += ORD_THREADS) {
-            const int n = c.seq[li];
-            const int4 ni = N.nodeInfo[n];
-            if ((ni.x & 15) != HTKAMD_NODE_HMM) {             // StepWord1 (HRec.c:1038): the sets' relative tokens stay as they are
-               const int t0 = ni.y;
-               TSet z = cur[t0]; ts_null_head(z); nxt[t0] = z;
-               TSet ze = ex[n]; ts_null_head(ze); ex[n] = ze;
-               imax[n] = LZERO;
-               continue;
-            }
-            TSet exS; ts_null(exS);
-            double mx = LZERO;
-            set_step1<true>(a, ud, sel, n, ni, tpBase + ni.z, cur, nxt, gT, nT, t, ko, exS, mx, myWord);
-            if (mx > myGen) myGen = mx;
-            ex[n] = exS; imax[n] = (double)(float)mx;
-         }
-         const double genMax = dec_block_max<ORD_THREADS>(myGen, red);
-         const double wordMax = dec_block_max<ORD_THREADS>(myWord, red2);
-         if (tid == 0) {
-            float w = (float)(wordMax - a.wordBeam); if (w < (float)LSMALL) w = (float)LSMALL;
-            float g = (float)(genMax - a.genBeam); if (g < (float)LSMALL) g = (float)LSMALL;
-            float nn = (float)(genMax - a.nBeam); if (nn < (float)(LSMALL / 2)) nn = (float)(LSMALL / 2);
-            thr[0] = g; thr[1] = w; thr[2] = nn;
-         }
-         __threadfence_block();
-         __syncthreads();
-         { TSet *sw = cur; cur = nxt; nxt = sw; }            // the new column is the current one from here on
-      }
-      // ---- pass 2: wavefront 0 walks the list while it changes
-      if (wv == 0) {
-         const float gT = thr[0], wT = thr[1], nT = thr[2];
-         volatile OrdShared *vs = &sh;
-         int idx = 0;
-         while (idx < vs->tail && vs->status == 0) {
-            const int tl = vs->tail;
-            const int cn = (tl - idx < 64) ? tl - idx : 64;
-            {
-               const int n = (lane < cn) ? c.seq[idx + lane] : -1;
-               vs->chunkNode[lane] = n;
-               vs->chunkMax[lane] = (n >= 0) ? (float)imax[n] : 0.0f;
-               if (lane == 0) { vs->base = idx; vs->cn = cn; }
-            }
-            __builtin_amdgcn_wave_barrier();
-            for (int i = 0; i < cn && vs->status == 0; i++) {
-               const int n = vs->chunkNode[i];
-               if (n < 0) continue;
-               const float nmax = vs->chunkMax[i];
-               const int4 ni = N.nodeInfo[n];
-               const int kind = ni.x & 15, NS = (ni.x >> 4) & 255, t0 = ni.y;
-               if (nmax < gT) {                               // DetachInst
-                  if (lane == 0) { TSet z; ts_null(z); o_blank(c, n); pos[n] = -1; imax[n] = LZERO; ex[n] = z; }
-                  const int nt = (kind == HTKAMD_NODE_HMM) ? NS - 1 : 1;
-                  if (lane < nt) { TSet z; ts_null(z); cur[t0 + lane] = z; nxt[t0 + lane] = z; }
-                  __threadfence_block();
-                  continue;
-               }
-               // StepInst2 (HRec.c:1360); lane 0 makes the exit set, then every lane reads it
-               if (lane == 0) {
-                  if (kind == HTKAMD_NODE_WORD) {
-                     const int pid = vs->nPath;
-                     if ((size_t)pid >= pathCap) vs->status = -4;
-                     else {
-                        TSet e = ex[n];
-                        const TSet st = cur[t0];
-                        const float r0 = e.rl[0], m0 = e.rlm[0]; const int a0 = e.ra[0];
-                        word_exit_ord(a, ud, n, t, st, e, pid, pathNode, pathFrame);
-                        e.rl[0] = r0; e.rlm[0] = m0; e.ra[0] = a0;
-                        vs->nPath = pid + 1;
-                        ex[n] = e;
-                     }
-                  } else if (kind == HTKAMD_NODE_NULL) ex[n] = cur[t0];
-                  else if ((ni.x >> 12) & 1) {              // tee model: StepHMM2 (HRec.c:790)
-                     const TSet st = cur[t0];
-                     TSet e = ex[n];
-                     ts_merge(e, st.like + tpBase[ni.z + (NS - 1)], st.lm, st.path, st, nT, a.nToks, ko, st.align);
-                     if (a.alignMode & 1) {                   // HRec.c:817-832
-                        const double alk = e.like - e.lm * a.lmScale;
-                        e.align = new_align(a, sel, n, -1, alk, t, e.align); e.ra[0] = e.align;
-                        for (int q = 1; q < e.n; q++) e.ra[q] = new_align(a, sel, n, -1, alk, t, e.ra[q]);
-                     }
-                     ex[n] = e;
-                  }
-               }
-               __threadfence_block();
-               if (vs->status != 0) break;
-               const TSet e = ex[n];
-               double tkLike = e.like; float tkLm = e.lm;
-               if (kind != HTKAMD_NODE_HMM && tkLike < wT) tkLike = LZERO;
-               if (tkLike > gT) {
-                  const int k0 = N.linkOff[n], k1 = N.linkOff[n + 1];
-                  const bool dup = N.dupDest[n] != 0;
-                  for (int kb = k0; kb < k1; kb += 64) {
-                     const int k = kb + lane;
-                     const bool act = k < k1;
-                     const int d = act ? N.linkDest[k] : 0;
-                     const float lm = act ? N.linkLike[k] : 0.0f;
-                     const double xl = tkLike + lm * a.lmScale;
-                     const bool pass = act && xl > gT;
-                     unsigned long long need = __ballot(pass && pos[d] < 0);
-                     while (need) {
-                        const int j = __ffsll((long long)need) - 1;
-                        need &= need - 1;
-                        const int dj = __shfl(d, j);
-                        if (lane == 0 && pos[dj] < 0) o_attach(c, dj);
-                        __threadfence_block();
-                     }
-                     if (vs->status != 0) break;
-                     unsigned long long todo = __ballot(pass);
-                     if (!dup) todo = pass ? (1ull << lane) : 0ull;
-                     while (todo) {
-                        const int j = dup ? __ffsll((long long)todo) - 1 : lane;
-                        todo = dup ? (todo & (todo - 1)) : 0ull;
-                        if (lane == j) {                      // SetEntryState (HRec.c:1303): TokSetMerge into the destination's entry set
-                           const int td = N.nodeInfo[d].y;
-                           TSet x = e;
-                           for (int q = 0; q < x.n; q++) x.rlm[q] = e.rlm[q] + lm;
-                           TSet res = cur[td];
-                           ts_merge(res, xl, tkLm + lm, e.path, x, nT, a.nToks, ko, e.align);
-                           cur[td] = res;
-                           const double m0 = imax[d];
-                           if (res.like > m0) {
-                              const float nm = (float)res.like;
-                              imax[d] = (double)nm;
-                              const int pd = pos[d];
-                              if (pd >= vs->base && pd < vs->base + vs->cn) vs->chunkMax[pd - vs->base] = nm;
-                           }
-                        }
-                        if (dup) __threadfence_block();
-                     }
-                     __threadfence_block();
-                  }
-               }
-            }
-            idx += cn;
-         }
-      }
-      __threadfence_block();
-      __syncthreads();
-      if (sh.status != 0) break;
-   }
+   OrdSets f{a, ud, N, sel, cur, nxt, ex, imax, N.transP, KeyOf{pathNode, 0}, pathCap, pathNode, pathFrame, (float)LSMALL};
+   ord_frames(c, f, OrdLds{red, red2, thr, usel, uhist, scan}, seqA, seqB, T, OrdBeams{a.maxActive, a.genBeam, a.wordBeam, a.lmScale});
+
+   // ---- CompleteRecognition -> CreateLattice.  This form's ending: no batch result to keep, a full table (-4) reported as "did not fit" (-3)
    if (tid == 0) {
       if (a.alignMode && a.alCount[sel] > a.alCap) sh.status = -4;                 // more alignment records than there was room for
       if (sh.status != 0) { a.total[u] = LZERO; a.latN[2 * u] = sh.status == -4 ? -3 : sh.status; a.latN[2 * u + 1] = 0; }

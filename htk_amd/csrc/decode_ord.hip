@@ -20,8 +20,11 @@
 // stepped are the lanes (the tokens a node sends go to different nodes; attaching, which appends, is taken link by link).  Tokens,
 // exit tokens and instance maxima are the arrays k_decode uses; Path records are allocated one by one (StepWord2 may run twice on a node
 // in one frame -- "may be repeated", HRec.c:1046 -- and both records can stay referenced).
-// The list and its compaction are decode_ord.h's (shared with k_decode_ord_n, which has this walk in its token-set form); the pruning
-// threshold and the traceback are decode_dev.h's.  Output probabilities come from the same score block (K1, exact mode).  Tested against HVite on the tie files and sweeps
+//
+// Where the code is.  The list, its compaction and the frame loop with the walk are decode_ord.h's, shared with k_decode_ord_n
+// (decode_n.hip); the pruning threshold, the beam thresholds and the traceback are decode_dev.h's.  This file has what is 1-best about
+// it: the token form OrdTok (a Tok per state, strict > where two tokens meet), the kernel's prologue and its ending.  Output
+// probabilities come from the same score block (K1, exact mode).  Tested against HVite on the tie files and sweeps
 // (tests/test_gpu_decode.py, tests/fuzz_parity.py) and against oracle/orc_decode.c, which walks the same list (oracle/orc_ilist.h).
 #include <hip/hip_runtime.h>
 #include <cstdlib>
@@ -32,6 +35,129 @@
 #include "decode.h"
 
 #include "decode_ord.h"
+
+// The 1-best token form of the walk (decode_ord.h says what a form is)
+struct OrdTok {
+   typedef Tok Exit;
+   const DecArgs &a; const DecUtt &ud; const DecNet &N;
+   Tok *tok, *ex; volatile double *imax;
+   const float *tpBase;
+   size_t pathCap;
+   int *pathPrev, *pathNode, *pathFrame; double *pathLike; float *pathLm;
+   Tok e;                       // the exit token step2 has just computed, in every lane (exit_of)
+
+   __device__ __forceinline__ void null_exit(const int n) const { ex[n] = dec_null(); }
+   __device__ __forceinline__ void null_state(const int i) const { tok[i] = dec_null(); }
+   __device__ __forceinline__ void thresholds(const float *) const {}
+   __device__ __forceinline__ void extra_threshold(float *, double) const {}
+   __device__ __forceinline__ void end_pass1() const {}
+
+   // StepHMM1 (HRec.c:642) with the model's tokens in registers; StepWord1 (:1038) for the rest
+   __device__ __forceinline__ void step1(const int n, const int4 ni, const int t, const float gT, double &myGen, double &myWord) const
+   {
+      if ((ni.x & 15) != HTKAMD_NODE_HMM) { tok[ni.y] = dec_null(); ex[n] = dec_null(); imax[n] = LZERO; return; }
+      const int NS = (ni.x >> 4) & 255, t0 = ni.y;
+      const float *tp = tpBase + ni.z;
+      Tok s[DEC_MAXN];
+      bool live = false;
+#pragma unroll
+      for (int q = 1; q < DEC_MAXN; q++) { s[q] = dec_null(); if (q < NS) s[q] = tok[t0 + q - 1]; }
+#pragma unroll
+      for (int q = 1; q < DEC_MAXN; q++) if (q < NS && s[q].like > LSMALL) live = true;
+      Tok exT = dec_null();
+      double mx = LZERO;
+      if (live) {
+         Tok nw[DEC_MAXN];
+#pragma unroll
+         for (int j = 2; j < DEC_MAXN; j++) {
+            nw[j] = dec_null();
+            if (j < NS) {
+               int lo, hi;
+               dec_se_range(tp, NS, j, 1, lo, hi);
+               Tok best = s[1]; double bl = LZERO;
+#pragma unroll
+               for (int q = 1; q < DEC_MAXN; q++)
+                  if (q >= lo && q <= hi) {
+                     const double cc = s[q].like + tp[(q - 1) * NS + (j - 1)];
+                     if (q == lo || cc > bl) { best = s[q]; bl = cc; }
+                  }
+               best.like = bl;
+               if (best.like > gT) {
+                  const int st = N.hmmState[ni.w + (j - 2)];
+                  best.like += a.score[ud.score0 + (size_t)(t - 1) * a.ns + N.stateSlot[st]];
+                  nw[j] = best;
+                  if (best.like > mx) mx = best.like;
+               }
+            }
+         }
+         {
+            int lo, hi;
+            dec_se_range(tp, NS, NS, 2, lo, hi);
+            Tok best = nw[2]; double bl = LZERO;
+#pragma unroll
+            for (int q = 2; q < DEC_MAXN; q++)
+               if (q >= lo && q <= hi) {
+                  const double cc = nw[q].like + tp[(q - 1) * NS + (NS - 1)];
+                  if (q == lo || cc > bl) { best = nw[q]; bl = cc; }
+               }
+            best.like = bl;
+            if (best.like > LSMALL) {
+               exT = best;
+               const double w = best.like + N.wdlk[n];
+               if (w > myWord) myWord = w;
+            }
+         }
+         tok[t0] = dec_null();                            // entry consumed
+#pragma unroll
+         for (int j = 2; j < DEC_MAXN; j++) if (j < NS) tok[t0 + j - 1] = nw[j];
+         if (mx > myGen) myGen = mx;
+      }
+      ex[n] = exT; imax[n] = (double)(float)mx;         // inst->max is a LogFloat (HRec.c:138)
+   }
+
+   // StepInst2 (HRec.c:1360): every lane computes the exit token, lane 0 stores it
+   __device__ __forceinline__ bool step2(const int n, const int4 ni, const int t, const int lane, volatile OrdShared *vs)
+   {
+      const int kind = ni.x & 15, NS = (ni.x >> 4) & 255, t0 = ni.y;
+      if (kind == HTKAMD_NODE_WORD) {               // StepWord2 (HRec.c:1046): a Path record per call
+         const Tok st = tok[t0];
+         e = st;
+         e.like += a.wordPen;
+         e.like += N.pronProb[n] * a.prScale;
+         const int pid = vs->nPath;
+         if ((size_t)pid >= pathCap) { if (lane == 0) vs->status = -4; return false; }
+         if (lane == 0) {
+            pathPrev[pid] = st.path; pathLike[pid] = e.like; pathLm[pid] = e.lm; pathNode[pid] = n; pathFrame[pid] = t;
+            vs->nPath = pid + 1;
+         }
+         e.path = pid; e.lm = 0.0f;
+         if (lane == 0) ex[n] = e;
+      } else if (kind == HTKAMD_NODE_NULL) {
+         e = tok[t0];
+         if (lane == 0) ex[n] = e;
+      } else {
+         e = ex[n];
+         if ((ni.x >> 12) & 1) {                    // tee model: StepHMM2 (HRec.c:790)
+            const Tok st = tok[t0];
+            const double cc = st.like + tpBase[ni.z + (NS - 1)];
+            if (cc > e.like) { e = st; e.like = cc; if (lane == 0) ex[n] = e; }
+         }
+      }
+      return true;
+   }
+   __device__ __forceinline__ Tok exit_of(int) const { return e; }
+
+   // SetEntryState (HRec.c:1303): strict >, the first of equal tokens stays
+   __device__ __forceinline__ double set_entry(const Tok &e, const int d, const float lm, const double xl) const
+   {
+      const int td = N.nodeInfo[d].y;
+      Tok x = e;
+      x.like = xl; x.lm = e.lm + lm;
+      Tok cur = tok[td];
+      if (x.like > cur.like) { tok[td] = x; cur = x; }
+      return cur.like;
+   }
+};
 
 __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
 {
@@ -44,7 +170,7 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
    __shared__ unsigned int usel[4];
    __shared__ int scan[ORD_THREADS / 64 + 1];
    __shared__ OrdShared sh;
-   const int sel = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+   const int sel = blockIdx.x, tid = threadIdx.x;
    if (sel >= a.nUtt) return;
    const DecUtt ud = a.utt[sel];
    const DecNet &N = a.net;
@@ -55,11 +181,10 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
    volatile unsigned char *ooo = oa.list.ooo + ud.node0;
    int *seqA = oa.list.seq + (size_t)sel * 2 * oa.list.seqCap, *seqB = seqA + oa.list.seqCap;
    const size_t pathCap = 3 * ((size_t)(T + 1) * N.nWordNodes) + (size_t)oa.list.pathExtra;      // as the host laid the records out (decode.hip)
-   int *pathPrev = a.pathPrev + ud.path0, *pathNode = oa.list.pathNode + ud.path0, *pathFrame = oa.list.pathFrame + ud.path0;
-   double *pathLike = a.pathLike + ud.path0; float *pathLm = a.pathLm + ud.path0;
+   int *pathNode = oa.list.pathNode + ud.path0, *pathFrame = oa.list.pathFrame + ud.path0;
+   // (this form only: the transition matrices in LDS where they fit -- pass 1 reads them per state pair, the N-best form through set_step1's sets)
    const bool tpInLds = N.nTpFloats <= 2048;
    if (tpInLds) for (int i = tid; i < N.nTpFloats; i += ORD_THREADS) ltp[i] = N.transP[i];
-   const float *tpBase = tpInLds ? ltp : N.transP;
 
    for (int i = tid; i < N.nTok; i += ORD_THREADS) tok[i] = dec_null();
    for (int i = tid; i < N.nNodes; i += ORD_THREADS) { ex[i] = dec_null(); imax[i] = LZERO; pos[i] = -1; ooo[i] = 0; }
@@ -74,222 +199,13 @@ __global__ __launch_bounds__(ORD_THREADS) void k_decode_ord(OrdArgs oa)
    }
    __syncthreads();
 
-   for (int t = 0; t <= T; t++) {
-      if (t >= 1) {
-         // ---- maximum-model pruning (ProcessObservation HRec.c:1966-1985): more than maxActive instances on the list -> those whose max
-         // lies below the (maxActive + 1)-th largest (as floats) are detached (the threshold: dec_prune_threshold, decode_dev.h)
-         if (a.maxActive > 0 && sh.tail > a.maxActive) {
-            const float uth = dec_prune_threshold<ORD_THREADS>(sh.tail, a.maxActive, usel, uhist, [&](const int i, float &key) {
-               const int n = c.seq[i];
-               if (n < 0) return false;
-               key = (float)imax[n];
-               return true;
-            });
-            if (uth > (float)LSMALL)
-               for (int i = tid; i < sh.tail; i += ORD_THREADS) {
-                  const int n = c.seq[i];
-                  if (n < 0 || !((float)imax[n] < uth)) continue;
-                  c.seq[i] = -1; pos[n] = -1; imax[n] = LZERO; ex[n] = dec_null();
-                  const int4 ni = N.nodeInfo[n];
-                  const int nt = ((ni.x & 15) == HTKAMD_NODE_HMM) ? ((ni.x >> 4) & 255) - 1 : 1;
-                  for (int q = 0; q < nt; q++) tok[ni.y + q] = dec_null();
-               }
-            __syncthreads();
-         }
-         ord_compact(c, seqA, seqB, scan);
-         // ---- pass 1: StepInst1 on every instance (no order in it: the beams' tops are maxima)
-         const float gT = thr[0];                           // threshold of the previous frame
-         double myGen = LZERO, myWord = LZERO;
-         const int nLive = sh.tail;
-         for (int i = tid; i < nLive; i += ORD_THREADS) {
-            const int n = c.seq[i];
-            const int4 ni = N.nodeInfo[n];
-            if ((ni.x & 15) != HTKAMD_NODE_HMM) { tok[ni.y] = dec_null(); ex[n] = dec_null(); imax[n] = LZERO; continue; }     // StepWord1 (HRec.c:1038)
-            const int NS = (ni.x >> 4) & 255, t0 = ni.y;
-            const float *tp = tpBase + ni.z;
-            Tok s[DEC_MAXN];
-            bool live = false;
-#pragma unroll
-            for (int q = 1; q < DEC_MAXN; q++) { s[q] = dec_null(); if (q < NS) s[q] = tok[t0 + q - 1]; }
-#pragma unroll
-            for (int q = 1; q < DEC_MAXN; q++) if (q < NS && s[q].like > LSMALL) live = true;
-            Tok exT = dec_null();
-            double mx = LZERO;
-            if (live) {
-               Tok nw[DEC_MAXN];
-#pragma unroll
-               for (int j = 2; j < DEC_MAXN; j++) {
-                  nw[j] = dec_null();
-                  if (j < NS) {
-                     int lo = 1, hi = NS - 1;                 // CreateSEIndex (HRec.c:1403)
-                     while (lo < NS && !(tp[(lo - 1) * NS + (j - 1)] > LSMALL)) lo++;
-                     while (hi > 1 && !(tp[(hi - 1) * NS + (j - 1)] > LSMALL)) hi--;
-                     if (lo > hi) { lo = 1; hi = NS - 1; }
-                     Tok best = s[1]; double bl = LZERO;
-#pragma unroll
-                     for (int q = 1; q < DEC_MAXN; q++)
-                        if (q >= lo && q <= hi) {
-                           const double cc = s[q].like + tp[(q - 1) * NS + (j - 1)];
-                           if (q == lo || cc > bl) { best = s[q]; bl = cc; }
-                        }
-                     best.like = bl;
-                     if (best.like > gT) {
-                        const int st = N.hmmState[ni.w + (j - 2)];
-                        best.like += a.score[ud.score0 + (size_t)(t - 1) * a.ns + N.stateSlot[st]];
-                        nw[j] = best;
-                        if (best.like > mx) mx = best.like;
-                     }
-                  }
-               }
-               {
-                  int lo = 2, hi = NS - 1;
-                  while (lo < NS && !(tp[(lo - 1) * NS + (NS - 1)] > LSMALL)) lo++;
-                  while (hi > 1 && !(tp[(hi - 1) * NS + (NS - 1)] > LSMALL)) hi--;
-                  if (lo > hi) { lo = 2; hi = NS - 1; }
-                  Tok best = nw[2]; double bl = LZERO;
-#pragma unroll
-                  for (int q = 2; q < DEC_MAXN; q++)
-                     if (q >= lo && q <= hi) {
-                        const double cc = nw[q].like + tp[(q - 1) * NS + (NS - 1)];
-                        if (q == lo || cc > bl) { best = nw[q]; bl = cc; }
-                     }
-                  best.like = bl;
-                  if (best.like > LSMALL) {
-                     exT = best;
-                     const double w = best.like + N.wdlk[n];
-                     if (w > myWord) myWord = w;
-                  }
-               }
-               tok[t0] = dec_null();                            // entry consumed
-#pragma unroll
-               for (int j = 2; j < DEC_MAXN; j++) if (j < NS) tok[t0 + j - 1] = nw[j];
-               if (mx > myGen) myGen = mx;
-            }
-            ex[n] = exT; imax[n] = (double)(float)mx;         // inst->max is a LogFloat (HRec.c:138)
-         }
-         const double genMax = dec_block_max<ORD_THREADS>(myGen, red);
-         const double wordMax = dec_block_max<ORD_THREADS>(myWord, red2);
-         if (tid == 0) {
-            float w = (float)(wordMax - a.wordBeam); if (w < (float)LSMALL) w = (float)LSMALL;
-            float g = (float)(genMax - a.genBeam); if (g < (float)LSMALL) g = (float)LSMALL;
-            thr[0] = g; thr[1] = w;
-         }
-         __threadfence_block();
-         __syncthreads();
-      }
-      // ---- pass 2 (HRec.c:2011-2021; at t = 0 StartRecognition's): wavefront 0 walks the list while it changes
-      if (wv == 0) {
-         const float gT = thr[0], wT = thr[1];
-         volatile OrdShared *vs = &sh;
-         int idx = 0;
-         while (idx < vs->tail && vs->status == 0) {
-            const int tl = vs->tail;
-            const int cn = (tl - idx < 64) ? tl - idx : 64;
-            {
-               const int n = (lane < cn) ? c.seq[idx + lane] : -1;
-               vs->chunkNode[lane] = n;
-               vs->chunkMax[lane] = (n >= 0) ? (float)imax[n] : 0.0f;
-               if (lane == 0) { vs->base = idx; vs->cn = cn; }
-            }
-            __builtin_amdgcn_wave_barrier();
-            for (int i = 0; i < cn && vs->status == 0; i++) {
-               const int n = vs->chunkNode[i];
-               if (n < 0) continue;                           // moved or detached since the chunk was fetched
-               const float nmax = vs->chunkMax[i];
-               const int4 ni = N.nodeInfo[n];
-               const int kind = ni.x & 15, NS = (ni.x >> 4) & 255, t0 = ni.y;
-               if (nmax < gT) {                               // DetachInst (HRec.c:1270): every token of the instance goes
-                  if (lane == 0) { o_blank(c, n); pos[n] = -1; imax[n] = LZERO; ex[n] = dec_null(); }
-                  const int nt = (kind == HTKAMD_NODE_HMM) ? NS - 1 : 1;
-                  if (lane < nt) tok[t0 + lane] = dec_null();
-                  __threadfence_block();
-                  continue;
-               }
-               // StepInst2 (HRec.c:1360)
-               Tok e;
-               if (kind == HTKAMD_NODE_WORD) {               // StepWord2 (HRec.c:1046): a Path record per call
-                  const Tok st = tok[t0];
-                  e = st;
-                  e.like += a.wordPen;
-                  e.like += N.pronProb[n] * a.prScale;
-                  const int pid = vs->nPath;
-                  if ((size_t)pid >= pathCap) { if (lane == 0) vs->status = -4; break; }
-                  if (lane == 0) {
-                     pathPrev[pid] = st.path; pathLike[pid] = e.like; pathLm[pid] = e.lm; pathNode[pid] = n; pathFrame[pid] = t;
-                     vs->nPath = pid + 1;
-                  }
-                  e.path = pid; e.lm = 0.0f;
-                  if (lane == 0) ex[n] = e;
-               } else if (kind == HTKAMD_NODE_NULL) {
-                  e = tok[t0];
-                  if (lane == 0) ex[n] = e;
-               } else {
-                  e = ex[n];
-                  if ((ni.x >> 12) & 1) {                    // tee model: StepHMM2 (HRec.c:790)
-                     const Tok st = tok[t0];
-                     const double cc = st.like + tpBase[ni.z + (NS - 1)];
-                     if (cc > e.like) { e = st; e.like = cc; if (lane == 0) ex[n] = e; }
-                  }
-               }
-               Tok tk = e;
-               if (kind != HTKAMD_NODE_HMM && tk.like < wT) tk = dec_null();
-               if (tk.like > gT) {
-                  const int k0 = N.linkOff[n], k1 = N.linkOff[n + 1];
-                  const bool dup = N.dupDest[n] != 0;
-                  for (int kb = k0; kb < k1; kb += 64) {
-                     const int k = kb + lane;
-                     const bool act = k < k1;
-                     const int d = act ? N.linkDest[k] : 0;
-                     const float lm = act ? N.linkLike[k] : 0.0f;
-                     Tok x = tk;
-                     x.like = tk.like + lm * a.lmScale; x.lm = tk.lm + lm;
-                     const bool pass = act && x.like > gT;
-                     // AttachInst for the destinations without an instance, link by link (appending is what orders the list)
-                     unsigned long long need = __ballot(pass && pos[d] < 0);
-                     while (need) {
-                        const int j = __ffsll((long long)need) - 1;
-                        need &= need - 1;
-                        const int dj = __shfl(d, j);
-                        if (lane == 0 && pos[dj] < 0) o_attach(c, dj);       // (a destination met twice among the links is attached once)
-                        __threadfence_block();
-                     }
-                     if (vs->status != 0) break;
-                     // SetEntryState (HRec.c:1303): strict >, the first of equal tokens stays; the instance's max follows
-                     unsigned long long todo = __ballot(pass);
-                     if (!dup) todo = pass ? (1ull << lane) : 0ull;          // distinct destinations: every lane its own, at once
-                     while (todo) {
-                        const int j = dup ? __ffsll((long long)todo) - 1 : lane;
-                        todo = dup ? (todo & (todo - 1)) : 0ull;
-                        if (lane == j) {
-                           const int td = N.nodeInfo[d].y;
-                           Tok cur = tok[td];
-                           if (x.like > cur.like) { tok[td] = x; cur = x; }
-                           const double m0 = imax[d];
-                           if (cur.like > m0) {
-                              const float nm = (float)cur.like;
-                              imax[d] = (double)nm;
-                              const int pd = pos[d];
-                              if (pd >= vs->base && pd < vs->base + vs->cn) vs->chunkMax[pd - vs->base] = nm;
-                           }
-                        }
-                        if (dup) __threadfence_block();
-                     }
-                     __threadfence_block();
-                  }
-               }
-            }
-            idx += cn;
-         }
-      }
-      __threadfence_block();
-      __syncthreads();
-      if (sh.status != 0) break;
-   }
+   OrdTok f{a, ud, N, tok, ex, imax, tpInLds ? ltp : N.transP, pathCap, a.pathPrev + ud.path0, pathNode, pathFrame, a.pathLike + ud.path0, a.pathLm + ud.path0, dec_null()};
+   ord_frames(c, f, OrdLds{red, red2, thr, usel, uhist, scan}, seqA, seqB, T, OrdBeams{a.maxActive, a.genBeam, a.wordBeam, a.lmScale});
 
    // ---- CompleteRecognition: the 1-best chain (dec_traceback, decode_dev.h)
    if (tid == 0) {
-      // (a capacity of the LIST walk is no reason to lose an answer the batch kernel has already given -- a tie-free order is
-      // one valid order of HRec's; the status codes -4 / -5 / -6 then never reach the caller in the default mode)
+      // (this form only: a capacity of the LIST walk is no reason to lose an answer the batch kernel has already given -- a tie-free order
+      // is one valid order of HRec's; the status codes -4 / -5 / -6 then never reach the caller in the default mode)
       if (sh.status != 0 && oa.keepFast && a.nWords[u] >= 0) return;
       if (sh.status != 0) { a.total[u] = LZERO; a.finalLm[u] = 0.0f; a.nWords[u] = sh.status; }
       else dec_traceback(a, ud, u, (pos[N.final] >= 0) ? ex[N.final] : dec_null(), PathView{pathFrame, pathNode, N.nWordNodes, N.wordNode});

@@ -82,7 +82,8 @@ __global__ __launch_bounds__(64 * W * UPB(W)) void k_viterbi_w(VitArgs a)
 #pragma unroll
          for (int j = 0; j < MAXN; j++)
             if (i < N && j < N) tp[i][j] = gt[i * N + j];
-      // CreateSEIndex (HRec.c:1403-1431)
+      // CreateSEIndex (HRec.c:1403-1431): dec_se_range's ranges (decode_dev.h), not its scan -- over the register copy of the matrix,
+      // fully unrolled, so that seLo / seHi stay in registers
 #pragma unroll
       for (int j = 2; j <= MAXN; j++)
          if (j <= N) {
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(VG_THREADS) void k_viterbi_g(VitArgs a)
             double nw[VG_MAXN];
             double mx = LZERO;
             for (int j = 2; j < N; j++) {
-               int lo = 1, hi = N - 1;                    // CreateSEIndex (HRec.c:1403)
+               int lo = 1, hi = N - 1;                    // CreateSEIndex (HRec.c:1403): dec_se_range (decode_dev.h); the copy stays, the helper cost this kernel 6 VGPRs
                while (lo < N && !(tp[(lo - 1) * N + (j - 1)] > (float)LSMALL)) lo++;
                while (hi > 1 && !(tp[(hi - 1) * N + (j - 1)] > (float)LSMALL)) hi--;
                if (lo > hi) { lo = 1; hi = N - 1; }

@@ -63,6 +63,10 @@ def test_decoder_larger_loop_matches_oracle(native, oracle, tmp_path):
     for u, (words, total) in enumerate(res):
         ow, ot = oracle.decode(om, feats[u], net.arrays(), genBeam=120.0)
         assert words == ow and total == ot and len(words) >= 3
+    # ... and every utterance through the list kernel: node 1 sends along 400 links, the walk's link loop takes them 64 at a time
+    dx = native.Decoder(model, net)
+    dx.set_order(native.ORDER_EXACT)
+    assert dx.run(feats, genBeam=120.0) == res and dx.last_tied() == len(feats)
     # an impossible utterance (shorter than any path through the network) reports "no token survived"
     short = native.Decoder(model, net).run([s.feats[0][:2]], genBeam=120.0)
     assert short[0][0] is None
@@ -405,6 +409,46 @@ def test_list_walk_out_of_capacity_keeps_the_batch_kernels_answer(native, tmp_pa
     auto = dec.run(feats, **p)
     assert dec.last_tied() >= 1                               # the tie was seen and the list kernel tried
     assert auto == fast
+
+
+def test_list_walk_parallel_links_match_oracle(native, oracle, tmp_path):
+    """Two links of a node with ONE destination (DecNet::dupDest: the walk then takes the node's links one lane after the other): tie_122's
+    lattice with parallel arcs of other LM likelihoods between the same words.  Both list kernels against the CPU oracle, which walks the
+    same list: the 1-best words and totals, and the N-best lattice (total, nodes, arcs) value for value."""
+    import json
+    from decode_util import GOLD
+    d = os.path.join(GOLD, "ties2", "tie_122")
+    lines = open(os.path.join(d, "net.slf")).read().splitlines()
+    nodes = [l for l in lines if l.startswith("I=")]
+    arcs = [l for l in lines if l.startswith("J=")]
+    extra = [(0, 1, -0.70), (1, 2, -1.20), (2, 2, -1.90), (3, 1, -2.10), (3, 4, -1.75), (1, 2, -2.50)]
+    xarcs = ["J=%d S=%d E=%d l=%.2f" % (len(arcs) + k, s, e, l) for k, (s, e, l) in enumerate(extra)]
+    slf = tmp_path / "net.slf"
+    slf.write_text("VERSION=1.0\nN=%d L=%d\n" % (len(nodes), len(arcs) + len(xarcs)) + "\n".join(nodes + arcs + xarcs) + "\n")
+    mmf = native.Mmf(files=[os.path.join(d, "MMF")], hmm_list=os.path.join(d, "hmmlist"))
+    net = native.Net(str(slf), os.path.join(d, "dict"), mmf)
+    a = net.arrays()
+    dup = [n for n in range(len(a["kind"])) if len(set(a["linkDest"][a["linkOff"][n]:a["linkOff"][n + 1]].tolist())) < a["linkOff"][n + 1] - a["linkOff"][n]]
+    assert len(dup) >= 3                                           # the parallel arcs are parallel links of the network
+    z = np.load(os.path.join(d, "feats.npz"))
+    feats = [z["u%d" % u] for u in range(len(z.files))]
+    p = parse_opts(next(iter(json.load(open(os.path.join(d, "expected.json"))))))
+    model, om = native.Model(mmf.packed()), oracle.Model(mmf.packed())
+    dec = native.Decoder(model, net, lmScale=p["lmScale"])
+    dec.set_order(native.ORDER_EXACT)
+    res = dec.run(feats, **p)
+    assert dec.last_tied() == len(feats)
+    for u, (words, total) in enumerate(res):
+        ow, ot = oracle.decode(om, feats[u], a, **p)
+        assert words is not None and words == ow and total == ot, u
+    lats = dec.run_lattice(feats, 4, **p)
+    arcs_of = lambda l: sorted(zip(l["arcStart"].tolist(), l["arcEnd"].tolist(), l["arcAc"].tolist(), l["arcLm"].tolist(), l["arcPr"].tolist(), l["arcScore"].tolist()))
+    for u, got in enumerate(lats):
+        ref = oracle.decode_nbest(om, feats[u], a, 4, **p)
+        assert got is not None and ref is not None and got["total"] == ref["total"], u
+        for k in ("nodeFrame", "nodeNet", "nodeLike"):
+            assert np.array_equal(got[k], ref[k]), (u, k)
+        assert arcs_of(got) == arcs_of(ref) and len(got["arcStart"]) > 4, u
 
 
 @pytest.mark.parametrize("case", ["loop", "bigram", "tee", "wint", "ties", "xwrd:net"])

@@ -42,6 +42,8 @@ def main():
     net = capi.Net(os.path.join(d, "net.slf"), os.path.join(d, "dict"), mmf)
     print("setup %.1f s; nodes %d links %d" % (time.time() - t0, net.desc.nNodes, net.desc.nLinks))
     dec = capi.Decoder(model, net)
+    # DEC_ORDER = auto | fast | exact (exact: every utterance through the list kernel k_decode_ord; one wavefront walks per utterance -- use a small size)
+    dec.set_order({"auto": capi.ORDER_AUTO, "fast": capi.ORDER_FAST, "exact": capi.ORDER_EXACT}[os.environ.get("DEC_ORDER", "auto")])
     for rep in range(2):
         t0 = time.time()
         res = dec.run(s.feats, genBeam=250.0, scoreMode=int(os.environ.get("DEC_SCORE_MODE", "0")))
