@@ -23,7 +23,7 @@ def main(argv=None):
     ap.add_argument("--trees", help="trees file (overrides the script's ST)")
     ap.add_argument("--no-merge", action="store_true"); ap.add_argument("--no-leaf-stats", action="store_true")
     a = ap.parse_args(argv)
-    sc = treeclust.parse_script(open(a.script).read(), synth=True)
+    sc = treeclust.parse_script(open(a.script).read(), synth=True, regtree=True)
     if a.trees:
         sc.trees_path = os.path.abspath(a.trees)
     mmf = capi.Mmf([a.mmf], hmm_list=a.hmmlist)

@@ -1009,6 +1009,71 @@ def tree_split_sums(item_stats, node_items, answers, stream=None) -> np.ndarray:
     return out
 
 
+class RegTree(_Handle):
+    """A regression class tree (htkamd_regtree): what Mmf.regtree built, or -- for the writers alone -- a tree from tables:
+    RegTree.from_tables(children=[(left, right) | (0, 0), ...] by node number from 1, components={terminal node: [(model, state, mix), ...]}).
+    write(identifier, dir) gives HHEd RC's two files, <identifier>.tree and <identifier>.base."""
+    _destroy = "htkamd_regtree_destroy"
+
+    def __init__(self, h):
+        self.h = h
+
+    @classmethod
+    def from_tables(cls, children, components):
+        n = len(children)
+        left = (C.c_int * max(n, 1))(*[int(c[0]) for c in children]); right = (C.c_int * max(n, 1))(*[int(c[1]) for c in children])
+        off, flat = [0], []
+        for i in range(1, n + 1):
+            flat += list(components.get(i, ()))
+            off.append(len(flat))
+        co = (C.c_int * (n + 1))(*off)
+        cm = (C.c_char_p * max(len(flat), 1))(*[str(x[0]).encode() for x in flat])
+        cs = (C.c_int * max(len(flat), 1))(*[int(x[1]) for x in flat]); cx = (C.c_int * max(len(flat), 1))(*[int(x[2]) for x in flat])
+        h = C.c_void_p()
+        check(lib().htkamd_regtree_from_tables(n, left, right, co, cm, cs, cx, C.byref(h)), "regtree_from_tables")
+        return cls(h)
+
+    @property
+    def num_nodes(self) -> int:
+        return lib().htkamd_regtree_num_nodes(self.h)
+
+    @property
+    def num_terminals(self) -> int:
+        return lib().htkamd_regtree_num_terminals(self.h)
+
+    def children(self, node: int):
+        """(left, right) of node `node` (from 1); (0, 0) for a terminal."""
+        a, b = C.c_int(0), C.c_int(0)
+        check(lib().htkamd_regtree_children(self.h, node, C.byref(a), C.byref(b)), "regtree_children")
+        return a.value, b.value
+
+    def terminal_node(self, base_class: int) -> int:
+        """The node of base class `base_class` (from 1); 0 when there is none."""
+        return lib().htkamd_regtree_terminal_node(self.h, base_class)
+
+    def components(self, node: int):
+        """[(physical model, state, mixture), ...] of a terminal node, in the order of the base class file."""
+        n = lib().htkamd_regtree_num_components(self.h, node)
+        if n < 0:
+            raise HtkAmdError("regtree_num_components failed: %s" % lib().htkamd_last_error().decode())
+        out = []
+        for i in range(n):
+            st, mx = C.c_int(0), C.c_int(0)
+            name = lib().htkamd_regtree_component(self.h, node, i, C.byref(st), C.byref(mx))
+            out.append((name.decode(), st.value, mx.value))
+        return out
+
+    def stats(self):
+        """(CalcDistance calls of every split in the order the splits were made, device time of the call's kernels in ms)."""
+        n = lib().htkamd_regtree_stats(self.h, None, 0, None)
+        it = (C.c_int * max(n, 1))(); ms = C.c_float(0.0)
+        lib().htkamd_regtree_stats(self.h, it, n, C.byref(ms))
+        return list(it[:n]), float(ms.value)
+
+    def write(self, identifier: str, out_dir=None):
+        check(lib().htkamd_regtree_write(self.h, str(identifier).encode(), str(out_dir).encode() if out_dir else None), "regtree_write")
+
+
 class ClusterSpec(C.Structure):
     _fields_ = [("byCount", C.c_int), ("value", C.c_float), ("macro", C.c_char_p), ("items", C.c_char_p)]
 
@@ -1354,6 +1419,16 @@ class Mmf(_Handle):
         msg = lib().htkamd_last_error().decode()
         self.last_warning = msg if "warning" in msg else None
         return nc[:len(specs)].tolist()
+
+    def regtree(self, occ, n_terminals: int, item_list=None, stream=None) -> "RegTree":
+        """HHEd's RC command on the loaded set (htkamd_mmf_regtree): `occ` the state occupations (read_stats), `item_list` the optional
+        list of non-speech states "{ sil.state[2-4].mix }".  The set is not changed; RegTree.write gives the two files."""
+        occ = np.ascontiguousarray(occ, np.float32)
+        if occ.shape != (self.desc.numStates,):
+            raise HtkAmdError("regtree: %s occupations for %d states" % (occ.shape, self.desc.numStates))
+        h = C.c_void_p()
+        check(lib().htkamd_mmf_regtree(self.h, _p(occ), int(n_terminals), str(item_list).encode() if item_list else None, C.byref(h), _stream(stream)), "mmf_regtree")
+        return RegTree(h)
 
     def tie(self, macro: str, items: str):
         """HHEd's TI command for .state[i] and .transP item lists (htkamd_mmf_tie); host only."""

@@ -71,6 +71,23 @@ typedef struct {
 } htkamd_dc_job;
 int  htkamd_dc_dev_run(const htkamd_dc_job *job, float *idistOut /* or NULL */, int *merges /*[2 * nItems]*/, int *nMerges /*[nCmds]*/, void *stream);
 
+/* ---- regression class trees: the device side (csrc/regtree.hip) as host/regtree.c drives it ----
+ * A member is one Gaussian of the scan: row m of mean / sum / sqr ([G][D]), occ[m], hasAcc[m] (0: no AccSum record, HHEd's hook == NULL).
+ * The member list starts as 0 .. G-1; a node is a range [off, off+n) of it, and a split leaves the left child's members in
+ * [off, off+nLeft) and the right child's behind them, both in the order they had.  A node's figures are 2D+2 floats: aveMean[D],
+ * aveCovar[D], clustAcc, clusterScore. */
+#define HTKAMD_RT_MAXDIM  960                          /* one lane per dimension and one for occupation and score, in one workgroup */
+#define HTKAMD_RT_MAXITER 500                          /* MAX_ITER (HHEd.c:61) */
+typedef struct htkamd_rt_dev htkamd_rt_dev;
+int  htkamd_rt_dev_open(htkamd_rt_dev **out, const float *mean, const float *sum, const float *sqr, const float *occ, const unsigned char *hasAcc,
+                        int G, int D, void *stream);
+int  htkamd_rt_dev_node(htkamd_rt_dev *t, int off, int n, float *node /*[2D+2]*/);
+int  htkamd_rt_dev_split(htkamd_rt_dev *t, int off, int n, const float *seeds /*[2][D]*/, int *counts /*nLeft, nRight, CalcDistance calls*/,
+                         float *nodes /*[2][2D+2]*/);
+int  htkamd_rt_dev_list(htkamd_rt_dev *t, int *list /*[G]*/);
+float htkamd_rt_dev_kernel_ms(const htkamd_rt_dev *t);
+void htkamd_rt_dev_close(htkamd_rt_dev *t);
+
 /* ---- unseen models from the trees: the device side (csrc/treesynth.hip) as host/treeclust.c drives it ----
  * Names and patterns are NUL-terminated strings in byte pools: name n at namePool + nameOff[n] (nameOff[N] = the pool's size), pattern k
  * at patPool + patOff[k], question q owns patterns qPat[q] .. qPat[q+1]-1.  The trees' node tables lie behind one another (tree t: nodes

@@ -1,6 +1,7 @@
 """HHEd edit scripts restricted to state clustering and tying: RO, LS, TR, QS, TB, ST (tree-based) and TC, NC, TI (data-driven), and -- for
 a caller that asks for them, parse_script(text, synth=True) -- LT, AU, CO: the unseen triphones from the trees and the compacted set
-(examples/tree_cluster.py, tools/tree_bench.py, tools/synth_bench.py).
+(examples/tree_cluster.py, tools/tree_bench.py, tools/synth_bench.py).  parse_script(text, regtree=True) takes RC as well: the regression
+class tree and its base classes (tools/regtree_bench.py).
 
     script = parse_script(open("tree.hed").read())
     run_script(mmf, script, stats_path)           # mmf: capi.Mmf; ties its states, writes script.trees_path if the script has an ST
@@ -15,6 +16,7 @@ from . import capi
 COMMANDS = ("RO", "TR", "QS", "TB", "ST", "TC", "NC", "TI", "LS")
 TREE_ONLY = ("RO", "TR", "QS", "TB", "ST")
 SYNTH = ("LT", "AU", "CO")
+_RC_ARGS = re.compile(r"""\s*([+-]?\d+)\s+("(?:\\.|[^"\\])*"|'(?:\\.|[^'\\])*'|\S+)(.*)$""")
 
 
 class Script:
@@ -26,7 +28,8 @@ class Script:
         self.trees_path = None       # ST's file name
         self.commands = []           # every command in script order: ("RO", threshold, file | None), ("LS", file), ("QS", name, patterns),
                                      # ("TB", threshold, macro, items), ("TC" | "NC", value, macro, items), ("TI", macro, items), ("ST", file),
-                                     # and with synth=True ("LT", file), ("AU", file), ("CO", file)
+                                     # and with synth=True ("LT", file), ("AU", file), ("CO", file); with regtree=True
+                                     # ("RC", terminals, identifier, item list | None)
 
 
 def _unquote(s: str) -> str:
@@ -43,9 +46,10 @@ def _item_list(rest: str, what: str):
     return rest[:a].strip(), rest[a:b + 1]
 
 
-def parse_script(text: str, synth: bool = False) -> Script:
+def parse_script(text: str, synth: bool = False, regtree: bool = False) -> Script:
     """One command per line, as HHEd scripts are written; the commands are kept in script order (Script.commands).  Any command but
-    RO, LS, TR, QS, TB, ST, TC, NC and TI is refused by name -- and with synth=True LT, AU and CO are taken, too."""
+    RO, LS, TR, QS, TB, ST, TC, NC and TI is refused by name -- and with synth=True LT, AU and CO are taken, too, with regtree=True
+    `RC N identifier [itemlist]`."""
     sc = Script()
     for raw in text.splitlines():
         line = raw.strip()
@@ -59,6 +63,17 @@ def parse_script(text: str, synth: bool = False) -> Script:
             if not rest.strip():
                 raise capi.HtkAmdError("%s: file name expected" % cmd)
             sc.commands.append((cmd, _unquote(rest)))
+            continue
+        if regtree and cmd == "RC":
+            m = _RC_ARGS.match(rest)      # the identifier as HHEd's ChkedAlpha reads a string: quoted (white space allowed inside) or up to white space
+            if not m:
+                raise capi.HtkAmdError("RC: number of terminal nodes and identifier expected in '%s'" % line)
+            n, ident, items = m.group(1), m.group(2), m.group(3).strip()
+            if not 0 <= int(n) <= 256:
+                raise capi.HtkAmdError("RC: maximum number of terminal nodes is 256, got %s" % n)
+            if items and not items.startswith("{"):
+                raise capi.HtkAmdError("RC: { item list } expected in '%s'" % items)
+            sc.commands.append(("RC", int(n), _unquote(ident), items or None))
             continue
         if cmd not in COMMANDS:
             raise capi.HtkAmdError("edit script: command %s is not supported (only %s: state clustering and tying)" % (cmd, ", ".join(COMMANDS)))
@@ -109,7 +124,8 @@ def run_script(mmf: "capi.Mmf", sc: Script, stats_path=None, merge: bool = True,
     A script of RO TR QS TB ST alone is one tree_cluster call.  Otherwise the commands run in script order, consecutive TC / NC commands
     as one device call and consecutive TB commands as another; returns the list of what the calls returned.  In a script with LT, AU or
     CO (parse_script(.., synth=True)) the trees stay on the set as in HHEd: AU after TB or LT uses them, ST writes all of them where it
-    stands; AU returns (seen, unseen), CO (logical, physical)."""
+    stands; AU returns (seen, unseen), CO (logical, physical).  RC (parse_script(.., regtree=True)) writes identifier.tree and
+    identifier.base under base_dir from the statistics loaded at that point and returns the capi.RegTree."""
     if all(c[0] in TREE_ONLY for c in sc.commands):
         if not sc.specs:
             raise capi.HtkAmdError("edit script: no TB command")
@@ -159,6 +175,12 @@ def run_script(mmf: "capi.Mmf", sc: Script, stats_path=None, merge: bool = True,
             continue
         elif c[0] == "TI":
             out.append(mmf.tie(c[1], c[2]))
+        elif c[0] == "RC":
+            if not loaded:
+                raise capi.HtkAmdError("edit script: no stats loaded (no RO or LS command names a statistics file before RC and none was given)")
+            tree = mmf.regtree(occupations(), c[1], c[3], stream=stream)
+            tree.write(c[2], base_dir)
+            out.append(tree)
         elif c[0] == "LT":
             mmf.load_trees(os.path.join(base_dir, c[1]))
         elif c[0] == "AU":

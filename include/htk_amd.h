@@ -268,6 +268,40 @@ int  htkamd_mmf_tie(htkamd_mmf *s, const char *macro, const char *items);
 int  htkamd_state_distances(htkamd_mmf *s, const char *items, float *dist /*[n][n] or NULL*/, int cap, int *n, void *stream);
 int  htkamd_cluster_merges(const float *idist, int N, const float *occ /*[N] or NULL*/, int numReq, float threshold, float outlierThresh,
                            int *merges /*[2(N-1)]*/, int *nMerges);
+/* Regression class trees as HHEd's RC command builds them (RegClassesCommand HHEd.c:6177): the two files every adaptation path of HTK
+   starts from, `<identifier>.tree` and `<identifier>.base`.  One-stream DIAGC sets with any number of mixture components.
+     mmf_regtree      : `occ` the state occupations of htkamd_stats_read_file (RC needs a loaded statistics file), `nTerminals` RC's number
+                        (0 .. 256), `itemList` RC's optional list of non-speech states "{ pat.state[i-j].mix }" (the only item form of
+                        type 'p' that a one-stream set has; NULL or "" = none): their Gaussians become node 2, the others node 3 under the
+                        root.  The Gaussians are taken in the order of InitRegTree's scan (:5734: models in the macro table's order, the
+                        unseen states of a model, their unseen mixture components), each with the AccSum record that InitTreeAccs (:2535)
+                        gives it -- none where the state has no occupation.  Every split (ClusterChildren :5961: the distances, the
+                        centroid sums in list order, the convergence loop, the stable partition, the children's distributions and scores)
+                        is one workgroup's work on the device (csrc/regtree.hip), bit for bit the reference's floats; which terminal to
+                        split next, the perturbed seeds and the node numbers are BuildRegClusters' (:6096) on the host.  The set itself is
+                        not changed.  Refused before a device is touched (HTKAMD_EINVAL / HTKAMD_EMODEL and the reason): sets with more than
+                        one stream, FULLC, tied-mixture and discrete sets; a vector size above 960; an item list that is not of that form.
+     regtree_from_tables : a tree from tables, for the writers alone: node i (1-based) has children left[i-1], right[i-1] (0, 0: a terminal);
+                        the terminals' components stand behind one another in node order, compOff[i-1] .. compOff[i] (nNodes + 1 offsets).
+     regtree_write    : PrintRegTree (:6010) into dir/<identifier>.tree and the base classes beside it (:6040) into dir/<identifier>.base
+                        (dir NULL: the working directory; <MMFIDMASK> is the reference's default "*").  `identifier` is a plain name.
+     accessors        : nodes are numbered from 1 as in the files; a terminal has children 0, 0; base class k (from 1) is terminal_node(k);
+                        component i of a terminal node is (physical model name, state, mixture).  regtree_stats: the CalcDistance calls
+                        of every split in the order the splits were made (at most `cap` are written; the return value is their number),
+                        and the device time of the call's kernels in ms. */
+typedef struct htkamd_regtree htkamd_regtree;
+int  htkamd_mmf_regtree(htkamd_mmf *s, const float *occ /*[numStates]*/, int nTerminals, const char *itemList /*may be NULL*/, htkamd_regtree **out, void *stream);
+int  htkamd_regtree_from_tables(int nNodes, const int *left, const int *right, const int *compOff /*[nNodes+1]*/, const char *const *compModel, const int *compState,
+                                const int *compMix, htkamd_regtree **out);
+int  htkamd_regtree_num_nodes(const htkamd_regtree *t);
+int  htkamd_regtree_children(const htkamd_regtree *t, int node, int *left, int *right);
+int  htkamd_regtree_num_terminals(const htkamd_regtree *t);
+int  htkamd_regtree_terminal_node(const htkamd_regtree *t, int baseClass);
+int  htkamd_regtree_num_components(const htkamd_regtree *t, int node);
+const char *htkamd_regtree_component(const htkamd_regtree *t, int node, int i, int *state, int *mix);      /* the physical model's name */
+int  htkamd_regtree_stats(const htkamd_regtree *t, int *iters /*[cap] or NULL*/, int cap, float *kernelMs /*or NULL*/);
+int  htkamd_regtree_write(const htkamd_regtree *t, const char *identifier, const char *dir /*may be NULL*/);
+void htkamd_regtree_destroy(htkamd_regtree *t);
 /* Unseen triphones from the trees and the compacted set: HHEd's LT / AU / CO commands (and ST for trees that were loaded).
    htkamd_mmf_tree_cluster leaves its trees on the holder, as HHEd's treeList and question list outlive TB: the kept questions with their
    patterns and per tree the base phone, the state number, the node table and the leaves' ~s macros.  Trees of further calls are added.
