@@ -1074,6 +1074,30 @@ class RegTree(_Handle):
         check(lib().htkamd_regtree_write(self.h, str(identifier).encode(), str(out_dir).encode() if out_dir else None), "regtree_write")
 
 
+def regtree_probe(mean, sum, sqr, occ, has, steps, stream=None):
+    """Test aid (htkamd_regtree_probe): the regression class tree's device steps over given members (mean, sum, sqr float32[G, D], occ
+    float32[G], has uint8[G]; the list starts as 0 .. G-1).  `steps` run in order on one device state, each ("node", off, n) or
+    ("split", off, n, seeds[2, D]).  Returns (results, list): per step float32[2D+2] for a node step, (counts int32[3] = members left,
+    right, CalcDistance calls, float32[2, 2D+2] = the two children) for a split; and the member list int32[G] as the last step left it."""
+    mean, sum, sqr = (np.ascontiguousarray(a, np.float32) for a in (mean, sum, sqr))
+    occ = np.ascontiguousarray(occ, np.float32); has = np.ascontiguousarray(has, np.uint8)
+    if mean.ndim != 2 or sum.shape != mean.shape or sqr.shape != mean.shape or occ.shape != mean.shape[:1] or has.shape != mean.shape[:1]:
+        raise HtkAmdError("regtree_probe: bad shapes %s %s %s %s %s" % (mean.shape, sum.shape, sqr.shape, occ.shape, has.shape))
+    G, D = mean.shape
+    nS = len(steps)
+    st = np.zeros((max(nS, 1), 3), np.int32); seeds = np.zeros((max(nS, 1), 2, D), np.float32)
+    for s, step in enumerate(steps):
+        if step[0] not in ("node", "split") or len(step) != (3 if step[0] == "node" else 4):
+            raise HtkAmdError("regtree_probe: step %d is %r" % (s, step[:3]))
+        st[s] = (step[0] == "split", step[1], step[2])
+        if step[0] == "split":
+            seeds[s] = np.asarray(step[3], np.float32).reshape(2, D)
+    counts = np.zeros((max(nS, 1), 3), np.int32); fig = np.zeros((max(nS, 1), 2, 2 * D + 2), np.float32); lst = np.zeros(max(G, 1), np.int32)
+    check(lib().htkamd_regtree_probe(_p(mean), _p(sum), _p(sqr), _p(occ), _p(has), G, D, _p(st), _p(seeds), nS, _p(counts), _p(fig), _p(lst),
+                                     _stream(stream)), "regtree_probe")
+    return [(counts[s].copy(), fig[s].copy()) if st[s, 0] else fig[s, 0].copy() for s in range(nS)], lst[:G]
+
+
 class ClusterSpec(C.Structure):
     _fields_ = [("byCount", C.c_int), ("value", C.c_float), ("macro", C.c_char_p), ("items", C.c_char_p)]
 

@@ -340,6 +340,29 @@ extern "C" int htkamd_rt_dev_list(htkamd_rt_dev *t, int *list)
 }
 #undef RT_HIP
 
+// Test aid: the device steps alone over a caller's member arrays, in order on one htkamd_rt_dev, so a later step sees the list as the
+// earlier splits left it.  Step s is steps[3s .. 3s+3) = (kind, off, n): kind 0 a node step (figures[s][0] is written), kind 1 a split
+// with the seeds seeds[s][2][D] (counts[s][3] and figures[s][2] are written).  What a step does not write stays as the caller left it.
+extern "C" int htkamd_regtree_probe(const float *mean, const float *sum, const float *sqr, const float *occ, const unsigned char *hasAcc, int G, int D,
+                                    const int *steps, const float *seeds, int nSteps, int *counts, float *figures, int *list, void *stream)
+{
+   if (!steps || !seeds || !counts || !figures || !list || nSteps < 0) { htkamd_set_error("regtree_probe: bad argument"); return HTKAMD_EINVAL; }
+   for (int s = 0; s < nSteps; s++)
+      if (steps[3 * s] != 0 && steps[3 * s] != 1) { htkamd_set_error("regtree_probe: step %d is of kind %d (0: node, 1: split)", s, steps[3 * s]); return HTKAMD_EINVAL; }
+   htkamd_rt_dev *t = nullptr;
+   int rc = htkamd_rt_dev_open(&t, mean, sum, sqr, occ, hasAcc, G, D, stream);
+   if (rc) return rc;
+   const size_t C = 2 * (size_t)D + 2;
+   for (int s = 0; s < nSteps && !rc; s++) {
+      const int off = steps[3 * s + 1], n = steps[3 * s + 2];
+      if (steps[3 * s]) rc = htkamd_rt_dev_split(t, off, n, seeds + (size_t)s * 2 * D, counts + 3 * (size_t)s, figures + (size_t)s * 2 * C);
+      else rc = htkamd_rt_dev_node(t, off, n, figures + (size_t)s * 2 * C);
+   }
+   if (!rc) rc = htkamd_rt_dev_list(t, list);
+   htkamd_rt_dev_close(t);
+   return rc;
+}
+
 extern "C" float htkamd_rt_dev_kernel_ms(const htkamd_rt_dev *t) { return t ? t->ms : 0.0f; }
 
 extern "C" void htkamd_rt_dev_close(htkamd_rt_dev *t)

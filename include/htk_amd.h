@@ -288,7 +288,15 @@ int  htkamd_cluster_merges(const float *idist, int N, const float *occ /*[N] or 
      accessors        : nodes are numbered from 1 as in the files; a terminal has children 0, 0; base class k (from 1) is terminal_node(k);
                         component i of a terminal node is (physical model name, state, mixture).  regtree_stats: the CalcDistance calls
                         of every split in the order the splits were made (at most `cap` are written; the return value is their number),
-                        and the device time of the call's kernels in ms. */
+                        and the device time of the call's kernels in ms.
+   Diagnostic entry point (a test aid, as htkamd_tree_split_sums is one):
+     regtree_probe    : the device steps of mmf_regtree alone over a caller's members: mean / sum / sqr rows, occupations and the flag
+                        "has an AccSum record" per member, the member list starting as 0 .. G-1.  steps[s] = (kind, off, n) run in order
+                        on one device state, so a later step sees the list as the earlier splits left it: kind 0 is
+                        CalcClusterDistribution and CalcNodeScore of the range (figures[s][0]: aveMean[D], aveCovar[D], clustAcc,
+                        clusterScore), kind 1 a ClusterChildren of it from seeds[s][2][D] (counts[s]: members left, right, CalcDistance
+                        calls; figures[s][0 .. 1]: the two children).  list[G]: the members as the last step left them.  Refused: a
+                        range outside the members, a split of no member, D above 960, any other kind. */
 typedef struct htkamd_regtree htkamd_regtree;
 int  htkamd_mmf_regtree(htkamd_mmf *s, const float *occ /*[numStates]*/, int nTerminals, const char *itemList /*may be NULL*/, htkamd_regtree **out, void *stream);
 int  htkamd_regtree_from_tables(int nNodes, const int *left, const int *right, const int *compOff /*[nNodes+1]*/, const char *const *compModel, const int *compState,
@@ -302,6 +310,9 @@ const char *htkamd_regtree_component(const htkamd_regtree *t, int node, int i, i
 int  htkamd_regtree_stats(const htkamd_regtree *t, int *iters /*[cap] or NULL*/, int cap, float *kernelMs /*or NULL*/);
 int  htkamd_regtree_write(const htkamd_regtree *t, const char *identifier, const char *dir /*may be NULL*/);
 void htkamd_regtree_destroy(htkamd_regtree *t);
+int  htkamd_regtree_probe(const float *mean /*[G][D]*/, const float *sum /*[G][D]*/, const float *sqr /*[G][D]*/, const float *occ /*[G]*/,
+                          const unsigned char *hasAcc /*[G]*/, int G, int D, const int *steps /*[nSteps][3]*/, const float *seeds /*[nSteps][2][D]*/,
+                          int nSteps, int *counts /*[nSteps][3]*/, float *figures /*[nSteps][2][2D+2]*/, int *list /*[G]*/, void *stream);
 /* Unseen triphones from the trees and the compacted set: HHEd's LT / AU / CO commands (and ST for trees that were loaded).
    htkamd_mmf_tree_cluster leaves its trees on the holder, as HHEd's treeList and question list outlive TB: the kept questions with their
    patterns and per tree the base phone, the state number, the node table and the leaves' ~s macros.  Trees of further calls are added.

@@ -54,6 +54,7 @@ def test_known_answers(native, table):
     assert table["htkamd_fb_mix_counts"] == (c_int, [c_void_p, c_void_p])                  # long long out[2]
     assert table["htkamd_model_get_prepared"] == (c_int, [c_void_p] * 5)                   # two lines, /*[n]*/ inside the list
     assert table["htkamd_version"] == (c_int, [])
+    assert table["htkamd_regtree_probe"] == (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4)      # three lines
     # the decoder set's entries, as its tests knew them when lib() declared them by hand
     assert table["htkamd_decoder_set_run"][1][4] is c_void_p and len(table["htkamd_decoder_set_run"][1]) == 9
     for s in ("htkamd_decoder_set_create", "htkamd_decoder_set_destroy", "htkamd_decoder_set_run", "htkamd_decoder_set_last_tied",

@@ -19,7 +19,7 @@ def declared_functions():
 def test_header_declares_the_path():
     names = declared_functions()
     for must in ("htkamd_model_create", "htkamd_outp_block", "htkamd_fb_prepare", "htkamd_fb_execute",
-                 "htkamd_accs_device_vector", "htkamd_model_update"):
+                 "htkamd_accs_device_vector", "htkamd_model_update", "htkamd_tree_split_sums", "htkamd_regtree_probe"):
         assert must in names
 
 

@@ -48,3 +48,17 @@ def test_live_sweep_against_hhed(tmp_path):
         t = ru.run_library(str(d), out)
         print("set %d: D=%d %dx%dx%d sil=%s -> %d nodes, iterations %s" % (k, D, H, S, M, sil, t.num_nodes, t.stats()[0]))
         _same_files(out, d)
+    # the shapes of tests/test_gpu_regtree_kernels.py end to end: more members than the workgroup has threads, the project's vector size,
+    # dimension lanes over two wavefronts, and zero occupations beside shared states and Gaussians.  Each has G > 3 D, so that a split happens.
+    for tag, H, S, M, D, n_term, more in (("g1120", 70, 4, 4, 3, 16, dict(clusters=4)), ("d39", 15, 3, 4, 39, 4, {}), ("d65", 15, 3, 6, 65, 4, dict(clusters=3)),
+                                          ("zt", 8, 3, 3, 4, 6, dict(occ_zero=((1, 0), (3, 2)), tied=True))):
+        d = tmp_path / tag
+        ru.write_set(str(d), ru.names_for(H), S, M, D, seed=300 + D, **more)
+        ru.write_script(str(d), n_term)
+        ru.run_hhed(str(d))
+        out = d / "lib"
+        out.mkdir()
+        t = ru.run_library(str(d), out)
+        print("set %s: D=%d %dx%dx%d -> %d nodes, iterations %s" % (tag, D, H, S, M, t.num_nodes, t.stats()[0]))
+        assert t.num_nodes >= 3
+        _same_files(out, d)

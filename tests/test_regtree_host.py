@@ -1,7 +1,9 @@
 """Regression class trees (HHEd RC), the host side: the edit-script parser, the refusals, the two writers and the order of the member
 list -- against HHEd's recorded files (tests/golden/regtree, tests/golden/make_regtree_golden.py).  No device is needed here."""
+import ctypes as C
 import os
 
+import numpy as np
 import pytest
 
 import regtree_util as ru
@@ -190,3 +192,30 @@ def test_member_order_against_the_golden_base(name, tmp_path):
         assert pos == sorted(pos)
     if items:
         assert classes[0] == t.components(2)
+
+
+# ------------------------------------------------------------------------------------------ the test aid over the device steps
+def test_probe_refuses_before_a_device_is_touched():
+    """capi.regtree_probe (htkamd_regtree_probe): a step of an unknown kind, a vector size above 960 and arrays that do not fit are
+    refused by name; without a device the call fails loudly, as every entry point does."""
+    z = lambda n, D: (np.zeros((n, D), np.float32),) * 3 + (np.zeros(n, np.float32), np.ones(n, np.uint8))
+    with pytest.raises(capi.HtkAmdError) as e:
+        capi.regtree_probe(*z(4, 3), [("merge", 0, 4)])
+    assert "step 0" in str(e.value)
+    steps = np.array([[2, 0, 4]], np.int32)
+    out = np.zeros(64, np.float32)
+    a = z(4, 3)
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    assert capi.lib().htkamd_regtree_probe(p(a[0]), p(a[1]), p(a[2]), p(a[3]), p(a[4]), 4, 3, p(steps), p(out), 1, p(steps.copy()), p(out), p(steps.copy()), None) == -1
+    assert b"kind 2" in capi.lib().htkamd_last_error()
+    assert capi.lib().htkamd_regtree_probe(p(a[0]), p(a[1]), p(a[2]), p(a[3]), p(a[4]), 4, 3, None, p(out), 0, None, p(out), None, None) == -1
+    with pytest.raises(capi.HtkAmdError) as e:
+        capi.regtree_probe(*z(2, 961), [("node", 0, 2)])
+    assert "bad argument" in str(e.value)
+    with pytest.raises(capi.HtkAmdError) as e:
+        capi.regtree_probe(np.zeros((4, 3)), np.zeros((4, 2)), np.zeros((4, 3)), np.zeros(4), np.ones(4), [])
+    assert "bad shapes" in str(e.value)
+    if capi.lib().htkamd_device_count() == 0:
+        with pytest.raises(capi.HtkAmdError) as e:
+            capi.regtree_probe(*z(4, 3), [("node", 0, 4)])
+        assert "no HIP device" in str(e.value)
