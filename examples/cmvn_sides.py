@@ -61,7 +61,7 @@ def main():
         print("warning: qualifier _Z not appropriate when calculating means", file=sys.stderr)
     if kind == fileKind:
         table = np.concatenate(stat)
-        frameOff = np.concatenate([[0], np.cumsum([x.shape[0] for x in stat])]).astype(np.int32)
+        frameOff = capi.offsets([x.shape[0] for x in stat])
         dX, cols = capi.DevArray(table), table.shape[1]
     else:
         dX, frameOff, cols = capi.parm_qualify(stat, capi.parm_quals_from_kind(kindStr, stat[0].shape[1]))

@@ -63,12 +63,11 @@ def main(argv=None):
     if need_d and not have_d:
         dX, frameOff, cols = capi.parm_add_qualifiers(stat, hasD=True, hasA=need_a)
     else:
-        X = np.ascontiguousarray(np.concatenate(stat), np.float32)
-        dX, cols = capi.DevArray(X), X.shape[1]
-        frameOff = np.concatenate([[0], np.cumsum([x.shape[0] for x in stat])]).astype(np.int32)
+        b = capi._Batch(stat, np.float32)      # the files as they are: one table on the device, and its offsets
+        dX, frameOff, cols = b.dev, b.off, b.host.shape[1]
     if cols != pk["vecSize"]:
         sys.exit("data have %d columns, the models %d" % (cols, pk["vecSize"]))
-    labOff = np.concatenate([[0], np.cumsum([len(q) for q in seqs])]).astype(np.int32)
+    labOff = capi.offsets([len(q) for q in seqs])
     fb, acc = capi.ForwardBackward(model), capi.Accs(model)
     fb.prepare(dX.ptr.value, frameOff, labOff, np.concatenate(seqs))
     pr = {}

@@ -152,7 +152,7 @@ def hinit(capi, mmf, name, tables, labels, max_iter=20, epsilon=1.0e-4, min_var=
     model = capi.Model(pk)
     model.set_params(mean=pk["mean"], var=pk["var"], compWeight=pk["compWeight"])
     X = np.ascontiguousarray(np.concatenate(segs), np.float32)
-    frameOff = np.concatenate([[0], np.cumsum([s.shape[0] for s in segs])]).astype(np.int32)
+    frameOff = capi.offsets([s.shape[0] for s in segs])
     labOff = np.arange(len(segs) + 1, dtype=np.int32)
     seq = np.full(len(segs), h, np.int32)
     dX = capi.DevArray(X)

@@ -35,7 +35,7 @@ def hrest(capi, mmf, name, tables, labels, max_iter=20, epsilon=1.0e-4, min_var=
         raise ValueError("HRest: only %d training tokens for %s (-m %d)" % (len(segs), name, min_seg))
     model = model or capi.Model(pk)
     X = np.ascontiguousarray(np.concatenate(segs), np.float32)
-    frameOff = np.concatenate([[0], np.cumsum([s.shape[0] for s in segs])]).astype(np.int32)
+    frameOff = capi.offsets([s.shape[0] for s in segs])
     labOff = np.arange(len(segs) + 1, dtype=np.int32)
     seq = np.full(len(segs), h, np.int32)
     dX = capi.DevArray(X)

@@ -86,9 +86,8 @@ def main(argv=None):
     if need_d and not kind & 0o400:
         dX, frame_off, cols = capi.parm_add_qualifiers(stat, hasD=True, hasA=need_a)
     else:
-        X = np.ascontiguousarray(np.concatenate(stat), np.float32)
-        dX, cols = capi.DevArray(X), X.shape[1]
-        frame_off = np.concatenate([[0], np.cumsum([x.shape[0] for x in stat])]).astype(np.int32)
+        b = capi._Batch(stat, np.float32)      # the files as they are: one table on the device, and its offsets
+        dX, frame_off, cols = b.dev, b.off, b.host.shape[1]
     if cols != pk["vecSize"]:
         sys.exit("data have %d columns, the models %d" % (cols, pk["vecSize"]))
     tokens = tokens_from_labels(pk, mmf.logical, frame_off, labels, seg_reject=False)      # (the call drops the short ones itself)

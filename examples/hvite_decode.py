@@ -43,11 +43,9 @@ def main(argv=None):
     al = None
     if args.models:
         chains = [np.array([m for w in (words or []) for m in net.pron_models[w[0]]], np.int32) for words, _ in res]
-        X = np.ascontiguousarray(np.concatenate(feats), np.float32)
-        frameOff = np.concatenate([[0], np.cumsum([x.shape[0] for x in feats])]).astype(np.int32)
-        labOff = np.concatenate([[0], np.cumsum([len(c) for c in chains])]).astype(np.int32)
-        dX = capi.DevArray(X)
-        al = capi.Viterbi(model).align(dX.ptr.value, frameOff, labOff, np.concatenate(chains) if len(chains) else np.zeros(0, np.int32), genBeam=args.beam)
+        b = capi._Batch(feats, np.float32)
+        labOff = capi.offsets([len(c) for c in chains])
+        al = capi.Viterbi(model).align(b.dev.ptr.value, b.off, labOff, np.concatenate(chains) if len(chains) else np.zeros(0, np.int32), genBeam=args.beam)
     with open(args.out, "w") as out:
         out.write("#!MLF!#\n")
         for u, (f, (words, total)) in enumerate(zip(args.data, res)):

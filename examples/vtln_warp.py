@@ -115,7 +115,7 @@ def main(argv=None):
     mmf.refuse_input_xform("vtln_warp")
     model = capi.Model(mmf.packed())
     seqs = [[mmf.logical[l.split()[-1]] for l in open(os.path.splitext(f)[0] + ".lab") if l.strip()] for f in files]
-    labOff = np.concatenate([[0], np.cumsum([len(q) for q in seqs])]).astype(np.int32)
+    labOff = capi.offsets([len(q) for q in seqs])
     labs = np.concatenate(seqs).astype(np.int32)
 
     best, _ = pick_warps(cfg, waves, speakers, model, labOff, labs, warps)

@@ -145,6 +145,35 @@ class DevArray:
             pass
 
 
+def offsets(lengths) -> np.ndarray:
+    """The int32 exclusive prefix sum of `lengths` -- frameOff, labOff, sampOff of a batch --, [0] for no lengths."""
+    return np.concatenate([[0], np.cumsum(lengths)]).astype(np.int32)
+
+
+def _pack(arrays, dtype, cols=None, who="batch"):
+    """(host, off): the arrays one behind the other as ONE C-contiguous `dtype` array, and offsets() of their lengths.  Every array has the
+    same shape behind its first axis: (cols,) where cols is given, else the first array's (vectors give a vector).  No array at all gives
+    [0, cols], or an empty vector.  An array of another shape is an HtkAmdError in `who`'s name."""
+    arrays = [np.asarray(a, dtype) for a in arrays]
+    tail = (cols,) if cols is not None else arrays[0].shape[1:] if arrays else ()
+    for u, a in enumerate(arrays):
+        if a.ndim == 0 or a.shape[1:] != tail:
+            raise HtkAmdError("%s: array %d of the batch has shape %s, %s expected" % (who, u, a.shape, ("n",) + tail))
+    host = np.concatenate(arrays) if arrays else np.zeros((0,) + tail, dtype)
+    return host, offsets([len(a) for a in arrays])
+
+
+class _Batch:
+    """A list of per-utterance arrays as the C ABI takes a batch: `host` and `off` (_pack), `n` arrays, and `dev`, the DevArray of `host`.
+    The empty batch: without a single row `dev` is still a device buffer, of 4 bytes, so no entry point is handed a null table.  The holder
+    owns all of them, and the C calls read `off` and `dev`: it lives until its call has returned and the results are unpacked."""
+
+    def __init__(self, arrays, dtype, cols=None, who="batch"):
+        self.host, self.off = _pack(arrays, dtype, cols, who)
+        self.n = len(self.off) - 1
+        self.dev = DevArray(self.host) if self.host.size else DevArray(nbytes=4)
+
+
 def _desc_from_packed(pk: dict):
     """(ModelDesc, keepalive) from a packed dict -- for the pure-host entry points that take a description."""
     f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
@@ -517,9 +546,20 @@ def mfcc_config(kind="MFCC_0_D_A", sampPeriod=625.0, winDur=250000.0, frPeriod=1
                       int("0" in q[1:]), int("E" in q[1:]), int("D" in q[1:]), int("A" in q[1:]), int("Z" in q[1:]), delWin, accWin)
 
 
-class Mfcc(_Handle):
+class _WaveCoder(_Handle):
+    """What Mfcc and FrontEnd share: a batch of waveforms on the device and the table its frames go to.  They differ in the symbols."""
+    _num_frames = None
+
+    def _upload(self, waves, tables=1):
+        """(batch of the int16 waveforms, DevArray for `tables` tables [sum frames, cols], frameOff for the call to fill, sum frames)"""
+        w = _Batch(waves, np.int16, who=type(self).__name__)
+        total = sum(int(getattr(lib(), self._num_frames)(C.byref(self.cfg), int(n))) for n in np.diff(w.off))
+        return w, DevArray(nbytes=4 * max(total, 1) * self.cols * tables), np.zeros(w.n + 1, np.int32), total
+
+
+class Mfcc(_WaveCoder):
     """htkamd_mfcc holder: waveform -> MFCC feature matrix on the device (HParm/HSigP front end)."""
-    _destroy = "htkamd_mfcc_destroy"
+    _destroy, _num_frames = "htkamd_mfcc_destroy", "htkamd_mfcc_num_frames"
 
     def __init__(self, cfg: MfccConfig):
         self.cfg = cfg
@@ -529,15 +569,8 @@ class Mfcc(_Handle):
 
     def compute(self, waves, stream=None):
         """waves: list of int16 arrays.  Returns (DevArray features [sumT, cols], frameOff)."""
-        waves = [np.ascontiguousarray(w, np.int16) for w in waves]
-        sampOff = np.concatenate([[0], np.cumsum([len(w) for w in waves])]).astype(np.int32)
-        allw = np.concatenate(waves) if waves else np.zeros(0, np.int16)
-        frames = [lib().htkamd_mfcc_num_frames(C.byref(self.cfg), len(w)) for w in waves]
-        total = int(sum(frames))
-        dW = DevArray(allw if len(allw) else np.zeros(1, np.int16))
-        dO = DevArray(nbytes=4 * max(total, 1) * self.cols)
-        frameOff = np.zeros(len(waves) + 1, np.int32)
-        check(lib().htkamd_mfcc_compute(self.h, dW.ptr, _p(sampOff), len(waves), _p(frameOff), dO.ptr, _stream(stream)), "mfcc_compute")
+        w, dO, frameOff, total = self._upload(waves)
+        check(lib().htkamd_mfcc_compute(self.h, w.dev.ptr, _p(w.off), w.n, _p(frameOff), dO.ptr, _stream(stream)), "mfcc_compute")
         assert frameOff[-1] == total
         return dO, frameOff
 
@@ -582,11 +615,11 @@ class Warp(C.Structure):
     _fields_ = [("warpFreq", C.c_float), ("warpLCutoff", C.c_float), ("warpUCutoff", C.c_float)]
 
 
-class FrontEnd(_Handle):
+class FrontEnd(_WaveCoder):
     """htkamd_frontend holder: waveform -> MFCC / FBANK / MELSPEC / PLP feature matrix on the device.
     warps: [(WARPFREQ, WARPLCUTOFF, WARPUCUTOFF), ...] (1..64) makes a front end with one filterbank per warp (VTLN): compute codes
     every utterance with the warp `warp_index` names for it, compute_grid every utterance under every warp."""
-    _destroy = "htkamd_frontend_destroy"
+    _destroy, _num_frames = "htkamd_frontend_destroy", "htkamd_frontend_num_frames"
 
     def __init__(self, cfg: FrontEndConfig, warps=None):
         self.cfg = cfg
@@ -599,29 +632,18 @@ class FrontEnd(_Handle):
             check(lib().htkamd_frontend_create_warped(C.byref(cfg), arr, len(warps), C.byref(self.h)), "frontend_create_warped")
         self.num_warps = lib().htkamd_frontend_num_warps(self.h)
 
-    def _upload(self, waves, tables=1):
-        waves = [np.ascontiguousarray(w, np.int16) for w in waves]
-        sampOff = np.concatenate([[0], np.cumsum([len(w) for w in waves])]).astype(np.int32)
-        allw = np.concatenate(waves) if waves else np.zeros(0, np.int16)
-        frames = [lib().htkamd_frontend_num_frames(C.byref(self.cfg), len(w)) for w in waves]
-        total = int(sum(frames))
-        dW = DevArray(allw if len(allw) else np.zeros(1, np.int16))
-        dO = DevArray(nbytes=4 * max(total, 1) * self.cols * tables)
-        return dW, dO, sampOff, np.zeros(len(waves) + 1, np.int32), total
-
     def compute(self, waves, warp_index=None, stream=None):
         """waves: list of int16 arrays; warp_index: the warp of every utterance (None: the first, or only, one for all).
         Returns (DevArray features [sumT, cols], frameOff)."""
-        dW, dO, sampOff, frameOff, total = self._upload(waves)
+        w, dO, frameOff, total = self._upload(waves)
         if warp_index is None:
-            check(lib().htkamd_frontend_compute(self.h, dW.ptr, _p(sampOff), len(waves), _p(frameOff), dO.ptr, _stream(stream)),
-                  "frontend_compute")
+            check(lib().htkamd_frontend_compute(self.h, w.dev.ptr, _p(w.off), w.n, _p(frameOff), dO.ptr, _stream(stream)), "frontend_compute")
         else:
             idx = np.ascontiguousarray(warp_index, np.int32)
-            if idx.shape != (len(waves),):
+            if idx.shape != (w.n,):
                 raise HtkAmdError("warp_index: one entry per utterance expected")
-            check(lib().htkamd_frontend_compute_warped(self.h, dW.ptr, _p(sampOff), len(waves), _p(idx), _p(frameOff), dO.ptr,
-                                                       _stream(stream)), "frontend_compute_warped")
+            check(lib().htkamd_frontend_compute_warped(self.h, w.dev.ptr, _p(w.off), w.n, _p(idx), _p(frameOff), dO.ptr, _stream(stream)),
+                  "frontend_compute_warped")
         assert frameOff[-1] == total
         return dO, frameOff
 
@@ -632,9 +654,8 @@ class FrontEnd(_Handle):
     def compute_grid(self, waves, stream=None):
         """Every utterance under every warp.  Returns (DevArray [num_warps, sumT, cols], frameOff): table w is what compute gives with
         every utterance on warp w."""
-        dW, dO, sampOff, frameOff, total = self._upload(waves, self.num_warps)
-        check(lib().htkamd_frontend_compute_grid(self.h, dW.ptr, _p(sampOff), len(waves), _p(frameOff), dO.ptr, _stream(stream)),
-              "frontend_compute_grid")
+        w, dO, frameOff, total = self._upload(waves, self.num_warps)
+        check(lib().htkamd_frontend_compute_grid(self.h, w.dev.ptr, _p(w.off), w.n, _p(frameOff), dO.ptr, _stream(stream)), "frontend_compute_grid")
         assert frameOff[-1] == total
         return dO, frameOff
 
@@ -711,18 +732,23 @@ def parm_write(path: str, X: np.ndarray, sampPeriod: int, kind: int, withCrc: bo
                                   int(withCrc)), "parm_write")
 
 
+def _stat_batch(who, stat_list, cols=None) -> _Batch:
+    """The statics of several utterances [T, cols] (cols None: the first one's) for a qualifier step.  No utterances, no table: refused."""
+    if len(stat_list) == 0:
+        raise HtkAmdError("%s: an empty list of utterances" % who)
+    return _Batch(stat_list, np.float32, np.atleast_1d(stat_list[0]).shape[-1] if cols is None else cols, who)
+
+
 def parm_add_qualifiers(stat_list, hasD=True, hasA=False, delWin=2, accWin=2) -> "DevArray":
     """Statics of several utterances -> device table with deltas/accelerations (AddQualifiers, HParm.c:1618).
     Returns (DevArray [sum T, cols], frameOff)."""
-    stat = np.ascontiguousarray(np.concatenate(stat_list), np.float32)
-    frameOff = np.concatenate([[0], np.cumsum([x.shape[0] for x in stat_list])]).astype(np.int32)
-    n = stat.shape[1]
+    b = _stat_batch("parm_add_qualifiers", stat_list)
+    T, n = b.host.shape
     cols = n * (1 + int(hasD) + int(hasA))
-    dIn = DevArray(stat)
-    dOut = DevArray(nbytes=4 * max(stat.shape[0] * cols, 1))
-    check(lib().htkamd_parm_add_qualifiers(dIn.ptr, _p(frameOff), len(stat_list), n, int(hasD), int(hasA),
+    dOut = DevArray(nbytes=4 * max(T * cols, 1))
+    check(lib().htkamd_parm_add_qualifiers(b.dev.ptr, _p(b.off), b.n, n, int(hasD), int(hasA),
                                            delWin, accWin, dOut.ptr, None), "parm_add_qualifiers")
-    return dOut, frameOff, cols
+    return dOut, b.off, cols
 
 
 def compv(dX_ptr, nFrames: int, D: int, minVar: float = 0.0):
@@ -754,14 +780,11 @@ def parm_quals_from_kind(kind: str, nStat: int, delWin=2, accWin=2, thirdWin=2, 
 
 def parm_qualify(stat_list, quals: ParmQuals):
     """htkamd_parm_qualify on the statics of several utterances. Returns (DevArray [sum T, cols], frameOff, cols)."""
-    stat = np.ascontiguousarray(np.concatenate(stat_list), np.float32)
-    frameOff = np.concatenate([[0], np.cumsum([x.shape[0] for x in stat_list])]).astype(np.int32)
-    assert stat.shape[1] == quals.nStat
+    b = _stat_batch("parm_qualify", stat_list, quals.nStat)
     cols = lib().htkamd_parm_quals_cols(C.byref(quals))
-    dIn = DevArray(stat)
-    dOut = DevArray(nbytes=4 * max(stat.shape[0] * cols, 1))
-    check(lib().htkamd_parm_qualify(dIn.ptr, _p(frameOff), len(stat_list), C.byref(quals), dOut.ptr, None), "parm_qualify")
-    return dOut, frameOff, cols
+    dOut = DevArray(nbytes=4 * max(b.host.shape[0] * cols, 1))
+    check(lib().htkamd_parm_qualify(b.dev.ptr, _p(b.off), b.n, C.byref(quals), dOut.ptr, None), "parm_qualify")
+    return dOut, b.off, cols
 
 
 def mask_match(mask: str, name: str):
@@ -904,14 +927,11 @@ class InputXForm:
     def apply(self, stat_list, quals: ParmQuals):
         """htkamd_inputxform_apply: the qualifier step of a transformed set on the statics of several utterances, in the reference's
         order.  Returns (DevArray [sum T, cols], frameOff, cols)."""
-        stat = np.ascontiguousarray(np.concatenate(stat_list), np.float32)
-        frameOff = np.concatenate([[0], np.cumsum([x.shape[0] for x in stat_list])]).astype(np.int32)
-        assert stat.shape[1] == quals.nStat
+        b = _stat_batch("InputXForm.apply", stat_list, quals.nStat)
         cols = lib().htkamd_inputxform_apply_cols(self.h, C.byref(quals))
-        dIn = DevArray(stat)
-        dOut = DevArray(nbytes=4 * max(stat.shape[0] * cols, 1))
-        check(lib().htkamd_inputxform_apply(self.h, dIn.ptr, _p(frameOff), len(stat_list), C.byref(quals), dOut.ptr, None), "inputxform_apply")
-        return dOut, frameOff, cols
+        dOut = DevArray(nbytes=4 * max(b.host.shape[0] * cols, 1))
+        check(lib().htkamd_inputxform_apply(self.h, b.dev.ptr, _p(b.off), b.n, C.byref(quals), dOut.ptr, None), "inputxform_apply")
+        return dOut, b.off, cols
 
     def close(self):
         if self.owned and self.h:
@@ -1148,13 +1168,33 @@ def _hinit_tokens(tokens):
     return [np.ascontiguousarray(t[:, k]) for k in range(3)]
 
 
+def _unit_train(sym, model, n_frames, tokens, cfg, models, run=None, extra=()):
+    """htkamd_<sym>_check on a packed description, and with run = (dX_ptr, stream) htkamd_<sym> itself -- HInit and HRest, one core on the C
+    side (csrc/unit_train.h) and here.  extra: the names of the int32 [models, maxIter] outputs behind logP.  Returns (model, results)."""
+    fr, ln, md = _hinit_tokens(tokens)
+    mo = np.ascontiguousarray(models, np.int32)
+    n = len(mo)
+    task = (int(n_frames), len(fr), _p(fr), _p(ln), _p(md), C.byref(cfg), n, _p(mo))
+    if not isinstance(model, Model):
+        d, keep = _desc_from_packed(model)
+        check(getattr(lib(), "htkamd_%s_check" % sym)(C.byref(d), *task), sym + "_check")
+        if run is None:
+            return None
+        model = Model(model)
+    n1, it = max(n, 1), max(cfg.maxIter, 1)
+    status, passes, conv = np.zeros(n1, np.int32), np.zeros(n1, np.int32), np.zeros(n1, np.int32)
+    logp = np.zeros((n1, it), np.float32)
+    more = {name: np.zeros((n1, it), np.int32) for name in extra}
+    check(getattr(lib(), "htkamd_" + sym)(model.h, _stream(run[0]), *task, _p(status), _p(passes), _p(conv), _p(logp), *[_p(a) for a in more.values()],
+                                          _stream(run[1])), sym)
+    return model, [dict(status=int(status[k]), passes=int(passes[k]), converged=bool(conv[k]), logP=[float(x) for x in logp[k, :passes[k]]],
+                        **{name: [int(x) for x in a[k, :passes[k]]] for name, a in more.items()}) for k in range(n)]
+
+
 def hinit_check(pk: dict, n_frames: int, tokens, cfg: HInitConfig, models):
     """Everything htkamd_hinit refuses before it touches a device, on a packed description (htkamd_hinit_check).  tokens: rows of
     (first frame, frames, physical model)."""
-    d, keep = _desc_from_packed(pk)
-    fr, ln, md = _hinit_tokens(tokens)
-    mo = np.ascontiguousarray(models, np.int32)
-    check(lib().htkamd_hinit_check(C.byref(d), int(n_frames), len(fr), _p(fr), _p(ln), _p(md), C.byref(cfg), len(mo), _p(mo)), "hinit_check")
+    _unit_train("hinit", pk, n_frames, tokens, cfg, models)
 
 
 def hinit(model, dX_ptr, n_frames: int, tokens, models, cfg: HInitConfig = None, stream=None):
@@ -1162,19 +1202,7 @@ def hinit(model, dX_ptr, n_frames: int, tokens, models, cfg: HInitConfig = None,
     description (checked first, then made a Model: the refusals need no device); tokens: rows of (first frame in the table, frames,
     physical model), the reference's order within each model.  Returns (model, results): results[k] for models[k] is a dict of status
     (HINIT_*), passes, converged and logP (the average log probability of every pass).  The estimates are in the model."""
-    cfg = cfg or hinit_config()
-    fr, ln, md = _hinit_tokens(tokens)
-    mo = np.ascontiguousarray(models, np.int32)
-    if not isinstance(model, Model):
-        hinit_check(model, n_frames, tokens, cfg, mo)
-        model = Model(model)
-    n = len(mo)
-    status = np.zeros(max(n, 1), np.int32); passes = np.zeros(max(n, 1), np.int32); conv = np.zeros(max(n, 1), np.int32)
-    logp = np.zeros((max(n, 1), max(cfg.maxIter, 1)), np.float32)
-    check(lib().htkamd_hinit(model.h, _stream(dX_ptr), int(n_frames), len(fr), _p(fr), _p(ln), _p(md), C.byref(cfg), n, _p(mo),
-                             _p(status), _p(passes), _p(conv), _p(logp), _stream(stream)), "hinit")
-    res = [dict(status=int(status[k]), passes=int(passes[k]), converged=bool(conv[k]), logP=[float(x) for x in logp[k, :passes[k]]]) for k in range(n)]
-    return model, res
+    return _unit_train("hinit", model, n_frames, tokens, cfg or hinit_config(), models, (dX_ptr, stream))
 
 
 def hinit_uniform_states(n_emit: int, tok_len) -> np.ndarray:
@@ -1189,13 +1217,11 @@ def flat_cluster(dX_ptr, n_rows: int, D: int, pools, nc, min_var: float = 0.0, s
     """FlatCluster (HTrain.c:763) of several pools in one launch (htkamd_flat_cluster).  pools: a list of row-number arrays into the
     device table dX [n_rows, D]; nc: clusters per pool.  Returns a list of dicts per pool: status, size [nc], centre / var [nc, D],
     assign [items] (a failed pool: status HINIT_ECLUSTER and nothing else)."""
-    pools = [np.ascontiguousarray(p, np.int32).reshape(-1) for p in pools]
     ncs = np.ascontiguousarray(nc, np.int32).reshape(-1)
     if len(ncs) != len(pools):
         raise HtkAmdError("flat_cluster: %d cluster counts for %d pools" % (len(ncs), len(pools)))
-    off = np.concatenate([[0], np.cumsum([len(p) for p in pools])]).astype(np.int32)
-    items = np.ascontiguousarray(np.concatenate(pools) if pools else np.zeros(0), np.int32)
-    if items.size == 0:
+    items, off = _pack([np.asarray(p).reshape(-1) for p in pools], np.int32, who="flat_cluster")
+    if items.size == 0:      # a host table, so no _Batch: non-null all the same
         items = np.zeros(1, np.int32)
     tot = max(int(np.clip(ncs, 0, None).sum()), 1)
     size = np.zeros(tot, np.int32); ctr = np.zeros((tot, D), np.float32); var = np.zeros((tot, D), np.float32)
@@ -1230,10 +1256,7 @@ def hrest_config(max_iter=20, epsilon=1.0e-4, min_var=0.0, min_seg=3, mix_weight
 def hrest_check(pk: dict, n_frames: int, tokens, cfg: HRestConfig, models):
     """Everything htkamd_hrest refuses before it touches a device, on a packed description (htkamd_hrest_check).  tokens: rows of
     (first frame, frames, physical model)."""
-    d, keep = _desc_from_packed(pk)
-    fr, ln, md = _hinit_tokens(tokens)
-    mo = np.ascontiguousarray(models, np.int32)
-    check(lib().htkamd_hrest_check(C.byref(d), int(n_frames), len(fr), _p(fr), _p(ln), _p(md), C.byref(cfg), len(mo), _p(mo)), "hrest_check")
+    _unit_train("hrest", pk, n_frames, tokens, cfg, models)
 
 
 def hrest_token_counts(pk: dict, tokens, cfg: HRestConfig, models):
@@ -1253,20 +1276,7 @@ def hrest(model, dX_ptr, n_frames: int, tokens, models, cfg: HRestConfig = None,
     packed description (checked first, then made a Model: the refusals need no device); tokens: rows of (first frame in the table,
     frames, physical model), the reference's order within each model.  Returns (model, results): results[k] for models[k] is a dict of
     status (HREST_*), passes, converged, logP ("Ave LogProb" of every pass) and used ("using N examples").  The estimates are in the model."""
-    cfg = cfg or hrest_config()
-    fr, ln, md = _hinit_tokens(tokens)
-    mo = np.ascontiguousarray(models, np.int32)
-    if not isinstance(model, Model):
-        hrest_check(model, n_frames, tokens, cfg, mo)
-        model = Model(model)
-    n = len(mo)
-    status = np.zeros(max(n, 1), np.int32); passes = np.zeros(max(n, 1), np.int32); conv = np.zeros(max(n, 1), np.int32)
-    logp = np.zeros((max(n, 1), max(cfg.maxIter, 1)), np.float32); used = np.zeros((max(n, 1), max(cfg.maxIter, 1)), np.int32)
-    check(lib().htkamd_hrest(model.h, _stream(dX_ptr), int(n_frames), len(fr), _p(fr), _p(ln), _p(md), C.byref(cfg), n, _p(mo),
-                             _p(status), _p(passes), _p(conv), _p(logp), _p(used), _stream(stream)), "hrest")
-    res = [dict(status=int(status[k]), passes=int(passes[k]), converged=bool(conv[k]), logP=[float(x) for x in logp[k, :passes[k]]],
-                used=[int(x) for x in used[k, :passes[k]]]) for k in range(n)]
-    return model, res
+    return _unit_train("hrest", model, n_frames, tokens, cfg or hrest_config(), models, (dX_ptr, stream), extra=("used",))
 
 
 class Mmf(_Handle):
@@ -1638,6 +1648,15 @@ class DecodeConfig(C.Structure):
                 ("scoreMode", C.c_int), ("maxActive", C.c_int)]
 
 
+# htkamd_decode_out's fields in order, with the type of the array each points to
+_DECODE_OUT = dict(nWords=np.int32, wordPron=np.int32, wordStart=np.int32, wordEnd=np.int32, wordScore=np.float32, wordLm=np.float32, wordAc=np.float32,
+                   wordLike=np.float64, total=np.float64, finalLm=np.float32)
+
+
+class DecodeOut(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _DECODE_OUT]
+
+
 class LatticeOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("nNodes", "nArcs", "nodeFrame", "nodePron", "nodeNet", "nodeLike", "arcStart", "arcEnd", "arcAc", "arcLm", "arcPr",
                                           "arcScore", "total")]
@@ -1719,17 +1738,14 @@ def lattice_nbest_align(lat: dict, net: "Net", mmf: "Mmf", N: int, states=False,
     return out
 
 
-class _LatticeRun:
+class _LatticeRun(_Batch):
     """The host side of one htkamd_decoder_run_lattice[_align] / htkamd_decoder_set_run_lattice[_align] call: the batch on the device, the
     output arrays and their per-utterance unpacking."""
 
-    def __init__(self, feats, D, maxNodes, maxArcs, align, maxAlign):
-        self.nU, self.maxNodes, self.maxArcs, self.align, self.maxAlign = len(feats), maxNodes, maxArcs, align, maxAlign
-        nU = self.nU
-        X = np.ascontiguousarray(np.concatenate(feats) if nU else np.zeros((0, D)), np.float32)
-        self.frameOff = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int32)
-        self.dX = DevArray(X) if X.size else DevArray(nbytes=4)
-        n1 = max(nU, 1)
+    def __init__(self, feats, D, maxNodes, maxArcs, align, maxAlign, who):
+        _Batch.__init__(self, feats, np.float32, D, who)
+        self.maxNodes, self.maxArcs, self.align, self.maxAlign = maxNodes, maxArcs, align, maxAlign
+        n1 = max(self.n, 1)
         self.nn = np.zeros(n1, np.int32); self.na = np.zeros(n1, np.int32); self.tot = np.zeros(n1, np.float64)
         self.nF = np.zeros(n1 * maxNodes, np.int32); self.nP = np.zeros_like(self.nF); self.nNet = np.zeros_like(self.nF); self.nL = np.zeros(n1 * maxNodes, np.float64)
         self.aS = np.zeros(n1 * maxArcs, np.int32); self.aE = np.zeros_like(self.aS); self.aAc = np.zeros(n1 * maxArcs, np.float32); self.aLm = np.zeros_like(self.aAc)
@@ -1744,7 +1760,7 @@ class _LatticeRun:
     def unpack(self, who, lmScale, wordPen, prScale):
         nn, na, maxNodes, maxArcs, maxAlign, align = self.nn, self.na, self.maxNodes, self.maxArcs, self.maxAlign, self.align
         res = []
-        for u in range(self.nU):
+        for u in range(self.n):
             if nn[u] == -1:
                 res.append(None); continue
             if nn[u] < 0:
@@ -1761,9 +1777,53 @@ class _LatticeRun:
         return res
 
 
-class Decoder(_Handle):
+class _Decoding(_Handle):
+    """What Decoder and DecoderSet share.  They differ in the symbols (_sym_out for the 1-best run, _prefix for the lattice runs) and in
+    net_of: None for a Decoder, whose entry points take no netOf argument."""
+
+    def _args(self, method, nU, net_of, genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, maxActive):
+        """(htkamd_decode_config, LM scale, [netOf array] or []) of one run; the refusals name the class and the method the user called."""
+        who = "%s.%s" % (type(self).__name__, method)
+        lmScale = self.lmScale if lmScale is None else float(lmScale)
+        if lmScale != self.lmScale:
+            raise HtkAmdError("%s: the LM scale is fixed at creation (LikeToWord look-ahead)" % who)
+        if net_of is not None and len(net_of) != nU:
+            raise HtkAmdError("%s: %d utterances, %d network indices" % (who, nU, len(net_of)))
+        netOf = [] if net_of is None else [np.ascontiguousarray(np.asarray(net_of, np.int64).astype(np.int32) if nU else np.zeros(1, np.int32))]
+        return DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive)), lmScale, netOf
+
+    def _run_out(self, feats, net_of, genBeam, wordBeam, lmScale, wordPen, prScale, maxWords, scoreMode, maxActive):
+        """htkamd_decoder_run_out / htkamd_decoder_set_run: every array of htkamd_decode_out, [nUtt] / [nUtt, maxWords]."""
+        cfg, _, netOf = self._args("run", len(feats), net_of, genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, maxActive)
+        b = _Batch(feats, np.float32, self.model.D, type(self).__name__ + ".run")
+        n1 = max(b.n, 1)
+        o = {n: np.zeros(n1 if n in ("nWords", "total", "finalLm") else (n1, maxWords), t) for n, t in _DECODE_OUT.items()}
+        out = DecodeOut(*[_p(a) for a in o.values()])
+        check(getattr(lib(), "htkamd_" + self._sym_out)(self.h, C.byref(cfg), b.dev.ptr, _p(b.off), *map(_p, netOf), b.n, maxWords, C.byref(out), None),
+              self._sym_out)
+        return {k: v[:b.n] for k, v in o.items()}
+
+    def _words(self, o):
+        """Sets last_lm and returns run()'s result from htkamd_decode_out's arrays: per utterance ([(pron, start, end, score), ...] or None, total)."""
+        nW = o["nWords"]
+        self.last_lm = [[float(o["wordLm"][u, i]) for i in range(max(int(nW[u]), 0))] for u in range(len(nW))]
+        return [(None if nW[u] < 0 else [(int(o["wordPron"][u, i]), int(o["wordStart"][u, i]), int(o["wordEnd"][u, i]), float(o["wordScore"][u, i]))
+                                         for i in range(nW[u])], float(o["total"][u])) for u in range(len(nW))]
+
+    def _run_lattice(self, feats, net_of, nToks, genBeam, wordBeam, nBeam, lmScale, wordPen, prScale, maxNodes, maxArcs, scoreMode, maxActive, align, maxAlign):
+        """htkamd_<_prefix>_run_lattice[_align]: per utterance the lattice as a dict of arrays, or None."""
+        cfg, lmScale, netOf = self._args("run_lattice", len(feats), net_of, genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, maxActive)
+        b = _LatticeRun(feats, self.model.D, maxNodes, maxArcs, align, maxAlign, type(self).__name__ + ".run_lattice")
+        sym = self._prefix + ("_run_lattice_align" if align else "_run_lattice")      # _align: HVite -n with -m (1) / -f (2), lAlign of every arc
+        mode, cap, alo = ([int(align)], [maxAlign], [C.byref(b.alo)]) if align else ([], [], [])      # ... and its three arguments more
+        check(getattr(lib(), "htkamd_" + sym)(self.h, C.byref(cfg), nToks, genBeam if nBeam is None else nBeam, *mode, b.dev.ptr, _p(b.off), *map(_p, netOf),
+                                              b.n, maxNodes, maxArcs, *cap, C.byref(b.out), *alo, None), sym)
+        return b.unpack(self._prefix + "_run_lattice", lmScale, wordPen, prScale)
+
+
+class Decoder(_Decoding):
     """htkamd_decoder holder: HVite -w (1-best word labels) for a batch of utterances on the device."""
-    _destroy = "htkamd_decoder_destroy"
+    _destroy, _sym_out, _prefix = "htkamd_decoder_destroy", "decoder_run_out", "decoder"
 
     def __init__(self, model: "Model", net: "Net", lmScale: float = 1.0):
         self.h = C.c_void_p()
@@ -1791,55 +1851,22 @@ class Decoder(_Handle):
 
     def run(self, feats, genBeam=1.0e10, wordBeam=1.0e10, lmScale=None, wordPen=0.0, prScale=1.0, maxWords=1024, scoreMode=0, maxActive=0):
         """feats: list of [T, D] arrays.  Returns per utterance (list of (pron, startFrame, endFrame, score) or None, total)."""
-        lmScale = self.lmScale if lmScale is None else float(lmScale)
-        if lmScale != self.lmScale:
-            raise HtkAmdError("Decoder.run: the LM scale is fixed at creation (LikeToWord look-ahead)")
-        nU = len(feats)
-        X = np.ascontiguousarray(np.concatenate(feats) if nU else np.zeros((0, self.model.D)), np.float32)
-        frameOff = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int32)
-        dX = DevArray(X) if X.size else DevArray(nbytes=4)
-        nW = np.zeros(max(nU, 1), np.int32); tot = np.zeros(max(nU, 1), np.float64)
-        wp = np.zeros(max(nU, 1) * maxWords, np.int32); ws = np.zeros_like(wp); we = np.zeros_like(wp); sc = np.zeros(max(nU, 1) * maxWords, np.float32)
-        lm = np.zeros_like(sc)
-        cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
-        check(lib().htkamd_decoder_run(self.h, C.byref(cfg), dX.ptr, _p(frameOff), nU, maxWords, _p(nW), _p(wp), _p(ws), _p(we),
-                                       _p(sc), _p(lm), _p(tot), None), "decoder_run")
-        self.last_lm = [[float(lm[u * maxWords + i]) for i in range(max(int(nW[u]), 0))] for u in range(nU)]
-        out = []
-        for u in range(nU):
-            if nW[u] < 0:
-                out.append((None, float(tot[u])))
-            else:
-                o = u * maxWords
-                out.append(([(int(wp[o + i]), int(ws[o + i]), int(we[o + i]), float(sc[o + i])) for i in range(nW[u])], float(tot[u])))
-        return out
+        return self._words(self._run_out(feats, None, genBeam, wordBeam, lmScale, wordPen, prScale, maxWords, scoreMode, maxActive))
+
+    def run_arrays(self, feats, genBeam=1.0e10, wordBeam=1.0e10, lmScale=None, wordPen=0.0, prScale=1.0, maxWords=1024, scoreMode=0, maxActive=0):
+        """Every output array of htkamd_decoder_run_out (htkamd_decode_out's fields, [nUtt] / [nUtt, maxWords])."""
+        return self._run_out(feats, None, genBeam, wordBeam, lmScale, wordPen, prScale, maxWords, scoreMode, maxActive)
 
     def run_lattice(self, feats, nToks, genBeam=1.0e10, wordBeam=1.0e10, nBeam=None, lmScale=None, wordPen=0.0, prScale=1.0, maxNodes=20000, maxArcs=80000, scoreMode=0, maxActive=0,
                     align=0, maxAlign=400000):
         """HVite -n nToks [-u maxActive]: per utterance the lattice as a dict of arrays (oracle.decode_nbest's fields + nodePron), or None."""
-        lmScale = self.lmScale if lmScale is None else float(lmScale)
-        if lmScale != self.lmScale:
-            raise HtkAmdError("Decoder.run_lattice: the LM scale is fixed at creation (LikeToWord look-ahead)")
-        b = _LatticeRun(feats, self.model.D, maxNodes, maxArcs, align, maxAlign)
-        cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
-        if align:                                            # HVite -n with -m (1) / -f (2): lAlign of every arc
-            check(lib().htkamd_decoder_run_lattice_align(self.h, C.byref(cfg), nToks, genBeam if nBeam is None else nBeam, int(align), b.dX.ptr,
-                                                         _p(b.frameOff), b.nU, maxNodes, maxArcs, maxAlign, C.byref(b.out), C.byref(b.alo), None),
-                  "decoder_run_lattice_align")
-        else:
-            check(lib().htkamd_decoder_run_lattice(self.h, C.byref(cfg), nToks, genBeam if nBeam is None else nBeam, b.dX.ptr, _p(b.frameOff), b.nU,
-                                                   maxNodes, maxArcs, C.byref(b.out), None), "decoder_run_lattice")
-        return b.unpack("decoder_run_lattice", lmScale, wordPen, prScale)
+        return self._run_lattice(feats, None, nToks, genBeam, wordBeam, nBeam, lmScale, wordPen, prScale, maxNodes, maxArcs, scoreMode, maxActive, align, maxAlign)
 
 
-class DecodeOut(C.Structure):
-    _fields_ = [(n, C.c_void_p) for n in ("nWords", "wordPron", "wordStart", "wordEnd", "wordScore", "wordLm", "wordAc", "wordLike", "total", "finalLm")]
-
-
-class DecoderSet(_Handle):
+class DecoderSet(_Decoding):
     """htkamd_decoder_set holder: a batch in which utterance u is decoded against nets[net_of[u]] -- HVite -a from word-level
     transcriptions, HVite -w with a lattice per file (DoAlignment, HVite.c:830) -- in one launch."""
-    _destroy = "htkamd_decoder_set_destroy"
+    _destroy, _sym_out, _prefix = "htkamd_decoder_set_destroy", "decoder_set_run", "decoder_set"
 
     def __init__(self, model: "Model", nets, lmScale: float = 1.0):
         self.h = C.c_void_p()
@@ -1855,57 +1882,20 @@ class DecoderSet(_Handle):
 
     def run_arrays(self, feats, net_of, genBeam=1.0e10, wordBeam=1.0e10, lmScale=None, wordPen=0.0, prScale=1.0, maxWords=1024, scoreMode=0, maxActive=0):
         """Every output array of htkamd_decoder_set_run (htkamd_decode_out's fields, [nUtt] / [nUtt, maxWords])."""
-        lmScale = self.lmScale if lmScale is None else float(lmScale)
-        if lmScale != self.lmScale:
-            raise HtkAmdError("DecoderSet.run: the LM scale is fixed at creation (LikeToWord look-ahead)")
-        nU = len(feats)
-        if len(net_of) != nU:
-            raise HtkAmdError("DecoderSet.run: %d utterances, %d network indices" % (nU, len(net_of)))
-        X = np.ascontiguousarray(np.concatenate(feats) if nU else np.zeros((0, self.model.D)), np.float32)
-        frameOff = np.concatenate([[0], np.cumsum([f.shape[0] for f in feats])]).astype(np.int32)
-        netOf = np.ascontiguousarray(np.asarray(net_of, np.int64).astype(np.int32) if nU else np.zeros(1, np.int32))
-        dX = DevArray(X) if X.size else DevArray(nbytes=4)
-        n1 = max(nU, 1)
-        o = dict(nWords=np.zeros(n1, np.int32), wordPron=np.zeros((n1, maxWords), np.int32), wordStart=np.zeros((n1, maxWords), np.int32),
-                 wordEnd=np.zeros((n1, maxWords), np.int32), wordScore=np.zeros((n1, maxWords), np.float32), wordLm=np.zeros((n1, maxWords), np.float32),
-                 wordAc=np.zeros((n1, maxWords), np.float32), wordLike=np.zeros((n1, maxWords), np.float64), total=np.zeros(n1, np.float64),
-                 finalLm=np.zeros(n1, np.float32))
-        out = DecodeOut(*[_p(o[n]) for n, _ in DecodeOut._fields_])
-        cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
-        check(lib().htkamd_decoder_set_run(self.h, C.byref(cfg), dX.ptr, _p(frameOff), _p(netOf), nU, maxWords, C.byref(out), None), "decoder_set_run")
-        return dict((k, v[:nU]) for k, v in o.items())
+        return self._run_out(feats, net_of, genBeam, wordBeam, lmScale, wordPen, prScale, maxWords, scoreMode, maxActive)
 
     def run(self, feats, net_of, **p):
         """feats: list of [T, D] arrays; net_of[u]: index into the set's networks.  Returns what Decoder.run returns per utterance -- (list of
         (pron, startFrame, endFrame, score) or None, total), pron indexing nets[net_of[u]] -- and sets last_lm and last_status."""
         o = self.run_arrays(feats, net_of, **p)
-        nW = o["nWords"]
-        self.last_status = [int(x) for x in nW]
-        self.last_lm = [[float(o["wordLm"][u, i]) for i in range(max(int(nW[u]), 0))] for u in range(len(feats))]
-        return [((None if nW[u] < 0 else [(int(o["wordPron"][u, i]), int(o["wordStart"][u, i]), int(o["wordEnd"][u, i]), float(o["wordScore"][u, i])) for i in range(nW[u])]),
-                 float(o["total"][u])) for u in range(len(feats))]
+        self.last_status = [int(x) for x in o["nWords"]]
+        return self._words(o)
 
     def run_lattice(self, feats, net_of, nToks, genBeam=1.0e10, wordBeam=1.0e10, nBeam=None, lmScale=None, wordPen=0.0, prScale=1.0, maxNodes=20000, maxArcs=80000,
                     scoreMode=0, maxActive=0, align=0, maxAlign=400000):
         """HVite -n nToks together with -a or a lattice per file: what Decoder.run_lattice returns per utterance, utterance u over
         nets[net_of[u]] (nodeNet / nodePron index that network) -- htkamd_decoder_set_run_lattice[_align], one launch for the batch."""
-        lmScale = self.lmScale if lmScale is None else float(lmScale)
-        if lmScale != self.lmScale:
-            raise HtkAmdError("DecoderSet.run_lattice: the LM scale is fixed at creation (LikeToWord look-ahead)")
-        if len(net_of) != len(feats):
-            raise HtkAmdError("DecoderSet.run_lattice: %d utterances, %d network indices" % (len(feats), len(net_of)))
-        b = _LatticeRun(feats, self.model.D, maxNodes, maxArcs, align, maxAlign)
-        netOf = np.ascontiguousarray(np.asarray(net_of, np.int64).astype(np.int32) if b.nU else np.zeros(1, np.int32))
-        cfg = DecodeConfig(genBeam, wordBeam, lmScale, wordPen, prScale, scoreMode, int(maxActive))
-        nB = genBeam if nBeam is None else nBeam
-        if align:
-            check(lib().htkamd_decoder_set_run_lattice_align(self.h, C.byref(cfg), nToks, nB, int(align), b.dX.ptr, _p(b.frameOff), _p(netOf), b.nU,
-                                                             maxNodes, maxArcs, maxAlign, C.byref(b.out), C.byref(b.alo), None),
-                  "decoder_set_run_lattice_align")
-        else:
-            check(lib().htkamd_decoder_set_run_lattice(self.h, C.byref(cfg), nToks, nB, b.dX.ptr, _p(b.frameOff), _p(netOf), b.nU, maxNodes,
-                                                       maxArcs, C.byref(b.out), None), "decoder_set_run_lattice")
-        return b.unpack("decoder_set_run_lattice", lmScale, wordPen, prScale)
+        return self._run_lattice(feats, net_of, nToks, genBeam, wordBeam, nBeam, lmScale, wordPen, prScale, maxNodes, maxArcs, scoreMode, maxActive, align, maxAlign)
 
 
 # ---- scoring recognition output (HResults): htkamd_results_* ----------------------------------------------------------------------
@@ -1993,7 +1983,7 @@ class Results(_Handle):
         flat = [np.asarray(h, np.int32).reshape(-1) for hs in hyps for h in hs]
         if len(flat) != K * U:
             raise HtkAmdError("Results.score: every set needs %d hypotheses" % U)
-        hypOff = np.concatenate([[0], np.cumsum([len(h) for h in flat])]).astype(np.int32)
+        hypOff = offsets([len(h) for h in flat])      # (the ids stay apart: a closing 0 keeps their host table non-empty)
         hypIds = np.ascontiguousarray(np.concatenate(flat + [np.zeros(1, np.int32)]), np.int32)
         uttRef = np.ascontiguousarray(np.asarray(list(utt_ref) + [0], np.int64).astype(np.int32))
         refLen = [int(lib().htkamd_results_ref_len(self.h, int(u))) for u in utt_ref]

@@ -16,8 +16,8 @@ def main():
         s = synth.generate_fast(1000, 8, 2000, nu, frames, seed=5, model_seed=3)
         model = capi.Model(s.packed())
         X = np.concatenate(s.feats)
-        frameOff = np.concatenate([[0], np.cumsum([f.shape[0] for f in s.feats])]).astype(np.int32)
-        labOff = np.concatenate([[0], np.cumsum([len(q) for q in s.seqs])]).astype(np.int32)
+        frameOff = capi.offsets([f.shape[0] for f in s.feats])
+        labOff = capi.offsets([len(q) for q in s.seqs])
         labs = np.concatenate(s.seqs).astype(np.int32)
         dX = capi.DevArray(X)
         vit = capi.Viterbi(model)

@@ -73,7 +73,7 @@ def main(argv=None):
         open(os.path.join(d, "list"), "w").write("\n".join(names) + "\n")
         mmf = capi.Mmf(hmm_list=os.path.join(d, "list"), hmm_dir=os.path.join(d, "proto"))
         pk = mmf.packed()
-        frame_off = np.concatenate([[0], np.cumsum([x.shape[0] for x in files])]).astype(np.int32)
+        frame_off = capi.offsets([x.shape[0] for x in files])
         dX = capi.DevArray(np.ascontiguousarray(np.concatenate(files)))
         tok = tokens_from_labels(pk, mmf.logical, frame_off, labels)
         cfg = capi.hinit_config(max_iter=a.maxiter)

@@ -41,7 +41,7 @@ def main(argv=None):
         for n in names:
             open(os.path.join(d, "proto", n), "w").write(proto_text(n, a.dim, a.states, a.mix))
         open(os.path.join(d, "list"), "w").write("\n".join(names) + "\n")
-        frame_off = np.concatenate([[0], np.cumsum([x.shape[0] for x in files])]).astype(np.int32)
+        frame_off = capi.offsets([x.shape[0] for x in files])
         dX = capi.DevArray(np.ascontiguousarray(np.concatenate(files)))
         proto = capi.Mmf(hmm_list=os.path.join(d, "list"), hmm_dir=os.path.join(d, "proto"))
         ppk = proto.packed()

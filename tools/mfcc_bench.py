@@ -25,7 +25,7 @@ def bench_warps(kind, K, waves, n, nU):
     L = capi.lib()
     fe = capi.FrontEnd(cfg, warps=[(float(a), 300.0, 3400.0) for a in np.linspace(0.88, 1.12, K)])
     plain = capi.FrontEnd(cfg)
-    sampOff = np.concatenate([[0], np.cumsum([len(w) for w in waves])]).astype(np.int32)
+    sampOff = capi.offsets([len(w) for w in waves])
     allw = np.concatenate(waves)
     frames = L.htkamd_frontend_num_frames(C.byref(cfg), C.c_int(n)) * nU
     dW = capi.DevArray(allw)
@@ -81,7 +81,7 @@ def main():
         fb = args.kind.upper().split("_")[0] in ("FBANK", "MELSPEC")
         cfg = capi.frontend_config(args.kind, numChans=40 if fb else 26, usePower=args.kind.upper().startswith("PLP"))
         fe, num_frames, compute = capi.FrontEnd(cfg), capi.lib().htkamd_frontend_num_frames, capi.lib().htkamd_frontend_compute
-    sampOff = np.concatenate([[0], np.cumsum([len(w) for w in waves])]).astype(np.int32)
+    sampOff = capi.offsets([len(w) for w in waves])
     allw = np.concatenate(waves)
     frames = num_frames(C.byref(cfg), C.c_int(n)) * nU
     dW = capi.DevArray(allw)

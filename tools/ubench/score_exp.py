@@ -10,8 +10,8 @@ s = synth.generate_fast(5000, 16, 6000, 1250, 500, seed=1000, model_seed=3)
 model = capi.Model(s.packed()); accs = capi.Accs(model); fb = capi.ForwardBackward(model)
 cfg = capi.fb_config(scoreMode=int(os.environ.get("SM", "6")))
 X = np.concatenate(s.feats)
-frameOff = np.concatenate([[0], np.cumsum([f.shape[0] for f in s.feats])]).astype(np.int32)
-labOff = np.concatenate([[0], np.cumsum([len(q) for q in s.seqs])]).astype(np.int32)
+frameOff = capi.offsets([f.shape[0] for f in s.feats])
+labOff = capi.offsets([len(q) for q in s.seqs])
 labs = np.concatenate(s.seqs).astype(np.int32)
 dX = capi.DevArray(X)
 kt = np.zeros(4)

@@ -52,7 +52,7 @@ def main():
     rng = np.random.default_rng(a.seed)
     utts = [synth_utt(pk, rng) for _ in range(a.utts)]
     X = np.concatenate([f for _, f in utts])
-    frameOff = np.concatenate([[0], np.cumsum([f.shape[0] for _, f in utts])]).astype(np.int32)
+    frameOff = capi.offsets([f.shape[0] for _, f in utts])
     dX = capi.DevArray(X)
     D = X.shape[1]
     dictp = os.path.join(SRC, "dict").encode()
