@@ -83,6 +83,14 @@ def build_tools(verbose: bool = False) -> None:
         if verbose:
             print(" ".join(cmd))
         subprocess.check_call(cmd)
+    # csrc/devbuf.h and csrc/hipcheck.h on their own (tests/test_devbuf.py runs it)
+    src, exe = os.path.join(root, "tests", "devbuf_selftest.hip"), os.path.join(bindir, "devbuf_selftest")
+    if os.path.exists(src) and _newer(exe, [src, LIB] + [os.path.join(HERE, "csrc", h) for h in ("devbuf.h", "hipcheck.h", "internal.h")]):
+        cmd = ["hipcc", "--offload-arch=" + ARCH, "-O1", "-std=c++17", "-Wall", "-I" + os.path.join(HERE, "csrc"), "-I" + os.path.join(root, "include"),
+               src, "-o", exe, "-L" + HERE, "-lhtk_amd", "-Wl,-rpath,$ORIGIN/../../htk_amd"]
+        if verbose:
+            print(" ".join(cmd))
+        subprocess.check_call(cmd)
 
 
 if __name__ == "__main__":

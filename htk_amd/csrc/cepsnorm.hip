@@ -15,6 +15,7 @@
 #include <vector>
 #include "internal.h"
 #include "hipcheck.h"
+#include "devbuf.h"
 
 #define SS_WAVES 4
 #define SS_LANES 64
@@ -82,14 +83,7 @@ static int check_batch(const char *who, const int *frameOff, const int *uttSide,
    return HTKAMD_OK;
 }
 
-namespace {
-struct DevBufs {                                         // device scratch of one call, released on every way out
-   void *p[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-   int n = 0;
-   template <typename T> hipError_t get(T **out, size_t count) { hipError_t e = hipMalloc((void **)out, sizeof(T) * (count ? count : 1)); if (e == hipSuccess) p[n++] = *out; return e; }
-   ~DevBufs() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
-};
-}
+DEVBUF_OWNER("cepsnorm")
 
 extern "C" int htkamd_side_stats(const float *dX, const int *frameOff, const int *uttSide, int nUtt, int nSide, int nCols, int D,
                                  double *sum, double *sqsum, long long *nFrames, void *stream)
@@ -107,14 +101,13 @@ extern "C" int htkamd_side_stats(const float *dX, const int *frameOff, const int
    for (int s = 0; s < nSide; s++) sideOff[s + 1] += sideOff[s];
    for (int u = 0; u < nUtt; u++) sideUtt[sideOff[uttSide[u]] + fill[uttSide[u]]++] = u;
    hipStream_t st = (hipStream_t)stream;
-   DevBufs b;
+   DevScratch b;
+   int rc;
    int *dOff = nullptr, *dSideOff = nullptr, *dSideUtt = nullptr;
    double *dPart = nullptr, *dOut = nullptr;
-   HIPCHECK(b.get(&dOff, (size_t)nUtt + 1));
-   HIPCHECK(b.get(&dSideOff, (size_t)nSide + 1));
-   HIPCHECK(b.get(&dSideUtt, (size_t)nUtt));
-   HIPCHECK(b.get(&dPart, (size_t)nUtt * 2 * D));
-   HIPCHECK(b.get(&dOut, (size_t)nSide * 2 * D));
+   if ((rc = b.get(&dOff, (size_t)nUtt + 1)) || (rc = b.get(&dSideOff, sideOff.size())) || (rc = b.get(&dSideUtt, sideUtt.size())) ||
+       (rc = b.get(&dPart, (size_t)nUtt * 2 * D)) || (rc = b.get(&dOut, (size_t)nSide * 2 * D)))
+      return rc;
    HIPCHECK(hipMemcpyAsync(dOff, frameOff, sizeof(int) * ((size_t)nUtt + 1), hipMemcpyHostToDevice, st));
    HIPCHECK(hipMemcpyAsync(dSideOff, sideOff.data(), sizeof(int) * sideOff.size(), hipMemcpyHostToDevice, st));
    HIPCHECK(hipMemcpyAsync(dSideUtt, sideUtt.data(), sizeof(int) * sideUtt.size(), hipMemcpyHostToDevice, st));
@@ -148,14 +141,13 @@ extern "C" int htkamd_parm_normalise(float *dX, const int *frameOff, const int *
    const int W = dMean > dScale ? dMean : dScale;
    if (F == 0 || W == 0) return HTKAMD_OK;
    hipStream_t st = (hipStream_t)stream;
-   DevBufs b;
+   DevScratch b;
+   int rc;
    int *dOff = nullptr, *dUttSide = nullptr, *dRowSide = nullptr;
    float *dMeanTab = nullptr, *dScaleTab = nullptr;
-   HIPCHECK(b.get(&dOff, (size_t)nUtt + 1));
-   HIPCHECK(b.get(&dUttSide, (size_t)nUtt));
-   HIPCHECK(b.get(&dRowSide, (size_t)F));
-   HIPCHECK(b.get(&dMeanTab, (size_t)nSide * dMean));
-   HIPCHECK(b.get(&dScaleTab, (size_t)nSide * dScale));
+   if ((rc = b.get(&dOff, (size_t)nUtt + 1)) || (rc = b.get(&dUttSide, (size_t)nUtt)) || (rc = b.get(&dRowSide, (size_t)F)) ||
+       (rc = b.get(&dMeanTab, (size_t)nSide * dMean)) || (rc = b.get(&dScaleTab, (size_t)nSide * dScale)))
+      return rc;
    HIPCHECK(hipMemcpyAsync(dOff, frameOff, sizeof(int) * ((size_t)nUtt + 1), hipMemcpyHostToDevice, st));
    HIPCHECK(hipMemcpyAsync(dUttSide, uttSide, sizeof(int) * (size_t)nUtt, hipMemcpyHostToDevice, st));
    if (dMean) HIPCHECK(hipMemcpyAsync(dMeanTab, mean, sizeof(float) * (size_t)nSide * dMean, hipMemcpyHostToDevice, st));

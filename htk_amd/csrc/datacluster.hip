@@ -200,10 +200,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_dc_merge(const DcCmd *cmds, floa
 }
 
 // ------------------------------------------------------------------------------------------ host side of the device
-namespace {
-constexpr char dcOwner[] = "data_cluster";
-typedef DevBufT<dcOwner> DevBuf;
-}
+DEVBUF_OWNER("data_cluster")
 
 extern "C" int htkamd_dc_dev_run(const htkamd_dc_job *job, float *idistOut, int *merges, int *nMerges, void *stream)
 {
@@ -229,22 +226,17 @@ extern "C" int htkamd_dc_dev_run(const htkamd_dc_job *job, float *idistOut, int 
    DevBuf dist, cmds, a, b, occ, chain, log, nlog, score, obs, sts;
    htkamd_model *model = nullptr;
    int *obsOff = nullptr; float *X = nullptr;
-   int rc = dist.reserve(sizeof(float) * (size_t)tot);
-   if (!rc) rc = cmds.reserve(sizeof(DcCmd) * (size_t)job->nCmds);
-#define DC_HIP(call) do { if (!rc) { hipError_t e_ = (call); if (e_ != hipSuccess) { htkamd_set_error("data_cluster: %s -> %s", #call, hipGetErrorString(e_)); rc = HTKAMD_EHIP; } } } while (0)
-   DC_HIP(hipMemcpyAsync(cmds.p, hc, sizeof(DcCmd) * (size_t)job->nCmds, hipMemcpyHostToDevice, st));
-   if (job->idist) DC_HIP(hipMemcpyAsync(dist.p, job->idist, sizeof(float) * (size_t)tot, hipMemcpyHostToDevice, st));
+   int rc = dist.reserve<float>((size_t)tot);
+   if (!rc) rc = cmds.upload(hc, (size_t)job->nCmds, st);
+   if (job->idist) { if (!rc) rc = dist.upload(job->idist, (size_t)tot, st); }
    else if (job->mean) {
-      const size_t bytes = sizeof(float) * (size_t)items * job->V;
-      if (!rc) rc = a.reserve(bytes);
-      if (!rc) rc = b.reserve(bytes);
-      DC_HIP(hipMemcpyAsync(a.p, job->mean, bytes, hipMemcpyHostToDevice, st));
-      DC_HIP(hipMemcpyAsync(b.p, job->var, bytes, hipMemcpyHostToDevice, st));
+      if (!rc) rc = a.upload(job->mean, (size_t)items * job->V, st);
+      if (!rc) rc = b.upload(job->var, (size_t)items * job->V, st);
       for (int k = 0; k < job->nCmds && !rc; k++) {
          const unsigned tiles = (unsigned)((hc[k].n + DC_TILE - 1) / DC_TILE);
-         hipLaunchKernelGGL(k_dc_divergence, dim3(tiles, tiles), dim3(DC_TILE, DC_TILE), 0, st, (const float *)a.p, (const float *)b.p, job->V, hc[k].off, hc[k].n,
-                            (float *)dist.p + hc[k].mat);
-         DC_HIP(hipGetLastError());
+         hipLaunchKernelGGL(k_dc_divergence, dim3(tiles, tiles), dim3(DC_TILE, DC_TILE), 0, st, a.as<const float>(), b.as<const float>(), job->V, hc[k].off, hc[k].n,
+                            dist.as<float>() + hc[k].mat);
+         HIPCHECK_RC(rc, devOwner, hipGetLastError());
       }
    } else {
       // GDistance: the observations are every component mean of every item, the states are the items
@@ -266,48 +258,45 @@ extern "C" int htkamd_dc_dev_run(const htkamd_dc_job *job, float *idistOut, int 
             for (int m = 0; m < obsOff[i + 1] - obsOff[i]; m++) memcpy(X + (size_t)(obsOff[i] + m) * D, d->mean + (size_t)d->compGauss[c0 + m] * D, sizeof(float) * (size_t)D);
          }
          for (int k = 0; k < job->nCmds; k++) { const int Tc = obsOff[hc[k].off + hc[k].n] - obsOff[hc[k].off]; if (Tc > maxT) maxT = Tc; }
-         rc = a.reserve(sizeof(float) * (size_t)(maxT ? maxT : 1) * D);
-         if (!rc) rc = obs.reserve(sizeof(int) * ((size_t)maxN + 1));
-         if (!rc) rc = sts.reserve(sizeof(int) * (size_t)items);
-         if (!rc) rc = score.reserve(sizeof(float) * (size_t)maxN * (maxT ? maxT : 1));
+         rc = a.reserve<float>((size_t)maxT * D);
+         if (!rc) rc = obs.reserve<int>((size_t)maxN + 1);
+         if (!rc) rc = sts.upload(job->itemState, (size_t)items, st);
+         if (!rc) rc = score.reserve<float>((size_t)maxN * maxT);
       }
-      DC_HIP(hipMemcpyAsync(sts.p, job->itemState, sizeof(int) * (size_t)items, hipMemcpyHostToDevice, st));
       for (int k = 0; k < job->nCmds && !rc; k++) {
          // the command's own offsets start at 0
          const int o0 = obsOff[hc[k].off], Tc = obsOff[hc[k].off + hc[k].n] - o0;
          int *rel = (int *)malloc(sizeof(int) * ((size_t)hc[k].n + 1));
          for (int i = 0; i <= hc[k].n; i++) rel[i] = obsOff[hc[k].off + i] - o0;
-         DC_HIP(hipMemcpyAsync(obs.p, rel, sizeof(int) * ((size_t)hc[k].n + 1), hipMemcpyHostToDevice, st));
-         DC_HIP(hipMemcpyAsync(a.p, X + (size_t)o0 * D, sizeof(float) * (size_t)Tc * D, hipMemcpyHostToDevice, st));
-         DC_HIP(hipStreamSynchronize(st));               // (rel goes; the observation and score buffers are one command's)
+         if (!rc) rc = obs.upload(rel, (size_t)hc[k].n + 1, st);
+         if (!rc) rc = a.upload(X + (size_t)o0 * D, (size_t)Tc * D, st);
+         HIPCHECK_RC(rc, devOwner, hipStreamSynchronize(st));               // (rel goes; the observation and score buffers are one command's)
          free(rel);
-         if (!rc) rc = htkamd_outp_block_mode(model, (const float *)a.p, Tc, (const int *)sts.p + hc[k].off, hc[k].n, (float *)score.p, Tc,
+         if (!rc) rc = htkamd_outp_block_mode(model, a.as<const float>(), Tc, sts.as<const int>() + hc[k].off, hc[k].n, score.as<float>(), Tc,
                                               HTKAMD_SCORE_SOUTP | HTKAMD_SCORE_DIAGC, st);
          if (rc) break;
          const unsigned tiles = (unsigned)((hc[k].n + DC_TILE - 1) / DC_TILE);
-         hipLaunchKernelGGL(k_dc_gdist, dim3(tiles, tiles), dim3(DC_TILE, DC_TILE), 0, st, (const float *)score.p, Tc, (const int *)obs.p, hc[k].n,
-                            (float *)dist.p + hc[k].mat);
-         DC_HIP(hipGetLastError());
-         DC_HIP(hipStreamSynchronize(st));
+         hipLaunchKernelGGL(k_dc_gdist, dim3(tiles, tiles), dim3(DC_TILE, DC_TILE), 0, st, score.as<const float>(), Tc, obs.as<const int>(), hc[k].n,
+                            dist.as<float>() + hc[k].mat);
+         HIPCHECK_RC(rc, devOwner, hipGetLastError());
+         HIPCHECK_RC(rc, devOwner, hipStreamSynchronize(st));
       }
    }
-   if (idistOut) DC_HIP(hipMemcpyAsync(idistOut, dist.p, sizeof(float) * (size_t)tot, hipMemcpyDeviceToHost, st));
+   if (idistOut && !rc) rc = dist.download(idistOut, (size_t)tot, st);
    if (!job->noMerge) {
-      if (!rc) rc = chain.reserve(sizeof(int) * 2 * (size_t)items);
-      if (!rc) rc = log.reserve(sizeof(int) * 2 * (size_t)items);
-      if (!rc) rc = nlog.reserve(sizeof(int) * (size_t)job->nCmds);
-      if (!rc && job->occ) rc = occ.reserve(sizeof(float) * (size_t)items);
-      if (job->occ) DC_HIP(hipMemcpyAsync(occ.p, job->occ, sizeof(float) * (size_t)items, hipMemcpyHostToDevice, st));
+      if (!rc) rc = chain.reserve<int>(2 * (size_t)items);
+      if (!rc) rc = log.reserve<int>(2 * (size_t)items);
+      if (!rc) rc = nlog.reserve<int>((size_t)job->nCmds);
+      if (!rc && job->occ) rc = occ.upload(job->occ, (size_t)items, st);
       if (!rc) {
-         hipLaunchKernelGGL(k_dc_merge, dim3((unsigned)job->nCmds), dim3(DC_THREADS), sizeof(int) * 5 * (size_t)maxN + sizeof(int), st, (const DcCmd *)cmds.p, (float *)dist.p,
-                            job->occ ? (const float *)occ.p : (const float *)nullptr, job->outlierThresh, (int *)chain.p, items, (int *)log.p, (int *)nlog.p);
-         DC_HIP(hipGetLastError());
+         hipLaunchKernelGGL(k_dc_merge, dim3((unsigned)job->nCmds), dim3(DC_THREADS), sizeof(int) * 5 * (size_t)maxN + sizeof(int), st, cmds.as<const DcCmd>(), dist.as<float>(),
+                            job->occ ? occ.as<const float>() : (const float *)nullptr, job->outlierThresh, chain.as<int>(), items, log.as<int>(), nlog.as<int>());
+         HIPCHECK_RC(rc, devOwner, hipGetLastError());
       }
-      DC_HIP(hipMemcpyAsync(merges, log.p, sizeof(int) * 2 * (size_t)items, hipMemcpyDeviceToHost, st));
-      DC_HIP(hipMemcpyAsync(nMerges, nlog.p, sizeof(int) * (size_t)job->nCmds, hipMemcpyDeviceToHost, st));
+      if (!rc) rc = log.download(merges, 2 * (size_t)items, st);
+      if (!rc) rc = nlog.download(nMerges, (size_t)job->nCmds, st);
    }
-   DC_HIP(hipStreamSynchronize(st));
-#undef DC_HIP
+   HIPCHECK_RC(rc, devOwner, hipStreamSynchronize(st));
    if (model) htkamd_model_destroy(model);
    free(hc); free(obsOff); free(X);
    return rc;

@@ -18,17 +18,18 @@
 #include <algorithm>
 #include "internal.h"
 #include "hipcheck.h"
+#include "devbuf.h"
 #include "kernels.h"
 #include "decode.h"
+
+DEVBUF_OWNER("decoder_set_create")
 
 struct htkamd_decoder_set {
    htkamd_model *m = nullptr;
    std::vector<DecNet> nets;           // absolute device pointers
    std::vector<int> ns, usedOff;       // per network: tied states it uses, its first entry in d_used
    int maxNs = 0;
-   char *d_tables = nullptr;           // every network's tables
-   DecNet *d_nets = nullptr;
-   int *d_used = nullptr;
+   DevBuf d_tables, d_nets, d_used;    // every network's tables (char), the records (DecNet), the slot table (int)
    std::vector<std::vector<int>> hostModel;     // per network: [nNodes] htkamd_net_desc.model (WORD nodes: the pronunciation)
    DecArena ws, wsN;                   // workspaces of htkamd_decoder_set_run and of htkamd_decoder_set_run_lattice, as htkamd_decoder's
    int orderMode = HTKAMD_ORDER_AUTO, lastTied = 0;
@@ -37,9 +38,6 @@ struct htkamd_decoder_set {
 extern "C" void htkamd_decoder_set_destroy(htkamd_decoder_set *d)
 {
    if (!d) return;
-   if (d->d_tables) (void)hipFree(d->d_tables);
-   if (d->d_nets) (void)hipFree(d->d_nets);
-   if (d->d_used) (void)hipFree(d->d_used);
    d->ws.release();
    d->wsN.release();
    delete d;
@@ -71,19 +69,16 @@ extern "C" int htkamd_decoder_set_create(htkamd_model *m, const htkamd_net_desc 
       d->maxNs = std::max(d->maxNs, d->ns[i]);
       used.insert(used.end(), us.begin(), us.end());
    }
-   hipError_t e;
-   if ((e = hipMalloc((void **)&d->d_tables, host.size() ? host.size() : 1)) != hipSuccess || (e = hipMalloc((void **)&d->d_nets, sizeof(DecNet) * nNets)) != hipSuccess ||
-       (e = hipMalloc((void **)&d->d_used, sizeof(int) * (used.size() ? used.size() : 1))) != hipSuccess) {
-      htkamd_set_error("decoder_set_create: hipMalloc: %s", hipGetErrorString(e)); htkamd_decoder_set_destroy(d);
-      return (e == hipErrorNoDevice || e == hipErrorInvalidDevice) ? HTKAMD_ENODEV : HTKAMD_ENOMEM;
+   int rc;
+   if ((rc = d->d_tables.reserve<char>(host.size())) || (rc = d->d_nets.reserve<DecNet>((size_t)nNets)) || (rc = d->d_used.reserve<int>(used.size()))) {
+      htkamd_decoder_set_destroy(d); return rc;
    }
-   for (const void **w : fix) *w = d->d_tables + ((size_t)*w - 1);
+   for (const void **w : fix) *w = d->d_tables.as<char>() + ((size_t)*w - 1);
    for (int i = 1; i < nNets; i++) d->nets[i].hmmState = d->nets[0].hmmState;
-   if ((e = hipMemcpy(d->d_tables, host.data(), host.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-       (e = hipMemcpy(d->d_nets, d->nets.data(), sizeof(DecNet) * nNets, hipMemcpyHostToDevice)) != hipSuccess ||
-       (e = hipMemcpy(d->d_used, used.data(), sizeof(int) * used.size(), hipMemcpyHostToDevice)) != hipSuccess) {
-      htkamd_set_error("decoder_set_create: %s", hipGetErrorString(e)); htkamd_decoder_set_destroy(d); return HTKAMD_EHIP;
-   }
+   HIPCHECK_RC(rc, devOwner, hipMemcpy(d->d_tables.p, host.data(), host.size(), hipMemcpyHostToDevice));
+   HIPCHECK_RC(rc, devOwner, hipMemcpy(d->d_nets.p, d->nets.data(), sizeof(DecNet) * nNets, hipMemcpyHostToDevice));
+   HIPCHECK_RC(rc, devOwner, hipMemcpy(d->d_used.p, used.data(), sizeof(int) * used.size(), hipMemcpyHostToDevice));
+   if (rc) { htkamd_decoder_set_destroy(d); return rc; }
    *out = d;
    return HTKAMD_OK;
 }
@@ -107,7 +102,7 @@ extern "C" int htkamd_decoder_set_run(htkamd_decoder_set *d, const htkamd_decode
    for (int u = 0; u < nUtt; u++)
       if (netOf[u] < 0 || netOf[u] >= nNets) { htkamd_set_error("decoder_set_run: utterance %d names network %d of %d", u, netOf[u], nNets); return HTKAMD_EINVAL; }
    const auto uttNet = [&](int u) { const int g = netOf[u]; return DecUttNet{&d->nets[g], g, d->ns[g], d->usedOff[g]}; };
-   const DecRun r = {"decoder_set_run", &d->ws, d->m, d->d_used, d->maxNs, uttNet, d->nets.data(), d->ns.data(), d->d_nets, htkamd_launch_decode_set,
+   const DecRun r = {"decoder_set_run", &d->ws, d->m, d->d_used.as<int>(), d->maxNs, uttNet, d->nets.data(), d->ns.data(), d->d_nets.as<DecNet>(), htkamd_launch_decode_set,
                      htkamd_decoder_order(d->orderMode), &d->lastTied, nullptr, nullptr, nullptr, nullptr};
    return htkamd_decoder_run_1best(r, cfg, dX, frameOff, nUtt, maxWords, out, (hipStream_t)stream);
 }
@@ -130,7 +125,7 @@ extern "C" int htkamd_decoder_set_run_lattice_align(htkamd_decoder_set *d, const
    for (int u = 0; u < nUtt; u++)
       if (netOf[u] < 0 || netOf[u] >= nNets) { htkamd_set_error("decoder_set_run_lattice: utterance %d names network %d of %d", u, netOf[u], nNets); return HTKAMD_EINVAL; }
    const auto uttNet = [&](int u) { const int g = netOf[u]; return DecUttNet{&d->nets[g], g, d->ns[g], d->usedOff[g]}; };
-   const DecNRun r = {"decoder_set_run_lattice", &d->wsN, d->m, d->d_used, d->maxNs, uttNet, d->nets.data(), d->ns.data(), d->d_nets, d->hostModel.data(),
+   const DecNRun r = {"decoder_set_run_lattice", &d->wsN, d->m, d->d_used.as<int>(), d->maxNs, uttNet, d->nets.data(), d->ns.data(), d->d_nets.as<DecNet>(), d->hostModel.data(),
                       htkamd_launch_decode_n_set, htkamd_decoder_order(d->orderMode), &d->lastTied};
    return htkamd_decoder_run_nbest(r, cfg, nToks, nBeam, dX, frameOff, nUtt, maxLatNodes, maxLatArcs, out, alignMode, maxAlign, alOut, (hipStream_t)stream);
 }

@@ -172,10 +172,7 @@ __global__ __launch_bounds__(HI_THREADS) void k_flat_cluster(FcArgs a)
    if (t == 0) a.status[p] = HTKAMD_HINIT_OK;
 }
 
-namespace {
-constexpr char hiOwner[] = "hinit";
-typedef DevBufT<hiOwner> DevBuf;
-}
+DEVBUF_OWNER("hinit")
 
 static size_t fc_lds_bytes(int nc, int D) { return sizeof(float) * (size_t)nc * D + (sizeof(float) + sizeof(int)) * (size_t)nc; }
 
@@ -200,26 +197,24 @@ extern "C" int htkamd_flat_cluster(const float *dX, int nRows, int D, int nPools
    hipStream_t s = (hipStream_t)stream;
    DevBuf dOff, dItems, dNc, dCOff, dSize, dCtr, dVar, dAssign, dCost, dStatus;
    int rc;
-   if ((rc = unit_upload(dOff, poolOff, (size_t)nPools + 1, s)) || (rc = unit_upload(dItems, items, (size_t)nItems, s)) || (rc = unit_upload(dNc, nc, (size_t)nPools, s)) ||
-       (rc = unit_upload(dCOff, cOff, s)) || (rc = dSize.reserve(sizeof(int) * (size_t)nClust)) || (rc = dCtr.reserve(sizeof(float) * (size_t)nClust * D)) ||
-       (rc = dVar.reserve(sizeof(float) * (size_t)nClust * D)) || (rc = dAssign.reserve(sizeof(int) * (size_t)(nItems ? nItems : 1))) ||
-       (rc = dCost.reserve(sizeof(float) * (size_t)(nItems ? nItems : 1))) || (rc = dStatus.reserve(sizeof(int) * (size_t)nPools)))
+   const size_t nI = (size_t)nItems, nCD = (size_t)nClust * D;
+   if ((rc = dOff.upload(poolOff, (size_t)nPools + 1, s)) || (rc = dItems.upload(items, nI, s)) || (rc = dNc.upload(nc, (size_t)nPools, s)) ||
+       (rc = dCOff.upload(cOff, s)) || (rc = dSize.reserve<int>((size_t)nClust)) || (rc = dCtr.reserve<float>(nCD)) || (rc = dVar.reserve<float>(nCD)) ||
+       (rc = dAssign.reserve<int>(nI)) || (rc = dCost.reserve<float>(nI)) || (rc = dStatus.reserve<int>((size_t)nPools)))
       return rc;
    HIPCHECK(hipMemsetAsync(dSize.p, 0, sizeof(int) * (size_t)nClust, s));
-   HIPCHECK(hipMemsetAsync(dCtr.p, 0, sizeof(float) * (size_t)nClust * D, s));
-   HIPCHECK(hipMemsetAsync(dVar.p, 0, sizeof(float) * (size_t)nClust * D, s));
-   HIPCHECK(hipMemsetAsync(dAssign.p, 0, sizeof(int) * (size_t)(nItems ? nItems : 1), s));
+   HIPCHECK(hipMemsetAsync(dCtr.p, 0, sizeof(float) * nCD, s));
+   HIPCHECK(hipMemsetAsync(dVar.p, 0, sizeof(float) * nCD, s));
+   HIPCHECK(hipMemsetAsync(dAssign.p, 0, sizeof(int) * (nI ? nI : 1), s));
    FcArgs a;
-   a.X = dX; a.D = D; a.poolOff = (const int *)dOff.p; a.items = (const int *)dItems.p; a.nc = (const int *)dNc.p; a.cOff = (const int *)dCOff.p;
-   a.minVar = minVar; a.size = (int *)dSize.p; a.centre = (float *)dCtr.p; a.var = (float *)dVar.p; a.assign = (int *)dAssign.p; a.cost = (float *)dCost.p;
-   a.status = (int *)dStatus.p;
+   a.X = dX; a.D = D; a.poolOff = dOff.as<const int>(); a.items = dItems.as<const int>(); a.nc = dNc.as<const int>(); a.cOff = dCOff.as<const int>();
+   a.minVar = minVar; a.size = dSize.as<int>(); a.centre = dCtr.as<float>(); a.var = dVar.as<float>(); a.assign = dAssign.as<int>(); a.cost = dCost.as<float>();
+   a.status = dStatus.as<int>();
    hipLaunchKernelGGL(k_flat_cluster, dim3((unsigned)nPools), dim3(HI_THREADS), fc_lds_bytes(maxNc, D), s, a);
    HIPCHECK(hipGetLastError());
-   HIPCHECK(hipMemcpyAsync(size, dSize.p, sizeof(int) * (size_t)nClust, hipMemcpyDeviceToHost, s));
-   HIPCHECK(hipMemcpyAsync(centre, dCtr.p, sizeof(float) * (size_t)nClust * D, hipMemcpyDeviceToHost, s));
-   HIPCHECK(hipMemcpyAsync(var, dVar.p, sizeof(float) * (size_t)nClust * D, hipMemcpyDeviceToHost, s));
-   if (nItems) HIPCHECK(hipMemcpyAsync(assign, dAssign.p, sizeof(int) * (size_t)nItems, hipMemcpyDeviceToHost, s));
-   HIPCHECK(hipMemcpyAsync(status, dStatus.p, sizeof(int) * (size_t)nPools, hipMemcpyDeviceToHost, s));
+   if ((rc = dSize.download(size, (size_t)nClust, s)) || (rc = dCtr.download(centre, nCD, s)) || (rc = dVar.download(var, nCD, s)) ||
+       (rc = dAssign.download(assign, nI, s)) || (rc = dStatus.download(status, (size_t)nPools, s)))
+      return rc;
    HIPCHECK(hipStreamSynchronize(s));
    return HTKAMD_OK;
 }
@@ -530,35 +525,34 @@ extern "C" int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int n
    DevBuf bMdl, bTokFrame, bTokLen, bTokMdl, bTokCnt, bTokPos, bPoolMdl, bPoolState, bPoolNc, bCOff, bPoolSize, bPoolOff, bItems, bMstatus;
    DevBuf bFcSize, bFcCtr, bFcVar, bFcAssign, bFcCost, bFcStatus, bBak, bXg, bUtt, bSeg, bRun, bUpd, bFrameComp, bAcc, bOut;
    const size_t nGD = (size_t)m->G * D, nTp = (size_t)m->h_transOff[m->nT], nOcc = (size_t)m->h_trOccOff[m->nT];
-   if ((rc = unit_upload(bMdl, mdl, s)) || (rc = unit_upload(bTokFrame, aFrame, s)) || (rc = unit_upload(bTokLen, aLen, s)) || (rc = unit_upload(bTokMdl, tb.aMdl, s)) ||
-       (rc = unit_upload(bPoolMdl, poolMdl, s)) || (rc = unit_upload(bPoolState, poolState, s)) || (rc = unit_upload(bPoolNc, poolNc, s)) || (rc = unit_upload(bCOff, cOff, s)) ||
-       (rc = bTokCnt.reserve(sizeof(int) * (size_t)nTok * maxNe)) || (rc = bTokPos.reserve(sizeof(int) * (size_t)nTok * maxNe)) ||
-       (rc = bPoolSize.reserve(sizeof(int) * (size_t)nPools)) || (rc = bPoolOff.reserve(sizeof(int) * ((size_t)nPools + 1))) ||
-       (rc = bItems.reserve(sizeof(int) * (size_t)totFrames)) || (rc = bMstatus.reserve(sizeof(int) * (size_t)nMdl)) ||
-       (rc = bXg.reserve(sizeof(float) * (size_t)totFrames * D)) || (rc = bFrameComp.reserve(sizeof(int) * (size_t)totFrames)) ||
-       (rc = bAcc.reserve(sizeof(double) * 2 * nGD + sizeof(int) * ((size_t)m->C + nTp + nOcc))) || (rc = bOut.reserve(8 * (size_t)nMdl)))
+   const size_t nF = (size_t)totFrames, nCD = (size_t)nClust * D, accBytes = sizeof(double) * 2 * nGD + sizeof(int) * ((size_t)m->C + nTp + nOcc);
+   if ((rc = bMdl.upload(mdl, s)) || (rc = bTokFrame.upload(aFrame, s)) || (rc = bTokLen.upload(aLen, s)) || (rc = bTokMdl.upload(tb.aMdl, s)) ||
+       (rc = bPoolMdl.upload(poolMdl, s)) || (rc = bPoolState.upload(poolState, s)) || (rc = bPoolNc.upload(poolNc, s)) || (rc = bCOff.upload(cOff, s)) ||
+       (rc = bTokCnt.reserve<int>((size_t)nTok * maxNe)) || (rc = bTokPos.reserve<int>((size_t)nTok * maxNe)) ||
+       (rc = bPoolSize.reserve<int>((size_t)nPools)) || (rc = bPoolOff.reserve<int>((size_t)nPools + 1)) ||
+       (rc = bItems.reserve<int>(nF)) || (rc = bMstatus.reserve<int>((size_t)nMdl)) || (rc = bXg.reserve<float>(nF * D)) || (rc = bFrameComp.reserve<int>(nF)) ||
+       (rc = bAcc.reserve(accBytes)) || (rc = bOut.reserve<float>(2 * (size_t)nMdl)))      // (bOut: a float and an int per model)
       return rc;
    HIPCHECK(hipMemsetAsync(bMstatus.p, 0, sizeof(int) * (size_t)nMdl, s));
    HiArgs a;
    memset(&a, 0, sizeof(a));
    if ((rc = unit_snapshot(m, bBak, s, &a.p))) return rc;
    a.uFlags = cfg->uFlags; a.minVar = cfg->minVar;
-   a.X = dX; a.mdl = (const UnitModel *)bMdl.p; a.nMdl = nMdl; a.maxNe = maxNe;
-   a.tokFrame = (const int *)bTokFrame.p; a.tokLen = (const int *)bTokLen.p; a.tokMdl = (const int *)bTokMdl.p; a.nTok = nTok;
-   a.tokCnt = (int *)bTokCnt.p; a.tokPos = (int *)bTokPos.p; a.poolMdl = (const int *)bPoolMdl.p; a.poolState = (const int *)bPoolState.p; a.nPools = nPools;
-   a.poolSize = (int *)bPoolSize.p; a.poolOff = (int *)bPoolOff.p; a.items = (int *)bItems.p; a.mstatus = (int *)bMstatus.p;
-   a.Xg = (float *)bXg.p; a.frameComp = (int *)bFrameComp.p;
-   a.accMu = (double *)bAcc.p; a.accVa = a.accMu + nGD; a.accCnt = (int *)(a.accVa + nGD); a.trCnt = a.accCnt + m->C; a.occCnt = a.trCnt + nTp;
-   a.logpOut = (float *)bOut.p; a.statOut = (int *)bOut.p + nMdl;
-   const size_t accBytes = sizeof(double) * 2 * nGD + sizeof(int) * ((size_t)m->C + nTp + nOcc);
+   a.X = dX; a.mdl = bMdl.as<const UnitModel>(); a.nMdl = nMdl; a.maxNe = maxNe;
+   a.tokFrame = bTokFrame.as<const int>(); a.tokLen = bTokLen.as<const int>(); a.tokMdl = bTokMdl.as<const int>(); a.nTok = nTok;
+   a.tokCnt = bTokCnt.as<int>(); a.tokPos = bTokPos.as<int>(); a.poolMdl = bPoolMdl.as<const int>(); a.poolState = bPoolState.as<const int>(); a.nPools = nPools;
+   a.poolSize = bPoolSize.as<int>(); a.poolOff = bPoolOff.as<int>(); a.items = bItems.as<int>(); a.mstatus = bMstatus.as<int>();
+   a.Xg = bXg.as<float>(); a.frameComp = bFrameComp.as<int>();
+   a.accMu = bAcc.as<double>(); a.accVa = a.accMu + nGD; a.accCnt = (int *)(a.accVa + nGD); a.trCnt = a.accCnt + m->C; a.occCnt = a.trCnt + nTp;
+   a.logpOut = bOut.as<float>(); a.statOut = bOut.as<int>() + nMdl;
    const unsigned tokBlocks = (unsigned)((nTok + HI_THREADS - 1) / HI_THREADS);
    std::vector<int> mstat((size_t)nMdl, 0);
 
    auto train = [&]() -> int {
       // ---- UniformSegment: pools, FlatCluster, the first parameters
       if (cfg->newModel) {
-         if ((rc = bFcSize.reserve(sizeof(int) * (size_t)nClust)) || (rc = bFcCtr.reserve(sizeof(float) * (size_t)nClust * D)) || (rc = bFcVar.reserve(sizeof(float) * (size_t)nClust * D)) ||
-             (rc = bFcAssign.reserve(sizeof(int) * (size_t)totFrames)) || (rc = bFcCost.reserve(sizeof(float) * (size_t)totFrames)) || (rc = bFcStatus.reserve(sizeof(int) * (size_t)nPools)))
+         if ((rc = bFcSize.reserve<int>((size_t)nClust)) || (rc = bFcCtr.reserve<float>(nCD)) || (rc = bFcVar.reserve<float>(nCD)) ||
+             (rc = bFcAssign.reserve<int>(nF)) || (rc = bFcCost.reserve<float>(nF)) || (rc = bFcStatus.reserve<int>((size_t)nPools)))
             return rc;
          hipLaunchKernelGGL(k_hi_count, dim3(tokBlocks), dim3(HI_THREADS), 0, s, a);
          hipLaunchKernelGGL(k_hi_scan, dim3((unsigned)nPools), dim3(HI_THREADS), 0, s, a);
@@ -566,17 +560,17 @@ extern "C" int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int n
          hipLaunchKernelGGL(k_hi_fill, dim3(tokBlocks), dim3(HI_THREADS), 0, s, a);
          HIPCHECK(hipGetLastError());
          FcArgs f;
-         f.X = dX; f.D = D; f.poolOff = a.poolOff; f.items = a.items; f.nc = (const int *)bPoolNc.p; f.cOff = (const int *)bCOff.p;
+         f.X = dX; f.D = D; f.poolOff = a.poolOff; f.items = a.items; f.nc = bPoolNc.as<const int>(); f.cOff = bCOff.as<const int>();
          // UniformSegment floors with vFloor (:592) where it copies, and only under UPVARS
-         f.minVar = cfg->minVar; f.size = (int *)bFcSize.p; f.centre = (float *)bFcCtr.p; f.var = (float *)bFcVar.p; f.assign = (int *)bFcAssign.p;
-         f.cost = (float *)bFcCost.p; f.status = (int *)bFcStatus.p;
+         f.minVar = cfg->minVar; f.size = bFcSize.as<int>(); f.centre = bFcCtr.as<float>(); f.var = bFcVar.as<float>(); f.assign = bFcAssign.as<int>();
+         f.cost = bFcCost.as<float>(); f.status = bFcStatus.as<int>();
          hipLaunchKernelGGL(k_flat_cluster, dim3((unsigned)nPools), dim3(HI_THREADS), fc_lds_bytes(maxNc, D), s, f);
          HIPCHECK(hipGetLastError());
          FcOut fo;
          fo.size = f.size; fo.centre = f.centre; fo.var = f.var; fo.status = f.status; fo.cOff = f.cOff;
          hipLaunchKernelGGL(k_hi_init, dim3((unsigned)nMdl), dim3(HI_THREADS), 0, s, a, fo);
          HIPCHECK(hipGetLastError());
-         HIPCHECK(hipMemcpyAsync(mstat.data(), bMstatus.p, sizeof(int) * (size_t)nMdl, hipMemcpyDeviceToHost, s));
+         if ((rc = bMstatus.download(mstat.data(), mstat.size(), s))) return rc;
          HIPCHECK(hipStreamSynchronize(s));
       }
 
@@ -605,15 +599,15 @@ extern "C" int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int n
             std::vector<int> pack;                          // one upload: uMdl, uFrame0, uSrc, uSeg0 | segUtt, segJ | running, runUtt0
             pack.insert(pack.end(), uMdl.begin(), uMdl.end()); pack.insert(pack.end(), uFrame0.begin(), uFrame0.end());
             pack.insert(pack.end(), uSrc.begin(), uSrc.end()); pack.insert(pack.end(), uSeg0.begin(), uSeg0.end());
-            if ((rc = unit_upload(bUtt, pack, s))) return rc;
-            a.uMdl = (const int *)bUtt.p; a.uFrame0 = a.uMdl + nU; a.uSrc = a.uFrame0 + nU + 1; a.uSeg0 = a.uSrc + nU;
+            if ((rc = bUtt.upload(pack, s))) return rc;
+            a.uMdl = bUtt.as<const int>(); a.uFrame0 = a.uMdl + nU; a.uSrc = a.uFrame0 + nU + 1; a.uSeg0 = a.uSrc + nU;
             a.nUtt = (int)nU; a.nFrames = uFrame0.back();
             pack.assign(segUtt.begin(), segUtt.end()); pack.insert(pack.end(), segJ.begin(), segJ.end());
-            if ((rc = unit_upload(bSeg, pack, s))) return rc;
-            a.segUtt = (const int *)bSeg.p; a.segJ = a.segUtt + segUtt.size(); a.nSeg = (int)segUtt.size();
+            if ((rc = bSeg.upload(pack, s))) return rc;
+            a.segUtt = bSeg.as<const int>(); a.segJ = a.segUtt + segUtt.size(); a.nSeg = (int)segUtt.size();
             pack.assign(running.begin(), running.end()); pack.insert(pack.end(), runUtt0.begin(), runUtt0.end());
-            if ((rc = unit_upload(bRun, pack, s))) return rc;
-            a.runMdl = (const int *)bRun.p; a.runUtt0 = a.runMdl + running.size(); a.nRun = (int)running.size();
+            if ((rc = bRun.upload(pack, s))) return rc;
+            a.runMdl = bRun.as<const int>(); a.runUtt0 = a.runMdl + running.size(); a.nRun = (int)running.size();
             hipLaunchKernelGGL(k_hi_gather, dim3((unsigned)nU), dim3(HI_THREADS), 0, s, a);
             HIPCHECK(hipGetLastError());
             HIPCHECK(hipStreamSynchronize(s));              // (pack goes)
@@ -628,7 +622,7 @@ extern "C" int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int n
          hipLaunchKernelGGL(k_hi_logp, dim3((unsigned)((a.nRun + 63) / 64)), dim3(64), 0, s, a);
          HIPCHECK(hipGetLastError());
          outHost.resize(2 * (size_t)nMdl);
-         HIPCHECK(hipMemcpyAsync(outHost.data(), bOut.p, 8 * (size_t)nMdl, hipMemcpyDeviceToHost, s));
+         if ((rc = bOut.download(outHost.data(), outHost.size(), s))) return rc;
          HIPCHECK(hipStreamSynchronize(s));
          const int *statHost = (const int *)(outHost.data() + nMdl);
          std::vector<int> next;
@@ -649,8 +643,8 @@ extern "C" int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int n
          if (!updList.empty()) {
             std::vector<int> pack(updFlag);
             pack.insert(pack.end(), updList.begin(), updList.end());
-            if ((rc = unit_upload(bUpd, pack, s))) return rc;
-            a.updFlag = (const int *)bUpd.p; a.updList = a.updFlag + nMdl; a.nUpd = (int)updList.size();
+            if ((rc = bUpd.upload(pack, s))) return rc;
+            a.updFlag = bUpd.as<const int>(); a.updList = a.updFlag + nMdl; a.nUpd = (int)updList.size();
             HIPCHECK(hipMemsetAsync(bAcc.p, 0, accBytes, s));
             hipLaunchKernelGGL(k_hi_best, dim3((unsigned)((a.nFrames + HI_THREADS - 1) / HI_THREADS)), dim3(HI_THREADS), 0, s, a);
             hipLaunchKernelGGL(k_hi_acc, dim3((unsigned)((a.nSeg + HI_THREADS / 64 - 1) / (HI_THREADS / 64))), dim3(HI_THREADS), 0, s, a);
@@ -662,7 +656,7 @@ extern "C" int htkamd_hinit(htkamd_model *m, const float *dX, int nFrames, int n
       }
 
       // ---- statuses raised by the last updates; the models that ended with one take back the parameters they came with
-      HIPCHECK(hipMemcpyAsync(mstat.data(), bMstatus.p, sizeof(int) * (size_t)nMdl, hipMemcpyDeviceToHost, s));
+      if ((rc = bMstatus.download(mstat.data(), mstat.size(), s))) return rc;
       HIPCHECK(hipStreamSynchronize(s));
       bool anyBad = false;
       for (int r = 0; r < nMdl; r++) if (mstat[r]) { status[mdlOf[r]] = mstat[r]; converged[mdlOf[r]] = 0; anyBad = true; }

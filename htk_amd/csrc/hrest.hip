@@ -200,10 +200,7 @@ __global__ __launch_bounds__(HR_THREADS) void k_hr_update(HrArgs a)
    for (int s = 0; s < m.ne; s++) htkamd_derive_state(a.p.g, a.p.hmmState[m.st0 + s], HR_THREADS);
 }
 
-namespace {
-constexpr char hrOwner[] = "hrest";
-typedef DevBufT<hrOwner> DevBuf;
-}
+DEVBUF_OWNER("hrest")
 
 extern "C" int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int nTokens, const int *tokFrame, const int *tokLen, const int *tokModel,
                             const htkamd_hrest_config *cfg, int nModels, const int *models,
@@ -245,21 +242,22 @@ extern "C" int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int n
    if ((rc = htkamd_fb_create(m, &fb)) || (rc = htkamd_accs_create(m, &accs)) || (rc = htkamd_accs_zero(accs, s))) return rc;
 
    DevBuf bMdl, bTokFrame, bTokLen, bTokMdl, bRunFlag, bUTok, bUFrame0, bMdlUtt0, bNUtt, bRun, bMstatus, bBak, bXg, bOut;
-   if ((rc = unit_upload(bMdl, mdl, s)) || (rc = unit_upload(bTokFrame, tb.aFrame, s)) || (rc = unit_upload(bTokLen, aLen, s)) || (rc = unit_upload(bTokMdl, tb.aMdl, s)) ||
-       (rc = bRunFlag.reserve(sizeof(int) * (size_t)nMdl)) || (rc = bUTok.reserve(sizeof(int) * (size_t)nTok)) || (rc = bUFrame0.reserve(sizeof(int) * ((size_t)nTok + 1))) ||
-       (rc = bMdlUtt0.reserve(sizeof(int) * (size_t)nMdl)) || (rc = bNUtt.reserve(2 * sizeof(int))) || (rc = bRun.reserve(sizeof(int) * (size_t)nMdl)) ||
-       (rc = bMstatus.reserve(sizeof(int) * (size_t)nMdl)) || (rc = bXg.reserve(sizeof(float) * (size_t)totFrames * D)) || (rc = bOut.reserve(sizeof(HrOut) * (size_t)nMdl)))
+   const size_t nM = (size_t)nMdl;
+   if ((rc = bMdl.upload(mdl, s)) || (rc = bTokFrame.upload(tb.aFrame, s)) || (rc = bTokLen.upload(aLen, s)) || (rc = bTokMdl.upload(tb.aMdl, s)) ||
+       (rc = bRunFlag.reserve<int>(nM)) || (rc = bUTok.reserve<int>((size_t)nTok)) || (rc = bUFrame0.reserve<int>((size_t)nTok + 1)) ||
+       (rc = bMdlUtt0.reserve<int>(nM)) || (rc = bNUtt.reserve<int>(2)) || (rc = bRun.reserve<int>(nM)) ||
+       (rc = bMstatus.reserve<int>(nM)) || (rc = bXg.reserve<float>((size_t)totFrames * D)) || (rc = bOut.reserve<HrOut>(nM)))
       return rc;
-   HIPCHECK(hipMemsetAsync(bMstatus.p, 0, sizeof(int) * (size_t)nMdl, s));
+   HIPCHECK(hipMemsetAsync(bMstatus.p, 0, sizeof(int) * nM, s));
    HrArgs a;
    memset(&a, 0, sizeof(a));
    if ((rc = unit_snapshot(m, bBak, s, &a.p))) return rc;      // the snapshot a failed model is put back to
    a.uFlags = cfg->uFlags; a.minVar = cfg->minVar; a.vDefunct = cfg->vDefunct; a.mixWeightFloor = cfg->mixWeightFloor;
    a.acc = accs->d_vec; a.lay = accs->lay;
-   a.X = dX; a.Xg = (float *)bXg.p; a.mdl = (const UnitModel *)bMdl.p; a.nMdl = nMdl;
-   a.tokFrame = (const int *)bTokFrame.p; a.tokLen = (const int *)bTokLen.p; a.tokMdl = (const int *)bTokMdl.p; a.nTok = nTok;
-   a.runFlag = (const int *)bRunFlag.p; a.uTok = (int *)bUTok.p; a.uFrame0 = (int *)bUFrame0.p; a.mdlUtt0 = (int *)bMdlUtt0.p; a.nUttOut = (int *)bNUtt.p;
-   a.runMdl = (const int *)bRun.p; a.mstatus = (int *)bMstatus.p; a.out = (HrOut *)bOut.p;
+   a.X = dX; a.Xg = bXg.as<float>(); a.mdl = bMdl.as<const UnitModel>(); a.nMdl = nMdl;
+   a.tokFrame = bTokFrame.as<const int>(); a.tokLen = bTokLen.as<const int>(); a.tokMdl = bTokMdl.as<const int>(); a.nTok = nTok;
+   a.runFlag = bRunFlag.as<const int>(); a.uTok = bUTok.as<int>(); a.uFrame0 = bUFrame0.as<int>(); a.mdlUtt0 = bMdlUtt0.as<int>(); a.nUttOut = bNUtt.as<int>();
+   a.runMdl = bRun.as<const int>(); a.mstatus = bMstatus.as<int>(); a.out = bOut.as<HrOut>();
 
    htkamd_fb_config fc;
    memset(&fc, 0, sizeof(fc));                              // HRest prunes nothing: no beam, and every state posterior counts
@@ -288,13 +286,13 @@ extern "C" int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int n
             const int nU = (int)labs.size();
             labOff.resize((size_t)nU + 1);
             for (int u = 0; u <= nU; u++) labOff[u] = u;
-            if ((rc = unit_upload(bRunFlag, runFlag, s)) || (rc = unit_upload(bRun, running, s))) return rc;
+            if ((rc = bRunFlag.upload(runFlag, s)) || (rc = bRun.upload(running, s))) return rc;
             a.nRun = nRun;
             hipLaunchKernelGGL(k_hr_compact, dim3(1), dim3(HR_THREADS), 0, s, a);
             hipLaunchKernelGGL(k_hr_gather, dim3((unsigned)nU), dim3(HR_THREADS), 0, s, a);
             HIPCHECK(hipGetLastError());
             int onDev[2];                                       // the two lists agree in utterances and frames, or the call ends
-            HIPCHECK(hipMemcpyAsync(onDev, bNUtt.p, sizeof(onDev), hipMemcpyDeviceToHost, s));
+            if ((rc = bNUtt.download(onDev, 2, s))) return rc;
             HIPCHECK(hipStreamSynchronize(s));
             if (onDev[0] != nU || onDev[1] != frameOff.back()) {
                htkamd_set_error("hrest: the device lists %d running tokens of %d frames, the host %d of %d", onDev[0], onDev[1], nU, frameOff.back());
@@ -314,7 +312,7 @@ extern "C" int htkamd_hrest(htkamd_model *m, const float *dX, int nFrames, int n
          hipLaunchKernelGGL(k_hr_logp, dim3((unsigned)((nRun + 63) / 64)), dim3(64), 0, s, a);
          hipLaunchKernelGGL(k_hr_update, dim3((unsigned)nRun), dim3(HR_THREADS), sizeof(int) * (size_t)maxM, s, a);
          HIPCHECK(hipGetLastError());
-         HIPCHECK(hipMemcpyAsync(out.data(), bOut.p, sizeof(HrOut) * (size_t)nRun, hipMemcpyDeviceToHost, s));
+         if ((rc = bOut.download(out.data(), (size_t)nRun, s))) return rc;
          HIPCHECK(hipStreamSynchronize(s));
          next.clear();
          for (int q = 0; q < nRun; q++) {

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 #include "internal.h"
 #include "hipcheck.h"
+#include "devbuf.h"
 
 // Product and sum are rounded separately: the project builds every file with -ffp-contract=off, and the two helpers are compiled under
 // a pragma that turns contraction off besides, which every mode that honours pragmas respects (off, on, fast-honor-pragmas -- hipcc's
@@ -119,14 +120,7 @@ extern "C" int htkamd_inputxform_apply_cols(const htkamd_inputxform *x, const ht
    return x->mrows * (1 + (q->hasD ? 1 : 0) + (q->hasA ? 1 : 0) + (q->hasT ? 1 : 0));
 }
 
-namespace {
-struct XfBufs {                                          // device scratch of one call, released on every way out
-   void *p[2] = {nullptr, nullptr};
-   int n = 0;
-   hipError_t get(float **out, size_t count) { hipError_t e = hipMalloc((void **)out, sizeof(float) * (count ? count : 1)); if (e == hipSuccess) p[n++] = *out; return e; }
-   ~XfBufs() { for (int i = 0; i < n; i++) (void)hipFree(p[i]); }
-};
-}
+DEVBUF_OWNER("inputxform_apply")
 
 extern "C" int htkamd_inputxform_apply(const htkamd_inputxform *x, const float *dStatic, const int *frameOff, int nUtt,
                                        const htkamd_parm_quals *q, float *dOut, void *stream)
@@ -142,20 +136,20 @@ extern "C" int htkamd_inputxform_apply(const htkamd_inputxform *x, const float *
    if (F == 0) return HTKAMD_OK;
    if (!dStatic || !dOut) { htkamd_set_error("inputxform_apply: NULL table"); return HTKAMD_EINVAL; }
    hipStream_t st = (hipStream_t)stream;
-   XfBufs b;
+   DevScratch b;
    float *dMat = nullptr, *dTmp = nullptr;
-   HIPCHECK(b.get(&dMat, (size_t)x->mrows * x->mcols));
-   HIPCHECK(hipMemcpyAsync(dMat, x->mat, sizeof(float) * (size_t)x->mrows * x->mcols, hipMemcpyHostToDevice, st));
    int rc;
+   if ((rc = b.get(&dMat, (size_t)x->mrows * x->mcols))) return rc;
+   HIPCHECK(hipMemcpyAsync(dMat, x->mat, sizeof(float) * (size_t)x->mrows * x->mcols, hipMemcpyHostToDevice, st));
    if (!x->preQual) {                                    // the qualifiers, then the transform over the whole row (HParm.c:1834-1843)
-      HIPCHECK(b.get(&dTmp, (size_t)F * qCols));
+      if ((rc = b.get(&dTmp, (size_t)F * qCols))) return rc;
       if ((rc = htkamd_parm_qualify(dStatic, frameOff, nUtt, q, dTmp, stream))) return rc;
       if ((rc = htkamd_parm_xform(dTmp, qCols, dOut, x->mrows, F, dMat, x->mrows, x->mcols, stream))) return rc;
    } else {                                              // the transform over the statics, then the qualifiers on mrows statics (HParm.c:1645-1652)
       htkamd_parm_quals q2 = *q;
       q2.nStat = x->mrows;
       q2.nZeroMean = q->nZeroMean > 0 ? x->mrows : 0;    // "No idea where the statics are so do everything" (HParm.c:1716-1720): base + C0 + energy = every static
-      HIPCHECK(b.get(&dTmp, (size_t)F * x->mrows));
+      if ((rc = b.get(&dTmp, (size_t)F * x->mrows))) return rc;
       if ((rc = htkamd_parm_xform(dStatic, q->nStat, dTmp, x->mrows, F, dMat, x->mrows, x->mcols, stream))) return rc;
       if ((rc = htkamd_parm_qualify(dTmp, frameOff, nUtt, &q2, dOut, stream))) return rc;
    }

@@ -21,8 +21,7 @@
 #include "devbuf.h"
 #include "latrescore.h"
 
-static constexpr char lat_owner[] = "latset";
-typedef DevBufT<lat_owner> DevBuf;
+DEVBUF_OWNER("latset")
 
 #define LAT_TILE      64          // nodes of a lattice whose scores a lane keeps in LDS
 #define LAT_MAXBLOCKS 4096
@@ -163,8 +162,7 @@ __global__ __launch_bounds__(64) void k_lat_prune(LatDev D, const double *fw, co
 
 struct LatBufs {
    DevBuf desc, rank, arcStart, arcEnd, fwd, bwd, ac, lm, pr, nullEnd, scales, score, back, nPath, status, path, totals, fw, bw, best, thresh, aps, keepNode, keepArc;
-   hipEvent_t ev[2] = {nullptr, nullptr};
-   ~LatBufs() { for (int k = 0; k < 2; k++) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+   KernelTimer timer;
 };
 static void lat_dev_free(void *dev) { delete (LatBufs *)dev; }
 
@@ -181,7 +179,6 @@ static int lat_upload(htkamd_latset *s, int K, const htkamd_lat_scales *scales, 
    if (htkamd_device_count() <= 0) { htkamd_set_error("%s: no HIP device", what); return HTKAMD_ENODEV; }
    if (!s->dev) { s->dev = new LatBufs(); s->devFree = lat_dev_free; }
    LatBufs &B = *(LatBufs *)s->dev;
-   for (int k = 0; k < 2; k++) if (!B.ev[k]) HIPCHECK(hipEventCreate(&B.ev[k]));
    const int U = s->nLats;
    const size_t TA = (size_t)s->totalArcs;
    int rc;
@@ -203,31 +200,30 @@ static int lat_upload(htkamd_latset *s, int K, const htkamd_lat_scales *scales, 
          no += l.nn; ao += l.na; rank[(size_t)u] = u;
       }
       std::stable_sort(rank.begin(), rank.end(), [&](int a, int b) { return s->lat[a].na > s->lat[b].na; });
-      if ((rc = B.desc.reserve(sizeof(LatDesc) * (size_t)U)) || (rc = B.rank.reserve(sizeof(int) * (size_t)U)) || (rc = B.arcStart.reserve(sizeof(int) * (TA + 1))) ||
-          (rc = B.arcEnd.reserve(sizeof(int) * (TA + 1))) || (rc = B.fwd.reserve(sizeof(int) * (TA + 1))) || (rc = B.bwd.reserve(sizeof(int) * (TA + 1))) ||
-          (rc = B.ac.reserve(sizeof(float) * (TA + 1))) || (rc = B.lm.reserve(sizeof(float) * (TA + 1))) || (rc = B.pr.reserve(sizeof(float) * (TA + 1))) || (rc = B.nullEnd.reserve(TA + 1)))
+      if ((rc = B.desc.upload(desc, st)) || (rc = B.rank.upload(rank, st)) || (rc = B.arcStart.upload(aS, st)) || (rc = B.arcEnd.upload(aE, st)) ||
+          (rc = B.fwd.upload(fwd, st)) || (rc = B.bwd.upload(bwd, st)) || (rc = B.ac.upload(ac, st)) || (rc = B.lm.upload(lm, st)) || (rc = B.pr.upload(pr, st)) ||
+          (rc = B.nullEnd.upload(ne, st)))
          return rc;
-      HIPCHECK(hipMemcpyAsync(B.desc.p, desc.data(), sizeof(LatDesc) * (size_t)U, hipMemcpyHostToDevice, st));
-      HIPCHECK(hipMemcpyAsync(B.rank.p, rank.data(), sizeof(int) * (size_t)U, hipMemcpyHostToDevice, st));
-      HIPCHECK(hipMemcpyAsync(B.arcStart.p, aS.data(), sizeof(int) * (TA + 1), hipMemcpyHostToDevice, st));
-      HIPCHECK(hipMemcpyAsync(B.arcEnd.p, aE.data(), sizeof(int) * (TA + 1), hipMemcpyHostToDevice, st));
-      HIPCHECK(hipMemcpyAsync(B.fwd.p, fwd.data(), sizeof(int) * (TA + 1), hipMemcpyHostToDevice, st));
-      HIPCHECK(hipMemcpyAsync(B.bwd.p, bwd.data(), sizeof(int) * (TA + 1), hipMemcpyHostToDevice, st));
-      HIPCHECK(hipMemcpyAsync(B.ac.p, ac.data(), sizeof(float) * (TA + 1), hipMemcpyHostToDevice, st));
-      HIPCHECK(hipMemcpyAsync(B.lm.p, lm.data(), sizeof(float) * (TA + 1), hipMemcpyHostToDevice, st));
-      HIPCHECK(hipMemcpyAsync(B.pr.p, pr.data(), sizeof(float) * (TA + 1), hipMemcpyHostToDevice, st));
-      HIPCHECK(hipMemcpyAsync(B.nullEnd.p, ne.data(), TA + 1, hipMemcpyHostToDevice, st));
       HIPCHECK(hipStreamSynchronize(st));                     // (the vectors go out of scope)
       s->latsOnDevice = U;
    }
-   if ((rc = B.scales.reserve(sizeof(htkamd_lat_scales) * (size_t)K))) return rc;
-   HIPCHECK(hipMemcpyAsync(B.scales.p, scales, sizeof(htkamd_lat_scales) * (size_t)K, hipMemcpyHostToDevice, st));
-   D.lat = (const LatDesc *)B.desc.p; D.rank = (const int *)B.rank.p;
-   D.arcStart = (const int *)B.arcStart.p; D.arcEnd = (const int *)B.arcEnd.p; D.fwd = (const int *)B.fwd.p; D.bwd = (const int *)B.bwd.p;
-   D.ac = (const float *)B.ac.p; D.lm = (const float *)B.lm.p; D.pr = (const float *)B.pr.p; D.nullEnd = (const unsigned char *)B.nullEnd.p;
+   if ((rc = B.scales.upload(scales, (size_t)K, st))) return rc;
+   D.lat = B.desc.as<const LatDesc>(); D.rank = B.rank.as<const int>();
+   D.arcStart = B.arcStart.as<const int>(); D.arcEnd = B.arcEnd.as<const int>(); D.fwd = B.fwd.as<const int>(); D.bwd = B.bwd.as<const int>();
+   D.ac = B.ac.as<const float>(); D.lm = B.lm.as<const float>(); D.pr = B.pr.as<const float>(); D.nullEnd = B.nullEnd.as<const unsigned char>();
    D.U = U; D.K = K; D.totalNodes = s->totalNodes; D.totalArcs = s->totalArcs;
-   D.scales = (const htkamd_lat_scales *)B.scales.p;
+   D.scales = B.scales.as<const htkamd_lat_scales>();
    s->kernelMs = 0.0;
+   return HTKAMD_OK;
+}
+
+// the end of a timed call: its copies are over and its kernel time is the set's
+static int lat_finish(htkamd_latset *s, hipStream_t st)
+{
+   float ms = 0.0f;
+   HIPCHECK(hipStreamSynchronize(st));
+   HIPCHECK(((LatBufs *)s->dev)->timer.ms(&ms));
+   s->kernelMs = ms;
    return HTKAMD_OK;
 }
 
@@ -248,22 +244,17 @@ extern "C" int htkamd_latset_best(htkamd_latset *s, int K, const htkamd_lat_scal
    const size_t KN = (size_t)K * (size_t)s->totalNodes, P = (size_t)K * (size_t)s->nLats;
    bool big = false;
    for (int u = 0; u < s->nLats && !big; u++) big = s->lat[u].nn > LAT_TILE;
-   if (big && ((rc = B.score.reserve(sizeof(double) * KN)) || (rc = B.back.reserve(sizeof(int) * KN)))) return rc;
-   if ((rc = B.nPath.reserve(sizeof(int) * P)) || (rc = B.status.reserve(sizeof(int) * P)) || (rc = B.path.reserve(sizeof(int) * KN)) || (rc = B.totals.reserve(sizeof(double) * 4 * P))) return rc;
-   HIPCHECK(hipEventRecord(B.ev[0], st));
-   hipLaunchKernelGGL(k_lat_best, dim3(lat_blocks(s, K)), dim3(64), 0, st, D, big ? (double *)B.score.p : nullptr, big ? (int *)B.back.p : nullptr, (int *)B.nPath.p,
-                      (int *)B.status.p, (int *)B.path.p, (double *)B.totals.p);
+   if (big && ((rc = B.score.reserve<double>(KN)) || (rc = B.back.reserve<int>(KN)))) return rc;
+   if ((rc = B.nPath.reserve<int>(P)) || (rc = B.status.reserve<int>(P)) || (rc = B.path.reserve<int>(KN)) || (rc = B.totals.reserve<double>(4 * P))) return rc;
+   HIPCHECK(B.timer.start(st));
+   hipLaunchKernelGGL(k_lat_best, dim3(lat_blocks(s, K)), dim3(64), 0, st, D, big ? B.score.as<double>() : nullptr, big ? B.back.as<int>() : nullptr, B.nPath.as<int>(),
+                      B.status.as<int>(), B.path.as<int>(), B.totals.as<double>());
    HIPCHECK(hipGetLastError());
-   HIPCHECK(hipEventRecord(B.ev[1], st));
-   HIPCHECK(hipMemcpyAsync(out->nPath, B.nPath.p, sizeof(int) * P, hipMemcpyDeviceToHost, st));
-   HIPCHECK(hipMemcpyAsync(out->status, B.status.p, sizeof(int) * P, hipMemcpyDeviceToHost, st));
-   HIPCHECK(hipMemcpyAsync(out->pathArcs, B.path.p, sizeof(int) * KN, hipMemcpyDeviceToHost, st));
-   HIPCHECK(hipMemcpyAsync(out->totals, B.totals.p, sizeof(double) * 4 * P, hipMemcpyDeviceToHost, st));
-   HIPCHECK(hipStreamSynchronize(st));
-   float ms = 0.0f;
-   HIPCHECK(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
-   s->kernelMs = ms;
-   return HTKAMD_OK;
+   HIPCHECK(B.timer.stop(st));
+   if ((rc = B.nPath.download(out->nPath, P, st)) || (rc = B.status.download(out->status, P, st)) || (rc = B.path.download(out->pathArcs, KN, st)) ||
+       (rc = B.totals.download(out->totals, 4 * P, st)))
+      return rc;
+   return lat_finish(s, st);
 }
 
 // the forward-backward launch both entry points share; leaves Fw / Bw / best on the device
@@ -272,8 +263,8 @@ static int lat_fb_launch(htkamd_latset *s, int K, const LatDev &D, hipStream_t s
    LatBufs &B = *(LatBufs *)s->dev;
    const size_t KN = (size_t)K * (size_t)s->totalNodes, P = (size_t)K * (size_t)s->nLats;
    int rc;
-   if ((rc = B.fw.reserve(sizeof(double) * KN)) || (rc = B.bw.reserve(sizeof(double) * KN)) || (rc = B.best.reserve(sizeof(double) * P))) return rc;
-   hipLaunchKernelGGL(k_lat_fb, dim3(lat_blocks(s, K)), dim3(64), 0, st, D, (double *)B.fw.p, (double *)B.bw.p, (double *)B.best.p);
+   if ((rc = B.fw.reserve<double>(KN)) || (rc = B.bw.reserve<double>(KN)) || (rc = B.best.reserve<double>(P))) return rc;
+   hipLaunchKernelGGL(k_lat_fb, dim3(lat_blocks(s, K)), dim3(64), 0, st, D, B.fw.as<double>(), B.bw.as<double>(), B.best.as<double>());
    HIPCHECK(hipGetLastError());
    return HTKAMD_OK;
 }
@@ -287,17 +278,11 @@ extern "C" int htkamd_latset_fb_max(htkamd_latset *s, int K, const htkamd_lat_sc
    if (rc) return rc;
    LatBufs &B = *(LatBufs *)s->dev;
    const size_t KN = (size_t)K * (size_t)s->totalNodes, P = (size_t)K * (size_t)s->nLats;
-   HIPCHECK(hipEventRecord(B.ev[0], st));
+   HIPCHECK(B.timer.start(st));
    if ((rc = lat_fb_launch(s, K, D, st))) return rc;
-   HIPCHECK(hipEventRecord(B.ev[1], st));
-   HIPCHECK(hipMemcpyAsync(out->fw, B.fw.p, sizeof(double) * KN, hipMemcpyDeviceToHost, st));
-   HIPCHECK(hipMemcpyAsync(out->bw, B.bw.p, sizeof(double) * KN, hipMemcpyDeviceToHost, st));
-   HIPCHECK(hipMemcpyAsync(out->best, B.best.p, sizeof(double) * P, hipMemcpyDeviceToHost, st));
-   HIPCHECK(hipStreamSynchronize(st));
-   float ms = 0.0f;
-   HIPCHECK(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
-   s->kernelMs = ms;
-   return HTKAMD_OK;
+   HIPCHECK(B.timer.stop(st));
+   if ((rc = B.fw.download(out->fw, KN, st)) || (rc = B.bw.download(out->bw, KN, st)) || (rc = B.best.download(out->best, P, st))) return rc;
+   return lat_finish(s, st);
 }
 
 extern "C" int htkamd_latset_prune(htkamd_latset *s, int K, const htkamd_lat_scales *scales, const double *thresh, const float *arcsPerSec,
@@ -313,20 +298,15 @@ extern "C" int htkamd_latset_prune(htkamd_latset *s, int K, const htkamd_lat_sca
    if (rc) return rc;
    LatBufs &B = *(LatBufs *)s->dev;
    const size_t KN = (size_t)K * (size_t)s->totalNodes, KA = (size_t)K * (size_t)s->totalArcs;
-   if ((rc = B.thresh.reserve(sizeof(double) * (size_t)K)) || (rc = B.aps.reserve(sizeof(float) * (size_t)K)) || (rc = B.keepNode.reserve(KN)) || (rc = B.keepArc.reserve(KA))) return rc;
-   HIPCHECK(hipMemcpyAsync(B.thresh.p, thresh, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, st));
-   HIPCHECK(hipMemcpyAsync(B.aps.p, arcsPerSec, sizeof(float) * (size_t)K, hipMemcpyHostToDevice, st));
-   HIPCHECK(hipEventRecord(B.ev[0], st));
+   if ((rc = B.thresh.upload(thresh, (size_t)K, st)) || (rc = B.aps.upload(arcsPerSec, (size_t)K, st)) || (rc = B.keepNode.reserve<unsigned char>(KN)) ||
+       (rc = B.keepArc.reserve<unsigned char>(KA)))
+      return rc;
+   HIPCHECK(B.timer.start(st));
    if ((rc = lat_fb_launch(s, K, D, st))) return rc;
-   hipLaunchKernelGGL(k_lat_prune, dim3(lat_blocks(s, K)), dim3(64), 0, st, D, (const double *)B.fw.p, (const double *)B.bw.p, (const double *)B.best.p,
-                      (const double *)B.thresh.p, (const float *)B.aps.p, (unsigned char *)B.keepNode.p, (unsigned char *)B.keepArc.p);
+   hipLaunchKernelGGL(k_lat_prune, dim3(lat_blocks(s, K)), dim3(64), 0, st, D, B.fw.as<const double>(), B.bw.as<const double>(), B.best.as<const double>(),
+                      B.thresh.as<const double>(), B.aps.as<const float>(), B.keepNode.as<unsigned char>(), B.keepArc.as<unsigned char>());
    HIPCHECK(hipGetLastError());
-   HIPCHECK(hipEventRecord(B.ev[1], st));
-   HIPCHECK(hipMemcpyAsync(keepNode, B.keepNode.p, KN, hipMemcpyDeviceToHost, st));
-   HIPCHECK(hipMemcpyAsync(keepArc, B.keepArc.p, KA, hipMemcpyDeviceToHost, st));
-   HIPCHECK(hipStreamSynchronize(st));
-   float ms = 0.0f;
-   HIPCHECK(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
-   s->kernelMs = ms;
-   return HTKAMD_OK;
+   HIPCHECK(B.timer.stop(st));
+   if ((rc = B.keepNode.download(keepNode, KN, st)) || (rc = B.keepArc.download(keepArc, KA, st))) return rc;
+   return lat_finish(s, st);
 }

@@ -30,6 +30,7 @@
 #include <vector>
 #include "internal.h"
 #include "hipcheck.h"
+#include "devbuf.h"
 
 struct MfccArgs {
    const short *wav;
@@ -576,29 +577,30 @@ __global__ void k_mfcc_zmean(float *out, const int *frameOff, int nUtt, int nCol
 }
 
 // ------------------------------------------------------------------------------------ host side
+DEVBUF_OWNER("frontend")
+
 struct htkamd_mfcc {
    htkamd_mfcc_config cfg;
    htkamd_mfcc_tables tab;
-   float *d_ham, *d_cepWin, *d_loWt, *d_frameMean;
-   int *d_bins, *d_frameOff, *d_frameUtt;
-   double *d_dct, *d_tw, *d_rtw;
-   short *d_brev;
-   long long *d_frameSamp;
-   size_t capFrames, capUtt;
+   DevBuf d_ham, d_cepWin, d_loWt, d_frameMean;          // float
+   DevBuf d_bins, d_frameOff, d_frameUtt;                // int; d_frameOff: frame offsets, then sample offsets
+   DevBuf d_dct, d_tw, d_rtw;                            // double
+   DevBuf d_brev;                                        // short
+   DevBuf d_frameSamp;                                   // long long
    int kind, lpcOrder;                   // FE_* (FE_MFCC for htkamd_mfcc_create); PLP: LPCORDER, COMPRESSFACT and its tables
    float compressFact;
-   float *d_eql;
-   double *d_cm;
+   DevBuf d_eql, d_cm;                                   // float, double
    int nWarp;                            // table sets: d_loWt [nWarp x (fftN/2 + 2)], d_bins [nWarp x 4 (numChans + 2)], d_eql [nWarp x (numChans + 1)]
-   int *d_uttWarp, *d_gridOff, *d_gridUtt;       // per-utterance warps; the grid's nWarp tables as nWarp * nUtt utterances: frame offsets, utterance of a frame
-   size_t capUttWarp, capGridUtt, capGridFrames;
+   DevBuf d_uttWarp, d_gridOff, d_gridUtt;       // int: per-utterance warps; the grid's nWarp tables as nWarp * nUtt utterances: frame offsets, utterance of a frame
+   ~htkamd_mfcc() { htkamd_mfcc_tables_free(&tab); }
 };
 struct htkamd_frontend { htkamd_mfcc m; };       // the same holder behind the general entry points
 
-template <typename T> static int up(T **d, const T *h, size_t n)
+template <typename T> static int up(DevBuf &d, const T *h, size_t n)
 {
-   HIPCHECK(hipMalloc((void **)d, sizeof(T) * (n ? n : 1)));
-   if (n) HIPCHECK(hipMemcpy(*d, h, sizeof(T) * n, hipMemcpyHostToDevice));
+   const int rc = d.reserve<T>(n);
+   if (rc) return rc;
+   if (n) HIPCHECK(hipMemcpy(d.p, h, sizeof(T) * n, hipMemcpyHostToDevice));
    return HTKAMD_OK;
 }
 
@@ -625,13 +627,13 @@ static int fe_create(const htkamd_frontend_config *fc, htkamd_mfcc *f, const htk
       if (nEql) eql.insert(eql.end(), tw.eql, tw.eql + nEql);
       htkamd_mfcc_tables_free(&tw);
    }
-   if ((rc = up(&f->d_ham, t.ham, (size_t)t.frSize + 1)) || (rc = up(&f->d_cepWin, t.cepWin, (size_t)nCep + 1)) ||
-       (rc = up(&f->d_loWt, loWt.data(), loWt.size())) || (rc = up(&f->d_bins, bins.data(), bins.size())) ||
-       (rc = up(&f->d_dct, t.dct, (size_t)(nDct + 1) * (cfg->numChans + 1))) || (rc = up(&f->d_tw, t.tw, (size_t)2 * nn)) ||
-       (rc = up(&f->d_rtw, t.rtw, (size_t)2 * (nn / 2 + 2))) || (rc = up(&f->d_brev, t.brev, (size_t)nn)))
+   if ((rc = up(f->d_ham, t.ham, (size_t)t.frSize + 1)) || (rc = up(f->d_cepWin, t.cepWin, (size_t)nCep + 1)) ||
+       (rc = up(f->d_loWt, loWt.data(), loWt.size())) || (rc = up(f->d_bins, bins.data(), bins.size())) ||
+       (rc = up(f->d_dct, t.dct, (size_t)(nDct + 1) * (cfg->numChans + 1))) || (rc = up(f->d_tw, t.tw, (size_t)2 * nn)) ||
+       (rc = up(f->d_rtw, t.rtw, (size_t)2 * (nn / 2 + 2))) || (rc = up(f->d_brev, t.brev, (size_t)nn)))
       return rc;
    if (f->kind == FE_PLP &&
-       ((rc = up(&f->d_eql, eql.data(), eql.size())) || (rc = up(&f->d_cm, t.cm, (size_t)(fc->lpcOrder + 1) * (cfg->numChans + 2)))))
+       ((rc = up(f->d_eql, eql.data(), eql.size())) || (rc = up(f->d_cm, t.cm, (size_t)(fc->lpcOrder + 1) * (cfg->numChans + 2)))))
       return rc;
    return HTKAMD_OK;
 }
@@ -643,28 +645,14 @@ extern "C" int htkamd_mfcc_create(const htkamd_mfcc_config *cfg, htkamd_mfcc **o
    htkamd_frontend_config fc;
    memset(&fc, 0, sizeof(fc));
    fc.base = *cfg; fc.baseKind = FE_MFCC;
-   htkamd_mfcc *f = (htkamd_mfcc *)calloc(1, sizeof(htkamd_mfcc));
+   htkamd_mfcc *f = new htkamd_mfcc();
    const int rc = fe_create(&fc, f);
    if (rc) { htkamd_mfcc_destroy(f); return rc; }
    *out = f;
    return HTKAMD_OK;
 }
 
-static void fe_release(htkamd_mfcc *f)
-{
-   (void)hipFree(f->d_ham); (void)hipFree(f->d_cepWin); (void)hipFree(f->d_loWt); (void)hipFree(f->d_bins); (void)hipFree(f->d_dct);
-   (void)hipFree(f->d_tw); (void)hipFree(f->d_rtw); (void)hipFree(f->d_brev); (void)hipFree(f->d_frameSamp); (void)hipFree(f->d_frameMean);
-   (void)hipFree(f->d_frameOff); (void)hipFree(f->d_frameUtt); (void)hipFree(f->d_eql); (void)hipFree(f->d_cm);
-   (void)hipFree(f->d_uttWarp); (void)hipFree(f->d_gridOff); (void)hipFree(f->d_gridUtt);
-   htkamd_mfcc_tables_free(&f->tab);
-}
-
-extern "C" void htkamd_mfcc_destroy(htkamd_mfcc *f)
-{
-   if (!f) return;
-   fe_release(f);
-   free(f);
-}
+extern "C" void htkamd_mfcc_destroy(htkamd_mfcc *f) { delete f; }
 
 template <int KIND> static void launch_frames(bool pair, int F, int maxGrid, size_t per, hipStream_t s, const MfccArgs &a)
 {
@@ -716,41 +704,35 @@ static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int
    }
    if (grid && f->nWarp == 1) grid = false;
    if (grid && (size_t)F * f->nWarp > (size_t)0x7fffffff) { htkamd_set_error("frontend_compute_grid: %d frames x %d warps exceed 2^31 - 1 rows", F, f->nWarp); return HTKAMD_EINVAL; }
-   if ((size_t)F > f->capFrames) {
-      (void)hipFree(f->d_frameSamp); (void)hipFree(f->d_frameMean); (void)hipFree(f->d_frameUtt);
-      f->d_frameSamp = nullptr; f->d_frameMean = nullptr; f->d_frameUtt = nullptr;
-      const size_t cap = (size_t)F + F / 8;
-      HIPCHECK(hipMalloc((void **)&f->d_frameSamp, sizeof(long long) * cap));
-      HIPCHECK(hipMalloc((void **)&f->d_frameMean, sizeof(float) * cap));
-      HIPCHECK(hipMalloc((void **)&f->d_frameUtt, sizeof(int) * cap));
-      f->capFrames = cap;
-   }
-   if ((size_t)nUtt + 1 > f->capUtt) {
-      (void)hipFree(f->d_frameOff); f->d_frameOff = nullptr;
-      HIPCHECK(hipMalloc((void **)&f->d_frameOff, sizeof(int) * 2 * ((size_t)nUtt + 1)));      // frame offsets, then sample offsets
-      f->capUtt = (size_t)nUtt + 1;
-   }
+   const size_t nOff = (size_t)nUtt + 1;
+   int rc;
+   if ((rc = f->d_frameSamp.reserve<long long>((size_t)F)) || (rc = f->d_frameMean.reserve<float>((size_t)F)) || (rc = f->d_frameUtt.reserve<int>((size_t)F)) ||
+       (rc = f->d_frameOff.reserve<int>(2 * nOff)))
+      return rc;
+   int *const dFrameOff = f->d_frameOff.as<int>(), *const dSampOff = dFrameOff + nOff, *const dFrameUtt = f->d_frameUtt.as<int>();
    // the per-frame tables (first sample, utterance) are made ON the device from the two per-utterance tables (round 6: 596 000 push_backs and
    // 7 MB of pageable copies were 0.7 ms of a 2.7 ms call)
-   HIPCHECK(hipMemcpyAsync(f->d_frameOff, frameOff, sizeof(int) * ((size_t)nUtt + 1), hipMemcpyHostToDevice, s));
-   HIPCHECK(hipMemcpyAsync(f->d_frameOff + f->capUtt, sampOff, sizeof(int) * ((size_t)nUtt + 1), hipMemcpyHostToDevice, s));
-   hipLaunchKernelGGL(k_mfcc_index, dim3((F + 255) / 256), dim3(256), 0, s, f->d_frameOff, f->d_frameOff + f->capUtt, nUtt, F, t.frRate, f->d_frameSamp, f->d_frameUtt);
+   HIPCHECK(hipMemcpyAsync(dFrameOff, frameOff, sizeof(int) * nOff, hipMemcpyHostToDevice, s));
+   HIPCHECK(hipMemcpyAsync(dSampOff, sampOff, sizeof(int) * nOff, hipMemcpyHostToDevice, s));
+   hipLaunchKernelGGL(k_mfcc_index, dim3((F + 255) / 256), dim3(256), 0, s, dFrameOff, dSampOff, nUtt, F, t.frRate, f->d_frameSamp.as<long long>(), dFrameUtt);
    HIPCHECK(hipGetLastError());
 
    MfccArgs a;
-   a.wav = dWav; a.frameSamp = f->d_frameSamp; a.nFrames = F;
+   a.wav = dWav; a.frameSamp = f->d_frameSamp.as<long long>(); a.nFrames = F;
    a.frSize = t.frSize; a.fftN = t.fftN; a.klo = t.klo; a.khi = t.khi; a.numChans = c.numChans; a.numCeps = c.numCeps;
    a.nCols = nCols; a.nStat = nStat; a.preEmph = c.preEmph; a.cepScale = c.cepScale; a.mfnorm = t.mfnorm;
    a.useHam = c.useHam; a.usePower = c.usePower; a.zMean = c.zMeanSource; a.hasC0 = c.hasC0; a.hasE = c.hasE; a.rawEnergy = c.rawEnergy;
-   a.ham = f->d_ham; a.cepWin = f->d_cepWin; a.loWt = f->d_loWt;
-   a.binA0 = f->d_bins; a.binA1 = f->d_bins + (c.numChans + 2); a.binB0 = a.binA1 + (c.numChans + 2); a.binB1 = a.binB0 + (c.numChans + 2);
-   a.dct = f->d_dct; a.tw = f->d_tw; a.rtw = f->d_rtw; a.brev = f->d_brev; a.frameMean = f->d_frameMean; a.out = dOut;
+   float *const dEql = f->d_eql.as<float>();
+   int *const dBins = f->d_bins.as<int>();
+   a.ham = f->d_ham.as<float>(); a.cepWin = f->d_cepWin.as<float>(); a.loWt = f->d_loWt.as<float>();
+   a.binA0 = dBins; a.binA1 = dBins + (c.numChans + 2); a.binB0 = a.binA1 + (c.numChans + 2); a.binB1 = a.binB0 + (c.numChans + 2);
+   a.dct = f->d_dct.as<double>(); a.tw = f->d_tw.as<double>(); a.rtw = f->d_rtw.as<double>(); a.brev = f->d_brev.as<short>(); a.frameMean = f->d_frameMean.as<float>(); a.out = dOut;
    if (set > 0) {
       a.loWt += (size_t)set * (t.fftN / 2 + 2);
       a.binA0 += (size_t)set * 4 * (c.numChans + 2); a.binA1 += (size_t)set * 4 * (c.numChans + 2);
       a.binB0 += (size_t)set * 4 * (c.numChans + 2); a.binB1 += (size_t)set * 4 * (c.numChans + 2);
    }
-   a.eql = (f->d_eql && set > 0) ? f->d_eql + (size_t)set * (c.numChans + 1) : f->d_eql; a.cm = f->d_cm; a.lpcOrder = f->lpcOrder; a.compressFact = f->compressFact;
+   a.eql = (dEql && set > 0) ? dEql + (size_t)set * (c.numChans + 1) : dEql; a.cm = f->d_cm.as<double>(); a.lpcOrder = f->lpcOrder; a.compressFact = f->compressFact;
    a.plpExtra = (f->kind == FE_PLP) ? (c.numChans + 3) + (f->lpcOrder + 1) + (f->lpcOrder + 2) + (c.numCeps + 2) : 0;
 
    if (c.hasE || c.zMeanSource) {
@@ -767,40 +749,26 @@ static int fe_compute(htkamd_mfcc *f, const short *dWav, const int *sampOff, int
    const bool pair = c.numChans <= 32 && (f->kind == FE_FBANK || f->kind == FE_MELSPEC || c.numCeps <= 31) &&
                      (f->kind != FE_PLP || f->lpcOrder <= 31) && 2 * per <= (size_t)64 * 1024;
    // what follows the frame kernel works per utterance: the grid's nWarp tables are nWarp * nUtt utterances of nWarp * F frames
-   const int *dOff = f->d_frameOff, *dUtt = f->d_frameUtt;
+   const int *dOff = dFrameOff, *dUtt = dFrameUtt;
    int nU = nUtt, nF = F;
    if (mixed || grid) {
       WarpArgs w;
-      w.loWt = f->d_loWt; w.eql = f->d_eql; w.bins = f->d_bins; w.loStride = t.fftN / 2 + 2; w.eqlStride = c.numChans + 1;
-      w.frameUtt = f->d_frameUtt; w.uttWarp = nullptr; w.nWarp = f->nWarp; w.tableStride = (size_t)F * nCols;
+      w.loWt = f->d_loWt.as<float>(); w.eql = dEql; w.bins = dBins; w.loStride = t.fftN / 2 + 2; w.eqlStride = c.numChans + 1;
+      w.frameUtt = dFrameUtt; w.uttWarp = nullptr; w.nWarp = f->nWarp; w.tableStride = (size_t)F * nCols;
       if (mixed) {
-         if ((size_t)nUtt > f->capUttWarp) {
-            (void)hipFree(f->d_uttWarp); f->d_uttWarp = nullptr; f->capUttWarp = 0;
-            HIPCHECK(hipMalloc((void **)&f->d_uttWarp, sizeof(int) * (size_t)nUtt));
-            f->capUttWarp = (size_t)nUtt;
-         }
-         HIPCHECK(hipMemcpy(f->d_uttWarp, uttWarp, sizeof(int) * (size_t)nUtt, hipMemcpyHostToDevice));      // (small, and the caller's: over when it returns)
-         w.uttWarp = f->d_uttWarp;
+         if ((rc = up(f->d_uttWarp, uttWarp, (size_t)nUtt))) return rc;      // (small, and the caller's: over when it returns)
+         w.uttWarp = f->d_uttWarp.as<int>();
       } else {
          nU = nUtt * f->nWarp; nF = F * f->nWarp;
-         if ((size_t)nU + 1 > f->capGridUtt) {
-            (void)hipFree(f->d_gridOff); f->d_gridOff = nullptr; f->capGridUtt = 0;
-            HIPCHECK(hipMalloc((void **)&f->d_gridOff, sizeof(int) * ((size_t)nU + 1)));
-            f->capGridUtt = (size_t)nU + 1;
-         }
-         if ((size_t)nF > f->capGridFrames) {
-            (void)hipFree(f->d_gridUtt); f->d_gridUtt = nullptr; f->capGridFrames = 0;
-            HIPCHECK(hipMalloc((void **)&f->d_gridUtt, sizeof(int) * (size_t)nF));
-            f->capGridFrames = (size_t)nF;
-         }
+         if ((rc = f->d_gridUtt.reserve<int>((size_t)nF))) return rc;
          std::vector<int> gridOff((size_t)nU + 1);
          for (int k = 0; k < f->nWarp; k++)
             for (int u = 0; u < nUtt; u++) gridOff[(size_t)k * nUtt + u] = k * F + frameOff[u];
          gridOff[nU] = nF;
-         HIPCHECK(hipMemcpy(f->d_gridOff, gridOff.data(), sizeof(int) * gridOff.size(), hipMemcpyHostToDevice));
-         hipLaunchKernelGGL(k_mfcc_grid_index, dim3((unsigned)(((size_t)nF + 255) / 256)), dim3(256), 0, s, f->d_frameUtt, F, nUtt, f->nWarp, f->d_gridUtt);
+         if ((rc = up(f->d_gridOff, gridOff.data(), gridOff.size()))) return rc;
+         hipLaunchKernelGGL(k_mfcc_grid_index, dim3((unsigned)(((size_t)nF + 255) / 256)), dim3(256), 0, s, dFrameUtt, F, nUtt, f->nWarp, f->d_gridUtt.as<int>());
          HIPCHECK(hipGetLastError());
-         dOff = f->d_gridOff; dUtt = f->d_gridUtt;
+         dOff = f->d_gridOff.as<int>(); dUtt = f->d_gridUtt.as<int>();
       }
       switch (f->kind) {
       case FE_MFCC: launch_frames_warp<FE_MFCC>(grid, pair, F, maxGrid, per, s, a, w); break;
@@ -865,18 +833,13 @@ extern "C" int htkamd_frontend_create(const htkamd_frontend_config *cfg, htkamd_
    int rc = htkamd_frontend_check(cfg);                 // (refusals come before the device is touched)
    if (rc) return rc;
    if (htkamd_device_count() <= 0) { htkamd_set_error("frontend_create: no HIP device"); return HTKAMD_ENODEV; }
-   htkamd_frontend *f = (htkamd_frontend *)calloc(1, sizeof(htkamd_frontend));
+   htkamd_frontend *f = new htkamd_frontend();
    if ((rc = fe_create(cfg, &f->m)) != HTKAMD_OK) { htkamd_frontend_destroy(f); return rc; }
    *out = f;
    return HTKAMD_OK;
 }
 
-extern "C" void htkamd_frontend_destroy(htkamd_frontend *f)
-{
-   if (!f) return;
-   fe_release(&f->m);
-   free(f);
-}
+extern "C" void htkamd_frontend_destroy(htkamd_frontend *f) { delete f; }
 
 extern "C" int htkamd_frontend_compute(htkamd_frontend *f, const short *dWav, const int *sampOff, int nUtt, int *frameOff, float *dOut, void *stream)
 {
@@ -893,7 +856,7 @@ extern "C" int htkamd_frontend_create_warped(const htkamd_frontend_config *cfg, 
    for (int w = 0; w < nWarp; w++)                       // (refusals come before the device is touched)
       if ((rc = htkamd_frontend_warp_check(cfg, warps + w)) != HTKAMD_OK) return rc;
    if (htkamd_device_count() <= 0) { htkamd_set_error("frontend_create_warped: no HIP device"); return HTKAMD_ENODEV; }
-   htkamd_frontend *f = (htkamd_frontend *)calloc(1, sizeof(htkamd_frontend));
+   htkamd_frontend *f = new htkamd_frontend();
    if ((rc = fe_create(cfg, &f->m, warps, nWarp)) != HTKAMD_OK) { htkamd_frontend_destroy(f); return rc; }
    *out = f;
    return HTKAMD_OK;
@@ -963,11 +926,10 @@ extern "C" int htkamd_parm_qualify(const float *dStatic, const int *frameOff, in
       if (frameOff[u + 1] < frameOff[u]) { htkamd_set_error("parm_qualify: frameOff not monotone"); return HTKAMD_EINVAL; }
       for (int f = frameOff[u]; f < frameOff[u + 1]; f++) frameUtt[f] = u;
    }
-   int *dUtt = nullptr, *dOff = nullptr;
+   DevScratch b;
+   int *dUtt = nullptr, *dOff = nullptr, rc;
    float *dFull = dOut;
-   HIPCHECK(hipMalloc((void **)&dUtt, sizeof(int) * (size_t)F));
-   HIPCHECK(hipMalloc((void **)&dOff, sizeof(int) * ((size_t)nUtt + 1)));
-   if (q->nullECol >= 0) HIPCHECK(hipMalloc((void **)&dFull, sizeof(float) * (size_t)F * nFull));
+   if ((rc = b.get(&dUtt, (size_t)F)) || (rc = b.get(&dOff, (size_t)nUtt + 1)) || (q->nullECol >= 0 && (rc = b.get(&dFull, (size_t)F * nFull)))) return rc;
    HIPCHECK(hipMemcpyAsync(dUtt, frameUtt.data(), sizeof(int) * (size_t)F, hipMemcpyHostToDevice, s));
    HIPCHECK(hipMemcpyAsync(dOff, frameOff, sizeof(int) * ((size_t)nUtt + 1), hipMemcpyHostToDevice, s));
    const size_t n = (size_t)F * nStat;
@@ -983,11 +945,9 @@ extern "C" int htkamd_parm_qualify(const float *dStatic, const int *frameOff, in
       const size_t m = (size_t)F * (nFull - 1);
       hipLaunchKernelGGL(k_parm_drop_col, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, dFull, dOut, (size_t)F, nFull, q->nullECol);
    }
-   hipError_t e = hipGetLastError();
-   hipError_t e2 = hipStreamSynchronize(s);
-   (void)hipFree(dUtt); (void)hipFree(dOff);
-   if (dFull != dOut) (void)hipFree(dFull);
-   HIPCHECK(e); HIPCHECK(e2);
+   const hipError_t e = hipGetLastError();
+   HIPCHECK(hipStreamSynchronize(s));                    // (the scratch is released on return)
+   HIPCHECK(e);
    return HTKAMD_OK;
 }
 
@@ -1010,7 +970,8 @@ struct htkamd_parm_stream {
    htkamd_parm_quals q;
    int qwin, nSeen, qst, base, cap;        // rows seen so far; next row to hand out; absolute index of dBuf's first row; rows of capacity
    int done;
-   float *dBuf, *dTmp;
+   DevBuf buf, tmp;
+   float *dBuf, *dTmp;                     // their rows
 };
 
 extern "C" int htkamd_parm_stream_open(const htkamd_parm_quals *q, int maxRows, htkamd_parm_stream **out)
@@ -1026,25 +987,15 @@ extern "C" int htkamd_parm_stream_open(const htkamd_parm_quals *q, int maxRows, 
    s->qwin = (q->hasD ? q->delWin : 0) + (q->hasA ? q->accWin : 0) + (q->hasT ? q->thirdWin : 0);
    s->nSeen = s->qst = s->base = 0; s->done = 0;
    s->cap = maxRows + 2 * s->qwin + 1;
-   s->dBuf = s->dTmp = nullptr;
    const int cols = htkamd_parm_quals_cols(q);
-   if (hipMalloc((void **)&s->dBuf, sizeof(float) * (size_t)s->cap * q->nStat) != hipSuccess ||
-       hipMalloc((void **)&s->dTmp, sizeof(float) * (size_t)s->cap * cols) != hipSuccess) {
-      if (s->dBuf) (void)hipFree(s->dBuf);
-      delete s;
-      htkamd_set_error("parm_stream_open: out of device memory"); return HTKAMD_ENOMEM;
-   }
+   int rc;
+   if ((rc = s->buf.reserve<float>((size_t)s->cap * q->nStat)) || (rc = s->tmp.reserve<float>((size_t)s->cap * cols))) { delete s; return rc; }
+   s->dBuf = s->buf.as<float>(); s->dTmp = s->tmp.as<float>();
    *out = s;
    return HTKAMD_OK;
 }
 
-extern "C" void htkamd_parm_stream_close(htkamd_parm_stream *s)
-{
-   if (!s) return;
-   if (s->dBuf) (void)hipFree(s->dBuf);
-   if (s->dTmp) (void)hipFree(s->dTmp);
-   delete s;
-}
+extern "C" void htkamd_parm_stream_close(htkamd_parm_stream *s) { delete s; }
 
 extern "C" int htkamd_parm_stream_lookahead(const htkamd_parm_stream *s) { return s ? s->qwin : 0; }
 
@@ -1104,18 +1055,18 @@ extern "C" int htkamd_compv(const float *dX, long long nFrames, int D, float min
    if (!dX || !mean || !var || D <= 0) { htkamd_set_error("compv: bad argument"); return HTKAMD_EINVAL; }
    if (nFrames < 2) { htkamd_set_error("compv: only %lld frames (HCompV error 2021)", nFrames); return HTKAMD_EINVAL; }
    hipStream_t s = (hipStream_t)stream;
+   DevScratch b;
    double *dAcc = nullptr;
-   HIPCHECK(hipMalloc((void **)&dAcc, sizeof(double) * 2 * (size_t)D));
+   int rc;
+   if ((rc = b.get(&dAcc, 2 * (size_t)D))) return rc;
    HIPCHECK(hipMemsetAsync(dAcc, 0, sizeof(double) * 2 * (size_t)D, s));
    long long blocks = (nFrames + 255) / 256;
    if (blocks > 4096) blocks = 4096;
    hipLaunchKernelGGL(k_compv, dim3((unsigned)blocks), dim3(64), 0, s, dX, nFrames, D, dAcc);
    std::vector<double> h(2 * (size_t)D);
-   hipError_t e = hipGetLastError();
-   hipError_t e2 = hipMemcpyAsync(h.data(), dAcc, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s);
-   hipError_t e3 = hipStreamSynchronize(s);
-   (void)hipFree(dAcc);
-   HIPCHECK(e); HIPCHECK(e2); HIPCHECK(e3);
+   HIPCHECK(hipGetLastError());
+   HIPCHECK(hipMemcpyAsync(h.data(), dAcc, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+   HIPCHECK(hipStreamSynchronize(s));
    const double n = (double)nFrames;
    for (int k = 0; k < D; k++) {
       const double m = h[k] / n, v = h[D + k] / n - m * m;

@@ -223,24 +223,21 @@ __global__ __launch_bounds__(RT_THREADS) void k_rt_split(RtSet S, int *list, int
 }
 
 // ------------------------------------------------------------------------------------------ host side of the device
-namespace {
-constexpr char rtOwner[] = "regtree";
-typedef DevBufT<rtOwner> DevBuf;
-}
+DEVBUF_OWNER("regtree")
 
 struct htkamd_rt_dev {
    DevBuf mean, sum, sqr, occ, has, list, tmp, flag, val, seeds, outI, outF;
-   int G, D;
-   hipStream_t st;
-   hipEvent_t e0, e1;
-   float ms;
+   int G = 0, D = 0;
+   hipStream_t st = nullptr;
+   KernelTimer timer;
+   float ms = 0.0f;
 };
 
 static RtSet rt_set(const htkamd_rt_dev *t)
 {
    RtSet S;
-   S.mean = (const float *)t->mean.p; S.sum = (const float *)t->sum.p; S.sqr = (const float *)t->sqr.p; S.occ = (const float *)t->occ.p;
-   S.has = (const unsigned char *)t->has.p; S.D = t->D;
+   S.mean = t->mean.as<const float>(); S.sum = t->sum.as<const float>(); S.sqr = t->sqr.as<const float>(); S.occ = t->occ.as<const float>();
+   S.has = t->has.as<const unsigned char>(); S.D = t->D;
    return S;
 }
 
@@ -250,53 +247,43 @@ extern "C" int htkamd_rt_dev_open(htkamd_rt_dev **out, const float *mean, const 
    if (!out || !mean || !sum || !sqr || !occ || !hasAcc || G < 1 || D < 1 || D > HTKAMD_RT_MAXDIM) { htkamd_set_error("regtree: bad argument"); return HTKAMD_EINVAL; }
    if (htkamd_device_count() <= 0) { htkamd_set_error("regtree: no HIP device"); return HTKAMD_ENODEV; }
    htkamd_rt_dev *t = new htkamd_rt_dev();
-   t->G = G; t->D = D; t->st = (hipStream_t)stream; t->ms = 0.0f; t->e0 = nullptr; t->e1 = nullptr;
-   const size_t rows = sizeof(float) * (size_t)G * D;
-   int rc = t->mean.reserve(rows);
-   if (!rc) rc = t->sum.reserve(rows);
-   if (!rc) rc = t->sqr.reserve(rows);
-   if (!rc) rc = t->occ.reserve(sizeof(float) * (size_t)G);
-   if (!rc) rc = t->has.reserve((size_t)G);
-   if (!rc) rc = t->list.reserve(sizeof(int) * (size_t)G);
-   if (!rc) rc = t->tmp.reserve(sizeof(int) * (size_t)G);
-   if (!rc) rc = t->flag.reserve((size_t)G);
-   if (!rc) rc = t->val.reserve(sizeof(float) * (size_t)G);
-   if (!rc) rc = t->seeds.reserve(sizeof(float) * 2 * (size_t)D);
-   if (!rc) rc = t->outI.reserve(sizeof(int) * 4);
-   if (!rc) rc = t->outF.reserve(sizeof(float) * 2 * (2 * (size_t)D + 2));
-   int *ident = (int *)malloc(sizeof(int) * (size_t)G);
+   t->G = G; t->D = D; t->st = (hipStream_t)stream;
+   const size_t nG = (size_t)G, rows = nG * D;
+   std::vector<int> ident(nG);
    for (int i = 0; i < G; i++) ident[i] = i;
-#define RT_HIP(call) do { if (!rc) { hipError_t e_ = (call); if (e_ != hipSuccess) { htkamd_set_error("regtree: %s -> %s", #call, hipGetErrorString(e_)); rc = HTKAMD_EHIP; } } } while (0)
-   RT_HIP(hipEventCreate(&t->e0));
-   RT_HIP(hipEventCreate(&t->e1));
-   RT_HIP(hipMemcpyAsync(t->mean.p, mean, rows, hipMemcpyHostToDevice, t->st));
-   RT_HIP(hipMemcpyAsync(t->sum.p, sum, rows, hipMemcpyHostToDevice, t->st));
-   RT_HIP(hipMemcpyAsync(t->sqr.p, sqr, rows, hipMemcpyHostToDevice, t->st));
-   RT_HIP(hipMemcpyAsync(t->occ.p, occ, sizeof(float) * (size_t)G, hipMemcpyHostToDevice, t->st));
-   RT_HIP(hipMemcpyAsync(t->has.p, hasAcc, (size_t)G, hipMemcpyHostToDevice, t->st));
-   RT_HIP(hipMemcpyAsync(t->list.p, ident, sizeof(int) * (size_t)G, hipMemcpyHostToDevice, t->st));
-   RT_HIP(hipStreamSynchronize(t->st));
-   free(ident);
+   int rc = t->mean.upload(mean, rows, t->st);
+   if (!rc) rc = t->sum.upload(sum, rows, t->st);
+   if (!rc) rc = t->sqr.upload(sqr, rows, t->st);
+   if (!rc) rc = t->occ.upload(occ, nG, t->st);
+   if (!rc) rc = t->has.upload(hasAcc, nG, t->st);
+   if (!rc) rc = t->list.upload(ident, t->st);
+   if (!rc) rc = t->tmp.reserve<int>(nG);
+   if (!rc) rc = t->flag.reserve<unsigned char>(nG);
+   if (!rc) rc = t->val.reserve<float>(nG);
+   if (!rc) rc = t->seeds.reserve<float>(2 * (size_t)D);
+   if (!rc) rc = t->outI.reserve<int>(4);
+   if (!rc) rc = t->outF.reserve<float>(2 * (2 * (size_t)D + 2));
+   HIPCHECK_RC(rc, devOwner, hipStreamSynchronize(t->st));
    if (rc) { htkamd_rt_dev_close(t); return rc; }
    *out = t;
    return HTKAMD_OK;
 }
 
-// one launch between two events, its figures fetched, its time added
+// one launch between the timer's two events; its time is added once its figures are fetched
 template <typename Launch> static int rt_timed(htkamd_rt_dev *t, Launch launch)
 {
    int rc = HTKAMD_OK;
-   RT_HIP(hipEventRecord(t->e0, t->st));
+   HIPCHECK_RC(rc, devOwner, t->timer.start(t->st));
    if (!rc) launch();
-   RT_HIP(hipGetLastError());
-   RT_HIP(hipEventRecord(t->e1, t->st));
+   HIPCHECK_RC(rc, devOwner, hipGetLastError());
+   HIPCHECK_RC(rc, devOwner, t->timer.stop(t->st));
    return rc;
 }
 static int rt_elapsed(htkamd_rt_dev *t)
 {
    int rc = HTKAMD_OK; float ms = 0.0f;
-   RT_HIP(hipStreamSynchronize(t->st));
-   RT_HIP(hipEventElapsedTime(&ms, t->e0, t->e1));
+   HIPCHECK_RC(rc, devOwner, hipStreamSynchronize(t->st));
+   HIPCHECK_RC(rc, devOwner, t->timer.ms(&ms));
    if (!rc) t->ms += ms;
    return rc;
 }
@@ -306,9 +293,9 @@ extern "C" int htkamd_rt_dev_node(htkamd_rt_dev *t, int off, int n, float *node)
    if (!t || !node || off < 0 || n < 0 || (long long)off + n > t->G) { htkamd_set_error("regtree: node range %d + %d of %d members", off, n, t ? t->G : 0); return HTKAMD_EINVAL; }
    const int D = t->D;
    int rc = rt_timed(t, [&] {
-      hipLaunchKernelGGL(k_rt_node, dim3(1), dim3(RT_THREADS), sizeof(float) * ((size_t)D + 2), t->st, rt_set(t), (const int *)t->list.p, (float *)t->val.p, off, n, (float *)t->outF.p);
+      hipLaunchKernelGGL(k_rt_node, dim3(1), dim3(RT_THREADS), sizeof(float) * ((size_t)D + 2), t->st, rt_set(t), t->list.as<const int>(), t->val.as<float>(), off, n, t->outF.as<float>());
    });
-   RT_HIP(hipMemcpyAsync(node, t->outF.p, sizeof(float) * (2 * (size_t)D + 2), hipMemcpyDeviceToHost, t->st));
+   if (!rc) rc = t->outF.download(node, 2 * (size_t)D + 2, t->st);
    if (!rc) rc = rt_elapsed(t);
    return rc;
 }
@@ -317,14 +304,13 @@ extern "C" int htkamd_rt_dev_split(htkamd_rt_dev *t, int off, int n, const float
 {
    if (!t || !seeds || !counts || !nodes || off < 0 || n < 1 || (long long)off + n > t->G) { htkamd_set_error("regtree: split range %d + %d of %d members", off, n, t ? t->G : 0); return HTKAMD_EINVAL; }
    const int D = t->D;
-   int rc = HTKAMD_OK;
-   RT_HIP(hipMemcpyAsync(t->seeds.p, seeds, sizeof(float) * 2 * (size_t)D, hipMemcpyHostToDevice, t->st));
+   int rc = t->seeds.upload(seeds, 2 * (size_t)D, t->st);
    if (!rc) rc = rt_timed(t, [&] {
-      hipLaunchKernelGGL(k_rt_split, dim3(1), dim3(RT_THREADS), sizeof(float) * (3 * (size_t)D + 6), t->st, rt_set(t), (int *)t->list.p, (int *)t->tmp.p, (unsigned char *)t->flag.p,
-                         (float *)t->val.p, off, n, (const float *)t->seeds.p, (int *)t->outI.p, (float *)t->outF.p);
+      hipLaunchKernelGGL(k_rt_split, dim3(1), dim3(RT_THREADS), sizeof(float) * (3 * (size_t)D + 6), t->st, rt_set(t), t->list.as<int>(), t->tmp.as<int>(), t->flag.as<unsigned char>(),
+                         t->val.as<float>(), off, n, t->seeds.as<const float>(), t->outI.as<int>(), t->outF.as<float>());
    });
-   RT_HIP(hipMemcpyAsync(counts, t->outI.p, sizeof(int) * 3, hipMemcpyDeviceToHost, t->st));
-   RT_HIP(hipMemcpyAsync(nodes, t->outF.p, sizeof(float) * 2 * (2 * (size_t)D + 2), hipMemcpyDeviceToHost, t->st));
+   if (!rc) rc = t->outI.download(counts, 3, t->st);
+   if (!rc) rc = t->outF.download(nodes, 2 * (2 * (size_t)D + 2), t->st);
    if (!rc) rc = rt_elapsed(t);
    if (!rc && (counts[0] < 0 || counts[1] < 0 || counts[0] + counts[1] != n)) { htkamd_set_error("regtree: a split of %d members came back as %d + %d", n, counts[0], counts[1]); rc = HTKAMD_EHIP; }
    return rc;
@@ -333,12 +319,10 @@ extern "C" int htkamd_rt_dev_split(htkamd_rt_dev *t, int off, int n, const float
 extern "C" int htkamd_rt_dev_list(htkamd_rt_dev *t, int *list)
 {
    if (!t || !list) { htkamd_set_error("regtree: bad argument"); return HTKAMD_EINVAL; }
-   int rc = HTKAMD_OK;
-   RT_HIP(hipMemcpyAsync(list, t->list.p, sizeof(int) * (size_t)t->G, hipMemcpyDeviceToHost, t->st));
-   RT_HIP(hipStreamSynchronize(t->st));
+   int rc = t->list.download(list, (size_t)t->G, t->st);
+   HIPCHECK_RC(rc, devOwner, hipStreamSynchronize(t->st));
    return rc;
 }
-#undef RT_HIP
 
 // Test aid: the device steps alone over a caller's member arrays, in order on one htkamd_rt_dev, so a later step sees the list as the
 // earlier splits left it.  Step s is steps[3s .. 3s+3) = (kind, off, n): kind 0 a node step (figures[s][0] is written), kind 1 a split
@@ -365,10 +349,4 @@ extern "C" int htkamd_regtree_probe(const float *mean, const float *sum, const f
 
 extern "C" float htkamd_rt_dev_kernel_ms(const htkamd_rt_dev *t) { return t ? t->ms : 0.0f; }
 
-extern "C" void htkamd_rt_dev_close(htkamd_rt_dev *t)
-{
-   if (!t) return;
-   if (t->e0) (void)hipEventDestroy(t->e0);
-   if (t->e1) (void)hipEventDestroy(t->e1);
-   delete t;
-}
+extern "C" void htkamd_rt_dev_close(htkamd_rt_dev *t) { delete t; }

@@ -24,8 +24,7 @@
 #include "devbuf.h"
 #include "results.h"
 
-static constexpr char res_owner[] = "results";
-typedef DevBufT<res_owner> DevBuf;
+DEVBUF_OWNER("results")
 
 #define RES_WAVES      4          // pairs in flight per workgroup
 #define RES_DIR_TILE   8192       // dir bytes (grid cells off the edge rows) a wavefront keeps in LDS
@@ -215,8 +214,7 @@ __global__ __launch_bounds__(256) void k_results_totals(const int *__restrict__ 
 
 struct ResDev {
    DevBuf refs, hyps, pairs, counts, aln, alnLen, totals, conf, dir, bnd;
-   hipEvent_t ev[2] = {nullptr, nullptr};
-   ~ResDev() { for (int k = 0; k < 2; k++) if (ev[k]) (void)hipEventDestroy(ev[k]); }
+   KernelTimer timer;
 };
 
 static void res_dev_free(void *dev) { delete (ResDev *)dev; }
@@ -271,7 +269,6 @@ extern "C" int htkamd_results_score(htkamd_results *r, int K, int U, const int *
    if (!r->dev) { r->dev = new ResDev(); r->devFree = res_dev_free; }
    ResDev &D = *(ResDev *)r->dev;
    hipStream_t st = (hipStream_t)stream;
-   for (int k = 0; k < 2; k++) if (!D.ev[k]) HIPCHECK(hipEventCreate(&D.ev[k]));
    int blocks = (nPairs + RES_WAVES - 1) / RES_WAVES;
    if (blocks > RES_MAXBLOCKS) blocks = RES_MAXBLOCKS;
    maxDir = (maxDir + 255) & ~(size_t)255;
@@ -279,50 +276,46 @@ extern "C" int htkamd_results_score(htkamd_results *r, int K, int U, const int *
    if (blocks < 1) blocks = 1;
    const size_t slots = (size_t)blocks * RES_WAVES, bndStride = (size_t)(maxBndT + 1);
    int rc;
-   const size_t nRefIds = (size_t)r->refOff[r->nRefs];
+   const size_t nP = (size_t)nPairs, nTot = 7 * (size_t)K, nConf = (size_t)K * W * W;
    if (r->refsOnDevice != r->nRefs) {
-      if ((rc = D.refs.reserve(sizeof(int) * (nRefIds + 1)))) return rc;
-      if (nRefIds) HIPCHECK(hipMemcpyAsync(D.refs.p, r->refIds, sizeof(int) * nRefIds, hipMemcpyHostToDevice, st));
+      if ((rc = D.refs.upload(r->refIds, (size_t)r->refOff[r->nRefs], st))) return rc;
       HIPCHECK(hipStreamSynchronize(st));                     // (the host array may move when a reference is added)
       r->refsOnDevice = r->nRefs;
    }
-   if ((rc = D.hyps.reserve(sizeof(int) * ((size_t)nHyp + 1)))) return rc;
-   if ((rc = D.pairs.reserve(sizeof(PairDesc) * (size_t)nPairs))) return rc;
-   if ((rc = D.counts.reserve(sizeof(int) * 6 * (size_t)nPairs))) return rc;
-   if ((rc = D.totals.reserve(sizeof(unsigned long long) * 7 * (size_t)K))) return rc;
-   if (wantDir && (rc = D.aln.reserve(sizeof(int) * 3 * ((size_t)alnTotal + 1)))) return rc;
-   if (wantDir && (rc = D.alnLen.reserve(sizeof(int) * (size_t)nPairs))) return rc;
-   if (wantConf && (rc = D.conf.reserve(sizeof(int) * (size_t)K * W * W))) return rc;
-   if (maxDir > 0 && (rc = D.dir.reserve(slots * maxDir))) return rc;
-   if (maxBndT >= 0 && (rc = D.bnd.reserve(sizeof(Cell) * slots * 2 * bndStride))) return rc;
-   if (nHyp) HIPCHECK(hipMemcpyAsync(D.hyps.p, hypIds, sizeof(int) * (size_t)nHyp, hipMemcpyHostToDevice, st));
-   HIPCHECK(hipMemcpyAsync(D.pairs.p, pd.data(), sizeof(PairDesc) * (size_t)nPairs, hipMemcpyHostToDevice, st));
-   HIPCHECK(hipMemsetAsync(D.totals.p, 0, sizeof(unsigned long long) * 7 * (size_t)K, st));
-   if (wantConf) HIPCHECK(hipMemsetAsync(D.conf.p, 0, sizeof(int) * (size_t)K * W * W, st));
-   HIPCHECK(hipEventRecord(D.ev[0], st));
+   if ((rc = D.hyps.upload(hypIds, (size_t)nHyp, st))) return rc;
+   if ((rc = D.pairs.upload(pd, st))) return rc;
+   if ((rc = D.counts.reserve<int>(6 * nP))) return rc;
+   if ((rc = D.totals.reserve<unsigned long long>(nTot))) return rc;
+   if (wantDir && (rc = D.aln.reserve<int>(3 * (size_t)alnTotal))) return rc;
+   if (wantDir && (rc = D.alnLen.reserve<int>(nP))) return rc;
+   if (wantConf && (rc = D.conf.reserve<int>(nConf))) return rc;
+   if (maxDir > 0 && (rc = D.dir.reserve<unsigned char>(slots * maxDir))) return rc;
+   if (maxBndT >= 0 && (rc = D.bnd.reserve<Cell>(slots * 2 * bndStride))) return rc;
+   HIPCHECK(hipMemsetAsync(D.totals.p, 0, sizeof(unsigned long long) * nTot, st));
+   if (wantConf) HIPCHECK(hipMemsetAsync(D.conf.p, 0, sizeof(int) * nConf, st));
+   HIPCHECK(D.timer.start(st));
    auto kern = r->nist ? k_results_align<true> : k_results_align<false>;
-   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(RES_WAVES * 64), 0, st, (const PairDesc *)D.pairs.p, nPairs, (const int *)D.refs.p, (const int *)D.hyps.p, (int)wantDir,
-                      maxDir > 0 ? (unsigned char *)D.dir.p : nullptr, maxDir, maxBndT >= 0 ? (Cell *)D.bnd.p : nullptr, bndStride, (int *)D.counts.p,
-                      wantDir ? (int *)D.aln.p : nullptr, wantDir ? (int *)D.alnLen.p : nullptr);
+   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(RES_WAVES * 64), 0, st, D.pairs.as<const PairDesc>(), nPairs, D.refs.as<const int>(), D.hyps.as<const int>(), (int)wantDir,
+                      maxDir > 0 ? D.dir.as<unsigned char>() : nullptr, maxDir, maxBndT >= 0 ? D.bnd.as<Cell>() : nullptr, bndStride, D.counts.as<int>(),
+                      wantDir ? D.aln.as<int>() : nullptr, wantDir ? D.alnLen.as<int>() : nullptr);
    HIPCHECK(hipGetLastError());
-   hipLaunchKernelGGL(k_results_totals, dim3((unsigned)((U + 255) / 256), (unsigned)K), dim3(256), 0, st, (const int *)D.counts.p, U, (unsigned long long *)D.totals.p,
-                      (const PairDesc *)D.pairs.p, (const int *)D.aln.p, (const int *)D.alnLen.p, wantConf ? (int *)D.conf.p : nullptr, V);
+   hipLaunchKernelGGL(k_results_totals, dim3((unsigned)((U + 255) / 256), (unsigned)K), dim3(256), 0, st, D.counts.as<const int>(), U, D.totals.as<unsigned long long>(),
+                      D.pairs.as<const PairDesc>(), D.aln.as<const int>(), D.alnLen.as<const int>(), wantConf ? D.conf.as<int>() : nullptr, V);
    HIPCHECK(hipGetLastError());
-   HIPCHECK(hipEventRecord(D.ev[1], st));
+   HIPCHECK(D.timer.stop(st));
    std::vector<int> hCounts, hLen, hAln;
    int *cnt = counts;
-   if (!cnt) { hCounts.resize(6 * (size_t)nPairs); cnt = hCounts.data(); }
-   HIPCHECK(hipMemcpyAsync(cnt, D.counts.p, sizeof(int) * 6 * (size_t)nPairs, hipMemcpyDeviceToHost, st));
-   if (totals) HIPCHECK(hipMemcpyAsync(totals, D.totals.p, sizeof(long long) * 7 * (size_t)K, hipMemcpyDeviceToHost, st));
-   if (wantConf) HIPCHECK(hipMemcpyAsync(conf, D.conf.p, sizeof(int) * (size_t)K * W * W, hipMemcpyDeviceToHost, st));
+   if (!cnt) { hCounts.resize(6 * nP); cnt = hCounts.data(); }
+   if ((rc = D.counts.download(cnt, 6 * nP, st))) return rc;
+   if (totals && (rc = D.totals.download((unsigned long long *)totals, nTot, st))) return rc;
+   if (wantConf && (rc = D.conf.download(conf, nConf, st))) return rc;
    if (wantAln) {
-      hLen.resize((size_t)nPairs); hAln.resize(3 * (size_t)alnTotal + 1);
-      HIPCHECK(hipMemcpyAsync(hLen.data(), D.alnLen.p, sizeof(int) * (size_t)nPairs, hipMemcpyDeviceToHost, st));
-      if (alnTotal) HIPCHECK(hipMemcpyAsync(hAln.data(), D.aln.p, sizeof(int) * 3 * (size_t)alnTotal, hipMemcpyDeviceToHost, st));
+      hLen.resize(nP); hAln.resize(3 * (size_t)alnTotal + 1);
+      if ((rc = D.alnLen.download(hLen.data(), nP, st)) || (rc = D.aln.download(hAln.data(), 3 * (size_t)alnTotal, st))) return rc;
    }
    HIPCHECK(hipStreamSynchronize(st));
    float ms = 0.0f;
-   HIPCHECK(hipEventElapsedTime(&ms, D.ev[0], D.ev[1]));
+   HIPCHECK(D.timer.ms(&ms));
    r->kernelMs = ms;
    if (wantAln) {                                             // the pairs' triples, closed up
       int at = 0;

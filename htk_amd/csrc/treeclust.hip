@@ -140,10 +140,7 @@ __global__ __launch_bounds__(TS_THREADS) void k_tree_pick(const float *blk, int 
    for (int i = t; i < n * 2 * C; i += TS_THREADS) { const int k = i / (2 * C); rf[i] = nb[(size_t)cand[k] * 2 * C + (i - k * 2 * C)]; }
 }
 
-namespace {
-constexpr char tcOwner[] = "tree_cluster";
-typedef DevBufT<tcOwner> DevBuf;
-}
+DEVBUF_OWNER("tree_cluster")
 struct htkamd_tree_dev {
    DevBuf stats, cols, ans, nodes, idx, blk, rec;
    int nItems = 0, D = 0, C = 0, nQ = 0, nCols = 0, hasCols = 0, lastNodes = 0;
@@ -162,19 +159,11 @@ extern "C" int htkamd_tree_dev_open(htkamd_tree_dev **out, const float *itemStat
    if (htkamd_device_count() <= 0) { htkamd_set_error("tree_cluster: no HIP device"); return HTKAMD_ENODEV; }
    htkamd_tree_dev *t = new htkamd_tree_dev;
    t->nItems = nItems; t->D = D; t->C = 2 * D + 1; t->nQ = nQ; t->nCols = nCols; t->hasCols = itemCol != nullptr; t->st = (hipStream_t)stream;
-   int rc = t->stats.reserve(sizeof(float) * (size_t)nItems * t->C);
-   if (!rc && itemCol) rc = t->cols.reserve(sizeof(int) * (size_t)nItems);
-   if (!rc && nQ > 0) rc = t->ans.reserve((size_t)nQ * nCols);
-   hipError_t e = hipSuccess;
-   if (!rc) e = hipMemcpyAsync(t->stats.p, itemStats, sizeof(float) * (size_t)nItems * t->C, hipMemcpyHostToDevice, t->st);
-   if (!rc && e == hipSuccess && itemCol) e = hipMemcpyAsync(t->cols.p, itemCol, sizeof(int) * (size_t)nItems, hipMemcpyHostToDevice, t->st);
-   if (!rc && e == hipSuccess && nQ > 0) e = hipMemcpyAsync(t->ans.p, answers, (size_t)nQ * nCols, hipMemcpyHostToDevice, t->st);
-   if (!rc && e == hipSuccess) e = hipStreamSynchronize(t->st);                 // (the caller's tables may go after the call)
-   if (rc || e != hipSuccess) {
-      if (!rc) { htkamd_set_error("tree_cluster: upload: %s", hipGetErrorString(e)); rc = HTKAMD_EHIP; }
-      delete t;
-      return rc;
-   }
+   int rc = t->stats.upload(itemStats, (size_t)nItems * t->C, t->st);
+   if (!rc && itemCol) rc = t->cols.upload(itemCol, (size_t)nItems, t->st);
+   if (!rc && nQ > 0) rc = t->ans.upload(answers, (size_t)nQ * nCols, t->st);
+   HIPCHECK_RC(rc, devOwner, hipStreamSynchronize(t->st));                      // (the caller's tables may go after the call)
+   if (rc) { delete t; return rc; }
    *out = t;
    return HTKAMD_OK;
 }
@@ -195,15 +184,13 @@ static int ts_launch(htkamd_tree_dev *t, const htkamd_tree_node *nodes, int nNod
    const int tiles = (nQ + 1 + QB - 1) / QB;
    if (tiles > 65535) { htkamd_set_error("tree_cluster: %d questions", nQ); return HTKAMD_EINVAL; }
    int rc;
-   if ((rc = t->nodes.reserve(sizeof(htkamd_tree_node) * (size_t)nNodes))) return rc;
-   if ((rc = t->idx.reserve(sizeof(int) * (size_t)nIdx))) return rc;
-   if ((rc = t->blk.reserve(sizeof(float) * (size_t)nNodes * (nQ + 1) * 2 * C))) return rc;
-   HIPCHECK(hipMemcpyAsync(t->nodes.p, nodes, sizeof(htkamd_tree_node) * (size_t)nNodes, hipMemcpyHostToDevice, t->st));
-   HIPCHECK(hipMemcpyAsync(t->idx.p, idx, sizeof(int) * (size_t)nIdx, hipMemcpyHostToDevice, t->st));
+   if ((rc = t->nodes.upload(nodes, (size_t)nNodes, t->st))) return rc;
+   if ((rc = t->idx.upload(idx, (size_t)nIdx, t->st))) return rc;
+   if ((rc = t->blk.reserve<float>((size_t)nNodes * (nQ + 1) * 2 * C))) return rc;
    const size_t ldsBytes = sizeof(float) * (size_t)TI * C + sizeof(int) * (size_t)TI + (size_t)QB * TI;      // <= 16 KB + 256 B + 340 * 64 B
    hipLaunchKernelGGL(k_tree_split, dim3((unsigned)nNodes, (unsigned)tiles), dim3(TS_THREADS), ldsBytes, t->st,
-                      (const float *)t->stats.p, t->hasCols ? (const int *)t->cols.p : (const int *)nullptr, (const unsigned char *)t->ans.p, t->nCols, nQ, C, TI,
-                      (const htkamd_tree_node *)t->nodes.p, (const int *)t->idx.p, (float *)t->blk.p);
+                      t->stats.as<const float>(), t->hasCols ? t->cols.as<const int>() : (const int *)nullptr, t->ans.as<const unsigned char>(), t->nCols, nQ, C, TI,
+                      t->nodes.as<const htkamd_tree_node>(), t->idx.as<const int>(), t->blk.as<float>());
    HIPCHECK(hipGetLastError());
    return HTKAMD_OK;
 }
@@ -213,12 +200,12 @@ extern "C" int htkamd_tree_dev_split(htkamd_tree_dev *t, const htkamd_tree_node 
    if (!rec) { htkamd_set_error("tree_cluster: bad node batch"); return HTKAMD_EINVAL; }
    int rc = ts_launch(t, nodes, nNodes, idx, nIdx, t ? t->nQ : 0);
    if (rc) return rc;
-   const size_t recBytes = sizeof(int) * (size_t)nNodes * HTKAMD_TREE_REC(t->C);
-   if ((rc = t->rec.reserve(recBytes))) return rc;
+   const size_t nRec = (size_t)nNodes * HTKAMD_TREE_REC(t->C);
+   if ((rc = t->rec.reserve<int>(nRec))) return rc;
    hipLaunchKernelGGL(k_tree_pick, dim3((unsigned)nNodes), dim3(TS_THREADS), sizeof(float) * (size_t)(t->nQ ? t->nQ : 1), t->st,
-                      (const float *)t->blk.p, t->nQ, t->D, outlierThresh, (int *)t->rec.p);
+                      t->blk.as<const float>(), t->nQ, t->D, outlierThresh, t->rec.as<int>());
    HIPCHECK(hipGetLastError());
-   HIPCHECK(hipMemcpyAsync(rec, t->rec.p, recBytes, hipMemcpyDeviceToHost, t->st));
+   if ((rc = t->rec.download(rec, nRec, t->st))) return rc;
    HIPCHECK(hipStreamSynchronize(t->st));
    t->lastNodes = nNodes;
    return HTKAMD_OK;
@@ -240,7 +227,7 @@ extern "C" int htkamd_tree_dev_block(htkamd_tree_dev *t, int node, float *blk)
 {
    if (!t || !blk || node < 0 || node >= t->lastNodes) { htkamd_set_error("tree_cluster: no block %d", node); return HTKAMD_EINVAL; }
    const size_t n = (size_t)(t->nQ + 1) * 2 * t->C;
-   HIPCHECK(hipMemcpyAsync(blk, (const float *)t->blk.p + (size_t)node * n, sizeof(float) * n, hipMemcpyDeviceToHost, t->st));
+   HIPCHECK(hipMemcpyAsync(blk, t->blk.as<const float>() + (size_t)node * n, sizeof(float) * n, hipMemcpyDeviceToHost, t->st));
    HIPCHECK(hipStreamSynchronize(t->st));
    return HTKAMD_OK;
 }

@@ -81,21 +81,10 @@ __global__ __launch_bounds__(SY_THREADS) void k_tree_descend(const unsigned char
    leaf[i] = out;
 }
 
-namespace {
-constexpr char syOwner[] = "add_unseen";
-typedef DevBufT<syOwner> DevBuf;
-float g_kernelMs[2];
-}
+DEVBUF_OWNER("add_unseen")
+namespace { float g_kernelMs[2]; }
 
 extern "C" void htkamd_synth_last_kernel_ms(float *ms) { if (ms) { ms[0] = g_kernelMs[0]; ms[1] = g_kernelMs[1]; } }
-
-static int sy_upload(DevBuf &b, const void *src, size_t bytes, hipStream_t st)
-{
-   int rc = b.reserve(bytes ? bytes : 4);
-   if (rc) return rc;
-   if (bytes) HIPCHECK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
-   return HTKAMD_OK;
-}
 
 extern "C" int htkamd_synth_dev_run(const htkamd_synth_job *j, unsigned char *answers, int *leaf, void *stream)
 {
@@ -145,43 +134,41 @@ extern "C" int htkamd_synth_dev_run(const htkamd_synth_job *j, unsigned char *an
    if (htkamd_device_count() <= 0) { htkamd_set_error("add_unseen: no HIP device"); return HTKAMD_ENODEV; }
    hipStream_t st = (hipStream_t)stream;
    DevBuf dNames, dNameOff, dPats, dPatOff, dQPat, dAns, dTreeOff, dQuest, dNo, dYes, dPairName, dPairTree, dLeaf;
+   KernelTimer tAns, tLeaf;
    int rc;
-   if ((rc = sy_upload(dNames, j->namePool, (size_t)j->nameOff[N], st))) return rc;
-   if ((rc = sy_upload(dNameOff, j->nameOff, sizeof(int) * ((size_t)N + 1), st))) return rc;
-   if ((rc = dAns.reserve((size_t)(nQ ? nQ : 1) * N))) return rc;
-   hipEvent_t ev[4];
-   for (int k = 0; k < 4; k++) HIPCHECK(hipEventCreate(&ev[k]));
+   if ((rc = dNames.upload(j->namePool, (size_t)j->nameOff[N], st))) return rc;
+   if ((rc = dNameOff.upload(j->nameOff, (size_t)N + 1, st))) return rc;
+   if ((rc = dAns.reserve<unsigned char>((size_t)nQ * N))) return rc;
    g_kernelMs[0] = g_kernelMs[1] = 0.0f;
    if (nQ > 0) {
-      if ((rc = sy_upload(dPats, j->patPool, (size_t)j->patOff[nPat], st))) return rc;
-      if ((rc = sy_upload(dPatOff, j->patOff, sizeof(int) * ((size_t)nPat + 1), st))) return rc;
-      if ((rc = sy_upload(dQPat, j->qPat, sizeof(int) * ((size_t)nQ + 1), st))) return rc;
-      HIPCHECK(hipEventRecord(ev[0], st));
+      if ((rc = dPats.upload(j->patPool, (size_t)j->patOff[nPat], st))) return rc;
+      if ((rc = dPatOff.upload(j->patOff, (size_t)nPat + 1, st))) return rc;
+      if ((rc = dQPat.upload(j->qPat, (size_t)nQ + 1, st))) return rc;
+      HIPCHECK(tAns.start(st));
       hipLaunchKernelGGL(k_name_answers, dim3((unsigned)((N + SY_THREADS - 1) / SY_THREADS), (unsigned)((nQ + SY_QB - 1) / SY_QB)), dim3(SY_THREADS), ldsBytes, st,
-                         (const char *)dNames.p, (const int *)dNameOff.p, N, (const char *)dPats.p, (const int *)dPatOff.p, (const int *)dQPat.p, nQ, (unsigned char *)dAns.p);
+                         dNames.as<const char>(), dNameOff.as<const int>(), N, dPats.as<const char>(), dPatOff.as<const int>(), dQPat.as<const int>(), nQ, dAns.as<unsigned char>());
       HIPCHECK(hipGetLastError());
-      HIPCHECK(hipEventRecord(ev[1], st));
-      if (answers) HIPCHECK(hipMemcpyAsync(answers, dAns.p, (size_t)nQ * N, hipMemcpyDeviceToHost, st));
+      HIPCHECK(tAns.stop(st));
+      if (answers && (rc = dAns.download(answers, (size_t)nQ * N, st))) return rc;
    }
    if (j->nPairs > 0) {
-      if ((rc = sy_upload(dTreeOff, j->treeOff, sizeof(int) * ((size_t)j->nTrees + 1), st))) return rc;
-      if ((rc = sy_upload(dQuest, j->quest, sizeof(int) * (size_t)nNodes, st))) return rc;
-      if ((rc = sy_upload(dNo, j->no, sizeof(int) * (size_t)nNodes, st))) return rc;
-      if ((rc = sy_upload(dYes, j->yes, sizeof(int) * (size_t)nNodes, st))) return rc;
-      if ((rc = sy_upload(dPairName, j->pairName, sizeof(int) * (size_t)j->nPairs, st))) return rc;
-      if ((rc = sy_upload(dPairTree, j->pairTree, sizeof(int) * (size_t)j->nPairs, st))) return rc;
-      if ((rc = dLeaf.reserve(sizeof(int) * (size_t)j->nPairs))) return rc;
-      HIPCHECK(hipEventRecord(ev[2], st));
+      if ((rc = dTreeOff.upload(j->treeOff, (size_t)j->nTrees + 1, st))) return rc;
+      if ((rc = dQuest.upload(j->quest, (size_t)nNodes, st))) return rc;
+      if ((rc = dNo.upload(j->no, (size_t)nNodes, st))) return rc;
+      if ((rc = dYes.upload(j->yes, (size_t)nNodes, st))) return rc;
+      if ((rc = dPairName.upload(j->pairName, (size_t)j->nPairs, st))) return rc;
+      if ((rc = dPairTree.upload(j->pairTree, (size_t)j->nPairs, st))) return rc;
+      if ((rc = dLeaf.reserve<int>((size_t)j->nPairs))) return rc;
+      HIPCHECK(tLeaf.start(st));
       hipLaunchKernelGGL(k_tree_descend, dim3((unsigned)((j->nPairs + SY_THREADS - 1) / SY_THREADS)), dim3(SY_THREADS), 0, st,
-                         (const unsigned char *)dAns.p, N, (const int *)dTreeOff.p, (const int *)dQuest.p, (const int *)dNo.p, (const int *)dYes.p,
-                         (const int *)dPairName.p, (const int *)dPairTree.p, j->nPairs, (int *)dLeaf.p);
+                         dAns.as<const unsigned char>(), N, dTreeOff.as<const int>(), dQuest.as<const int>(), dNo.as<const int>(), dYes.as<const int>(),
+                         dPairName.as<const int>(), dPairTree.as<const int>(), j->nPairs, dLeaf.as<int>());
       HIPCHECK(hipGetLastError());
-      HIPCHECK(hipEventRecord(ev[3], st));
-      HIPCHECK(hipMemcpyAsync(leaf, dLeaf.p, sizeof(int) * (size_t)j->nPairs, hipMemcpyDeviceToHost, st));
+      HIPCHECK(tLeaf.stop(st));
+      if ((rc = dLeaf.download(leaf, (size_t)j->nPairs, st))) return rc;
    }
    HIPCHECK(hipStreamSynchronize(st));
-   if (nQ > 0) HIPCHECK(hipEventElapsedTime(&g_kernelMs[0], ev[0], ev[1]));
-   if (j->nPairs > 0) HIPCHECK(hipEventElapsedTime(&g_kernelMs[1], ev[2], ev[3]));
-   for (int k = 0; k < 4; k++) (void)hipEventDestroy(ev[k]);
+   if (nQ > 0) HIPCHECK(tAns.ms(&g_kernelMs[0]));
+   if (j->nPairs > 0) HIPCHECK(tLeaf.ms(&g_kernelMs[1]));
    return HTKAMD_OK;
 }

@@ -82,15 +82,6 @@ template <typename F> static __device__ void unit_trans_row(float *row, int N, F
 }
 
 // ------------------------------------------------------------------------------------------ host
-template <const char *Owner, typename T> int unit_upload(DevBufT<Owner> &b, const T *src, size_t n, hipStream_t s)
-{
-   const int rc = b.reserve(sizeof(T) * (n ? n : 1));
-   if (rc) return rc;
-   if (n) HIPCHECK(hipMemcpyAsync(b.p, src, sizeof(T) * n, hipMemcpyHostToDevice, s));
-   return HTKAMD_OK;
-}
-template <const char *Owner, typename T> int unit_upload(DevBufT<Owner> &b, const std::vector<T> &v, hipStream_t s) { return unit_upload(b, v.data(), v.size(), s); }
-
 // what the call itself refuses on the handle; *d: the description the model was made from, for the tool's own check (host/unit_train.c)
 static int unit_refuse_handle(const htkamd_model *m, const char *pfx, const char *tool, htkamd_model_desc *d)
 {
@@ -142,9 +133,9 @@ static int unit_tables(const char *pfx, htkamd_model *m, int nTokens, const int 
 template <const char *Owner> int unit_snapshot(const htkamd_model *m, DevBufT<Owner> &bak, hipStream_t s, UnitParams *p)
 {
    const size_t nGD = (size_t)m->G * m->D, nC = (size_t)m->C, nTp = (size_t)m->h_transOff[m->nT];
-   const int rc = bak.reserve(sizeof(float) * (2 * nGD + nC + nTp));
+   const int rc = bak.template reserve<float>(2 * nGD + nC + nTp);
    if (rc) return rc;
-   float *b = (float *)bak.p;
+   float *b = bak.template as<float>();
    HIPCHECK(hipMemcpyAsync(b, m->d_mean, sizeof(float) * nGD, hipMemcpyDeviceToDevice, s));
    HIPCHECK(hipMemcpyAsync(b + nGD, m->d_var, sizeof(float) * nGD, hipMemcpyDeviceToDevice, s));
    HIPCHECK(hipMemcpyAsync(b + 2 * nGD, m->d_compWeight, sizeof(float) * nC, hipMemcpyDeviceToDevice, s));

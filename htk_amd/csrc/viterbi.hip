@@ -457,8 +457,7 @@ __global__ void k_viterbi_trace(VitArgs a)
 }
 
 // ------------------------------------------------------------------------------------ host side
-static constexpr char vitOwner[] = "viterbi";
-typedef DevBufT<vitOwner> DevBuf;
+DEVBUF_OWNER("viterbi")
 
 struct htkamd_viterbi {
    htkamd_model *m;
@@ -482,23 +481,7 @@ extern "C" int htkamd_viterbi_create(htkamd_model *m, htkamd_viterbi **out)
    return HTKAMD_OK;
 }
 
-extern "C" void htkamd_viterbi_destroy(htkamd_viterbi *v)
-{
-   if (!v) return;
-   DevBuf *all[] = {&v->d_uttList, &v->d_utt, &v->d_mN, &v->d_mTp, &v->d_mSlot0, &v->d_slotState, &v->d_tasks, &v->d_counter, &v->d_outp, &v->d_bp,
-                  &v->d_pre, &v->d_exl, &v->d_ent, &v->d_exbp, &v->d_segStart, &v->d_segEnd, &v->d_segScore, &v->d_modStart,
-                  &v->d_modEnd, &v->d_modScore, &v->d_total, &v->d_status};
-   for (DevBuf *b : all) b->release();
-   delete v;
-}
-
-template <typename T> static int vupload(DevBuf &b, const std::vector<T> &v, hipStream_t s)
-{
-   int rc = b.reserve(sizeof(T) * (v.size() ? v.size() : 1));
-   if (rc) return rc;
-   if (!v.empty()) HIPCHECK(hipMemcpyAsync(b.p, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s));
-   return HTKAMD_OK;
-}
+extern "C" void htkamd_viterbi_destroy(htkamd_viterbi *v) { delete v; }
 
 extern "C" int htkamd_viterbi_align(htkamd_viterbi *v, const htkamd_batch_desc *b, float genBeam, void *stream)
 {
@@ -554,40 +537,39 @@ extern "C" int htkamd_viterbi_align_mode(htkamd_viterbi *v, const htkamd_batch_d
    for (int c = 0; c < 5; c++) { uttList.insert(uttList.end(), cls[c].begin(), cls[c].end()); clsOff[c + 1] = (int)uttList.size(); }
    if (uttList.empty()) uttList.push_back(0);
    int rc;
-   if ((rc = vupload(v->d_uttList, uttList, s))) return rc;
-   if ((rc = vupload(v->d_utt, v->utt, s)) || (rc = vupload(v->d_mN, v->mN, s)) || (rc = vupload(v->d_mTp, v->mTp, s)) ||
-       (rc = vupload(v->d_mSlot0, v->mSlot0, s)) || (rc = vupload(v->d_slotState, v->slotState, s)) || (rc = vupload(v->d_tasks, v->tasks, s)))
+   if ((rc = v->d_uttList.upload(uttList, s))) return rc;
+   if ((rc = v->d_utt.upload(v->utt, s)) || (rc = v->d_mN.upload(v->mN, s)) || (rc = v->d_mTp.upload(v->mTp, s)) ||
+       (rc = v->d_mSlot0.upload(v->mSlot0, s)) || (rc = v->d_slotState.upload(v->slotState, s)) || (rc = v->d_tasks.upload(v->tasks, s)))
       return rc;
-   auto nz = [](size_t x) { return x ? x : (size_t)1; };
-   if ((rc = v->d_counter.reserve(64)) || (rc = v->d_outp.reserve(4 * nz(outp))) || (rc = v->d_bp.reserve(nz(tr))) ||
-       (rc = v->d_pre.reserve(8 * nz(tr))) || (rc = v->d_exl.reserve(8 * nz(mt))) || (rc = v->d_ent.reserve(8 * nz(mt))) ||
-       (rc = v->d_exbp.reserve(nz(mt))) || (rc = v->d_segStart.reserve(4 * nz(seg))) || (rc = v->d_segEnd.reserve(4 * nz(seg))) ||
-       (rc = v->d_segScore.reserve(8 * nz(seg))) || (rc = v->d_modStart.reserve(4 * nz(mod))) || (rc = v->d_modEnd.reserve(4 * nz(mod))) ||
-       (rc = v->d_modScore.reserve(8 * nz(mod))) || (rc = v->d_total.reserve(8 * nz(U))) || (rc = v->d_status.reserve(4 * nz(U))))
+   if ((rc = v->d_counter.reserve(64)) || (rc = v->d_outp.reserve<float>(outp)) || (rc = v->d_bp.reserve<signed char>(tr)) ||
+       (rc = v->d_pre.reserve<double>(tr)) || (rc = v->d_exl.reserve<double>(mt)) || (rc = v->d_ent.reserve<double>(mt)) ||
+       (rc = v->d_exbp.reserve<signed char>(mt)) || (rc = v->d_segStart.reserve<int>(seg)) || (rc = v->d_segEnd.reserve<int>(seg)) ||
+       (rc = v->d_segScore.reserve<double>(seg)) || (rc = v->d_modStart.reserve<int>(mod)) || (rc = v->d_modEnd.reserve<int>(mod)) ||
+       (rc = v->d_modScore.reserve<double>(mod)) || (rc = v->d_total.reserve<double>((size_t)U)) || (rc = v->d_status.reserve<int>((size_t)U)))
       return rc;
    if (U == 0) return HTKAMD_OK;
 
    if (scoreMode & HTKAMD_SCORE_DIAGC) { if ((rc = htkamd_model_device_tables((htkamd_model *)m))) return rc; }
    ScoreArgs sa = htkamd_score_args(m);
-   sa.tasks = (const ScoreTask *)v->d_tasks.p; sa.nTasks = (int)v->tasks.size(); sa.X = b->dX;
-   sa.slotState = (const int *)v->d_slotState.p; sa.out = (float *)v->d_outp.p; sa.taskCounter = (int *)v->d_counter.p;
+   sa.tasks = v->d_tasks.as<const ScoreTask>(); sa.nTasks = (int)v->tasks.size(); sa.X = b->dX;
+   sa.slotState = v->d_slotState.as<const int>(); sa.out = v->d_outp.as<float>(); sa.taskCounter = v->d_counter.as<int>();
    if (m->tiedMix) {                                      // hsKind TIEDHS: PrecomputeTMix(tmBeam) per frame + SOutP's pool sum (HRec.c:1987, 493-503)
       if ((rc = htkamd_tm_score_block(m, sa, b->frameOff[U], m->tmBeam, s))) return rc;
    } else
    if ((rc = htkamd_launch_score_exact(m, sa, s, nullptr, nullptr, (scoreMode & HTKAMD_SCORE_SOUTP) != 0, (scoreMode & HTKAMD_SCORE_DIAGC) != 0))) return rc;
 
    VitArgs va;
-   va.utt = (const VitUtt *)v->d_utt.p; va.nUtt = U;
-   va.mN = (const int *)v->d_mN.p; va.mTp = (const int *)v->d_mTp.p; va.mSlot0 = (const int *)v->d_mSlot0.p;
-   va.transP = m->d_transP; va.outp = (const float *)v->d_outp.p;
-   va.bp = (signed char *)v->d_bp.p; va.pre = (double *)v->d_pre.p;
-   va.exl = (double *)v->d_exl.p; va.entAt = (double *)v->d_ent.p; va.exbp = (signed char *)v->d_exbp.p;
-   va.segStart = (int *)v->d_segStart.p; va.segEnd = (int *)v->d_segEnd.p; va.segScore = (double *)v->d_segScore.p;
-   va.modStart = (int *)v->d_modStart.p; va.modEnd = (int *)v->d_modEnd.p; va.modScore = (double *)v->d_modScore.p;
-   va.total = (double *)v->d_total.p; va.status = (int *)v->d_status.p;
+   va.utt = v->d_utt.as<const VitUtt>(); va.nUtt = U;
+   va.mN = v->d_mN.as<const int>(); va.mTp = v->d_mTp.as<const int>(); va.mSlot0 = v->d_mSlot0.as<const int>();
+   va.transP = m->d_transP; va.outp = v->d_outp.as<const float>();
+   va.bp = v->d_bp.as<signed char>(); va.pre = v->d_pre.as<double>();
+   va.exl = v->d_exl.as<double>(); va.entAt = v->d_ent.as<double>(); va.exbp = v->d_exbp.as<signed char>();
+   va.segStart = v->d_segStart.as<int>(); va.segEnd = v->d_segEnd.as<int>(); va.segScore = v->d_segScore.as<double>();
+   va.modStart = v->d_modStart.as<int>(); va.modEnd = v->d_modEnd.as<int>(); va.modScore = v->d_modScore.as<double>();
+   va.total = v->d_total.as<double>(); va.status = v->d_status.as<int>();
    va.genBeam = genBeam;
    for (int c = 3; c >= 0; c--) {                        // the longest chains first
-      va.uttList = (const int *)v->d_uttList.p + clsOff[c]; va.nList = clsOff[c + 1] - clsOff[c];
+      va.uttList = v->d_uttList.as<const int>() + clsOff[c]; va.nList = clsOff[c + 1] - clsOff[c];
       if (va.nList <= 0) continue;
       if (c == 0) hipLaunchKernelGGL((k_viterbi_w<VMAXN, 1>), dim3((va.nList + 3) / 4), dim3(256), 0, s, va);
       else if (c == 1) hipLaunchKernelGGL((k_viterbi_w<VMAXN, 2>), dim3(va.nList), dim3(128), 0, s, va);
@@ -595,7 +577,7 @@ extern "C" int htkamd_viterbi_align_mode(htkamd_viterbi *v, const htkamd_batch_d
       else hipLaunchKernelGGL((k_viterbi_w<VMAXN, 8>), dim3(va.nList), dim3(512), 0, s, va);
       HIPCHECK(hipGetLastError());
    }
-   va.uttList = (const int *)v->d_uttList.p + clsOff[4]; va.nList = clsOff[5] - clsOff[4];
+   va.uttList = v->d_uttList.as<const int>() + clsOff[4]; va.nList = clsOff[5] - clsOff[4];
    if (va.nList > 0) {
       const size_t lds = sizeof(double) * ((size_t)maxQ * (m->maxN + 1) + 2 * (size_t)maxQ) + 2 * (size_t)maxQ + 64;
       if (lds > 150 * 1024) { htkamd_set_error("viterbi_align: %d models of up to %d states need %zu bytes of LDS", maxQ, m->maxN, lds); return HTKAMD_EMODEL; }
@@ -641,7 +623,7 @@ extern "C" int htkamd_viterbi_results(htkamd_viterbi *v, int *segStart, int *seg
 int htkamd_viterbi_device_results(htkamd_viterbi *v, htkamd_viterbi_dev *out)
 {
    if (!v || !out) { htkamd_set_error("viterbi_device_results: NULL"); return HTKAMD_EINVAL; }
-   out->segStart = (const int *)v->d_segStart.p; out->segEnd = (const int *)v->d_segEnd.p;
-   out->total = (const double *)v->d_total.p; out->status = (const int *)v->d_status.p;
+   out->segStart = v->d_segStart.as<const int>(); out->segEnd = v->d_segEnd.as<const int>();
+   out->total = v->d_total.as<const double>(); out->status = v->d_status.as<const int>();
    return HTKAMD_OK;
 }
