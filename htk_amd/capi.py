@@ -1118,6 +1118,180 @@ def regtree_probe(mean, sum, sqr, occ, has, steps, stream=None):
     return [(counts[s].copy(), fig[s].copy()) if st[s, 0] else fig[s, 0].copy() for s in range(nS)], lst[:G]
 
 
+class MllrConfig(C.Structure):
+    _fields_ = [("splitThresh", C.c_float), ("minOccThresh", C.c_float), ("useBias", C.c_int), ("nBlocks", C.c_int), ("blockSize", C.POINTER(C.c_int))]
+
+
+MLLR_NOSET = 1
+
+
+def mllr_config(split_thresh=0.0, min_occ_thresh=0.0, use_bias=True, blocks=None):
+    """(htkamd_mllr_config, the array its blockSize points into).  blocks None: one block of the vector size."""
+    b = None if blocks is None else (C.c_int * len(blocks))(*[int(x) for x in blocks])
+    return MllrConfig(split_thresh, min_occ_thresh, int(bool(use_bias)), 0 if b is None else len(blocks), b), b
+
+
+def _tree_tables(children):
+    n = len(children)
+    return n, np.array([c[0] for c in children], np.int32), np.array([c[1] for c in children], np.int32)
+
+
+class Mllr(_Handle):
+    """A set of MLLR mean transforms (htkamd_xformset): Mllr.estimate from a pass's statistics over a regression class tree, Mllr.read from a
+    transform file, Mllr.from_tables from matrices.  Transforms and base classes count from 1."""
+    _destroy = "htkamd_xformset_destroy"
+
+    def __init__(self, h, status=0):
+        self.h, self.status = h, status      # status MLLR_NOSET: the root's occupation did not exceed the threshold, the set has no transform
+
+    @staticmethod
+    def check(mmf, tree, **cfg):
+        c, keep = mllr_config(**cfg)
+        check(lib().htkamd_mllr_check(mmf.h, tree.h if tree is not None else None, C.byref(c)), "mllr_check")
+
+    @classmethod
+    def estimate(cls, mmf, model, accs, tree, stream=None, **cfg):
+        c, keep = mllr_config(**cfg)
+        h = C.c_void_p()
+        rc = lib().htkamd_mllr_estimate(mmf.h, model.h if model is not None else None, accs.h if accs is not None else None,
+                                        tree.h if tree is not None else None, C.byref(c), C.byref(h), _stream(stream))
+        if rc != MLLR_NOSET:
+            check(rc, "mllr_estimate")
+        return cls(h, rc)
+
+    @classmethod
+    def read(cls, path):
+        h = C.c_void_p()
+        check(lib().htkamd_xformset_read(str(path).encode(), C.byref(h)), "xformset_read")
+        return cls(h)
+
+    @classmethod
+    def from_tables(cls, A, bias, class_xform, blocks=None, name="mllr", base_name="rtree.base"):
+        A = np.ascontiguousarray(A, np.float32)
+        nX, D = A.shape[0], A.shape[1]
+        b = None if bias is None else np.ascontiguousarray(bias, np.float32).reshape(nX, D)
+        bl = np.array([D] if blocks is None else blocks, np.int32); cx = np.ascontiguousarray(class_xform, np.int32)
+        h = C.c_void_p()
+        check(lib().htkamd_xformset_from_tables(D, len(bl), _p(bl), int(b is not None), nX, _p(A), _p(b), len(cx), _p(cx), name.encode(), base_name.encode(),
+                                                C.byref(h)), "xformset_from_tables")
+        return cls(h)
+
+    def set_names(self, name=None, base_name=None):
+        check(lib().htkamd_xformset_set_names(self.h, name.encode() if name else None, base_name.encode() if base_name else None), "xformset_set_names")
+
+    @property
+    def num_xforms(self) -> int:
+        return lib().htkamd_xformset_num_xforms(self.h)
+
+    @property
+    def vec_size(self) -> int:
+        return lib().htkamd_xformset_vec_size(self.h)
+
+    @property
+    def blocks(self):
+        n = lib().htkamd_xformset_blocks(self.h, None, 0)
+        b = (C.c_int * max(n, 1))()
+        lib().htkamd_xformset_blocks(self.h, b, n)
+        return list(b[:n])
+
+    @property
+    def class_xform(self):
+        return [lib().htkamd_xformset_class_xform(self.h, c) for c in range(1, lib().htkamd_xformset_num_classes(self.h) + 1)]
+
+    @property
+    def xform_nodes(self):
+        return [lib().htkamd_xformset_xform_node(self.h, k) for k in range(1, self.num_xforms + 1)]
+
+    def xform(self, k: int):
+        """(A float32[D, D], bias float32[D] or None) of transform k."""
+        D = self.vec_size
+        A, b = np.zeros((D, D), np.float32), np.zeros(D, np.float32)
+        check(lib().htkamd_xformset_xform(self.h, k, _p(A), _p(b)), "xformset_xform")
+        return A, (b if lib().htkamd_xformset_use_bias(self.h) else None)
+
+    def node_occ(self):
+        n = lib().htkamd_xformset_node_occ(self.h, None, 0)
+        o = np.zeros(max(n, 1), np.float64)
+        lib().htkamd_xformset_node_occ(self.h, _p(o), n)
+        return o[:n]
+
+    def kernel_ms(self):
+        ms = (C.c_float * 3)()
+        lib().htkamd_xformset_kernel_ms(self.h, ms)
+        return list(ms)
+
+    def write(self, path):
+        check(lib().htkamd_xformset_write(self.h, str(path).encode()), "xformset_write")
+
+    def apply(self, model, gauss_class=None, stream=None):
+        gc = None if gauss_class is None else np.ascontiguousarray(gauss_class, np.int32)
+        check(lib().htkamd_mllr_apply(model.h, self.h, _p(gc), _stream(stream)), "mllr_apply")
+
+    @staticmethod
+    def restore(model, stream=None):
+        check(lib().htkamd_mllr_restore(model.h, _stream(stream)), "mllr_restore")
+
+    @staticmethod
+    def gauss_classes(mmf, tree):
+        cls = np.zeros(max(mmf.desc.numGauss, 1), np.int32)
+        check(lib().htkamd_mllr_gauss_classes(mmf.h, tree.h, _p(cls)), "mllr_gauss_classes")
+        return cls[:mmf.desc.numGauss]
+
+
+def mllr_select(children, node_occ, thresh):
+    """ParseNode's choice (htkamd_mllr_select): (status, [node of transform 1..], [transform of class 1..])."""
+    n, left, right = _tree_tables(children)
+    occ = np.ascontiguousarray(node_occ, np.float64)
+    nterm = int((left == 0).sum())
+    nX = C.c_int(0); xn = np.zeros(n, np.int32); cx = np.zeros(max(nterm, 1), np.int32)
+    rc = lib().htkamd_mllr_select(n, _p(left), _p(right), _p(occ), float(thresh), C.byref(nX), _p(xn), _p(cx))
+    if rc != MLLR_NOSET:
+        check(rc, "mllr_select")
+    return rc, xn[:nX.value].tolist(), cx[:nterm].tolist()
+
+
+def mllr_record_offsets(D, blocks):
+    """Row i's place in a node's record of mllr_probe's statistics: (offset, block start, block size); and the record's length."""
+    off, rows = 0, []
+    c0 = 0
+    for bs in blocks:
+        for _ in range(bs):
+            rows.append((off, c0, bs)); off += (bs + 1) * (bs + 2) // 2 + bs + 1
+        c0 += bs
+    return rows, off + 1
+
+
+def mllr_probe(mean, var, occ, sp_sum, cls, children, stream=None, want_stats=True, **cfg):
+    """Test aid (htkamd_mllr_probe): the device steps of Mllr.estimate over tables.  Returns a dict: status (0, MLLR_NOSET), stats
+    float64[nNodes, record] (mllr_record_offsets), node_occ, x_node, class_xform, A float32[nX, D, D], bias float32[nX, D], W float64[nX, D,
+    maxBlock+1], ms [3].  HTKAMD_ERANGE raises HtkAmdError with .rc, .bad_node, .bad_row."""
+    mean = np.ascontiguousarray(mean, np.float32); var = np.ascontiguousarray(var, np.float32)
+    occ = np.ascontiguousarray(occ, np.float64); sp = np.ascontiguousarray(sp_sum, np.float64); cls = np.ascontiguousarray(cls, np.int32)
+    G, D = mean.shape
+    if var.shape != (G, D) or occ.shape != (G,) or sp.shape != (G, D) or cls.shape != (G,):
+        raise HtkAmdError("mllr_probe: bad shapes")
+    c, keep = mllr_config(**cfg)
+    blocks = [D] if c.nBlocks == 0 else list(keep)
+    n, left, right = _tree_tables(children)
+    nterm = int((left == 0).sum())
+    rec = lib().htkamd_mllr_record_len(D, len(blocks), (C.c_int * len(blocks))(*blocks))
+    stats = np.zeros((n, max(rec, 1)), np.float64) if want_stats else None
+    maxd = max(blocks) + 1
+    nocc = np.zeros(n, np.float64); nX = C.c_int(0); xn = np.zeros(n, np.int32); cx = np.zeros(max(nterm, 1), np.int32)
+    A = np.zeros((n, D, D), np.float32); b = np.zeros((n, D), np.float32); W = np.zeros((n, D, maxd), np.float64)
+    bn, br = C.c_int(0), C.c_int(0); ms = (C.c_float * 3)()
+    rc = lib().htkamd_mllr_probe(_p(mean), _p(var), _p(occ), _p(sp), _p(cls), G, D, n, _p(left), _p(right), C.byref(c), _p(stats), 0 if stats is None else stats.size,
+                                 _p(nocc), C.byref(nX), _p(xn), _p(cx), _p(A), _p(b), _p(W), C.byref(bn), C.byref(br), ms, _stream(stream))
+    if rc not in (0, MLLR_NOSET):
+        try:
+            check(rc, "mllr_probe")
+        except HtkAmdError as e:
+            e.bad_node, e.bad_row = bn.value, br.value
+            raise
+    k = nX.value
+    return dict(status=rc, stats=stats, node_occ=nocc, x_node=xn[:k].tolist(), class_xform=cx[:nterm].tolist(), A=A[:k], bias=b[:k], W=W[:k], ms=list(ms))
+
+
 class ClusterSpec(C.Structure):
     _fields_ = [("byCount", C.c_int), ("value", C.c_float), ("macro", C.c_char_p), ("items", C.c_char_p)]
 
@@ -2194,4 +2368,4 @@ STRUCTS = {"htkamd_model_desc": ModelDesc, "htkamd_accs_layout": AccsLayout, "ht
            "htkamd_net_desc": NetDesc, "htkamd_decode_config": DecodeConfig, "htkamd_lattice_out": LatticeOut, "htkamd_lattice_align_out": LatticeAlignOut,
            "htkamd_lattice_align": LatticeAlign, "htkamd_lattice": Lattice, "htkamd_decode_out": DecodeOut, "htkamd_results_config": ResultsConfig,
            "htkamd_results_report": ResultsReport, "htkamd_lat_scales": LatScales, "htkamd_latset_view": LatSetView, "htkamd_latset_best_out": LatBestOut,
-           "htkamd_latset_fb_out": LatFbOut}
+           "htkamd_latset_fb_out": LatFbOut, "htkamd_mllr_config": MllrConfig}

@@ -88,6 +88,32 @@ int  htkamd_rt_dev_list(htkamd_rt_dev *t, int *list /*[G]*/);
 float htkamd_rt_dev_kernel_ms(const htkamd_rt_dev *t);
 void htkamd_rt_dev_close(htkamd_rt_dev *t);
 
+/* ---- MLLR mean transforms: the device side (csrc/mllr.hip) as host/mllr.c drives it ----
+ * A job: the set's Gaussians (mean, var [G][D]; occ [G] and spSum [G][D] as the floats the reference keeps), the base classes as member
+ * lists (class c: mem[memOff[c] .. memOff[c+1])), the tree with 0-based nodes (left / right: -1 for a terminal; termClass: a terminal's
+ * class, -1 for an inner node; inner: the inner nodes, children before parents).  dev_stats runs the class statistics and the sums up the
+ * tree and brings back the node occupations; a node's record is htkamd_mllr_record_len doubles: per row i of a block of size bs the packed
+ * lower triangle of G_i ((bs+1)(bs+2)/2), then k_i (bs+1); the node's occupation last. */
+#define HTKAMD_MLLR_MAXBLOCK 64
+typedef struct {
+   int G, D, nBlocks, useBias, nClass, nNodes, nInner;
+   const int *blockSize;
+   const float *mean, *var, *occ, *spSum;
+   float minOcc;
+   const int *memOff, *mem, *left, *right, *termClass, *inner;
+} htkamd_mllr_job;
+typedef struct htkamd_mllr_dev htkamd_mllr_dev;
+struct htkamd_model;
+int  htkamd_mllr_dev_stats(const htkamd_mllr_job *job, htkamd_mllr_dev **out, double *nodeOcc /*[nNodes]*/, void *stream);
+int  htkamd_mllr_dev_fetch(htkamd_mllr_dev *t, double *stats /*[nNodes][record]*/);
+int  htkamd_mllr_dev_solve(htkamd_mllr_dev *t, int nX, const int *xNode, float *A /*[nX][D][D]*/, float *bias /*[nX][D]*/, double *W /*[nX][D][maxd] or NULL*/,
+                           int *badX, int *badRow);
+void htkamd_mllr_dev_times(const htkamd_mllr_dev *t, float *ms /*[3]: statistics, tree sums, solves*/);
+void htkamd_mllr_dev_close(htkamd_mllr_dev *t);
+int  htkamd_mllr_dev_apply(struct htkamd_model *m, int nX, const float *A, const float *bias /*or NULL*/, const int *gaussX /*[G]*/, const int *rowC0, const int *rowBs, void *stream);
+int  htkamd_mllr_dev_restore(struct htkamd_model *m, void *stream);
+int  htkamd_mllr_model_state(const char *who, const struct htkamd_model *m, int *D, int *G, int *adapted);   /* mllr.hip: what host/mllr.c may know of a model; EMODEL + reason for a set apply refuses */
+
 /* ---- unseen models from the trees: the device side (csrc/treesynth.hip) as host/treeclust.c drives it ----
  * Names and patterns are NUL-terminated strings in byte pools: name n at namePool + nameOff[n] (nameOff[N] = the pool's size), pattern k
  * at patPool + patOff[k], question q owns patterns qPat[q] .. qPat[q+1]-1.  The trees' node tables lie behind one another (tree t: nodes
@@ -231,6 +257,7 @@ struct htkamd_model {
    int    fullc, FPS;
    float *h_invCov, *d_fparam;
    double minLogExp;
+   float *d_mllrMean;          /* htkamd_mllr_apply (mllr.hip): the means as they were, [G*D]; NULL = the set is not adapted */
 };
 
 void htkamd_outp_ring_free(void *ring);                      /* gmm_exact.hip */

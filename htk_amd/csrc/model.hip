@@ -500,6 +500,7 @@ extern "C" void htkamd_model_destroy(htkamd_model *m)
       if (a.d != NOF) (void)hipFree(field(m, a.d));
    }
    (void)hipFree(m->d_updScratch);
+   (void)hipFree(m->d_mllrMean);
    htkamd_outp_ring_free(m->obRing);
    if (m->h_updPin) (void)hipHostFree(m->h_updPin);
    if (m->evUpd) (void)hipEventDestroy((hipEvent_t)m->evUpd);

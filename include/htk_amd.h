@@ -659,6 +659,70 @@ int htkamd_model_update_device(htkamd_model *m, htkamd_accs *accs, const htkamd_
    pass has to be repeated (a minimum duration changed: rare).  One update in flight per model. */
 int htkamd_model_update_device_begin(htkamd_model *m, htkamd_accs *accs, const htkamd_update_config *cfg, void *stream);
 int htkamd_model_update_device_end(htkamd_model *m, htkamd_update_stats *stats);
+
+/* MLLR mean transforms of one speaker over a regression class tree (htkamd_mmf_regtree): what HERest -u a estimates at transform time (HAdapt.c), from the statistics of any
+   forward-backward pass over the speaker's data.  One-stream DIAGC continuous sets.  A separate surface: no pass, update or decoder changes.
+     config           : splitThresh SPLITTHRESH (<= 0: MLLRMEANSPLITTHRESH's default 1000), minOccThresh MINOCCTHRESH, useBias USEBIAS,
+                        blockSize[nBlocks] BLOCKSIZE (nBlocks 0: one block of the vector size; a block has at most 64 rows).
+     mllr_check       : the refusals alone, no device (HTKAMD_EMODEL / HTKAMD_EINVAL and the reason): sets with more than one stream, FULLC,
+                        tied-mixture and discrete sets; no tree (ADAPTKIND = BASE); blocks that do not sum to the vector size; a tree with
+                        a component that is no Gaussian of the set.
+     mllr_estimate    : per Gaussian occ = muOcc and spSum = the plain sum of gamma o.  htkamd_accs holds mu = sum of gamma (o - mean), so
+                        spSum = mu + occ * mean, formed in fp64 and rounded to float once (the reference keeps occ and spSum as floats).
+                        On the device (csrc/mllr.hip): G and k of every base class as AccMLLRPDFStats (:1709) forms them -- float factors in
+                        the reference's order, fp64 sums in a fixed order, no atomics --, the sums up the tree (the reference re-accumulates
+                        every node from its Gaussians: another fp64 order), and per chosen node and row the solve of G w = k in fp64.
+                        Which nodes get a transform, their numbering and the classes' transforms are ParseNode's (:1547) with the strict >.
+                        Returns HTKAMD_OK and the set; HTKAMD_MLLR_NOSET (positive; a set without transforms) when the root's occupation
+                        does not exceed the threshold; HTKAMD_ERANGE, naming node and row, when a row's G is not positive definite (the
+                        reference's InvSVD would zero the small singular values; here nothing is estimated on such statistics).
+     xformset_*       : accessors (transforms and classes count from 1; xform gives A as [D][D], zero outside the blocks; node_occ
+                        SetNodeOcc's occupations by node; kernel_ms the device time of statistics, tree sums and solves);
+                        write / read: the text form of a transform file as SaveOneXForm (HModel.c:4804) writes it for -K, byte for byte.
+                        read refuses, by name: <PARENTXFORM>, <XFORMKIND> other than MLLRMEAN, <ADAPTKIND> other than TREE, binary files.
+     mllr_apply       : mean' = A mean + b for every Gaussian of a class with a transform (float products, float sums in index order, the
+                        bias last), into the model's mean table; every derived scoring table follows as after htkamd_model_update_device.
+                        gaussClass[G]: the base class (from 1; 0 none) of every Gaussian, or NULL for a set that mllr_estimate made.
+                        The original means are kept: mllr_restore puts them back bit for bit.  A second apply without a restore is refused
+                        (parent transforms are not supported), and so are sets with shared mean vectors (mllr_check and mllr_estimate
+                        refuse those too).  While a model is adapted its parameters are not to be replaced: htkamd_model_update*,
+                        htkamd_model_set_params and the unit trainers do not know of the kept means, and a later mllr_restore would put
+                        the means of before the apply over theirs.  Restore first, then re-estimate.
+   Diagnostic entry point (a test aid, as htkamd_regtree_probe is one):
+     mllr_probe       : the device steps over a caller's tables: mean, var [G][D], occ [G], spSum [G][D], the class (from 1; 0 none) of
+                        every Gaussian, the tree (children from 1, 0 0 a terminal; classes count the terminals in node order).  stats
+                        [nNodes][htkamd_mllr_record_len] (or NULL): per row i of a block of size bs the lower triangle of G_i packed by
+                        rows ((bs+1)(bs+2)/2, the bias row and column last), then k_i (bs+1); the node's occupation is the record's last
+                        word.  A [nNodes][D][D], bias [nNodes][D], W [nNodes][D][maxBlock+1] (or NULL; the fp64 rows) of the first nX. */
+#define HTKAMD_MLLR_NOSET 1
+typedef struct htkamd_xformset htkamd_xformset;
+typedef struct { float splitThresh, minOccThresh; int useBias, nBlocks; const int *blockSize; } htkamd_mllr_config;
+int  htkamd_mllr_check(const htkamd_mmf *s, const htkamd_regtree *t, const htkamd_mllr_config *cfg);
+int  htkamd_mllr_estimate(htkamd_mmf *s, htkamd_model *m, htkamd_accs *a, const htkamd_regtree *t, const htkamd_mllr_config *cfg, htkamd_xformset **out, void *stream);
+int  htkamd_mllr_gauss_classes(const htkamd_mmf *s, const htkamd_regtree *t, int *cls /*[numGauss]*/);
+int  htkamd_mllr_select(int nNodes, const int *left, const int *right, const double *nodeOcc, float thresh, int *nX, int *xNode /*[nNodes]*/, int *classX /*[terminals]*/);
+int  htkamd_mllr_apply(htkamd_model *m, const htkamd_xformset *x, const int *gaussClass /*[numGauss] or NULL*/, void *stream);
+int  htkamd_mllr_restore(htkamd_model *m, void *stream);
+int  htkamd_xformset_from_tables(int D, int nBlocks, const int *blockSize, int useBias, int nX, const float *A /*[nX][D][D]*/, const float *bias /*[nX][D]*/, int nClass,
+                                 const int *classX, const char *name, const char *baseName, htkamd_xformset **out);
+int  htkamd_xformset_set_names(htkamd_xformset *x, const char *name /*or NULL*/, const char *baseName /*or NULL*/);
+int  htkamd_xformset_num_xforms(const htkamd_xformset *x);
+int  htkamd_xformset_num_classes(const htkamd_xformset *x);
+int  htkamd_xformset_vec_size(const htkamd_xformset *x);
+int  htkamd_xformset_use_bias(const htkamd_xformset *x);
+int  htkamd_xformset_blocks(const htkamd_xformset *x, int *blockSize /*[cap] or NULL*/, int cap);
+int  htkamd_xformset_class_xform(const htkamd_xformset *x, int baseClass);
+int  htkamd_xformset_xform_node(const htkamd_xformset *x, int xform);
+int  htkamd_xformset_xform(const htkamd_xformset *x, int xform, float *A /*[D][D] or NULL*/, float *bias /*[D] or NULL*/);
+int  htkamd_xformset_node_occ(const htkamd_xformset *x, double *occ /*[cap] or NULL*/, int cap);
+void htkamd_xformset_kernel_ms(const htkamd_xformset *x, float *ms /*[3]*/);
+int  htkamd_xformset_write(const htkamd_xformset *x, const char *path);
+int  htkamd_xformset_read(const char *path, htkamd_xformset **out);
+void htkamd_xformset_destroy(htkamd_xformset *x);
+size_t htkamd_mllr_record_len(int D, int nBlocks, const int *blockSize);
+int  htkamd_mllr_probe(const float *mean, const float *var, const double *occ, const double *spSum, const int *cls, int G, int D, int nNodes, const int *left,
+                       const int *right, const htkamd_mllr_config *cfg, double *stats, size_t statsCap, double *nodeOcc, int *nX, int *xNode, int *classX,
+                       float *A, float *bias, double *W, int *badNode, int *badRow, float *ms, void *stream);
 /* Current parameters (DIAGC variances, linear weights, log transitions); any pointer may be NULL. */
 int htkamd_model_get_params(htkamd_model *m, float *mean, float *var, float *gconst, float *compWeight, float *transP);
 
