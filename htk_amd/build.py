@@ -15,9 +15,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libhtk_amd.so")
-HIP_SRCS = ["csrc/model.hip", "csrc/gmm_exact.hip", "csrc/gmm_full.hip", "csrc/gmm_mfma.hip", "csrc/gmm_bf16.hip", "csrc/gmm_f16.hip", "csrc/fb_kernels.hip", "csrc/fb_wave.hip", "csrc/fb_state.hip", "csrc/fb_lr.hip", "csrc/fb.hip", "csrc/viterbi.hip", "csrc/decode.hip", "csrc/decode_n.hip", "csrc/decode_ord.hip", "csrc/decode_set.hip", "csrc/mfcc.hip", "csrc/cepsnorm.hip", "csrc/inputxform.hip", "csrc/update.hip", "csrc/comm.hip", "csrc/treeclust.hip", "csrc/datacluster.hip", "csrc/treesynth.hip", "csrc/regtree.hip", "csrc/mllr.hip", "csrc/hinit.hip", "csrc/hrest.hip", "csrc/results.hip", "csrc/latrescore.hip"]
-C_SRCS = ["host/prep.c", "host/update.c", "host/fbank.c", "host/accio.c", "host/parmfile.c", "host/cepsnorm.c", "host/mmf.c", "host/labio.c", "host/net.c", "host/lattice.c", "host/slfout.c", "host/treeclust.c", "host/treesynth.c", "host/regtree.c", "host/mllr.c", "host/hinit.c", "host/hrest.c", "host/unit_train.c", "host/results.c", "host/latrescore.c", "host/htktext.c"]
-HEADERS = ["csrc/fb_lr_lean.inc", "csrc/internal.h", "csrc/kernels.h", "csrc/hipcheck.h", "csrc/devbuf.h", "csrc/ladd.h", "csrc/wavegrp.h", "csrc/fb_state.h", "csrc/decode.h", "csrc/decode_dev.h", "csrc/decode_ord.h", "csrc/hinit_seg.h", "csrc/gauss_derive.h", "csrc/unit_train.h", "csrc/results.h", "csrc/latrescore.h", "host/mmf_priv.h", "host/htktext.h", "../include/htk_amd.h"]
+HIP_SRCS = ["csrc/model.hip", "csrc/gmm_exact.hip", "csrc/gmm_full.hip", "csrc/gmm_mfma.hip", "csrc/gmm_bf16.hip", "csrc/gmm_f16.hip", "csrc/fb_kernels.hip", "csrc/fb_wave.hip", "csrc/fb_state.hip", "csrc/fb_lr.hip", "csrc/fb.hip", "csrc/viterbi.hip", "csrc/decode.hip", "csrc/decode_n.hip", "csrc/decode_ord.hip", "csrc/decode_set.hip", "csrc/mfcc.hip", "csrc/cepsnorm.hip", "csrc/inputxform.hip", "csrc/update.hip", "csrc/comm.hip", "csrc/treeclust.hip", "csrc/datacluster.hip", "csrc/treesynth.hip", "csrc/regtree.hip", "csrc/mllr.hip", "csrc/hinit.hip", "csrc/hrest.hip", "csrc/results.hip", "csrc/latrescore.hip", "csrc/lstats.hip", "csrc/netbuild.hip"]
+C_SRCS = ["host/prep.c", "host/update.c", "host/fbank.c", "host/accio.c", "host/parmfile.c", "host/cepsnorm.c", "host/mmf.c", "host/labio.c", "host/net.c", "host/lattice.c", "host/slfout.c", "host/treeclust.c", "host/treesynth.c", "host/regtree.c", "host/mllr.c", "host/hinit.c", "host/hrest.c", "host/unit_train.c", "host/results.c", "host/latrescore.c", "host/htktext.c", "host/lstats.c", "host/netbuild.c"]
+HEADERS = ["csrc/fb_lr_lean.inc", "csrc/internal.h", "csrc/kernels.h", "csrc/hipcheck.h", "csrc/devbuf.h", "csrc/ladd.h", "csrc/wavegrp.h", "csrc/fb_state.h", "csrc/decode.h", "csrc/decode_dev.h", "csrc/decode_ord.h", "csrc/hinit_seg.h", "csrc/gauss_derive.h", "csrc/unit_train.h", "csrc/results.h", "csrc/latrescore.h", "csrc/lstats.h", "csrc/lmscan.h", "host/mmf_priv.h", "host/htktext.h", "../include/htk_amd.h"]
 ARCH = "gfx950"
 # the tolerance-class scoring kernel never sees NaNs: lets v_max_f32 go without the IEEE canonicalisation of its operands
 EXTRA_FLAGS = {"csrc/gmm_mfma.hip": ["-fno-honor-nans"], "csrc/gmm_bf16.hip": ["-fno-honor-nans"], "csrc/gmm_f16.hip": ["-fno-honor-nans"],

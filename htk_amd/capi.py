@@ -1783,6 +1783,11 @@ class Net(_Handle):
             arr = (C.c_char_p * len(words))(*[w.encode() for w in words])
             check(L.htkamd_net_build_words(arr, len(words), boundary.encode() if boundary else None, dictionary.encode(),
                                            mmf.h, C.byref(self.h)), "net_build_words")
+        self._fill()
+
+    def _fill(self):
+        """What the holder keeps of a built network."""
+        L = lib()
         self.desc = L.htkamd_net_get(self.h).contents
         self.out_syms = [L.htkamd_net_out_sym(self.h, k).decode() for k in range(self.desc.nProns)]
         self.word_names = [L.htkamd_net_word_name(self.h, k).decode() for k in range(self.desc.nProns)]
@@ -2369,3 +2374,192 @@ STRUCTS = {"htkamd_model_desc": ModelDesc, "htkamd_accs_layout": AccsLayout, "ht
            "htkamd_lattice_align": LatticeAlign, "htkamd_lattice": Lattice, "htkamd_decode_out": DecodeOut, "htkamd_results_config": ResultsConfig,
            "htkamd_results_report": ResultsReport, "htkamd_lat_scales": LatScales, "htkamd_latset_view": LatSetView, "htkamd_latset_best_out": LatBestOut,
            "htkamd_latset_fb_out": LatFbOut, "htkamd_mllr_config": MllrConfig}
+
+
+# ---- label statistics and bigram models (HLStats), word networks (HBuild) ----
+
+LS_DURS, LS_LIST, LS_COUNTS = 1, 2, 4
+LM_BACKOFF, LM_MATRIX = 0, 1
+
+
+def _str_array(words):
+    return (C.c_char_p * max(len(words), 1))(*[w.encode() for w in words])
+
+
+def read_word_list(path: str):
+    """The first string of every line: HLStats' label list, HBuild's word list."""
+    out = []
+    for line in open(path, encoding="latin-1"):
+        f = line.split()
+        if f:
+            out.append(f[0])
+    return out
+
+
+def lstats_probe(V, utts, enter, exit_, wave_cap=None, group_cap=None, times=None, stream=None):
+    """htkamd_lstats_probe: the device chain over plain id lists -> dict(count, rowOff, succ, cnt[, durSum, durMin, durMax])."""
+    L = lib()
+    b = _pack(utts, np.int32, who="lstats_probe")
+    ids, off = b
+    n = len(ids) + len(utts)
+    count, rowOff = np.zeros(V, np.int32), np.zeros(V + 1, np.int32)
+    succ, cnt = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    st = en = None
+    dur = [None, None, None]
+    if times is not None:
+        st = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int64)[:, 0] for t in times]) if len(ids) else np.zeros(0, np.int64))
+        en = np.ascontiguousarray(np.concatenate([np.asarray(t, np.int64)[:, 1] for t in times]) if len(ids) else np.zeros(0, np.int64))
+        dur = [np.zeros(V, np.int64) for _ in range(3)]
+    check(L.htkamd_lstats_probe(V, len(utts), _p(off), _p(ids), _p(st), _p(en), enter, exit_, wave_cap or L.htkamd_lstats_wave_cap(), group_cap or L.htkamd_lstats_group_cap(),
+                                _p(count), _p(dur[0]), _p(dur[1]), _p(dur[2]), _p(rowOff), _p(succ), _p(cnt), n, _stream(stream)), "lstats_probe")
+    out = dict(count=count, rowOff=rowOff, succ=succ[:rowOff[V]].copy(), cnt=cnt[:rowOff[V]].copy())
+    if times is not None:
+        out.update(durSum=dur[0], durMin=dur[1], durMax=dur[2])
+    return out
+
+
+class LabelStats(_Handle):
+    """htkamd_lstats holder: HLStats for a batch of label sequences (csrc/lstats.hip, host/lstats.c)."""
+    _destroy = "htkamd_lstats_destroy"
+
+    def __init__(self, words, enter: str = "!ENTER", exit: str = "!EXIT"):
+        self.h = C.c_void_p()
+        check(lib().htkamd_lstats_create(_str_array(words), len(words), enter.encode(), exit.encode(), C.byref(self.h)), "lstats_create")
+        self.n = lib().htkamd_lstats_nwords(self.h)
+        self.words = [lib().htkamd_lstats_word(self.h, i).decode("latin-1") for i in range(self.n + 1)]
+
+    def id(self, name: str) -> int:
+        return lib().htkamd_lstats_id(self.h, name.encode("latin-1"))
+
+    def ids_of(self, labels_handle):
+        """(ids, times [n, 2]) of a label list handle (Mlf.entries(), htkamd_labels_read)."""
+        L = lib()
+        n = L.htkamd_labels_count(labels_handle)
+        ids, st, en = np.zeros(n, np.int32), np.zeros(n, np.int64), np.zeros(n, np.int64)
+        check(L.htkamd_lstats_ids(self.h, labels_handle, _p(ids), _p(st), _p(en)), "lstats_ids")
+        return ids, np.stack([st, en], 1)
+
+    def count(self, utts, times=None, stream=None):
+        """utts: per utterance the ids of its labels; times: per utterance [n, 2] start / end in 100 ns units (for -d), or None."""
+        ids, off = _pack(utts, np.int32, who="LabelStats.count")
+        st = en = None
+        if times is not None:
+            t = np.concatenate([np.asarray(x, np.int64).reshape(-1, 2) for x in times]) if len(ids) else np.zeros((0, 2), np.int64)
+            st, en = np.ascontiguousarray(t[:, 0]), np.ascontiguousarray(t[:, 1])
+        check(lib().htkamd_lstats_count(self.h, len(utts), _p(off), _p(ids), _p(st), _p(en), _stream(stream)), "lstats_count")
+        return self
+
+    def plant(self, n_utt, count, rowOff, succ, cnt, dur=None):
+        a = [np.ascontiguousarray(x, np.int32) for x in (count, rowOff, succ, cnt)]
+        d = [np.ascontiguousarray(x, np.int64) for x in dur] if dur is not None else [None] * 3
+        check(lib().htkamd_lstats_plant(self.h, n_utt, _p(a[0]), _p(a[1]), _p(a[2]) if len(a[2]) else None, _p(a[3]) if len(a[3]) else None, _p(d[0]), _p(d[1]), _p(d[2])),
+              "lstats_plant")
+        return self
+
+    def tables(self) -> dict:
+        V = self.n + 1
+        count, pcount, rowOff = np.zeros(V, np.int32), np.zeros(V, np.int32), np.zeros(V + 1, np.int32)
+        dur = [np.zeros(V, np.int64) for _ in range(3)]
+        check(lib().htkamd_lstats_get(self.h, _p(count), _p(pcount), _p(dur[0]), _p(dur[1]), _p(dur[2]), _p(rowOff)), "lstats_get")
+        succ, cnt = np.zeros(max(rowOff[V], 1), np.int32), np.zeros(max(rowOff[V], 1), np.int32)
+        check(lib().htkamd_lstats_bigrams(self.h, _p(succ), _p(cnt)), "lstats_bigrams")
+        return dict(count=count, pcount=pcount, rowOff=rowOff, succ=succ[:rowOff[V]], cnt=cnt[:rowOff[V]], durSum=dur[0], durMin=dur[1], durMax=dur[2])
+
+    def bigram_write(self, path, backoff=False, uni_floor=1.0, big_thresh=0, big_floor=0.0, discount=0.5, trace_path=None):
+        check(lib().htkamd_lstats_bigram_write(self.h, path.encode(), int(backoff), uni_floor, big_thresh, big_floor, discount, trace_path.encode() if trace_path else None),
+              "lstats_bigram_write")
+
+    def stats_write(self, path, flags, count_limit=0, list_path=None, append=False):
+        check(lib().htkamd_lstats_stats_write(self.h, path.encode() if path else None, int(append), flags, count_limit, list_path.encode() if list_path else None),
+              "lstats_stats_write")
+
+    @property
+    def kernel_ms(self):
+        return lib().htkamd_lstats_last_kernel_ms(self.h)
+
+
+class Bigram(_Handle):
+    """htkamd_bigram holder: a back-off or matrix bigram file as ReadLModel reads it."""
+    _destroy = "htkamd_bigram_destroy"
+
+    def __init__(self, path: str):
+        L = lib()
+        self.h = C.c_void_p()
+        check(L.htkamd_bigram_read(path.encode(), C.byref(self.h)), "bigram_read")
+        self.type, self.n = L.htkamd_bigram_type(self.h), L.htkamd_bigram_nwords(self.h)
+        self.words = [None] + [L.htkamd_bigram_word(self.h, i).decode("latin-1") for i in range(1, self.n + 1)]
+
+    def tables(self) -> dict:
+        L = lib()
+        W = self.n + 1
+        if self.type == LM_MATRIX:
+            mat = np.zeros((W, W), np.float32)
+            check(L.htkamd_bigram_get(self.h, None, None, None, None, None, None, _p(mat)), "bigram_get")
+            return dict(mat=mat)
+        nb = L.htkamd_bigram_nbigrams(self.h)
+        uni, bowt, has, rowOff = np.zeros(W, np.float32), np.zeros(W, np.float32), np.zeros(W, np.int32), np.zeros(W + 1, np.int32)
+        succ, prob = np.zeros(max(nb, 1), np.int32), np.zeros(max(nb, 1), np.float32)
+        check(L.htkamd_bigram_get(self.h, _p(uni), _p(bowt), _p(has), _p(rowOff), _p(succ), _p(prob), None), "bigram_get")
+        return dict(unigram=uni, bowt=bowt, hasEntry=has, rowOff=rowOff, succ=succ[:nb], prob=prob[:nb])
+
+
+class Network(_Handle):
+    """htkamd_wordnet holder: one of HBuild's flat word networks, in memory."""
+    _destroy = "htkamd_wordnet_destroy"
+
+    def __init__(self, h):
+        self.h = h
+
+    @classmethod
+    def word_loop(cls, words, bracket=None):
+        h = C.c_void_p()
+        b0, b1 = (bracket[0].encode(), bracket[1].encode()) if bracket else (None, None)
+        check(lib().htkamd_netbuild_loop(_str_array(words), len(words), b0, b1, C.byref(h)), "netbuild_loop")
+        return cls(h)
+
+    @classmethod
+    def from_bigram(cls, bigram: Bigram, words, enter="!ENTER", exit="!EXIT", unknown="!NULL", zap_unknown=False, stream=None):
+        h = C.c_void_p()
+        check(lib().htkamd_netbuild_bigram(bigram.h, _str_array(words), len(words), enter.encode(), exit.encode(), unknown.encode(), int(zap_unknown), C.byref(h),
+                                           _stream(stream)), "netbuild_bigram")
+        return cls(h)
+
+    def write(self, path: str):
+        check(lib().htkamd_wordnet_write(self.h, path.encode()), "wordnet_write")
+
+    def arrays(self) -> dict:
+        L = lib()
+        lat = L.htkamd_wordnet_lattice(self.h).contents
+        def arr(p, n, dt):
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(dt)), (max(n, 1),))[:n].copy()
+        pron = arr(lat.nodePron, lat.nNodes, C.c_int)
+        return dict(nodeWord=[L.htkamd_wordnet_word(self.h, int(w)).decode("latin-1") if w >= 0 else "!NULL" for w in pron],
+                    arcStart=arr(lat.arcStart, lat.nArcs, C.c_int), arcEnd=arr(lat.arcEnd, lat.nArcs, C.c_int), arcLm=arr(lat.arcLm, lat.nArcs, C.c_float))
+
+    def expand(self, dictionary: str, mmf: "Mmf", flags: int = 0) -> "Net":
+        """The model-level network for the decoders, as Net(slf, ...) gives it for the written file -- without the file."""
+        net = Net.__new__(Net)
+        net._mmf = mmf
+        net.h = C.c_void_p()
+        L = lib()
+        n = L.htkamd_wordnet_nwords(self.h)
+        words = (C.c_char_p * max(n, 1))(*[L.htkamd_wordnet_word(self.h, w) for w in range(n)])
+        check(L.htkamd_net_build_lattice(L.htkamd_wordnet_lattice(self.h), words, n, dictionary.encode(), mmf.h, flags, C.byref(net.h)), "net_build_lattice")
+        net._fill()
+        return net
+
+    @property
+    def kernel_ms(self):
+        return lib().htkamd_wordnet_last_kernel_ms(self.h)
+
+
+def netbuild_probe(mode, N, nodeOf, rowKeep, enter_idx, zap_idx=0, back_node=0, rowOff=None, succ=None, val=None, rowVal=None, uni=None, stream=None):
+    """htkamd_netbuild_probe: k_nb_arcs over caller tables -> (arcStart, arcEnd, arcLm)."""
+    i32 = lambda x: None if x is None else np.ascontiguousarray(x, np.int32)
+    f32 = lambda x: None if x is None else np.ascontiguousarray(x, np.float32)
+    rowOff, succ, nodeOf, rowKeep, val, rowVal, uni = i32(rowOff), i32(succ), i32(nodeOf), i32(rowKeep), f32(val), f32(rowVal), f32(uni)
+    cap = (len(succ) + 2 * N) if mode == LM_BACKOFF else N * N
+    S, E, Lm, n = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float32), C.c_int(0)
+    check(lib().htkamd_netbuild_probe(mode, N, _p(rowOff), _p(succ) if succ is not None and len(succ) else None, _p(val), _p(rowVal), _p(uni), _p(nodeOf), _p(rowKeep), enter_idx,
+                                      zap_idx, back_node, _p(S), _p(E), _p(Lm), cap, C.byref(n), _stream(stream)), "netbuild_probe")
+    return S[:n.value], E[:n.value], Lm[:n.value]

@@ -311,6 +311,38 @@ int htkamd_net_build_words(const char *const *words, int nWords, const char *bou
    return expand_lattice(ln, NN, la, NA, pr, nPr, "(transcription)", dictPath, htkamd_mmf_desc(hmms), NULL, out);
 }
 
+/* A word network made in memory (host/netbuild.c: its lattice and its words) expanded as its SLF file would be: the nodes in their order,
+   the arcs in the order WriteLattice sorts them into (QSCmpArcs), and every l= as the file's two decimals give it back. */
+int htkamd_net_build_lattice(const htkamd_lattice *lat, const char *const *words, int nWords, const char *dictPath, const struct htkamd_mmf *hmms, int flags,
+                             struct htkamd_net **out)
+{
+   if (!lat || !dictPath || !hmms || !out || (nWords > 0 && !words)) { htkamd_set_error("net_build_lattice: NULL argument"); return HTKAMD_EINVAL; }
+   for (int i = 0; i < lat->nNodes; i++)
+      if (lat->nodePron[i] >= nWords || (lat->nodePron[i] >= 0 && !words[lat->nodePron[i]])) { htkamd_set_error("net_build_lattice: node %d names word %d of %d", i, lat->nodePron[i], nWords); return HTKAMD_EINVAL; }
+   for (int a = 0; a < lat->nArcs; a++)
+      if (lat->arcStart[a] < 0 || lat->arcStart[a] >= lat->nNodes || lat->arcEnd[a] < 0 || lat->arcEnd[a] >= lat->nNodes) { htkamd_set_error("net_build_lattice: arc %d has bad end points", a); return HTKAMD_EINVAL; }
+   const htkamd_model_desc *md = htkamd_mmf_desc(hmms);
+   if (!md) { htkamd_set_error("net_build_lattice: model set not finished"); return HTKAMD_EINVAL; }
+   dpron *pr = NULL; int nPr = 0, rc, xwrd = 0;
+   if ((rc = read_dict(dictPath, hmms, flags, &xwrd, &pr, &nPr))) return rc;
+   const int NN = lat->nNodes, NA = lat->nArcs;
+   lnode *ln = (lnode *)calloc((size_t)NN, sizeof(lnode));
+   larc *la = (larc *)calloc((size_t)(NA ? NA : 1), sizeof(larc));
+   int *rank = (int *)malloc(sizeof(int) * (size_t)NN), *order = (int *)malloc(sizeof(int) * ((size_t)NA + 1));
+   for (int i = 0; i < NN; i++) { rank[i] = i; ln[i].word = strdup(lat->nodePron[i] >= 0 ? words[lat->nodePron[i]] : "!NULL"); }
+   htkamd_slf_sort_arcs(order, NA, lat->arcStart, lat->arcEnd, rank);
+   for (int i = 0; i < NA; i++) {
+      char txt[64];
+      const int a = order[i];
+      const float tl = lat->arcLm[a] * lat->lmScale;
+      snprintf(txt, sizeof(txt), "%-8.2f", (float)(tl + lat->wordPen));
+      la[i].s = lat->arcStart[a]; la[i].e = lat->arcEnd[a]; la[i].l = strtof(txt, NULL);
+   }
+   free(rank); free(order);
+   xwrd_t xw; xw.hmms = hmms; xw.flags = flags;
+   return expand_lattice(ln, NN, la, NA, pr, nPr, "(network)", dictPath, md, xwrd ? &xw : NULL, out);
+}
+
 static int expand_lattice(lnode *ln, int NN, larc *la, int NA, dpron *pr, int nPr, const char *slfPath, const char *dictPath, const htkamd_model_desc *md, const xwrd_t *xw, struct htkamd_net **out)
 {
    int rc;

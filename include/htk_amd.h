@@ -1583,6 +1583,96 @@ int  htkamd_latset_best_ids(const htkamd_latset *s, htkamd_results *r, int K, co
  * format: HTKAMD_LAT_* bits, 0 = HLRescore's default (HLAT_DEFAULT | HLAT_PRLIKE: t v a l d m n r) */
 int  htkamd_latset_write(const htkamd_latset *s, int u, const htkamd_lat_scales *sc, const double *nodeScore, const char *path, int format);
 
+/* ------------------------------------------------------------------------------------------
+ * Label statistics and bigram models (HLStats): a batch of label sequences counted in one call.
+ * Replaces InitStats (HLStats.c:367), GatherStats (:471) and OutputStats (:888).  The counting is integer work on the device
+ * (csrc/lstats.hip); the probabilities are host arithmetic in the reference's types and order (host/lstats.c), so the files match the
+ * reference's byte for byte.
+ * Word ids: 0 = a label that is not in the list (the reference's !NULL slot), 1..htkamd_lstats_nwords = the list as the reference sorts
+ * it: the start label first, the end label last (both added when the list lacks them), strcmp order between.  The list is HLStats'
+ * hmmList with one name a line (no logical -> physical pairs, so -p is refused and -c's PCount column counts the same labels).
+ * A start label at the head of an utterance and an end label at its tail are skipped, as GatherStats skips them.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct htkamd_lstats htkamd_lstats;
+int  htkamd_lstats_create(const char *const *words, int nWords, const char *enterWord /* -s; NULL = !ENTER */, const char *exitWord /* NULL = !EXIT */, htkamd_lstats **out);
+void htkamd_lstats_destroy(htkamd_lstats *s);
+int  htkamd_lstats_nwords(const htkamd_lstats *s);
+const char *htkamd_lstats_word(const htkamd_lstats *s, int id);
+int  htkamd_lstats_id(const htkamd_lstats *s, const char *name);      /* 0: not in the list */
+/* ids (and times, either may be NULL) of a label list: [htkamd_labels_count(l)] */
+int  htkamd_lstats_ids(const htkamd_lstats *s, const htkamd_labels *l, int *ids, long long *start, long long *end);
+/* Counts the batch: utterance u = labIds[labOff[u] .. labOff[u+1]), the form htkamd_results_score takes.  start / end: the labels' times in
+ * 100 ns units for the duration statistics (-d), or both NULL.  A call replaces what the call before counted.  Synchronises `stream`. */
+int  htkamd_lstats_count(htkamd_lstats *s, int nUtt, const int *labOff, const int *labIds, const long long *start, const long long *end, void *stream);
+/* Results over ids 0..nwords: count = lTab[].count (with the start and end label of every utterance), pcount = occurrences as labels,
+ * durations in 100 ns units (min / max of a word never seen: LLONG_MAX / LLONG_MIN), rowOff [nwords + 2] = the CSR rows by predecessor.
+ * Any pointer may be NULL. */
+int  htkamd_lstats_get(const htkamd_lstats *s, int *count, int *pcount, long long *durSum, long long *durMin, long long *durMax, int *rowOff);
+int  htkamd_lstats_bigrams(const htkamd_lstats *s, int *succ, int *cnt);      /* [rowOff[nwords + 1]]: successors increasing within a row */
+double htkamd_lstats_last_kernel_ms(const htkamd_lstats *s);
+/* HLStats -b path: backoff != 0 is -o (OutputBoBigram; uniFloor -u, bigThresh -t, discount = the DISCOUNT configuration value, 0.5),
+ * else the matrix bigram (OutputMatBigram; bigFloor -f).  tracePath: the lines -T 4 prints are APPENDED to that file; NULL = none. */
+int  htkamd_lstats_bigram_write(const htkamd_lstats *s, const char *path, int backoff, float uniFloor, int bigThresh, float bigFloor, double discount, const char *tracePath);
+/* What HLStats prints: flags HTKAMD_LS_DURS (-d; needs the times), HTKAMD_LS_LIST (-l listPath), HTKAMD_LS_COUNTS (-c countLimit), in the
+ * reference's order.  HLStats prints the -T 4 lines of the bigram between the durations and the counts: write the durations, then the
+ * bigram with tracePath = path, then the rest with append != 0. */
+#define HTKAMD_LS_DURS   1
+#define HTKAMD_LS_LIST   2
+#define HTKAMD_LS_COUNTS 4
+int  htkamd_lstats_stats_write(const htkamd_lstats *s, const char *path, int append, int flags, int countLimit, const char *listPath);
+int  htkamd_lstats_check_switch(const char *sw);      /* 0 for a switch of HLStats that is served ("-b"), else HTKAMD_EINVAL and the refusal by name */
+/* Counts planted in place of a counting run (tests of the host arithmetic): count = occurrences as labels, then the CSR table and the durations */
+int  htkamd_lstats_plant(htkamd_lstats *s, int nUtt, const int *count, const int *rowOff, const int *succ, const int *cnt, const long long *durSum, const long long *durMin,
+                         const long long *durMax);
+/* The device chain over caller tables: V ids, boundary ids, and the capacities of the wavefront path and the workgroup path of the row
+ * kernel (1 <= waveCap <= htkamd_lstats_wave_cap(), waveCap <= groupCap <= htkamd_lstats_group_cap(); a row longer than groupCap goes
+ * through the histogram path with windows of groupCap ids).  count / dur* [V], rowOff [V + 1], succ / cnt [pairCap]. */
+int  htkamd_lstats_probe(int V, int nUtt, const int *labOff, const int *labIds, const long long *start, const long long *end, int enterId, int exitId, int waveCap, int groupCap,
+                         int *count, long long *durSum, long long *durMin, long long *durMax, int *rowOff, int *succ, int *cnt, int pairCap, void *stream);
+int  htkamd_lstats_wave_cap(void);
+int  htkamd_lstats_group_cap(void);
+
+/* ------------------------------------------------------------------------------------------
+ * Word networks from a word list or a bigram model (HBuild).  htkamd_bigram_read = ReadLModel (HLM.c:813) for the two text forms HLStats
+ * writes; words 1..N in file order, log probabilities natural.  The networks are ProcessWordLoop (HBuild.c:299), ProcessBoBiGram (:368)
+ * and ProcessMatBiGram (:463): nodes, arcs and l= values as HBuild saves them, the arcs of the bigram forms written on the device
+ * (csrc/netbuild.hip).  The word loop's nodes follow the word list (the reference's follow the addresses of its name table and change
+ * from run to run).  `words` = HBuild's word list: every word of the model must be in it.
+ * ------------------------------------------------------------------------------------------ */
+#define HTKAMD_LM_BACKOFF 0
+#define HTKAMD_LM_MATRIX  1
+typedef struct htkamd_bigram htkamd_bigram;
+int  htkamd_bigram_read(const char *path, htkamd_bigram **out);
+void htkamd_bigram_destroy(htkamd_bigram *b);
+int  htkamd_bigram_type(const htkamd_bigram *b);
+int  htkamd_bigram_nwords(const htkamd_bigram *b);
+const char *htkamd_bigram_word(const htkamd_bigram *b, int i);      /* 1..N */
+int  htkamd_bigram_nbigrams(const htkamd_bigram *b);
+/* back-off form: unigram / bowt / hasEntry [N + 1], rowOff [N + 2], succ / prob [nbigrams]; matrix form: mat [(N + 1) * (N + 1)] */
+int  htkamd_bigram_get(const htkamd_bigram *b, float *unigram, float *bowt, int *hasEntry, int *rowOff, int *succ, float *prob, float *mat);
+typedef struct htkamd_wordnet htkamd_wordnet;
+/* bracketStart / bracketEnd: -t s1 s2, or both NULL */
+int  htkamd_netbuild_loop(const char *const *words, int nWords, const char *bracketStart, const char *bracketEnd, htkamd_wordnet **out);
+/* -n / -m by the model's form; enterWord / exitWord -s (NULL = !ENTER / !EXIT), unknownWord -u (NULL = !NULL), zapUnknown -z */
+int  htkamd_netbuild_bigram(const htkamd_bigram *b, const char *const *words, int nWords, const char *enterWord, const char *exitWord, const char *unknownWord, int zapUnknown,
+                            htkamd_wordnet **out, void *stream);
+void htkamd_wordnet_destroy(htkamd_wordnet *n);
+/* the network as a lattice: nodePron = index for htkamd_wordnet_word (-1: !NULL), times and acoustic scores 0, lmScale 1 */
+const htkamd_lattice *htkamd_wordnet_lattice(const htkamd_wordnet *n);
+const char *htkamd_wordnet_word(const htkamd_wordnet *n, int w);
+double htkamd_wordnet_last_kernel_ms(const htkamd_wordnet *n);
+int  htkamd_wordnet_write(const htkamd_wordnet *n, const char *path);      /* SaveLattice: the SLF file; the bigram networks byte for byte HBuild's */
+int  htkamd_wordnet_nwords(const htkamd_wordnet *n);
+/* the network (htkamd_wordnet_lattice and the words its nodePron index) expanded over a dictionary and a model set as htkamd_net_build_ex
+ * expands its SLF file, without the file: arcs in the file's order, every l= through the file's two decimals */
+int  htkamd_net_build_lattice(const htkamd_lattice *lat, const char *const *words, int nWords, const char *dictPath, const htkamd_mmf *hmms, int flags,
+                              htkamd_net **out);
+int  htkamd_netbuild_check_switch(const char *sw);
+/* k_nb_arcs over caller tables, words 1..N: mode HTKAMD_LM_*; back-off: rowOff [N + 2] / succ / val = the rows, rowVal [N + 1] the back-off
+ * weights, uni [N + 1] the unigrams; matrix: val [(N + 1) * (N + 1)].  nodeOf [N + 1] (-1: no node), rowKeep [N + 1]. */
+int  htkamd_netbuild_probe(int mode, int N, const int *rowOff, const int *succ, const float *val, const float *rowVal, const float *uni, const int *nodeOf, const int *rowKeep,
+                           int enterIdx, int zapIdx, int backNode, int *arcStart, int *arcEnd, float *arcLm, int arcCap, int *nArcs, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
