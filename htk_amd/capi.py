@@ -2366,6 +2366,21 @@ class LatSet(_Handle):
 
 
 # Every struct of include/htk_amd.h and its mirror above: abi.declare reads the pointer returns from it, tests/test_capi_abi.py the layouts.
+# ---- VQ codebooks and VQ coding (HQuant, HParm's _V): the structs; the holder is at the end of the file
+CK_DIAGC, CK_INVDIAGC, CK_FULLC, CK_NULLC = 0, 1, 2, 5
+VQ_LINTREE, VQ_BINTREE = 0, 1
+VQ_ECLUSTER, VQ_EPOW2, VQ_EKIND, VQ_EINVERT, VQ_ETABKIND = 7120, 7172, 7170, 5220, 6172
+
+
+class VqConfig(C.Structure):
+    _fields_ = [("maxIter", C.c_int), ("minClustSize", C.c_int), ("clustKind", C.c_int)]
+
+
+class VqClusters(C.Structure):
+    _fields_ = [("numNodes", C.c_int), ("iterations", C.c_int), ("launches", C.c_int), ("kernelMs", C.c_double),
+                ("size", C.c_void_p), ("centre", C.c_void_p), ("cov", C.c_void_p), ("aveCost", C.c_void_p), ("cmap", C.c_void_p)]
+
+
 STRUCTS = {"htkamd_model_desc": ModelDesc, "htkamd_accs_layout": AccsLayout, "htkamd_fb_config": FbConfig, "htkamd_update_config": UpdateConfig,
            "htkamd_update_stats": UpdateStats, "htkamd_batch_desc": BatchDesc, "htkamd_mfcc_config": MfccConfig, "htkamd_frontend_config": FrontEndConfig,
            "htkamd_warp": Warp, "htkamd_parm_quals": ParmQuals, "htkamd_tree_question": TreeQuestion, "htkamd_tree_spec": TreeSpec,
@@ -2373,7 +2388,8 @@ STRUCTS = {"htkamd_model_desc": ModelDesc, "htkamd_accs_layout": AccsLayout, "ht
            "htkamd_net_desc": NetDesc, "htkamd_decode_config": DecodeConfig, "htkamd_lattice_out": LatticeOut, "htkamd_lattice_align_out": LatticeAlignOut,
            "htkamd_lattice_align": LatticeAlign, "htkamd_lattice": Lattice, "htkamd_decode_out": DecodeOut, "htkamd_results_config": ResultsConfig,
            "htkamd_results_report": ResultsReport, "htkamd_lat_scales": LatScales, "htkamd_latset_view": LatSetView, "htkamd_latset_best_out": LatBestOut,
-           "htkamd_latset_fb_out": LatFbOut, "htkamd_mllr_config": MllrConfig}
+           "htkamd_latset_fb_out": LatFbOut, "htkamd_mllr_config": MllrConfig,
+           "htkamd_vq_config": VqConfig, "htkamd_vq_clusters": VqClusters}
 
 
 # ---- label statistics and bigram models (HLStats), word networks (HBuild) ----
@@ -2563,3 +2579,89 @@ def netbuild_probe(mode, N, nodeOf, rowKeep, enter_idx, zap_idx=0, back_node=0, 
     check(lib().htkamd_netbuild_probe(mode, N, _p(rowOff), _p(succ) if succ is not None and len(succ) else None, _p(val), _p(rowVal), _p(uni), _p(nodeOf), _p(rowKeep), enter_idx,
                                       zap_idx, back_node, _p(S), _p(E), _p(Lm), cap, C.byref(n), _stream(stream)), "netbuild_probe")
     return S[:n.value], E[:n.value], Lm[:n.value]
+
+
+# ---- VQ codebooks and VQ coding (csrc/vquant.hip, host/vqtab.c) ----
+def hquant_check_switch(sw: str):
+    check(lib().htkamd_hquant_check_switch(sw.encode()), "hquant_check_switch")
+
+
+def vq_cluster(dX_ptr, N: int, D: int, nc: int, tree: bool = False, dist_kind: int = CK_NULLC, dist_cov=None, clust_kind: int = -1, max_iter: int = 10,
+               min_clust_size: int = 3, stream=None) -> dict:
+    """FlatCluster / TreeCluster of one pool dX [N, D] on the device (htkamd_vq_cluster).  Returns size, centre, cov (None for NULLC),
+    aveCost per node, cmap [N] (0-based node of every item), iterations, launches, kernel_ms, kind (the clusters' covariance kind)."""
+    L = lib()
+    nodes = L.htkamd_vq_num_nodes(int(nc), int(bool(tree)))
+    kind = dist_kind if clust_kind < 0 else clust_kind
+    clen = max(L.htkamd_vq_cov_len(int(D), int(kind)), 0)
+    n = max(nodes, 1)
+    size, ctr, ave = np.zeros(n, np.int32), np.zeros((n, D), np.float32), np.zeros(n, np.float32)
+    cov, cmap = np.zeros((n, max(clen, 1)), np.float32), np.zeros(max(int(N), 1), np.int32)
+    dc = None if dist_cov is None else np.ascontiguousarray(dist_cov, np.float32).reshape(-1)
+    cfg = VqConfig(int(max_iter), int(min_clust_size), int(clust_kind))
+    out = VqClusters(0, 0, 0, 0.0, _p(size), _p(ctr), _p(cov), _p(ave), _p(cmap))
+    check(L.htkamd_vq_cluster(_stream(dX_ptr), int(N), int(D), int(nc), int(bool(tree)), int(dist_kind), _p(dc), C.byref(cfg), C.byref(out), _stream(stream)), "vq_cluster")
+    return dict(size=size, centre=ctr, cov=cov[:, :clen] if clen else None, aveCost=ave, cmap=cmap[:N], iterations=out.iterations, launches=out.launches,
+                kernel_ms=out.kernelMs, kind=kind, tree=bool(tree))
+
+
+class VQ(_Handle):
+    """htkamd_vqtab holder: a VQ table read from a file or made from cluster sets (one per stream, vq_cluster's dicts), written as
+    StoreVQTab writes it, and the coder over it."""
+    _destroy = "htkamd_vqtab_destroy"
+
+    def __init__(self, path: str = None, magic: int = 0, clusters=None, kind: int = CK_NULLC, global_cov=None):
+        L = lib()
+        self.h = C.c_void_p()
+        if path is not None:
+            check(L.htkamd_vqtab_read(path.encode(), int(magic), C.byref(self.h)), "vqtab_read")
+        else:
+            S = len(clusters)
+            keep, cs = [], (VqClusters * max(S, 1))()
+            for s, c in enumerate(clusters):
+                arr = [np.ascontiguousarray(c["size"], np.int32), np.ascontiguousarray(c["centre"], np.float32), None if c.get("cov") is None else np.ascontiguousarray(c["cov"], np.float32)]
+                keep.append(arr)
+                cs[s] = VqClusters(len(arr[0]), 0, 0, 0.0, _p(arr[0]), _p(arr[1]), _p(arr[2]), None, None)
+            width = np.array([np.asarray(c["centre"]).shape[1] for c in clusters], np.int32)
+            g = [None if global_cov is None or global_cov[s] is None else np.ascontiguousarray(global_cov[s], np.float32).reshape(-1) for s in range(S)]
+            gp = (C.c_void_p * max(S, 1))(*[None if x is None else x.ctypes.data for x in g])
+            tree = bool(clusters[0].get("tree")) if S else False
+            check(L.htkamd_vqtab_from_clusters(int(magic), VQ_BINTREE if tree else VQ_LINTREE, int(kind), S, _p(width), cs, gp, C.byref(self.h)), "vqtab_from_clusters")
+        info = np.zeros(5, np.int32)
+        check(L.htkamd_vqtab_info(self.h, _p(info), None), "vqtab_info")
+        self.magic, self.type, self.kind, self.num_nodes, self.num_streams = (int(x) for x in info)
+        self.width = np.zeros(self.num_streams, np.int32)
+        check(L.htkamd_vqtab_info(self.h, None, _p(self.width)), "vqtab_info")
+
+    def write(self, path: str):
+        check(lib().htkamd_vqtab_write(self.h, path.encode()), "vqtab_write")
+
+    def stream(self, s: int) -> dict:
+        """Stream s (from 0) in the coder's order: vqidx, left, right (indices, -1 none), gconst, mean [n, width], cov [n, len] or None."""
+        L = lib()
+        n = L.htkamd_vqtab_stream(self.h, s, None, None, None, None, None, None)
+        if n < 0:
+            check(n, "vqtab_stream")
+        D = int(self.width[s])
+        clen = max(L.htkamd_vq_cov_len(D, self.kind), 0)
+        vqidx, left, right = (np.zeros(n, np.int32) for _ in range(3))
+        gconst, mean, cov = np.zeros(n, np.float32), np.zeros((n, D), np.float32), np.zeros((n, max(clen, 1)), np.float32)
+        L.htkamd_vqtab_stream(self.h, s, _p(vqidx), _p(left), _p(right), _p(gconst), _p(mean), _p(cov))
+        return dict(vqidx=vqidx, left=left, right=right, gconst=gconst, mean=mean, cov=cov[:, :clen] if clen else None)
+
+    def code(self, dX_ptr, frame_off, n_cols: int, stream=None) -> np.ndarray:
+        """GetVQ for every frame of a batch on the device: codes [frames, streams] int16."""
+        off = np.ascontiguousarray(frame_off, np.int32)
+        codes = np.zeros((max(int(off[-1]), 1), self.num_streams), np.int16)
+        check(lib().htkamd_vq_code(self.h, _stream(dX_ptr), len(off) - 1, _p(off), int(n_cols), _p(codes), _stream(stream)), "vq_code")
+        return codes[:int(off[-1])]
+
+    @property
+    def kernel_ms(self):
+        return lib().htkamd_vq_code_last_kernel_ms(self.h)
+
+
+def parm_write_discrete(path: str, codes: np.ndarray, sampPeriod: int, withCrc: bool = False):
+    c = np.ascontiguousarray(codes, np.int16)
+    c = c.reshape(len(c), -1)
+    check(lib().htkamd_parm_write_discrete(path.encode(), _p(c), c.shape[0], c.shape[1], int(sampPeriod), int(withCrc)), "parm_write_discrete")

@@ -74,20 +74,27 @@ int htkamd_parm_read(const char *path, float **data, int *nFrames, int *nCols, i
    return rc;
 }
 
+/* the 12-byte big-endian header of a parameter file: nSamples, sampPeriod, sampSize, parmKind */
+static void parm_put_header(FILE *f, int nFrames, int sampPeriod, int sz, int pk)
+{
+   unsigned char hdr[12];
+   hdr[0] = (unsigned char)(nFrames >> 24); hdr[1] = (unsigned char)(nFrames >> 16); hdr[2] = (unsigned char)(nFrames >> 8); hdr[3] = (unsigned char)nFrames;
+   hdr[4] = (unsigned char)(sampPeriod >> 24); hdr[5] = (unsigned char)(sampPeriod >> 16); hdr[6] = (unsigned char)(sampPeriod >> 8); hdr[7] = (unsigned char)sampPeriod;
+   hdr[8] = (unsigned char)(sz >> 8); hdr[9] = (unsigned char)sz; hdr[10] = (unsigned char)(pk >> 8); hdr[11] = (unsigned char)pk;
+   fwrite(hdr, 1, 12, f);
+}
+
 int htkamd_parm_write(const char *path, const float *data, int nFrames, int nCols, int sampPeriod, int kind, int withCrc)
 {
    FILE *f;
-   unsigned char hdr[12], *buf;
+   unsigned char *buf;
    unsigned crc = 0;
    size_t i, n = (size_t)nFrames * nCols;
    int pk = (kind & ~(HASCOMPX | HASCRCC)) | (withCrc ? HASCRCC : 0), sz = nCols * 4;
    if (!path || (!data && n) || nFrames < 0 || nCols <= 0) { htkamd_set_error("parm_write: bad argument"); return HTKAMD_EINVAL; }
    f = fopen(path, "wb");
    if (!f) { htkamd_set_error("parm_write: cannot open %s", path); return HTKAMD_EINVAL; }
-   hdr[0] = (unsigned char)(nFrames >> 24); hdr[1] = (unsigned char)(nFrames >> 16); hdr[2] = (unsigned char)(nFrames >> 8); hdr[3] = (unsigned char)nFrames;
-   hdr[4] = (unsigned char)(sampPeriod >> 24); hdr[5] = (unsigned char)(sampPeriod >> 16); hdr[6] = (unsigned char)(sampPeriod >> 8); hdr[7] = (unsigned char)sampPeriod;
-   hdr[8] = (unsigned char)(sz >> 8); hdr[9] = (unsigned char)sz; hdr[10] = (unsigned char)(pk >> 8); hdr[11] = (unsigned char)pk;
-   fwrite(hdr, 1, 12, f);
+   parm_put_header(f, nFrames, sampPeriod, sz, pk);
    buf = (unsigned char *)malloc(4 * (n ? n : 1));
    if (!buf) { fclose(f); htkamd_set_error("parm_write: out of memory"); return HTKAMD_ENOMEM; }
    for (i = 0; i < n; i++) {
@@ -97,6 +104,33 @@ int htkamd_parm_write(const char *path, const float *data, int nFrames, int nCol
       crc = (crc * 65536u + (u & 0xffffu)) % 36897u;
    }
    fwrite(buf, 1, 4 * n, f);
+   if (withCrc) { unsigned char c[2] = {(unsigned char)(crc >> 8), (unsigned char)crc}; fwrite(c, 1, 2, f); }
+   free(buf);
+   fclose(f);
+   return HTKAMD_OK;
+}
+
+/* A file of kind DISCRETE (HParm's HASVQ target saved with SAVEASVQ): per frame the streams' VQ indices as big-endian shorts, sampSize
+   2 * nStreams; the check sum runs over the shorts as it runs over the halves of a float. */
+#define PARM_DISCRETE 10
+int htkamd_parm_write_discrete(const char *path, const short *codes, int nFrames, int nStreams, int sampPeriod, int withCrc)
+{
+   FILE *f;
+   unsigned char *buf;
+   unsigned crc = 0;
+   size_t i, n = (size_t)nFrames * nStreams;
+   if (!path || (!codes && n) || nFrames < 0 || nStreams <= 0) { htkamd_set_error("parm_write_discrete: bad argument"); return HTKAMD_EINVAL; }
+   f = fopen(path, "wb");
+   if (!f) { htkamd_set_error("parm_write_discrete: cannot open %s", path); return HTKAMD_EINVAL; }
+   parm_put_header(f, nFrames, sampPeriod, nStreams * 2, PARM_DISCRETE | (withCrc ? HASCRCC : 0));
+   buf = (unsigned char *)malloc(2 * (n ? n : 1));
+   if (!buf) { fclose(f); htkamd_set_error("parm_write_discrete: out of memory"); return HTKAMD_ENOMEM; }
+   for (i = 0; i < n; i++) {
+      const unsigned u = (unsigned short)codes[i];
+      buf[2 * i] = (unsigned char)(u >> 8); buf[2 * i + 1] = (unsigned char)u;
+      crc = (crc * 65536u + u) % 36897u;
+   }
+   fwrite(buf, 1, 2 * n, f);
    if (withCrc) { unsigned char c[2] = {(unsigned char)(crc >> 8), (unsigned char)crc}; fwrite(c, 1, 2, f); }
    free(buf);
    fclose(f);

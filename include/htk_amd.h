@@ -1673,6 +1673,72 @@ int  htkamd_netbuild_check_switch(const char *sw);
 int  htkamd_netbuild_probe(int mode, int N, const int *rowOff, const int *succ, const float *val, const float *rowVal, const float *uni, const int *nodeOf, const int *rowKeep,
                            int enterIdx, int zapIdx, int backNode, int *arcStart, int *arcEnd, float *arcLm, int arcCap, int *nArcs, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * VQ codebooks and VQ coding (HQuant, and HParm's _V qualifier with VQTABLE): the front half of the discrete path.  Discrete MODELS
+ * are still refused everywhere (HTKAMD_EMODEL).
+ *   htkamd_vq_cluster : FlatCluster (HTrain.c:763; tree == 0) or TreeCluster (:806) of ONE pool dX [N x D] on the device, spread over
+ *                       the grid (csrc/vquant.hip), bit for bit the reference's arithmetic.  distKind / distCov: the covariance of
+ *                       Distance (:424): NULLC (distCov NULL), DIAGC / INVDIAGC (distCov [D], host) or FULLC (the inverse's lower
+ *                       triangle packed row-major, (i, j) at i(i+1)/2 + j, [D(D+1)/2]).  The clusters' own covariances are of
+ *                       cfg->clustKind (-1 or cfg NULL: distKind, as HQuant asks).  Nodes: nc for a flat set, 2nc-1 for a tree (node 1 the root, the children of row
+ *                       node i behind one another as TreeCluster numbers them); out's arrays are the caller's (host):
+ *                       size / aveCost [nodes], centre [nodes x D], cov [nodes x htkamd_vq_cov_len] (NULL for NULLC), cmap [N]
+ *                       (0-based node of every item; may be NULL).
+ *                       Returns 0, or the reference's error number with the cause in htkamd_last_error(): 7120 (fewer items than
+ *                       clusters; a cluster below minClustSize that the repairs could not fill; an empty child of a tree split), 7172
+ *                       (tree and nc not a power of two), 7170 (a kind that is none of the four), 5220 (a FULLC cluster covariance
+ *                       that cannot be inverted); HTKAMD_EINVAL for D above htkamd_vq_max_dim() or nc above htkamd_vq_max_clusters().
+ *   htkamd_vqtab_*    : the VQ table (HVQ.c): from cluster sets as HQuant numbers the nodes (AddLinEntries HQuant.c:316, AddBinEntries
+ *                       :335), read (LoadVQTab) and written (StoreVQTab) as text, byte for byte.  Table kinds NULLC, INVDIAGC, FULLC;
+ *                       DIAGC is refused as CKCheck refuses it (6172).
+ *   htkamd_vq_code    : GetVQ (HVQ.c:459) for every (frame, stream) of a batch on the device: dX [frameOff[nUtt] x nCols], the streams
+ *                       are consecutive column ranges of the table's widths (their sum must be nCols); codes [frames x streams]
+ *                       shorts (host).
+ *   htkamd_parm_write_discrete : a parameter file of kind DISCRETE from such codes.
+ * ------------------------------------------------------------------------------------------ */
+#define HTKAMD_CK_DIAGC    0      /* CovKind as the reference numbers it (HModel.h) and the table file stores it */
+#define HTKAMD_CK_INVDIAGC 1
+#define HTKAMD_CK_FULLC    2
+#define HTKAMD_CK_NULLC    5
+#define HTKAMD_VQ_LINTREE  0
+#define HTKAMD_VQ_BINTREE  1
+#define HTKAMD_VQ_ECLUSTER 7120
+#define HTKAMD_VQ_EPOW2    7172
+#define HTKAMD_VQ_EKIND    7170
+#define HTKAMD_VQ_EINVERT  5220
+#define HTKAMD_VQ_ETABKIND 6172
+typedef struct { int maxIter, minClustSize, clustKind; } htkamd_vq_config;      /* HTrain's MAXCLUSTITER (10), MINCLUSTSIZE (3); clustKind -1: distKind */
+typedef struct {
+   int numNodes, iterations, launches;      /* iterations: AllocateVectors rounds (flat) or levels (tree) */
+   double kernelMs;
+   int *size; float *centre, *cov, *aveCost; int *cmap;
+} htkamd_vq_clusters;
+int  htkamd_vq_max_dim(void);
+int  htkamd_vq_max_clusters(void);
+int  htkamd_vq_num_nodes(int nc, int tree);             /* nc or 2nc-1; 0 for a tree whose nc is no power of two */
+int  htkamd_vq_cov_len(int D, int kind);                /* 0, D or D(D+1)/2; -1: no such kind */
+/* CovInvert (HMath.c:567) of a packed lower triangle [D(D+1)/2] into one (host); 5220 where it is not positive definite */
+int  htkamd_vq_cov_invert(int D, const float *tri, float *inv);
+int  htkamd_vq_cluster(const float *dX, int N, int D, int nc, int tree, int distKind, const float *distCov, const htkamd_vq_config *cfg,
+                       htkamd_vq_clusters *out, void *stream);
+typedef struct htkamd_vqtab htkamd_vqtab;
+/* cs[s]: the cluster set of stream s (size, centre and cov used; all linear or all trees by `type`); globalCov[s] non-NULL: HQuant -g, that
+   covariance in every node of the stream */
+int  htkamd_vqtab_from_clusters(int magic, int type, int kind, int nStreams, const int *width, const htkamd_vq_clusters *cs, const float *const *globalCov,
+                                htkamd_vqtab **out);
+int  htkamd_vqtab_read(const char *path, int magic /* 0: any */, htkamd_vqtab **out);
+int  htkamd_vqtab_write(const htkamd_vqtab *t, const char *path);
+void htkamd_vqtab_destroy(htkamd_vqtab *t);
+/* info [5]: magic, type, kind, nodes, streams; width [streams] (either may be NULL) */
+int  htkamd_vqtab_info(const htkamd_vqtab *t, int *info, int *width);
+/* stream s (0-based) in the order the coder walks it (linear: the list; tree: the file's order, root first): vqidx / left / right [n]
+   (children as indices into this order, -1 none), gconst [n], mean [n x width], cov [n x cov_len]; any pointer may be NULL; returns n */
+int  htkamd_vqtab_stream(const htkamd_vqtab *t, int s, int *vqidx, int *left, int *right, float *gconst, float *mean, float *cov);
+int  htkamd_vq_code(htkamd_vqtab *t, const float *dX, int nUtt, const int *frameOff, int nCols, short *codes, void *stream);
+double htkamd_vq_code_last_kernel_ms(const htkamd_vqtab *t);
+int  htkamd_parm_write_discrete(const char *path, const short *codes, int nFrames, int nStreams, int sampPeriod, int withCrc);
+int  htkamd_hquant_check_switch(const char *sw);      /* 0 for a switch of HQuant that is served ("-d"), else HTKAMD_EINVAL and the refusal by name */
+
 #ifdef __cplusplus
 }
 #endif
