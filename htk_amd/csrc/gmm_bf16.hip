@@ -591,6 +591,7 @@ int htkamd_launch_score_bf16(const htkamd_model *m, const ScoreArgs &a, hipStrea
       HIPCHECK(hipMemsetAsync(a.taskCounter, 0, sizeof(int), stream));
       if (a.qCounters) HIPCHECK(hipMemsetAsync(a.qCounters, 0, 8 * sizeof(int), stream));
    }
+   if (m->bf16NC > 3) return htkamd_launch_score_bf16x(m, a, stream, evStart, evStop);      // D > 45: gmm_bf16x.hip (64-bit table addresses: no guard)
    if (m->f16Wide && (size_t)m->nTiles * ((size_t)3 * m->bf16NC * 64 * 16 + 64 * 16) >= ((size_t)1 << 32)) {
       htkamd_set_error("score_bf16: a table of %d tiles is beyond the kernel's 32-bit staging offsets", m->nTiles); return HTKAMD_EMODEL;
    }
@@ -772,6 +773,7 @@ int htkamd_model_refresh_bf16_device(htkamd_model *m, void *stream)
 {
    hipStream_t s = (hipStream_t)stream;
    if (!m->d_bf16Tab) return HTKAMD_OK;
+   if (m->bf16NC > 3) return htkamd_model_refresh_bf16x_device(m, stream);
    Bf16TabArgs t;
    t.D = m->D; t.NC = m->bf16NC; t.S = m->S; t.stateCompOff = m->d_stateCompOff; t.stateTileOff = m->d_stateTileOff; t.compGauss = m->d_compGauss; t.tileState = m->d_tileState;
    t.mean = m->d_mean; t.ivar = m->d_ivar; t.gconst = m->d_gconst; t.compLogWt = m->d_compLogWt; t.tab = (unsigned short *)m->d_bf16Tab;

@@ -220,7 +220,7 @@ struct htkamd_model {
    int   *d_stateTileOff;      /* [S+1] */
    int   *d_tileState;         /* [nTiles] tied state of every fragment tile */
    int    mfmaNS, nTiles;
-   void  *d_bf16Tab;           /* bf16 x 3 scoring path (gmm_bf16.hip): A-operand pieces per tile; NULL when D > 45 */
+   void  *d_bf16Tab;           /* bf16 x 3 scoring path (gmm_bf16.hip): A-operand pieces per tile (D > 45: in gmm_bf16x.hip's layout); NULL when D > 120 */
    int    bf16NC;              /* K chunks of 32 per piece: ceil(D/15) */
    int    bf16Dense;           /* the 32 x 32 bf16 kernel's five-k-step layout (31 <= D <= 39, every state in one tile): gmm_bf16.hip, k_score_bf16w<5> */
    void  *d_f16Tab;            /* fp16 x 2 scoring path (gmm_f16.hip): A-operand pieces per tile, K chunks as the bf16 path; NULL when D > 45 */
@@ -264,6 +264,7 @@ void htkamd_outp_ring_free(void *ring);                      /* gmm_exact.hip */
 /* the builders of the derived tables, each the only one of its table (stream: hipStream_t); called through the two functions below */
 int htkamd_model_refresh_mfma_device(struct htkamd_model *m, void *stream);   /* update.hip */
 int htkamd_model_refresh_bf16_device(struct htkamd_model *m, void *stream);   /* gmm_bf16.hip */
+int htkamd_model_refresh_bf16x_device(struct htkamd_model *m, void *stream);  /* gmm_bf16x.hip: the same table in the wide-vector kernel's layout (bf16NC > 3) */
 int htkamd_model_refresh_f16_device(struct htkamd_model *m, void *stream);    /* gmm_f16.hip */
 /* model.hip.  The parameters on the device changed: every derived table is stale; fromDevice (a device update): those of the paths in
    fastUse are rebuilt on `stream` and the host copies are stale; otherwise (the host pushed them) all are rebuilt and waited for */

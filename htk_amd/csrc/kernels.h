@@ -97,6 +97,8 @@ int htkamd_launch_score_full(const htkamd_model *m, const ScoreArgs &a, hipStrea
 int htkamd_launch_score_mfma(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart = nullptr, hipEvent_t evStop = nullptr);
 int htkamd_launch_score_bf16(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart = nullptr, hipEvent_t evStop = nullptr);
 int htkamd_launch_score_f16(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart = nullptr, hipEvent_t evStop = nullptr);
+// vector sizes 46 .. 120 (gmm_bf16x.hip): htkamd_launch_score_bf16 hands them on to this, after bringing the table up to date and zeroing the counter
+int htkamd_launch_score_bf16x(const htkamd_model *m, const ScoreArgs &a, hipStream_t stream, hipEvent_t evStart, hipEvent_t evStop);
 // the scoring kernel of a score mode (HTKAMD_SCORE_* bits: F16 before BF16 before MFMA before exact)
 static inline int htkamd_launch_score(int mode, const htkamd_model *m, const ScoreArgs &a, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr)
 {

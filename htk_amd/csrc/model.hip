@@ -138,6 +138,7 @@ struct ModelArray { size_t h, d, elem; size_t (*count)(const htkamd_model *); in
 #define OF(f) offsetof(htkamd_model, f)
 #define CNT(expr) [](const htkamd_model *m) -> size_t { return (size_t)(expr); }
 #define TABLE_BYTES(pieces) ((size_t)m->nTiles * ((size_t)(pieces) * m->bf16NC * 64 * 16 + 64 * 16))      /* bf16 x 3, fp16 x 2 (gmm_bf16.hip) */
+#define TABLE_BYTES_BF16X ((size_t)m->nTiles * ((size_t)3 * m->bf16NC * 64 * 16 + 64))                       /* bf16 x 3, D > 45 (gmm_bf16x.hip) */
 static const ModelArray MODEL_ARRAYS[] = {
    {OF(h_stateCompOff), OF(d_stateCompOff), sizeof(int), CNT(m->S + 1), 0},
    {OF(h_compGauss), OF(d_compGauss), sizeof(int), CNT(m->C), 0},
@@ -174,7 +175,7 @@ static const ModelArray MODEL_ARRAYS[] = {
    {NOF, OF(d_stateTileOff), sizeof(int), CNT(m->S + 1), 0},
    {NOF, OF(d_tileState), sizeof(int), CNT(m->nTiles), 0},
    {NOF, OF(d_mfmaTab), sizeof(float), CNT((size_t)m->nTiles * (m->mfmaNS + 8) * 64), 0},
-   {NOF, OF(d_bf16Tab), 1, CNT(TABLE_BYTES(3)), 0},
+   {NOF, OF(d_bf16Tab), 1, CNT(m->bf16NC > 3 ? TABLE_BYTES_BF16X : TABLE_BYTES(3)), 0},
    {NOF, OF(d_f16Tab), 1, CNT(TABLE_BYTES(2)), 0},
    {NOF, OF(d_f16Ctl), sizeof(float), CNT(512), 0},
 };
@@ -201,9 +202,9 @@ static int upload(htkamd_model *m, const ModelArray &a, const void *src = nullpt
 // ---- the derived tables of the matrix-core paths: fp32 fragments (gmm_mfma.hip), bf16 x 3 (gmm_bf16.hip), fp16 x 2 (gmm_f16.hip), named
 // by their HTKAMD_SCORE_* bit.  Each has one builder, on the device; a FULLC model has none of them.
 static const struct DerivedTable { int path; size_t tab; int (*build)(htkamd_model *, void *); const char *refusal; } DERIVED[] = {
-   {HTKAMD_SCORE_MFMA, OF(d_mfmaTab), htkamd_model_refresh_mfma_device, "score_mfma: vector size %d not supported by the MFMA path (up to 40)"},
-   {HTKAMD_SCORE_BF16, OF(d_bf16Tab), htkamd_model_refresh_bf16_device, "score_bf16: vector size %d not supported by the bf16 matrix-core path (up to 45)"},
-   {HTKAMD_SCORE_F16, OF(d_f16Tab), htkamd_model_refresh_f16_device, "score_f16: vector size %d not supported by the fp16 matrix-core path (up to 45)"},
+   {HTKAMD_SCORE_MFMA, OF(d_mfmaTab), htkamd_model_refresh_mfma_device, "score_mfma: vector size %d not supported by the MFMA path (up to 40; HTKAMD_SCORE_BF16, --score bf16, takes up to 120)"},
+   {HTKAMD_SCORE_BF16, OF(d_bf16Tab), htkamd_model_refresh_bf16_device, "score_bf16: vector size %d not supported by the bf16 matrix-core path (up to 120)"},
+   {HTKAMD_SCORE_F16, OF(d_f16Tab), htkamd_model_refresh_f16_device, "score_f16: vector size %d not supported by the fp16 matrix-core path (up to 45; HTKAMD_SCORE_BF16, --score bf16, takes up to 120)"},
 };
 // the paths whose tables follow every device update once they have scored; the fp32 table is always rebuilt on its next use
 static const int FOLLOWING_PATHS = HTKAMD_SCORE_BF16 | HTKAMD_SCORE_F16, ALL_PATHS = HTKAMD_SCORE_MFMA | FOLLOWING_PATHS;
@@ -244,7 +245,7 @@ int htkamd_model_table_current(const htkamd_model *cm, int path, void *stream)
 static int derived_tables_alloc(htkamd_model *m)
 {
    const int D = m->D;
-   if (D > 48 || m->d_stateTileOff) return HTKAMD_OK;    // D > 48: no matrix-core kernel, the exact path serves such sets
+   if (D > 120 || m->d_stateTileOff) return HTKAMD_OK;   // D > 120: no matrix-core kernel, the exact path serves such sets
    // fp32 path: K steps of 4 = 2 dimensions each; kernels exist for 7, 13 and 20 steps, smaller sizes are zero-padded up to the next
    const int need = (D + 1) / 2;
    m->mfmaNS = need <= 7 ? 7 : (need <= 13 ? 13 : 20);
@@ -262,6 +263,9 @@ static int derived_tables_alloc(htkamd_model *m)
       m->bf16Dense = m->f16Wide && D >= 31 && D <= 39;
       if ((rc = UPLOAD(m, d_bf16Tab)) || (rc = UPLOAD(m, d_f16Tab)) || (rc = UPLOAD(m, d_f16Ctl))) return rc;
       HIPCHECK(hipMemset(m->d_f16Ctl, 0, BYTES(m, d_f16Ctl)));
+   } else if (m->bf16NC <= 8) {                       // D = 46 .. 120: the bf16 path alone (gmm_bf16x.hip, 16 x 16 tiles whatever the states' sizes)
+      m->f16Wide = m->bf16Dense = 0;
+      if ((rc = UPLOAD(m, d_bf16Tab))) return rc;
    }
    return D > 40 ? HTKAMD_OK : UPLOAD(m, d_mfmaTab);     // (the fp32 kernels go up to 20 K steps)
 }

@@ -489,8 +489,9 @@ int htkamd_outp_block(htkamd_model *m, const float *dX, int T, const int *dState
  * inside the 1e-4 bar of the HERest path.  Chains that need the general kernels (models of > 5 states) ignore the bit. */
 #define HTKAMD_SCORE_FASTLADD 2
 /* The same expanded form on the BF16 matrix pipe, both operands split exactly into three bf16 pieces and the six piece products that
- * matter at fp32 accuracy summed in fp32 (gmm_bf16.hip): the tolerance class of HTKAMD_SCORE_MFMA at ~2.5x its speed (vector sizes up
- * to 48; HTKAMD_EMODEL beyond).  Takes precedence over HTKAMD_SCORE_MFMA when both bits are set. */
+ * matter at fp32 accuracy summed in fp32 (gmm_bf16.hip): the tolerance class of HTKAMD_SCORE_MFMA at ~2.5x its speed.  Vector sizes up
+ * to 120 (46 .. 120: gmm_bf16x.hip, the same arithmetic with the table streamed chunk by chunk); a larger one gets HTKAMD_EMODEL and is
+ * scored by HTKAMD_SCORE_EXACT.  Takes precedence over HTKAMD_SCORE_MFMA when both bits are set. */
 #define HTKAMD_SCORE_BF16  4
 /* Exact arithmetic with SOutP's rounding (HModel.c:5538-5552: the mixture log-sum kept in double, one rounding to float at the end)
  * instead of ShStrP's / cSOutP's float after every component: what OutP / POutP / SOutP return to a direct caller (HRest, HInit).
