@@ -740,7 +740,7 @@ static int fb_reserve_lr(htkamd_fb *fb, const htkamd_fb_config *cfg, FbArgs &fa,
    fb->mixStateLast = false;
    fa.fastMath = fastLadd ? 1 : 0;
    // mixture statistics bucketed by tied state (k_mixstate): the default list mode, one stream, the sparse statistics kernel counting
-   if (fb->recCapForce == 0 && !fa.hitSlots && m->maxM <= 16 && (m->D == 39 || m->D == 26 || m->D == 13) &&
+   if (fb->recCapForce == 0 && htkamd_mixstate_serves(fa) &&
        (cfg->uFlags & (HTKAMD_UPMEANS | HTKAMD_UPVARS | HTKAMD_UPMIXES))) {
       // room per state: eight times an even share of 2 pairs per frame, a power of two in [64, 65536], the lot within 1 GB
       size_t cap = 64;
@@ -1005,7 +1005,7 @@ extern "C" int htkamd_fb_kernel_times5(htkamd_fb *fb, double out[5])
 
 // out[0]: (frame, state) pairs the MINFORPROB prune let through in the last pass, out[1]: (frame, state, component) triples whose
 // statistics were accumulated -- the units of the mixture-statistics kernel's roofline (2 D FMAs and 624 bytes of
-// accumulator traffic per triple at D = 39).  Counted by k_mixstate; -1 where the pass ran on the list kernels alone.
+// accumulator traffic per triple at D = 39).  Counted by k_mixstate / k_mixstate_x; -1 where the pass ran on the list kernels alone.
 extern "C" int htkamd_fb_mix_counts(htkamd_fb *fb, long long out[2])
 {
    if (!fb || !out) { htkamd_set_error("fb_mix_counts: NULL"); return HTKAMD_EINVAL; }

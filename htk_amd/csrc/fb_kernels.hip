@@ -782,14 +782,6 @@ __global__ __launch_bounds__(256, 4) void k_mixstats(FbArgs a)
    if (recBase >= 0 && recUsed + lane < 64) a.rec[recBase + recUsed + lane].g = -1;
 }
 
-// a wave-uniform double held in scalar registers (the compiler keeps a converted kernel argument in a vector pair otherwise)
-__device__ __forceinline__ double uniform_f64(double v)
-{
-   const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
-   const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)b), hi = __builtin_amdgcn_readfirstlane((unsigned int)(b >> 32));
-   return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
-}
-
 // k_mixhits: the pairs come as LISTS (fb_lr_lean.inc: every wavefront of k_stats_sp owns a region of the list -- room for all its (frame,
 // state) pairs, so nothing can overflow and no cursor is shared -- and leaves the number of 16-byte records it wrote in hitCtl):
 // ~20 MB instead of the 0.5 GB seed array written and read back at the bench workload
@@ -1197,7 +1189,10 @@ __global__ __launch_bounds__(64, MS_EU) void k_mixstate(FbArgs a)
 }
 
 // the pass's surviving pairs by tied state (the buckets k_stats_sp filled): a wavefront per state
-bool htkamd_mixstate_applies(const FbArgs &a) { return a.stCnt && a.stBucket && !a.hitSlots && a.maxM <= 16 && (a.D == 39 || a.D == 26 || a.D == 13); }
+// (the gate, stated once: one stream, not tied-mixture, a vector of at most two wavefronts of dimensions -- fb.hip asks _serves before it
+//  makes the buckets, everyone else _applies)
+bool htkamd_mixstate_serves(const FbArgs &a) { return !a.hitSlots && a.D >= 1 && a.D <= 128; }
+bool htkamd_mixstate_applies(const FbArgs &a) { return a.stCnt && a.stBucket && htkamd_mixstate_serves(a); }
 int htkamd_launch_mixstate_range(const FbArgs &a_in, int st0, int st1, hipStream_t s)
 {
    if (st0 < 0 || st1 > a_in.nTiedStates || st0 > st1) { htkamd_set_error("mixture statistics: state range [%d, %d) outside the set's %d", st0, st1, a_in.nTiedStates); return HTKAMD_EINVAL; }
@@ -1213,6 +1208,8 @@ int htkamd_launch_mixstate_range(const FbArgs &a_in, int st0, int st1, hipStream
       else if (mode == 2) hipLaunchKernelGGL((k_mixstate<DT_, 2>), dim3(S, MS_PARTS), dim3(64), 0, s, a); \
       else hipLaunchKernelGGL((k_mixstate<DT_, 0>), dim3(S, MS_PARTS), dim3(64), 0, s, a); \
    } while (0)
+   // k_mixstate for the sizes it is written for; any other vector size or more than 16 components per state: k_mixstate_x (fb_mixwide.hip)
+   if (a.maxM > 16 || !(a.D == 39 || a.D == 26 || a.D == 13)) return htkamd_launch_mixstate_x(a, S, s);
    if (a.D == 39) MS_LAUNCH(39); else if (a.D == 26) MS_LAUNCH(26); else MS_LAUNCH(13);
 #undef MS_LAUNCH
    HIPCHECK(hipGetLastError());

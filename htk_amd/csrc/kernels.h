@@ -211,7 +211,7 @@ struct FbArgs {
    int nHitRegions, hitRegionCap;
    LaneRec *laneRec;                 // left-to-right path: [slot0 + lane], written by the beta kernels
    const int *qBeamNP;               // left-to-right path: the beta beams of the un-pruned pass (host: SetBeamTaper alone decides them), lo | hi << 16 per frame
-   // mixture statistics bucketed by tied state (k_mixstate; sets of one stream with <= 16 components per state): k_stats_sp drops a surviving
+   // mixture statistics bucketed by tied state (k_mixstate, k_mixstate_x; sets of one stream with D <= 128): k_stats_sp drops a surviving
    // pair into its state's bucket (stCnt[st] counts, stBucket[st * stCap ...]); what a bucket has no room for goes to the list of k_mixhits
    int stBase;                                                   // k_mixstate: first tied state of the launch (htkamd_fb_execute_mix takes the states in ranges)
    int *stCnt; int nTiedStates; HitS *stBucket; int stCap;      // stCnt[nTiedStates] = pairs turned away by a full bucket (0: the list kernels have nothing to do)
@@ -219,13 +219,23 @@ struct FbArgs {
    double *sink;                     // 64 bytes nobody reads: where the lanes outside a beam "store" (one cache line instead of a branch around the store)
 };
 
+// a wave-uniform double held in scalar registers (the compiler keeps a converted kernel argument in a vector pair otherwise)
+__device__ __forceinline__ double uniform_f64(double v)
+{
+   const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+   const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)b), hi = __builtin_amdgcn_readfirstlane((unsigned int)(b >> 32));
+   return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
 int htkamd_launch_beta(const FbArgs &a, int blockDim, size_t lds, hipStream_t s);
 int htkamd_launch_alpha(const FbArgs &a, int blockDim, size_t lds, hipStream_t s);
 // deferState: where the state-bucketed kernel applies, only what its buckets turned away is taken now (by the list kernel, direct atomics);
 // the states themselves wait for htkamd_launch_mixstate_range (htkamd_fb_execute_mix)
 int htkamd_launch_mixstats(const FbArgs &a, hipStream_t s, bool dense, bool listed, bool deferState = false);
-bool htkamd_mixstate_applies(const FbArgs &a);
+bool htkamd_mixstate_serves(const FbArgs &a);       // the set and the path allow state buckets (asked before they are made)
+bool htkamd_mixstate_applies(const FbArgs &a);      // ... and the pass has them
 int htkamd_launch_mixstate_range(const FbArgs &a, int st0, int st1, hipStream_t s);
+int htkamd_launch_mixstate_x(const FbArgs &a, int S, hipStream_t s);      // fb_mixwide.hip: tied states [a.stBase, a.stBase + S), any D <= 128 and any mixture size
 // several streams: outp = sum over streams of outpU; UpMixParms per stream from the dense seed array
 int htkamd_launch_combine_streams(const FbArgs &a, hipStream_t s);
 int htkamd_launch_mixstats_ms(const FbArgs &a, hipStream_t s);
