@@ -2381,6 +2381,10 @@ class VqClusters(C.Structure):
                 ("size", C.c_void_p), ("centre", C.c_void_p), ("cov", C.c_void_p), ("aveCost", C.c_void_p), ("cmap", C.c_void_p)]
 
 
+class Seg(C.Structure):
+    _fields_ = [("first", C.c_longlong), ("count", C.c_int), ("cls", C.c_int)]
+
+
 STRUCTS = {"htkamd_model_desc": ModelDesc, "htkamd_accs_layout": AccsLayout, "htkamd_fb_config": FbConfig, "htkamd_update_config": UpdateConfig,
            "htkamd_update_stats": UpdateStats, "htkamd_batch_desc": BatchDesc, "htkamd_mfcc_config": MfccConfig, "htkamd_frontend_config": FrontEndConfig,
            "htkamd_warp": Warp, "htkamd_parm_quals": ParmQuals, "htkamd_tree_question": TreeQuestion, "htkamd_tree_spec": TreeSpec,
@@ -2389,7 +2393,7 @@ STRUCTS = {"htkamd_model_desc": ModelDesc, "htkamd_accs_layout": AccsLayout, "ht
            "htkamd_lattice_align": LatticeAlign, "htkamd_lattice": Lattice, "htkamd_decode_out": DecodeOut, "htkamd_results_config": ResultsConfig,
            "htkamd_results_report": ResultsReport, "htkamd_lat_scales": LatScales, "htkamd_latset_view": LatSetView, "htkamd_latset_best_out": LatBestOut,
            "htkamd_latset_fb_out": LatFbOut, "htkamd_mllr_config": MllrConfig,
-           "htkamd_vq_config": VqConfig, "htkamd_vq_clusters": VqClusters}
+           "htkamd_vq_config": VqConfig, "htkamd_vq_clusters": VqClusters, "htkamd_seg": Seg}
 
 
 # ---- label statistics and bigram models (HLStats), word networks (HBuild) ----
@@ -2665,3 +2669,41 @@ def parm_write_discrete(path: str, codes: np.ndarray, sampPeriod: int, withCrc: 
     c = np.ascontiguousarray(codes, np.int16)
     c = c.reshape(len(c), -1)
     check(lib().htkamd_parm_write_discrete(path.encode(), _p(c), c.shape[0], c.shape[1], int(sampPeriod), int(withCrc)), "parm_write_discrete")
+
+
+# ---- full-covariance statistics of a frame table (csrc/compv_full.hip, host/compv_full.c) ----
+def compv_full_chunk() -> int:
+    """Frames of one workgroup's chunk: the size at which the kernel's paths change."""
+    return lib().htkamd_compv_full_chunk()
+
+
+def compv_full(dX_ptr, nFrames: int, D: int, segs=None, nClass: int = 1, weights_ptr=None, stream=None, out=None):
+    """htkamd_compv_full over a device table [nFrames, D]: (count [K], sum [K, D], sq [K, D(D+1)/2]) in float64.  segs: rows of
+    (first frame, frames, class), None = the whole table as class 0; weights_ptr: a device float per frame, None = 1.  `out`: the three
+    arrays to fill instead of new ones."""
+    K = max(int(nClass), 1)
+    tri = max(int(D), 0) * (max(int(D), 0) + 1) // 2
+    count, sum_, sq = out if out is not None else (np.zeros(K), np.zeros((K, max(int(D), 1))), np.zeros((K, max(tri, 1))))
+    sg, n = None, 0
+    if segs is not None:
+        rows = np.asarray(segs, np.int64).reshape(-1, 3)
+        n = len(rows)
+        sg = (Seg * max(n, 1))(*[Seg(int(a), int(b), int(c)) for a, b, c in rows])
+    check(lib().htkamd_compv_full(_stream(dX_ptr), int(nFrames), int(D), _stream(weights_ptr), sg, n, int(nClass), _p(count), _p(sum_), _p(sq),
+                                  _stream(stream)), "compv_full")
+    return count, sum_, sq
+
+
+def compv_full_kernel_ms() -> float:
+    return lib().htkamd_compv_full_last_kernel_ms()
+
+
+def compv_full_cov(count: float, sum_, sq, minVar: float = 0.0, want_inverse: bool = True):
+    """htkamd_compv_full_cov for one class: (mean [D], cov, invCov) as float32, the triangles packed row-major as an MMF holds them;
+    invCov is None unless wanted."""
+    s, q = np.ascontiguousarray(sum_, np.float64).reshape(-1), np.ascontiguousarray(sq, np.float64).reshape(-1)
+    D = len(s)
+    assert len(q) == D * (D + 1) // 2, "compv_full_cov: sq is not the triangle of sum's size"
+    mean, cov, inv = np.zeros(D, np.float32), np.zeros(len(q), np.float32), np.zeros(len(q), np.float32) if want_inverse else None
+    check(lib().htkamd_compv_full_cov(D, float(count), _p(s), _p(q), float(minVar), _p(mean), _p(cov), _p(inv)), "compv_full_cov")
+    return mean, cov, inv

@@ -1740,6 +1740,33 @@ double htkamd_vq_code_last_kernel_ms(const htkamd_vqtab *t);
 int  htkamd_parm_write_discrete(const char *path, const short *codes, int nFrames, int nStreams, int sampPeriod, int withCrc);
 int  htkamd_hquant_check_switch(const char *sw);      /* 0 for a switch of HQuant that is served ("-d"), else HTKAMD_EINVAL and the refusal by name */
 
+/* ------------------------------------------------------------------------------------------
+ * Full-covariance statistics of a frame table (csrc/compv_full.hip): what HCompV accumulates for a <FULLC> prototype
+ * (AccVar HCompV.c:392-411), with a weight per frame and classes of label segments, summed in fp64 on the matrix pipe.
+ *   htkamd_compv_full     : dX [nFrames x D] on the device, rows packed; dW [nFrames] on the device or NULL (every weight 1); segs
+ *                           (host) the segments (first frame, frames, class), NULL = the whole table as class 0.  Segments may overlap,
+ *                           leave frames out, be empty and name a class several times.  Per class k (host, fp64): count[k] = sum w,
+ *                           sum[k][D] = sum w x, sq[k][D(D+1)/2] = the lower triangle of sum w x x^T packed row-major ((x, y), y <= x,
+ *                           at x(x+1)/2 + y, as the reference's TriMat); a class without frames gets zeros.  Each product is
+ *                           (w x_x, rounded once in fp64) * x_y.  The bytes are the same run to run.  HTKAMD_EINVAL and the reason,
+ *                           before anything is launched and with the outputs untouched: D above htkamd_compv_full_max_dim() (128), a
+ *                           segment outside 0 .. nFrames, a class outside 0 .. nClass-1.  Synchronises `stream`.
+ *   htkamd_compv_full_cov : CalcCovs (HCompV.c:261-297) of one class's statistics on the host, in double: mean = sum / n, cov[x][y] =
+ *                           sq[x][y] / n - mean[x] mean[y] with the diagonal floored at minVar (:281-283), invCov = its inverse by a
+ *                           Choleski factorisation (CovInvert HMath.c:567), all triangles packed as above; cov or invCov may be NULL.
+ *                           HTKAMD_EINVAL when n < 2 (HCompV's error 2021), HTKAMD_EMODEL when the floored matrix is not positive
+ *                           definite (5220); nothing is written then.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct { long long first; int count; int cls; } htkamd_seg;
+int  htkamd_compv_full_chunk(void);                   /* frames of one workgroup's chunk: where the kernel's paths change */
+int  htkamd_compv_full_max_dim(void);
+int  htkamd_compv_full(const float *dX, long long nFrames, int D, const float *dW /*NULL: weights 1*/,
+                       const htkamd_seg *segs, int nSeg, int nClass,
+                       double *count /*[K]*/, double *sum /*[K x D]*/, double *sq /*[K x D(D+1)/2]*/, void *stream);
+double htkamd_compv_full_last_kernel_ms(void);        /* the two kernels of the last call, by events */
+int  htkamd_compv_full_cov(int D, double count, const double *sum, const double *sq, float minVar,
+                           float *mean, float *cov /*tri*/, float *invCov /*tri*/);
+
 #ifdef __cplusplus
 }
 #endif
